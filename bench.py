@@ -13,6 +13,8 @@ corpus, inputs already resident in HBM.
   python bench.py --gpus N ...            (no launcher: starts its own N rank processes, see self_launch)
   python bench.py --gpus N --config 3     (BASELINE.json configs[3]: 12.5M x 1536 f16 rows PER GPU, weak scaling)
   python bench.py --gpus N --multi        (the same shards through svs_multi_search: one process, no RCCL)
+  python bench.py --full                  (also the secondary figures and checks, see below)
+  python bench.py --dump-outputs DIR      (the last timed step's results as DIR/scores.npy, DIR/rows.npy)
 
 N > 1: the 1M-row corpus is row-sharded; every rank scores its
 shard for every query, local top-k lists are exchanged with one RCCL all-gather
@@ -23,6 +25,11 @@ Prints ONE JSON line on rank 0 (see the driver contract in the task notes):
 value = whole-job queries/s; roofline = algorithmic corpus bytes per launch of
 the dominant kernel / its HIP-event-measured duration; cpu_baseline = the numpy
 restatement of the reference path (oracle/) timed on this host's cores.
+
+A plain run sets up, warms up, times the --steps steps and prints the line: `value`, `ms_per_step`, `stage_ms` and
+`roofline` come from the timed steps alone.  `--full` adds what takes runs of its own (N = 1, configs[1] only): the
+p50 latency at the C ABI, the batched and concurrent-caller figures, configs[2..4], the KB figures, the CPU baseline
+and the parity spot check against the oracle.  Without it those fields are null, empty or absent.
 """
 import argparse
 import glob
@@ -405,6 +412,15 @@ def single_query_config(torch, idx, name, n, d, dtype, k, seed, iters=60):
                     "python bench.py --gpus N --config 3)" % len(lats)}
 
 
+def dump_outputs(out_dir, scores, rows):
+    """`--dump-outputs`: what the caller of the timed path receives for the LAST timed step -- the top-k scores
+    (float32) and their global row indices (as float64: exact below 2**53) -- so that two builds can be compared
+    output for output (the inputs are seeded: same arguments, same corpus and queries)."""
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "scores.npy"), np.asarray(scores, dtype=np.float32))
+    np.save(os.path.join(out_dir, "rows.npy"), np.asarray(rows, dtype=np.int64).astype(np.float64))
+
+
 def run_multi(args):
     """`--multi`: the shards of the N-rank run inside ONE process through the multi-device entry -- config 1: the C ABI's
     svs_multi_create / svs_multi_search (NativeMultiIndex: host matrix in, one worker thread per shard inside the library,
@@ -448,6 +464,8 @@ def run_multi(args):
     torch.cuda.synchronize()
     elapsed = time.perf_counter() - t0
     assert len(res) == min(k, n_total)
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, [s for s, _ in res], [r for _, r in res])
     esz = {"f32": 4, "f16": 2, "fp8": 1}[args.dtype]
     out = {"metric": "queries/sec, cosine top-%d over %dx%d %s, single query" % (k, n_total, d, {"f32": "fp32", "f16": "fp16", "fp8": "fp8"}[args.dtype]),
            "value": K / elapsed, "unit": "queries/s", "n_gpus": G, "steps": K, "warmup": W, "ms_per_step": elapsed / K * 1e3,
@@ -511,7 +529,14 @@ def main():
     ap.add_argument("--inflight", type=int, default=1,
                     help="searches kept in flight on separate HIP streams (2 lets the top-k "
                          "stage of query i overlap the score stage of query i+1)")
+    ap.add_argument("--full", action="store_true",
+                    help="also the secondary figures and checks (N = 1, configs[1]): p50 latency, batched and concurrent "
+                         "callers, configs[2..4], KB figures, CPU baseline and parity spot check; a plain run times the steps only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the results of the last timed step as DIR/scores.npy (float32) and DIR/rows.npy (float64)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     if args.config == 3:
         args.rows = 12_500_000 if args.rows == 1_000_000 else args.rows
         args.dtype = args.dtype or "f16"
@@ -567,7 +592,7 @@ def main():
 
     # ---- synthetic corpus straight into HBM, then into the index's own layout
     main_cfg = args.config == 1 and args.dtype == "f32"           # the metric's config: carries the secondary figures
-    keep_rows_for_cpu = rank == 0 and world == 1 and not args.no_cpu_baseline and main_cfg
+    keep_rows_for_cpu = args.full and rank == 0 and world == 1 and not args.no_cpu_baseline and main_cfg
     rows = None
     if keep_rows_for_cpu or (hi - lo) * d * 4 <= (8 << 30):
         rows = gen_rows(torch, dev, args.seed, lo, hi, d)
@@ -640,6 +665,8 @@ def main():
         t = torch.tensor([elapsed], device=dev, dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, *results[-1])
 
     # ---- rehearsal check (SVS_BENCH_VERIFY=1, N > 1): the merged result of the sharded run must
     # be IDENTICAL (rows and score bits) to one index over the whole corpus -- the kernels'
@@ -661,7 +688,7 @@ def main():
     # ---- p50 latency at the C-ABI boundary (host buffers in, results out, synced): its own
     # latency_iters (>= 200) distinct queries, whatever --steps / --warmup were
     lat_ms, lat_n = None, 0
-    if world == 1 and n_local * d:
+    if args.full and world == 1 and n_local * d:
         gl = torch.Generator(device=dev)
         gl.manual_seed(args.seed + 555)
         ql = torch.randn((max(args.latency_iters, 200) + 5, d), device=dev, dtype=torch.float32, generator=gl)
@@ -687,7 +714,7 @@ def main():
     # ---- secondary figure (N = 1 only; not `value`): batched search, 16 queries
     # share one pass over the corpus (north_star: >= 10,000 queries/s at 1 GPU)
     batched = None
-    if world == 1 and args.batch and main_cfg:
+    if args.full and world == 1 and args.batch and main_cfg:
         batched = []
         for B in [int(x) for x in str(args.batch).split(",") if int(x) > 1]:
             gb = torch.Generator(device=dev)
@@ -717,7 +744,7 @@ def main():
     # svs_index_set_coalesce.  Python threads, so the GIL caps it (~12 k queries/s; 64 C threads reach 24.6 k:
     # tools/coalesce_bench.c)
     concurrent = None
-    if world == 1 and args.concurrent > 1 and n_local * d and main_cfg:
+    if args.full and world == 1 and args.concurrent > 1 and n_local * d and main_cfg:
         import threading
         gc = torch.Generator(device=dev)
         gc.manual_seed(args.seed + 4242)
@@ -779,7 +806,7 @@ def main():
     # ---- secondary figures (N = 1 only; not `value`): BASELINE.json configs[2] and configs[4], the
     # MFMA-bound batch configurations, each on its own index (synthetic, same recipe as the headline corpus)
     configs = []
-    want = [c.strip() for c in str(args.configs).split(",") if c.strip()] if (world == 1 and main_cfg) else []
+    want = [c.strip() for c in str(args.configs).split(",") if c.strip()] if (args.full and world == 1 and main_cfg) else []
     if "2" in want and n_total == 1_000_000 and d == 1536:
         src = rows if keep_rows_for_cpu else gen_rows(torch, dev, args.seed, 0, n_total, d)
         i2 = DeviceIndex.from_device_pointer(src.data_ptr(), n_total, d, device=dev_index, dtype="f16")
@@ -814,7 +841,7 @@ def main():
     # (in a child process: its small-corpus launches of the single-query kernels would otherwise sit in the
     #  per-kernel statistics rocprofv3 keeps for THIS process, next to the 1M-row launches the roofline is about)
     kb_out = {}
-    if world == 1 and args.kb and main_cfg:
+    if args.full and world == 1 and args.kb and main_cfg:
         import subprocess
         try:
             r = subprocess.run([sys.executable, os.path.abspath(__file__), "--kb-only", "--seed", str(args.seed), "--k", str(k)],
@@ -877,7 +904,7 @@ def main():
         }
 
     # ---- CPU baseline: the numpy restatement of the reference path, this host's cores
-    if rank == 0 and world == 1 and not args.no_cpu_baseline and main_cfg:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline and main_cfg:
         from oracle import svs_oracle as oracle  # cpu_baseline leg only (checker + baseline)
         m_host = rows.cpu().numpy()
         del rows

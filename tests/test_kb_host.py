@@ -5,8 +5,6 @@ reference (tests/golden/kb_cases.json).  The arithmetic is a test double
 tests/test_kb_gpu.py."""
 import asyncio
 import json
-import os
-import sys
 
 import numpy as np
 import pytest
@@ -221,28 +219,78 @@ def test_invalidate_while_search_in_flight():
         cache.search(m[0], 1)
 
 
-@pytest.mark.skipif(not os.path.isdir("/root/reference/src/svs"), reason="reference not present (GPU box)")
-def test_attach_to_the_real_reference_kb(tmp_path):
-    """attach(): the reference's OWN retrieve() code runs unchanged; its np.dot /
-    np.argpartition calls are served through __array_function__."""
-    sys.path.insert(0, "/root/reference/src")
-    try:
-        import svs
-        cases = load_cases()
-        kb = svs.KB(str(tmp_path / "ref.sqlite"), embedding_func_from(cases))
-        svs_amd.attach(kb, index_factory=OracleIndex)
-        assert isinstance(kb.embeddings_matrix, mx.DeviceEmbeddingsMatrix)
-        replay_sync(kb, cases)
-        # pairwise path still works through the host copy
-        with kb.bulk_add_docs() as add_doc:
-            add_doc("first doc"); add_doc("second doc"); add_doc("third doc")
-        assert len(kb.document_top_pairwise_scores(2)) == 2
-        kb.close()
-        assert OracleIndex.live == 0
-    finally:
-        sys.path.remove("/root/reference/src")
-        for k in [k for k in sys.modules if k == "svs" or k.startswith("svs.")]:
-            del sys.modules[k]
+class _Db:
+    """``with db as q: q.build_embeddings_matrix()`` over a fixed matrix."""
+
+    def __init__(self, matrix, ids):
+        self.matrix, self.ids = matrix, ids
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        return False
+
+    def build_embeddings_matrix(self):
+        return self.matrix, self.ids
+
+
+class _HostCache:
+    """The host matrix cache of a KB that knows nothing of svs_amd: get_sync(db) -> (matrix, ids)."""
+
+    def __init__(self):
+        self.m = None
+
+    def get_sync(self, db):
+        if self.m is None:
+            with db as q:
+                self.m = q.build_embeddings_matrix()
+        return self.m
+
+    def invalidate(self):
+        self.m = None
+
+
+class _PlainKB:
+    """retrieve() and pairwise scores written in plain numpy over whatever the cache hands out: np.dot for the
+    scores, np.argpartition and its top-k tail, float() of each score, a sort; np.dot(M, M.T) for the pairs."""
+
+    def __init__(self, matrix, ids):
+        self.db = _Db(matrix, ids)
+        self.embeddings_matrix = _HostCache()
+
+    def retrieve(self, query_vec, n):
+        m, ids = self.embeddings_matrix.get_sync(self.db)
+        scores = np.dot(m, query_vec)
+        top = np.argpartition(scores, -n)[-n:]
+        return sorted(((float(scores[i]), int(ids[i])) for i in top), reverse=True)
+
+    def pair_scores(self):
+        m, _ = self.embeddings_matrix.get_sync(self.db)
+        return np.dot(m, m.T)
+
+
+def test_attach_serves_the_numpy_calls_of_an_unchanged_kb():
+    """attach(): a KB's OWN retrieve() code runs unchanged; its np.dot / np.argpartition calls are served through
+    __array_function__, and anything else (np.dot(M, M.T)) through the host copy.  Same answers as before attach()."""
+    rng = np.random.default_rng(5)
+    m = rng.standard_normal((300, 24)).astype(np.float32)
+    m /= np.linalg.norm(m, axis=1, keepdims=True)
+    ids = np.arange(1000, 1300, dtype=np.int64)
+    qs = rng.standard_normal((4, 24)).astype(np.float32)
+    kb = _PlainKB(m, ids)
+    want = [kb.retrieve(q, n) for q, n in zip(qs, (1, 7, 50, 300))]
+    want_pairs = kb.pair_scores()
+    svs_amd.attach(kb, index_factory=OracleIndex)
+    assert isinstance(kb.embeddings_matrix, mx.DeviceEmbeddingsMatrix) and kb.embeddings_matrix.index is None
+    got = [kb.retrieve(q, n) for q, n in zip(qs, (1, 7, 50, 300))]
+    assert isinstance(kb.embeddings_matrix.get_sync(kb.db)[0], mx.DeviceMatrixView)
+    for g, w in zip(got, want):
+        assert [r for _, r in g] == [r for _, r in w]
+        assert max(abs(a - b) for (a, _), (b, _) in zip(g, w)) <= 1e-6
+    assert np.array_equal(kb.pair_scores(), want_pairs)
+    kb.embeddings_matrix.invalidate()
+    assert OracleIndex.live == 0
 
 
 def test_embedding_blocks_equal_the_matrix_build(tmp_path):

@@ -106,7 +106,7 @@ def test_bench_rccl_exchange_path_with_the_one_rank_a_box_has(gpu):
     all-gather + copy home on the exchange stream, chunk-by-chunk host merge on 64-bit keys) with one rank -- 29 steps,
     so that the warm-up's partly filled chunk is re-sent and the last chunk is partial -- and every timed result checked
     against the numpy oracle by bench.py's own spot check (the CPU baseline leg, 8 queries)."""
-    line = _bench_line(["--rows", "200000", "--steps", "29", "--warmup", "5", "--batch", "", "--concurrent", "0", "--configs", "",
+    line = _bench_line(["--rows", "200000", "--steps", "29", "--warmup", "5", "--full", "--batch", "", "--concurrent", "0", "--configs", "",
                         "--kb", "0", "--cpu-iters", "3"], {"SVS_BENCH_FORCE_DIST": "1"})
     assert line["n_gpus"] == 1 and line["steps"] == 29 and line["config"]["steps_per_exchange"] == 8
     assert line["config"]["searches_in_flight"] >= 2
