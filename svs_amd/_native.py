@@ -94,6 +94,7 @@ INTERNAL = {
     "svs_internal_coalesce_hold": (C.c_int32, [_P, C.c_int32]),
     "svs_internal_tune": (C.c_int32, [C.c_int32, C.c_int64]),
     "svs_internal_host_phases": (C.c_int32, [C.POINTER(C.c_double), C.c_int32]),
+    "svs_internal_last_launches": (C.c_int32, [C.POINTER(C.c_char_p), C.POINTER(C.c_int64), C.POINTER(C.c_int32), C.c_int32]),
 }
 
 _lib: Optional[C.CDLL] = None
@@ -199,3 +200,12 @@ def device_memory(device: int = 0):
     f, t = C.c_int64(0), C.c_int64(0)
     check(load().svs_device_memory(int(device), C.byref(f), C.byref(t)))
     return f.value, t.value
+
+
+def last_launches():
+    """[(kernel, rows, queries)]: the score kernels this thread's last search / scores call enqueued, in order
+    (svs_internal_last_launches; tests)."""
+    cap = 32
+    names, rows, nq = (C.c_char_p * cap)(), (C.c_int64 * cap)(), (C.c_int32 * cap)()
+    total = int(load().svs_internal_last_launches(names, rows, nq, cap))
+    return [(names[i].decode(), int(rows[i]), int(nq[i])) for i in range(min(total, cap))]

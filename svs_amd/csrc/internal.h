@@ -22,6 +22,14 @@ int32_t svs_internal_tune(int32_t what, int64_t value);
  * drained, [4] the results were in the caller's buffers; [5] = the number of the call's queries whose fused candidate list
  * overflowed and that were re-run through the materialised path (a count, not a time). */
 int32_t svs_internal_host_phases(double* out, int32_t n);
+/* The score kernels the calling thread's last svs_index_search, svs_index_search_device or svs_index_scores_n call
+ * enqueued, in order (each of those calls starts a new record): kernels[i] is the kernel with its template arguments as
+ * c++filt prints it ("gemm_phased_kernel<true, 2, 20, 256>"; a static string), or "gemv" for the single-query kernels
+ * (one entry for a whole per-query loop); rows[i] its row count (a fused search's threshold pass covers fewer rows than
+ * the corpus); nq[i] its query count.  A fused search whose candidate lists overflowed lists the materialised re-run's
+ * launches after its own.  Up to cap entries (and at most 32) are written; returns the number of launches recorded.
+ * Coalesced single-query passes and svs_multi_* launch from other threads: they are not in the caller's record. */
+int32_t svs_internal_last_launches(const char** kernels, int64_t* rows, int32_t* nq, int32_t cap);
 /* multi.hip -> svs_amd.hip: carries a worker thread's error message over to the caller's thread */
 int32_t svs_internal_set_error(int32_t code, const char* msg);
 #ifdef __cplusplus

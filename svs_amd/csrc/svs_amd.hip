@@ -19,6 +19,7 @@
 #include <new>
 #include <string>
 #include <thread>
+#include <type_traits>
 #include <vector>
 
 #include "fp8.h"
@@ -60,6 +61,53 @@ std::atomic<int64_t> g_tune_upload{0};        // host batches: 0 = f16 batches a
                                               // (no DMA, no f32 copy in HBM); 1 = round 3's staging + DMA for every dtype
 std::atomic<int64_t> g_tune_spread{1};        // fused path: 1 = thresholds from a sample spread over the whole corpus (prefix_image), 0 = from its first rows (rounds 1-3)
 thread_local double g_host_phase[6];          // svs_internal_host_phases: seconds since the call began (last svs_index_search on this thread)
+
+// svs_internal_last_launches: the score kernels the calling thread's last search / scores call enqueued, in order.  Fixed
+// thread-local slots and names that are compile-time constants: recording is a few stores, no allocation, no lock.
+struct LaunchRec {
+  const char* kernel;
+  int64_t rows;
+  int32_t nq;
+};
+constexpr int LAUNCH_REC_CAP = 32;
+thread_local LaunchRec g_launch[LAUNCH_REC_CAP];
+thread_local int32_t g_nlaunch;                // launches since the reset (may exceed LAUNCH_REC_CAP: those are not kept)
+
+inline void launch_reset() { g_nlaunch = 0; }
+inline void launch_record(const char* kernel, int64_t rows, int nq) {
+  if (g_nlaunch < LAUNCH_REC_CAP) g_launch[g_nlaunch] = LaunchRec{kernel, rows, (int32_t)nq};
+  ++g_nlaunch;
+}
+
+// "name<a, b, ...>": a kernel and its template arguments spelled as c++filt prints them (the build's resource report),
+// built at compile time
+struct KernelName {
+  char s[64] = {};
+};
+template <class... A>
+constexpr KernelName kernel_name(const char* base, A... args) {
+  KernelName k{};
+  int p = 0;
+  for (const char* c = base; *c; ++c) k.s[p++] = *c;
+  k.s[p++] = '<';
+  int i = 0;
+  auto put = [&](auto v) {
+    if (i++) { k.s[p++] = ','; k.s[p++] = ' '; }
+    if constexpr (std::is_same_v<decltype(v), bool>) {
+      for (const char* c = v ? "true" : "false"; *c; ++c) k.s[p++] = *c;
+    } else {
+      long long x = v;
+      if (x < 0) { k.s[p++] = '-'; x = -x; }
+      char dig[20] = {};
+      int nd = 0;
+      do { dig[nd++] = (char)('0' + x % 10); x /= 10; } while (x);
+      while (nd) k.s[p++] = dig[--nd];
+    }
+  };
+  (put(args), ...);
+  k.s[p++] = '>';
+  return k;
+}
 
 struct EvTriple {
   hipEvent_t e0, e1, e2;
@@ -605,9 +653,16 @@ int stage_queries_f32(const svs_index* idx, Ctx* c, const float* q_dev, int nq, 
   return SVS_OK;
 }
 
+template <bool FUSE, int EB>
+constexpr KernelName kQ16rName = kernel_name("gemm_q16r_kernel", FUSE, EB, G4_RG, G4_PF);
+template <bool FUSE>
+constexpr KernelName kF32Q16Name = kernel_name("gemm_f32_q16_kernel", false, 2, GEMM_PF, FUSE);
+
+// (name: the kernel as svs_internal_last_launches reports it)
 template <class K, class P>
-void launch_q16_kernel(K kernel, const svs_index* idx, const P* rows, const P* q16, int ld_units, size_t row_bytes, int nq_g,
+void launch_q16_kernel(K kernel, const char* name, const svs_index* idx, const P* rows, const P* q16, int ld_units, size_t row_bytes, int nq_g,
                        int64_t n_rows, float* scores, int64_t sstride, int rows_per_block, FuseLaunch fl, hipStream_t st) {
+  launch_record(name, n_rows, nq_g);
   const unsigned blocks = (unsigned)((n_rows + rows_per_block - 1) / rows_per_block);
   const size_t lds = row_bytes * 16 + (fl.state ? GEMM_FUSE_LDS : 0);   // 16 queries x row bytes
   hipLaunchKernelGGL(kernel, dim3(blocks), dim3(GEMM_WAVES * 64), lds, st,
@@ -636,14 +691,14 @@ int launch_scores_q16(const svs_index* idx, const void* q16, int nq_g, int64_t n
   const size_t row_bytes = (size_t)idx->ld * elem_bytes(idx);
   const int ld16 = (int)(row_bytes / 16);
   if (idx->dtype == SVS_DTYPE_F16) {
-    if (fl.state) launch_q16_kernel(gemm_q16r_kernel<true, 2>, idx, (const v4f*)fl.rows_of(idx), (const v4f*)q16, ld16, row_bytes, nq_g, n_rows, scores, sstride, rows_per_block, fl, st);
-    else launch_q16_kernel(gemm_q16r_kernel<false, 2>, idx, (const v4f*)fl.rows_of(idx), (const v4f*)q16, ld16, row_bytes, nq_g, n_rows, scores, sstride, rows_per_block, fl, st);
+    if (fl.state) launch_q16_kernel(gemm_q16r_kernel<true, 2>, kQ16rName<true, 2>.s, idx, (const v4f*)fl.rows_of(idx), (const v4f*)q16, ld16, row_bytes, nq_g, n_rows, scores, sstride, rows_per_block, fl, st);
+    else launch_q16_kernel(gemm_q16r_kernel<false, 2>, kQ16rName<false, 2>.s, idx, (const v4f*)fl.rows_of(idx), (const v4f*)q16, ld16, row_bytes, nq_g, n_rows, scores, sstride, rows_per_block, fl, st);
   } else if (variant == 3) {   // A/B: the 16x16x4 kernel (half-line loads)
-    if (fl.state) launch_q16_kernel(gemm_f32_q16_kernel<false, 2, GEMM_PF, true>, idx, (const float*)fl.rows_of(idx), (const float*)q16, idx->ld, row_bytes, nq_g, n_rows, scores, sstride, rows_per_block, fl, st);
-    else launch_q16_kernel(gemm_f32_q16_kernel<false, 2, GEMM_PF, false>, idx, (const float*)fl.rows_of(idx), (const float*)q16, idx->ld, row_bytes, nq_g, n_rows, scores, sstride, rows_per_block, fl, st);
+    if (fl.state) launch_q16_kernel(gemm_f32_q16_kernel<false, 2, GEMM_PF, true>, kF32Q16Name<true>.s, idx, (const float*)fl.rows_of(idx), (const float*)q16, idx->ld, row_bytes, nq_g, n_rows, scores, sstride, rows_per_block, fl, st);
+    else launch_q16_kernel(gemm_f32_q16_kernel<false, 2, GEMM_PF, false>, kF32Q16Name<false>.s, idx, (const float*)fl.rows_of(idx), (const float*)q16, idx->ld, row_bytes, nq_g, n_rows, scores, sstride, rows_per_block, fl, st);
   } else {
-    if (fl.state) launch_q16_kernel(gemm_q16r_kernel<true, 4>, idx, (const v4f*)fl.rows_of(idx), (const v4f*)q16, ld16, row_bytes, nq_g, n_rows, scores, sstride, rows_per_block, fl, st);
-    else launch_q16_kernel(gemm_q16r_kernel<false, 4>, idx, (const v4f*)fl.rows_of(idx), (const v4f*)q16, ld16, row_bytes, nq_g, n_rows, scores, sstride, rows_per_block, fl, st);
+    if (fl.state) launch_q16_kernel(gemm_q16r_kernel<true, 4>, kQ16rName<true, 4>.s, idx, (const v4f*)fl.rows_of(idx), (const v4f*)q16, ld16, row_bytes, nq_g, n_rows, scores, sstride, rows_per_block, fl, st);
+    else launch_q16_kernel(gemm_q16r_kernel<false, 4>, kQ16rName<false, 4>.s, idx, (const v4f*)fl.rows_of(idx), (const v4f*)q16, ld16, row_bytes, nq_g, n_rows, scores, sstride, rows_per_block, fl, st);
   }
   return SVS_OK;
 }
@@ -666,6 +721,8 @@ int launch_tiled_bn(const svs_index* idx, Ctx* c, int64_t n_rows, int nq, float*
     (void)hipFuncSetAttribute((const void*)gemm_tiled_kernel<BN, FUSE, EB, BM>, hipFuncAttributeMaxDynamicSharedMemorySize,
                               tg_lds_bytes(BM, BN));
   });
+  static constexpr KernelName name = kernel_name("gemm_tiled_kernel", BN, FUSE, EB, BM);
+  launch_record(name.s, n_rows, nq);
   const unsigned gx = (unsigned)((n_rows + BM - 1) / BM), gy = (unsigned)((nq + BN - 1) / BN);
   const uint8_t* Q = EB == 2 ? (const uint8_t*)c->qh : (EB == 1 ? (const uint8_t*)c->q8 : (const uint8_t*)c->q_f32);
   // pair mode: the row operand starts at global row fl.pairs.row_base (n_rows counts from there)
@@ -685,6 +742,8 @@ int launch_phased(const svs_index* idx, Ctx* c, int64_t n_rows, int nq, float* s
   std::call_once(once, [] {
     (void)hipFuncSetAttribute((const void*)gemm_phased_kernel<FUSE, EB, EXP, QT>, hipFuncAttributeMaxDynamicSharedMemorySize, PG_LDS_TOTAL);
   });
+  static constexpr KernelName name = kernel_name("gemm_phased_kernel", FUSE, EB, EXP, QT);
+  launch_record(name.s, n_rows, nq);
   const int gx = (int)((n_rows + PG_TILE - 1) / PG_TILE), gy = (nq + QT - 1) / QT;
   const int64_t total = (int64_t)gx * gy;
   const unsigned grid = (unsigned)std::min<int64_t>(total, idx->cu_count);   // one persistent workgroup per CU
@@ -864,6 +923,7 @@ int launch_scores_any(svs_index* idx, Ctx* c, const float* q_dev, int64_t n_rows
     if ((rc = launch_scores_tiled(idx, c, q_dev, n_rows, nq, scores, sstride, fl, st, restage)) != SVS_OK) return rc;
   } else {
     if (fl.state || n_rows != idx->n) return fail(SVS_ERR_INVALID, "internal: single-query kernels have no fused / prefix form");
+    launch_record("gemv", n_rows, nq);   // (one entry for the per-query loop)
     for (int qi = 0; qi < nq; ++qi) {
       rc = launch_scores(idx, c, q_dev + (size_t)qi * idx->d, scores + (size_t)qi * sstride, st);
       if (rc != SVS_OK) return rc;
@@ -1881,6 +1941,7 @@ static void coalesced_pass(svs_index* idx, std::vector<svs_index::Waiter*>& batc
 
 int32_t svs_index_search(svs_index* idx, const float* queries, int32_t nq, int32_t d, int32_t k,
                          float* out_scores, int64_t* out_rows, int32_t* out_count) {
+  launch_reset();
   if (!idx) return fail(SVS_ERR_INVALID, "null index");
   // (only well-formed single queries are coalesced: every error stays with the call that made it)
   // (and only ordinary k: a "rank everything" call must not size a whole pass's buffers)
@@ -1968,6 +2029,7 @@ int32_t svs_index_coalesce_sizes(svs_index* idx, int64_t* out, int32_t cap) {
 int32_t svs_index_search_device(svs_index* idx, const float* dev_queries, int32_t nq, int32_t d,
                                 int32_t k, float* dev_out_scores, int64_t* dev_out_rows,
                                 int32_t* out_count, void* hip_stream) {
+  launch_reset();
   if (!idx) return fail(SVS_ERR_INVALID, "null index");
   RefGuard guard(idx);
   std::shared_lock<std::shared_mutex> geo(idx->rw);
@@ -1993,6 +2055,7 @@ int32_t svs_index_search_device(svs_index* idx, const float* dev_queries, int32_
 
 int32_t svs_index_scores_n(svs_index* idx, const float* query, int32_t d, float* out_scores, int64_t out_capacity,
                            int64_t* out_n) {
+  launch_reset();
   if (!idx) return fail(SVS_ERR_INVALID, "null index");
   RefGuard guard(idx);
   std::shared_lock<std::shared_mutex> geo(idx->rw);   // (appends / commits take it exclusively: idx->n cannot move below)
@@ -2011,6 +2074,7 @@ int32_t svs_index_scores_n(svs_index* idx, const float* query, int32_t d, float*
   if ((rc = grow_dev(&c->q_dev, &c->q_cap, (size_t)d)) != SVS_OK) return rc;
   if ((rc = grow_dev(&c->scores, &c->scores_cap, (size_t)((idx->n + 3) & ~(int64_t)3))) != SVS_OK) return rc;
   HIP_TRY(hipMemcpyAsync(c->q_dev, query, (size_t)d * sizeof(float), hipMemcpyHostToDevice, c->stream));
+  launch_record("gemv", idx->n, 1);
   if ((rc = launch_scores(idx, c, c->q_dev, c->scores, c->stream)) != SVS_OK) return rc;
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipMemcpyAsync(out_scores, c->scores, (size_t)idx->n * sizeof(float), hipMemcpyDeviceToHost, c->stream));
@@ -2144,6 +2208,15 @@ int32_t svs_internal_tune(int32_t what, int64_t value) {
 int32_t svs_internal_host_phases(double* out, int32_t n) {
   for (int i = 0; i < n && i < 6; ++i) out[i] = g_host_phase[i];
   return SVS_OK;
+}
+
+int32_t svs_internal_last_launches(const char** kernels, int64_t* rows, int32_t* nq, int32_t cap) {
+  for (int i = 0; i < cap && i < g_nlaunch && i < LAUNCH_REC_CAP; ++i) {
+    if (kernels) kernels[i] = g_launch[i].kernel;
+    if (rows) rows[i] = g_launch[i].rows;
+    if (nq) nq[i] = g_launch[i].nq;
+  }
+  return g_nlaunch;
 }
 
 int32_t svs_index_set_variant(svs_index* idx, int32_t variant) {

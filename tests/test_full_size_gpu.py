@@ -89,19 +89,28 @@ def test_config1_f32_batch16_equals_single_queries(gpu):
 
 def test_config2_f16_b1024_fused_equals_materialised(gpu):
     """BASELINE configs[2]: 1M x 1536 f16, 1024 queries per call.  The fused run never writes
-    the 4 GB score matrix; the materialised run of the same GEMM does, 256 queries at a time."""
+    the 4 GB score matrix; the materialised run of the same GEMM does, 256 queries at a time.
+    Queries equal to rows 123,456, n - 1 (the last, partial row tile) and 0 come first in their lists, and queries
+    of every query tile are checked against the oracle on the stored corpus."""
     import torch
+    from svs_amd import _native
+    from compare import assert_topk_parity
+    from oracle import svs_oracle as oracle
     n, d, k, nq = 1_000_000, 1536, 100, 1024
     rows = _corpus(n, d, 5151)
     qs = _queries(nq, d, 17)
-    planted = 123_456
-    qs[1000] = rows[planted]
+    planted = {1000: 123_456, 1001: n - 1, 1002: 0}
+    for qi, row in planted.items():
+        qs[qi] = rows[row]
     idx = _index(rows, "f16")
     del rows
     torch.cuda.empty_cache()
     qh = qs.cpu().numpy()
     fs, fr = idx.search_batch(qh, k)
-    assert fr[1000, 0] == planted and abs(fs[1000, 0] - 1.0) < 2e-3      # f16 rounding of a unit vector
+    launches = _native.last_launches()
+    assert [x[0] for x in launches if x[1] == n][:1] == ["gemm_phased_kernel<true, 2, 0, 256>"], launches
+    for qi, row in planted.items():
+        assert fr[qi, 0] == row and abs(fs[qi, 0] - 1.0) < 2e-3, (qi, row, fr[qi, :3])   # f16 rounding of a unit vector
     assert np.all(np.diff(fs, axis=1) <= 0) and fr.min() >= 0 and fr.max() < n
     idx.set_variant(6)
     for q0 in range(0, nq, 256):
@@ -113,7 +122,19 @@ def test_config2_f16_b1024_fused_equals_materialised(gpu):
         one = idx.search(qh[qi], k)
         _same_up_to_near_ties(fs[qi], fr[qi], np.array([s for s, _ in one], dtype=np.float32),
                               np.array([r for _, r in one], dtype=np.int64), 4e-6)
+    # the oracle on the stored corpus (6 GB of f32 on the host), f64 truth computed in row blocks
+    check = [0, 255, 256, 511, 1000, 1001, 1002, 1023]
+    md = idx.stored_rows()
+    idx_q = [idx.stored_query(qh[qi]) for qi in check]
     idx.release()
+    q64 = np.array(idx_q, dtype=np.float64).T
+    truth = np.empty((len(check), n))
+    for r0 in range(0, n, 65536):
+        truth[:, r0:r0 + 65536] = (md[r0:r0 + 65536].astype(np.float64) @ q64).T
+    for j, qi in enumerate(check):
+        exp = oracle.cpu_search(md, idx_q[j], k)
+        assert_topk_parity(fs[qi], fr[qi], [x for x, _ in exp], [i for _, i in exp], truth[j], label=f"configs[2] q{qi}")
+    del md
 
 
 def _build_in_blocks(n, d, dtype, seed, planted, block=500_000, row_offset=0):

@@ -142,3 +142,32 @@ def test_no_shipped_gemm_kernel_touches_scratch_inside_its_k_loop(build_reports)
             continue
         assert r["scratch"] == 0 and r["vgpr_spill"] == 0, f"{pretty}: {r}"
     assert seen_allowed
+
+
+def _gemm_instantiations(table):
+    """'gemm_tiled_kernel<32, true, 4, 128>', ...: every batched score kernel in the report, as c++filt spells it."""
+    names = _demangle([n for n in table if re.search(r"gemm_(q16r|tiled|phased|f32_q16)_kernel", n)])
+    out = set()
+    for pretty in names.values():
+        m = re.search(r"(gemm_\w+_kernel<[^>]*>)", pretty)
+        assert m, pretty
+        out.add(m.group(1))
+    return out
+
+
+def test_every_shipped_gemm_kernel_has_a_test_case(build_reports):
+    """Every gemm_q16r / gemm_tiled / gemm_phased (and gemm_f32_q16) instantiation in the library is the main-pass kernel
+    of some case of tests/batch_kernel_table.py (which tests/test_batch_kernels_gpu.py checks against f64 and asserts it
+    reached), or on the table's list of kernels that only an A/B variant reaches.  A kernel added without a case fails
+    here, on CPU."""
+    from batch_kernel_table import AB_ONLY, CASES
+    built = _gemm_instantiations(_resources(build_reports[0]))
+    assert len(built) >= 48, sorted(built)
+    tested = {c[6] for c in CASES}
+    untested = sorted(built - tested - set(AB_ONLY))
+    assert not untested, f"kernels in the build that no case of tests/batch_kernel_table.py reaches: {untested}"
+    stale = sorted((tested | set(AB_ONLY)) - built - {"gemv"})
+    assert not stale, f"kernels the table names that the build does not hold: {stale}"
+    both = sorted(tested & set(AB_ONLY))
+    assert not both, f"kernels both tested and listed as A/B-only: {both}"
+    assert set(AB_ONLY.values()) <= {3, 4, 8, 9}

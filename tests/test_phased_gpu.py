@@ -5,7 +5,10 @@ queries over f16 / fp8 corpora -- BASELINE.json configs[2] and configs[4]) again
     svs_index_set_variant(2)): same arithmetic in the same k order, so BIT-identical scores and rows.
 The second check is also the race screen for the LDS-DMA ring (reads are placed by the
 vmcnt / barrier counts; an early read shows up as a rare wrong tile): every shape is searched
-several times, and the repetitions must agree bit for bit."""
+several times, and the repetitions must agree bit for bit.
+Every case asserts, through svs_internal_last_launches, the kernel its main pass ran: rows shorter than PG_MIN_KT = 6
+k-tiles of 128 bytes, or an odd number of them, are the tiled kernel's (phased_ok), and the cases that land there are
+labelled as that fallback."""
 import numpy as np
 import pytest
 
@@ -16,29 +19,68 @@ from synth import corpus_and_query
 pytestmark = pytest.mark.gpu
 
 
-@pytest.mark.parametrize("dtype,n,d,nq,k", [
-    ("f16", 140000, 1536, 300, 100),   # fused top-k, two query tiles (one partial), last row tile partial
-    ("f16", 131072 + 77, 256, 129, 50),  # 4 k-tiles per row, one query tile with 127 padded queries
-    ("f16", 9000, 128, 256, 100),      # 2 k-tiles per row (the minimum), materialised scores (n < 131,072)
-    ("f16", 300, 1536, 200, 300),      # fewer rows than one tile, k == n
-    ("f16", 20000, 768, 1024, 10),     # 4 query tiles share every row tile
-    ("fp8", 140000, 3072, 256, 100),   # configs[4]'s row length
-    ("fp8", 10000, 256, 130, 20),      # 2 k-tiles per row
-    ("fp8", 135000, 1536, 513, 64),    # three query tiles, the last with one query
+def _ph(fused, eb, exp, qt):
+    return f"gemm_phased_kernel<{'true' if fused else 'false'}, {eb}, {exp}, {qt}>"
+
+
+def _tg(bn, fused, eb):
+    return f"gemm_tiled_kernel<{bn}, {'true' if fused else 'false'}, {eb}, 256>"
+
+
+def _round1(kernel, nq):
+    """The tiled kernel svs_index_set_variant(2) puts in the place of `kernel` (phased or tiled) for nq queries."""
+    args = kernel[kernel.index("<") + 1:-1].split(", ")
+    fused, eb = (args[0], args[1]) if kernel.startswith("gemm_phased") else (args[1], args[2])
+    return _tg(256 if nq > 128 else 128, fused == "true", int(eb))
+
+
+def _with_ids(cases):
+    """(dtype, n, d, nq, k) name each case, as they did before the kernel column"""
+    return [pytest.param(*c, id="-".join(str(x) for x in c[:5])) for c in cases]
+
+
+def _assert_ran(n, kernel):
+    """The main pass (the launch over all n rows) of this thread's last search ran `kernel`."""
+    from svs_amd import _native
+    launches = _native.last_launches()
+    main = [rec[0] for rec in launches if rec[1] == n]
+    assert main and main[0] == kernel, f"main pass {main[:1]}, expected {kernel}: {launches}"
+
+
+@pytest.mark.parametrize("dtype,n,d,nq,k,kernel", _with_ids([
+    ("f16", 140000, 1536, 300, 100, _ph(True, 2, 0, 256)),   # fused top-k, two query tiles (one partial), last row tile partial
+    ("f16", 140000, 384, 200, 100, _ph(True, 2, 20, 256)),   # 6 k-tiles per row (the minimum), fused
+    ("f16", 20000, 512, 300, 50, _ph(False, 2, 0, 256)),     # 8 k-tiles, materialised scores (n < 131,072)
+    ("f16", 140000, 640, 257, 64, _ph(True, 2, 0, 256)),     # 10 k-tiles, fused, two query tiles
+    ("f16", 20000, 4608, 129, 50, _ph(False, 2, 0, 256)),    # 72 k-tiles (the longest f16 row of the 16-query kernel)
+    ("f16", 300, 1536, 200, 300, _ph(False, 2, 0, 256)),     # fewer rows than one tile, k == n
+    ("f16", 20000, 768, 1024, 10, _ph(False, 2, 0, 256)),    # 4 query tiles share every row tile
+    ("fp8", 140000, 3072, 256, 100, _ph(True, 1, 20, 256)),  # configs[4]'s row length
+    ("fp8", 140000, 768, 300, 100, _ph(True, 1, 0, 256)),    # 6 k-tiles, fused
+    ("fp8", 20000, 1024, 256, 50, _ph(False, 1, 0, 256)),    # 8 k-tiles, materialised
+    ("fp8", 140000, 1280, 129, 64, _ph(True, 1, 20, 256)),   # 10 k-tiles, fused
+    ("fp8", 131100, 4096, 200, 100, _ph(True, 1, 20, 256)),  # 32 k-tiles, fused
+    ("fp8", 135000, 1536, 513, 64, _ph(True, 1, 0, 256)),    # three query tiles, the last with one query
     # few survivors per tile (small k): the epilogue's grouped compare-and-branch path (PG_SPARSE_MAX)
-    ("f16", 140000, 1536, 300, 8),
-    ("fp8", 140000, 3072, 256, 5),
-])
-def test_phased_equals_round1_kernel_and_oracle(gpu, dtype, n, d, nq, k):
+    ("f16", 140000, 1536, 300, 8, _ph(True, 2, 0, 256)),
+    ("fp8", 140000, 3072, 256, 5, _ph(True, 1, 20, 256)),
+    # rows of fewer than 6 k-tiles are the tiled kernel's (phased_ok): the variant-2 run below is the same kernel
+    ("f16", 131072 + 77, 256, 129, 50, _tg(256, True, 2)),   # 4 k-tiles per row, one query tile with 127 padded queries
+    ("f16", 9000, 128, 256, 100, _tg(256, False, 2)),        # 2 k-tiles per row, materialised scores
+    ("fp8", 10000, 256, 130, 20, _tg(256, False, 1)),        # 2 k-tiles per row
+]))
+def test_phased_equals_round1_kernel_and_oracle(gpu, dtype, n, d, nq, k, kernel):
     from svs_amd import DeviceIndex
     m, qs = corpus_and_query("gaussian", 900 + n % 1000 + nq, n, d, nq)
     idx = DeviceIndex(m, dtype=dtype)
     s0, r0 = idx.search_batch(qs, k)
+    _assert_ran(n, kernel)
     for rep in range(4):                 # race screen: repetitions agree bit for bit
         s1, r1 = idx.search_batch(qs, k)
         assert np.array_equal(r0, r1) and np.array_equal(s0, s1), f"run {rep} differs"
     idx.set_variant(2)                   # the round-1 256 x 256 kernel
     s2, r2 = idx.search_batch(qs, k)
+    _assert_ran(n, _round1(kernel, nq))
     idx.set_variant(0)
     assert np.array_equal(r0, r2) and np.array_equal(s0, s2), "phased kernel != gemm_tiled kernel"
     md = idx.stored_rows()
@@ -50,15 +92,24 @@ def test_phased_equals_round1_kernel_and_oracle(gpu, dtype, n, d, nq, k):
     idx.release()
 
 
-@pytest.mark.parametrize("dtype,n,d,nq,k", [
-    ("f16", 140000, 1536, 128, 100),   # one full 128-query tile, fused top-k, last row tile partial
-    ("f16", 140000, 1536, 65, 100),    # 63 padded queries (+inf thresholds in the sweeps)
-    ("f16", 9000, 128, 100, 50),       # 2 k-tiles per row, materialised scores
-    ("fp8", 140000, 3072, 128, 100),   # configs[4]'s row length
-    ("fp8", 135000, 1536, 97, 7),      # few survivors per tile: the grouped epilogue path with padded queries
-    ("fp8", 10000, 256, 66, 20),
-])
-def test_phased_128_query_tiles_equal_tiled_kernel_and_oracle(gpu, dtype, n, d, nq, k):
+@pytest.mark.parametrize("dtype,n,d,nq,k,kernel", _with_ids([
+    ("f16", 140000, 1536, 128, 100, _ph(True, 2, 20, 128)),  # one full 128-query tile, fused top-k, last row tile partial
+    ("f16", 140000, 1536, 65, 100, _ph(True, 2, 20, 128)),   # 63 padded queries (+inf thresholds in the sweeps)
+    ("f16", 140000, 384, 100, 100, _ph(True, 2, 20, 128)),   # 6 k-tiles, fused
+    ("f16", 9000, 512, 77, 50, _ph(False, 2, 0, 128)),       # 8 k-tiles, materialised
+    ("f16", 9000, 640, 128, 50, _ph(False, 2, 0, 128)),      # 10 k-tiles, materialised
+    ("f16", 9000, 4608, 100, 50, _ph(False, 2, 0, 128)),     # 72 k-tiles
+    ("fp8", 140000, 3072, 128, 100, _ph(True, 1, 20, 128)),  # configs[4]'s row length
+    ("fp8", 135000, 1536, 97, 7, _ph(True, 1, 20, 128)),     # few survivors per tile: the grouped epilogue path with padded queries
+    ("fp8", 140000, 768, 128, 100, _ph(True, 1, 20, 128)),   # 6 k-tiles, fused
+    ("fp8", 140000, 1024, 70, 50, _ph(True, 1, 20, 128)),    # 8 k-tiles, fused
+    ("fp8", 9000, 1280, 100, 50, _ph(False, 1, 0, 128)),     # 10 k-tiles, materialised
+    ("fp8", 9000, 4096, 66, 50, _ph(False, 1, 0, 128)),      # 32 k-tiles
+    # rows of fewer than 6 k-tiles: the tiled fallback (128-query tiles, 256 rows), the same kernel under variant 2
+    ("f16", 9000, 128, 100, 50, _tg(128, False, 2)),         # 2 k-tiles per row, materialised scores
+    ("fp8", 10000, 256, 66, 20, _tg(128, False, 1)),         # 2 k-tiles per row
+]))
+def test_phased_128_query_tiles_equal_tiled_kernel_and_oracle(gpu, dtype, n, d, nq, k, kernel):
     """Panels of 65 .. 128 queries (the batches a coalescer forms on a reduced-precision index, reference
     src/svs/kb.py:1184-1190): gemm_phased_kernel<.., QT = 128> against the tiled kernel it replaces
     (svs_index_set_variant(2): bit-identical scores and rows) and the numpy oracle on the stored corpus."""
@@ -66,11 +117,13 @@ def test_phased_128_query_tiles_equal_tiled_kernel_and_oracle(gpu, dtype, n, d, 
     m, qs = corpus_and_query("gaussian", 1700 + n % 1000 + nq, n, d, nq)
     idx = DeviceIndex(m, dtype=dtype)
     s0, r0 = idx.search_batch(qs, k)
+    _assert_ran(n, kernel)
     for rep in range(4):                 # race screen of the LDS-DMA ring at the new counted waits
         s1, r1 = idx.search_batch(qs, k)
         assert np.array_equal(r0, r1) and np.array_equal(s0, s1), f"run {rep} differs"
     idx.set_variant(2)
     s2, r2 = idx.search_batch(qs, k)
+    _assert_ran(n, _round1(kernel, nq))
     idx.set_variant(0)
     assert np.array_equal(r0, r2) and np.array_equal(s0, s2), "128-query phased kernel != gemm_tiled kernel"
     md = idx.stored_rows()
@@ -92,6 +145,7 @@ def test_small_panels_on_reduced_precision_match_oracle(gpu, dtype, nq):
     m, qs = corpus_and_query("gaussian", 2100 + nq, n, d, nq)
     idx = DeviceIndex(m, dtype=dtype)
     s0, r0 = idx.search_batch(qs, k)
+    _assert_ran(n, f"gemm_tiled_kernel<{32 if nq <= 32 else 64}, true, {2 if dtype == 'f16' else 1}, 128>")
     md = idx.stored_rows()
     for qi in sorted({0, nq // 2, nq - 1}):
         qd = idx.stored_query(qs[qi])
@@ -108,6 +162,7 @@ def test_phased_odd_ktile_count_falls_back(gpu):
     m, qs = corpus_and_query("gaussian", 5, 6000, 192, 200)
     idx = DeviceIndex(m, dtype="f16")
     s, r = idx.search_batch(qs, 20)
+    _assert_ran(6000, _tg(256, False, 2))
     md = idx.stored_rows()
     for qi in (0, 199):
         qd = idx.stored_query(qs[qi])
@@ -132,8 +187,10 @@ def test_phased_clustered_rows_overflow_the_parking_lot(gpu, dtype):
         m[base:base + cnt] = rows / np.linalg.norm(rows, axis=1, keepdims=True)
     idx = DeviceIndex(m, dtype=dtype)
     s0, r0 = idx.search_batch(qs, k)
+    _assert_ran(n, _ph(True, 2 if dtype == "f16" else 1, 20, 256))
     idx.set_variant(2)
     s2, r2 = idx.search_batch(qs, k)
+    _assert_ran(n, _tg(256, True, 2 if dtype == "f16" else 1))
     idx.set_variant(0)
     # nobody leaves the fused path: what does not fit a wave's eighth goes straight to the global lists
     assert np.array_equal(r0, r2) and np.array_equal(s0, s2)
@@ -166,8 +223,10 @@ def test_phased_small_topics_flush_by_runs(gpu, dtype, k):
         m[base:base + cnt] = rows / np.linalg.norm(rows, axis=1, keepdims=True)
     idx = DeviceIndex(m, dtype=dtype)
     s0, r0 = idx.search_batch(qs, k)
+    _assert_ran(n, _ph(True, 2 if dtype == "f16" else 1, 20, 256))
     idx.set_variant(2)
     s2, r2 = idx.search_batch(qs, k)
+    _assert_ran(n, _tg(256, True, 2 if dtype == "f16" else 1))
     idx.set_variant(0)
     assert np.array_equal(r0, r2) and np.array_equal(s0, s2)
     md = idx.stored_rows()
@@ -199,6 +258,7 @@ def test_phased_kernel_rate_floor(gpu):
     q = (q / q.norm(dim=1, keepdim=True)).cpu().numpy()
     for _ in range(3):
         idx.search_batch(q, 100)
+    _assert_ran(n, _ph(True, 2, 0, 256))
     idx.set_timing(True)
     for _ in range(6):
         idx.search_batch(q, 100)
