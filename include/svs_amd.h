@@ -208,6 +208,23 @@ int32_t svs_index_search_device(svs_index* idx, const float* dev_queries, int32_
 int32_t svs_index_scores_n(svs_index* idx, const float* query, int32_t d, float* out_scores,
                            int64_t out_capacity, int64_t* out_n);
 
+/* Filtered search: svs_index_search over a caller-given subset of the rows (one book's chunks, one
+ * user's files, one level of the document tree).  Generalises np.dot + get_top_k of superheavy()
+ * (src/svs/kb.py:1622-1627, src/svs/util.py:190-203) to get_top_k(np.dot(M[S], q), k) with position
+ * p mapped to S[p], where S = the live rows of `rows`, ascending, duplicates collapsed:
+ *   rows      GLOBAL rows (row_offset + local, like svs_index_mask_rows), any order, duplicates
+ *             allowed; a row outside [row_offset, row_offset + n) -> SVS_ERR_INVALID; tombstoned
+ *             rows drop out
+ *   count   = min(max(k, 0), |S|); out_scores / out_rows as svs_index_search (stride k, order
+ *             (score desc, row desc), f32 dot products of the stored row and the stored query)
+ * d != index d -> SVS_ERR_SHAPE; nrows < 0 -> SVS_ERR_INVALID; nrows == 0 or k <= 0 -> count 0,
+ * nothing launched.  Only the listed rows are read (a subset of m rows costs about m / n of a corpus
+ * pass; each row once per group of queries), and a query's results do not depend on nq.  Blocks;
+ * re-entrant on one handle.  Rows of more than 16 KiB -> SVS_ERR_UNSUPPORTED. */
+int32_t svs_index_search_rows(svs_index* idx, const float* queries, int32_t nq, int32_t d, int32_t k,
+                              const int64_t* rows, int64_t nrows,
+                              float* out_scores, int64_t* out_rows, int32_t* out_count);
+
 /* ---- pairwise: replaces np.dot(M, M.T) + get_top_pairs of
  *      document_top_pairwise_scores, src/svs/kb.py:1642-1671, src/svs/util.py:206-233 --
  * The k best-scoring row PAIRS (i < j; diagonal and lower triangle ignored), ordered

@@ -23,6 +23,7 @@
 #include <vector>
 
 #include "fp8.h"
+#include "gather.h"
 #include "gemm_tiled.h"
 #include "gemm_phased.h"
 #include "gemm_q16.h"
@@ -134,6 +135,8 @@ struct Ctx {
   float* out_s_pin = nullptr;   int64_t* out_r_pin = nullptr; size_t out_pin_cap = 0;
   float* redo_s_pin = nullptr;  int64_t* redo_r_pin = nullptr; size_t redo_pin_cap = 0;   // results of re-run queries (search_host)
   float* redo_q_pin = nullptr;  size_t redo_q_cap = 0;                                      // ... and the queries themselves, gathered
+  uint32_t* list_dev = nullptr; size_t list_cap = 0;     // svs_index_search_rows: the listed local rows (u32)
+  uint32_t* list_pin = nullptr; size_t list_pin_cap = 0; // ... built here, uploaded from here
   // Scratch is reused in stream order.  A context stays with the stream that
   // last used it; handing it to ANOTHER stream first drains the old one.
   hipStream_t last_stream = nullptr;
@@ -239,6 +242,8 @@ void ctx_destroy(Ctx* c) {
   (void)hipFree(c->hist);
   (void)hipFree(c->cand);
   (void)hipFree(c->keys);
+  (void)hipFree(c->list_dev);
+  if (c->list_pin) (void)hipHostFree(c->list_pin);
   (void)hipHostFree(c->q_pin);
   (void)hipHostFree(c->out_s_pin);
   (void)hipHostFree(c->out_r_pin);
@@ -878,6 +883,76 @@ int run_select(svs_index* idx, Ctx* c, const float* scores, int64_t n_eff, int64
   return SVS_OK;
 }
 
+// ---- filtered search: scores of nq queries over a row list (gather.h) ---------------------------
+template <int DT, int T, int NC, int U, int G>
+constexpr KernelName kGatherName = kernel_name("gather_scores_kernel", DT, T, NC, U, G);
+
+template <int DT, int T, int NC, int U>
+void launch_gather_geo(const svs_index* idx, const void* q, const float* q_scales, int nq, const uint32_t* list, int64_t m,
+                       float* scores, int64_t sstride, int ld16, hipStream_t st) {
+  constexpr int WPB = gather_wpb(NC);
+  constexpr int64_t per_block = (int64_t)(64 / T) * U * WPB;
+  const unsigned blocks = (unsigned)((m + per_block - 1) / per_block);
+  if (nq == 1) {
+    launch_record(kGatherName<DT, T, NC, U, 1>.s, m, nq);
+    hipLaunchKernelGGL((gather_scores_kernel<DT, T, NC, U, 1>), dim3(blocks, 1), dim3(WPB * 64), 0, st,
+                       (const u32x4*)idx->rows, ld16, list, m, (const u32x4*)q, nq, idx->row_scales, q_scales, scores, sstride);
+  } else {
+    launch_record(kGatherName<DT, T, NC, U, GATHER_G>.s, m, nq);
+    const size_t lds = (size_t)std::min(nq, GATHER_G) * ld16 * 16;
+    hipLaunchKernelGGL((gather_scores_kernel<DT, T, NC, U, GATHER_G>), dim3(blocks, (nq + GATHER_G - 1) / GATHER_G),
+                       dim3(WPB * 64), lds, st, (const u32x4*)idx->rows, ld16, list, m, (const u32x4*)q, nq,
+                       idx->row_scales, q_scales, scores, sstride);
+  }
+}
+
+// q: nq staged queries ([nq][ld] in the corpus dtype, zero padded); list: m local rows on the device
+template <int DT>
+int launch_gather_dt(const svs_index* idx, const void* q, const float* q_scales, int nq, const uint32_t* list, int64_t m,
+                     float* scores, int64_t sstride, hipStream_t st) {
+  const int ld16 = (int)((size_t)idx->ld * elem_bytes(idx) / 16);
+#define SVS_GATHER(T, NC, U)                                                                            \
+  do {                                                                                                  \
+    launch_gather_geo<DT, T, NC, U>(idx, q, q_scales, nq, list, m, scores, sstride, ld16, st);          \
+    return SVS_OK;                                                                                      \
+  } while (0)
+  // (12-16 KiB of row loads in flight per wave: the gather rates of random whole rows need several rows per wave)
+  if (ld16 <= 1) SVS_GATHER(1, 1, 8);
+  if (ld16 <= 2) SVS_GATHER(2, 1, 8);
+  if (ld16 <= 4) SVS_GATHER(4, 1, 8);
+  if (ld16 <= 8) SVS_GATHER(8, 1, 8);
+  if (ld16 <= 16) SVS_GATHER(16, 1, 8);
+  if (ld16 <= 32) SVS_GATHER(32, 1, 8);
+  if (ld16 <= 64) SVS_GATHER(64, 1, 8);
+  if (ld16 <= 128) SVS_GATHER(64, 2, 6);
+  if (ld16 <= 192) SVS_GATHER(64, 3, 4);
+  if (ld16 <= 256) SVS_GATHER(64, 4, 3);
+  if (ld16 <= 384) SVS_GATHER(64, 6, 2);
+  if (ld16 <= 512) SVS_GATHER(64, 8, 2);
+  if (ld16 <= 768) SVS_GATHER(64, 12, 1);
+  if (ld16 <= 1024) SVS_GATHER(64, 16, 1);
+#undef SVS_GATHER
+  return fail(SVS_ERR_UNSUPPORTED, "svs_index_search_rows: rows of %d bytes; the gather kernel takes rows of up to 16 KiB",
+              ld16 * 16);
+}
+
+// Stages queries [q0, q0 + nq) of the call (f32 in c->q_dev) in the corpus dtype and scores them over the list.
+int launch_gather(const svs_index* idx, Ctx* c, const float* q_dev, int nq, const uint32_t* list, int64_t m, float* scores,
+                  int64_t sstride, hipStream_t st) {
+  int rc;
+  if (idx->dtype == SVS_DTYPE_F32) {
+    const float* qs = nullptr;
+    if ((rc = stage_queries_f32(idx, c, q_dev, nq, 1, &qs, st)) != SVS_OK) return rc;
+    return launch_gather_dt<0>(idx, qs, nullptr, nq, list, m, scores, sstride, st);
+  }
+  if (idx->dtype == SVS_DTYPE_F16) {
+    if ((rc = stage_queries_f16(idx, c, q_dev, nq, nq, st)) != SVS_OK) return rc;
+    return launch_gather_dt<1>(idx, c->qh, nullptr, nq, list, m, scores, sstride, st);
+  }
+  if ((rc = stage_queries_fp8(idx, c, q_dev, nq, nq, false, st)) != SVS_OK) return rc;
+  return launch_gather_dt<2>(idx, c->q8, c->q8s, nq, list, m, scores, sstride, st);
+}
+
 // rows whose exact k-th best seeds the fused epilogue's thresholds: about k * n / prefix
 // candidates per query survive, so the prefix grows with n (n/64 -> ~64 k survivors)
 // Materialised scores of nq queries: scores[q][sstride] (the non-fused score stage).
@@ -991,6 +1066,21 @@ struct SearchPlan {
   EvTriple ev{};
 };
 
+// Histogram / candidate scratch of run_select's window path (n_eff > SORT_CAP, count <= SEL_KMAX) for nq queries.
+int grow_select_scratch(Ctx* c, int nq, hipStream_t st) {
+  if ((size_t)nq <= c->hist_cap) return SVS_OK;
+  if (c->hist) HIP_TRY(hipFree(c->hist));
+  if (c->cand) HIP_TRY(hipFree(c->cand));
+  c->hist = nullptr; c->cand = nullptr; c->hist_cap = 0;
+  const size_t scr_bytes = (size_t)nq * SCR_WORDS * sizeof(uint32_t);
+  HIP_TRY(hipMalloc((void**)&c->hist, scr_bytes));
+  HIP_TRY(hipMalloc((void**)&c->cand, (size_t)nq * CAND_CAP * sizeof(uint64_t)));
+  // zeroed once; select_final_kernel leaves it zeroed after every search
+  HIP_TRY(hipMemsetAsync(c->hist, 0, scr_bytes, st));
+  c->hist_cap = nq;
+  return SVS_OK;
+}
+
 int plan_search(svs_index* idx, Ctx* c, int nq, int k, int count, hipStream_t st, bool allow_fused, SearchPlan* p) {
   const int64_t n = idx->n;
   int rc;
@@ -1012,17 +1102,7 @@ int plan_search(svs_index* idx, Ctx* c, int nq, int k, int count, hipStream_t st
   // (16 queries: 20 vs 33 us; 256 x 156,250 rows: 119 vs 284 us).
   p->kth = p->fused && nq >= 256 && p->n_mat <= 32768;
   if ((rc = grow_dev(&c->scores, &c->scores_cap, (size_t)nq * (size_t)p->sstride)) != SVS_OK) return rc;
-  if (p->path_a && (size_t)nq > c->hist_cap) {
-    if (c->hist) HIP_TRY(hipFree(c->hist));
-    if (c->cand) HIP_TRY(hipFree(c->cand));
-    c->hist = nullptr; c->cand = nullptr; c->hist_cap = 0;
-    const size_t scr_bytes = (size_t)nq * SCR_WORDS * sizeof(uint32_t);
-    HIP_TRY(hipMalloc((void**)&c->hist, scr_bytes));
-    HIP_TRY(hipMalloc((void**)&c->cand, (size_t)nq * CAND_CAP * sizeof(uint64_t)));
-    // zeroed once; select_final_kernel leaves it zeroed after every search
-    HIP_TRY(hipMemsetAsync(c->hist, 0, scr_bytes, st));
-    c->hist_cap = nq;
-  }
+  if (p->path_a && (rc = grow_select_scratch(c, nq, st)) != SVS_OK) return rc;
   if (p->fused) {
     if ((rc = grow_dev(&c->pref_s, &c->pref_s_cap, (size_t)nq * (p->kth ? 1 : count))) != SVS_OK) return rc;
     if (!p->kth && (rc = grow_dev(&c->pref_r, &c->pref_r_cap, (size_t)nq * count)) != SVS_OK) return rc;
@@ -2079,6 +2159,129 @@ int32_t svs_index_scores_n(svs_index* idx, const float* query, int32_t d, float*
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipMemcpyAsync(out_scores, c->scores, (size_t)idx->n * sizeof(float), hipMemcpyDeviceToHost, c->stream));
   HIP_TRY(hipStreamSynchronize(c->stream));
+  return SVS_OK;
+}
+
+int32_t svs_index_search_rows(svs_index* idx, const float* queries, int32_t nq, int32_t d, int32_t k,
+                              const int64_t* rows, int64_t nrows, float* out_scores, int64_t* out_rows,
+                              int32_t* out_count) {
+  launch_reset();
+  if (!idx) return fail(SVS_ERR_INVALID, "null index");
+  if (out_count) *out_count = 0;
+  RefGuard guard(idx);
+  std::shared_lock<std::shared_mutex> geo(idx->rw);
+  int rc = check_query_args(idx, queries, nq, d);
+  if (rc != SVS_OK) return rc;
+  if (nrows < 0) return fail(SVS_ERR_INVALID, "nrows must be >= 0");
+  if (nrows > 0 && !rows) return fail(SVS_ERR_INVALID, "null row list");
+  const int64_t lo = idx->row_offset, n = idx->n;
+  bool ascending = true;   // (strictly: then the list needs neither sorting nor deduplication)
+  for (int64_t t = 0; t < nrows; ++t) {
+    const int64_t r = rows[t] - lo;
+    if (r < 0 || r >= n)
+      return fail(SVS_ERR_INVALID, "row %lld out of range [%lld, %lld)", (long long)rows[t], (long long)lo, (long long)(lo + n));
+    if (t && rows[t] <= rows[t - 1]) ascending = false;
+  }
+  if (nq == 0 || nrows == 0 || k <= 0) return SVS_OK;
+  if (!out_scores || !out_rows) return fail(SVS_ERR_INVALID, "null output");
+  HIP_TRY(hipSetDevice(idx->device));
+  if ((rc = staging_wait(idx)) != SVS_OK) return rc;
+  Ctx* c = nullptr;
+  if ((rc = ctx_acquire(idx, nullptr, true, &c)) != SVS_OK) return rc;
+  struct CtxGuard { svs_index* i; Ctx* c; ~CtxGuard() { ctx_release(i, c); } } cg{idx, c};
+  // S = the live listed rows, ascending, as local u32 rows in pinned memory (the upload's source)
+  if ((size_t)nrows > c->list_pin_cap) {
+    if (c->list_pin) HIP_TRY(hipHostFree(c->list_pin));
+    c->list_pin = nullptr; c->list_pin_cap = 0;
+    HIP_TRY(hipHostMalloc((void**)&c->list_pin, (size_t)nrows * sizeof(uint32_t), hipHostMallocDefault));
+    c->list_pin_cap = (size_t)nrows;
+  }
+  uint32_t* S = c->list_pin;
+  int64_t m = 0;
+  const uint8_t* dead = idx->dead_flag.data();
+  if (ascending) {
+    for (int64_t t = 0; t < nrows; ++t) {
+      const uint32_t r = (uint32_t)(rows[t] - lo);
+      if (!dead[r]) S[m++] = r;
+    }
+  } else {
+    std::vector<uint32_t> tmp;
+    try {
+      tmp.resize((size_t)nrows);
+    } catch (const std::bad_alloc&) {
+      return fail(SVS_ERR_NOMEM, "out of host memory for a %lld-row list", (long long)nrows);
+    }
+    for (int64_t t = 0; t < nrows; ++t) tmp[(size_t)t] = (uint32_t)(rows[t] - lo);
+    std::sort(tmp.begin(), tmp.end());
+    const size_t u = (size_t)(std::unique(tmp.begin(), tmp.end()) - tmp.begin());
+    for (size_t t = 0; t < u; ++t)
+      if (!dead[tmp[t]]) S[m++] = tmp[t];
+  }
+  const int count = (int)std::min<int64_t>(k, m);
+  if (out_count) *out_count = count;
+  if (count == 0) return SVS_OK;
+  hipStream_t st = c->stream;
+  const size_t qn = (size_t)nq * (size_t)d, on = (size_t)nq * (size_t)count;
+  if ((rc = grow_dev(&c->q_dev, &c->q_cap, qn)) != SVS_OK) return rc;
+  if ((rc = grow_dev(&c->list_dev, &c->list_cap, (size_t)m)) != SVS_OK) return rc;
+  if (qn > c->q_pin_cap) {
+    if (c->q_pin) HIP_TRY(hipHostFree(c->q_pin));
+    c->q_pin = nullptr; c->q_pin_cap = 0;
+    HIP_TRY(hipHostMalloc((void**)&c->q_pin, qn * sizeof(float), hipHostMallocDefault));
+    c->q_pin_cap = qn;
+  }
+  if (on > c->out_pin_cap) {
+    if (c->out_s_pin) HIP_TRY(hipHostFree(c->out_s_pin));
+    if (c->out_r_pin) HIP_TRY(hipHostFree(c->out_r_pin));
+    c->out_s_pin = nullptr; c->out_r_pin = nullptr; c->out_pin_cap = 0;
+    HIP_TRY(hipHostMalloc((void**)&c->out_s_pin, on * sizeof(float), hipHostMallocDefault));
+    HIP_TRY(hipHostMalloc((void**)&c->out_r_pin, on * sizeof(int64_t), hipHostMallocDefault));
+    c->out_pin_cap = on;
+  }
+  memcpy(c->q_pin, queries, qn * sizeof(float));
+  HIP_TRY(hipMemcpyAsync(c->q_dev, c->q_pin, qn * sizeof(float), hipMemcpyHostToDevice, st));
+  HIP_TRY(hipMemcpyAsync(c->list_dev, S, (size_t)m * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+  // Query chunks whose score matrix (and, for k > SEL_KMAX over more than SORT_CAP rows, sort keys) stays <= 2 GiB
+  const int64_t sstride = (m + 3) & ~(int64_t)3;
+  int64_t per_q = 4 * sstride;
+  const bool window = m > SORT_CAP && count <= SEL_KMAX;
+  if (m > SORT_CAP && !window) {
+    int64_t npad;
+    next_pow2_i64(m, &npad);
+    per_q += 8 * npad;
+  }
+  const int qc = (int)std::max<int64_t>(1, std::min<int64_t>(nq, ((int64_t)2 << 30) / per_q));
+  if ((rc = grow_dev(&c->scores, &c->scores_cap, (size_t)qc * (size_t)sstride)) != SVS_OK) return rc;
+  if (window && (rc = grow_select_scratch(c, qc, st)) != SVS_OK) return rc;
+  for (int q0 = 0; q0 < nq && rc == SVS_OK; q0 += qc) {
+    const int nc = std::min(qc, nq - q0);
+    rc = launch_gather(idx, c, c->q_dev + (size_t)q0 * d, nc, c->list_dev, m, c->scores, sstride, st);
+    if (rc == SVS_OK)
+      rc = run_select(idx, c, c->scores, m, sstride, nc, count, count, c->out_s_pin + (size_t)q0 * count,
+                      c->out_r_pin + (size_t)q0 * count, st, 0);
+  }
+  if (rc == SVS_OK) {
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) rc = fail(SVS_ERR_DEVICE, "search_rows launch: %s", hipGetErrorString(e));
+  }
+  if (rc != SVS_OK) {
+    (void)hipStreamSynchronize(st);
+    return rc;
+  }
+  HIP_TRY(hipStreamSynchronize(st));
+  // positions in S -> global rows; device layout has stride `count`, the caller's stride k
+  for (int qi = 0; qi < nq; ++qi) {
+    const float* ss = c->out_s_pin + (size_t)qi * count;
+    const int64_t* pp = c->out_r_pin + (size_t)qi * count;
+    float* ds = out_scores + (size_t)qi * k;
+    int64_t* dr = out_rows + (size_t)qi * k;
+    memcpy(ds, ss, (size_t)count * sizeof(float));
+    for (int i = 0; i < count; ++i) {
+      const int64_t p = pp[i];
+      if (p < 0 || p >= m) return fail(SVS_ERR_DEVICE, "search_rows: position %lld outside the %lld listed rows", (long long)p, (long long)m);
+      dr[i] = (int64_t)S[p] + lo;
+    }
+  }
   return SVS_OK;
 }
 

@@ -229,6 +229,39 @@ class DeviceIndex:
         # (tolist(): python floats -- the exact widening float(np.float32) does, src/svs/util.py:203 -- and ints in C)
         return list(zip(s[0].astype(np.float64).tolist(), r[0].tolist()))
 
+    def search_batch_within(self, queries: np.ndarray, n: int, rows) -> Tuple[np.ndarray, np.ndarray]:
+        """``search_batch`` over the listed rows only (GLOBAL indices, any order, duplicates allowed;
+        masked rows drop out): (scores f32 (nq, count), rows i64 (nq, count)), count = min(max(n, 0),
+        live listed rows), each row ordered (score desc, row desc) -- ``get_top_k(np.dot(M[S], q), n)``
+        with positions mapped back to rows S (svs_index_search_rows)."""
+        assert isinstance(n, int)
+        q = np.ascontiguousarray(queries, dtype=np.float32)
+        if q.ndim != 2:
+            raise ValueError(f"queries must be 2-D, got shape {q.shape}")
+        r = np.ascontiguousarray(rows, dtype=np.int64).reshape(-1)
+        nq, d = q.shape
+        k = min(max(n, 0), len(r), 2 ** 31 - 1)   # (count <= listed rows: clamp before allocating)
+        scores = np.empty((nq, k), dtype=np.float32)
+        out_rows = np.empty((nq, k), dtype=np.int64)
+        count = C.c_int32(0)
+        h = self._pinned_handle()
+        try:
+            _native.check(self._lib.svs_index_search_rows(h, q.ctypes.data, nq, d, k, r.ctypes.data, len(r),
+                                                          scores.ctypes.data, out_rows.ctypes.data, C.byref(count)))
+        finally:
+            self._unpin(h)
+        c = count.value
+        return (scores, out_rows) if c == k else (scores[:, :c], out_rows[:, :c])
+
+    def search_within(self, query_vec: np.ndarray, n: int, rows) -> List[Tuple[float, int]]:
+        """``search`` restricted to the listed rows (see ``search_batch_within``): [(score, row)]."""
+        assert isinstance(n, int)
+        q = np.asarray(query_vec, dtype=np.float32)
+        if q.ndim != 1:
+            raise ValueError(f"query must be 1-D, got shape {q.shape}")
+        s, r = self.search_batch_within(q[None, :], n, rows)
+        return list(zip(s[0].astype(np.float64).tolist(), r[0].tolist()))
+
     def scores(self, query_vec: np.ndarray) -> np.ndarray:
         """The raw ``np.dot(M, q)`` vector, f32 (N,)."""
         q = np.ascontiguousarray(query_vec, dtype=np.float32)

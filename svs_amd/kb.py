@@ -30,7 +30,7 @@ from typing import Any, Awaitable, Callable, Dict, Iterator, List, Optional, Tup
 import numpy as np
 
 from .index import DeviceIndex
-from .matrix import DeviceEmbeddingsMatrix
+from .matrix import DeviceEmbeddingsMatrix, search_within_held
 
 _LOG = logging.getLogger(__name__)
 
@@ -175,6 +175,22 @@ class _Store:
                 out[row[4]] = {"id": row[0], "parent_id": row[1], "level": row[2], "text": row[3],
                                "embedding": True, "meta": json.loads(row[5]) if row[5] is not None else None}
         return out
+
+    def embeddings_for_docs(self, doc_ids: List[int]) -> List[int]:
+        """Embedding ids of the listed docs, ascending and distinct (``retrieve_within``): one ``IN (...)``
+        query per 500 ids, as ``fetch_docs_for_embeddings``.  An unknown doc id raises KeyError(doc_id),
+        like the reference's fetch_doc; docs without an embedding are skipped."""
+        ids = [int(x) for x in doc_ids]
+        found: Dict[int, Optional[int]] = {}
+        for c0 in range(0, len(ids), 500):   # stay under SQLITE_MAX_VARIABLE_NUMBER
+            chunk = ids[c0:c0 + 500]
+            marks = ",".join("?" * len(chunk))
+            for row in self.conn.execute(f"SELECT id, embedding FROM docs WHERE id IN ({marks})", chunk):
+                found[row[0]] = row[1]
+        for doc_id in ids:
+            if doc_id not in found:
+                raise KeyError(doc_id)
+        return sorted({e for e in found.values() if e is not None})
 
     # -- A7: the producer of the matrix ---------------------------------------
     def build_embeddings_matrix(self) -> Tuple[np.ndarray, np.ndarray]:
@@ -385,6 +401,25 @@ class KB:
         return res
 
 
+    def retrieve_within(self, query: str, n: int, doc_ids: List[int]) -> List[Dict[str, Any]]:
+        """``retrieve`` restricted to the documents ``doc_ids`` (the children of one parent, the docs of one
+        level, ...): the top n of those docs, same log lines and result shape.  Only their rows are scored
+        (svs_index_search_rows).  An unknown doc id raises KeyError; docs without an embedding are skipped."""
+        _LOG.info(f"retrieving {n} documents with query string: {query}")
+        assert self.db is not None
+        self.embeddings_matrix.get_sync(self.db)
+        with self.db.transaction():
+            emb = self.db.embeddings_for_docs(list(doc_ids))
+        query_vec = np.array(self._embed([query])[0], dtype=np.float32)
+        _LOG.info("got embedding for query!")
+        emb_ids = self.embeddings_matrix.search_within(query_vec, n, emb)   # superheavy() over the listed rows: HIP
+        _LOG.info(f"computed {len(emb)} cosine similarities")
+        with self.db.transaction():
+            docs = self.db.fetch_docs_for_embeddings([e for _, e in emb_ids])
+        res = [{"score": score, "doc": docs[e]} for score, e in emb_ids]
+        _LOG.info(f"retrieved top {n} documents")
+        return res
+
     def document_top_pairwise_scores(self, n: int) -> List[Tuple[float, Dict[str, Any], Dict[str, Any]]]:
         """Reference src/svs/kb.py:1642-1671: the n most similar document pairs,
         [(score, doc_1, doc_2)].  M.M^T and the upper-triangle top-n run on the GPU
@@ -569,6 +604,41 @@ class AsyncKB:
             def heavy() -> List[Dict[str, Any]]:
                 with db.transaction():
                     return [{"score": s, "doc": db.fetch_doc_for_embedding(e)} for s, e in emb_ids]
+
+            res = await loop.run_in_executor(None, heavy)
+        _LOG.info(f"retrieved top {n} documents")
+        return res
+
+    async def retrieve_within(self, query: str, n: int, doc_ids: List[int]) -> List[Dict[str, Any]]:
+        """Async twin of ``KB.retrieve_within``, structured as ``retrieve``: the SQL and the reference to the
+        matrix under the lock, the filtered search on an executor thread outside it, the docs under the lock."""
+        _LOG.info(f"retrieving {n} documents with query string: {query}")
+        loop = asyncio.get_running_loop()
+        ids = list(doc_ids)
+        async with self._get_lock():
+            db = await self._ensure_db()
+            await self.embeddings_matrix.get(db)
+
+            def sql() -> List[int]:
+                with db.transaction():
+                    return db.embeddings_for_docs(ids)
+
+            emb = await loop.run_in_executor(None, sql)
+            idx, lookup = self.embeddings_matrix.hold()
+        try:
+            query_vec = np.array((await self._embed([query]))[0], dtype=np.float32)
+            _LOG.info("got embedding for query!")
+            emb_ids = await loop.run_in_executor(None, lambda: search_within_held(idx, lookup, query_vec, n, emb))
+            _LOG.info(f"computed {len(emb)} cosine similarities")
+        finally:
+            idx.release()
+        async with self._get_lock():
+            db = await self._ensure_db()
+
+            def heavy() -> List[Dict[str, Any]]:
+                with db.transaction():
+                    docs = db.fetch_docs_for_embeddings([e for _, e in emb_ids])
+                return [{"score": s, "doc": docs[e]} for s, e in emb_ids]
 
             res = await loop.run_in_executor(None, heavy)
         _LOG.info(f"retrieved top {n} documents")

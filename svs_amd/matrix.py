@@ -51,6 +51,25 @@ class _Lookup:
         self.arr = arr
 
 
+def search_within_held(idx, lookup: _Lookup, query_vec: np.ndarray, n: int, emb_ids) -> List[Tuple[float, int]]:
+    """Top-n among ``emb_ids`` on a held (index, lookup): ids -> rows through ``lookup.arr`` (strictly increasing,
+    so one ``searchsorted``, as ``remove`` does), the filtered search, rows -> ids.  KeyError for an id the
+    loaded matrix does not hold."""
+    ids = np.asarray(emb_ids if isinstance(emb_ids, np.ndarray) else list(emb_ids), dtype=np.int64).reshape(-1)
+    arr = lookup.arr
+    pos = np.searchsorted(arr, ids)
+    if len(ids):
+        bad = pos >= len(arr)
+        if len(arr):
+            bad |= arr[np.minimum(pos, len(arr) - 1)] != ids
+        if bad.any():
+            raise KeyError(int(ids[np.argmax(bad)]))
+    off = int(getattr(idx, "row_offset", 0))
+    res = idx.search_within(query_vec, n, pos + off)
+    arr = lookup.arr   # (an append during the search only extends it)
+    return [(score, int(arr[row - off])) for score, row in res]
+
+
 class DeviceEmbeddingsMatrix:
     """Lazy cache of (DeviceIndex, emb_id_lookup); drop-in for
     ``svs.kb._EmbeddingsMatrix``."""
@@ -259,6 +278,14 @@ class DeviceEmbeddingsMatrix:
             res = co.search(idx, query_vec, n) if co is not None else idx.search(query_vec, n)
             arr = lookup.arr
             return [(score, int(arr[row])) for score, row in res]
+        finally:
+            idx.release()
+
+    def search_within(self, query_vec: np.ndarray, n: int, emb_ids) -> List[Tuple[float, int]]:
+        """``search`` restricted to the listed embedding ids: [(score, emb_id)] (``KB.retrieve_within``)."""
+        idx, lookup = self.hold()
+        try:
+            return search_within_held(idx, lookup, query_vec, n, emb_ids)
         finally:
             idx.release()
 

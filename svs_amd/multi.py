@@ -143,6 +143,46 @@ class MultiDeviceIndex:
         s, r = self.search_batch(q[None, :], n)
         return [(float(a), int(b)) for a, b in zip(s[0], r[0])]
 
+    def search_batch_within(self, queries: np.ndarray, n: int, rows) -> Tuple[np.ndarray, np.ndarray]:
+        """``DeviceIndex.search_batch_within`` over the shards: the sorted global rows are split by shard,
+        each shard searches its part (shards with no listed rows are skipped) and the parts are merged."""
+        assert isinstance(n, int)
+        q = np.ascontiguousarray(queries, dtype=np.float32)
+        if q.ndim != 2:
+            raise ValueError(f"queries must be 2-D, got shape {q.shape}")
+        r = np.unique(np.asarray(rows, dtype=np.int64).reshape(-1))   # sorted, duplicates collapsed
+        if q.shape[1] != self.d:
+            return self._shards[0].search_batch_within(q, n, r[:0])  # same error as a single index
+        if len(r) and (r[0] < 0 or r[-1] >= self.n):
+            raise ValueError(f"row {int(r[0] if r[0] < 0 else r[-1])} out of range [0, {self.n})")
+        jobs = []
+        for s, (lo, hi) in zip(self._shards, self._bounds):
+            part = r[np.searchsorted(r, lo):np.searchsorted(r, hi)]
+            if len(part):
+                jobs.append((s, part))
+        parts = list(self._pool.map(lambda j: j[0].search_batch_within(q, n, j[1]), jobs))
+        nq = q.shape[0]
+        # each shard returns min(n, its live listed rows): the true count is min(n, their sum) -- never more
+        # than the real candidates, so no padding entry can reach the top of the merge
+        count = min(max(n, 0), sum(p[0].shape[1] for p in parts))
+        if count == 0:
+            return np.empty((nq, 0), dtype=np.float32), np.empty((nq, 0), dtype=np.int64)
+        width = max(p[0].shape[1] for p in parts)
+        sc = np.full((len(parts), nq, width), -np.inf, dtype=np.float32)
+        rw = np.full((len(parts), nq, width), -1, dtype=np.int64)
+        for g, (ps, pr) in enumerate(parts):
+            sc[g, :, : ps.shape[1]] = ps
+            rw[g, :, : pr.shape[1]] = pr
+        return merge_topk_batch(sc, rw, count)
+
+    def search_within(self, query_vec: np.ndarray, n: int, rows) -> List[Tuple[float, int]]:
+        assert isinstance(n, int)
+        q = np.asarray(query_vec, dtype=np.float32)
+        if q.ndim != 1:
+            raise ValueError(f"query must be 1-D, got shape {q.shape}")
+        s, r = self.search_batch_within(q[None, :], n, rows)
+        return [(float(a), int(b)) for a, b in zip(s[0], r[0])]
+
     def scores(self, query_vec: np.ndarray) -> np.ndarray:
         parts = list(self._pool.map(lambda s: s.scores(query_vec), [s for s in self._shards if s.n > 0]))
         return np.concatenate(parts) if parts else np.empty(0, dtype=np.float32)
