@@ -64,7 +64,7 @@ typedef struct svs_index_info_t {
   int32_t dtype;      /* svs_dtype                                             */
   int32_t device;     /* HIP device ordinal                                    */
   int64_t row_offset; /* global row index of local row 0 (row sharding, 8(e))  */
-  int64_t hbm_bytes;  /* bytes of HBM held by the corpus                       */
+  int64_t hbm_bytes;  /* bytes of HBM held by the corpus (an f32 index's half shadow included: svs_index_set_screen) */
   int64_t n_masked;   /* rows tombstoned by svs_index_mask_rows (still counted in n) */
 } svs_index_info_t;
 
@@ -282,8 +282,18 @@ int32_t svs_index_set_timing(svs_index* idx, int32_t enable);
 /* Waits for outstanding timed searches, returns the sums, and resets them. */
 int32_t svs_index_get_timing(svs_index* idx, svs_timing_t* out);
 
+/* Screened single-query search (f32 indexes whose rows are 512 .. 4096 elements, a multiple of 512, in HBM).
+ * mode 1 (the default; SVS_AMD_SCREEN=0 in the environment makes 0 the default): the index keeps an IEEE-half
+ * shadow of its rows (+50 % HBM, counted in hbm_bytes); a single query is scored against the shadow (half the
+ * bytes), the rows that a proven error bound leaves in contention are re-scored from the f32 rows, and the
+ * result -- rows, order, score bits -- is that of the unscreened search.  If HBM has no room for the shadow the
+ * index works without it.  mode 0: frees the shadow; every search reads the f32 rows.  mode 1 again rebuilds it
+ * from the rows in HBM.  Blocks searches on this handle while it runs. */
+int32_t svs_index_set_screen(svs_index* idx, int32_t mode);
+
 /* Tuning knob for A/B runs (bench/profiling only): selects a kernel variant of
- * the score stage; 0 = library default.  Returns SVS_ERR_INVALID if unknown. */
+ * the score stage; 0 = library default (11: never screen a single query, 12: screen
+ * whatever the row count).  Returns SVS_ERR_INVALID if unknown. */
 int32_t svs_index_set_variant(svs_index* idx, int32_t variant);
 
 #ifdef __cplusplus

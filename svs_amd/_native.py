@@ -88,6 +88,7 @@ SIGNATURES = {
     "svs_index_set_timing": (C.c_int32, [_P, C.c_int32]),
     "svs_index_get_timing": (C.c_int32, [_P, C.POINTER(Timing)]),
     "svs_index_set_variant": (C.c_int32, [_P, C.c_int32]),
+    "svs_index_set_screen": (C.c_int32, [_P, C.c_int32]),
 }
 
 # svs_amd/csrc/internal.h: hooks for this repo's own tests, tools and bench (not part of the boundary)
@@ -96,6 +97,7 @@ INTERNAL = {
     "svs_internal_tune": (C.c_int32, [C.c_int32, C.c_int64]),
     "svs_internal_host_phases": (C.c_int32, [C.POINTER(C.c_double), C.c_int32]),
     "svs_internal_last_launches": (C.c_int32, [C.POINTER(C.c_char_p), C.POINTER(C.c_int64), C.POINTER(C.c_int32), C.c_int32]),
+    "svs_internal_screen_stats": (C.c_int32, [_P, C.POINTER(C.c_int64), C.c_int32]),
 }
 
 _lib: Optional[C.CDLL] = None
@@ -149,7 +151,12 @@ def load() -> C.CDLL:
     _share_torch_hip_runtime()
     lib = C.CDLL(_LIB_PATH)  # CDLL releases the GIL around every call
     for name, (res, args) in list(SIGNATURES.items()) + list(INTERNAL.items()):
-        fn = getattr(lib, name)
+        try:
+            fn = getattr(lib, name)
+        except AttributeError:
+            if os.environ.get("SVS_AMD_LIB"):   # another revision's build (before / after runs): what it lacks fails when called
+                continue
+            raise
         fn.restype = res
         fn.argtypes = args
     _lib = lib

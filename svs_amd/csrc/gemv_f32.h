@@ -64,6 +64,22 @@ __device__ __forceinline__ float wave_sum(float v) {
   return (r0 + r1) + (r2 + r3);
 }
 
+// ---- one row's score: THE summation order of every ld == NSTEP * 256 kernel ----
+// Lane l holds chunks j*64 + l of the row and of the query; dot4 FMAs in element
+// order into s0 (even j) and s1 (odd j); then wave_sum(s0 + s1).  Every kernel that
+// scores such a row (the two below, and the exact re-score of a screened search,
+// screen.h) calls this, so a row's score bits do not depend on which of them ran.
+template <int NSTEP>
+__device__ __forceinline__ float row_dot_f32(const v4f (&row)[NSTEP], const v4f (&qv)[NSTEP]) {
+  float s0 = 0.f, s1 = 0.f;
+#pragma unroll
+  for (int j = 0; j < NSTEP; ++j) {
+    if (j & 1) s1 = dot4(row[j], qv[j], s1);
+    else s0 = dot4(row[j], qv[j], s0);
+  }
+  return wave_sum(s0 + s1);
+}
+
 // ---- hot kernel: ld == NSTEP * 256 floats -----------------------------------
 // tile t = rows [t*R, t*R + R).  Wave gw of W takes tiles gw, gw+W, ... when
 // CONTIG == false (the whole grid sweeps the matrix front to back), or a
@@ -112,13 +128,7 @@ __global__ __launch_bounds__(WPB * 64) void gemv_f32_rows_kernel(
     float out = 0.f;
 #pragma unroll
     for (int r = 0; r < R; ++r) {
-      float s0 = 0.f, s1 = 0.f;
-#pragma unroll
-      for (int j = 0; j < NSTEP; ++j) {
-        if (j & 1) s1 = dot4(buf[r][j], qv[j], s1);
-        else s0 = dot4(buf[r][j], qv[j], s0);
-      }
-      const float v = wave_sum(s0 + s1);
+      const float v = row_dot_f32<NSTEP>(buf[r], qv);
       out = lane == r ? v : out;
     }
     const int64_t row = t * R + lane;
@@ -195,13 +205,7 @@ __global__ __launch_bounds__(WPB * 64) void gemv_f32_oneshot_kernel(
   float out = 0.f;
 #pragma unroll
   for (int r = 0; r < R; ++r) {
-    float s0 = 0.f, s1 = 0.f;
-#pragma unroll
-    for (int j = 0; j < NSTEP; ++j) {
-      if (j & 1) s1 = dot4(buf[r][j], qv[j], s1);
-      else s0 = dot4(buf[r][j], qv[j], s0);
-    }
-    const float v = wave_sum(s0 + s1);
+    const float v = row_dot_f32<NSTEP>(buf[r], qv);
     out = lane == r ? v : out;
   }
   const int64_t row = row0 + lane;

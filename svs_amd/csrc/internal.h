@@ -15,7 +15,8 @@ int32_t svs_internal_coalesce_hold(svs_index* idx, int32_t n);
  *   0  fused path: threshold prefix = n / value rows (default 64; at least 16,384 rows)
  *   1  host batches: 0 = f16 batches pulled from pinned memory by the staging kernel, chunk by chunk (default);
  *      1 = staged DMA for every dtype (round 3)
- *   2  fused path's threshold rows: 1 = a sample spread over the whole corpus (default); 0 = the first rows (rounds 1-3) */
+ *   2  fused path's threshold rows: 1 = a sample spread over the whole corpus (default); 0 = the first rows (rounds 1-3)
+ *   3  1 = every allocation of an f32 index's half shadow is refused, as if HBM were full (default 0) */
 int32_t svs_internal_tune(int32_t what, int64_t value);
 /* Seconds since the start of the calling thread's last svs_index_search(host batch) at which: [0] scratch was planned,
  * [1] the queries were in pinned memory (and their DMA enqueued), [2] every kernel was enqueued, [3] the stream had
@@ -30,6 +31,12 @@ int32_t svs_internal_host_phases(double* out, int32_t n);
  * launches after its own.  Up to cap entries (and at most 32) are written; returns the number of launches recorded.
  * Coalesced single-query passes and svs_multi_* launch from other threads: they are not in the caller's record. */
 int32_t svs_internal_last_launches(const char** kernels, int64_t* rows, int32_t* nq, int32_t cap);
+/* Screened search (screen.h) on this handle, up to cap (<= 9) values: [0] queries answered from the candidate list,
+ * [1] queries that took the exact whole-corpus fallback (both as the kernels last wrote them to pinned memory: drain
+ * the stream first), [2] shadow: 0 none, 1 valid, 2 invalid for good (an element half cannot hold), [3] 1 = screening
+ * paused until the next ingest (fallbacks dominated), [4] bits of the bound E and [5] candidate count of the calling
+ * thread's last screened search, [6..8] bits of the corpus statistics A, B, C. */
+int32_t svs_internal_screen_stats(svs_index* idx, int64_t* out, int32_t cap);
 /* multi.hip -> svs_amd.hip: carries a worker thread's error message over to the caller's thread */
 int32_t svs_internal_set_error(int32_t code, const char* msg);
 #ifdef __cplusplus

@@ -186,31 +186,11 @@ __global__ __launch_bounds__(FA_THREADS) void select_window_hist_kernel(
   }
 }
 
-// ---- path A, launch 2.  grid = (blocks, nq); cand is [nq][CAND_CAP] ----------
-__global__ __launch_bounds__(FA_THREADS) void select_window_filter_kernel(
-    const float* __restrict__ scores, int64_t n, int64_t score_stride, uint32_t k,
-    uint32_t* __restrict__ scratch, uint64_t* __restrict__ cand) {
-  __shared__ uint32_t sh[FA_THREADS + 2];
-  const int qi = blockIdx.y;
-  const float* s = scores + (int64_t)qi * score_stride;
-  const sel_v4f* s4 = (const sel_v4f*)s;
-  SelHeader* hdr = (SelHeader*)(scratch + (int64_t)qi * SCR_WORDS);
-  const uint32_t* hist = scratch + (int64_t)qi * SCR_WORDS + sizeof(SelHeader) / 4;
-  const int64_t n4 = (n + 3) >> 2;
-  const int64_t base = ((int64_t)blockIdx.x * SEL_VPT) * FA_THREADS + threadIdx.x;
-  sel_v4f v[SEL_VPT];
-#pragma unroll
-  for (int j = 0; j < SEL_VPT; ++j) {   // requested before the histogram scan: the latency hides under it
-    const int64_t i4 = base + (int64_t)j * FA_THREADS;
-    v[j] = i4 < n4 ? s4[i4] : (sel_v4f){0.f, 0.f, 0.f, 0.f};
-  }
-  uint32_t bstar, krank;
-  pick_bucket<FA_THREADS>(hist, WBINS, k, sh, &bstar, &krank);
-  if (bstar == 0xffffffffu) {  // fewer than k scores inside the window: exact fallback in the final kernel
-    if (blockIdx.x == 0 && threadIdx.x == 0) hdr->flag = 1;
-    return;
-  }
-  uint64_t* cq = cand + (int64_t)qi * CAND_CAP;
+// The compaction of the filter kernels: of the SEL_VPT float4 groups a thread holds (group j covers scores
+// (base + j * FA_THREADS) * 4 .. + 3), every score whose window bin is >= bcut is appended to cq as
+// (key << 32 | row); hdr->n_cand counts them all, also those past CAND_CAP (the list is then invalid).
+__device__ __forceinline__ void filter_compact(const sel_v4f (&v)[SEL_VPT], int64_t base, int64_t n, int bcut,
+                                               SelHeader* hdr, uint64_t* cq) {
   const int lane = threadIdx.x & 63;
 #pragma unroll
   for (int j = 0; j < SEL_VPT; ++j) {
@@ -222,7 +202,7 @@ __global__ __launch_bounds__(FA_THREADS) void select_window_filter_kernel(
       key[e] = 0;
       if (i + e < n) {
         const uint32_t kk = score_key(v[j][e]);
-        if (window_bin(kk) >= (int)bstar) {
+        if (window_bin(kk) >= bcut) {
           key[e] = kk;
           ++cnt;
         }
@@ -252,6 +232,33 @@ __global__ __launch_bounds__(FA_THREADS) void select_window_filter_kernel(
       }
     }
   }
+}
+
+// ---- path A, launch 2.  grid = (blocks, nq); cand is [nq][CAND_CAP] ----------
+__global__ __launch_bounds__(FA_THREADS) void select_window_filter_kernel(
+    const float* __restrict__ scores, int64_t n, int64_t score_stride, uint32_t k,
+    uint32_t* __restrict__ scratch, uint64_t* __restrict__ cand) {
+  __shared__ uint32_t sh[FA_THREADS + 2];
+  const int qi = blockIdx.y;
+  const float* s = scores + (int64_t)qi * score_stride;
+  const sel_v4f* s4 = (const sel_v4f*)s;
+  SelHeader* hdr = (SelHeader*)(scratch + (int64_t)qi * SCR_WORDS);
+  const uint32_t* hist = scratch + (int64_t)qi * SCR_WORDS + sizeof(SelHeader) / 4;
+  const int64_t n4 = (n + 3) >> 2;
+  const int64_t base = ((int64_t)blockIdx.x * SEL_VPT) * FA_THREADS + threadIdx.x;
+  sel_v4f v[SEL_VPT];
+#pragma unroll
+  for (int j = 0; j < SEL_VPT; ++j) {   // requested before the histogram scan: the latency hides under it
+    const int64_t i4 = base + (int64_t)j * FA_THREADS;
+    v[j] = i4 < n4 ? s4[i4] : (sel_v4f){0.f, 0.f, 0.f, 0.f};
+  }
+  uint32_t bstar, krank;
+  pick_bucket<FA_THREADS>(hist, WBINS, k, sh, &bstar, &krank);
+  if (bstar == 0xffffffffu) {  // fewer than k scores inside the window: exact fallback in the final kernel
+    if (blockIdx.x == 0 && threadIdx.x == 0) hdr->flag = 1;
+    return;
+  }
+  filter_compact(v, base, n, (int)bstar, hdr, cand + (int64_t)qi * CAND_CAP);
 }
 
 // Bitonic sort of S[0, m) (m a power of two <= SORT_CAP) in LDS, descending.

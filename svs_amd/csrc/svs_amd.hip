@@ -13,6 +13,7 @@
 #include <condition_variable>
 #include <cstdarg>
 #include <cstdio>
+#include <cstdlib>
 #include <cstring>
 #include <mutex>
 #include <shared_mutex>
@@ -31,6 +32,7 @@
 #include "gemv_f16.h"
 #include "gemv_f32.h"
 #include "select.h"
+#include "screen.h"
 
 namespace {
 
@@ -61,6 +63,7 @@ std::atomic<int64_t> g_tune_prefix_div{64};   // fused path: rows of the thresho
 std::atomic<int64_t> g_tune_upload{0};        // host batches: 0 = f16 batches are PULLED from pinned memory by the staging kernel, chunk by chunk
                                               // (no DMA, no f32 copy in HBM); 1 = round 3's staging + DMA for every dtype
 std::atomic<int64_t> g_tune_spread{1};        // fused path: 1 = thresholds from a sample spread over the whole corpus (prefix_image), 0 = from its first rows (rounds 1-3)
+std::atomic<int64_t> g_tune_refuse_shadow{0}; // 1 = every allocation of an f32 index's half shadow "fails" (tests of the best-effort path)
 thread_local double g_host_phase[6];          // svs_internal_host_phases: seconds since the call began (last svs_index_search on this thread)
 
 // svs_internal_last_launches: the score kernels the calling thread's last search / scores call enqueued, in order.  Fixed
@@ -141,6 +144,7 @@ struct Ctx {
   // last used it; handing it to ANOTHER stream first drains the old one.
   hipStream_t last_stream = nullptr;
   bool async_pending = false;
+  int slot = 0;                 // this context's counters in svs_index::scr_dev / scr_host (screened search)
 };
 
 }  // namespace
@@ -175,6 +179,20 @@ struct svs_index {
   int64_t pfx_n = -1, pfx_nmat = 0, pfx_stride = 0;
   const void* pfx_src = nullptr;       // idx->rows when the image was taken (a reallocation moves the rows)
   std::mutex pfx_mu;
+
+  // Screened single-query search (screen.h): an IEEE-half shadow of an f32 corpus, same capacity and row stride (in
+  // elements) as `rows`, kept in step by every ingest path under the locks those paths hold.  Best effort: an
+  // allocation that fails drops the shadow and the index searches unscreened.
+  void* shadow = nullptr;
+  size_t shadow_bytes = 0;
+  uint32_t* scr_dev = nullptr;         // ScreenStats, then kMaxCtx x SCREEN_SLOT_WORDS per-context counters
+  uint32_t* scr_host = nullptr;        // pinned mirror of the counters, written by the kernels
+  std::atomic<bool> shadow_bad{false}; // an element that half cannot hold: never screens again
+  bool shadow_gave_up = false;         // an allocation failed: not retried until svs_index_set_screen(1)
+  bool stats_dirty = false;            // a staging commit's conversion is still queued (under stg_mu)
+  std::atomic<int> screen_mode{1};     // svs_index_set_screen
+  std::atomic<bool> scr_paused{false}; // fallbacks dominated recent queries: no screening until the next ingest
+  std::atomic<uint64_t> scr_base_s{0}, scr_base_f{0};
 
   std::mutex mu;
   std::condition_variable cv;
@@ -281,9 +299,25 @@ void index_destroy(svs_index* idx) {
   (void)hipFree(idx->row_scales);
   (void)hipFree(idx->pfx_rows);
   (void)hipFree(idx->pfx_scales);
+  (void)hipFree(idx->shadow);
+  (void)hipFree(idx->scr_dev);
+  if (idx->scr_host) (void)hipHostFree(idx->scr_host);
   (void)hipFree(idx->dead_dev);
   (void)hipFree(idx->dead_bits_dev);
   delete idx;
+}
+
+// The shadow's `bad` flag after a staging commit's conversion has drained (caller holds stg_mu, stream synchronised).
+void shadow_refresh_stats(svs_index* idx) {
+  if (!idx->stats_dirty) return;
+  idx->stats_dirty = false;
+  ScreenStats h{};
+  if (idx->scr_dev && hipMemcpy(&h, idx->scr_dev, sizeof h, hipMemcpyDeviceToHost) == hipSuccess) {
+    if (h.bad) idx->shadow_bad.store(true);
+  } else {
+    (void)hipGetLastError();
+    idx->shadow_bad.store(true);   // (unknown statistics: never screen on them)
+  }
 }
 
 // svs_index_staging_commit publishes idx->n while its H2D copy and conversion are still queued on the staging
@@ -292,6 +326,7 @@ int staging_wait(svs_index* idx) {
   if (!idx->staging_pending.load()) return SVS_OK;
   std::lock_guard<std::mutex> lk(idx->stg_mu);
   if (idx->stg.st) HIP_TRY(hipStreamSynchronize(idx->stg.st));
+  shadow_refresh_stats(idx);
   idx->staging_pending.store(false);
   return SVS_OK;
 }
@@ -311,9 +346,10 @@ int ctx_acquire(svs_index* idx, hipStream_t want, bool own_stream, Ctx** out) {
         }
       }
       if (pick < 0 && idx->n_ctx < svs_index::kMaxCtx) {
-        idx->n_ctx++;
+        const int slot = idx->n_ctx++;
         lk.unlock();
         c = new (std::nothrow) Ctx();
+        if (c) c->slot = slot;
         hipError_t e = c ? hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking) : hipErrorOutOfMemory;
         if (e != hipSuccess) {
           ctx_destroy(c);
@@ -414,13 +450,16 @@ void launch_generic(const svs_index* idx, const float* q, float* scores, hipStre
                      (const v4f*)idx->rows, q, scores, idx->n, idx->d, idx->ld / 4);
 }
 
+constexpr int f16_rows_r(int nstep) { return nstep <= 1 ? 4 : (nstep <= 3 ? 2 : 1); }
+constexpr int f16_rows_wpb(int nstep) { return nstep <= 6 ? 16 : 8; }
+// half_rows: the index's own rows (an f16 index) or the half shadow of an f32 index (screened search)
 template <int NSTEP>
-void launch_rows_f16(const svs_index* idx, const float* q, float* scores, hipStream_t st) {
-  constexpr int R = NSTEP <= 1 ? 4 : (NSTEP <= 3 ? 2 : 1), WPB = NSTEP <= 6 ? 16 : 8;
+void launch_rows_f16(const svs_index* idx, const void* half_rows, const float* q, float* scores, hipStream_t st) {
+  constexpr int R = f16_rows_r(NSTEP), WPB = f16_rows_wpb(NSTEP);
   const int64_t rows_per_block = (int64_t)R * WPB;
   const int64_t blocks = (idx->n + rows_per_block - 1) / rows_per_block;
   hipLaunchKernelGGL((gemv_f16_oneshot_kernel<NSTEP, R, WPB>), dim3((unsigned)blocks), dim3(WPB * 64), 0, st,
-                     (const u32x4*)idx->rows, (const v4f*)q, scores, idx->n);
+                     (const u32x4*)half_rows, (const v4f*)q, scores, idx->n);
 }
 
 template <int T>
@@ -550,7 +589,7 @@ int launch_scores(const svs_index* idx, Ctx* c, const float* q, float* scores, h
         qq = c->q16;
       }
       switch (idx->ld / 512) {
-#define SVS_ROWS_CASE(N) case N: launch_rows_f16<N>(idx, qq, scores, st); return SVS_OK;
+#define SVS_ROWS_CASE(N) case N: launch_rows_f16<N>(idx, idx->rows, qq, scores, st); return SVS_OK;
         SVS_ROWS_CASE(1) SVS_ROWS_CASE(2) SVS_ROWS_CASE(3) SVS_ROWS_CASE(4) SVS_ROWS_CASE(5) SVS_ROWS_CASE(6)
         SVS_ROWS_CASE(7) SVS_ROWS_CASE(8)
 #undef SVS_ROWS_CASE
@@ -883,6 +922,103 @@ int run_select(svs_index* idx, Ctx* c, const float* scores, int64_t n_eff, int64
   return SVS_OK;
 }
 
+// ---- screened single-query search over an f32 corpus (screen.h) --------------------------------
+// Rows below which a screened query is not ahead of the plain f32 pass by more than the run-to-run spread (one more
+// launch, the gather; measured with tools/screen_threshold.py, table in DESIGN.md): at 32,768 rows it is 15-22 % ahead
+// for rows of 1536-4096 floats and level (1.02 x) for rows of 512, which are ahead from 65,536 (0.87 x).
+// svs_index_set_variant(12) screens whatever n, 11 never.
+inline int64_t screen_min_rows(int ld) { return ld <= 512 ? 65536 : 32768; }
+constexpr int VARIANT_SCREEN_OFF = 11, VARIANT_SCREEN_FORCE = 12;
+
+template <int NSTEP>
+constexpr KernelName kScreenName = kernel_name("gemv_f16_oneshot_kernel", NSTEP, f16_rows_r(NSTEP), f16_rows_wpb(NSTEP));
+constexpr int rescore_u(int nstep) { return nstep <= 4 ? 4 : (nstep <= 8 ? 2 : 1); }
+template <int NSTEP>
+constexpr KernelName kRescoreName = kernel_name("rescore_f32_kernel", NSTEP, rescore_u(NSTEP));
+
+bool screen_ready(const svs_index* idx) {
+  return idx->dtype == SVS_DTYPE_F32 && idx->shadow && idx->scr_dev && idx->scr_host && idx->screen_mode.load() == 1 &&
+         !idx->shadow_bad.load() && !idx->scr_paused.load();
+}
+
+// Fallbacks (exact, but the screen pass on top of the f32 pass) dominating the recent queries: stop screening until the
+// next ingest.  The counters are written by the re-score kernel into pinned memory; read here without synchronising.
+void screen_review(svs_index* idx) {
+  uint64_t s_tot = 0, f_tot = 0;
+  const volatile uint32_t* h = idx->scr_host;
+  for (int i = 0; i < svs_index::kMaxCtx; ++i) {
+    s_tot += h[i * SCREEN_SLOT_WORDS];
+    f_tot += h[i * SCREEN_SLOT_WORDS + 1];
+  }
+  const uint64_t ds = s_tot - idx->scr_base_s.load(), df = f_tot - idx->scr_base_f.load();
+  if (ds + df < 32) return;
+  if (df > ds) idx->scr_paused.store(true);
+  idx->scr_base_s.store(s_tot);
+  idx->scr_base_f.store(f_tot);
+}
+
+thread_local const svs_index* g_screen_idx;   // svs_internal_screen_stats: the calling thread's last screened search
+thread_local int g_screen_slot;
+
+// The query as the single-query kernels read it: ld floats, 16-byte aligned (rows padded beyond d: zero padded)
+int pad_query(const svs_index* idx, Ctx* c, const float* q, const float** out, hipStream_t st) {
+  *out = q;
+  if (idx->ld == idx->d && (((uintptr_t)q) & 15) == 0) return SVS_OK;
+  int rc = grow_dev(&c->q16, &c->q16_cap, (size_t)GQ * idx->ld);
+  if (rc != SVS_OK) return rc;
+  HIP_TRY(hipMemsetAsync(c->q16, 0, (size_t)idx->ld * sizeof(float), st));
+  HIP_TRY(hipMemcpyAsync(c->q16, q, (size_t)idx->d * sizeof(float), hipMemcpyDeviceToDevice, st));
+  *out = c->q16;
+  return SVS_OK;
+}
+
+// step 1: approximate scores of the whole corpus from the half shadow
+int launch_screen_scores(const svs_index* idx, Ctx* c, const float* q, float* scores, const float** q_padded, hipStream_t st) {
+  int rc = pad_query(idx, c, q, q_padded, st);
+  if (rc != SVS_OK) return rc;
+  switch (idx->ld / 512) {
+#define SVS_ROWS_CASE(N) case N: launch_record(kScreenName<N>.s, idx->n, 1); launch_rows_f16<N>(idx, idx->shadow, *q_padded, scores, st); return SVS_OK;
+    SVS_ROWS_CASE(1) SVS_ROWS_CASE(2) SVS_ROWS_CASE(3) SVS_ROWS_CASE(4) SVS_ROWS_CASE(5) SVS_ROWS_CASE(6)
+    SVS_ROWS_CASE(7) SVS_ROWS_CASE(8)
+#undef SVS_ROWS_CASE
+    default: break;
+  }
+  return fail(SVS_ERR_INVALID, "internal: no screen kernel for ld %d", idx->ld);
+}
+
+// steps 2-5: histogram, filter with margin, exact re-score of the candidates, final top-k
+int run_select_screened(svs_index* idx, Ctx* c, const float* q_padded, int k, int count, float* out_s, int64_t* out_r,
+                        hipStream_t st) {
+  const int64_t n = idx->n, sstride = (n + 3) & ~(int64_t)3;
+  const int64_t per_block = (int64_t)FA_THREADS * SEL_VPT * 4;
+  const unsigned blocks = (unsigned)((n + per_block - 1) / per_block);
+  uint32_t* cnt_dev = idx->scr_dev + sizeof(ScreenStats) / 4 + (size_t)c->slot * SCREEN_SLOT_WORDS;
+  uint32_t* slot_host = idx->scr_host + (size_t)c->slot * SCREEN_SLOT_WORDS;
+  g_screen_idx = idx;
+  g_screen_slot = c->slot;
+  hipLaunchKernelGGL(select_window_hist_kernel, dim3(blocks, 1), dim3(FA_THREADS), 0, st, (const float*)c->scores, n, sstride, c->hist);
+  hipLaunchKernelGGL(screen_filter_kernel, dim3(blocks), dim3(FA_THREADS), 0, st, (const float*)c->scores, n, (uint32_t)count,
+                     c->hist, c->cand, q_padded, idx->ld, (const ScreenStats*)idx->scr_dev, slot_host);
+  const uint32_t* dead_bits = idx->dead_list.empty() ? nullptr : idx->dead_bits_dev;
+  const int rblocks = idx->cu_count * 4;
+  switch (idx->ld / 256) {
+#define SVS_RESCORE_CASE(N)                                                                                          \
+  case N:                                                                                                            \
+    launch_record(kRescoreName<N>.s, n, 1);                                                                          \
+    hipLaunchKernelGGL((rescore_f32_kernel<N, rescore_u(N)>), dim3(rblocks), dim3(256), 0, st, (const v4f*)idx->rows, \
+                       (const v4f*)q_padded, c->scores, n, (const uint32_t*)c->hist, c->cand, dead_bits, cnt_dev,     \
+                       slot_host);                                                                                   \
+    break;
+    SVS_RESCORE_CASE(2) SVS_RESCORE_CASE(4) SVS_RESCORE_CASE(6) SVS_RESCORE_CASE(8) SVS_RESCORE_CASE(10)
+    SVS_RESCORE_CASE(12) SVS_RESCORE_CASE(14) SVS_RESCORE_CASE(16)
+#undef SVS_RESCORE_CASE
+    default: return fail(SVS_ERR_INVALID, "internal: no re-score kernel for ld %d", idx->ld);
+  }
+  hipLaunchKernelGGL(select_final_kernel, dim3(1), dim3(FINAL_THREADS), 0, st, (const float*)c->scores, n, sstride, k, count, 0,
+                     c->hist, c->cand, idx->row_offset, out_s, out_r, (const uint32_t*)nullptr);
+  return SVS_OK;
+}
+
 // ---- filtered search: scores of nq queries over a row list (gather.h) ---------------------------
 template <int DT, int T, int NC, int U, int G>
 constexpr KernelName kGatherName = kernel_name("gather_scores_kernel", DT, T, NC, U, G);
@@ -1061,6 +1197,7 @@ int prefix_image(svs_index* idx, int64_t n_mat, hipStream_t st) {
 struct SearchPlan {
   int nq = 0, k = 0, count = 0;
   bool path_a = false, fused = false, kth = false, timed = false;
+  bool screen = false;   // one query over an f32 index with a valid half shadow: screen.h
   bool staged = false;   // the caller has staged the queries in the corpus dtype already (search_host, chunk by chunk)
   int64_t n_mat = 0, sstride = 0;
   EvTriple ev{};
@@ -1095,6 +1232,15 @@ int plan_search(svs_index* idx, Ctx* c, int nq, int k, int count, hipStream_t st
   p->fused = allow_fused && p->path_a && batched && nq >= 16 &&
              n >= 8 * FUSE_PREFIX_MIN && (int64_t)n < ((int64_t)1 << 32) &&
              count <= 256 && idx->variant.load() != 6;
+  {
+    const int variant = idx->variant.load();
+    p->screen = nq == 1 && p->path_a && screen_ready(idx) &&
+                variant != VARIANT_SCREEN_OFF && (variant == VARIANT_SCREEN_FORCE || (variant == 0 && n >= screen_min_rows(idx->ld)));
+    if (p->screen) {
+      screen_review(idx);
+      p->screen = !idx->scr_paused.load();
+    }
+  }
   p->n_mat = p->fused ? fuse_prefix_rows(n) : n;       // rows of the materialised score matrix
   p->sstride = (p->n_mat + 3) & ~(int64_t)3;           // float4-aligned score vectors
   // thresholds: many queries over a short prefix -> one k-th-value kernel (47 vs 62 us at 1024 x 16,384);
@@ -1161,12 +1307,21 @@ int enqueue_main(svs_index* idx, Ctx* c, SearchPlan& p, const float* q_dev, floa
                        c->hist, c->cand, idx->row_offset, out_s, out_r,
                        (const uint32_t*)(idx->dead_list.empty() ? nullptr : idx->dead_bits_dev));
   } else {
-    if ((rc = launch_scores_any(idx, c, q_dev, n, nq, c->scores, p.sstride, FuseLaunch{}, st, !p.staged)) != SVS_OK) return rc;
+    const float* q_padded = nullptr;
+    if (p.screen) {
+      if ((rc = launch_screen_scores(idx, c, q_dev, c->scores, &q_padded, st)) != SVS_OK) return rc;
+    } else if ((rc = launch_scores_any(idx, c, q_dev, n, nq, c->scores, p.sstride, FuseLaunch{}, st, !p.staged)) != SVS_OK) {
+      return rc;
+    }
     if (!idx->dead_list.empty())   // tombstoned rows can never be returned
       hipLaunchKernelGGL(mask_dead_rows_kernel, dim3(64), dim3(256), 0, st, c->scores, p.sstride, nq, idx->dead_dev,
                          (int64_t)idx->dead_list.size(), n, (int64_t)0);
     if (p.timed) HIP_TRY(hipEventRecord(ev.e1, st));
-    if (k > 0 && (rc = run_select(idx, c, c->scores, n, p.sstride, nq, k, count, out_s, out_r, st, idx->row_offset)) != SVS_OK) return rc;
+    if (p.screen) {   // (stage_ms.score is the screen pass; the exact re-score of the candidates counts as select)
+      if ((rc = run_select_screened(idx, c, q_padded, k, count, out_s, out_r, st)) != SVS_OK) return rc;
+    } else if (k > 0 && (rc = run_select(idx, c, c->scores, n, p.sstride, nq, k, count, out_s, out_r, st, idx->row_offset)) != SVS_OK) {
+      return rc;
+    }
   }
   HIP_TRY(hipGetLastError());
   if (p.timed) {
@@ -1448,6 +1603,87 @@ int choose_ld(int d, int dtype) {
   return tight;
 }
 
+// ---- the half shadow of an f32 corpus (screen.h): ingest side ----------------------------------
+bool shadow_eligible(const svs_index* idx) {
+  return idx->dtype == SVS_DTYPE_F32 && idx->d > 0 && idx->ld % 512 == 0 && idx->ld <= 4096 &&
+         choose_ld(idx->d, SVS_DTYPE_F16) == idx->ld;   // a hot geometry of the f16 one-shot kernel, same stride as the f32 rows
+}
+
+void shadow_free(svs_index* idx) {
+  (void)hipFree(idx->shadow);
+  idx->shadow = nullptr;
+  idx->shadow_bytes = 0;
+}
+
+// Best effort: false (and no shadow) when HBM is short.  Never leaves a HIP error behind.
+bool shadow_alloc(svs_index* idx, int64_t rows_cap, void** out) {
+  *out = nullptr;
+  if (g_tune_refuse_shadow.load() || rows_cap <= 0) return false;
+  if (!idx->scr_dev) {
+    const size_t words = sizeof(ScreenStats) / 4 + (size_t)svs_index::kMaxCtx * SCREEN_SLOT_WORDS;
+    if (hipMalloc((void**)&idx->scr_dev, words * 4) != hipSuccess || hipMemset(idx->scr_dev, 0, words * 4) != hipSuccess) {
+      (void)hipGetLastError();
+      (void)hipFree(idx->scr_dev);
+      idx->scr_dev = nullptr;
+      return false;
+    }
+  }
+  if (!idx->scr_host) {
+    const size_t bytes = (size_t)svs_index::kMaxCtx * SCREEN_SLOT_WORDS * 4;
+    if (hipHostMalloc((void**)&idx->scr_host, bytes, hipHostMallocDefault) != hipSuccess) {
+      (void)hipGetLastError();
+      idx->scr_host = nullptr;
+      return false;
+    }
+    memset(idx->scr_host, 0, bytes);
+  }
+  if (hipMalloc(out, (size_t)rows_cap * idx->ld * sizeof(_Float16)) != hipSuccess) {
+    (void)hipGetLastError();
+    *out = nullptr;
+    return false;
+  }
+  return true;
+}
+
+// Rows [row0, row0 + nrows) of idx->rows were written (or are being written, in order, on `st`): convert them into
+// the shadow on `st`.  A handle that has no shadow yet (created empty, or after set_screen(1)) gets one over all
+// n_total rows.  sync: wait for the conversion and read the `bad` flag back (every ingest path but the staging commit,
+// whose flag is read when the staging stream is next drained).  Caller holds the geometry lock exclusively.
+void shadow_ingest(svs_index* idx, int64_t row0, int64_t nrows, int64_t n_total, hipStream_t st, bool sync) {
+  idx->scr_paused.store(false);   // new rows: whatever made the fallbacks dominate may be gone
+  if (!shadow_eligible(idx) || idx->screen_mode.load() != 1 || idx->shadow_bad.load() || idx->shadow_gave_up) return;
+  if (!idx->shadow) {
+    void* sh = nullptr;
+    if (!shadow_alloc(idx, std::max(idx->cap, n_total), &sh)) {
+      idx->shadow_gave_up = true;
+      return;
+    }
+    idx->shadow = sh;
+    idx->shadow_bytes = (size_t)std::max(idx->cap, n_total) * idx->ld * sizeof(_Float16);
+    if (hipMemsetAsync(idx->scr_dev, 0, sizeof(ScreenStats), st) != hipSuccess) (void)hipGetLastError();
+    row0 = 0;
+    nrows = n_total;
+  }
+  if (nrows <= 0) return;
+  const int blocks = (int)std::min<int64_t>((nrows + 3) / 4, (int64_t)idx->cu_count * 8);
+  hipLaunchKernelGGL(shadow_rows_kernel, dim3(blocks), dim3(256), 0, st, (const v4f*)idx->rows, row0, nrows, idx->ld / 4,
+                     (uint2*)idx->shadow, (ScreenStats*)idx->scr_dev);
+  hipError_t e = hipGetLastError();
+  if (e == hipSuccess && sync) {
+    ScreenStats h{};
+    e = hipMemcpyAsync(&h, idx->scr_dev, sizeof h, hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess) e = hipStreamSynchronize(st);
+    if (e == hipSuccess && h.bad) idx->shadow_bad.store(true);
+  } else if (e == hipSuccess) {
+    idx->stats_dirty = true;
+  }
+  if (e != hipSuccess) {   // never a new failure: search unscreened
+    (void)hipGetLastError();
+    idx->shadow_bad.store(true);
+  }
+  if (idx->shadow_bad.load() && sync) shadow_free(idx);   // (nothing reads a shadow that never screens)
+}
+
 // Device rows [0, nrows) (f32, stride src_ld) -> HBM rows [row0, row0 + nrows) of the index's layout.
 hipError_t copy_device_rows(svs_index* idx, const float* dev_rows, int64_t nrows, int64_t src_ld, int64_t row0) {
   const int d = idx->d;
@@ -1522,6 +1758,22 @@ int ensure_capacity(svs_index* idx, int64_t rows, bool exact) {
   (void)hipFree(idx->row_scales);
   idx->rows = nrows;
   idx->row_scales = nscales;
+  if (idx->shadow) {   // grows with the rows; if there is no room for it the index carries on without
+    void* nsh = nullptr;
+    bool ok = shadow_alloc(idx, new_cap, &nsh);
+    if (ok && n_old && hipMemcpy(nsh, idx->shadow, (size_t)n_old * idx->ld * sizeof(_Float16), hipMemcpyDeviceToDevice) != hipSuccess) {
+      (void)hipGetLastError();
+      (void)hipFree(nsh);
+      ok = false;
+    }
+    shadow_free(idx);
+    if (ok) {
+      idx->shadow = nsh;
+      idx->shadow_bytes = (size_t)new_cap * idx->ld * sizeof(_Float16);
+    } else {
+      idx->shadow_gave_up = true;
+    }
+  }
   idx->cap = new_cap;
   idx->bytes = (size_t)new_cap * row_b + (idx->dtype == SVS_DTYPE_FP8 ? (size_t)new_cap * sizeof(float) : 0);
   return SVS_OK;
@@ -1568,6 +1820,7 @@ int create_common(int64_t n, int32_t d, int32_t store_dtype, int32_t device, int
     }
   }
   idx->dead_flag.assign((size_t)n, 0);
+  if (const char* env = getenv("SVS_AMD_SCREEN")) idx->screen_mode.store(atoi(env) != 0 ? 1 : 0);
   *made = idx;
   return SVS_OK;
 }
@@ -1612,6 +1865,7 @@ int32_t svs_index_create(const float* host_rows, int64_t n, int32_t d, int32_t s
       index_destroy(idx);
       return fail(SVS_ERR_DEVICE, "corpus upload: %s", hipGetErrorString(e));
     }
+    shadow_ingest(idx, 0, n, n, nullptr, true);
   }
   *out = idx;
   return SVS_OK;
@@ -1633,6 +1887,7 @@ int32_t svs_index_create_from_device(const float* dev_rows, int64_t n, int32_t d
       index_destroy(idx);
       return fail(SVS_ERR_DEVICE, "device corpus copy: %s", hipGetErrorString(e));
     }
+    shadow_ingest(idx, 0, n, n, nullptr, true);
   }
   *out = idx;
   return SVS_OK;
@@ -1651,6 +1906,7 @@ int32_t svs_index_append(svs_index* idx, const float* host_rows, int64_t n_new) 
   if (rc != SVS_OK) return rc;
   hipError_t e = upload_host_rows(idx, host_rows, n_new, n_old);
   if (e != hipSuccess) return fail(SVS_ERR_DEVICE, "append upload: %s", hipGetErrorString(e));
+  shadow_ingest(idx, n_old, n_new, n_tot, nullptr, true);
   idx->n = n_tot;
   idx->dead_flag.resize((size_t)n_tot, 0);
   return sync_dead_bits(idx);
@@ -1677,6 +1933,7 @@ int32_t svs_index_append_from_device(svs_index* idx, const float* dev_rows, int6
   if (rc != SVS_OK) return rc;
   hipError_t e = copy_device_rows(idx, dev_rows, n_new, src_ld, n_old);
   if (e != hipSuccess) return fail(SVS_ERR_DEVICE, "device append: %s", hipGetErrorString(e));
+  shadow_ingest(idx, n_old, n_new, n_tot, nullptr, true);
   idx->n = n_tot;
   idx->dead_flag.resize((size_t)n_tot, 0);
   return sync_dead_bits(idx);
@@ -1748,6 +2005,7 @@ int32_t svs_index_staging_commit(svs_index* idx, int64_t n_rows) {
                          (uint8_t*)idx->rows + (size_t)n_old * idx->ld, idx->ld, idx->row_scales + n_old, (float*)nullptr);
     HIP_TRY(hipGetLastError());
   }
+  shadow_ingest(idx, n_old, n_rows, n_tot, g.st, false);   // (on the staging stream, behind the DMA it reads)
   HIP_TRY(hipEventRecord(g.done[b], g.st));
   idx->staging_pending.store(true);
   idx->n = n_tot;
@@ -1760,6 +2018,7 @@ int32_t svs_index_staging_finish(svs_index* idx) {
   HIP_TRY(hipSetDevice(idx->device));
   std::lock_guard<std::mutex> lk(idx->stg_mu);
   if (idx->stg.st) HIP_TRY(hipStreamSynchronize(idx->stg.st));
+  shadow_refresh_stats(idx);
   staging_free(idx);
   return SVS_OK;
 }
@@ -1820,7 +2079,7 @@ int32_t svs_index_info(const svs_index* idx, svs_index_info_t* out) {
   out->dtype = idx->dtype;
   out->device = idx->device;
   out->row_offset = idx->row_offset;
-  out->hbm_bytes = (int64_t)idx->bytes;
+  out->hbm_bytes = (int64_t)(idx->bytes + idx->shadow_bytes);
   out->n_masked = (int64_t)idx->dead_list.size();
   return SVS_OK;
 }
@@ -2403,6 +2662,7 @@ int32_t svs_internal_tune(int32_t what, int64_t value) {
     case 0: if (value < 1) break; g_tune_prefix_div.store(value); return SVS_OK;
     case 1: if (value < 0 || value > 1) break; g_tune_upload.store(value); return SVS_OK;
     case 2: if (value < 0 || value > 1) break; g_tune_spread.store(value); return SVS_OK;
+    case 3: if (value < 0 || value > 1) break; g_tune_refuse_shadow.store(value); return SVS_OK;
     default: break;
   }
   return fail(SVS_ERR_INVALID, "svs_internal_tune(%d, %lld): unknown knob or value", what, (long long)value);
@@ -2422,9 +2682,54 @@ int32_t svs_internal_last_launches(const char** kernels, int64_t* rows, int32_t*
   return g_nlaunch;
 }
 
+int32_t svs_index_set_screen(svs_index* idx, int32_t mode) {
+  if (!idx) return fail(SVS_ERR_INVALID, "null index");
+  if (mode != 0 && mode != 1) return fail(SVS_ERR_INVALID, "svs_index_set_screen: mode %d (0 = off, 1 = automatic)", mode);
+  RefGuard guard(idx);
+  std::unique_lock<std::shared_mutex> geo(idx->rw);
+  HIP_TRY(hipSetDevice(idx->device));
+  int rc = staging_wait(idx);
+  if (rc != SVS_OK) return rc;
+  idx->screen_mode.store(mode);
+  if (mode == 0) {
+    HIP_TRY(hipDeviceSynchronize());   // searches enqueued by the device API may still read the shadow
+    shadow_free(idx);
+    return SVS_OK;
+  }
+  idx->shadow_gave_up = false;
+  if (!idx->shadow && idx->n > 0) shadow_ingest(idx, 0, idx->n, idx->n, nullptr, true);
+  return SVS_OK;
+}
+
+int32_t svs_internal_screen_stats(svs_index* idx, int64_t* out, int32_t cap) {
+  if (!idx || !out) return fail(SVS_ERR_INVALID, "null argument");
+  int64_t v[9] = {};
+  if (idx->scr_host) {
+    const volatile uint32_t* h = idx->scr_host;
+    for (int i = 0; i < svs_index::kMaxCtx; ++i) {
+      v[0] += h[i * SCREEN_SLOT_WORDS];
+      v[1] += h[i * SCREEN_SLOT_WORDS + 1];
+    }
+    if (g_screen_idx == idx) {
+      v[4] = h[g_screen_slot * SCREEN_SLOT_WORDS + 2];
+      v[5] = h[g_screen_slot * SCREEN_SLOT_WORDS + 3];
+    }
+  }
+  v[2] = idx->shadow_bad.load() ? 2 : (idx->shadow ? 1 : 0);
+  v[3] = idx->scr_paused.load() ? 1 : 0;
+  if (idx->scr_dev && idx->shadow) {
+    HIP_TRY(hipSetDevice(idx->device));
+    ScreenStats h{};
+    HIP_TRY(hipMemcpy(&h, idx->scr_dev, sizeof h, hipMemcpyDeviceToHost));
+    v[6] = h.A; v[7] = h.B; v[8] = h.C;
+  }
+  for (int i = 0; i < cap && i < 9; ++i) out[i] = v[i];
+  return SVS_OK;
+}
+
 int32_t svs_index_set_variant(svs_index* idx, int32_t variant) {
   if (!idx) return fail(SVS_ERR_INVALID, "null index");
-  if (variant < 0 || variant > 10) return fail(SVS_ERR_INVALID, "unknown variant %d", variant);
+  if (variant < 0 || variant > 12) return fail(SVS_ERR_INVALID, "unknown variant %d", variant);
   idx->variant.store(variant);
   return SVS_OK;
 }

@@ -372,3 +372,17 @@ class DeviceIndex:
 
     def set_variant(self, variant: int) -> None:
         _native.check(self._lib.svs_index_set_variant(self._handle(), int(variant)))
+
+    def set_screen(self, mode: int) -> None:
+        """0: free the half shadow of an f32 index, every search reads the f32 rows; 1 (the default): keep it
+        (+50 % HBM) and screen single queries on it -- same rows, order and score bits (svs_index_set_screen)."""
+        _native.check(self._lib.svs_index_set_screen(self._handle(), int(mode)))
+        self._refresh()
+
+    def screen_stats(self) -> dict:
+        """Counters and state of the screened search (svs_internal_screen_stats; tests).  Drain the stream first."""
+        out = (C.c_int64 * 9)()
+        _native.check(self._lib.svs_internal_screen_stats(self._handle(), out, 9))
+        f = lambda b: float(np.array([b], dtype=np.uint32).view(np.float32)[0])
+        return {"screened": int(out[0]), "fallback": int(out[1]), "shadow": int(out[2]), "paused": bool(out[3]),
+                "E": f(out[4]), "n_cand": int(out[5]), "A": f(out[6]), "B": f(out[7]), "C": f(out[8])}
