@@ -3,6 +3,7 @@
 // scratch, so searches are re-entrant), launch sequencing of the score stage
 // (gemv_f32.h) and the top-k stage (select.h).  gfx950 only.
 #include "../../include/svs_amd.h"
+#include "coalesce.h"
 #include "internal.h"
 
 #include <hip/hip_runtime.h>
@@ -57,6 +58,37 @@ int fail(int code, const char* fmt, ...) {
       return fail(e_ == hipErrorOutOfMemory ? SVS_ERR_NOMEM : SVS_ERR_DEVICE, "%s: %s (%s:%d)", \
                   #expr, hipGetErrorString(e_), __FILE__, __LINE__);                        \
   } while (0)
+
+// Scratch that frees itself: pointer + capacity (in elements), device memory or pinned host memory.  grow(need) does
+// nothing when `need` fits; otherwise it frees, then allocates: the old contents are NOT kept, and the capacity is 0
+// after a failed allocation.
+template <typename T, bool PINNED>
+struct Buf {
+  T* p = nullptr;
+  size_t cap = 0;
+  Buf() = default;
+  Buf(const Buf&) = delete;
+  Buf& operator=(const Buf&) = delete;
+  ~Buf() { (void)release(); }
+  operator T*() const { return p; }
+  hipError_t release() {
+    hipError_t e = hipSuccess;
+    if (p) e = PINNED ? hipHostFree(p) : hipFree(p);
+    p = nullptr;
+    cap = 0;
+    return e;
+  }
+  int grow(size_t need) {
+    if (need <= cap) return SVS_OK;
+    HIP_TRY(release());
+    if constexpr (PINNED) HIP_TRY(hipHostMalloc((void**)&p, need * sizeof(T), hipHostMallocDefault));
+    else HIP_TRY(hipMalloc((void**)&p, need * sizeof(T)));
+    cap = need;
+    return SVS_OK;
+  }
+};
+template <typename T> using DevBuf = Buf<T, false>;
+template <typename T> using PinBuf = Buf<T, true>;
 
 // ---- internal tunables (svs_internal_tune: tools and tests; not part of the ABI) --------------------
 std::atomic<int64_t> g_tune_prefix_div{64};   // fused path: rows of the threshold prefix = n / this (>= FUSE_PREFIX_MIN)
@@ -117,29 +149,37 @@ struct EvTriple {
   hipEvent_t e0, e1, e2;
   hipEvent_t d0 = nullptr, d1 = nullptr;   // around the dominant kernel of a fused search (else unset)
 };
+void ev_destroy(EvTriple& t) {
+  (void)hipEventDestroy(t.e0);
+  (void)hipEventDestroy(t.e1);
+  (void)hipEventDestroy(t.e2);
+  if (t.d0) (void)hipEventDestroy(t.d0);
+  if (t.d1) (void)hipEventDestroy(t.d1);
+}
 
 // One in-flight search: stream, device scratch, pinned staging.
 struct Ctx {
   hipStream_t stream = nullptr;
-  float* q_dev = nullptr;       size_t q_cap = 0;        // floats
-  float* q16 = nullptr;         size_t q16_cap = 0;      // [16][ld] zero-padded query group
-  _Float16* qh = nullptr;       size_t qh_cap = 0;       // half queries, [rows][ld] zero padded
-  uint8_t* q8 = nullptr;        size_t q8_cap = 0;       // e4m3 queries [rows][ld], zero padded
-  float* q8f = nullptr;         size_t q8f_cap = 0;      // the same values as f32 (single-query kernel)
-  float* q8s = nullptr;         size_t q8s_cap = 0;      // query scales
-  const float* q_f32 = nullptr;                          // staged f32 queries (q16 or the caller's buffer)
-  float* pref_s = nullptr;      size_t pref_s_cap = 0;   // fused GEMM: top-k of the prefix rows (thresholds)
-  int64_t* pref_r = nullptr;    size_t pref_r_cap = 0;
-  float* scores = nullptr;      size_t scores_cap = 0;   // floats
-  uint32_t* hist = nullptr;     size_t hist_cap = 0;     // queries
-  uint64_t* cand = nullptr;                               // counters live behind hist
-  uint64_t* keys = nullptr;     size_t keys_cap = 0;     // u64
-  float* q_pin = nullptr;       size_t q_pin_cap = 0;
-  float* out_s_pin = nullptr;   int64_t* out_r_pin = nullptr; size_t out_pin_cap = 0;
-  float* redo_s_pin = nullptr;  int64_t* redo_r_pin = nullptr; size_t redo_pin_cap = 0;   // results of re-run queries (search_host)
-  float* redo_q_pin = nullptr;  size_t redo_q_cap = 0;                                      // ... and the queries themselves, gathered
-  uint32_t* list_dev = nullptr; size_t list_cap = 0;     // svs_index_search_rows: the listed local rows (u32)
-  uint32_t* list_pin = nullptr; size_t list_pin_cap = 0; // ... built here, uploaded from here
+  DevBuf<float> q_dev;
+  DevBuf<float> q16;            // [16][ld] zero-padded query group
+  DevBuf<_Float16> qh;          // half queries, [rows][ld] zero padded
+  DevBuf<uint8_t> q8;           // e4m3 queries [rows][ld], zero padded
+  DevBuf<float> q8f;            // the same values as f32 (single-query kernel)
+  DevBuf<float> q8s;            // query scales
+  const float* q_f32 = nullptr; // staged f32 queries (q16 or the caller's buffer)
+  DevBuf<float> pref_s;         // fused GEMM: top-k of the prefix rows (thresholds)
+  DevBuf<int64_t> pref_r;
+  DevBuf<float> scores;
+  DevBuf<uint32_t> hist;        // histogram and candidate counters, then the candidate lists: one capacity, allocated,
+  DevBuf<uint64_t> cand;        // zeroed and released together (grow_select_scratch)
+  size_t hist_cap = 0;          // queries
+  DevBuf<uint64_t> keys;
+  PinBuf<float> q_pin;
+  PinBuf<float> out_s_pin;      PinBuf<int64_t> out_r_pin;
+  PinBuf<float> redo_s_pin;     PinBuf<int64_t> redo_r_pin;   // results of re-run queries (search_host)
+  PinBuf<float> redo_q_pin;                                    // ... and the queries themselves, gathered
+  DevBuf<uint32_t> list_dev;    // svs_index_search_rows: the listed local rows (u32)
+  PinBuf<uint32_t> list_pin;    // ... built here, uploaded from here
   // Scratch is reused in stream order.  A context stays with the stream that
   // last used it; handing it to ANOTHER stream first drains the old one.
   hipStream_t last_stream = nullptr;
@@ -164,11 +204,9 @@ struct svs_index {
   std::shared_mutex rw;
   std::vector<uint8_t> dead_flag;      // host, one per row
   std::vector<uint32_t> dead_list;     // host copy of the masked (tombstoned) local rows
-  uint32_t* dead_dev = nullptr;        // device copy
-  size_t dead_dev_cap = 0;
+  DevBuf<uint32_t> dead_dev;           // device copy
   std::vector<uint32_t> dead_bits;     // host bitmap, one bit per row (bit r & 31 of word r >> 5)
-  uint32_t* dead_bits_dev = nullptr;   // device copy: the fused top-k path drops masked candidates with it
-  size_t dead_bits_cap = 0;            // words
+  DevBuf<uint32_t> dead_bits_dev;      // device copy (capacity in words): the fused top-k path drops masked candidates with it
   int cu_count = 256;
   // The fused batch path's threshold sample ("prefix image", prefix_image()): pfx_nmat rows copied out of the corpus in
   // blocks of PFX_BLOCK rows taken every pfx_stride rows, as one contiguous matrix the batched kernels can run over.
@@ -214,24 +252,9 @@ struct svs_index {
   std::atomic<bool> staging_pending{false};
 
   // svs_index_set_coalesce: single-query host searches that are in flight together share corpus passes
-  struct Waiter {
-    const float* q;
-    int k, count = 0, rc = SVS_OK;
-    float* out_s;
-    int64_t* out_r;
-    std::string err;
-    bool done = false, lead = false;
-    std::condition_variable cv;
-  };
   std::atomic<bool> coalesce{false};
   std::atomic<bool> co_round{true};
-  std::atomic<int64_t> co_sizes[257] = {};   // co_sizes[s]: passes that carried s queries
-  int co_hold = 0;                           // svs_index_coalesce_hold: the next pass waits for this many queued callers (under co_mu)
-  std::condition_variable co_hold_cv;
-  std::mutex co_mu;
-  std::vector<Waiter*> co_pending;
-  bool co_busy = false;
-  std::atomic<int64_t> co_passes{0}, co_queries{0};
+  svs::Coalescer co;
 
   std::atomic<int> timing{0};          // 0 off, N: time every N-th search
   std::atomic<uint32_t> timing_seq{0};
@@ -245,28 +268,9 @@ void ctx_destroy(Ctx* c) {
   if (!c) return;
   if (c->async_pending) (void)hipStreamSynchronize(c->last_stream);
   if (c->stream) (void)hipStreamSynchronize(c->stream);
-  (void)hipFree(c->q_dev);
-  (void)hipFree(c->q16);
-  (void)hipFree(c->qh);
-  (void)hipFree(c->q8);
-  (void)hipFree(c->q8f);
-  (void)hipFree(c->q8s);
-  (void)hipFree(c->pref_s);
-  (void)hipFree(c->pref_r);
-  if (c->redo_q_pin) (void)hipHostFree(c->redo_q_pin);
-  if (c->redo_s_pin) (void)hipHostFree(c->redo_s_pin);
-  if (c->redo_r_pin) (void)hipHostFree(c->redo_r_pin);
-  (void)hipFree(c->scores);
-  (void)hipFree(c->hist);
-  (void)hipFree(c->cand);
-  (void)hipFree(c->keys);
-  (void)hipFree(c->list_dev);
-  if (c->list_pin) (void)hipHostFree(c->list_pin);
-  (void)hipHostFree(c->q_pin);
-  (void)hipHostFree(c->out_s_pin);
-  (void)hipHostFree(c->out_r_pin);
-  if (c->stream) (void)hipStreamDestroy(c->stream);
-  delete c;
+  hipStream_t st = c->stream;
+  delete c;   // (frees every buffer)
+  if (st) (void)hipStreamDestroy(st);
 }
 
 void staging_free(svs_index* idx) {
@@ -288,13 +292,7 @@ void index_destroy(svs_index* idx) {
   (void)hipSetDevice(idx->device);
   staging_free(idx);
   for (Ctx* c : idx->free_ctx) ctx_destroy(c);
-  for (auto& t : idx->evs) {
-    (void)hipEventDestroy(t.e0);
-    (void)hipEventDestroy(t.e1);
-    (void)hipEventDestroy(t.e2);
-    if (t.d0) (void)hipEventDestroy(t.d0);
-    if (t.d1) (void)hipEventDestroy(t.d1);
-  }
+  for (auto& t : idx->evs) ev_destroy(t);
   (void)hipFree(idx->rows);
   (void)hipFree(idx->row_scales);
   (void)hipFree(idx->pfx_rows);
@@ -302,9 +300,7 @@ void index_destroy(svs_index* idx) {
   (void)hipFree(idx->shadow);
   (void)hipFree(idx->scr_dev);
   if (idx->scr_host) (void)hipHostFree(idx->scr_host);
-  (void)hipFree(idx->dead_dev);
-  (void)hipFree(idx->dead_bits_dev);
-  delete idx;
+  delete idx;   // (and its owned buffers)
 }
 
 // The shadow's `bad` flag after a staging commit's conversion has drained (caller holds stg_mu, stream synchronised).
@@ -386,23 +382,103 @@ void ctx_release(svs_index* idx, Ctx* c) {
   idx->cv.notify_one();
 }
 
-template <typename T>
-int grow_dev(T** p, size_t* cap, size_t need) {
-  if (need <= *cap) return SVS_OK;
-  if (*p) HIP_TRY(hipFree(*p));
-  *p = nullptr;
-  *cap = 0;
-  HIP_TRY(hipMalloc((void**)p, need * sizeof(T)));
-  *cap = need;
-  return SVS_OK;
-}
-
-int next_pow2_i64(int64_t v, int64_t* out) {
+int64_t next_pow2_i64(int64_t v) {
   int64_t p = 2;
   while (p < v) p <<= 1;
-  *out = p;
-  return 0;
+  return p;
 }
+
+constexpr size_t dtype_bytes(int dtype) { return dtype == SVS_DTYPE_F32 ? 4 : (dtype == SVS_DTYPE_F16 ? 2 : 1); }
+size_t elem_bytes(const svs_index* idx) { return dtype_bytes(idx->dtype); }
+
+// ---- launch rules that several kernel families share ---------------------------------------------------
+template <int N>
+using Int = std::integral_constant<int, N>;
+
+// f(std::true_type) or f(std::false_type): a run-time flag as a template argument (`flag()` is a constant in f)
+template <class F>
+auto with_bool(bool flag, F&& f) {
+  return flag ? f(std::true_type{}) : f(std::false_type{});
+}
+
+// f(Int<T>): the lanes that share a row of `units` 16-byte (generic kernels: their own) units -- the smallest
+// power of two that covers it, 64 (a whole wave, looping) beyond
+template <class F>
+void for_width(int units, F&& f) {
+  if (units <= 1) f(Int<1>{});
+  else if (units <= 2) f(Int<2>{});
+  else if (units <= 4) f(Int<4>{});
+  else if (units <= 8) f(Int<8>{});
+  else if (units <= 16) f(Int<16>{});
+  else if (units <= 32) f(Int<32>{});
+  else f(Int<64>{});
+}
+
+// f(Int<T>, Int<NC>): the row geometry of the kernels that hold a whole row of ld16 16-byte units in registers
+// (gemv_unrolled.h, gather.h) -- T lanes per row up to 1 KiB, then a wave per row at NC KiB-chunks per lane.
+// false: rows longer than 16 KiB.  Rows per lane group (U) differ by family: unrolled_u / gather_u.
+template <class F>
+bool for_row_geometry(int ld16, F&& f) {
+  if (ld16 <= 64) for_width(ld16, [&](auto t) { f(t, Int<1>{}); });
+  else if (ld16 <= 128) f(Int<64>{}, Int<2>{});
+  else if (ld16 <= 192) f(Int<64>{}, Int<3>{});
+  else if (ld16 <= 256) f(Int<64>{}, Int<4>{});
+  else if (ld16 <= 384) f(Int<64>{}, Int<6>{});
+  else if (ld16 <= 512) f(Int<64>{}, Int<8>{});
+  else if (ld16 <= 768) f(Int<64>{}, Int<12>{});
+  else if (ld16 <= 1024) f(Int<64>{}, Int<16>{});
+  else return false;
+  return true;
+}
+constexpr int unrolled_u(int nc) { return nc <= 1 ? 8 : (nc <= 2 ? 4 : (nc <= 4 ? 2 : 1)); }
+// (12-16 KiB of row loads in flight per wave: the gather rates of random whole rows need several rows per wave)
+constexpr int gather_u(int nc) { return nc <= 1 ? 8 : (nc <= 2 ? 6 : (nc <= 3 ? 4 : (nc <= 4 ? 3 : (nc <= 8 ? 2 : 1)))); }
+
+// Queries per tile of the tiled / phased kernels (f16, fp8) for a batch of nq, and so the padding of its staged image
+constexpr int query_tile(int nq) { return nq <= 32 ? 32 : (nq <= 64 ? 64 : (nq <= 128 ? 128 : 256)); }
+
+// ---- svs_index_set_variant: A/B forms of the launch rules.  Tests, tools and bench.py --variant pass the NUMBERS. ----
+//  value  acts in               effect
+//   0     (everywhere)          the measured defaults; the only value under which plan_search screens on its own rule
+//   1     launch_rows           f32 gemv over whole wave loads: persistent grid, 1 row per wave, temporal loads
+//         svs_index_top_pairs   the tiled pair path whatever n
+//   2     launch_rows           persistent grid, 2 rows per wave
+//         phased_ok             false: no phased kernel (the tiled kernels take its batches)
+//   3     launch_rows           one-shot, 2 rows x 16 waves
+//         launch_scores_q16     f32: gemm_f32_q16_kernel (16x16x4 MFMA, half-line loads) for gemm_q16r_kernel
+//   4     launch_rows           one-shot, 1 row x 16 waves, temporal loads
+//         launch_scores         no gemv_unrolled kernels, any dtype: the generic kernels take those rows
+//         launch_scores_q16     2048 rows per workgroup (default 1024)
+//         launch_scores_tiled   f32: 32-query tiles whatever nq
+//         launch_tiled_eb       f16 / fp8: no 128-query phased kernel; 128-row tiles (BM = TG_BM) at 128 / 256 queries per tile
+//   5     launch_rows           one-shot, 1 row x 8 waves
+//         launch_scores_q16     512 rows per workgroup
+//         uses_q16              f16 batches never take the q16 kernel; f32 batches take it whatever nq
+//         tiled_ok              f32: false
+//   6     plan_search           no fused epilogue
+//   7     batch_kernel_ok, tiled_ok   false: no batched kernels, a per-query gemv loop
+//   8     launch_tiled_eb       fused phased kernel: LDS-DMA pieces issued with the fragment reads (EXP 30)
+//   9     launch_tiled_eb       fused phased kernel: epilogue with a branch per register (EXP 31), never the nontemporal form
+//  10     launch_tiled_eb       fused phased kernel: nontemporal corpus pieces (EXP 20) with several query tiles too
+//  11     plan_search           never screens
+//  12     plan_search           screens whatever n
+//  Any value but 0 and 12 also keeps plan_search from screening.
+enum Variant : int {
+  VARIANT_DEFAULT = 0,
+  VARIANT_GEMV_PERSISTENT_R1 = 1,
+  VARIANT_GEMV_PERSISTENT_R2 = 2,
+  VARIANT_GEMV_2X16 = 3,
+  VARIANT_ALT_GEOMETRY = 4,
+  VARIANT_GEMV_1X8 = 5,
+  VARIANT_NO_FUSION = 6,
+  VARIANT_NO_BATCH_KERNELS = 7,
+  VARIANT_PHASED_DMA_WITH_READS = 8,
+  VARIANT_PHASED_BRANCHY_EPILOGUE = 9,
+  VARIANT_PHASED_NONTEMPORAL = 10,
+  VARIANT_SCREEN_OFF = 11,
+  VARIANT_SCREEN_FORCE = 12,
+  VARIANT_LAST = VARIANT_SCREEN_FORCE,
+};
 
 // ---- score stage launch -----------------------------------------------------
 template <int NSTEP, int R, int WPB, bool NT>
@@ -428,11 +504,11 @@ void launch_persistent(const svs_index* idx, const float* q, float* scores, hipS
 template <int NSTEP>
 void launch_rows(const svs_index* idx, const float* q, float* scores, hipStream_t st, int variant) {
   switch (variant) {
-    case 1: launch_persistent<NSTEP, 1, false>(idx, q, scores, st); return;
-    case 2: launch_persistent<NSTEP, 2, true>(idx, q, scores, st); return;
-    case 3: launch_oneshot<NSTEP, 2, 16, true>(idx, q, scores, st); return;
-    case 4: launch_oneshot<NSTEP, 1, 16, false>(idx, q, scores, st); return;
-    case 5: launch_oneshot<NSTEP, 1, 8, true>(idx, q, scores, st); return;
+    case VARIANT_GEMV_PERSISTENT_R1: launch_persistent<NSTEP, 1, false>(idx, q, scores, st); return;
+    case VARIANT_GEMV_PERSISTENT_R2: launch_persistent<NSTEP, 2, true>(idx, q, scores, st); return;
+    case VARIANT_GEMV_2X16: launch_oneshot<NSTEP, 2, 16, true>(idx, q, scores, st); return;
+    case VARIANT_ALT_GEOMETRY: launch_oneshot<NSTEP, 1, 16, false>(idx, q, scores, st); return;
+    case VARIANT_GEMV_1X8: launch_oneshot<NSTEP, 1, 8, true>(idx, q, scores, st); return;
     default: break;
   }
   if constexpr (NSTEP <= 2) launch_oneshot<NSTEP, 4, 16, true>(idx, q, scores, st);
@@ -475,7 +551,7 @@ void launch_generic_f16(const svs_index* idx, const _Float16* qh, float* scores,
 // (row0 > 0: a later chunk of a batch staged piece by piece -- search_host; the buffer was grown by the first chunk's
 //  call, which passes the whole batch's row count as rows_alloc, and only the last chunk zeroes the padding rows)
 int stage_queries_f16(const svs_index* idx, Ctx* c, const float* q, int nq, int rows_alloc, hipStream_t st, int row0 = 0) {
-  int rc = grow_dev(&c->qh, &c->qh_cap, (size_t)rows_alloc * idx->ld);
+  int rc = c->qh.grow((size_t)rows_alloc * idx->ld);
   if (rc != SVS_OK) return rc;
   _Float16* dst = c->qh + (size_t)row0 * idx->ld;
   rows_alloc -= row0;
@@ -489,9 +565,9 @@ int stage_queries_f16(const svs_index* idx, Ctx* c, const float* q, int nq, int 
 // scales c->q8s; want_f32 also fills c->q8f with the quantised values as f32
 int stage_queries_fp8(const svs_index* idx, Ctx* c, const float* q, int nq, int rows_alloc, bool want_f32, hipStream_t st) {
   int rc;
-  if ((rc = grow_dev(&c->q8, &c->q8_cap, (size_t)rows_alloc * idx->ld)) != SVS_OK) return rc;
-  if ((rc = grow_dev(&c->q8s, &c->q8s_cap, (size_t)rows_alloc)) != SVS_OK) return rc;
-  if (want_f32 && (rc = grow_dev(&c->q8f, &c->q8f_cap, (size_t)rows_alloc * idx->ld)) != SVS_OK) return rc;
+  if ((rc = c->q8.grow((size_t)rows_alloc * idx->ld)) != SVS_OK) return rc;
+  if ((rc = c->q8s.grow((size_t)rows_alloc)) != SVS_OK) return rc;
+  if (want_f32 && (rc = c->q8f.grow((size_t)rows_alloc * idx->ld)) != SVS_OK) return rc;
   if (rows_alloc > nq) {   // (the kernel writes whole padded rows: only the rows behind the queries need zeroing)
     HIP_TRY(hipMemsetAsync(c->q8 + (size_t)nq * idx->ld, 0, (size_t)(rows_alloc - nq) * idx->ld, st));
     HIP_TRY(hipMemsetAsync(c->q8s + nq, 0, (size_t)(rows_alloc - nq) * sizeof(float), st));
@@ -507,7 +583,7 @@ void launch_gemv_fp8(const svs_index* idx, Ctx* c, float* scores, hipStream_t st
   int64_t waves = (idx->n + RPW - 1) / RPW;
   int blocks = (int)std::min<int64_t>((waves + 3) / 4, (int64_t)idx->cu_count * 8);
   hipLaunchKernelGGL((gemv_fp8_kernel<T>), dim3(blocks), dim3(256), 0, st, (const u32x4_t*)idx->rows, idx->row_scales,
-                     (const v4f*)c->q8f, c->q8s, scores, idx->n, idx->ld / 16);
+                     (const v4f*)c->q8f.p, c->q8s, scores, idx->n, idx->ld / 16);
 }
 
 // Rows that are not whole 1 KiB wave loads (gemv_unrolled.h); false: longer than 16 KiB
@@ -515,35 +591,29 @@ template <class Dot>
 bool launch_unrolled(const svs_index* idx, const void* q_staged, int ld16, float* scores, hipStream_t st, Dot dot) {
   const u32x4* M = (const u32x4*)idx->rows;
   const u32x4* q = (const u32x4*)q_staged;
-#define SVS_UNROLLED(T, NC, U)                                                                                   \
-  do {                                                                                                           \
-    const int64_t groups = (idx->n + (64 / (T)) * (U) - 1) / ((64 / (T)) * (U));                                   \
-    const int64_t blocks = (groups + UNR_WPB - 1) / UNR_WPB;                                                       \
-    hipLaunchKernelGGL((gemv_unrolled_kernel<T, NC, U, Dot>), dim3((unsigned)blocks), dim3(UNR_WPB * 64), 0, st, M, q, scores, idx->n, ld16, dot); \
-    return true;                                                                                                 \
-  } while (0)
-  if (ld16 <= 1) SVS_UNROLLED(1, 1, 8);
-  if (ld16 <= 2) SVS_UNROLLED(2, 1, 8);
-  if (ld16 <= 4) SVS_UNROLLED(4, 1, 8);
-  if (ld16 <= 8) SVS_UNROLLED(8, 1, 8);
-  if (ld16 <= 16) SVS_UNROLLED(16, 1, 8);
-  if (ld16 <= 32) SVS_UNROLLED(32, 1, 8);
-  if (ld16 <= 64) SVS_UNROLLED(64, 1, 8);
-  if (ld16 <= 128) SVS_UNROLLED(64, 2, 4);
-  if (ld16 <= 192) SVS_UNROLLED(64, 3, 2);
-  if (ld16 <= 256) SVS_UNROLLED(64, 4, 2);
-  if (ld16 <= 384) SVS_UNROLLED(64, 6, 1);
-  if (ld16 <= 512) SVS_UNROLLED(64, 8, 1);
-  if (ld16 <= 768) SVS_UNROLLED(64, 12, 1);
-  if (ld16 <= 1024) SVS_UNROLLED(64, 16, 1);
-#undef SVS_UNROLLED
-  return false;
+  return for_row_geometry(ld16, [&](auto t, auto nc) {
+    constexpr int T = t(), NC = nc(), U = unrolled_u(NC);
+    const int64_t groups = (idx->n + (64 / T) * U - 1) / ((64 / T) * U);
+    const int64_t blocks = (groups + UNR_WPB - 1) / UNR_WPB;
+    hipLaunchKernelGGL((gemv_unrolled_kernel<T, NC, U, Dot>), dim3((unsigned)blocks), dim3(UNR_WPB * 64), 0, st, M, q, scores, idx->n, ld16, dot);
+  });
+}
+
+// The query as the single-query kernels read it: ld floats, 16-byte aligned (rows padded beyond d: zero padded)
+int pad_query(const svs_index* idx, Ctx* c, const float* q, const float** out, hipStream_t st) {
+  *out = q;
+  if (idx->ld == idx->d && (((uintptr_t)q) & 15) == 0) return SVS_OK;
+  int rc = c->q16.grow((size_t)GQ * idx->ld);
+  if (rc != SVS_OK) return rc;
+  HIP_TRY(hipMemsetAsync(c->q16, 0, (size_t)idx->ld * sizeof(float), st));
+  HIP_TRY(hipMemcpyAsync(c->q16, q, (size_t)idx->d * sizeof(float), hipMemcpyDeviceToDevice, st));
+  *out = c->q16;
+  return SVS_OK;
 }
 
 // q: device, d floats (unpadded); scores: device, n floats
 int launch_scores(const svs_index* idx, Ctx* c, const float* q, float* scores, hipStream_t st) {
   const int variant = idx->variant.load();
-  const bool q_aligned = (((uintptr_t)q) & 15) == 0;
   if (idx->dtype == SVS_DTYPE_FP8) {
     int rc = stage_queries_fp8(idx, c, q, 1, 1, true, st);
     if (rc != SVS_OK) return rc;
@@ -568,26 +638,15 @@ int launch_scores(const svs_index* idx, Ctx* c, const float* q, float* scores, h
     }
 #undef SVS_FP8_HOT
     const int ld16 = idx->ld / 16;
-    if (variant != 4 && launch_unrolled(idx, c->q8, ld16, scores, st, DotFp8{idx->row_scales, c->q8s})) return SVS_OK;
-    if (ld16 <= 1) launch_gemv_fp8<1>(idx, c, scores, st);
-    else if (ld16 <= 2) launch_gemv_fp8<2>(idx, c, scores, st);
-    else if (ld16 <= 4) launch_gemv_fp8<4>(idx, c, scores, st);
-    else if (ld16 <= 8) launch_gemv_fp8<8>(idx, c, scores, st);
-    else if (ld16 <= 16) launch_gemv_fp8<16>(idx, c, scores, st);
-    else if (ld16 <= 32) launch_gemv_fp8<32>(idx, c, scores, st);
-    else launch_gemv_fp8<64>(idx, c, scores, st);
+    if (variant != VARIANT_ALT_GEOMETRY && launch_unrolled(idx, c->q8, ld16, scores, st, DotFp8{idx->row_scales, c->q8s})) return SVS_OK;
+    for_width(ld16, [&](auto t) { launch_gemv_fp8<t()>(idx, c, scores, st); });
     return SVS_OK;
   }
   if (idx->dtype == SVS_DTYPE_F16) {
     if (idx->ld % 512 == 0 && idx->ld <= 4096) {
-      const float* qq = q;   // the kernel rounds ld query floats itself: pad them when rows are padded
-      if (idx->ld != idx->d || !q_aligned) {
-        int rc = grow_dev(&c->q16, &c->q16_cap, (size_t)GQ * idx->ld);
-        if (rc != SVS_OK) return rc;
-        HIP_TRY(hipMemsetAsync(c->q16, 0, (size_t)idx->ld * sizeof(float), st));
-        HIP_TRY(hipMemcpyAsync(c->q16, q, (size_t)idx->d * sizeof(float), hipMemcpyDeviceToDevice, st));
-        qq = c->q16;
-      }
+      const float* qq = nullptr;   // the kernel rounds ld query floats itself: pad them when rows are padded
+      int rc = pad_query(idx, c, q, &qq, st);
+      if (rc != SVS_OK) return rc;
       switch (idx->ld / 512) {
 #define SVS_ROWS_CASE(N) case N: launch_rows_f16<N>(idx, idx->rows, qq, scores, st); return SVS_OK;
         SVS_ROWS_CASE(1) SVS_ROWS_CASE(2) SVS_ROWS_CASE(3) SVS_ROWS_CASE(4) SVS_ROWS_CASE(5) SVS_ROWS_CASE(6)
@@ -599,26 +658,15 @@ int launch_scores(const svs_index* idx, Ctx* c, const float* q, float* scores, h
     int rc = stage_queries_f16(idx, c, q, 1, 1, st);
     if (rc != SVS_OK) return rc;
     const int ld8 = idx->ld / 8;
-    if (variant != 4 && launch_unrolled(idx, c->qh, ld8, scores, st, DotF16{})) return SVS_OK;
-    if (ld8 <= 1) launch_generic_f16<1>(idx, c->qh, scores, st);
-    else if (ld8 <= 2) launch_generic_f16<2>(idx, c->qh, scores, st);
-    else if (ld8 <= 4) launch_generic_f16<4>(idx, c->qh, scores, st);
-    else if (ld8 <= 8) launch_generic_f16<8>(idx, c->qh, scores, st);
-    else if (ld8 <= 16) launch_generic_f16<16>(idx, c->qh, scores, st);
-    else if (ld8 <= 32) launch_generic_f16<32>(idx, c->qh, scores, st);
-    else launch_generic_f16<64>(idx, c->qh, scores, st);
+    if (variant != VARIANT_ALT_GEOMETRY && launch_unrolled(idx, c->qh, ld8, scores, st, DotF16{})) return SVS_OK;
+    for_width(ld8, [&](auto t) { launch_generic_f16<t()>(idx, c->qh, scores, st); });
     return SVS_OK;
   }
   if (idx->ld % 256 == 0 && idx->ld <= 4096) {
     // rows padded beyond d (choose_ld): the kernel reads ld query floats, so pad the query too
-    const float* qq = q;
-    if (idx->ld != idx->d || !q_aligned) {
-      int rc = grow_dev(&c->q16, &c->q16_cap, (size_t)GQ * idx->ld);
-      if (rc != SVS_OK) return rc;
-      HIP_TRY(hipMemsetAsync(c->q16, 0, (size_t)idx->ld * sizeof(float), st));
-      HIP_TRY(hipMemcpyAsync(c->q16, q, (size_t)idx->d * sizeof(float), hipMemcpyDeviceToDevice, st));
-      qq = c->q16;
-    }
+    const float* qq = nullptr;
+    int rc = pad_query(idx, c, q, &qq, st);
+    if (rc != SVS_OK) return rc;
     switch (idx->ld / 256) {
 #define SVS_ROWS_CASE(N) case N: launch_rows<N>(idx, qq, scores, st, variant); return SVS_OK;
       SVS_ROWS_CASE(1) SVS_ROWS_CASE(2) SVS_ROWS_CASE(3) SVS_ROWS_CASE(4) SVS_ROWS_CASE(5) SVS_ROWS_CASE(6)
@@ -629,34 +677,21 @@ int launch_scores(const svs_index* idx, Ctx* c, const float* q, float* scores, h
     }
   }
   const int ld4 = idx->ld / 4;
-  if (variant != 4 && ld4 <= 1024) {
+  if (variant != VARIANT_ALT_GEOMETRY && ld4 <= 1024) {
     // rows of up to 16 KiB that are not whole wave loads (gemv_unrolled.h): the query is read in
     // 16-byte chunks of the padded row, so it is padded (and aligned) the same way
-    const float* qq = q;
-    if (idx->ld != idx->d || !q_aligned) {
-      int rc = grow_dev(&c->q16, &c->q16_cap, (size_t)GQ * idx->ld);
-      if (rc != SVS_OK) return rc;
-      HIP_TRY(hipMemsetAsync(c->q16, 0, (size_t)idx->ld * sizeof(float), st));
-      HIP_TRY(hipMemcpyAsync(c->q16, q, (size_t)idx->d * sizeof(float), hipMemcpyDeviceToDevice, st));
-      qq = c->q16;
-    }
+    const float* qq = nullptr;
+    int rc = pad_query(idx, c, q, &qq, st);
+    if (rc != SVS_OK) return rc;
     if (launch_unrolled(idx, qq, ld4, scores, st, DotF32{})) return SVS_OK;
   }
-  if (ld4 <= 1) launch_generic<1>(idx, q, scores, st);
-  else if (ld4 <= 2) launch_generic<2>(idx, q, scores, st);
-  else if (ld4 <= 4) launch_generic<4>(idx, q, scores, st);
-  else if (ld4 <= 8) launch_generic<8>(idx, q, scores, st);
-  else if (ld4 <= 16) launch_generic<16>(idx, q, scores, st);
-  else if (ld4 <= 32) launch_generic<32>(idx, q, scores, st);
-  else launch_generic<64>(idx, q, scores, st);
+  for_width(ld4, [&](auto t) { launch_generic<t()>(idx, q, scores, st); });
   return SVS_OK;
 }
 
 // ---- up to 16 queries per corpus pass (gemm_q16.h) ---------------------------
-size_t elem_bytes(const svs_index* idx) { return idx->dtype == SVS_DTYPE_F32 ? 4 : (idx->dtype == SVS_DTYPE_F16 ? 2 : 1); }
-
 bool batch_kernel_ok(const svs_index* idx) {
-  if (idx->variant.load() == 7) return false;
+  if (idx->variant.load() == VARIANT_NO_BATCH_KERNELS) return false;
   // the query image (16 x row bytes) must fit the LDS beside the fused candidate list
   if (idx->dtype == SVS_DTYPE_F32) return idx->ld % 128 == 0 && idx->ld <= 2304;
   if (idx->dtype == SVS_DTYPE_F16) return idx->ld % 256 == 0 && idx->ld <= 4608;   // whole pairs of 256-byte steps
@@ -688,7 +723,7 @@ int stage_queries_f32(const svs_index* idx, Ctx* c, const float* q_dev, int nq, 
   const int ld = idx->ld;
   const int nq_pad = (nq + group - 1) / group * group;
   if (nq_pad == nq && ld == idx->d && !(((uintptr_t)q_dev) & 15)) { *out = q_dev; return SVS_OK; }
-  int rc = grow_dev(&c->q16, &c->q16_cap, (size_t)nq_pad * ld);
+  int rc = c->q16.grow((size_t)nq_pad * ld);
   if (rc != SVS_OK) return rc;
   HIP_TRY(hipMemsetAsync(c->q16, 0, (size_t)nq_pad * ld * sizeof(float), st));
   HIP_TRY(hipMemcpy2DAsync(c->q16, (size_t)ld * sizeof(float), q_dev, (size_t)idx->d * sizeof(float),
@@ -730,27 +765,26 @@ int launch_scores_q16(const svs_index* idx, const void* q16, int nq_g, int64_t n
   const int variant = idx->variant.load();
   // 1024 rows (6 MB at d = 1536) per workgroup amortise the 96 KiB query staging; short
   // row ranges (the fused path's prefix) take smaller blocks so that every CU gets one.
-  int rows_per_block = variant == 4 ? 2048 : (variant == 5 ? 512 : 1024);
+  int rows_per_block = variant == VARIANT_ALT_GEOMETRY ? 2048 : (variant == VARIANT_GEMV_1X8 ? 512 : 1024);
   while (rows_per_block > 64 && (n_rows + rows_per_block - 1) / rows_per_block < 512) rows_per_block /= 2;
   const size_t row_bytes = (size_t)idx->ld * elem_bytes(idx);
   const int ld16 = (int)(row_bytes / 16);
-  if (idx->dtype == SVS_DTYPE_F16) {
-    if (fl.state) launch_q16_kernel(gemm_q16r_kernel<true, 2>, kQ16rName<true, 2>.s, idx, (const v4f*)fl.rows_of(idx), (const v4f*)q16, ld16, row_bytes, nq_g, n_rows, scores, sstride, rows_per_block, fl, st);
-    else launch_q16_kernel(gemm_q16r_kernel<false, 2>, kQ16rName<false, 2>.s, idx, (const v4f*)fl.rows_of(idx), (const v4f*)q16, ld16, row_bytes, nq_g, n_rows, scores, sstride, rows_per_block, fl, st);
-  } else if (variant == 3) {   // A/B: the 16x16x4 kernel (half-line loads)
-    if (fl.state) launch_q16_kernel(gemm_f32_q16_kernel<false, 2, GEMM_PF, true>, kF32Q16Name<true>.s, idx, (const float*)fl.rows_of(idx), (const float*)q16, idx->ld, row_bytes, nq_g, n_rows, scores, sstride, rows_per_block, fl, st);
-    else launch_q16_kernel(gemm_f32_q16_kernel<false, 2, GEMM_PF, false>, kF32Q16Name<false>.s, idx, (const float*)fl.rows_of(idx), (const float*)q16, idx->ld, row_bytes, nq_g, n_rows, scores, sstride, rows_per_block, fl, st);
-  } else {
-    if (fl.state) launch_q16_kernel(gemm_q16r_kernel<true, 4>, kQ16rName<true, 4>.s, idx, (const v4f*)fl.rows_of(idx), (const v4f*)q16, ld16, row_bytes, nq_g, n_rows, scores, sstride, rows_per_block, fl, st);
-    else launch_q16_kernel(gemm_q16r_kernel<false, 4>, kQ16rName<false, 4>.s, idx, (const v4f*)fl.rows_of(idx), (const v4f*)q16, ld16, row_bytes, nq_g, n_rows, scores, sstride, rows_per_block, fl, st);
-  }
+  with_bool(fl.state != nullptr, [&](auto fuse) {
+    constexpr bool F = fuse();
+    if (idx->dtype == SVS_DTYPE_F16)
+      launch_q16_kernel(gemm_q16r_kernel<F, 2>, kQ16rName<F, 2>.s, idx, (const v4f*)fl.rows_of(idx), (const v4f*)q16, ld16, row_bytes, nq_g, n_rows, scores, sstride, rows_per_block, fl, st);
+    else if (variant == VARIANT_GEMV_2X16)   // A/B: the 16x16x4 kernel (half-line loads)
+      launch_q16_kernel(gemm_f32_q16_kernel<false, 2, GEMM_PF, F>, kF32Q16Name<F>.s, idx, (const float*)fl.rows_of(idx), (const float*)q16, idx->ld, row_bytes, nq_g, n_rows, scores, sstride, rows_per_block, fl, st);
+    else
+      launch_q16_kernel(gemm_q16r_kernel<F, 4>, kQ16rName<F, 4>.s, idx, (const v4f*)fl.rows_of(idx), (const v4f*)q16, ld16, row_bytes, nq_g, n_rows, scores, sstride, rows_per_block, fl, st);
+  });
   return SVS_OK;
 }
 
 // ---- LDS-tiled MFMA GEMM, f16 / fp8 corpus (gemm_tiled.h) ----------------------
 bool tiled_ok(const svs_index* idx) {
-  if (idx->variant.load() == 7) return false;
-  if (idx->dtype == SVS_DTYPE_F32) return (idx->ld * 4) % TG_BKB == 0 && idx->variant.load() != 5;
+  if (idx->variant.load() == VARIANT_NO_BATCH_KERNELS) return false;
+  if (idx->dtype == SVS_DTYPE_F32) return (idx->ld * 4) % TG_BKB == 0 && idx->variant.load() != VARIANT_GEMV_1X8;
   if (idx->dtype == SVS_DTYPE_F16) return (idx->ld * 2) % TG_BKB == 0;
   if (idx->dtype == SVS_DTYPE_FP8) return idx->ld % TG_BKB == 0;
   return false;
@@ -768,7 +802,7 @@ int launch_tiled_bn(const svs_index* idx, Ctx* c, int64_t n_rows, int nq, float*
   static constexpr KernelName name = kernel_name("gemm_tiled_kernel", BN, FUSE, EB, BM);
   launch_record(name.s, n_rows, nq);
   const unsigned gx = (unsigned)((n_rows + BM - 1) / BM), gy = (unsigned)((nq + BN - 1) / BN);
-  const uint8_t* Q = EB == 2 ? (const uint8_t*)c->qh : (EB == 1 ? (const uint8_t*)c->q8 : (const uint8_t*)c->q_f32);
+  const uint8_t* Q = EB == 2 ? (const uint8_t*)c->qh.p : (EB == 1 ? (const uint8_t*)c->q8.p : (const uint8_t*)c->q_f32);
   // pair mode: the row operand starts at global row fl.pairs.row_base (n_rows counts from there)
   const int64_t rb = fl.pairs.on ? fl.pairs.row_base : 0;
   hipLaunchKernelGGL((gemm_tiled_kernel<BN, FUSE, EB, BM>), dim3(gx, gy), dim3(TG_WAVES * 64), lds, st,
@@ -791,7 +825,7 @@ int launch_phased(const svs_index* idx, Ctx* c, int64_t n_rows, int nq, float* s
   const int gx = (int)((n_rows + PG_TILE - 1) / PG_TILE), gy = (nq + QT - 1) / QT;
   const int64_t total = (int64_t)gx * gy;
   const unsigned grid = (unsigned)std::min<int64_t>(total, idx->cu_count);   // one persistent workgroup per CU
-  const uint8_t* Q = EB == 2 ? (const uint8_t*)c->qh : (const uint8_t*)c->q8;
+  const uint8_t* Q = EB == 2 ? (const uint8_t*)c->qh.p : (const uint8_t*)c->q8.p;
   // pair mode: the row operand starts at global row fl.pairs.row_base (n_rows counts from there)
   const int64_t rb = fl.pairs.on ? fl.pairs.row_base : 0;
   hipLaunchKernelGGL((gemm_phased_kernel<FUSE, EB, EXP, QT>), dim3(grid), dim3(PG_THREADS), PG_LDS_TOTAL, st,
@@ -805,50 +839,50 @@ int launch_phased(const svs_index* idx, Ctx* c, int64_t n_rows, int nq, float* s
 // and tile counts inside 32-bit descriptors / ints
 bool phased_ok(const svs_index* idx, int64_t n_rows, int nq) {
   const int64_t ldb = (int64_t)idx->ld * (int64_t)elem_bytes(idx);
-  return idx->variant.load() != 2 && (idx->dtype == SVS_DTYPE_F16 || idx->dtype == SVS_DTYPE_FP8) && ldb % (2 * TG_BKB) == 0 && ldb >= PG_MIN_KT * TG_BKB && ldb <= (1 << 20) &&
+  return idx->variant.load() != VARIANT_GEMV_PERSISTENT_R2 && (idx->dtype == SVS_DTYPE_F16 || idx->dtype == SVS_DTYPE_FP8) && ldb % (2 * TG_BKB) == 0 && ldb >= PG_MIN_KT * TG_BKB && ldb <= (1 << 20) &&
          ((n_rows + PG_TILE - 1) / PG_TILE) * ((nq + PG_TILE - 1) / PG_TILE) < (1ll << 30);
 }
 
 template <int EB>
 int launch_tiled_eb(const svs_index* idx, Ctx* c, int64_t n_rows, int nq, int bn, float* scores, int64_t sstride,
                     FuseLaunch fl, hipStream_t st) {
-  const bool f = fl.state != nullptr;
-  if constexpr (EB != 4) {
-    if (bn == 256 && phased_ok(idx, n_rows, nq)) {
-      if (f && idx->variant.load() == 8)   // A/B: LDS-DMA pieces issued with the fragment reads
-        return launch_phased<true, EB, 30>(idx, c, n_rows, nq, scores, sstride, fl, st);
-      if (f && idx->variant.load() == 9)   // A/B: fused epilogue with a branch per register
-        return launch_phased<true, EB, 31>(idx, c, n_rows, nq, scores, sstride, fl, st);
-      // One query tile (up to 256 queries): every corpus byte is used by exactly one workgroup, so its LDS-DMA
-      // pieces are issued nontemporal (EXP 20) and leave the L2 to the queries (configs[4]: 7.63 vs 7.89-8.0 ms in
-      // tools/gemm_phased_bench; with several query tiles the corpus tile is SHARED through the L2: not there).
-      if (f && (nq <= PG_TILE || idx->variant.load() == 10) && idx->variant.load() != 9)   // (variant 10: nontemporal with several query tiles too, A/B)
-        return launch_phased<true, EB, 20>(idx, c, n_rows, nq, scores, sstride, fl, st);
-      return f ? launch_phased<true, EB>(idx, c, n_rows, nq, scores, sstride, fl, st)
-               : launch_phased<false, EB>(idx, c, n_rows, nq, scores, sstride, fl, st);
+  const int variant = idx->variant.load();
+  return with_bool(fl.state != nullptr, [&](auto fuse) -> int {
+    constexpr bool F = fuse();
+    if constexpr (EB != 4) {
+      if (bn == 256 && phased_ok(idx, n_rows, nq)) {
+        if constexpr (F) {
+          if (variant == VARIANT_PHASED_DMA_WITH_READS)   // A/B: LDS-DMA pieces issued with the fragment reads
+            return launch_phased<true, EB, 30>(idx, c, n_rows, nq, scores, sstride, fl, st);
+          if (variant == VARIANT_PHASED_BRANCHY_EPILOGUE)   // A/B: fused epilogue with a branch per register
+            return launch_phased<true, EB, 31>(idx, c, n_rows, nq, scores, sstride, fl, st);
+          // One query tile (up to 256 queries): every corpus byte is used by exactly one workgroup, so its LDS-DMA
+          // pieces are issued nontemporal (EXP 20) and leave the L2 to the queries (configs[4]: 7.63 vs 7.89-8.0 ms in
+          // tools/gemm_phased_bench; with several query tiles the corpus tile is SHARED through the L2: not there).
+          if (nq <= PG_TILE || variant == VARIANT_PHASED_NONTEMPORAL)   // (nontemporal with several query tiles too, A/B)
+            return launch_phased<true, EB, 20>(idx, c, n_rows, nq, scores, sstride, fl, st);
+        }
+        return launch_phased<F, EB>(idx, c, n_rows, nq, scores, sstride, fl, st);
+      }
+      // 65 .. 128 queries (one query tile: the batches a coalescer forms on a reduced-precision index): the phased
+      // kernel at 128-query tiles, corpus pieces nontemporal -- HBM-bound, every corpus byte used once
+      if (bn == 128 && !fl.pairs.on && variant != VARIANT_ALT_GEOMETRY && phased_ok(idx, n_rows, nq))
+        return launch_phased<F, EB, F ? 20 : 0, 128>(idx, c, n_rows, nq, scores, sstride, fl, st);
     }
-  }
-  if constexpr (EB != 4) {
-    // 65 .. 128 queries (one query tile: the batches a coalescer forms on a reduced-precision index): the phased
-    // kernel at 128-query tiles, corpus pieces nontemporal -- HBM-bound, every corpus byte used once
-    if (bn == 128 && !fl.pairs.on && idx->variant.load() != 4 && phased_ok(idx, n_rows, nq))
-      return f ? launch_phased<true, EB, 20, 128>(idx, c, n_rows, nq, scores, sstride, fl, st)
-               : launch_phased<false, EB, 0, 128>(idx, c, n_rows, nq, scores, sstride, fl, st);
-  }
-  switch (bn) {
-    case 32: return f ? launch_tiled_bn<32, true, EB>(idx, c, n_rows, nq, scores, sstride, fl, st) : launch_tiled_bn<32, false, EB>(idx, c, n_rows, nq, scores, sstride, fl, st);
-    case 64:   // (256-row tiles measured 2-5 % slower here)
-      return f ? launch_tiled_bn<64, true, EB>(idx, c, n_rows, nq, scores, sstride, fl, st) : launch_tiled_bn<64, false, EB>(idx, c, n_rows, nq, scores, sstride, fl, st);
-    case 128:
-      if (idx->variant.load() == 4)   // A/B: 128-row tiles (0.87 vs 0.76 ms at 1M x 1536 f16)
-        return f ? launch_tiled_bn<128, true, EB>(idx, c, n_rows, nq, scores, sstride, fl, st) : launch_tiled_bn<128, false, EB>(idx, c, n_rows, nq, scores, sstride, fl, st);
-      return f ? launch_tiled_bn<128, true, EB, 256>(idx, c, n_rows, nq, scores, sstride, fl, st) : launch_tiled_bn<128, false, EB, 256>(idx, c, n_rows, nq, scores, sstride, fl, st);
-    default:
-      if (idx->variant.load() == 4)   // A/B: 128-row tiles, three-stage ring
-        return f ? launch_tiled_bn<256, true, EB>(idx, c, n_rows, nq, scores, sstride, fl, st) : launch_tiled_bn<256, false, EB>(idx, c, n_rows, nq, scores, sstride, fl, st);
-      return f ? launch_tiled_bn<256, true, EB, 256>(idx, c, n_rows, nq, scores, sstride, fl, st)
-               : launch_tiled_bn<256, false, EB, 256>(idx, c, n_rows, nq, scores, sstride, fl, st);
-  }
+    switch (bn) {
+      case 32: return launch_tiled_bn<32, F, EB>(idx, c, n_rows, nq, scores, sstride, fl, st);
+      case 64:   // (256-row tiles measured 2-5 % slower here)
+        return launch_tiled_bn<64, F, EB>(idx, c, n_rows, nq, scores, sstride, fl, st);
+      case 128:
+        if (variant == VARIANT_ALT_GEOMETRY)   // A/B: 128-row tiles (0.87 vs 0.76 ms at 1M x 1536 f16)
+          return launch_tiled_bn<128, F, EB>(idx, c, n_rows, nq, scores, sstride, fl, st);
+        return launch_tiled_bn<128, F, EB, 256>(idx, c, n_rows, nq, scores, sstride, fl, st);
+      default:
+        if (variant == VARIANT_ALT_GEOMETRY)   // A/B: 128-row tiles, three-stage ring
+          return launch_tiled_bn<256, F, EB>(idx, c, n_rows, nq, scores, sstride, fl, st);
+        return launch_tiled_bn<256, F, EB, 256>(idx, c, n_rows, nq, scores, sstride, fl, st);
+    }
+  });
 }
 
 // rows [0, n_rows) of the corpus; restage == false reuses the quantised queries already staged in the context
@@ -859,20 +893,19 @@ int launch_scores_tiled(const svs_index* idx, Ctx* c, const float* q_dev, int64_
     // (62 % of the matrix pipe); larger batches are more query tiles of the same launch (grid y).
     // 64 queries per tile from 33 queries up (256 queries: 6.7 vs 7.3 ms with 32; 128-query tiles
     // measured the same as 64: ~125 TFLOP/s of the 157 TF f32 MFMA peak)
-    const bool wide = nq > 32 && idx->variant.load() != 4;   // (variant 4: 32-query tiles, A/B)
+    const bool wide = nq > 32 && idx->variant.load() != VARIANT_ALT_GEOMETRY;   // (32-query tiles, A/B)
     if (restage) {
       const float* qs = nullptr;
       int rc = stage_queries_f32(idx, c, q_dev, nq, wide ? 64 : 32, &qs, st);
       if (rc != SVS_OK) return rc;
       c->q_f32 = qs;
     }
-    if (wide)
-      return fl.state ? launch_tiled_bn<64, true, 4>(idx, c, n_rows, nq, scores, sstride, fl, st)
-                      : launch_tiled_bn<64, false, 4>(idx, c, n_rows, nq, scores, sstride, fl, st);
-    return fl.state ? launch_tiled_bn<32, true, 4>(idx, c, n_rows, nq, scores, sstride, fl, st)
-                    : launch_tiled_bn<32, false, 4>(idx, c, n_rows, nq, scores, sstride, fl, st);
+    return with_bool(fl.state != nullptr, [&](auto fuse) {
+      return wide ? launch_tiled_bn<64, fuse(), 4>(idx, c, n_rows, nq, scores, sstride, fl, st)
+                  : launch_tiled_bn<32, fuse(), 4>(idx, c, n_rows, nq, scores, sstride, fl, st);
+    });
   }
-  const int bn = nq <= 32 ? 32 : (nq <= 64 ? 64 : (nq <= 128 ? 128 : 256));
+  const int bn = query_tile(nq);
   const int nq_pad = (nq + bn - 1) / bn * bn;
   if (restage) {
     int rc = idx->dtype == SVS_DTYPE_F16 ? stage_queries_f16(idx, c, q_dev, nq, nq_pad, st)
@@ -901,9 +934,8 @@ int run_select(svs_index* idx, Ctx* c, const float* scores, int64_t n_eff, int64
     hipLaunchKernelGGL(select_final_kernel, dim3(nq), dim3(FINAL_THREADS), 0, st, scores, n_eff, sstride, k, count, 0,
                        hist, cand, row_offset, out_s, out_r, (const uint32_t*)nullptr);
   } else {
-    int64_t npad;
-    next_pow2_i64(n_eff, &npad);
-    if ((rc = grow_dev(&c->keys, &c->keys_cap, (size_t)nq * (size_t)npad)) != SVS_OK) return rc;
+    const int64_t npad = next_pow2_i64(n_eff);
+    if ((rc = c->keys.grow((size_t)nq * (size_t)npad)) != SVS_OK) return rc;
     int gb = (int)std::min<int64_t>((npad + 255) / 256, 4096);
     hipLaunchKernelGGL(keys_build_kernel, dim3(gb, nq), dim3(256), 0, st, scores, n_eff, sstride, npad, c->keys);
     const int64_t chunk = std::min<int64_t>(npad, SORT_CAP);
@@ -928,7 +960,6 @@ int run_select(svs_index* idx, Ctx* c, const float* scores, int64_t n_eff, int64
 // for rows of 1536-4096 floats and level (1.02 x) for rows of 512, which are ahead from 65,536 (0.87 x).
 // svs_index_set_variant(12) screens whatever n, 11 never.
 inline int64_t screen_min_rows(int ld) { return ld <= 512 ? 65536 : 32768; }
-constexpr int VARIANT_SCREEN_OFF = 11, VARIANT_SCREEN_FORCE = 12;
 
 template <int NSTEP>
 constexpr KernelName kScreenName = kernel_name("gemv_f16_oneshot_kernel", NSTEP, f16_rows_r(NSTEP), f16_rows_wpb(NSTEP));
@@ -960,18 +991,6 @@ void screen_review(svs_index* idx) {
 thread_local const svs_index* g_screen_idx;   // svs_internal_screen_stats: the calling thread's last screened search
 thread_local int g_screen_slot;
 
-// The query as the single-query kernels read it: ld floats, 16-byte aligned (rows padded beyond d: zero padded)
-int pad_query(const svs_index* idx, Ctx* c, const float* q, const float** out, hipStream_t st) {
-  *out = q;
-  if (idx->ld == idx->d && (((uintptr_t)q) & 15) == 0) return SVS_OK;
-  int rc = grow_dev(&c->q16, &c->q16_cap, (size_t)GQ * idx->ld);
-  if (rc != SVS_OK) return rc;
-  HIP_TRY(hipMemsetAsync(c->q16, 0, (size_t)idx->ld * sizeof(float), st));
-  HIP_TRY(hipMemcpyAsync(c->q16, q, (size_t)idx->d * sizeof(float), hipMemcpyDeviceToDevice, st));
-  *out = c->q16;
-  return SVS_OK;
-}
-
 // step 1: approximate scores of the whole corpus from the half shadow
 int launch_screen_scores(const svs_index* idx, Ctx* c, const float* q, float* scores, const float** q_padded, hipStream_t st) {
   int rc = pad_query(idx, c, q, q_padded, st);
@@ -999,7 +1018,7 @@ int run_select_screened(svs_index* idx, Ctx* c, const float* q_padded, int k, in
   hipLaunchKernelGGL(select_window_hist_kernel, dim3(blocks, 1), dim3(FA_THREADS), 0, st, (const float*)c->scores, n, sstride, c->hist);
   hipLaunchKernelGGL(screen_filter_kernel, dim3(blocks), dim3(FA_THREADS), 0, st, (const float*)c->scores, n, (uint32_t)count,
                      c->hist, c->cand, q_padded, idx->ld, (const ScreenStats*)idx->scr_dev, slot_host);
-  const uint32_t* dead_bits = idx->dead_list.empty() ? nullptr : idx->dead_bits_dev;
+  const uint32_t* dead_bits = idx->dead_list.empty() ? nullptr : idx->dead_bits_dev.p;
   const int rblocks = idx->cu_count * 4;
   switch (idx->ld / 256) {
 #define SVS_RESCORE_CASE(N)                                                                                          \
@@ -1047,27 +1066,10 @@ template <int DT>
 int launch_gather_dt(const svs_index* idx, const void* q, const float* q_scales, int nq, const uint32_t* list, int64_t m,
                      float* scores, int64_t sstride, hipStream_t st) {
   const int ld16 = (int)((size_t)idx->ld * elem_bytes(idx) / 16);
-#define SVS_GATHER(T, NC, U)                                                                            \
-  do {                                                                                                  \
-    launch_gather_geo<DT, T, NC, U>(idx, q, q_scales, nq, list, m, scores, sstride, ld16, st);          \
-    return SVS_OK;                                                                                      \
-  } while (0)
-  // (12-16 KiB of row loads in flight per wave: the gather rates of random whole rows need several rows per wave)
-  if (ld16 <= 1) SVS_GATHER(1, 1, 8);
-  if (ld16 <= 2) SVS_GATHER(2, 1, 8);
-  if (ld16 <= 4) SVS_GATHER(4, 1, 8);
-  if (ld16 <= 8) SVS_GATHER(8, 1, 8);
-  if (ld16 <= 16) SVS_GATHER(16, 1, 8);
-  if (ld16 <= 32) SVS_GATHER(32, 1, 8);
-  if (ld16 <= 64) SVS_GATHER(64, 1, 8);
-  if (ld16 <= 128) SVS_GATHER(64, 2, 6);
-  if (ld16 <= 192) SVS_GATHER(64, 3, 4);
-  if (ld16 <= 256) SVS_GATHER(64, 4, 3);
-  if (ld16 <= 384) SVS_GATHER(64, 6, 2);
-  if (ld16 <= 512) SVS_GATHER(64, 8, 2);
-  if (ld16 <= 768) SVS_GATHER(64, 12, 1);
-  if (ld16 <= 1024) SVS_GATHER(64, 16, 1);
-#undef SVS_GATHER
+  const bool ok = for_row_geometry(ld16, [&](auto t, auto nc) {
+    launch_gather_geo<DT, t(), nc(), gather_u(nc())>(idx, q, q_scales, nq, list, m, scores, sstride, ld16, st);
+  });
+  if (ok) return SVS_OK;
   return fail(SVS_ERR_UNSUPPORTED, "svs_index_search_rows: rows of %d bytes; the gather kernel takes rows of up to 16 KiB",
               ld16 * 16);
 }
@@ -1094,15 +1096,18 @@ int launch_gather(const svs_index* idx, Ctx* c, const float* q_dev, int nq, cons
 // Materialised scores of nq queries: scores[q][sstride] (the non-fused score stage).
 bool uses_q16(const svs_index* idx, int nq) {
   if (nq < 2 || !batch_kernel_ok(idx)) return false;
-  if (idx->dtype == SVS_DTYPE_F16) return nq <= GQ && idx->variant.load() != 5;   // (variant 5: tiled kernel, A/B)
-  return nq <= GQ || idx->variant.load() == 5 || !tiled_ok(idx);
+  if (idx->dtype == SVS_DTYPE_F16) return nq <= GQ && idx->variant.load() != VARIANT_GEMV_1X8;   // (tiled kernel, A/B)
+  return nq <= GQ || idx->variant.load() == VARIANT_GEMV_1X8 || !tiled_ok(idx);
 }
+
+// nq queries go through a batched kernel (q16 or tiled), not the per-query gemv loop: launch_scores_any's first two branches
+bool is_batched(const svs_index* idx, int nq) { return uses_q16(idx, nq) || (nq >= 2 && tiled_ok(idx)); }
 
 // Rows of the staged (half / e4m3) query image the batched kernels read for nq queries: the batch padded to the
 // query tile of the kernel that will take it (launch_scores_any / launch_scores_tiled use the same rule).
 int staged_rows(const svs_index* idx, int nq) {
   if (uses_q16(idx, nq)) return (nq + GQ - 1) / GQ * GQ;
-  const int bn = nq <= 32 ? 32 : (nq <= 64 ? 64 : (nq <= 128 ? 128 : 256));
+  const int bn = query_tile(nq);
   return (nq + bn - 1) / bn * bn;
 }
 
@@ -1130,7 +1135,7 @@ int launch_scores_any(svs_index* idx, Ctx* c, const float* q_dev, int64_t n_rows
                              scores ? scores + (size_t)q0 * sstride : nullptr, sstride, fl.at(q0), st);
       if (rc != SVS_OK) return rc;
     }
-  } else if (nq >= 2 && tiled_ok(idx)) {
+  } else if (is_batched(idx, nq)) {
     if ((rc = launch_scores_tiled(idx, c, q_dev, n_rows, nq, scores, sstride, fl, st, restage)) != SVS_OK) return rc;
   } else {
     if (fl.state || n_rows != idx->n) return fail(SVS_ERR_INVALID, "internal: single-query kernels have no fused / prefix form");
@@ -1206,14 +1211,14 @@ struct SearchPlan {
 // Histogram / candidate scratch of run_select's window path (n_eff > SORT_CAP, count <= SEL_KMAX) for nq queries.
 int grow_select_scratch(Ctx* c, int nq, hipStream_t st) {
   if ((size_t)nq <= c->hist_cap) return SVS_OK;
-  if (c->hist) HIP_TRY(hipFree(c->hist));
-  if (c->cand) HIP_TRY(hipFree(c->cand));
-  c->hist = nullptr; c->cand = nullptr; c->hist_cap = 0;
-  const size_t scr_bytes = (size_t)nq * SCR_WORDS * sizeof(uint32_t);
-  HIP_TRY(hipMalloc((void**)&c->hist, scr_bytes));
-  HIP_TRY(hipMalloc((void**)&c->cand, (size_t)nq * CAND_CAP * sizeof(uint64_t)));
+  c->hist_cap = 0;
+  HIP_TRY(c->hist.release());
+  HIP_TRY(c->cand.release());
+  int rc;
+  if ((rc = c->hist.grow((size_t)nq * SCR_WORDS)) != SVS_OK) return rc;
+  if ((rc = c->cand.grow((size_t)nq * CAND_CAP)) != SVS_OK) return rc;
   // zeroed once; select_final_kernel leaves it zeroed after every search
-  HIP_TRY(hipMemsetAsync(c->hist, 0, scr_bytes, st));
+  HIP_TRY(hipMemsetAsync(c->hist, 0, (size_t)nq * SCR_WORDS * sizeof(uint32_t), st));
   c->hist_cap = nq;
   return SVS_OK;
 }
@@ -1228,14 +1233,13 @@ int plan_search(svs_index* idx, Ctx* c, int nq, int k, int count, hipStream_t st
   // candidate list overflows comes back marked and is re-run by the caller.  The prefix
   // pass costs ~60 us whatever the batch: measured break-even is 16 queries (f32: 13.2 k vs
   // 12.7 k queries/s at 16, 6.4 k vs 6.5 k at 8; f16 at 32: 49 k vs 41 k; fp8 at 32: 77 k vs 64 k).
-  const bool batched = uses_q16(idx, nq) || (nq >= 2 && tiled_ok(idx));
-  p->fused = allow_fused && p->path_a && batched && nq >= 16 &&
+  p->fused = allow_fused && p->path_a && is_batched(idx, nq) && nq >= 16 &&
              n >= 8 * FUSE_PREFIX_MIN && (int64_t)n < ((int64_t)1 << 32) &&
-             count <= 256 && idx->variant.load() != 6;
+             count <= 256 && idx->variant.load() != VARIANT_NO_FUSION;
   {
     const int variant = idx->variant.load();
     p->screen = nq == 1 && p->path_a && screen_ready(idx) &&
-                variant != VARIANT_SCREEN_OFF && (variant == VARIANT_SCREEN_FORCE || (variant == 0 && n >= screen_min_rows(idx->ld)));
+                variant != VARIANT_SCREEN_OFF && (variant == VARIANT_SCREEN_FORCE || (variant == VARIANT_DEFAULT && n >= screen_min_rows(idx->ld)));
     if (p->screen) {
       screen_review(idx);
       p->screen = !idx->scr_paused.load();
@@ -1247,11 +1251,11 @@ int plan_search(svs_index* idx, Ctx* c, int nq, int k, int count, hipStream_t st
   // otherwise the ordinary three-launch top-k, whose kernels spread one query over many workgroups
   // (16 queries: 20 vs 33 us; 256 x 156,250 rows: 119 vs 284 us).
   p->kth = p->fused && nq >= 256 && p->n_mat <= 32768;
-  if ((rc = grow_dev(&c->scores, &c->scores_cap, (size_t)nq * (size_t)p->sstride)) != SVS_OK) return rc;
+  if ((rc = c->scores.grow((size_t)nq * (size_t)p->sstride)) != SVS_OK) return rc;
   if (p->path_a && (rc = grow_select_scratch(c, nq, st)) != SVS_OK) return rc;
   if (p->fused) {
-    if ((rc = grow_dev(&c->pref_s, &c->pref_s_cap, (size_t)nq * (p->kth ? 1 : count))) != SVS_OK) return rc;
-    if (!p->kth && (rc = grow_dev(&c->pref_r, &c->pref_r_cap, (size_t)nq * count)) != SVS_OK) return rc;
+    if ((rc = c->pref_s.grow((size_t)nq * (p->kth ? 1 : count))) != SVS_OK) return rc;
+    if (!p->kth && (rc = c->pref_r.grow((size_t)nq * count)) != SVS_OK) return rc;
   }
   const int tevery = idx->timing.load();
   p->timed = tevery > 0 && (idx->timing_seq.fetch_add(1) % (uint32_t)tevery) == 0;
@@ -1305,7 +1309,7 @@ int enqueue_main(svs_index* idx, Ctx* c, SearchPlan& p, const float* q_dev, floa
     if (p.timed) HIP_TRY(hipEventRecord(ev.e1, st));
     hipLaunchKernelGGL(select_final_kernel, dim3(nq), dim3(FINAL_THREADS), 0, st, (const float*)nullptr, n, (int64_t)0, k, count, 3,
                        c->hist, c->cand, idx->row_offset, out_s, out_r,
-                       (const uint32_t*)(idx->dead_list.empty() ? nullptr : idx->dead_bits_dev));
+                       (const uint32_t*)(idx->dead_list.empty() ? nullptr : idx->dead_bits_dev.p));
   } else {
     const float* q_padded = nullptr;
     if (p.screen) {
@@ -1353,6 +1357,13 @@ struct RefGuard {
   RefGuard& operator=(const RefGuard&) = delete;
 };
 
+// Hands an acquired search context back on scope exit.
+struct CtxGuard {
+  svs_index* i;
+  Ctx* c;
+  ~CtxGuard() { ctx_release(i, c); }
+};
+
 // ---- pairwise (document_top_pairwise_scores, src/svs/kb.py:1642-1671) -----------------------
 // rows [r0, r0 + nrows) of the corpus as f32 queries (what the index holds), [nrows][d]
 int dequant_rows_to(svs_index* idx, int64_t r0, int64_t nrows, float* out, hipStream_t st) {
@@ -1384,12 +1395,7 @@ int pairs_block_device(svs_index* idx, Ctx* c, int64_t ns, int count, float* S, 
     hipLaunchKernelGGL(mask_dead_pairs_kernel, dim3(1024), dim3(256), 0, st, S, ns, np, idx->dead_dev, (int64_t)idx->dead_list.size());
   const int64_t flat = ns * np;
   const bool path_a = flat > SORT_CAP && count <= SEL_KMAX;
-  if (path_a && c->hist_cap < 1) {
-    HIP_TRY(hipMalloc((void**)&c->hist, (size_t)SCR_WORDS * sizeof(uint32_t)));
-    HIP_TRY(hipMalloc((void**)&c->cand, (size_t)CAND_CAP * sizeof(uint64_t)));
-    HIP_TRY(hipMemsetAsync(c->hist, 0, (size_t)SCR_WORDS * sizeof(uint32_t), st));
-    c->hist_cap = 1;
-  }
+  if (path_a && (rc = grow_select_scratch(c, 1, st)) != SVS_OK) return rc;
   if ((rc = run_select(idx, c, S, flat, flat, 1, count, count, d_s, d_r, st, /*row_offset=*/0)) != SVS_OK) return rc;
   HIP_TRY(hipGetLastError());
   return SVS_OK;
@@ -1464,15 +1470,7 @@ int top_pairs_tiled(svs_index* idx, Ctx* c, int count, float* out_scores, int64_
   if ((rc = pairs_block_device(idx, c, P, count, S, qbuf, d_s, d_r, st)) != SVS_OK) return rc;
   const float* thr = d_s + (count - 1);    // the bound, read by the epilogue with stride 0
   // per-query candidate scratch for one chunk
-  if ((size_t)QC > c->hist_cap) {
-    if (c->hist) HIP_TRY(hipFree(c->hist));
-    if (c->cand) HIP_TRY(hipFree(c->cand));
-    c->hist = nullptr; c->cand = nullptr; c->hist_cap = 0;
-    HIP_TRY(hipMalloc((void**)&c->hist, (size_t)QC * SCR_WORDS * sizeof(uint32_t)));
-    HIP_TRY(hipMalloc((void**)&c->cand, (size_t)QC * CAND_CAP * sizeof(uint64_t)));
-    HIP_TRY(hipMemsetAsync(c->hist, 0, (size_t)QC * SCR_WORDS * sizeof(uint32_t), st));
-    c->hist_cap = QC;
-  }
+  if ((rc = grow_select_scratch(c, QC, st)) != SVS_OK) return rc;
   for (int64_t q0 = 0; q0 < n - 1; q0 += QC) {
     // the last chunk is moved back so that it still holds QC rows (its first rows were done: first_query)
     const int64_t qs = std::max<int64_t>(0, std::min<int64_t>(q0, n - QC));
@@ -1482,7 +1480,7 @@ int top_pairs_tiled(svs_index* idx, Ctx* c, int count, float* out_scores, int64_
     FuseLaunch fl{c->hist, c->cand, thr, 0, TgPairs{(long long)qs, (long long)row_base, (long long)q0, 1}};
     if ((rc = launch_scores_any(idx, c, qbuf, n - row_base, nq, nullptr, 0, fl, st)) != SVS_OK) return rc;
     hipLaunchKernelGGL(collect_pairs_kernel, dim3(nq), dim3(256), 0, st, c->hist, (const uint64_t*)c->cand, (long long)qs, (long long)q0,
-                       (const uint32_t*)(idx->dead_list.empty() ? nullptr : idx->dead_bits_dev), gstate, LIST_CAP, l_key, l_i, l_j);
+                       (const uint32_t*)(idx->dead_list.empty() ? nullptr : idx->dead_bits_dev.p), gstate, LIST_CAP, l_key, l_i, l_j);
   }
   HIP_TRY(hipGetLastError());
   uint32_t hs[4] = {0, 0, 0, 0};
@@ -1523,6 +1521,30 @@ int check_query_args(const svs_index* idx, const void* q, int nq, int d) {
   return SVS_OK;
 }
 
+// f32 source rows [0, nrows) with a stride of src_ld floats -> rows [row0, row0 + nrows) of the corpus layout, on `st`.
+// f32 corpus: a copy of `kind` (the source is device or pinned memory) that writes the d floats of every row; the
+// columns of padded rows beyond d are the caller's to zero.  f16 / fp8 corpus: the source is on the device and a kernel
+// of `blocks` workgroups converts it.
+hipError_t ingest_rows(svs_index* idx, const float* src, int64_t nrows, int64_t src_ld, int64_t row0, hipMemcpyKind kind,
+                       unsigned blocks, hipStream_t st) {
+  const int d = idx->d;
+  if (idx->dtype == SVS_DTYPE_F16) {
+    hipLaunchKernelGGL(convert_rows_f16_kernel, dim3(blocks), dim3(256), 0, st, src, nrows, d, src_ld,
+                       (_Float16*)idx->rows + (size_t)row0 * idx->ld, idx->ld);
+    return hipGetLastError();
+  }
+  if (idx->dtype == SVS_DTYPE_FP8) {
+    hipLaunchKernelGGL(quantize_rows_fp8_kernel, dim3(blocks), dim3(256), 0, st, src, nrows, d, src_ld,
+                       (uint8_t*)idx->rows + (size_t)row0 * idx->ld, idx->ld, idx->row_scales + row0, (float*)nullptr);
+    return hipGetLastError();
+  }
+  float* dst = (float*)idx->rows + (size_t)row0 * idx->ld;
+  if (kind == hipMemcpyHostToDevice && idx->ld == d && src_ld == d)
+    return hipMemcpyAsync(dst, src, (size_t)nrows * d * sizeof(float), kind, st);
+  return hipMemcpy2DAsync(dst, (size_t)idx->ld * sizeof(float), src, (size_t)src_ld * sizeof(float), (size_t)d * sizeof(float),
+                          (size_t)nrows, kind, st);
+}
+
 // Host rows [0, nrows) (f32, C-contiguous, d floats each) -> HBM rows [row0, row0+nrows).
 // Pinned double-buffered staging: host memcpy of chunk i+1 overlaps the DMA of chunk i.
 // f32 corpus: the DMA writes the padded HBM layout directly (2D copy).
@@ -1532,7 +1554,7 @@ hipError_t upload_host_rows(svs_index* idx, const float* host_rows, int64_t nrow
   const int64_t n = nrows;
   const bool f16 = idx->dtype != SVS_DTYPE_F32;   // f16 and fp8: convert on the device
   const size_t row_b = (size_t)d * sizeof(float);
-  const size_t esz = idx->dtype == SVS_DTYPE_F32 ? 4 : (idx->dtype == SVS_DTYPE_F16 ? 2 : 1);
+  const size_t esz = elem_bytes(idx);
   const size_t chunk_rows = std::max<size_t>(1, std::min<size_t>((32u << 20) / row_b, (size_t)n));
   void* pin[2] = {nullptr, nullptr};
   float* dstage[2] = {nullptr, nullptr};
@@ -1553,24 +1575,8 @@ hipError_t upload_host_rows(svs_index* idx, const float* host_rows, int64_t nrow
     e = hipEventSynchronize(done[b]);
     if (e != hipSuccess) break;
     memcpy(pin[b], host_rows + r0 * (size_t)d, rows * row_b);
-    if (f16) {
-      e = hipMemcpyAsync(dstage[b], pin[b], rows * row_b, hipMemcpyHostToDevice, st);
-      if (e == hipSuccess) {
-        if (idx->dtype == SVS_DTYPE_F16)
-          hipLaunchKernelGGL(convert_rows_f16_kernel, dim3(2048), dim3(256), 0, st, (const float*)dstage[b],
-                             (int64_t)rows, d, (int64_t)d, (_Float16*)idx->rows + dr * (size_t)idx->ld, idx->ld);
-        else
-          hipLaunchKernelGGL(quantize_rows_fp8_kernel, dim3(2048), dim3(256), 0, st, (const float*)dstage[b],
-                             (int64_t)rows, d, (int64_t)d, (uint8_t*)idx->rows + dr * (size_t)idx->ld, idx->ld,
-                             idx->row_scales + dr, (float*)nullptr);
-        e = hipGetLastError();
-      }
-    } else if (idx->ld == d) {
-      e = hipMemcpyAsync((float*)idx->rows + dr * (size_t)d, pin[b], rows * row_b, hipMemcpyHostToDevice, st);
-    } else {
-      e = hipMemcpy2DAsync((float*)idx->rows + dr * (size_t)idx->ld, (size_t)idx->ld * sizeof(float), pin[b], row_b,
-                           row_b, rows, hipMemcpyHostToDevice, st);
-    }
+    if (f16) e = hipMemcpyAsync(dstage[b], pin[b], rows * row_b, hipMemcpyHostToDevice, st);
+    if (e == hipSuccess) e = ingest_rows(idx, f16 ? dstage[b] : (const float*)pin[b], (int64_t)rows, d, (int64_t)dr, hipMemcpyHostToDevice, 2048, st);
     if (e == hipSuccess) e = hipEventRecord(done[b], st);
   }
   if (e == hipSuccess) e = hipStreamSynchronize(st);
@@ -1593,7 +1599,7 @@ hipError_t upload_host_rows(svs_index* idx, const float* host_rows, int64_t nrow
 //     the earlier rule padded them to 1 KiB, +33 % bytes).
 //  3. Otherwise tight.
 int choose_ld(int d, int dtype) {
-  const int align = dtype == SVS_DTYPE_F32 ? 4 : (dtype == SVS_DTYPE_F16 ? 8 : 16);   // elements per 16 bytes
+  const int align = 16 / (int)dtype_bytes(dtype);   // elements per 16 bytes
   const int tight = (d + align - 1) / align * align;
   if (d <= 0) return tight;
   const int wave = 64 * align, line = 8 * align;
@@ -1686,25 +1692,20 @@ void shadow_ingest(svs_index* idx, int64_t row0, int64_t nrows, int64_t n_total,
 
 // Device rows [0, nrows) (f32, stride src_ld) -> HBM rows [row0, row0 + nrows) of the index's layout.
 hipError_t copy_device_rows(svs_index* idx, const float* dev_rows, int64_t nrows, int64_t src_ld, int64_t row0) {
-  const int d = idx->d;
   hipError_t e = hipSuccess;
-  if (idx->dtype == SVS_DTYPE_F16) {
-    hipLaunchKernelGGL(convert_rows_f16_kernel, dim3(4096), dim3(256), 0, 0, dev_rows, nrows, d, src_ld,
-                       (_Float16*)idx->rows + (size_t)row0 * idx->ld, idx->ld);
-    e = hipGetLastError();
-  } else if (idx->dtype == SVS_DTYPE_FP8) {
-    hipLaunchKernelGGL(quantize_rows_fp8_kernel, dim3(4096), dim3(256), 0, 0, dev_rows, nrows, d, src_ld,
-                       (uint8_t*)idx->rows + (size_t)row0 * idx->ld, idx->ld, idx->row_scales + row0, (float*)nullptr);
-    e = hipGetLastError();
-  } else {
-    float* dst = (float*)idx->rows + (size_t)row0 * idx->ld;
-    if (idx->ld != d) e = hipMemset(dst, 0, (size_t)nrows * idx->ld * sizeof(float));
-    if (e == hipSuccess)
-      e = hipMemcpy2D(dst, (size_t)idx->ld * sizeof(float), dev_rows, (size_t)src_ld * sizeof(float),
-                      (size_t)d * sizeof(float), (size_t)nrows, hipMemcpyDeviceToDevice);
-  }
+  if (idx->dtype == SVS_DTYPE_F32 && idx->ld != idx->d)
+    e = hipMemset((float*)idx->rows + (size_t)row0 * idx->ld, 0, (size_t)nrows * idx->ld * sizeof(float));
+  if (e == hipSuccess) e = ingest_rows(idx, dev_rows, nrows, src_ld, row0, hipMemcpyDeviceToDevice, 4096, nullptr);
   if (e == hipSuccess) e = hipDeviceSynchronize();
   return e;
+}
+
+// Room for `need` words in a device buffer that enqueued searches may still read: drained before it is replaced
+// (caller holds the geometry lock exclusively).
+int grow_drained(DevBuf<uint32_t>& buf, size_t need) {
+  if (need <= buf.cap) return SVS_OK;
+  HIP_TRY(hipDeviceSynchronize());
+  return buf.grow(need);
 }
 
 // Device bitmap of the masked rows, one bit per row of the current capacity (caller holds the
@@ -1714,14 +1715,8 @@ int sync_dead_bits(svs_index* idx) {
   const size_t words = (size_t)((std::max(idx->cap, idx->n) + 31) / 32);
   idx->dead_bits.assign(words, 0u);
   for (uint32_t r : idx->dead_list) idx->dead_bits[r >> 5] |= 1u << (r & 31);
-  if (words > idx->dead_bits_cap) {
-    HIP_TRY(hipDeviceSynchronize());   // enqueued searches may still read the old bitmap
-    (void)hipFree(idx->dead_bits_dev);
-    idx->dead_bits_dev = nullptr;
-    idx->dead_bits_cap = 0;
-    HIP_TRY(hipMalloc((void**)&idx->dead_bits_dev, words * sizeof(uint32_t)));
-    idx->dead_bits_cap = words;
-  }
+  int rc = grow_drained(idx->dead_bits_dev, words);
+  if (rc != SVS_OK) return rc;
   HIP_TRY(hipMemcpy(idx->dead_bits_dev, idx->dead_bits.data(), words * sizeof(uint32_t), hipMemcpyHostToDevice));
   return SVS_OK;
 }
@@ -1731,7 +1726,7 @@ int sync_dead_bits(svs_index* idx) {
 int ensure_capacity(svs_index* idx, int64_t rows, bool exact) {
   if (rows > 0xffffffffll) return fail(SVS_ERR_INVALID, "at most 2^32 rows per handle; shard the corpus");
   if (rows <= idx->cap) return SVS_OK;
-  const size_t esz = idx->dtype == SVS_DTYPE_F32 ? 4 : (idx->dtype == SVS_DTYPE_F16 ? 2 : 1), row_b = (size_t)idx->ld * esz;
+  const size_t row_b = (size_t)idx->ld * elem_bytes(idx);
   const int64_t new_cap = exact ? rows : std::max<int64_t>(rows, idx->cap + idx->cap / 2 + 1024);
   void* nrows = nullptr;
   float* nscales = nullptr;
@@ -1802,7 +1797,7 @@ int create_common(int64_t n, int32_t d, int32_t store_dtype, int32_t device, int
   idx->row_offset = row_offset;
   hipDeviceProp_t prop;
   if (hipGetDeviceProperties(&prop, device) == hipSuccess) idx->cu_count = prop.multiProcessorCount;
-  idx->bytes = (size_t)n * (size_t)idx->ld * (store_dtype == SVS_DTYPE_F16 ? 2 : (store_dtype == SVS_DTYPE_FP8 ? 1 : 4));
+  idx->bytes = (size_t)n * (size_t)idx->ld * elem_bytes(idx);
   if (idx->bytes) {
     hipError_t e = hipMalloc(&idx->rows, idx->bytes);
     if (e != hipSuccess) {
@@ -1823,6 +1818,40 @@ int create_common(int64_t n, int32_t d, int32_t store_dtype, int32_t device, int
   if (const char* env = getenv("SVS_AMD_SCREEN")) idx->screen_mode.store(atoi(env) != 0 ? 1 : 0);
   *made = idx;
   return SVS_OK;
+}
+
+// svs_index_create / _from_device: fill(idx) checks the source and brings rows [0, n) in (SVS_OK, or the failure as
+// it has reported it)
+template <class Fill>
+int create_index(int64_t n, int32_t d, int32_t store_dtype, int32_t device, int64_t row_offset, svs_index** out, Fill fill) {
+  svs_index* idx = nullptr;
+  int rc = create_common(n, d, store_dtype, device, row_offset, out, &idx);
+  if (rc != SVS_OK) return rc;
+  if (idx->bytes) {
+    if ((rc = fill(idx)) != SVS_OK) {
+      index_destroy(idx);
+      return rc;
+    }
+    shadow_ingest(idx, 0, n, n, nullptr, true);
+  }
+  *out = idx;
+  return SVS_OK;
+}
+
+// svs_index_append / _from_device behind their argument checks: copy(row0) brings the n_new rows in at row0
+template <class Copy>
+int append_rows(svs_index* idx, int64_t n_new, const char* what, Copy copy) {
+  std::unique_lock<std::shared_mutex> geo(idx->rw);   // no search is enqueuing while the geometry changes
+  HIP_TRY(hipSetDevice(idx->device));
+  const int64_t n_old = idx->n, n_tot = n_old + n_new;
+  int rc = ensure_capacity(idx, n_tot, false);
+  if (rc != SVS_OK) return rc;
+  hipError_t e = copy(n_old);
+  if (e != hipSuccess) return fail(SVS_ERR_DEVICE, "%s: %s", what, hipGetErrorString(e));
+  shadow_ingest(idx, n_old, n_new, n_tot, nullptr, true);
+  idx->n = n_tot;
+  idx->dead_flag.resize((size_t)n_tot, 0);
+  return sync_dead_bits(idx);
 }
 
 }  // namespace
@@ -1852,45 +1881,21 @@ int32_t svs_device_memory(int32_t device, int64_t* free_bytes, int64_t* total_by
 
 int32_t svs_index_create(const float* host_rows, int64_t n, int32_t d, int32_t store_dtype,
                          int32_t device, int64_t row_offset, svs_index** out) {
-  svs_index* idx = nullptr;
-  int rc = create_common(n, d, store_dtype, device, row_offset, out, &idx);
-  if (rc != SVS_OK) return rc;
-  if (idx->bytes) {
-    if (!host_rows) {
-      index_destroy(idx);
-      return fail(SVS_ERR_INVALID, "null host_rows");
-    }
+  return create_index(n, d, store_dtype, device, row_offset, out, [&](svs_index* idx) {
+    if (!host_rows) return fail(SVS_ERR_INVALID, "null host_rows");
     hipError_t e = upload_host_rows(idx, host_rows, n, 0);
-    if (e != hipSuccess) {
-      index_destroy(idx);
-      return fail(SVS_ERR_DEVICE, "corpus upload: %s", hipGetErrorString(e));
-    }
-    shadow_ingest(idx, 0, n, n, nullptr, true);
-  }
-  *out = idx;
-  return SVS_OK;
+    return e == hipSuccess ? (int)SVS_OK : fail(SVS_ERR_DEVICE, "corpus upload: %s", hipGetErrorString(e));
+  });
 }
 
 int32_t svs_index_create_from_device(const float* dev_rows, int64_t n, int32_t d, int64_t src_ld,
                                      int32_t store_dtype, int32_t device, int64_t row_offset,
                                      svs_index** out) {
-  svs_index* idx = nullptr;
-  int rc = create_common(n, d, store_dtype, device, row_offset, out, &idx);
-  if (rc != SVS_OK) return rc;
-  if (idx->bytes) {
-    if (!dev_rows || src_ld < d) {
-      index_destroy(idx);
-      return fail(SVS_ERR_INVALID, "bad device source (ptr %p, ld %lld)", (const void*)dev_rows, (long long)src_ld);
-    }
+  return create_index(n, d, store_dtype, device, row_offset, out, [&](svs_index* idx) {
+    if (!dev_rows || src_ld < d) return fail(SVS_ERR_INVALID, "bad device source (ptr %p, ld %lld)", (const void*)dev_rows, (long long)src_ld);
     hipError_t e = copy_device_rows(idx, dev_rows, n, src_ld, 0);
-    if (e != hipSuccess) {
-      index_destroy(idx);
-      return fail(SVS_ERR_DEVICE, "device corpus copy: %s", hipGetErrorString(e));
-    }
-    shadow_ingest(idx, 0, n, n, nullptr, true);
-  }
-  *out = idx;
-  return SVS_OK;
+    return e == hipSuccess ? (int)SVS_OK : fail(SVS_ERR_DEVICE, "device corpus copy: %s", hipGetErrorString(e));
+  });
 }
 
 int32_t svs_index_append(svs_index* idx, const float* host_rows, int64_t n_new) {
@@ -1899,17 +1904,7 @@ int32_t svs_index_append(svs_index* idx, const float* host_rows, int64_t n_new) 
   if (n_new == 0) return SVS_OK;
   if (!host_rows) return fail(SVS_ERR_INVALID, "null host_rows");
   if (idx->d == 0) return fail(SVS_ERR_SHAPE, "cannot append to a zero-dimensional index");
-  std::unique_lock<std::shared_mutex> geo(idx->rw);   // no search is enqueuing while the geometry changes
-  HIP_TRY(hipSetDevice(idx->device));
-  const int64_t n_old = idx->n, n_tot = n_old + n_new;
-  int rc = ensure_capacity(idx, n_tot, false);
-  if (rc != SVS_OK) return rc;
-  hipError_t e = upload_host_rows(idx, host_rows, n_new, n_old);
-  if (e != hipSuccess) return fail(SVS_ERR_DEVICE, "append upload: %s", hipGetErrorString(e));
-  shadow_ingest(idx, n_old, n_new, n_tot, nullptr, true);
-  idx->n = n_tot;
-  idx->dead_flag.resize((size_t)n_tot, 0);
-  return sync_dead_bits(idx);
+  return append_rows(idx, n_new, "append upload", [&](int64_t row0) { return upload_host_rows(idx, host_rows, n_new, row0); });
 }
 
 int32_t svs_index_reserve(svs_index* idx, int64_t rows_capacity) {
@@ -1926,17 +1921,7 @@ int32_t svs_index_append_from_device(svs_index* idx, const float* dev_rows, int6
   if (n_new == 0) return SVS_OK;
   if (idx->d == 0) return fail(SVS_ERR_SHAPE, "cannot append to a zero-dimensional index");
   if (!dev_rows || src_ld < idx->d) return fail(SVS_ERR_INVALID, "bad device source (ptr %p, ld %lld)", (const void*)dev_rows, (long long)src_ld);
-  std::unique_lock<std::shared_mutex> geo(idx->rw);
-  HIP_TRY(hipSetDevice(idx->device));
-  const int64_t n_old = idx->n, n_tot = n_old + n_new;
-  int rc = ensure_capacity(idx, n_tot, false);
-  if (rc != SVS_OK) return rc;
-  hipError_t e = copy_device_rows(idx, dev_rows, n_new, src_ld, n_old);
-  if (e != hipSuccess) return fail(SVS_ERR_DEVICE, "device append: %s", hipGetErrorString(e));
-  shadow_ingest(idx, n_old, n_new, n_tot, nullptr, true);
-  idx->n = n_tot;
-  idx->dead_flag.resize((size_t)n_tot, 0);
-  return sync_dead_bits(idx);
+  return append_rows(idx, n_new, "device append", [&](int64_t row0) { return copy_device_rows(idx, dev_rows, n_new, src_ld, row0); });
 }
 
 int32_t svs_index_staging_acquire(svs_index* idx, float** host_block, int64_t* rows_cap) {
@@ -1987,24 +1972,11 @@ int32_t svs_index_staging_commit(svs_index* idx, int64_t n_rows) {
     if (rc != SVS_OK) return rc;
   }
   const int d = idx->d, b = g.cur;
-  const size_t row_b = (size_t)d * sizeof(float);
-  if (idx->dtype == SVS_DTYPE_F32) {
-    float* dst = (float*)idx->rows + (size_t)n_old * idx->ld;
-    if (idx->ld == d) HIP_TRY(hipMemcpyAsync(dst, g.pin[b], (size_t)n_rows * row_b, hipMemcpyHostToDevice, g.st));
-    else {
-      HIP_TRY(hipMemsetAsync(dst, 0, (size_t)n_rows * idx->ld * sizeof(float), g.st));
-      HIP_TRY(hipMemcpy2DAsync(dst, (size_t)idx->ld * sizeof(float), g.pin[b], row_b, row_b, (size_t)n_rows, hipMemcpyHostToDevice, g.st));
-    }
-  } else {
-    HIP_TRY(hipMemcpyAsync(g.dstage[b], g.pin[b], (size_t)n_rows * row_b, hipMemcpyHostToDevice, g.st));
-    if (idx->dtype == SVS_DTYPE_F16)
-      hipLaunchKernelGGL(convert_rows_f16_kernel, dim3(2048), dim3(256), 0, g.st, (const float*)g.dstage[b], n_rows, d, (int64_t)d,
-                         (_Float16*)idx->rows + (size_t)n_old * idx->ld, idx->ld);
-    else
-      hipLaunchKernelGGL(quantize_rows_fp8_kernel, dim3(2048), dim3(256), 0, g.st, (const float*)g.dstage[b], n_rows, d, (int64_t)d,
-                         (uint8_t*)idx->rows + (size_t)n_old * idx->ld, idx->ld, idx->row_scales + n_old, (float*)nullptr);
-    HIP_TRY(hipGetLastError());
-  }
+  if (idx->dtype != SVS_DTYPE_F32)
+    HIP_TRY(hipMemcpyAsync(g.dstage[b], g.pin[b], (size_t)n_rows * d * sizeof(float), hipMemcpyHostToDevice, g.st));
+  else if (idx->ld != d)
+    HIP_TRY(hipMemsetAsync((float*)idx->rows + (size_t)n_old * idx->ld, 0, (size_t)n_rows * idx->ld * sizeof(float), g.st));
+  HIP_TRY(ingest_rows(idx, idx->dtype != SVS_DTYPE_F32 ? g.dstage[b] : (const float*)g.pin[b], n_rows, d, n_old, hipMemcpyHostToDevice, 2048, g.st));
   shadow_ingest(idx, n_old, n_rows, n_tot, g.st, false);   // (on the staging stream, behind the DMA it reads)
   HIP_TRY(hipEventRecord(g.done[b], g.st));
   idx->staging_pending.store(true);
@@ -2046,14 +2018,9 @@ int32_t svs_index_mask_rows(svs_index* idx, const int64_t* rows, int64_t count) 
     int rc = sync_dead_bits(idx);
     if (rc != SVS_OK) return rc;
   }
-  if (idx->dead_list.size() > idx->dead_dev_cap) {
-    HIP_TRY(hipDeviceSynchronize());   // enqueued searches may still read the old list
-    (void)hipFree(idx->dead_dev);
-    idx->dead_dev = nullptr;
-    idx->dead_dev_cap = 0;
-    const size_t cap = idx->dead_list.size() * 2 + 64;
-    HIP_TRY(hipMalloc((void**)&idx->dead_dev, cap * sizeof(uint32_t)));
-    idx->dead_dev_cap = cap;
+  if (idx->dead_list.size() > idx->dead_dev.cap) {
+    int rc = grow_drained(idx->dead_dev, idx->dead_list.size() * 2 + 64);
+    if (rc != SVS_OK) return rc;
   }
   HIP_TRY(hipMemcpy(idx->dead_dev, idx->dead_list.data(), idx->dead_list.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
   return SVS_OK;
@@ -2097,23 +2064,11 @@ static int32_t search_host(svs_index* idx, const float* queries, int32_t nq, int
   HIP_TRY(hipSetDevice(idx->device));
   Ctx* c = nullptr;
   if ((rc = ctx_acquire(idx, nullptr, true, &c)) != SVS_OK) return rc;
-  struct CtxGuard { svs_index* i; Ctx* c; ~CtxGuard() { ctx_release(i, c); } } cg{idx, c};
+  CtxGuard cg{idx, c};
   const size_t qn = (size_t)nq * (size_t)d, on = (size_t)nq * (size_t)count;
-  if ((rc = grow_dev(&c->q_dev, &c->q_cap, qn)) != SVS_OK) return rc;
-  if (qn > c->q_pin_cap) {
-    if (c->q_pin) HIP_TRY(hipHostFree(c->q_pin));
-    c->q_pin = nullptr; c->q_pin_cap = 0;
-    HIP_TRY(hipHostMalloc((void**)&c->q_pin, qn * sizeof(float), hipHostMallocDefault));
-    c->q_pin_cap = qn;
-  }
-  if (on > c->out_pin_cap) {
-    if (c->out_s_pin) HIP_TRY(hipHostFree(c->out_s_pin));
-    if (c->out_r_pin) HIP_TRY(hipHostFree(c->out_r_pin));
-    c->out_s_pin = nullptr; c->out_r_pin = nullptr; c->out_pin_cap = 0;
-    HIP_TRY(hipHostMalloc((void**)&c->out_s_pin, on * sizeof(float), hipHostMallocDefault));
-    HIP_TRY(hipHostMalloc((void**)&c->out_r_pin, on * sizeof(int64_t), hipHostMallocDefault));
-    c->out_pin_cap = on;
-  }
+  if ((rc = c->q_dev.grow(qn)) != SVS_OK) return rc;
+  if ((rc = c->q_pin.grow(qn)) != SVS_OK) return rc;
+  if ((rc = c->out_s_pin.grow(on)) != SVS_OK || (rc = c->out_r_pin.grow(on)) != SVS_OK) return rc;
   // The final top-k kernel stores its k results straight into the pinned host
   // buffers (device-visible, zero-copy): no D2H copies on the latency path.
   const auto t_begin = std::chrono::steady_clock::now();
@@ -2131,11 +2086,11 @@ static int32_t search_host(svs_index* idx, const float* queries, int32_t nq, int
   // ones: quantize_rows_fp8 reads its source twice -- row maximum, then the bytes -- and over the bus that cost configs[4]
   // 0.03-0.05 ms per call.  (Also measured and dropped: helper threads sharing the host copy -- their hand-offs cost what
   // they saved, 0.112 vs 0.088 ms to fill the pinned buffer; and the prefix pass per query tile, see SearchPlan.)
-  const bool pull = mode == 0 && idx->dtype == SVS_DTYPE_F16 && (uses_q16(idx, nq) || (nq >= 2 && tiled_ok(idx)));
-  const float* q_src = pull ? c->q_pin : c->q_dev;
+  const bool pull = mode == 0 && idx->dtype == SVS_DTYPE_F16 && is_batched(idx, nq);
+  const float* q_src = pull ? c->q_pin.p : c->q_dev.p;
   if (pull) {
     const int rows_total = staged_rows(idx, nq);            // the image of the WHOLE batch: sized once, before the first chunk
-    rc = grow_dev(&c->qh, &c->qh_cap, (size_t)rows_total * idx->ld);
+    rc = c->qh.grow((size_t)rows_total * idx->ld);
     int cq = 256;                                           // queries per chunk: <= 1 MiB, a power of two
     while (cq > 1 && (size_t)cq * d * sizeof(float) > ((size_t)1 << 20)) cq >>= 1;
     for (int q0 = 0; q0 < nq && rc == SVS_OK; q0 += cq) {
@@ -2164,11 +2119,7 @@ static int32_t search_host(svs_index* idx, const float* queries, int32_t nq, int
       std::lock_guard<std::mutex> lk(idx->mu);
       bool kept = false;
       for (auto& t : idx->evs) kept = kept || t.e0 == plan.ev.e0;
-      if (!kept) {
-        (void)hipEventDestroy(plan.ev.e0); (void)hipEventDestroy(plan.ev.e1); (void)hipEventDestroy(plan.ev.e2);
-        if (plan.ev.d0) (void)hipEventDestroy(plan.ev.d0);
-        if (plan.ev.d1) (void)hipEventDestroy(plan.ev.d1);
-      }
+      if (!kept) ev_destroy(plan.ev);
     }
     return rc;
   }
@@ -2188,24 +2139,12 @@ static int32_t search_host(svs_index* idx, const float* queries, int32_t nq, int
       if (c->out_r_pin[(size_t)q0 * count] == -2) grp[m++] = q0;
     if (m == 0) break;
     n_redo += m;
-    if ((size_t)REDO_BATCH * count > c->redo_pin_cap) {
-      if (c->redo_s_pin) HIP_TRY(hipHostFree(c->redo_s_pin));
-      if (c->redo_r_pin) HIP_TRY(hipHostFree(c->redo_r_pin));
-      c->redo_s_pin = nullptr; c->redo_r_pin = nullptr; c->redo_pin_cap = 0;
-      HIP_TRY(hipHostMalloc((void**)&c->redo_s_pin, (size_t)REDO_BATCH * count * sizeof(float), hipHostMallocDefault));
-      HIP_TRY(hipHostMalloc((void**)&c->redo_r_pin, (size_t)REDO_BATCH * count * sizeof(int64_t), hipHostMallocDefault));
-      c->redo_pin_cap = (size_t)REDO_BATCH * count;
-    }
+    if ((rc = c->redo_s_pin.grow((size_t)REDO_BATCH * count)) != SVS_OK || (rc = c->redo_r_pin.grow((size_t)REDO_BATCH * count)) != SVS_OK) return rc;
     // (the group's queries go to the front of q_dev in ONE copy -- whatever the main pass kept there is no longer needed,
     //  the pinned buffer still holds every query of the call; a group that is not one run of queries is gathered first)
     const float* src = c->q_pin + (size_t)grp[0] * d;
     if (grp[m - 1] - grp[0] != m - 1) {
-      if ((size_t)REDO_BATCH * d > c->redo_q_cap) {
-        if (c->redo_q_pin) HIP_TRY(hipHostFree(c->redo_q_pin));
-        c->redo_q_pin = nullptr; c->redo_q_cap = 0;
-        HIP_TRY(hipHostMalloc((void**)&c->redo_q_pin, (size_t)REDO_BATCH * d * sizeof(float), hipHostMallocDefault));
-        c->redo_q_cap = (size_t)REDO_BATCH * d;
-      }
+      if ((rc = c->redo_q_pin.grow((size_t)REDO_BATCH * d)) != SVS_OK) return rc;
       for (int j = 0; j < m; ++j) memcpy(c->redo_q_pin + (size_t)j * d, c->q_pin + (size_t)grp[j] * d, (size_t)d * sizeof(float));
       src = c->redo_q_pin;
     }
@@ -2236,48 +2175,6 @@ static int32_t search_host(svs_index* idx, const float* queries, int32_t nq, int
   return SVS_OK;
 }
 
-// One pass for everything that queued up while the device was busy.  The calling thread (the leader)
-// owns the pass: queries gathered into one batch, k = the largest asked for (a top-k list's first n
-// entries are the top-n list), results handed back to the waiters' own buffers.
-static void coalesced_pass(svs_index* idx, std::vector<svs_index::Waiter*>& batch, int d) {
-  const int nb = (int)batch.size();
-  int kmax = 0;
-  for (auto* w : batch) kmax = std::max(kmax, w->k);
-  int rc = SVS_OK;
-  int32_t count = 0;
-  std::vector<float> qs, ss;
-  std::vector<int64_t> rr;
-  try {
-    qs.resize((size_t)nb * d);
-    ss.resize((size_t)nb * kmax);
-    rr.resize((size_t)nb * kmax);
-  } catch (const std::bad_alloc&) {
-    rc = fail(SVS_ERR_NOMEM, "out of host memory for a coalesced pass");
-  }
-  if (rc == SVS_OK) {
-    for (int i = 0; i < nb; ++i) memcpy(qs.data() + (size_t)i * d, batch[i]->q, (size_t)d * sizeof(float));
-    rc = search_host(idx, qs.data(), nb, d, kmax, ss.data(), rr.data(), &count);
-  }
-  const std::string err = rc == SVS_OK ? std::string() : std::string(svs_last_error());
-  idx->co_passes.fetch_add(1);
-  idx->co_queries.fetch_add(nb);
-  idx->co_sizes[std::min(nb, 256)].fetch_add(1);
-  std::lock_guard<std::mutex> lk(idx->co_mu);
-  for (int i = 0; i < nb; ++i) {
-    svs_index::Waiter* w = batch[i];
-    w->rc = rc;
-    if (rc == SVS_OK) {
-      w->count = std::min(w->k, (int)count);
-      memcpy(w->out_s, ss.data() + (size_t)i * kmax, (size_t)w->count * sizeof(float));
-      memcpy(w->out_r, rr.data() + (size_t)i * kmax, (size_t)w->count * sizeof(int64_t));
-    } else {
-      w->err = err;
-    }
-    w->done = true;
-    if (!w->lead) w->cv.notify_one();
-  }
-}
-
 int32_t svs_index_search(svs_index* idx, const float* queries, int32_t nq, int32_t d, int32_t k,
                          float* out_scores, int64_t* out_rows, int32_t* out_count) {
   launch_reset();
@@ -2287,51 +2184,15 @@ int32_t svs_index_search(svs_index* idx, const float* queries, int32_t nq, int32
   if (!(idx->coalesce.load() && nq == 1 && k > 0 && k <= 2048 && d == idx->d && queries && out_scores && out_rows && idx->n > 0))
     return search_host(idx, queries, nq, d, k, out_scores, out_rows, out_count);
   RefGuard guard(idx);
-  svs_index::Waiter me;
-  me.q = queries; me.k = k; me.out_s = out_scores; me.out_r = out_rows;
-  {
-    std::unique_lock<std::mutex> lk(idx->co_mu);
-    idx->co_pending.push_back(&me);
-    if (idx->co_hold > 0) idx->co_hold_cv.notify_all();
-    if (!idx->co_busy) { idx->co_busy = true; me.lead = true; }
-    else me.cv.wait(lk, [&] { return me.done || me.lead; });
-  }
-  if (me.lead) {
-    // drive the device until this call's own query is answered, then hand over
-    std::vector<svs_index::Waiter*> batch;
-    while (!me.done) {
-      {
-        std::unique_lock<std::mutex> lk(idx->co_mu);
-        if (idx->co_hold > 0) {   // (tests / benchmarks: a pass of a chosen size; bounded, so a miscounted test cannot hang)
-          const int want = idx->co_hold;
-          idx->co_hold_cv.wait_for(lk, std::chrono::seconds(5), [&] { return (int)idx->co_pending.size() >= want; });
-          if (idx->co_hold == want) idx->co_hold = 0;   // (one shot; a hold set by another thread meanwhile stays)
-        }
-        // f32: whole kernel tiles -- the exact-f32 MFMA kernels cost the same for 33 queries as for 64 (1.8 vs 1.2 ms
-        // for 32), so a queue that does not fill the next tile size leaves its tail for the following pass.
-        // f16 / fp8: the passes are HBM-bound up to 128 queries and cost almost the same whatever they carry
-        // (1M x 1536 f16: 0.57 / 0.60 / 0.64 ms at 16 / 32 / 64 queries; fp8 0.32 / 0.33 / 0.40): cutting 40
-        // queued callers into 32 + 8 would cost two passes for the price of one, so everything queued goes out.
-        size_t take = std::min<size_t>(idx->co_pending.size(), 256);
-        if (idx->co_round.load() && idx->dtype == SVS_DTYPE_F32)
-          for (size_t g : {(size_t)128, (size_t)64, (size_t)32, (size_t)16})
-            if (take > g && take < 2 * g) { take = g; break; }
-        batch.assign(idx->co_pending.begin(), idx->co_pending.begin() + take);
-        idx->co_pending.erase(idx->co_pending.begin(), idx->co_pending.begin() + take);
-      }
-      coalesced_pass(idx, batch, d);
-    }
-    std::lock_guard<std::mutex> lk(idx->co_mu);
-    if (!idx->co_pending.empty()) {
-      idx->co_pending.front()->lead = true;   // (stays queued: its own loop takes it out)
-      idx->co_pending.front()->cv.notify_one();
-    } else {
-      idx->co_busy = false;
-    }
-  }
-  if (me.rc != SVS_OK) return fail(me.rc, "%s", me.err.c_str());
-  if (out_count) *out_count = me.count;
-  return SVS_OK;
+  // f32: whole kernel tiles -- the exact-f32 MFMA kernels cost the same for 33 queries as for 64 (1.8 vs 1.2 ms
+  // for 32), so a queue that does not fill the next tile size leaves its tail for the following pass.
+  // f16 / fp8: the passes are HBM-bound up to 128 queries and cost almost the same whatever they carry
+  // (1M x 1536 f16: 0.57 / 0.60 / 0.64 ms at 16 / 32 / 64 queries; fp8 0.32 / 0.33 / 0.40): cutting 40
+  // queued callers into 32 + 8 would cost two passes for the price of one, so everything queued goes out.
+  return idx->co.search(
+      queries, d, k, out_scores, out_rows, out_count,
+      [&](const float* q, int n, int kmax, float* s, int64_t* r, int32_t* cnt) { return search_host(idx, q, n, d, kmax, s, r, cnt); },
+      [&] { return idx->co_round.load() && idx->dtype == SVS_DTYPE_F32; });
 }
 
 int32_t svs_index_set_coalesce(svs_index* idx, int32_t enable) {
@@ -2343,8 +2204,8 @@ int32_t svs_index_set_coalesce(svs_index* idx, int32_t enable) {
 
 int32_t svs_index_coalesce_stats(svs_index* idx, int64_t* passes, int64_t* queries) {
   if (!idx) return fail(SVS_ERR_INVALID, "null index");
-  if (passes) *passes = idx->co_passes.load();
-  if (queries) *queries = idx->co_queries.load();
+  if (passes) *passes = idx->co.passes.load();
+  if (queries) *queries = idx->co.queries.load();
   return SVS_OK;
 }
 
@@ -2353,15 +2214,14 @@ int32_t svs_index_coalesce_stats(svs_index* idx, int64_t* passes, int64_t* queri
 int32_t svs_internal_coalesce_hold(svs_index* idx, int32_t n) {
   if (!idx) return fail(SVS_ERR_INVALID, "null index");
   if (n < 0 || n > 256) return fail(SVS_ERR_INVALID, "svs_internal_coalesce_hold: 0 <= n <= 256");
-  std::lock_guard<std::mutex> lk(idx->co_mu);
-  idx->co_hold = n;
+  idx->co.set_hold(n);
   return SVS_OK;
 }
 
 int32_t svs_index_coalesce_sizes(svs_index* idx, int64_t* out, int32_t cap) {
   if (!idx) return fail(SVS_ERR_INVALID, "null index");
   if (!out || cap < 0 || cap > 257) return fail(SVS_ERR_INVALID, "svs_index_coalesce_sizes: out must hold cap <= 257 counters");
-  for (int s = 0; s < cap; ++s) out[s] = idx->co_sizes[s].load();
+  for (int s = 0; s < cap; ++s) out[s] = idx->co.sizes[s].load();
   return SVS_OK;
 }
 
@@ -2382,10 +2242,10 @@ int32_t svs_index_search_device(svs_index* idx, const float* dev_queries, int32_
   hipStream_t st = (hipStream_t)hip_stream;
   Ctx* c = nullptr;
   if ((rc = ctx_acquire(idx, st, false, &c)) != SVS_OK) return rc;
-  struct CtxGuard { svs_index* i; Ctx* c; ~CtxGuard() { ctx_release(i, c); } } cg{idx, c};
+  CtxGuard cg{idx, c};
   // growing scratch frees buffers that earlier work on this stream may still read
   const size_t need_scores = (size_t)nq * (size_t)((idx->n + 3) & ~(int64_t)3);
-  if (c->async_pending && (need_scores > c->scores_cap || (size_t)nq > c->hist_cap)) HIP_TRY(hipStreamSynchronize(st));
+  if (c->async_pending && (need_scores > c->scores.cap || (size_t)nq > c->hist_cap)) HIP_TRY(hipStreamSynchronize(st));
   rc = enqueue_search(idx, c, dev_queries, nq, k, count, dev_out_scores, dev_out_rows, st);
   c->last_stream = st;
   c->async_pending = true;
@@ -2409,9 +2269,9 @@ int32_t svs_index_scores_n(svs_index* idx, const float* query, int32_t d, float*
   if ((rc = staging_wait(idx)) != SVS_OK) return rc;
   Ctx* c = nullptr;
   if ((rc = ctx_acquire(idx, nullptr, true, &c)) != SVS_OK) return rc;
-  struct CtxGuard { svs_index* i; Ctx* c; ~CtxGuard() { ctx_release(i, c); } } cg{idx, c};
-  if ((rc = grow_dev(&c->q_dev, &c->q_cap, (size_t)d)) != SVS_OK) return rc;
-  if ((rc = grow_dev(&c->scores, &c->scores_cap, (size_t)((idx->n + 3) & ~(int64_t)3))) != SVS_OK) return rc;
+  CtxGuard cg{idx, c};
+  if ((rc = c->q_dev.grow((size_t)d)) != SVS_OK) return rc;
+  if ((rc = c->scores.grow((size_t)((idx->n + 3) & ~(int64_t)3))) != SVS_OK) return rc;
   HIP_TRY(hipMemcpyAsync(c->q_dev, query, (size_t)d * sizeof(float), hipMemcpyHostToDevice, c->stream));
   launch_record("gemv", idx->n, 1);
   if ((rc = launch_scores(idx, c, c->q_dev, c->scores, c->stream)) != SVS_OK) return rc;
@@ -2447,14 +2307,9 @@ int32_t svs_index_search_rows(svs_index* idx, const float* queries, int32_t nq, 
   if ((rc = staging_wait(idx)) != SVS_OK) return rc;
   Ctx* c = nullptr;
   if ((rc = ctx_acquire(idx, nullptr, true, &c)) != SVS_OK) return rc;
-  struct CtxGuard { svs_index* i; Ctx* c; ~CtxGuard() { ctx_release(i, c); } } cg{idx, c};
+  CtxGuard cg{idx, c};
   // S = the live listed rows, ascending, as local u32 rows in pinned memory (the upload's source)
-  if ((size_t)nrows > c->list_pin_cap) {
-    if (c->list_pin) HIP_TRY(hipHostFree(c->list_pin));
-    c->list_pin = nullptr; c->list_pin_cap = 0;
-    HIP_TRY(hipHostMalloc((void**)&c->list_pin, (size_t)nrows * sizeof(uint32_t), hipHostMallocDefault));
-    c->list_pin_cap = (size_t)nrows;
-  }
+  if ((rc = c->list_pin.grow((size_t)nrows)) != SVS_OK) return rc;
   uint32_t* S = c->list_pin;
   int64_t m = 0;
   const uint8_t* dead = idx->dead_flag.data();
@@ -2481,22 +2336,10 @@ int32_t svs_index_search_rows(svs_index* idx, const float* queries, int32_t nq, 
   if (count == 0) return SVS_OK;
   hipStream_t st = c->stream;
   const size_t qn = (size_t)nq * (size_t)d, on = (size_t)nq * (size_t)count;
-  if ((rc = grow_dev(&c->q_dev, &c->q_cap, qn)) != SVS_OK) return rc;
-  if ((rc = grow_dev(&c->list_dev, &c->list_cap, (size_t)m)) != SVS_OK) return rc;
-  if (qn > c->q_pin_cap) {
-    if (c->q_pin) HIP_TRY(hipHostFree(c->q_pin));
-    c->q_pin = nullptr; c->q_pin_cap = 0;
-    HIP_TRY(hipHostMalloc((void**)&c->q_pin, qn * sizeof(float), hipHostMallocDefault));
-    c->q_pin_cap = qn;
-  }
-  if (on > c->out_pin_cap) {
-    if (c->out_s_pin) HIP_TRY(hipHostFree(c->out_s_pin));
-    if (c->out_r_pin) HIP_TRY(hipHostFree(c->out_r_pin));
-    c->out_s_pin = nullptr; c->out_r_pin = nullptr; c->out_pin_cap = 0;
-    HIP_TRY(hipHostMalloc((void**)&c->out_s_pin, on * sizeof(float), hipHostMallocDefault));
-    HIP_TRY(hipHostMalloc((void**)&c->out_r_pin, on * sizeof(int64_t), hipHostMallocDefault));
-    c->out_pin_cap = on;
-  }
+  if ((rc = c->q_dev.grow(qn)) != SVS_OK) return rc;
+  if ((rc = c->list_dev.grow((size_t)m)) != SVS_OK) return rc;
+  if ((rc = c->q_pin.grow(qn)) != SVS_OK) return rc;
+  if ((rc = c->out_s_pin.grow(on)) != SVS_OK || (rc = c->out_r_pin.grow(on)) != SVS_OK) return rc;
   memcpy(c->q_pin, queries, qn * sizeof(float));
   HIP_TRY(hipMemcpyAsync(c->q_dev, c->q_pin, qn * sizeof(float), hipMemcpyHostToDevice, st));
   HIP_TRY(hipMemcpyAsync(c->list_dev, S, (size_t)m * sizeof(uint32_t), hipMemcpyHostToDevice, st));
@@ -2504,13 +2347,9 @@ int32_t svs_index_search_rows(svs_index* idx, const float* queries, int32_t nq, 
   const int64_t sstride = (m + 3) & ~(int64_t)3;
   int64_t per_q = 4 * sstride;
   const bool window = m > SORT_CAP && count <= SEL_KMAX;
-  if (m > SORT_CAP && !window) {
-    int64_t npad;
-    next_pow2_i64(m, &npad);
-    per_q += 8 * npad;
-  }
+  if (m > SORT_CAP && !window) per_q += 8 * next_pow2_i64(m);
   const int qc = (int)std::max<int64_t>(1, std::min<int64_t>(nq, ((int64_t)2 << 30) / per_q));
-  if ((rc = grow_dev(&c->scores, &c->scores_cap, (size_t)qc * (size_t)sstride)) != SVS_OK) return rc;
+  if ((rc = c->scores.grow((size_t)qc * (size_t)sstride)) != SVS_OK) return rc;
   if (window && (rc = grow_select_scratch(c, qc, st)) != SVS_OK) return rc;
   for (int q0 = 0; q0 < nq && rc == SVS_OK; q0 += qc) {
     const int nc = std::min(qc, nq - q0);
@@ -2562,11 +2401,11 @@ int32_t svs_index_top_pairs(svs_index* idx, int32_t k, float* out_scores, int64_
   int rc;
   if ((rc = staging_wait(idx)) != SVS_OK) return rc;
   if ((rc = ctx_acquire(idx, nullptr, true, &c)) != SVS_OK) return rc;
-  struct CtxGuard { svs_index* i; Ctx* c; ~CtxGuard() { ctx_release(i, c); } } cg{idx, c};
+  CtxGuard cg{idx, c};
   // Small corpora: materialise n x n like the reference (src/svs/kb.py:1651).  Past n^2 = 2^32 scores
   // (or with variant 1, for A/B and tests): tiled GEMM with the i < j mask and a threshold in the
   // fused epilogue, nothing materialised but a prefix block.
-  if (n * np <= 0xffffffffll && idx->variant.load() != 1)
+  if (n * np <= 0xffffffffll && idx->variant.load() != VARIANT_GEMV_PERSISTENT_R1)
     return top_pairs_materialised(idx, c, n, count, out_scores, out_i, out_j);
   return top_pairs_tiled(idx, c, count, out_scores, out_i, out_j);
 }
@@ -2648,11 +2487,7 @@ int32_t svs_index_get_timing(svs_index* idx, svs_timing_t* out) {
     } else {
       rc = fail(SVS_ERR_DEVICE, "timing events: %s", hipGetErrorString(e));
     }
-    (void)hipEventDestroy(t.e0);
-    (void)hipEventDestroy(t.e1);
-    (void)hipEventDestroy(t.e2);
-    if (t.d0) (void)hipEventDestroy(t.d0);
-    if (t.d1) (void)hipEventDestroy(t.d1);
+    ev_destroy(t);
   }
   return rc;
 }
@@ -2729,7 +2564,7 @@ int32_t svs_internal_screen_stats(svs_index* idx, int64_t* out, int32_t cap) {
 
 int32_t svs_index_set_variant(svs_index* idx, int32_t variant) {
   if (!idx) return fail(SVS_ERR_INVALID, "null index");
-  if (variant < 0 || variant > 12) return fail(SVS_ERR_INVALID, "unknown variant %d", variant);
+  if (variant < VARIANT_DEFAULT || variant > VARIANT_LAST) return fail(SVS_ERR_INVALID, "unknown variant %d", variant);
   idx->variant.store(variant);
   return SVS_OK;
 }
