@@ -11,7 +11,7 @@
 //
 // Geometry per row length, as gemv_unrolled.h: T lanes share a row (T a power of two >= the row's
 // 16-byte chunks, up to the wave), a wave instruction covers 64 / T rows, rows longer than a wave take
-// NC chunks per lane; lanes past the row re-read its last chunk against a zero query chunk.
+// NC chunks per lane; lanes past the row re-read its last chunk (in bounds) and drop what it adds.
 //
 // Arithmetic per dtype (that dtype's single-query kernel):
 //   f32  f32 FMAs (DotF32)
@@ -130,7 +130,9 @@ __global__ __launch_bounds__(gather_wpb(NC) * 64) void gather_scores_kernel(
         // chunks decoded ahead of their FMAs, it would hold 16 registers per chunk instead of 4 and spill.  Empty
         // asm statements (kept in order) pin each chunk's decode between its own load and its FMAs.
         if constexpr (SCALED) asm volatile("" : "+v"(av));
-        acc[u] = dot.dot(av, qc, acc[u]);
+        // (lanes past the row keep their sum: the chunk they re-read may hold inf or NaN, and 0 * inf is NaN)
+        const float with_chunk = dot.dot(av, qc, acc[u]);
+        acc[u] = i < ld16 ? with_chunk : acc[u];
         if constexpr (SCALED) asm volatile("" : "+v"(acc[u]));
       }
     }

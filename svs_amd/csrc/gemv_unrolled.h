@@ -102,7 +102,7 @@ __global__ __launch_bounds__(UNR_WPB * 64) void gemv_unrolled_kernel(
 #pragma unroll
   for (int c = 0; c < NC; ++c) {
     const int i = sub + c * T;
-    col[c] = i < ld16 ? i : ld16 - 1;                       // lanes past the row re-read its last chunk
+    col[c] = i < ld16 ? i : ld16 - 1;                       // lanes past the row re-read its last chunk (in bounds)
     qv[c] = dot.prep(i < ld16 ? q[i] : (u32x4){0u, 0u, 0u, 0u});   // ... against a zero query chunk
   }
   {
@@ -121,7 +121,12 @@ __global__ __launch_bounds__(UNR_WPB * 64) void gemv_unrolled_kernel(
     for (int u = 0; u < U; ++u) {
       float acc = 0.f;
 #pragma unroll
-      for (int c = 0; c < NC; ++c) acc = dot.dot(a[u][c], qv[c], acc);
+      for (int c = 0; c < NC; ++c) {
+        // ... and drop the result: that chunk may hold inf or NaN, and 0 * inf is NaN where the row's score is +-inf
+        // (a select on the sum, not on the chunk: one instruction, and the row registers die where they did)
+        const float with_chunk = dot.dot(a[u][c], qv[c], acc);
+        acc = sub + c * T < ld16 ? with_chunk : acc;
+      }
       acc = seg_sum<T>(acc);
       const int64_t row = base + u * RPW + rsub;
       if (sub == 0 && row < n) scores[row] = dot.finish(acc, extra[u]);

@@ -25,8 +25,11 @@ int32_t svs_internal_tune(int32_t what, int64_t value);
 int32_t svs_internal_host_phases(double* out, int32_t n);
 /* The score kernels the calling thread's last svs_index_search, svs_index_search_device or svs_index_scores_n call
  * enqueued, in order (each of those calls starts a new record): kernels[i] is the kernel with its template arguments as
- * c++filt prints it ("gemm_phased_kernel<true, 2, 20, 256>"; a static string), or "gemv" for the single-query kernels
- * (one entry for a whole per-query loop); rows[i] its row count (a fused search's threshold pass covers fewer rows than
+ * c++filt prints it, without the svs:: of the function ("gemm_phased_kernel<true, 2, 20, 256>",
+ * "gemv_unrolled_kernel<64, 2, 4, svs::DotF16>"; a static string).  The single-query kernels are announced by one "gemv"
+ * entry for the whole per-query loop (nq = the loop's queries), followed by one entry per query with the kernel that
+ * query's launch_scores enqueued (nq = 1); a screened search lists its gemv_f16_oneshot_kernel and rescore_f32_kernel
+ * without a "gemv" entry.  rows[i] is the entry's row count (a fused search's threshold pass covers fewer rows than
  * the corpus); nq[i] its query count.  A fused search whose candidate lists overflowed lists the materialised re-run's
  * launches after its own.  Up to cap entries (and at most 32) are written; returns the number of launches recorded.
  * Coalesced single-query passes and svs_multi_* launch from other threads: they are not in the caller's record. */

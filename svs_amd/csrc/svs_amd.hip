@@ -98,8 +98,10 @@ std::atomic<int64_t> g_tune_spread{1};        // fused path: 1 = thresholds from
 std::atomic<int64_t> g_tune_refuse_shadow{0}; // 1 = every allocation of an f32 index's half shadow "fails" (tests of the best-effort path)
 thread_local double g_host_phase[6];          // svs_internal_host_phases: seconds since the call began (last svs_index_search on this thread)
 
-// svs_internal_last_launches: the score kernels the calling thread's last search / scores call enqueued, in order.  Fixed
-// thread-local slots and names that are compile-time constants: recording is a few stores, no allocation, no lock.
+// svs_internal_last_launches: the score kernels the calling thread's last search / scores call enqueued, in order: every
+// batched launch, and for the single-query kernels a "gemv" entry per loop (launch_scores_any, svs_index_scores_n)
+// followed by the kernel of each query (launch_scores).  Fixed thread-local slots and names that are compile-time
+// constants: recording is a few stores, no allocation, no lock; entries past LAUNCH_REC_CAP are dropped.
 struct LaunchRec {
   const char* kernel;
   int64_t rows;
@@ -131,6 +133,8 @@ constexpr KernelName kernel_name(const char* base, A... args) {
     if (i++) { k.s[p++] = ','; k.s[p++] = ' '; }
     if constexpr (std::is_same_v<decltype(v), bool>) {
       for (const char* c = v ? "true" : "false"; *c; ++c) k.s[p++] = *c;
+    } else if constexpr (std::is_same_v<decltype(v), const char*>) {   // a type argument, spelled by the caller
+      for (const char* c = v; *c; ++c) k.s[p++] = *c;
     } else {
       long long x = v;
       if (x < 0) { k.s[p++] = '-'; x = -x; }
@@ -485,6 +489,8 @@ template <int NSTEP, int R, int WPB, bool NT>
 void launch_oneshot(const svs_index* idx, const float* q, float* scores, hipStream_t st) {
   const int64_t rows_per_block = (int64_t)R * WPB;
   const int64_t blocks = (idx->n + rows_per_block - 1) / rows_per_block;
+  static constexpr KernelName name = kernel_name("gemv_f32_oneshot_kernel", NSTEP, R, WPB, NT, false, false);
+  launch_record(name.s, idx->n, 1);
   hipLaunchKernelGGL((gemv_f32_oneshot_kernel<NSTEP, R, WPB, NT, false>), dim3((unsigned)blocks), dim3(WPB * 64), 0, st,
                      (const v4f*)idx->rows, (const v4f*)q, scores, idx->n);
 }
@@ -494,6 +500,8 @@ void launch_persistent(const svs_index* idx, const float* q, float* scores, hipS
   constexpr int WPB = 4;
   const int64_t tiles = (idx->n + R - 1) / R;
   const int blocks = (int)std::min<int64_t>((tiles + WPB - 1) / WPB, (int64_t)idx->cu_count * 4);
+  static constexpr KernelName name = kernel_name("gemv_f32_rows_kernel", NSTEP, R, WPB, NT, false);
+  launch_record(name.s, idx->n, 1);
   hipLaunchKernelGGL((gemv_f32_rows_kernel<NSTEP, R, WPB, NT, false>), dim3(blocks), dim3(WPB * 64), 0, st,
                      (const v4f*)idx->rows, (const v4f*)q, scores, idx->n);
 }
@@ -522,18 +530,23 @@ void launch_generic(const svs_index* idx, const float* q, float* scores, hipStre
   constexpr int RPW = 64 / T;
   int64_t waves = (idx->n + RPW - 1) / RPW;
   int blocks = (int)std::min<int64_t>((waves + 3) / 4, (int64_t)idx->cu_count * 8);
+  static constexpr KernelName name = kernel_name("gemv_f32_generic_kernel", T);
+  launch_record(name.s, idx->n, 1);
   hipLaunchKernelGGL((gemv_f32_generic_kernel<T>), dim3(blocks), dim3(256), 0, st,
                      (const v4f*)idx->rows, q, scores, idx->n, idx->d, idx->ld / 4);
 }
 
 constexpr int f16_rows_r(int nstep) { return nstep <= 1 ? 4 : (nstep <= 3 ? 2 : 1); }
 constexpr int f16_rows_wpb(int nstep) { return nstep <= 6 ? 16 : 8; }
+template <int NSTEP>
+constexpr KernelName kF16OneshotName = kernel_name("gemv_f16_oneshot_kernel", NSTEP, f16_rows_r(NSTEP), f16_rows_wpb(NSTEP));
 // half_rows: the index's own rows (an f16 index) or the half shadow of an f32 index (screened search)
 template <int NSTEP>
 void launch_rows_f16(const svs_index* idx, const void* half_rows, const float* q, float* scores, hipStream_t st) {
   constexpr int R = f16_rows_r(NSTEP), WPB = f16_rows_wpb(NSTEP);
   const int64_t rows_per_block = (int64_t)R * WPB;
   const int64_t blocks = (idx->n + rows_per_block - 1) / rows_per_block;
+  launch_record(kF16OneshotName<NSTEP>.s, idx->n, 1);
   hipLaunchKernelGGL((gemv_f16_oneshot_kernel<NSTEP, R, WPB>), dim3((unsigned)blocks), dim3(WPB * 64), 0, st,
                      (const u32x4*)half_rows, (const v4f*)q, scores, idx->n);
 }
@@ -543,6 +556,8 @@ void launch_generic_f16(const svs_index* idx, const _Float16* qh, float* scores,
   constexpr int RPW = 64 / T;
   int64_t waves = (idx->n + RPW - 1) / RPW;
   int blocks = (int)std::min<int64_t>((waves + 3) / 4, (int64_t)idx->cu_count * 8);
+  static constexpr KernelName name = kernel_name("gemv_f16_generic_kernel", T);
+  launch_record(name.s, idx->n, 1);
   hipLaunchKernelGGL((gemv_f16_generic_kernel<T>), dim3(blocks), dim3(256), 0, st, (const u32x4*)idx->rows,
                      (const u32x4*)qh, scores, idx->n, idx->ld / 8);
 }
@@ -582,9 +597,17 @@ void launch_gemv_fp8(const svs_index* idx, Ctx* c, float* scores, hipStream_t st
   constexpr int RPW = 64 / T;
   int64_t waves = (idx->n + RPW - 1) / RPW;
   int blocks = (int)std::min<int64_t>((waves + 3) / 4, (int64_t)idx->cu_count * 8);
+  static constexpr KernelName name = kernel_name("gemv_fp8_kernel", T);
+  launch_record(name.s, idx->n, 1);
   hipLaunchKernelGGL((gemv_fp8_kernel<T>), dim3(blocks), dim3(256), 0, st, (const u32x4_t*)idx->rows, idx->row_scales,
                      (const v4f*)c->q8f.p, c->q8s, scores, idx->n, idx->ld / 16);
 }
+
+// The Dot argument of gemv_unrolled_kernel as c++filt prints it
+template <class Dot> constexpr const char* kDotName = nullptr;
+template <> constexpr const char* kDotName<DotF32> = "svs::DotF32";
+template <> constexpr const char* kDotName<DotF16> = "svs::DotF16";
+template <> constexpr const char* kDotName<DotFp8> = "svs::DotFp8";
 
 // Rows that are not whole 1 KiB wave loads (gemv_unrolled.h); false: longer than 16 KiB
 template <class Dot>
@@ -595,6 +618,8 @@ bool launch_unrolled(const svs_index* idx, const void* q_staged, int ld16, float
     constexpr int T = t(), NC = nc(), U = unrolled_u(NC);
     const int64_t groups = (idx->n + (64 / T) * U - 1) / ((64 / T) * U);
     const int64_t blocks = (groups + UNR_WPB - 1) / UNR_WPB;
+    static constexpr KernelName name = kernel_name("gemv_unrolled_kernel", T, NC, U, kDotName<Dot>);
+    launch_record(name.s, idx->n, 1);
     hipLaunchKernelGGL((gemv_unrolled_kernel<T, NC, U, Dot>), dim3((unsigned)blocks), dim3(UNR_WPB * 64), 0, st, M, q, scores, idx->n, ld16, dot);
   });
 }
@@ -621,6 +646,8 @@ int launch_scores(const svs_index* idx, Ctx* c, const float* q, float* scores, h
 #define SVS_FP8_HOT(NSTEP, LB, R)                                                                               \
   do {                                                                                                          \
     const int64_t blocks = (idx->n + (R) * 16 - 1) / ((R) * 16);                                                \
+    static constexpr KernelName name = kernel_name("gemv_fp8_oneshot_kernel", NSTEP, LB, R, 16);                \
+    launch_record(name.s, idx->n, 1);                                                                           \
     hipLaunchKernelGGL((gemv_fp8_oneshot_kernel<NSTEP, LB, R, 16>), dim3((unsigned)blocks), dim3(16 * 64), 0, st, \
                        (const uint8_t*)idx->rows, idx->row_scales, (const uint8_t*)c->q8, c->q8s, scores, idx->n);     \
     return SVS_OK;                                                                                              \
@@ -961,8 +988,6 @@ int run_select(svs_index* idx, Ctx* c, const float* scores, int64_t n_eff, int64
 // svs_index_set_variant(12) screens whatever n, 11 never.
 inline int64_t screen_min_rows(int ld) { return ld <= 512 ? 65536 : 32768; }
 
-template <int NSTEP>
-constexpr KernelName kScreenName = kernel_name("gemv_f16_oneshot_kernel", NSTEP, f16_rows_r(NSTEP), f16_rows_wpb(NSTEP));
 constexpr int rescore_u(int nstep) { return nstep <= 4 ? 4 : (nstep <= 8 ? 2 : 1); }
 template <int NSTEP>
 constexpr KernelName kRescoreName = kernel_name("rescore_f32_kernel", NSTEP, rescore_u(NSTEP));
@@ -996,7 +1021,7 @@ int launch_screen_scores(const svs_index* idx, Ctx* c, const float* q, float* sc
   int rc = pad_query(idx, c, q, q_padded, st);
   if (rc != SVS_OK) return rc;
   switch (idx->ld / 512) {
-#define SVS_ROWS_CASE(N) case N: launch_record(kScreenName<N>.s, idx->n, 1); launch_rows_f16<N>(idx, idx->shadow, *q_padded, scores, st); return SVS_OK;
+#define SVS_ROWS_CASE(N) case N: launch_rows_f16<N>(idx, idx->shadow, *q_padded, scores, st); return SVS_OK;
     SVS_ROWS_CASE(1) SVS_ROWS_CASE(2) SVS_ROWS_CASE(3) SVS_ROWS_CASE(4) SVS_ROWS_CASE(5) SVS_ROWS_CASE(6)
     SVS_ROWS_CASE(7) SVS_ROWS_CASE(8)
 #undef SVS_ROWS_CASE

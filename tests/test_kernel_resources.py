@@ -171,3 +171,69 @@ def test_every_shipped_gemm_kernel_has_a_test_case(build_reports):
     both = sorted(tested & set(AB_ONLY))
     assert not both, f"kernels both tested and listed as A/B-only: {both}"
     assert set(AB_ONLY.values()) <= {3, 4, 8, 9}
+
+
+def _gemv_instantiations(table):
+    """'gemv_unrolled_kernel<64, 2, 4, svs::DotF16>', ...: every single-query score kernel in the report."""
+    names = _demangle([n for n in table if "gemv_" in n])
+    out = set()
+    for pretty in names.values():
+        m = re.search(r"(gemv_\w+<[^>]*>)", pretty)
+        assert m, pretty
+        out.add(m.group(1))
+    return out
+
+
+def test_every_shipped_gemv_kernel_has_a_test_case(build_reports):
+    """Every single-query score kernel in the library (gemv_*: one-shot, persistent, unrolled and loop kernels of the
+    three dtypes) has a row in tests/single_kernel_table.py, which tests/test_single_kernels_gpu.py runs, asserting the
+    kernel was reached -- or is on the table's short list of instantiations that no index can launch.  A kernel added
+    without a case, or a row deleted from the table, fails here, on CPU."""
+    from single_kernel_table import CASES, LONG_ROWS, NO_SHAPE
+    built = _gemv_instantiations(_resources(build_reports[0]))
+    assert len(built) >= 161, sorted(built)
+    tested = {c[3] for c in CASES}
+    assert len(tested) == len(CASES), "two rows of CASES name one kernel"
+    untested = sorted(built - tested - set(NO_SHAPE))
+    assert not untested, f"kernels in the build that tests/single_kernel_table.py has no row for: {untested}"
+    stale = sorted((tested | set(NO_SHAPE)) - built)
+    assert not stale, f"kernels the table names that the build does not hold: {stale}"
+    assert not tested & set(NO_SHAPE)
+    assert {c[3] for c in LONG_ROWS} <= tested
+    assert {c[2] for c in CASES} == {0, 1, 2, 3, 4, 5}
+
+
+def _geometry(chunks):
+    """(T, NC) of for_row_geometry / for_width for a row of `chunks` 16-byte chunks (NC None: too long to unroll)."""
+    if chunks <= 64:
+        return next(t for t in (1, 2, 4, 8, 16, 32, 64) if t >= chunks), 1
+    return 64, next((nc for nc in (2, 3, 4, 6, 8, 12, 16) if 64 * nc >= chunks), None)
+
+
+def test_single_kernel_table_rows_have_the_row_length_their_kernel_takes():
+    """Each row's d, through the padding rule, is a row length of its kernel's geometry (which kernel really runs is
+    asserted on the GPU); and no f32 dimension gives a row that gemv_unrolled_kernel<64, 12 | 16, 1, svs::DotF32>
+    would take -- the two instantiations the table lists as unreachable."""
+    from single_kernel_table import CASES, FP8_HOT, LONG_ROWS, NO_SHAPE, PER16, choose_ld
+    for dtype, d, variant, kernel in CASES + LONG_ROWS:
+        ld = choose_ld(d, dtype)
+        chunks, args = ld // PER16[dtype], kernel[kernel.index("<") + 1:-1].split(", ")
+        assert ld % PER16[dtype] == 0 and ld >= d
+        if "oneshot" in kernel or "rows_kernel" in kernel:
+            assert ld == d, (dtype, d, ld)
+            if dtype == "fp8":
+                assert FP8_HOT[ld] == tuple(int(a) for a in args[:3]) and ld == int(args[0]) * 64 * int(args[1])
+            else:
+                assert chunks == 64 * int(args[0]) and chunks <= (1024 if dtype == "f32" else 512), (kernel, ld)
+        else:
+            exact = chunks % 64 == 0 and (chunks <= 1024 if dtype == "f32" else chunks <= 512 if dtype == "f16" else ld in FP8_HOT)
+            assert not exact, f"{dtype} d={d}: ld {ld} is a one-shot kernel's"
+            t, nc = _geometry(chunks)
+            if kernel.startswith("gemv_unrolled_kernel"):
+                assert variant == 0 and chunks <= 1024 and (t, nc) == (int(args[0]), int(args[1])), (kernel, d, ld)
+            else:
+                assert t == int(args[0]) and (variant == 4) == (chunks <= 1024), (kernel, d, ld)
+    assert sorted(NO_SHAPE) == ["gemv_unrolled_kernel<64, 12, 1, svs::DotF32>", "gemv_unrolled_kernel<64, 16, 1, svs::DotF32>"]
+    for d in range(1, 4097):      # (longer rows are more than 1024 chunks: not the unrolled kernel's)
+        chunks = choose_ld(d, "f32") // 4
+        assert chunks <= 512 or chunks % 64 == 0, f"f32 d={d}: {chunks} chunks would reach an unrolled kernel of 12 or 16 chunks per lane"
