@@ -196,6 +196,27 @@ int32_t svs_index_search_device(svs_index* idx, const float* dev_queries, int32_
                                 int32_t k, float* dev_out_scores, int64_t* dev_out_rows,
                                 int32_t* out_count, void* hip_stream);
 
+/* svs_index_search_device for back-to-back single queries: the score pass of one search runs beside the
+ * selection kernels of the search before it.  Same arguments, outputs and results (rows, order, score bits).
+ *   - Results are ordered on `hip_stream` exactly as with svs_index_search_device: work enqueued on that
+ *     stream after the call sees them.
+ *   - The SCORE stage runs on a stream of the library's own, one pass after another, and may start before
+ *     earlier work on `hip_stream` has finished: the query is NOT ordered by that stream.  If
+ *     `query_ready_event` (a hipEvent_t) is not NULL, the score stage runs once that event has fired; if it
+ *     is NULL, the query must already be complete on the device when the call is made.
+ *   - The query buffer may be reused by work ordered on `hip_stream` after the call (the stream waits for
+ *     the score pass and for everything else that reads the query).
+ *   - With nq != 1 the call is svs_index_search_device (behind query_ready_event, if given).
+ *   - An index keeps at most four pipelines, one per caller stream.  A stream that has none when four exist takes
+ *     over one whose work has all finished (least recently used first), so any number of streams may use the
+ *     entry one after another.  Only while four OTHER streams each have such searches still in flight is the
+ *     call an svs_index_search_device call: same results, no overlap.
+ * Ingest (append, reserve, staging commit, mask_rows, set_screen) and svs_index_release may be called with
+ * such searches enqueued, as with svs_index_search_device: they wait for what they would disturb. */
+int32_t svs_index_search_device_ahead(svs_index* idx, const float* dev_query, int32_t nq, int32_t d, int32_t k,
+                                      float* dev_out_scores, int64_t* dev_out_rows, int32_t* out_count,
+                                      void* hip_stream, void* query_ready_event);
+
 /* All scores of one query, f32 (n) to host: the raw `np.dot(M, q)` vector
  * (src/svs/kb.py:1623) for callers that want it and for parity tests.  The call writes one float per
  * row the handle holds WHEN IT RUNS and never more than out_capacity: a handle that has grown past the

@@ -80,6 +80,7 @@ SIGNATURES = {
     "svs_index_info": (C.c_int32, [_P, C.POINTER(IndexInfo)]),
     "svs_index_search": (C.c_int32, [_P, _P, C.c_int32, C.c_int32, C.c_int32, _P, _P, C.POINTER(C.c_int32)]),
     "svs_index_search_device": (C.c_int32, [_P, _P, C.c_int32, C.c_int32, C.c_int32, _P, _P, C.POINTER(C.c_int32), _P]),
+    "svs_index_search_device_ahead": (C.c_int32, [_P, _P, C.c_int32, C.c_int32, C.c_int32, _P, _P, C.POINTER(C.c_int32), _P, _P]),
     "svs_index_scores_n": (C.c_int32, [_P, _P, C.c_int32, _P, C.c_int64, C.POINTER(C.c_int64)]),
     "svs_index_search_rows": (C.c_int32, [_P, _P, C.c_int32, C.c_int32, C.c_int32, _P, C.c_int64, _P, _P, C.POINTER(C.c_int32)]),
     "svs_index_top_pairs": (C.c_int32, [_P, C.c_int32, _P, _P, _P, C.POINTER(C.c_int32)]),
@@ -98,6 +99,7 @@ INTERNAL = {
     "svs_internal_host_phases": (C.c_int32, [C.POINTER(C.c_double), C.c_int32]),
     "svs_internal_last_launches": (C.c_int32, [C.POINTER(C.c_char_p), C.POINTER(C.c_int64), C.POINTER(C.c_int32), C.c_int32]),
     "svs_internal_screen_stats": (C.c_int32, [_P, C.POINTER(C.c_int64), C.c_int32]),
+    "svs_internal_ahead_stats": (C.c_int32, [_P, C.POINTER(C.c_int64), C.c_int32]),
 }
 
 _lib: Optional[C.CDLL] = None

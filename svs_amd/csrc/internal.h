@@ -40,6 +40,10 @@ int32_t svs_internal_last_launches(const char** kernels, int64_t* rows, int32_t*
  * paused until the next ingest (fallbacks dominated), [4] bits of the bound E and [5] candidate count of the calling
  * thread's last screened search, [6..8] bits of the corpus statistics A, B, C. */
 int32_t svs_internal_screen_stats(svs_index* idx, int64_t* out, int32_t cap);
+/* svs_index_search_device_ahead on this handle, up to cap (<= 4) values: [0] single-query calls that went through a
+ * pipeline, [1] single-query calls that were plain calls because every pipeline had work in flight, [2] idle
+ * pipelines handed over to another caller stream, [3] pipelines that exist. */
+int32_t svs_internal_ahead_stats(svs_index* idx, int64_t* out, int32_t cap);
 /* multi.hip -> svs_amd.hip: carries a worker thread's error message over to the caller's thread */
 int32_t svs_internal_set_error(int32_t code, const char* msg);
 #ifdef __cplusplus

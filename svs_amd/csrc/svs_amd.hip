@@ -191,6 +191,21 @@ struct Ctx {
   int slot = 0;                 // this context's counters in svs_index::scr_dev / scr_host (screened search)
 };
 
+// svs_index_search_device_ahead: the ordered pipeline of one (index, caller stream).  Score passes run one after
+// another on `pass`; search i uses ctx[i & 1], and its selection chain runs on the caller's stream behind pass_done,
+// beside the pass of search i + 1.  The two contexts never enter svs_index::free_ctx and own no stream.
+struct AheadPipe {
+  std::mutex mu;                               // one ahead call at a time per pipeline
+  hipStream_t caller = nullptr;                // the key
+  hipStream_t pass = nullptr;
+  Ctx* ctx[2] = {nullptr, nullptr};
+  hipEvent_t pass_done[2] = {nullptr, nullptr};   // on `pass`, behind the score half of the context's last search
+  hipEvent_t sel_done[2] = {nullptr, nullptr};    // on the caller's stream, behind its selection half: the last reader of the scratch
+  bool used[2] = {false, false};
+  uint64_t seq = 0;
+  uint64_t tick = 0;                           // svs_index::pipe_tick of the last call that looked it up (under svs_index::mu)
+};
+
 }  // namespace
 
 struct svs_index {
@@ -227,7 +242,7 @@ struct svs_index {
   // allocation that fails drops the shadow and the index searches unscreened.
   void* shadow = nullptr;
   size_t shadow_bytes = 0;
-  uint32_t* scr_dev = nullptr;         // ScreenStats, then kMaxCtx x SCREEN_SLOT_WORDS per-context counters
+  uint32_t* scr_dev = nullptr;         // ScreenStats, then kSlots x SCREEN_SLOT_WORDS per-context counters
   uint32_t* scr_host = nullptr;        // pinned mirror of the counters, written by the kernels
   std::atomic<bool> shadow_bad{false}; // an element that half cannot hold: never screens again
   bool shadow_gave_up = false;         // an allocation failed: not retried until svs_index_set_screen(1)
@@ -241,6 +256,15 @@ struct svs_index {
   std::vector<Ctx*> free_ctx;
   int n_ctx = 0;
   static constexpr int kMaxCtx = 8;
+  // svs_index_search_device_ahead: one pipeline per caller stream (guarded by mu), at most kMaxPipes of them; they
+  // live until the index goes.  A stream that has none when all exist takes over the least recently used pipeline
+  // that is IDLE (pipe_get); only when every pipeline has work in flight is the call a plain one, and counted.
+  // Counter slots: the pooled contexts take [0, kMaxCtx), pipeline p's two contexts kMaxCtx + 2 p and the next.
+  static constexpr int kMaxPipes = 4;
+  static constexpr int kSlots = kMaxCtx + 2 * kMaxPipes;
+  std::vector<AheadPipe*> pipes;
+  uint64_t pipe_tick = 0;
+  std::atomic<int64_t> ahead_calls{0}, ahead_plain{0}, ahead_retired{0};   // svs_internal_ahead_stats
 
   // cold-start staging (svs_index_staging_*): two pinned blocks, DMA'd on their own stream
   struct Staging {
@@ -277,6 +301,31 @@ void ctx_destroy(Ctx* c) {
   if (st) (void)hipStreamDestroy(st);
 }
 
+// Everything the pipeline has enqueued is over: its passes, and the selection chains on the caller's stream.  The
+// chains are waited for through the pipeline's OWN events (the caller may have destroyed its stream since; an event
+// that was never recorded counts as fired).
+hipError_t pipe_drain(AheadPipe* p) {
+  hipError_t e = hipStreamSynchronize(p->pass);
+  for (int j = 0; j < 2; ++j) {
+    const hipError_t e2 = p->sel_done[j] ? hipEventSynchronize(p->sel_done[j]) : hipSuccess;
+    if (e == hipSuccess) e = e2;
+    p->used[j] = false;
+  }
+  return e;
+}
+
+void pipe_destroy(AheadPipe* p) {
+  if (!p) return;
+  if (p->pass) (void)pipe_drain(p);
+  for (int j = 0; j < 2; ++j) {
+    ctx_destroy(p->ctx[j]);   // (drained above; the contexts own no stream)
+    if (p->pass_done[j]) (void)hipEventDestroy(p->pass_done[j]);
+    if (p->sel_done[j]) (void)hipEventDestroy(p->sel_done[j]);
+  }
+  if (p->pass) (void)hipStreamDestroy(p->pass);
+  delete p;
+}
+
 void staging_free(svs_index* idx) {
   auto& g = idx->stg;
   if (g.st) (void)hipStreamSynchronize(g.st);
@@ -295,6 +344,7 @@ void staging_free(svs_index* idx) {
 void index_destroy(svs_index* idx) {
   (void)hipSetDevice(idx->device);
   staging_free(idx);
+  for (AheadPipe* p : idx->pipes) pipe_destroy(p);   // (before the rows go: drains their passes and selection chains)
   for (Ctx* c : idx->free_ctx) ctx_destroy(c);
   for (auto& t : idx->evs) ev_destroy(t);
   (void)hipFree(idx->rows);
@@ -1002,7 +1052,7 @@ bool screen_ready(const svs_index* idx) {
 void screen_review(svs_index* idx) {
   uint64_t s_tot = 0, f_tot = 0;
   const volatile uint32_t* h = idx->scr_host;
-  for (int i = 0; i < svs_index::kMaxCtx; ++i) {
+  for (int i = 0; i < svs_index::kSlots; ++i) {
     s_tot += h[i * SCREEN_SLOT_WORDS];
     f_tot += h[i * SCREEN_SLOT_WORDS + 1];
   }
@@ -1230,6 +1280,7 @@ struct SearchPlan {
   bool screen = false;   // one query over an f32 index with a valid half shadow: screen.h
   bool staged = false;   // the caller has staged the queries in the corpus dtype already (search_host, chunk by chunk)
   int64_t n_mat = 0, sstride = 0;
+  const float* q_padded = nullptr;   // screened search: the query as launch_screen_scores staged it (the re-score reads it)
   EvTriple ev{};
 };
 
@@ -1316,9 +1367,12 @@ int enqueue_prefix(svs_index* idx, Ctx* c, const SearchPlan& p, const float* q_d
   return SVS_OK;
 }
 
-int enqueue_main(svs_index* idx, Ctx* c, SearchPlan& p, const float* q_dev, float* out_s, int64_t* out_r, hipStream_t st) {
+// enqueue_main in two halves, so that svs_index_search_device_ahead can put them on two streams: everything up to and
+// including the `e1` timing event (query padding and staging, the screen pass or the score launch, the tombstone
+// mask), then the selection.  Both take the same plan; q_padded carries the staged query of a screened search across.
+int enqueue_score_half(svs_index* idx, Ctx* c, SearchPlan& p, const float* q_dev, hipStream_t st) {
   const int64_t n = idx->n;
-  const int nq = p.nq, k = p.k, count = p.count;
+  const int nq = p.nq, count = p.count;
   int rc;
   EvTriple& ev = p.ev;
   if (p.fused) {
@@ -1332,25 +1386,33 @@ int enqueue_main(svs_index* idx, Ctx* c, SearchPlan& p, const float* q_dev, floa
     if ((rc = launch_scores_any(idx, c, q_dev, n, nq, nullptr, 0, fl, st, false)) != SVS_OK) return rc;
     if (p.timed) HIP_TRY(hipEventRecord(ev.d1, st));
     if (p.timed) HIP_TRY(hipEventRecord(ev.e1, st));
+    return SVS_OK;
+  }
+  if (p.screen) {
+    if ((rc = launch_screen_scores(idx, c, q_dev, c->scores, &p.q_padded, st)) != SVS_OK) return rc;
+  } else if ((rc = launch_scores_any(idx, c, q_dev, n, nq, c->scores, p.sstride, FuseLaunch{}, st, !p.staged)) != SVS_OK) {
+    return rc;
+  }
+  if (!idx->dead_list.empty())   // tombstoned rows can never be returned
+    hipLaunchKernelGGL(mask_dead_rows_kernel, dim3(64), dim3(256), 0, st, c->scores, p.sstride, nq, idx->dead_dev,
+                       (int64_t)idx->dead_list.size(), n, (int64_t)0);
+  if (p.timed) HIP_TRY(hipEventRecord(ev.e1, st));
+  return SVS_OK;
+}
+
+int enqueue_select_half(svs_index* idx, Ctx* c, SearchPlan& p, float* out_s, int64_t* out_r, hipStream_t st) {
+  const int64_t n = idx->n;
+  const int nq = p.nq, k = p.k, count = p.count;
+  int rc;
+  EvTriple& ev = p.ev;
+  if (p.fused) {
     hipLaunchKernelGGL(select_final_kernel, dim3(nq), dim3(FINAL_THREADS), 0, st, (const float*)nullptr, n, (int64_t)0, k, count, 3,
                        c->hist, c->cand, idx->row_offset, out_s, out_r,
                        (const uint32_t*)(idx->dead_list.empty() ? nullptr : idx->dead_bits_dev.p));
-  } else {
-    const float* q_padded = nullptr;
-    if (p.screen) {
-      if ((rc = launch_screen_scores(idx, c, q_dev, c->scores, &q_padded, st)) != SVS_OK) return rc;
-    } else if ((rc = launch_scores_any(idx, c, q_dev, n, nq, c->scores, p.sstride, FuseLaunch{}, st, !p.staged)) != SVS_OK) {
-      return rc;
-    }
-    if (!idx->dead_list.empty())   // tombstoned rows can never be returned
-      hipLaunchKernelGGL(mask_dead_rows_kernel, dim3(64), dim3(256), 0, st, c->scores, p.sstride, nq, idx->dead_dev,
-                         (int64_t)idx->dead_list.size(), n, (int64_t)0);
-    if (p.timed) HIP_TRY(hipEventRecord(ev.e1, st));
-    if (p.screen) {   // (stage_ms.score is the screen pass; the exact re-score of the candidates counts as select)
-      if ((rc = run_select_screened(idx, c, q_padded, k, count, out_s, out_r, st)) != SVS_OK) return rc;
-    } else if (k > 0 && (rc = run_select(idx, c, c->scores, n, p.sstride, nq, k, count, out_s, out_r, st, idx->row_offset)) != SVS_OK) {
-      return rc;
-    }
+  } else if (p.screen) {   // (stage_ms.score is the screen pass; the exact re-score of the candidates counts as select)
+    if ((rc = run_select_screened(idx, c, p.q_padded, k, count, out_s, out_r, st)) != SVS_OK) return rc;
+  } else if (k > 0 && (rc = run_select(idx, c, c->scores, n, p.sstride, nq, k, count, out_s, out_r, st, idx->row_offset)) != SVS_OK) {
+    return rc;
   }
   HIP_TRY(hipGetLastError());
   if (p.timed) {
@@ -1359,6 +1421,12 @@ int enqueue_main(svs_index* idx, Ctx* c, SearchPlan& p, const float* q_dev, floa
     idx->evs.push_back(ev);
   }
   return SVS_OK;
+}
+
+int enqueue_main(svs_index* idx, Ctx* c, SearchPlan& p, const float* q_dev, float* out_s, int64_t* out_r, hipStream_t st) {
+  int rc = enqueue_score_half(idx, c, p, q_dev, st);
+  if (rc != SVS_OK) return rc;
+  return enqueue_select_half(idx, c, p, out_s, out_r, st);
 }
 
 int enqueue_search(svs_index* idx, Ctx* c, const float* q_dev, int nq, int k, int count,
@@ -1651,7 +1719,7 @@ bool shadow_alloc(svs_index* idx, int64_t rows_cap, void** out) {
   *out = nullptr;
   if (g_tune_refuse_shadow.load() || rows_cap <= 0) return false;
   if (!idx->scr_dev) {
-    const size_t words = sizeof(ScreenStats) / 4 + (size_t)svs_index::kMaxCtx * SCREEN_SLOT_WORDS;
+    const size_t words = sizeof(ScreenStats) / 4 + (size_t)svs_index::kSlots * SCREEN_SLOT_WORDS;
     if (hipMalloc((void**)&idx->scr_dev, words * 4) != hipSuccess || hipMemset(idx->scr_dev, 0, words * 4) != hipSuccess) {
       (void)hipGetLastError();
       (void)hipFree(idx->scr_dev);
@@ -1660,7 +1728,7 @@ bool shadow_alloc(svs_index* idx, int64_t rows_cap, void** out) {
     }
   }
   if (!idx->scr_host) {
-    const size_t bytes = (size_t)svs_index::kMaxCtx * SCREEN_SLOT_WORDS * 4;
+    const size_t bytes = (size_t)svs_index::kSlots * SCREEN_SLOT_WORDS * 4;
     if (hipHostMalloc((void**)&idx->scr_host, bytes, hipHostMallocDefault) != hipSuccess) {
       (void)hipGetLastError();
       idx->scr_host = nullptr;
@@ -2250,9 +2318,102 @@ int32_t svs_index_coalesce_sizes(svs_index* idx, int64_t* out, int32_t cap) {
   return SVS_OK;
 }
 
-int32_t svs_index_search_device(svs_index* idx, const float* dev_queries, int32_t nq, int32_t d,
-                                int32_t k, float* dev_out_scores, int64_t* dev_out_rows,
-                                int32_t* out_count, void* hip_stream) {
+// Nothing the pipeline enqueued is still running (no call is inside it either: the caller holds p->mu).  Leaves no
+// "not ready" behind for a later hipGetLastError.
+static bool pipe_idle(AheadPipe* p) {
+  bool idle = hipStreamQuery(p->pass) == hipSuccess;
+  for (int j = 0; j < 2 && idle; ++j) idle = !p->used[j] || hipEventQuery(p->sel_done[j]) == hipSuccess;
+  (void)hipGetLastError();
+  return idle;
+}
+
+// The pipeline of (idx, caller), made on first use.  When kMaxPipes exist and none is this stream's, the least
+// recently used one that is idle is handed over: a pipeline's stream, contexts and events serve any caller stream
+// (the key only finds it again), and an idle one has no ordering left to keep.  *out stays null when every pipeline
+// has work in flight: the call is then a plain one (ahead_plain counts them).
+static int pipe_get(svs_index* idx, hipStream_t caller, AheadPipe** out) {
+  *out = nullptr;
+  std::lock_guard<std::mutex> lk(idx->mu);
+  for (AheadPipe* p : idx->pipes)
+    if (p->caller == caller) {
+      p->tick = ++idx->pipe_tick;
+      *out = p;
+      return SVS_OK;
+    }
+  if ((int)idx->pipes.size() >= svs_index::kMaxPipes) {
+    AheadPipe* pick = nullptr;
+    for (AheadPipe* p : idx->pipes) {
+      if (pick && p->tick >= pick->tick) continue;
+      if (!p->mu.try_lock()) continue;   // (a call is enqueuing on it)
+      if (pipe_idle(p)) pick = p;
+      p->mu.unlock();
+    }
+    if (!pick) return SVS_OK;
+    pick->caller = caller;
+    pick->tick = ++idx->pipe_tick;
+    idx->ahead_retired.fetch_add(1);
+    *out = pick;
+    return SVS_OK;
+  }
+  AheadPipe* p = new (std::nothrow) AheadPipe();
+  if (!p) return fail(SVS_ERR_NOMEM, "host allocation failed");
+  p->caller = caller;
+  p->tick = ++idx->pipe_tick;
+  hipError_t e = hipStreamCreateWithFlags(&p->pass, hipStreamNonBlocking);
+  for (int j = 0; j < 2 && e == hipSuccess; ++j) {
+    p->ctx[j] = new (std::nothrow) Ctx();
+    if (!p->ctx[j]) { e = hipErrorOutOfMemory; break; }
+    p->ctx[j]->slot = svs_index::kMaxCtx + 2 * (int)idx->pipes.size() + j;
+    e = hipEventCreateWithFlags(&p->pass_done[j], hipEventDisableTiming);
+    if (e == hipSuccess) e = hipEventCreateWithFlags(&p->sel_done[j], hipEventDisableTiming);
+  }
+  if (e != hipSuccess) {
+    pipe_destroy(p);
+    return fail(e == hipErrorOutOfMemory ? SVS_ERR_NOMEM : SVS_ERR_DEVICE, "run-ahead pipeline: %s", hipGetErrorString(e));
+  }
+  idx->pipes.push_back(p);
+  *out = p;
+  return SVS_OK;
+}
+
+// One single-query search through the pipeline: score half on the pass stream (behind the query's event and behind
+// the selection that last read this context's scratch), selection half on the caller's stream behind the pass.
+static int enqueue_ahead(svs_index* idx, AheadPipe* pipe, const float* q_dev, int k, int count, float* out_s, int64_t* out_r,
+                         hipStream_t st, hipEvent_t query_ready) {
+  std::lock_guard<std::mutex> lk(pipe->mu);
+  const int j = (int)(pipe->seq & 1);
+  Ctx* c = pipe->ctx[j];
+  // growing scratch frees buffers that the context's earlier search may still read (the histogram and candidate
+  // scratch grows on the window path only -- plan_search's path_a; the sort keys of path B grow with n, like scores)
+  const size_t need_scores = (size_t)((idx->n + 3) & ~(int64_t)3);
+  const bool path_a = idx->n > SORT_CAP && count <= SEL_KMAX;
+  if (pipe->used[j] && (need_scores > c->scores.cap || (path_a && c->hist_cap < 1))) HIP_TRY(pipe_drain(pipe));
+  if (query_ready) HIP_TRY(hipStreamWaitEvent(pipe->pass, query_ready, 0));
+  if (pipe->used[j]) HIP_TRY(hipStreamWaitEvent(pipe->pass, pipe->sel_done[j], 0));
+  SearchPlan p;
+  int rc = plan_search(idx, c, 1, k, count, pipe->pass, false, &p);
+  if (rc == SVS_OK) rc = enqueue_score_half(idx, c, p, q_dev, pipe->pass);
+  auto hip_step = [&](hipError_t e, const char* what) {
+    if (rc == SVS_OK && e != hipSuccess) rc = fail(SVS_ERR_DEVICE, "run-ahead pipeline, %s: %s", what, hipGetErrorString(e));
+  };
+  if (rc == SVS_OK) hip_step(hipEventRecord(pipe->pass_done[j], pipe->pass), "pass event");
+  if (rc == SVS_OK) hip_step(hipStreamWaitEvent(st, pipe->pass_done[j], 0), "wait for the pass");
+  if (rc == SVS_OK) rc = enqueue_select_half(idx, c, p, out_s, out_r, st);
+  if (rc == SVS_OK) hip_step(hipEventRecord(pipe->sel_done[j], st), "selection event");
+  if (rc != SVS_OK) {   // nothing half enqueued outlives a failed call
+    (void)hipStreamSynchronize(st);
+    (void)pipe_drain(pipe);
+    return rc;
+  }
+  pipe->used[j] = true;
+  pipe->seq++;
+  return SVS_OK;
+}
+
+// svs_index_search_device and svs_index_search_device_ahead (ahead: single queries go through the caller stream's
+// pipeline; everything else is the plain call, behind the query's event if one was given)
+static int32_t search_device(svs_index* idx, const float* dev_queries, int32_t nq, int32_t d, int32_t k, float* dev_out_scores,
+                             int64_t* dev_out_rows, int32_t* out_count, void* hip_stream, bool ahead, void* query_ready_event) {
   launch_reset();
   if (!idx) return fail(SVS_ERR_INVALID, "null index");
   RefGuard guard(idx);
@@ -2265,6 +2426,16 @@ int32_t svs_index_search_device(svs_index* idx, const float* dev_queries, int32_
   if (!dev_out_scores || !dev_out_rows) return fail(SVS_ERR_INVALID, "null output");
   HIP_TRY(hipSetDevice(idx->device));
   hipStream_t st = (hipStream_t)hip_stream;
+  if (ahead && nq == 1) {
+    AheadPipe* pipe = nullptr;
+    if ((rc = pipe_get(idx, st, &pipe)) != SVS_OK) return rc;
+    if (pipe) {
+      idx->ahead_calls.fetch_add(1);
+      return enqueue_ahead(idx, pipe, dev_queries, k, count, dev_out_scores, dev_out_rows, st, (hipEvent_t)query_ready_event);
+    }
+    idx->ahead_plain.fetch_add(1);
+  }
+  if (ahead && query_ready_event) HIP_TRY(hipStreamWaitEvent(st, (hipEvent_t)query_ready_event, 0));
   Ctx* c = nullptr;
   if ((rc = ctx_acquire(idx, st, false, &c)) != SVS_OK) return rc;
   CtxGuard cg{idx, c};
@@ -2275,6 +2446,18 @@ int32_t svs_index_search_device(svs_index* idx, const float* dev_queries, int32_
   c->last_stream = st;
   c->async_pending = true;
   return rc;
+}
+
+int32_t svs_index_search_device(svs_index* idx, const float* dev_queries, int32_t nq, int32_t d,
+                                int32_t k, float* dev_out_scores, int64_t* dev_out_rows,
+                                int32_t* out_count, void* hip_stream) {
+  return search_device(idx, dev_queries, nq, d, k, dev_out_scores, dev_out_rows, out_count, hip_stream, false, nullptr);
+}
+
+int32_t svs_index_search_device_ahead(svs_index* idx, const float* dev_query, int32_t nq, int32_t d, int32_t k,
+                                      float* dev_out_scores, int64_t* dev_out_rows, int32_t* out_count,
+                                      void* hip_stream, void* query_ready_event) {
+  return search_device(idx, dev_query, nq, d, k, dev_out_scores, dev_out_rows, out_count, hip_stream, true, query_ready_event);
 }
 
 int32_t svs_index_scores_n(svs_index* idx, const float* query, int32_t d, float* out_scores, int64_t out_capacity,
@@ -2561,12 +2744,20 @@ int32_t svs_index_set_screen(svs_index* idx, int32_t mode) {
   return SVS_OK;
 }
 
+int32_t svs_internal_ahead_stats(svs_index* idx, int64_t* out, int32_t cap) {
+  if (!idx || !out) return fail(SVS_ERR_INVALID, "null argument");
+  std::lock_guard<std::mutex> lk(idx->mu);
+  const int64_t v[4] = {idx->ahead_calls.load(), idx->ahead_plain.load(), idx->ahead_retired.load(), (int64_t)idx->pipes.size()};
+  for (int i = 0; i < cap && i < 4; ++i) out[i] = v[i];
+  return SVS_OK;
+}
+
 int32_t svs_internal_screen_stats(svs_index* idx, int64_t* out, int32_t cap) {
   if (!idx || !out) return fail(SVS_ERR_INVALID, "null argument");
   int64_t v[9] = {};
   if (idx->scr_host) {
     const volatile uint32_t* h = idx->scr_host;
-    for (int i = 0; i < svs_index::kMaxCtx; ++i) {
+    for (int i = 0; i < svs_index::kSlots; ++i) {
       v[0] += h[i * SCREEN_SLOT_WORDS];
       v[1] += h[i * SCREEN_SLOT_WORDS + 1];
     }

@@ -301,6 +301,27 @@ class DeviceIndex:
             self._unpin(h)
         return count.value
 
+    def search_device_ahead(self, q_ptr: int, nq: int, d: int, k: int, out_scores_ptr: int,
+                            out_rows_ptr: int, stream: int = 0, ready_event=None) -> int:
+        """``search_device`` for back-to-back single queries: the score pass runs on the library's own stream,
+        beside the selection kernels of the search before it; results are ordered on ``stream`` as usual.  The
+        query is NOT ordered by ``stream``: it must be complete on the device at the call, or ``ready_event`` (a
+        raw hipEvent_t, or a ``torch.cuda.Event`` that HAS BEEN RECORDED) fires when it is; an event object without
+        a handle yet (never recorded) is a ValueError, not an unguarded search.  See svs_index_search_device_ahead."""
+        ev = getattr(ready_event, "cuda_event", ready_event)
+        ev = getattr(ev, "value", ev)
+        if ready_event is not None and not ev:
+            raise ValueError("ready_event has no device handle: record it before passing it (an unrecorded event guards nothing)")
+        count = C.c_int32(0)
+        h = self._pinned_handle()
+        try:
+            _native.check(self._lib.svs_index_search_device_ahead(
+                h, C.c_void_p(q_ptr), int(nq), int(d), int(k), C.c_void_p(out_scores_ptr),
+                C.c_void_p(out_rows_ptr), C.byref(count), C.c_void_p(stream), C.c_void_p(ev or None)))
+        finally:
+            self._unpin(h)
+        return count.value
+
     def top_pairs(self, n: int) -> List[Tuple[float, int, int]]:
         """``get_top_pairs(np.dot(M, M.T), n)`` (reference src/svs/kb.py:1651,
         src/svs/util.py:206-233): [(score, row_i, row_j)] with i < j."""
@@ -378,6 +399,14 @@ class DeviceIndex:
         (+50 % HBM) and screen single queries on it -- same rows, order and score bits (svs_index_set_screen)."""
         _native.check(self._lib.svs_index_set_screen(self._handle(), int(mode)))
         self._refresh()
+
+    def ahead_stats(self) -> dict:
+        """``search_device_ahead`` on this handle (svs_internal_ahead_stats; tests): single-query calls that went through
+        a pipeline, those that were plain calls because every pipeline had work in flight, idle pipelines handed over to
+        another stream, pipelines that exist."""
+        out = (C.c_int64 * 4)()
+        _native.check(self._lib.svs_internal_ahead_stats(self._handle(), out, 4))
+        return {"ahead": int(out[0]), "plain": int(out[1]), "handed_over": int(out[2]), "pipelines": int(out[3])}
 
     def screen_stats(self) -> dict:
         """Counters and state of the screened search (svs_internal_screen_stats; tests).  Drain the stream first."""

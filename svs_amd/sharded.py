@@ -149,7 +149,13 @@ class ShardedIndex:
         self._multi = self.world > 1 or (bool(force_collective) and dist.is_initialized())
         self.gather_every = max(1, int(gather_every)) if self._multi else 1
         self._n_streams = max(1, int(streams)) if not self._multi else max(2, int(streams))
+        # one rank, one search stream: svs_index_search_device_ahead -- each search's score pass runs beside the
+        # selection kernels of the search before it.  (N > 1 keeps the alternating streams; a library of another
+        # revision loaded through SVS_AMD_LIB for a before / after run may not have the entry.)
+        self._ahead = (self._on_device and not self._multi and self._n_streams == 1 and
+                       hasattr(getattr(local, "_lib", None), "svs_index_search_device_ahead"))
         self._pipe = None
+        self._streams = None        # the search streams, made by the first open() and kept: a run-ahead pipeline is per stream
         self._rec_cache = {}
 
     # ---- one record, one collective -------------------------------------------------
@@ -215,12 +221,18 @@ class ShardedIndex:
              "host": torch.zeros((nchunks, self.world, g * rec), dtype=torch.uint8, pin_memory=True),
              "local": None if not self._multi else torch.zeros((nchunks, g * rec), device=dev, dtype=torch.uint8),
              "gathered": None if not self._multi else torch.zeros((nchunks, self.world, g * rec), device=dev, dtype=torch.uint8),
-             "streams": [torch.cuda.Stream(device=dev) for _ in range(self._n_streams)],
+             "streams": self._search_streams(),
              # the exchange has a stream of its own: issued on a search stream (rounds 1-3) that stream's next searches
              # sat behind the collective and the copy home -- ~120 us per exchange with one of two streams stalled,
              # 15 us per step at one GPU's share of the 8-GPU strong-scaling run (125 k rows: 0.131 -> see DESIGN 6)
              "xstream": None if not self._multi else torch.cuda.Stream(device=dev), "done": {}}
         self._pipe = p
+
+    def _search_streams(self):
+        import torch
+        if self._streams is None:
+            self._streams = [torch.cuda.Stream(device=self.device) for _ in range(self._n_streams)]
+        return self._streams
 
     def _send_chunk(self, c: int, st) -> None:
         """One all-gather for chunk c (its records were written on every search stream), issued on the exchange
@@ -242,10 +254,19 @@ class ShardedIndex:
                 p["done"][c] = done          # chunk c is home when this fires (collect merges it while later chunks still run)
         p["sent"] = c + 1
 
-    def enqueue(self, query_ptr: int, d: int) -> int:
+    def enqueue(self, query_ptr: int, d: int, ready_event=None) -> int:
         """Enqueue one search (device pointer to d f32) without synchronising; returns its ticket.
         Consecutive searches alternate streams: the next query's score kernel fills the CUs this
-        query's small top-k kernels leave idle.  Every ``gather_every``-th one issues the exchange."""
+        query's small top-k kernels leave idle.  Every ``gather_every``-th one issues the exchange.
+        One rank with one search stream runs ahead instead (``runs_ahead``): one stream, and each search's
+        score pass beside the selection kernels of the search before it.
+
+        Readiness: the search streams are this object's own, so the query is ordered by NONE of the caller's
+        streams.  It must be complete on the device when ``enqueue`` is called (the producer synchronised, as
+        bench.py does), or ``ready_event`` -- a ``torch.cuda.Event`` that has been recorded (an unrecorded one is
+        a ValueError) -- fires when it is: the search waits for it on the device.  When ``runs_ahead`` a raw
+        hipEvent_t works as well; the alternating-stream path waits through torch and takes a torch event only
+        (TypeError otherwise).  The buffer may be rewritten once ``collect`` has returned."""
         p = self._pipe
         i = p["n"]
         g = self.gather_every
@@ -253,7 +274,16 @@ class ShardedIndex:
         assert c < p["nchunks"], "ShardedIndex.open(capacity) exceeded"
         st = p["streams"][i % len(p["streams"])]
         base = (p["host"][c, 0] if not self._multi else p["local"][c]).data_ptr() + j * p["rec"]
-        self.local.search_device(query_ptr, 1, d, p["k"], base, base + p["s_bytes"], st.cuda_stream)
+        if self._ahead:
+            self.local.search_device_ahead(query_ptr, 1, d, p["k"], base, base + p["s_bytes"], st.cuda_stream, ready_event)
+        else:
+            if ready_event is not None:
+                if not hasattr(ready_event, "cuda_event"):
+                    raise TypeError("ready_event must be a torch.cuda.Event on this path (raw hipEvent_t: only when runs_ahead)")
+                if not ready_event.cuda_event:
+                    raise ValueError("ready_event has no device handle: record it before passing it")
+                st.wait_event(ready_event)
+            self.local.search_device(query_ptr, 1, d, p["k"], base, base + p["s_bytes"], st.cuda_stream)
         p["n"] = i + 1
         if self._multi and j == g - 1:
             self._send_chunk(c, st)
@@ -300,3 +330,10 @@ class ShardedIndex:
     @property
     def streams(self) -> int:
         return self._n_streams
+
+    @property
+    def runs_ahead(self) -> bool:
+        """``enqueue`` calls svs_index_search_device_ahead (one rank, one search stream).  Whether those calls really
+        went through a pipeline is counted by the library: ``local.ahead_stats()`` ("plain" stays 0 unless more than
+        four streams have searches of this index in flight at once)."""
+        return self._ahead
