@@ -16,7 +16,10 @@ int32_t svs_internal_coalesce_hold(svs_index* idx, int32_t n);
  *   1  host batches: 0 = f16 batches pulled from pinned memory by the staging kernel, chunk by chunk (default);
  *      1 = staged DMA for every dtype (round 3)
  *   2  fused path's threshold rows: 1 = a sample spread over the whole corpus (default); 0 = the first rows (rounds 1-3)
- *   3  1 = every allocation of an f32 index's half shadow is refused, as if HBM were full (default 0) */
+ *   3  1 = every allocation of an f32 index's half shadow is refused, as if HBM were full (default 0)
+ *   4  run-ahead pipelines MADE FROM NOW ON: 0 = a pass's last kernel carries its completion event and the pass stream
+ *      waits for a selection once per group of passes (default); 1 = an event record behind every pass and a wait in
+ *      front of every pass */
 int32_t svs_internal_tune(int32_t what, int64_t value);
 /* Seconds since the start of the calling thread's last svs_index_search(host batch) at which: [0] scratch was planned,
  * [1] the queries were in pinned memory (and their DMA enqueued), [2] every kernel was enqueued, [3] the stream had
@@ -40,9 +43,11 @@ int32_t svs_internal_last_launches(const char** kernels, int64_t* rows, int32_t*
  * paused until the next ingest (fallbacks dominated), [4] bits of the bound E and [5] candidate count of the calling
  * thread's last screened search, [6..8] bits of the corpus statistics A, B, C. */
 int32_t svs_internal_screen_stats(svs_index* idx, int64_t* out, int32_t cap);
-/* svs_index_search_device_ahead on this handle, up to cap (<= 4) values: [0] single-query calls that went through a
+/* svs_index_search_device_ahead on this handle, up to cap (<= 7) values: [0] single-query calls that went through a
  * pipeline, [1] single-query calls that were plain calls because every pipeline had work in flight, [2] idle
- * pipelines handed over to another caller stream, [3] pipelines that exist. */
+ * pipelines handed over to another caller stream, [3] pipelines that exist, [4] passes whose completion event was
+ * carried by their last kernel, [5] event records enqueued on pass streams (the timing events among them), [6] waits
+ * enqueued on pass streams, the caller's query_ready_event not counted. */
 int32_t svs_internal_ahead_stats(svs_index* idx, int64_t* out, int32_t cap);
 /* multi.hip -> svs_amd.hip: carries a worker thread's error message over to the caller's thread */
 int32_t svs_internal_set_error(int32_t code, const char* msg);

@@ -7,6 +7,7 @@
 #include "internal.h"
 
 #include <hip/hip_runtime.h>
+#include <hip/hip_ext.h>
 
 #include <algorithm>
 #include <atomic>
@@ -96,6 +97,8 @@ std::atomic<int64_t> g_tune_upload{0};        // host batches: 0 = f16 batches a
                                               // (no DMA, no f32 copy in HBM); 1 = round 3's staging + DMA for every dtype
 std::atomic<int64_t> g_tune_spread{1};        // fused path: 1 = thresholds from a sample spread over the whole corpus (prefix_image), 0 = from its first rows (rounds 1-3)
 std::atomic<int64_t> g_tune_refuse_shadow{0}; // 1 = every allocation of an f32 index's half shadow "fails" (tests of the best-effort path)
+std::atomic<int64_t> g_tune_handover{0};      // run-ahead pipelines made from now on: 0 = the pass carries its completion event and the pass stream
+                                              // waits once per group of passes; 1 = a record and a wait per pass
 thread_local double g_host_phase[6];          // svs_internal_host_phases: seconds since the call began (last svs_index_search on this thread)
 
 // svs_internal_last_launches: the score kernels the calling thread's last search / scores call enqueued, in order: every
@@ -149,6 +152,33 @@ constexpr KernelName kernel_name(const char* base, A... args) {
   return k;
 }
 
+// The completion event of a score half, carried by its LAST kernel instead of a record behind it (run-ahead pipeline:
+// no packet between consecutive passes).  enqueue_score_half arms the calling thread's slot in front of that launch;
+// the single-query launchers and the tombstone mask launch through launch_tail, which hands an armed event to the
+// extended launch as its stop event.  tail_take() disarms and says whether a launch took it: a route that never
+// came by (or an event nobody armed) leaves the caller to record the event as before.
+struct TailEvent {
+  hipEvent_t stop = nullptr;
+  bool bound = false;
+};
+thread_local TailEvent g_tail;
+
+inline void tail_arm(hipEvent_t stop) { g_tail = TailEvent{stop, false}; }
+inline bool tail_take() {
+  const bool bound = g_tail.bound;
+  g_tail = TailEvent{};
+  return bound;
+}
+template <class... P, class... A>
+inline void launch_tail(void (*kernel)(P...), dim3 grid, dim3 block, unsigned lds, hipStream_t st, A&&... args) {
+  if (hipEvent_t stop = g_tail.stop) {
+    g_tail = TailEvent{nullptr, true};
+    hipExtLaunchKernelGGL<P...>(kernel, grid, block, lds, st, nullptr, stop, 0, static_cast<P>(args)...);
+  } else {
+    hipLaunchKernelGGL(kernel, grid, block, lds, st, static_cast<P>(args)...);
+  }
+}
+
 struct EvTriple {
   hipEvent_t e0, e1, e2;
   hipEvent_t d0 = nullptr, d1 = nullptr;   // around the dominant kernel of a fused search (else unset)
@@ -192,17 +222,26 @@ struct Ctx {
 };
 
 // svs_index_search_device_ahead: the ordered pipeline of one (index, caller stream).  Score passes run one after
-// another on `pass`; search i uses ctx[i & 1], and its selection chain runs on the caller's stream behind pass_done,
-// beside the pass of search i + 1.  The two contexts never enter svs_index::free_ctx and own no stream.
+// another on `pass`; search i uses ctx[i % AHEAD_RING], and its selection chain runs on the caller's stream behind
+// pass_done, beside the passes of the searches after it.  The contexts never enter svs_index::free_ctx and own no
+// stream.  Pass i may overwrite its context's scratch once selection i - AHEAD_RING is over.  The caller's stream is
+// in order -- a selection that is over means every earlier one is -- so the pass stream does not wait in front of
+// every pass but once per AHEAD_GROUP passes: at the passes with i % AHEAD_GROUP == 0 (i >= AHEAD_RING), for the
+// selection of search i - AHEAD_GROUP - 1, which covers the passes i .. i + AHEAD_GROUP - 1 (the last of them reuses
+// the scratch of search i + AHEAD_GROUP - 1 - AHEAD_RING = i - AHEAD_GROUP - 1).
+constexpr int AHEAD_RING = 4;
+constexpr int AHEAD_GROUP = AHEAD_RING / 2;
+static_assert(AHEAD_RING == 2 * AHEAD_GROUP && AHEAD_GROUP >= 1, "the wait rule above needs a ring of two groups");
 struct AheadPipe {
   std::mutex mu;                               // one ahead call at a time per pipeline
   hipStream_t caller = nullptr;                // the key
   hipStream_t pass = nullptr;
-  Ctx* ctx[2] = {nullptr, nullptr};
-  hipEvent_t pass_done[2] = {nullptr, nullptr};   // on `pass`, behind the score half of the context's last search
-  hipEvent_t sel_done[2] = {nullptr, nullptr};    // on the caller's stream, behind its selection half: the last reader of the scratch
-  bool used[2] = {false, false};
-  uint64_t seq = 0;
+  Ctx* ctx[AHEAD_RING] = {};
+  hipEvent_t pass_done[AHEAD_RING] = {};       // the end of the score half of the context's last search (carried by its last kernel, or recorded on `pass`)
+  hipEvent_t sel_done[AHEAD_RING] = {};        // on the caller's stream, behind its selection half: the last reader of the scratch
+  bool used[AHEAD_RING] = {};
+  bool per_pass = false;                       // svs_internal_tune(4, 1) when the pipeline was made: a record and a wait per pass
+  uint64_t seq = 0;                            // searches since the pipeline last drained (0: every context is free)
   uint64_t tick = 0;                           // svs_index::pipe_tick of the last call that looked it up (under svs_index::mu)
 };
 
@@ -259,12 +298,14 @@ struct svs_index {
   // svs_index_search_device_ahead: one pipeline per caller stream (guarded by mu), at most kMaxPipes of them; they
   // live until the index goes.  A stream that has none when all exist takes over the least recently used pipeline
   // that is IDLE (pipe_get); only when every pipeline has work in flight is the call a plain one, and counted.
-  // Counter slots: the pooled contexts take [0, kMaxCtx), pipeline p's two contexts kMaxCtx + 2 p and the next.
+  // Counter slots: the pooled contexts take [0, kMaxCtx), pipeline p's contexts the AHEAD_RING slots from
+  // kMaxCtx + AHEAD_RING p on.
   static constexpr int kMaxPipes = 4;
-  static constexpr int kSlots = kMaxCtx + 2 * kMaxPipes;
+  static constexpr int kSlots = kMaxCtx + AHEAD_RING * kMaxPipes;
   std::vector<AheadPipe*> pipes;
   uint64_t pipe_tick = 0;
   std::atomic<int64_t> ahead_calls{0}, ahead_plain{0}, ahead_retired{0};   // svs_internal_ahead_stats
+  std::atomic<int64_t> ahead_bound{0}, ahead_records{0}, ahead_waits{0};   // ... what the calls put on their pass streams
 
   // cold-start staging (svs_index_staging_*): two pinned blocks, DMA'd on their own stream
   struct Staging {
@@ -304,20 +345,22 @@ void ctx_destroy(Ctx* c) {
 // Everything the pipeline has enqueued is over: its passes, and the selection chains on the caller's stream.  The
 // chains are waited for through the pipeline's OWN events (the caller may have destroyed its stream since; an event
 // that was never recorded counts as fired).
+// Afterwards the ring starts over (seq = 0): no context is in use, and the next AHEAD_RING passes wait for nothing.
 hipError_t pipe_drain(AheadPipe* p) {
   hipError_t e = hipStreamSynchronize(p->pass);
-  for (int j = 0; j < 2; ++j) {
+  for (int j = 0; j < AHEAD_RING; ++j) {
     const hipError_t e2 = p->sel_done[j] ? hipEventSynchronize(p->sel_done[j]) : hipSuccess;
     if (e == hipSuccess) e = e2;
     p->used[j] = false;
   }
+  p->seq = 0;
   return e;
 }
 
 void pipe_destroy(AheadPipe* p) {
   if (!p) return;
   if (p->pass) (void)pipe_drain(p);
-  for (int j = 0; j < 2; ++j) {
+  for (int j = 0; j < AHEAD_RING; ++j) {
     ctx_destroy(p->ctx[j]);   // (drained above; the contexts own no stream)
     if (p->pass_done[j]) (void)hipEventDestroy(p->pass_done[j]);
     if (p->sel_done[j]) (void)hipEventDestroy(p->sel_done[j]);
@@ -541,8 +584,8 @@ void launch_oneshot(const svs_index* idx, const float* q, float* scores, hipStre
   const int64_t blocks = (idx->n + rows_per_block - 1) / rows_per_block;
   static constexpr KernelName name = kernel_name("gemv_f32_oneshot_kernel", NSTEP, R, WPB, NT, false, false);
   launch_record(name.s, idx->n, 1);
-  hipLaunchKernelGGL((gemv_f32_oneshot_kernel<NSTEP, R, WPB, NT, false>), dim3((unsigned)blocks), dim3(WPB * 64), 0, st,
-                     (const v4f*)idx->rows, (const v4f*)q, scores, idx->n);
+  launch_tail(gemv_f32_oneshot_kernel<NSTEP, R, WPB, NT, false>, dim3((unsigned)blocks), dim3(WPB * 64), 0, st,
+              (const v4f*)idx->rows, (const v4f*)q, scores, idx->n);
 }
 
 template <int NSTEP, int R, bool NT>
@@ -552,8 +595,8 @@ void launch_persistent(const svs_index* idx, const float* q, float* scores, hipS
   const int blocks = (int)std::min<int64_t>((tiles + WPB - 1) / WPB, (int64_t)idx->cu_count * 4);
   static constexpr KernelName name = kernel_name("gemv_f32_rows_kernel", NSTEP, R, WPB, NT, false);
   launch_record(name.s, idx->n, 1);
-  hipLaunchKernelGGL((gemv_f32_rows_kernel<NSTEP, R, WPB, NT, false>), dim3(blocks), dim3(WPB * 64), 0, st,
-                     (const v4f*)idx->rows, (const v4f*)q, scores, idx->n);
+  launch_tail(gemv_f32_rows_kernel<NSTEP, R, WPB, NT, false>, dim3(blocks), dim3(WPB * 64), 0, st,
+              (const v4f*)idx->rows, (const v4f*)q, scores, idx->n);
 }
 
 // Default geometry per row length (measured at NSTEP = 6: one-shot, 16-wave
@@ -582,8 +625,8 @@ void launch_generic(const svs_index* idx, const float* q, float* scores, hipStre
   int blocks = (int)std::min<int64_t>((waves + 3) / 4, (int64_t)idx->cu_count * 8);
   static constexpr KernelName name = kernel_name("gemv_f32_generic_kernel", T);
   launch_record(name.s, idx->n, 1);
-  hipLaunchKernelGGL((gemv_f32_generic_kernel<T>), dim3(blocks), dim3(256), 0, st,
-                     (const v4f*)idx->rows, q, scores, idx->n, idx->d, idx->ld / 4);
+  launch_tail(gemv_f32_generic_kernel<T>, dim3(blocks), dim3(256), 0, st,
+              (const v4f*)idx->rows, q, scores, idx->n, idx->d, idx->ld / 4);
 }
 
 constexpr int f16_rows_r(int nstep) { return nstep <= 1 ? 4 : (nstep <= 3 ? 2 : 1); }
@@ -597,8 +640,8 @@ void launch_rows_f16(const svs_index* idx, const void* half_rows, const float* q
   const int64_t rows_per_block = (int64_t)R * WPB;
   const int64_t blocks = (idx->n + rows_per_block - 1) / rows_per_block;
   launch_record(kF16OneshotName<NSTEP>.s, idx->n, 1);
-  hipLaunchKernelGGL((gemv_f16_oneshot_kernel<NSTEP, R, WPB>), dim3((unsigned)blocks), dim3(WPB * 64), 0, st,
-                     (const u32x4*)half_rows, (const v4f*)q, scores, idx->n);
+  launch_tail(gemv_f16_oneshot_kernel<NSTEP, R, WPB>, dim3((unsigned)blocks), dim3(WPB * 64), 0, st,
+              (const u32x4*)half_rows, (const v4f*)q, scores, idx->n);
 }
 
 template <int T>
@@ -608,8 +651,8 @@ void launch_generic_f16(const svs_index* idx, const _Float16* qh, float* scores,
   int blocks = (int)std::min<int64_t>((waves + 3) / 4, (int64_t)idx->cu_count * 8);
   static constexpr KernelName name = kernel_name("gemv_f16_generic_kernel", T);
   launch_record(name.s, idx->n, 1);
-  hipLaunchKernelGGL((gemv_f16_generic_kernel<T>), dim3(blocks), dim3(256), 0, st, (const u32x4*)idx->rows,
-                     (const u32x4*)qh, scores, idx->n, idx->ld / 8);
+  launch_tail(gemv_f16_generic_kernel<T>, dim3(blocks), dim3(256), 0, st, (const u32x4*)idx->rows,
+              (const u32x4*)qh, scores, idx->n, idx->ld / 8);
 }
 
 // rounds nq f32 queries to half into c->qh ([rows_alloc][ld], rows >= nq zero)
@@ -649,8 +692,8 @@ void launch_gemv_fp8(const svs_index* idx, Ctx* c, float* scores, hipStream_t st
   int blocks = (int)std::min<int64_t>((waves + 3) / 4, (int64_t)idx->cu_count * 8);
   static constexpr KernelName name = kernel_name("gemv_fp8_kernel", T);
   launch_record(name.s, idx->n, 1);
-  hipLaunchKernelGGL((gemv_fp8_kernel<T>), dim3(blocks), dim3(256), 0, st, (const u32x4_t*)idx->rows, idx->row_scales,
-                     (const v4f*)c->q8f.p, c->q8s, scores, idx->n, idx->ld / 16);
+  launch_tail(gemv_fp8_kernel<T>, dim3(blocks), dim3(256), 0, st, (const u32x4_t*)idx->rows, idx->row_scales,
+              (const v4f*)c->q8f.p, c->q8s.p, scores, idx->n, idx->ld / 16);
 }
 
 // The Dot argument of gemv_unrolled_kernel as c++filt prints it
@@ -670,7 +713,7 @@ bool launch_unrolled(const svs_index* idx, const void* q_staged, int ld16, float
     const int64_t blocks = (groups + UNR_WPB - 1) / UNR_WPB;
     static constexpr KernelName name = kernel_name("gemv_unrolled_kernel", T, NC, U, kDotName<Dot>);
     launch_record(name.s, idx->n, 1);
-    hipLaunchKernelGGL((gemv_unrolled_kernel<T, NC, U, Dot>), dim3((unsigned)blocks), dim3(UNR_WPB * 64), 0, st, M, q, scores, idx->n, ld16, dot);
+    launch_tail(gemv_unrolled_kernel<T, NC, U, Dot>, dim3((unsigned)blocks), dim3(UNR_WPB * 64), 0, st, M, q, scores, idx->n, ld16, dot);
   });
 }
 
@@ -698,8 +741,8 @@ int launch_scores(const svs_index* idx, Ctx* c, const float* q, float* scores, h
     const int64_t blocks = (idx->n + (R) * 16 - 1) / ((R) * 16);                                                \
     static constexpr KernelName name = kernel_name("gemv_fp8_oneshot_kernel", NSTEP, LB, R, 16);                \
     launch_record(name.s, idx->n, 1);                                                                           \
-    hipLaunchKernelGGL((gemv_fp8_oneshot_kernel<NSTEP, LB, R, 16>), dim3((unsigned)blocks), dim3(16 * 64), 0, st, \
-                       (const uint8_t*)idx->rows, idx->row_scales, (const uint8_t*)c->q8, c->q8s, scores, idx->n);     \
+    launch_tail(gemv_fp8_oneshot_kernel<NSTEP, LB, R, 16>, dim3((unsigned)blocks), dim3(16 * 64), 0, st,          \
+                (const uint8_t*)idx->rows, idx->row_scales, (const uint8_t*)c->q8, c->q8s.p, scores, idx->n);       \
     return SVS_OK;                                                                                              \
   } while (0)
     switch (idx->ld) {
@@ -1282,6 +1325,8 @@ struct SearchPlan {
   int64_t n_mat = 0, sstride = 0;
   const float* q_padded = nullptr;   // screened search: the query as launch_screen_scores staged it (the re-score reads it)
   EvTriple ev{};
+  hipEvent_t pass_stop = nullptr;    // run-ahead pipeline, one query: the event the LAST kernel of the score half is to carry (launch_tail)
+  bool pass_bound = false;           // ... and it does: nothing was recorded for it
 };
 
 // Histogram / candidate scratch of run_select's window path (n_eff > SORT_CAP, count <= SEL_KMAX) for nq queries.
@@ -1388,15 +1433,22 @@ int enqueue_score_half(svs_index* idx, Ctx* c, SearchPlan& p, const float* q_dev
     if (p.timed) HIP_TRY(hipEventRecord(ev.e1, st));
     return SVS_OK;
   }
-  if (p.screen) {
-    if ((rc = launch_screen_scores(idx, c, q_dev, c->scores, &p.q_padded, st)) != SVS_OK) return rc;
-  } else if ((rc = launch_scores_any(idx, c, q_dev, n, nq, c->scores, p.sstride, FuseLaunch{}, st, !p.staged)) != SVS_OK) {
+  // (the half's last kernel carries p.pass_stop: the score kernel, or the mask behind it)
+  const bool masked = !idx->dead_list.empty(), carry = p.pass_stop && nq == 1;
+  if (carry && !masked) tail_arm(p.pass_stop);
+  if (p.screen) rc = launch_screen_scores(idx, c, q_dev, c->scores, &p.q_padded, st);
+  else rc = launch_scores_any(idx, c, q_dev, n, nq, c->scores, p.sstride, FuseLaunch{}, st, !p.staged);
+  if (rc != SVS_OK) {
+    (void)tail_take();
     return rc;
   }
-  if (!idx->dead_list.empty())   // tombstoned rows can never be returned
-    hipLaunchKernelGGL(mask_dead_rows_kernel, dim3(64), dim3(256), 0, st, c->scores, p.sstride, nq, idx->dead_dev,
-                       (int64_t)idx->dead_list.size(), n, (int64_t)0);
-  if (p.timed) HIP_TRY(hipEventRecord(ev.e1, st));
+  if (masked) {   // tombstoned rows can never be returned
+    if (carry) tail_arm(p.pass_stop);
+    launch_tail(mask_dead_rows_kernel, dim3(64), dim3(256), 0, st, c->scores.p, p.sstride, nq, idx->dead_dev.p,
+                (int64_t)idx->dead_list.size(), n, (int64_t)0);
+  }
+  p.pass_bound = tail_take();
+  if (p.timed && !(p.pass_bound && p.pass_stop == ev.e1)) HIP_TRY(hipEventRecord(ev.e1, st));
   return SVS_OK;
 }
 
@@ -2322,7 +2374,7 @@ int32_t svs_index_coalesce_sizes(svs_index* idx, int64_t* out, int32_t cap) {
 // "not ready" behind for a later hipGetLastError.
 static bool pipe_idle(AheadPipe* p) {
   bool idle = hipStreamQuery(p->pass) == hipSuccess;
-  for (int j = 0; j < 2 && idle; ++j) idle = !p->used[j] || hipEventQuery(p->sel_done[j]) == hipSuccess;
+  for (int j = 0; j < AHEAD_RING && idle; ++j) idle = !p->used[j] || hipEventQuery(p->sel_done[j]) == hipSuccess;
   (void)hipGetLastError();
   return idle;
 }
@@ -2359,11 +2411,12 @@ static int pipe_get(svs_index* idx, hipStream_t caller, AheadPipe** out) {
   if (!p) return fail(SVS_ERR_NOMEM, "host allocation failed");
   p->caller = caller;
   p->tick = ++idx->pipe_tick;
+  p->per_pass = g_tune_handover.load() == 1;
   hipError_t e = hipStreamCreateWithFlags(&p->pass, hipStreamNonBlocking);
-  for (int j = 0; j < 2 && e == hipSuccess; ++j) {
+  for (int j = 0; j < AHEAD_RING && e == hipSuccess; ++j) {
     p->ctx[j] = new (std::nothrow) Ctx();
     if (!p->ctx[j]) { e = hipErrorOutOfMemory; break; }
-    p->ctx[j]->slot = svs_index::kMaxCtx + 2 * (int)idx->pipes.size() + j;
+    p->ctx[j]->slot = svs_index::kMaxCtx + AHEAD_RING * (int)idx->pipes.size() + j;
     e = hipEventCreateWithFlags(&p->pass_done[j], hipEventDisableTiming);
     if (e == hipSuccess) e = hipEventCreateWithFlags(&p->sel_done[j], hipEventDisableTiming);
   }
@@ -2376,31 +2429,82 @@ static int pipe_get(svs_index* idx, hipStream_t caller, AheadPipe** out) {
   return SVS_OK;
 }
 
-// One single-query search through the pipeline: score half on the pass stream (behind the query's event and behind
-// the selection that last read this context's scratch), selection half on the caller's stream behind the pass.
+// Everything a single-query search of this index takes from its context, so that a pipeline's contexts get their
+// scratch TOGETHER (ahead_scratch_ok / enqueue_ahead) and no later call allocates: the scores, the window path's
+// histogram and candidates or path B's sort keys, and the staged query of every score route.
+static size_t ahead_keys_need(const svs_index* idx, int k, int count) {
+  return k > 0 && idx->n > SORT_CAP && count > SEL_KMAX ? (size_t)next_pow2_i64(idx->n) : 0;
+}
+static bool ahead_scratch_ok(const svs_index* idx, const Ctx* c, int k, int count) {
+  const bool path_a = k > 0 && idx->n > SORT_CAP && count <= SEL_KMAX;
+  return (size_t)((idx->n + 3) & ~(int64_t)3) <= c->scores.cap && !(path_a && c->hist_cap < 1) &&
+         ahead_keys_need(idx, k, count) <= c->keys.cap;
+}
+static int ahead_scratch_grow(const svs_index* idx, Ctx* c, int k, int count, hipStream_t st) {
+  const bool path_a = k > 0 && idx->n > SORT_CAP && count <= SEL_KMAX;
+  const size_t ld = (size_t)idx->ld;
+  int rc;
+  if ((rc = c->scores.grow((size_t)((idx->n + 3) & ~(int64_t)3))) != SVS_OK) return rc;
+  if (path_a && (rc = grow_select_scratch(c, 1, st)) != SVS_OK) return rc;
+  if ((rc = c->keys.grow(ahead_keys_need(idx, k, count))) != SVS_OK) return rc;
+  if (idx->dtype == SVS_DTYPE_FP8) {
+    if ((rc = c->q8.grow(ld)) != SVS_OK || (rc = c->q8s.grow(1)) != SVS_OK || (rc = c->q8f.grow(ld)) != SVS_OK) return rc;
+  } else {
+    if ((rc = c->q16.grow((size_t)GQ * ld)) != SVS_OK) return rc;
+    if (idx->dtype == SVS_DTYPE_F16 && (rc = c->qh.grow(ld)) != SVS_OK) return rc;
+  }
+  return SVS_OK;
+}
+
+// One single-query search through the pipeline: score half on the pass stream (behind the query's event and, once
+// per group of passes, behind a selection that covers the scratch the group overwrites: AheadPipe), selection half
+// on the caller's stream behind the pass.  The caller's stream waits for the event the pass's last kernel carries
+// (`e1` on a timed step); a pipeline made under svs_internal_tune(4, 1) records pass_done behind every pass and
+// waits in front of every pass instead.
 static int enqueue_ahead(svs_index* idx, AheadPipe* pipe, const float* q_dev, int k, int count, float* out_s, int64_t* out_r,
                          hipStream_t st, hipEvent_t query_ready) {
   std::lock_guard<std::mutex> lk(pipe->mu);
-  const int j = (int)(pipe->seq & 1);
+  // growing scratch frees buffers that earlier searches may still read: drain first, then grow every context of
+  // the ring, so that the calls that follow allocate nothing
+  bool fits = true;
+  for (int j = 0; j < AHEAD_RING; ++j) fits = fits && ahead_scratch_ok(idx, pipe->ctx[j], k, count);
+  if (!fits) {
+    if (pipe->seq) HIP_TRY(pipe_drain(pipe));
+    for (int j = 0; j < AHEAD_RING; ++j) {
+      const int rc = ahead_scratch_grow(idx, pipe->ctx[j], k, count, pipe->pass);
+      if (rc != SVS_OK) return rc;
+    }
+  }
+  const uint64_t i = pipe->seq;
+  const int j = (int)(i % AHEAD_RING);
   Ctx* c = pipe->ctx[j];
-  // growing scratch frees buffers that the context's earlier search may still read (the histogram and candidate
-  // scratch grows on the window path only -- plan_search's path_a; the sort keys of path B grow with n, like scores)
-  const size_t need_scores = (size_t)((idx->n + 3) & ~(int64_t)3);
-  const bool path_a = idx->n > SORT_CAP && count <= SEL_KMAX;
-  if (pipe->used[j] && (need_scores > c->scores.cap || (path_a && c->hist_cap < 1))) HIP_TRY(pipe_drain(pipe));
   if (query_ready) HIP_TRY(hipStreamWaitEvent(pipe->pass, query_ready, 0));
-  if (pipe->used[j]) HIP_TRY(hipStreamWaitEvent(pipe->pass, pipe->sel_done[j], 0));
+  if (pipe->per_pass ? pipe->used[j] : (i >= (uint64_t)AHEAD_RING && i % AHEAD_GROUP == 0)) {
+    const int jw = pipe->per_pass ? j : (int)((i - AHEAD_GROUP - 1) % AHEAD_RING);
+    HIP_TRY(hipStreamWaitEvent(pipe->pass, pipe->sel_done[jw], 0));
+    idx->ahead_waits.fetch_add(1);
+  }
   SearchPlan p;
   int rc = plan_search(idx, c, 1, k, count, pipe->pass, false, &p);
+  if (rc == SVS_OK && p.timed) idx->ahead_records.fetch_add(1);   // (e0: a start event of the extended launch is a marker of its own, so it stays a record)
+  hipEvent_t done = rc == SVS_OK && p.timed && !pipe->per_pass ? p.ev.e1 : pipe->pass_done[j];
+  if (!pipe->per_pass) p.pass_stop = done;
   if (rc == SVS_OK) rc = enqueue_score_half(idx, c, p, q_dev, pipe->pass);
   auto hip_step = [&](hipError_t e, const char* what) {
     if (rc == SVS_OK && e != hipSuccess) rc = fail(SVS_ERR_DEVICE, "run-ahead pipeline, %s: %s", what, hipGetErrorString(e));
   };
-  if (rc == SVS_OK) hip_step(hipEventRecord(pipe->pass_done[j], pipe->pass), "pass event");
-  if (rc == SVS_OK) hip_step(hipStreamWaitEvent(st, pipe->pass_done[j], 0), "wait for the pass");
+  if (rc == SVS_OK) {
+    if (p.pass_bound) idx->ahead_bound.fetch_add(1);
+    else if (p.timed) idx->ahead_records.fetch_add(1);           // (e1, recorded by the score half)
+    if (!p.pass_bound && done != p.ev.e1) {
+      hip_step(hipEventRecord(done, pipe->pass), "pass event");
+      idx->ahead_records.fetch_add(1);
+    }
+  }
+  if (rc == SVS_OK) hip_step(hipStreamWaitEvent(st, done, 0), "wait for the pass");
   if (rc == SVS_OK) rc = enqueue_select_half(idx, c, p, out_s, out_r, st);
   if (rc == SVS_OK) hip_step(hipEventRecord(pipe->sel_done[j], st), "selection event");
-  if (rc != SVS_OK) {   // nothing half enqueued outlives a failed call
+  if (rc != SVS_OK) {   // nothing half enqueued outlives a failed call (the drain also starts the ring over)
     (void)hipStreamSynchronize(st);
     (void)pipe_drain(pipe);
     return rc;
@@ -2706,6 +2810,7 @@ int32_t svs_internal_tune(int32_t what, int64_t value) {
     case 1: if (value < 0 || value > 1) break; g_tune_upload.store(value); return SVS_OK;
     case 2: if (value < 0 || value > 1) break; g_tune_spread.store(value); return SVS_OK;
     case 3: if (value < 0 || value > 1) break; g_tune_refuse_shadow.store(value); return SVS_OK;
+    case 4: if (value < 0 || value > 1) break; g_tune_handover.store(value); return SVS_OK;
     default: break;
   }
   return fail(SVS_ERR_INVALID, "svs_internal_tune(%d, %lld): unknown knob or value", what, (long long)value);
@@ -2747,8 +2852,9 @@ int32_t svs_index_set_screen(svs_index* idx, int32_t mode) {
 int32_t svs_internal_ahead_stats(svs_index* idx, int64_t* out, int32_t cap) {
   if (!idx || !out) return fail(SVS_ERR_INVALID, "null argument");
   std::lock_guard<std::mutex> lk(idx->mu);
-  const int64_t v[4] = {idx->ahead_calls.load(), idx->ahead_plain.load(), idx->ahead_retired.load(), (int64_t)idx->pipes.size()};
-  for (int i = 0; i < cap && i < 4; ++i) out[i] = v[i];
+  const int64_t v[7] = {idx->ahead_calls.load(), idx->ahead_plain.load(), idx->ahead_retired.load(), (int64_t)idx->pipes.size(),
+                        idx->ahead_bound.load(), idx->ahead_records.load(), idx->ahead_waits.load()};
+  for (int i = 0; i < cap && i < 7; ++i) out[i] = v[i];
   return SVS_OK;
 }
 

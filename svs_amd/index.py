@@ -403,10 +403,12 @@ class DeviceIndex:
     def ahead_stats(self) -> dict:
         """``search_device_ahead`` on this handle (svs_internal_ahead_stats; tests): single-query calls that went through
         a pipeline, those that were plain calls because every pipeline had work in flight, idle pipelines handed over to
-        another stream, pipelines that exist."""
-        out = (C.c_int64 * 4)()
-        _native.check(self._lib.svs_internal_ahead_stats(self._handle(), out, 4))
-        return {"ahead": int(out[0]), "plain": int(out[1]), "handed_over": int(out[2]), "pipelines": int(out[3])}
+        another stream, pipelines that exist; then what those calls put on their pass streams: passes whose completion
+        event their last kernel carried, event records, waits for a selection."""
+        out = (C.c_int64 * 7)()
+        _native.check(self._lib.svs_internal_ahead_stats(self._handle(), out, 7))
+        return {"ahead": int(out[0]), "plain": int(out[1]), "handed_over": int(out[2]), "pipelines": int(out[3]),
+                "bound": int(out[4]), "pass_records": int(out[5]), "pass_waits": int(out[6])}
 
     def screen_stats(self) -> dict:
         """Counters and state of the screened search (svs_internal_screen_stats; tests).  Drain the stream first."""
