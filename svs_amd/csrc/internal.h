@@ -49,6 +49,27 @@ int32_t svs_internal_screen_stats(svs_index* idx, int64_t* out, int32_t cap);
  * carried by their last kernel, [5] event records enqueued on pass streams (the timing events among them), [6] waits
  * enqueued on pass streams, the caller's query_ready_event not counted. */
 int32_t svs_internal_ahead_stats(svs_index* idx, int64_t* out, int32_t cap);
+/* The top-k stage ALONE on caller-given data (tests/test_select_routes_gpu.py).  The index supplies the device, a search
+ * context and, where asked, its tombstone bitmap; n is the caller's, not the index's.  Each hook runs on the context's own
+ * stream, has drained it when it returns, and reports in *out_dirty the number of non-zero words among the nq per-query
+ * scratch blocks (header + window histogram) of that context, read back behind the selection: the stage's invariant is 0.
+ *
+ * svs_internal_select_scores: run_select over host scores[nq][n] (copied to float4-aligned device rows), scratch grown as
+ *   a search grows it.  out_scores / out_rows are [nq][k], filled past *out_count = min(k, n) with -inf / -1. */
+int32_t svs_internal_select_scores(svs_index* idx, const float* scores, int32_t nq, int64_t n, int32_t k, int64_t row_offset,
+                                   float* out_scores, int64_t* out_rows, int32_t* out_count, int64_t* out_dirty);
+/* svs_internal_kth_value: prefix_kth_kernel over host scores[nq][n], 1 <= k <= n; out_thr[nq].  misalign != 0 places the
+ *   device rows one float off a 16-byte boundary, so that the kernel takes its streaming branch whatever n. */
+int32_t svs_internal_kth_value(svs_index* idx, const float* scores, int32_t nq, int64_t n, int32_t k, int32_t misalign,
+                               float* out_thr, int64_t* out_dirty);
+/* svs_internal_select_candidates: select_final_kernel on candidate lists as the fused epilogue leaves them.  Query q's
+ *   keys (score key << 32 | local row, unique rows) are keys[key_offsets[q] .. key_offsets[q + 1]), uploaded in the order
+ *   given; its header claims n_cand[q] candidates, and exactly min(n_cand[q], 32768) keys must be given.  1 <= count <= 256,
+ *   count <= k.  use_dead != 0 strikes out the index's masked rows (every row must then lie inside the index).  out_scores /
+ *   out_rows are [nq][k]; a query the kernel could not answer has -2 in every out_rows entry. */
+int32_t svs_internal_select_candidates(svs_index* idx, const uint64_t* keys, const int64_t* key_offsets, const uint32_t* n_cand,
+                                       int32_t nq, int32_t k, int32_t count, int32_t use_dead, float* out_scores,
+                                       int64_t* out_rows, int64_t* out_dirty);
 /* multi.hip -> svs_amd.hip: carries a worker thread's error message over to the caller's thread */
 int32_t svs_internal_set_error(int32_t code, const char* msg);
 #ifdef __cplusplus

@@ -2858,6 +2858,149 @@ int32_t svs_internal_ahead_stats(svs_index* idx, int64_t* out, int32_t cap) {
   return SVS_OK;
 }
 
+// ---- test hooks: the selection stage alone on caller-given data (internal.h) -------------------
+// The index supplies the device, a context and (candidates hook) its tombstone bitmap; the data and n are the
+// caller's.  Each runs on the context's own stream and has drained it when it returns.
+namespace {
+constexpr int64_t HOOK_MAX_N = (int64_t)1 << 26;   // rows / k a hook accepts (the kernels themselves go to 2^32 rows)
+
+// Non-zero words among the first nq * SCR_WORDS words of the context's select scratch, read back behind everything
+// enqueued on st (also drains st).  A context whose scratch holds fewer than nq queries was not touched: 0.
+int scratch_dirty(Ctx* c, int nq, hipStream_t st, int64_t* out) {
+  *out = 0;
+  std::vector<uint32_t> w;
+  if ((size_t)nq <= c->hist_cap) {
+    w.resize((size_t)nq * SCR_WORDS);
+    HIP_TRY(hipMemcpyAsync(w.data(), c->hist, w.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+  }
+  HIP_TRY(hipStreamSynchronize(st));
+  int64_t d = 0;
+  for (uint32_t x : w) d += x != 0u;
+  *out = d;
+  return SVS_OK;
+}
+}  // namespace
+
+int32_t svs_internal_select_scores(svs_index* idx, const float* scores, int32_t nq, int64_t n, int32_t k, int64_t row_offset,
+                                   float* out_scores, int64_t* out_rows, int32_t* out_count, int64_t* out_dirty) {
+  if (!idx || !scores || !out_scores || !out_rows || !out_count || !out_dirty) return fail(SVS_ERR_INVALID, "null argument");
+  if (nq < 1 || nq > 1024 || n < 1 || n > HOOK_MAX_N || k < 1 || k > HOOK_MAX_N)
+    return fail(SVS_ERR_INVALID, "svs_internal_select_scores: nq %d, n %lld, k %d out of range", nq, (long long)n, k);
+  RefGuard guard(idx);
+  std::shared_lock<std::shared_mutex> geo(idx->rw);
+  HIP_TRY(hipSetDevice(idx->device));
+  int rc;
+  if ((rc = staging_wait(idx)) != SVS_OK) return rc;
+  const int count = (int)std::min<int64_t>(k, n);
+  *out_count = count;
+  const int64_t sstride = (n + 3) & ~(int64_t)3;   // float4-aligned score vectors, as plan_search lays them out
+  const bool path_a = n > SORT_CAP && count <= SEL_KMAX;
+  Ctx* c = nullptr;
+  if ((rc = ctx_acquire(idx, nullptr, true, &c)) != SVS_OK) return rc;
+  CtxGuard cg{idx, c};
+  hipStream_t st = c->stream;
+  if ((rc = c->scores.grow((size_t)nq * (size_t)sstride)) != SVS_OK) return rc;
+  if (path_a && (rc = grow_select_scratch(c, nq, st)) != SVS_OK) return rc;
+  DevTmp tmp;
+  float* d_s = nullptr;
+  int64_t* d_r = nullptr;
+  HIP_TRY(tmp.alloc(&d_s, (size_t)nq * k * sizeof(float)));
+  HIP_TRY(tmp.alloc(&d_r, (size_t)nq * k * sizeof(int64_t)));
+  HIP_TRY(hipMemcpy2DAsync(c->scores, (size_t)sstride * sizeof(float), scores, (size_t)n * sizeof(float), (size_t)n * sizeof(float),
+                           (size_t)nq, hipMemcpyHostToDevice, st));
+  if ((rc = run_select(idx, c, c->scores, n, sstride, nq, k, count, d_s, d_r, st, row_offset)) != SVS_OK) return rc;
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipMemcpyAsync(out_scores, d_s, (size_t)nq * k * sizeof(float), hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipMemcpyAsync(out_rows, d_r, (size_t)nq * k * sizeof(int64_t), hipMemcpyDeviceToHost, st));
+  return scratch_dirty(c, nq, st, out_dirty);
+}
+
+int32_t svs_internal_kth_value(svs_index* idx, const float* scores, int32_t nq, int64_t n, int32_t k, int32_t misalign,
+                               float* out_thr, int64_t* out_dirty) {
+  if (!idx || !scores || !out_thr || !out_dirty) return fail(SVS_ERR_INVALID, "null argument");
+  if (nq < 1 || nq > 1024 || n < 1 || n > HOOK_MAX_N || k < 1 || k > n)
+    return fail(SVS_ERR_INVALID, "svs_internal_kth_value: nq %d, n %lld, k %d out of range (1 <= k <= n)", nq, (long long)n, k);
+  RefGuard guard(idx);
+  std::shared_lock<std::shared_mutex> geo(idx->rw);
+  HIP_TRY(hipSetDevice(idx->device));
+  int rc;
+  if ((rc = staging_wait(idx)) != SVS_OK) return rc;
+  const int64_t sstride = (n + 3) & ~(int64_t)3;
+  Ctx* c = nullptr;
+  if ((rc = ctx_acquire(idx, nullptr, true, &c)) != SVS_OK) return rc;
+  CtxGuard cg{idx, c};
+  hipStream_t st = c->stream;
+  if ((rc = c->scores.grow((size_t)nq * (size_t)sstride + 4)) != SVS_OK) return rc;
+  if ((rc = c->pref_s.grow((size_t)nq)) != SVS_OK) return rc;
+  float* base = c->scores.p + (misalign ? 1 : 0);   // one float off a 16-byte boundary: the kernel's streaming branch
+  HIP_TRY(hipMemcpy2DAsync(base, (size_t)sstride * sizeof(float), scores, (size_t)n * sizeof(float), (size_t)n * sizeof(float),
+                           (size_t)nq, hipMemcpyHostToDevice, st));
+  HIP_TRY(hipMemsetAsync(c->pref_s, 0xff, (size_t)nq * sizeof(float), st));   // (a threshold nobody wrote reads back as NaN)
+  hipLaunchKernelGGL(prefix_kth_kernel, dim3(nq), dim3(FINAL_THREADS), 0, st, (const float*)base, n, sstride, k, c->pref_s.p);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipMemcpyAsync(out_thr, c->pref_s, (size_t)nq * sizeof(float), hipMemcpyDeviceToHost, st));
+  return scratch_dirty(c, nq, st, out_dirty);
+}
+
+int32_t svs_internal_select_candidates(svs_index* idx, const uint64_t* keys, const int64_t* key_offsets, const uint32_t* n_cand,
+                                       int32_t nq, int32_t k, int32_t count, int32_t use_dead, float* out_scores,
+                                       int64_t* out_rows, int64_t* out_dirty) {
+  if (!idx || !key_offsets || !n_cand || !out_scores || !out_rows || !out_dirty) return fail(SVS_ERR_INVALID, "null argument");
+  // (count <= 256: plan_search's rule for the fused path, whose lists these are)
+  if (nq < 1 || nq > 1024 || count < 1 || count > FINAL_THREADS || k < count || k > HOOK_MAX_N)
+    return fail(SVS_ERR_INVALID, "svs_internal_select_candidates: nq %d, k %d, count %d out of range", nq, k, count);
+  RefGuard guard(idx);
+  std::shared_lock<std::shared_mutex> geo(idx->rw);
+  if (use_dead && idx->dead_list.empty()) return fail(SVS_ERR_INVALID, "svs_internal_select_candidates: the index has no masked rows");
+  for (int q = 0; q < nq; ++q) {
+    const int64_t len = key_offsets[q + 1] - key_offsets[q];
+    if (key_offsets[q] < 0 || len != (int64_t)std::min<uint32_t>(n_cand[q], (uint32_t)CAND_CAP) || (len > 0 && !keys))
+      return fail(SVS_ERR_INVALID, "svs_internal_select_candidates: query %d gives %lld keys for a claim of %u", q, (long long)len, n_cand[q]);
+    if (use_dead)   // the kernel looks every row up in the bitmap
+      for (int64_t i = key_offsets[q]; i < key_offsets[q + 1]; ++i)
+        if ((int64_t)(uint32_t)keys[i] >= idx->n)
+          return fail(SVS_ERR_INVALID, "svs_internal_select_candidates: row %u outside the index", (uint32_t)keys[i]);
+  }
+  HIP_TRY(hipSetDevice(idx->device));
+  int rc;
+  if ((rc = staging_wait(idx)) != SVS_OK) return rc;
+  Ctx* c = nullptr;
+  if ((rc = ctx_acquire(idx, nullptr, true, &c)) != SVS_OK) return rc;
+  CtxGuard cg{idx, c};
+  hipStream_t st = c->stream;
+  if ((rc = grow_select_scratch(c, nq, st)) != SVS_OK) return rc;
+  DevTmp tmp;
+  float* d_s = nullptr;
+  int64_t* d_r = nullptr;
+  HIP_TRY(tmp.alloc(&d_s, (size_t)nq * k * sizeof(float)));
+  HIP_TRY(tmp.alloc(&d_r, (size_t)nq * k * sizeof(int64_t)));
+  // what the fused epilogue leaves: the keys in the order given, and a header that carries the claim
+  std::vector<SelHeader> hdr((size_t)nq);
+  auto run = [&]() -> int {
+    for (int q = 0; q < nq; ++q) {
+      hdr[q] = SelHeader{n_cand[q], 0u, 0u, 0u};
+      const int64_t len = key_offsets[q + 1] - key_offsets[q];
+      if (len > 0)
+        HIP_TRY(hipMemcpyAsync(c->cand.p + (size_t)q * CAND_CAP, keys + key_offsets[q], (size_t)len * sizeof(uint64_t), hipMemcpyHostToDevice, st));
+      HIP_TRY(hipMemcpyAsync(c->hist.p + (size_t)q * SCR_WORDS, &hdr[q], sizeof(SelHeader), hipMemcpyHostToDevice, st));
+    }
+    hipLaunchKernelGGL(select_final_kernel, dim3(nq), dim3(FINAL_THREADS), 0, st, (const float*)nullptr, idx->n, (int64_t)0, k, count, 3,
+                       c->hist.p, c->cand.p, idx->row_offset, d_s, d_r, (const uint32_t*)(use_dead ? idx->dead_bits_dev.p : nullptr));
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(out_scores, d_s, (size_t)nq * k * sizeof(float), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(out_rows, d_r, (size_t)nq * k * sizeof(int64_t), hipMemcpyDeviceToHost, st));
+    return scratch_dirty(c, nq, st, out_dirty);
+  };
+  rc = run();
+  if (rc != SVS_OK) {
+    // A failed hook must not hand the context back with the headers it uploaded: the next search on it relies on an
+    // all-zero scratch.  (Best effort, behind whatever is still queued; the first error stays the one reported.)
+    (void)hipMemset2DAsync(c->hist.p, (size_t)SCR_WORDS * sizeof(uint32_t), 0, sizeof(SelHeader), (size_t)nq, st);
+    (void)hipStreamSynchronize(st);
+  }
+  return rc;
+}
+
 int32_t svs_internal_screen_stats(svs_index* idx, int64_t* out, int32_t cap) {
   if (!idx || !out) return fail(SVS_ERR_INVALID, "null argument");
   int64_t v[9] = {};

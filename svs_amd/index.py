@@ -417,3 +417,44 @@ class DeviceIndex:
         f = lambda b: float(np.array([b], dtype=np.uint32).view(np.float32)[0])
         return {"screened": int(out[0]), "fallback": int(out[1]), "shadow": int(out[2]), "paused": bool(out[3]),
                 "E": f(out[4]), "n_cand": int(out[5]), "A": f(out[6]), "B": f(out[7]), "C": f(out[8])}
+
+    # -- the top-k stage alone on caller-given data (svs_amd/csrc/internal.h; tests) ----------------
+    def select_scores(self, scores: np.ndarray, k: int, row_offset: int = 0) -> Tuple[np.ndarray, np.ndarray, int, int]:
+        """run_select over host ``scores`` (nq, n): (scores f32 (nq, k), rows i64 (nq, k), count, dirty scratch words)
+        (svs_internal_select_scores).  Test hook; not part of the API."""
+        s = np.ascontiguousarray(scores, dtype=np.float32)
+        nq, n = s.shape
+        out_s, out_r = np.empty((nq, k), dtype=np.float32), np.empty((nq, k), dtype=np.int64)
+        count, dirty = C.c_int32(0), C.c_int64(-1)
+        _native.check(self._lib.svs_internal_select_scores(self._handle(), s.ctypes.data, nq, n, int(k), int(row_offset),
+                                                           out_s.ctypes.data, out_r.ctypes.data, C.byref(count), C.byref(dirty)))
+        return out_s, out_r, count.value, dirty.value
+
+    def kth_value(self, scores: np.ndarray, k: int, misalign: bool = False) -> Tuple[np.ndarray, int]:
+        """prefix_kth_kernel over host ``scores`` (nq, n): (k-th best score of every row f32 (nq,), dirty scratch words)
+        (svs_internal_kth_value).  Test hook; not part of the API."""
+        s = np.ascontiguousarray(scores, dtype=np.float32)
+        nq, n = s.shape
+        thr = np.empty(nq, dtype=np.float32)
+        dirty = C.c_int64(-1)
+        _native.check(self._lib.svs_internal_kth_value(self._handle(), s.ctypes.data, nq, n, int(k), int(bool(misalign)),
+                                                       thr.ctypes.data, C.byref(dirty)))
+        return thr, dirty.value
+
+    def select_candidates(self, lists, claims, k: int, count: int, use_dead: bool = False) -> Tuple[np.ndarray, np.ndarray, int]:
+        """select_final_kernel over per-query candidate key lists (u64: score key << 32 | local row, uploaded in the order
+        given) whose headers claim ``claims[q]`` candidates: (scores f32 (nq, k), rows i64 (nq, k), dirty scratch words);
+        a query the kernel could not answer has -2 in every row entry (svs_internal_select_candidates).  Test hook; not part of the API."""
+        lists = [np.ascontiguousarray(x, dtype=np.uint64) for x in lists]
+        nq = len(lists)
+        offs = np.zeros(nq + 1, dtype=np.int64)
+        offs[1:] = np.cumsum([x.size for x in lists])
+        keys = np.concatenate(lists + [np.zeros(1, dtype=np.uint64)])   # (never empty: a pointer to pass)
+        n_cand = np.ascontiguousarray(claims, dtype=np.uint32)
+        assert n_cand.shape == (nq,)
+        out_s, out_r = np.empty((nq, k), dtype=np.float32), np.empty((nq, k), dtype=np.int64)
+        dirty = C.c_int64(-1)
+        _native.check(self._lib.svs_internal_select_candidates(self._handle(), keys.ctypes.data, offs.ctypes.data, n_cand.ctypes.data,
+                                                               nq, int(k), int(count), int(bool(use_dead)), out_s.ctypes.data,
+                                                               out_r.ctypes.data, C.byref(dirty)))
+        return out_s, out_r, dirty.value

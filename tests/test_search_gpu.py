@@ -9,6 +9,7 @@ import pytest
 
 from compare import assert_topk_parity
 from oracle import svs_oracle as oracle
+from select_model import SEL_KMAX, SORT_CAP
 from synth import corpus_and_query
 
 pytestmark = pytest.mark.gpu
@@ -202,11 +203,14 @@ def test_odd_shapes_against_oracle(gpu, n, d):
 
 
 def test_full_ranking_path(gpu):
-    """k > 1024 goes through the global bitonic sort; the reference's 'rank the
-    whole KB' call (n = 10,548, examples/dad_jokes)."""
+    """k > SEL_KMAX (2048: select_model mirrors select.h) goes through the global bitonic sort; the reference's 'rank the
+    whole KB' call (n = 10,548, examples/dad_jokes).  k = 1025 was the first such k while the limit was 1024 and is
+    path A now; SEL_KMAX + 1 is the first today."""
+    ks = (1025, SEL_KMAX + 1, 5000, 10548, 20000)
+    assert min(k for k in ks if k > SEL_KMAX) == SEL_KMAX + 1
     m, qs = corpus_and_query("gaussian", 77, 10548, 256, 1)
     idx = _index(m)
-    for k in (1025, 5000, 10548, 20000):
+    for k in ks:
         got = idx.search(qs[0], k)
         exp = oracle.cpu_search(m, qs[0], k)
         assert len(got) == min(k, 10548)
@@ -217,16 +221,25 @@ def test_full_ranking_path(gpu):
 
 
 def test_select_paths_agree(gpu):
-    """path A (radix select, k <= 1024) and path B (full sort) must produce the
-    same prefix on the same scores."""
+    """path A (window histogram + filter + final select, k <= SEL_KMAX) and path B (full sort, k > SEL_KMAX) must produce
+    the same prefix on the same scores.  (70,000 rows: a single f32 query is screened on the half shadow first, whose
+    selection is path A's histogram and final kernel around another filter; with the shadow freed the plain three
+    launches run.  Both are compared.)"""
     rng = np.random.default_rng(3)
     vals = rng.standard_normal(70000).astype(np.float32)
     idx = _index(vals[:, None])
     q = np.array([1.0], dtype=np.float32)
-    a = idx.search(q, 1024)
-    b = idx.search(q, 1500)
-    assert a == b[:1024]
-    assert a == oracle.total_order_top_k(vals, 1024)
+    k_a, k_b = 1024, SEL_KMAX + 452
+    assert k_a <= SEL_KMAX < k_b and len(vals) > SORT_CAP
+    a = idx.search(q, k_a)
+    b = idx.search(q, k_b)
+    assert a == b[:k_a]
+    assert a == oracle.total_order_top_k(vals, k_a)
+    assert b == oracle.total_order_top_k(vals, k_b)
+    top = idx.search(q, SEL_KMAX)                      # the largest path A count against the path B order
+    assert top == b[:SEL_KMAX]
+    idx.set_screen(0)
+    assert idx.search(q, k_a) == a and idx.search(q, SEL_KMAX) == top and idx.search(q, k_b) == b
     idx.release()
 
 
