@@ -237,3 +237,63 @@ def test_single_kernel_table_rows_have_the_row_length_their_kernel_takes():
     for d in range(1, 4097):      # (longer rows are more than 1024 chunks: not the unrolled kernel's)
         chunks = choose_ld(d, "f32") // 4
         assert chunks <= 512 or chunks % 64 == 0, f"f32 d={d}: {chunks} chunks would reach an unrolled kernel of 12 or 16 chunks per lane"
+
+
+def _gather_instantiations(table):
+    """'gather_scores_kernel<2, 64, 16, 1, 4>', ...: every filtered-search score kernel in the report."""
+    names = _demangle([n for n in table if "gather_scores_kernel" in n])
+    out = set()
+    for pretty in names.values():
+        m = re.search(r"(gather_scores_kernel<[^>]*>)", pretty)
+        assert m, pretty
+        out.add(m.group(1))
+    return out
+
+
+def test_every_shipped_gather_kernel_has_a_test_case(build_reports):
+    """Every gather_scores_kernel instantiation in the library (14 row geometries x 3 dtypes x a lone query / a batch)
+    is named by a row of tests/gather_kernel_table.py, which tests/test_gather_kernels_gpu.py runs, asserting the kernel
+    was reached.  A geometry added to for_row_geometry without a row, or a row deleted from the table, fails here."""
+    from gather_kernel_table import CASES
+    built = _gather_instantiations(_resources(build_reports[0]))
+    assert len(built) >= 84, sorted(built)
+    tested = {k for c in CASES for k in c[3:5]}
+    untested = sorted(built - tested)
+    assert not untested, f"kernels in the build that tests/gather_kernel_table.py has no row for: {untested}"
+    stale = sorted(tested - built)
+    assert not stale, f"kernels the table names that the build does not hold: {stale}"
+
+
+GATHER_U = {1: 8, 2: 6, 3: 4, 4: 3, 6: 2, 8: 2, 12: 1, 16: 1}      # gather_u, per chunks per lane
+
+
+def test_gather_kernel_table_rows_have_the_row_length_their_kernels_take():
+    """Each row's d, through the padding rule, is a row length of the geometry in its two kernel names; U and G follow
+    gather_u and GATHER_G; and every geometry has a ragged and an exact row in all three dtypes."""
+    from gather_kernel_table import CASES, DT, case_id, rows_per_block, rows_per_wave
+    from single_kernel_table import PER16, choose_ld
+    seen = {}
+    for case in CASES:
+        dtype, d, shape, k1, k4 = case
+        ld = choose_ld(d, dtype)
+        assert ld % PER16[dtype] == 0 and ld >= d
+        chunks = ld // PER16[dtype]
+        t, nc = _geometry(chunks)
+        assert nc is not None, case
+        assert k1 == f"gather_scores_kernel<{DT[dtype]}, {t}, {nc}, {GATHER_U[nc]}, 1>", (case, chunks)
+        assert k4 == f"gather_scores_kernel<{DT[dtype]}, {t}, {nc}, {GATHER_U[nc]}, 4>", (case, chunks)
+        for k in (k1, k4):
+            assert rows_per_wave(k) == 64 // t * GATHER_U[nc] and rows_per_block(k) == rows_per_wave(k) * (8 if nc >= 12 else 16)
+        if shape == "exact":       # no lane past the row, no padding
+            assert d == ld == t * nc * PER16[dtype], case
+        else:                      # the last chunk ends in one zero column
+            assert shape == "ragged" and ld == d + 1, case
+        assert (dtype, t, nc, shape) not in seen, f"{case_id(case)} and {case_id(seen[(dtype, t, nc, shape)])} are one case"
+        seen[(dtype, t, nc, shape)] = case
+    geometries = [(t, 1) for t in (1, 2, 4, 8, 16, 32, 64)] + [(64, nc) for nc in (2, 3, 4, 6, 8, 12, 16)]
+    want = {(dtype, t, nc, shape) for dtype in ("f32", "f16", "fp8") for t, nc in geometries for shape in ("ragged", "exact")}
+    assert set(seen) == want, sorted(want ^ set(seen))
+    assert len({case_id(c) for c in CASES}) == len(CASES) == 84
+    # the ragged rows leave lanes past the row for every geometry but T = 1 and 2
+    assert sorted(t * nc - choose_ld(d, dtype) // PER16[dtype] for (dtype, t, nc, shape), (_, d, *_) in seen.items()
+                  if shape == "ragged" and dtype == "f32") == [0, 0, 1, 2, 4, 8, 24, 24, 32, 32, 104, 120, 192, 192]

@@ -18,6 +18,7 @@ import threading
 import numpy as np
 import pytest
 
+from single_kernel_table import _f16_oneshot
 from svs_amd import DeviceIndex, _native
 
 OFF, FORCE = 11, 12
@@ -49,9 +50,10 @@ def is_screen(name):
     return name.startswith("gemv_f16_oneshot_kernel<") or name.startswith("rescore_f32_kernel<")
 
 
-def check(idx, q, k, expect, on=FORCE, label=""):
+def check(idx, q, k, expect, on=FORCE, label="", names=None):
     """expect: 'list' (answered from the candidate list), 'fallback' (exact whole-corpus re-score), 'any' (screened,
-    either branch), 'off' (the screened variant must NOT screen this call)."""
+    either branch), 'off' (the screened variant must NOT screen this call).  names: the exact (screen pass, re-score)
+    kernels a screened call must have launched."""
     q = np.ascontiguousarray(q, dtype=np.float32)
     idx.set_variant(OFF)
     s0, r0 = idx.search_batch(q[None, :], k)
@@ -73,6 +75,8 @@ def check(idx, q, k, expect, on=FORCE, label=""):
         return s1, r1
     assert len(l1) == 2 and l1[0][0].startswith("gemv_f16_oneshot_kernel<") and l1[0][1:] == (idx.n, 1), (label, l1)
     assert l1[1][0].startswith("rescore_f32_kernel<") and l1[1][1:] == (idx.n, 1), (label, l1)
+    if names is not None:
+        assert (l1[0][0], l1[1][0]) == tuple(names), (label, l1, names)
     assert ds + df == 1, (label, ds, df)
     if expect == "list":
         assert ds == 1, (label, after)
@@ -100,15 +104,25 @@ def test_large_corpus_d1536(gpu, recipe):
     idx.release()
 
 
-@pytest.mark.parametrize("d", [512, 3072, 4096])
+def screen_kernels(d):
+    """The shadow pass and the re-score of an f32 index of d = ld floats: gemv_f16_oneshot_kernel<d / 512, R, WPB> as
+    an f16 index of that row length launches it, rescore_f32_kernel<d / 256, U> with U = 4, 2, 1 (rescore_u)."""
+    nstep = d // 256
+    return _f16_oneshot(d // 512), f"rescore_f32_kernel<{nstep}, {4 if nstep <= 4 else 2 if nstep <= 8 else 1}>"
+
+
+@pytest.mark.parametrize("d", [512, 1024, 1536, 2048, 2560, 3072, 3584, 4096])
 @pytest.mark.gpu
 def test_other_row_lengths(gpu, d):
+    """Every row length that has a shadow: each of the eight rescore_f32_kernel instantiations and of the eight shadow
+    passes, by name."""
     n = 12_000
     m = gaussian(n, d, 10 + d)
     idx = DeviceIndex(m, device=0)
+    assert idx.ld == d
     rng = np.random.default_rng(d)
     for k in (1, 100, 2048):
-        check(idx, unit(rng.standard_normal(d)), k, "list", label=f"d={d} k={k}")
+        check(idx, unit(rng.standard_normal(d)), k, "list", label=f"d={d} k={k}", names=screen_kernels(d))
     check(idx, unit(rng.standard_normal(d)), 2049, "off", label=f"d={d} k=2049")
     idx.release()
 
