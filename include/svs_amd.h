@@ -211,6 +211,11 @@ int32_t svs_index_search_device(svs_index* idx, const float* dev_queries, int32_
  *     over one whose work has all finished (least recently used first), so any number of streams may use the
  *     entry one after another.  Only while four OTHER streams each have such searches still in flight is the
  *     call an svs_index_search_device call: same results, no overlap.
+ *   - Searches queued on one pipeline may be served by ONE pass over the corpus: a pass that starts while the
+ *     searches behind it are already enqueued scores their queries from the rows it has loaded (up to four per
+ *     pass).  Results are bit-identical to searches served one by one.  It relies on the rule above: a query
+ *     without a ready event must be complete on the device when the call is made, because an EARLIER search's
+ *     pass may read it.  A search with a ready event is always served by its own pass.
  * Ingest (append, reserve, staging commit, mask_rows, set_screen) and svs_index_release may be called with
  * such searches enqueued, as with svs_index_search_device: they wait for what they would disturb. */
 int32_t svs_index_search_device_ahead(svs_index* idx, const float* dev_query, int32_t nq, int32_t d, int32_t k,

@@ -16,6 +16,7 @@
 #include <stdint.h>
 
 #include "gemv_f32.h"
+#include "pass_share.h"
 
 namespace svs {
 
@@ -71,14 +72,33 @@ __global__ void convert_queries_f16_kernel(const float* __restrict__ q, int nq, 
 // ---- hot kernel: ld16 == NSTEP * 512 halves, one-shot grid, R rows per wave ----
 // q is the f32 query (d = ld16 floats, 16-byte aligned): each wave rounds its
 // slice to half itself (RNE), saving a conversion launch on the latency path.
+//
+// plan != nullptr (run-ahead pipeline, pass_share.h): the pass serves the plan's c queries from ONE load of its
+// rows -- the rows stay in registers and the queries are streamed through them one after another, each with the
+// arithmetic of a pass of its own (same dot8 chain, same wave_sum), each into its own score vector.  c is
+// wave-uniform (a scalar load); c == 0 returns before the first row load.  plan == nullptr: q and scores, as ever.
+//
+// Row lengths on which the plan is compiled in: those where the loop over the plan's queries keeps the kernel at its
+// occupancy without scratch (the build's resource report: 512 .. 3584 halves; at 4096 the loop costs 10 registers and
+// two waves per SIMD).  Elsewhere the kernel ignores `plan`, and the host never passes one.
+constexpr int F16_SHARE_NSTEP_MAX = 7;
+constexpr bool f16_rows_share(int nstep) { return nstep >= 1 && nstep <= F16_SHARE_NSTEP_MAX; }
+
 template <int NSTEP, int R, int WPB>
 __global__ __launch_bounds__(WPB * 64) void gemv_f16_oneshot_kernel(
-    const u32x4* __restrict__ M, const v4f* __restrict__ q, float* __restrict__ scores, int64_t n) {
+    const u32x4* __restrict__ M, const v4f* __restrict__ q, float* __restrict__ scores, int64_t n,
+    const PassPlan* __restrict__ plan_arg) {
+  const PassPlan* __restrict__ plan = f16_rows_share(NSTEP) ? plan_arg : nullptr;
   constexpr int LD4 = NSTEP * 64;  // row stride in 16-byte units
   const int lane = threadIdx.x & 63;
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int64_t row0 = ((int64_t)blockIdx.x * WPB + wave) * R;
   if (row0 >= n) return;
+  int c = 1;
+  if (plan) {
+    c = __builtin_amdgcn_readfirstlane((int)plan->c);
+    if (c == 0) return;
+  }
   u32x4 buf[R][NSTEP];
 #pragma unroll
   for (int r = 0; r < R; ++r) {
@@ -88,29 +108,34 @@ __global__ __launch_bounds__(WPB * 64) void gemv_f16_oneshot_kernel(
 #pragma unroll
     for (int j = 0; j < NSTEP; ++j) buf[r][j] = __builtin_nontemporal_load(p + j * 64);
   }
-  u32x4 qv[NSTEP];
-#pragma unroll
-  for (int j = 0; j < NSTEP; ++j) {
-    const v4f lo = q[(j * 64 + lane) * 2], hi = q[(j * 64 + lane) * 2 + 1];
-    const h2 p0 = {(_Float16)lo.x, (_Float16)lo.y}, p1 = {(_Float16)lo.z, (_Float16)lo.w};
-    const h2 p2 = {(_Float16)hi.x, (_Float16)hi.y}, p3 = {(_Float16)hi.z, (_Float16)hi.w};
-    qv[j] = (u32x4){__builtin_bit_cast(uint32_t, p0), __builtin_bit_cast(uint32_t, p1),
-                    __builtin_bit_cast(uint32_t, p2), __builtin_bit_cast(uint32_t, p3)};
-  }
-  float out = 0.f;
-#pragma unroll
-  for (int r = 0; r < R; ++r) {
-    float s0 = 0.f, s1 = 0.f;
+#pragma unroll 1
+  for (int t = 0; t < c; ++t) {
+    const v4f* qt = plan ? plan->q[t] : q;
+    float* st = plan ? plan->scores[t] : scores;
+    u32x4 qv[NSTEP];
 #pragma unroll
     for (int j = 0; j < NSTEP; ++j) {
-      if (j & 1) s1 = dot8(buf[r][j], qv[j], s1);
-      else s0 = dot8(buf[r][j], qv[j], s0);
+      const v4f lo = qt[(j * 64 + lane) * 2], hi = qt[(j * 64 + lane) * 2 + 1];
+      const h2 p0 = {(_Float16)lo.x, (_Float16)lo.y}, p1 = {(_Float16)lo.z, (_Float16)lo.w};
+      const h2 p2 = {(_Float16)hi.x, (_Float16)hi.y}, p3 = {(_Float16)hi.z, (_Float16)hi.w};
+      qv[j] = (u32x4){__builtin_bit_cast(uint32_t, p0), __builtin_bit_cast(uint32_t, p1),
+                      __builtin_bit_cast(uint32_t, p2), __builtin_bit_cast(uint32_t, p3)};
     }
-    const float v = wave_sum(s0 + s1);
-    out = lane == r ? v : out;
+    float out = 0.f;
+#pragma unroll
+    for (int r = 0; r < R; ++r) {
+      float s0 = 0.f, s1 = 0.f;
+#pragma unroll
+      for (int j = 0; j < NSTEP; ++j) {
+        if (j & 1) s1 = dot8(buf[r][j], qv[j], s1);
+        else s0 = dot8(buf[r][j], qv[j], s0);
+      }
+      const float v = wave_sum(s0 + s1);
+      out = lane == r ? v : out;
+    }
+    const int64_t row = row0 + lane;
+    if (lane < R && row < n) st[row] = out;
   }
-  const int64_t row = row0 + lane;
-  if (lane < R && row < n) scores[row] = out;
 }
 
 // ---- generic kernel: any d (rows zero padded to ld16 % 8 == 0) ----------------

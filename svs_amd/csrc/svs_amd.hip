@@ -99,6 +99,7 @@ std::atomic<int64_t> g_tune_spread{1};        // fused path: 1 = thresholds from
 std::atomic<int64_t> g_tune_refuse_shadow{0}; // 1 = every allocation of an f32 index's half shadow "fails" (tests of the best-effort path)
 std::atomic<int64_t> g_tune_handover{0};      // run-ahead pipelines made from now on: 0 = the pass carries its completion event and the pass stream
                                               // waits once per group of passes; 1 = a record and a wait per pass
+std::atomic<int64_t> g_tune_share{SHARE_DEFAULT};  // run-ahead pipelines made from now on: queries one score pass may serve (1: its own search only)
 thread_local double g_host_phase[6];          // svs_internal_host_phases: seconds since the call began (last svs_index_search on this thread)
 
 // svs_internal_last_launches: the score kernels the calling thread's last search / scores call enqueued, in order: every
@@ -224,14 +225,23 @@ struct Ctx {
 // svs_index_search_device_ahead: the ordered pipeline of one (index, caller stream).  Score passes run one after
 // another on `pass`; search i uses ctx[i % AHEAD_RING], and its selection chain runs on the caller's stream behind
 // pass_done, beside the passes of the searches after it.  The contexts never enter svs_index::free_ctx and own no
-// stream.  Pass i may overwrite its context's scratch once selection i - AHEAD_RING is over.  The caller's stream is
-// in order -- a selection that is over means every earlier one is -- so the pass stream does not wait in front of
-// every pass but once per AHEAD_GROUP passes: at the passes with i % AHEAD_GROUP == 0 (i >= AHEAD_RING), for the
-// selection of search i - AHEAD_GROUP - 1, which covers the passes i .. i + AHEAD_GROUP - 1 (the last of them reuses
-// the scratch of search i + AHEAD_GROUP - 1 - AHEAD_RING = i - AHEAD_GROUP - 1).
-constexpr int AHEAD_RING = 4;
-constexpr int AHEAD_GROUP = AHEAD_RING / 2;
-static_assert(AHEAD_RING == 2 * AHEAD_GROUP && AHEAD_GROUP >= 1, "the wait rule above needs a ring of two groups");
+// stream.  A pass may overwrite the scratch of search s's context once selection s - AHEAD_RING is over.  The caller's
+// stream is in order -- a selection that is over means every earlier one is -- so the pass stream does not wait in
+// front of every pass but once per AHEAD_GROUP passes: at the passes with i % AHEAD_GROUP == 0 (i >= AHEAD_LAG), for
+// the selection of search i - AHEAD_LAG.  Behind that wait every selection up to i - AHEAD_LAG is over, so the
+// contexts of the searches up to i - AHEAD_LAG + AHEAD_RING may be written: that is the `reach` of the passes
+// i .. i + AHEAD_GROUP - 1 (AheadPipe::covered; a wait a LATER call enqueues cannot protect an earlier pass).  A pass
+// serves its own search and up to SHARE_MAX - 1 searches behind it (pass_share.h), so the last pass of a group,
+// i + AHEAD_GROUP - 1, reaches SHARE_MAX searches when
+//     i - AHEAD_LAG + AHEAD_RING >= i + AHEAD_GROUP - 1 + SHARE_MAX - 1.
+// The lag is kept as large as that allows: the older the selection a pass waits for, the less likely it is still
+// running.  (A pipeline made under svs_internal_tune(4, 1) waits in front of EVERY pass from the AHEAD_LAG-th on.)
+constexpr int AHEAD_RING = 8;
+constexpr int AHEAD_GROUP = 2;
+constexpr int AHEAD_LAG = 4;
+static_assert(AHEAD_LAG >= 1 && AHEAD_GROUP >= 1 && AHEAD_LAG <= AHEAD_RING - AHEAD_GROUP - SHARE_MAX + 2,
+              "the wait rule above: every pass of a group must reach SHARE_MAX searches");
+static_assert(AHEAD_LAG + AHEAD_GROUP - 1 <= AHEAD_RING, "a pass's own context must be covered by its group's wait");
 struct AheadPipe {
   std::mutex mu;                               // one ahead call at a time per pipeline
   hipStream_t caller = nullptr;                // the key
@@ -242,6 +252,13 @@ struct AheadPipe {
   bool used[AHEAD_RING] = {};
   bool per_pass = false;                       // svs_internal_tune(4, 1) when the pipeline was made: a record and a wait per pass
   uint64_t seq = 0;                            // searches since the pipeline last drained (0: every context is free)
+  uint64_t covered = 0;                        // selections of the searches seq < covered are over for everything enqueued on `pass` from now on
+  // shared passes (pass_share.h).  Search numbers never start over: number = base + seq.
+  uint64_t base = 0;
+  int share_limit = 1;                         // svs_internal_tune(5, v) when the pipeline was made
+  MailEntry* mailbox = nullptr;                // pinned: MAILBOX_SIZE entries, then the mirror of ShareState::hist
+  ShareState* share_dev = nullptr;
+  uint32_t* share_mirror() const { return (uint32_t*)(mailbox + MAILBOX_SIZE); }
   uint64_t tick = 0;                           // svs_index::pipe_tick of the last call that looked it up (under svs_index::mu)
 };
 
@@ -289,6 +306,9 @@ struct svs_index {
   std::atomic<int> screen_mode{1};     // svs_index_set_screen
   std::atomic<bool> scr_paused{false}; // fallbacks dominated recent queries: no screening until the next ingest
   std::atomic<uint64_t> scr_base_s{0}, scr_base_f{0};
+  // Bumped by everything that changes n, the row pointers, the shadow or the score route (under the exclusive
+  // geometry lock, or where a search drops the screen): a shared pass never serves a search planned under another one.
+  std::atomic<uint64_t> geo_epoch{1};
 
   std::mutex mu;
   std::condition_variable cv;
@@ -353,7 +373,9 @@ hipError_t pipe_drain(AheadPipe* p) {
     if (e == hipSuccess) e = e2;
     p->used[j] = false;
   }
+  p->base += p->seq;   // (search numbers go on: a pass that has run never meets a later search under its number)
   p->seq = 0;
+  p->covered = 0;
   return e;
 }
 
@@ -366,6 +388,8 @@ void pipe_destroy(AheadPipe* p) {
     if (p->sel_done[j]) (void)hipEventDestroy(p->sel_done[j]);
   }
   if (p->pass) (void)hipStreamDestroy(p->pass);
+  if (p->mailbox) (void)hipHostFree(p->mailbox);
+  (void)hipFree(p->share_dev);
   delete p;
 }
 
@@ -411,6 +435,7 @@ void shadow_refresh_stats(svs_index* idx) {
     (void)hipGetLastError();
     idx->shadow_bad.store(true);   // (unknown statistics: never screen on them)
   }
+  idx->geo_epoch.fetch_add(1);
 }
 
 // svs_index_staging_commit publishes idx->n while its H2D copy and conversion are still queued on the staging
@@ -634,6 +659,9 @@ constexpr int f16_rows_wpb(int nstep) { return nstep <= 6 ? 16 : 8; }
 template <int NSTEP>
 constexpr KernelName kF16OneshotName = kernel_name("gemv_f16_oneshot_kernel", NSTEP, f16_rows_r(NSTEP), f16_rows_wpb(NSTEP));
 // half_rows: the index's own rows (an f16 index) or the half shadow of an f32 index (screened search)
+// The plan the next f16 one-shot launch of this thread is to serve (enqueue_score_half sets and clears it around the
+// score launch of a shareable pipeline search); null: the launch's own q and scores.
+thread_local const PassPlan* g_pass_plan;
 template <int NSTEP>
 void launch_rows_f16(const svs_index* idx, const void* half_rows, const float* q, float* scores, hipStream_t st) {
   constexpr int R = f16_rows_r(NSTEP), WPB = f16_rows_wpb(NSTEP);
@@ -641,7 +669,7 @@ void launch_rows_f16(const svs_index* idx, const void* half_rows, const float* q
   const int64_t blocks = (idx->n + rows_per_block - 1) / rows_per_block;
   launch_record(kF16OneshotName<NSTEP>.s, idx->n, 1);
   launch_tail(gemv_f16_oneshot_kernel<NSTEP, R, WPB>, dim3((unsigned)blocks), dim3(WPB * 64), 0, st,
-              (const u32x4*)half_rows, (const v4f*)q, scores, idx->n);
+              (const u32x4*)half_rows, (const v4f*)q, scores, idx->n, g_pass_plan);
 }
 
 template <int T>
@@ -1101,7 +1129,10 @@ void screen_review(svs_index* idx) {
   }
   const uint64_t ds = s_tot - idx->scr_base_s.load(), df = f_tot - idx->scr_base_f.load();
   if (ds + df < 32) return;
-  if (df > ds) idx->scr_paused.store(true);
+  if (df > ds) {
+    idx->scr_paused.store(true);
+    idx->geo_epoch.fetch_add(1);
+  }
   idx->scr_base_s.store(s_tot);
   idx->scr_base_f.store(f_tot);
 }
@@ -1327,6 +1358,9 @@ struct SearchPlan {
   EvTriple ev{};
   hipEvent_t pass_stop = nullptr;    // run-ahead pipeline, one query: the event the LAST kernel of the score half is to carry (launch_tail)
   bool pass_bound = false;           // ... and it does: nothing was recorded for it
+  // run-ahead pipeline, shareable search (enqueue_ahead): the claim kernel's launch in front of the pass
+  const AheadPipe* share = nullptr;
+  uint64_t share_num = 0, share_reach = 0, share_epoch = 0;
 };
 
 // Histogram / candidate scratch of run_select's window path (n_eff > SORT_CAP, count <= SEL_KMAX) for nq queries.
@@ -1412,6 +1446,9 @@ int enqueue_prefix(svs_index* idx, Ctx* c, const SearchPlan& p, const float* q_d
   return SVS_OK;
 }
 
+// The half rows a single-query search's f16 one-shot pass reads: the shadow (screened f32 index) or the rows (f16 index)
+inline const void* half_rows_of(const svs_index* idx, const SearchPlan& p) { return p.screen ? idx->shadow : idx->rows; }
+
 // enqueue_main in two halves, so that svs_index_search_device_ahead can put them on two streams: everything up to and
 // including the `e1` timing event (query padding and staging, the screen pass or the score launch, the tombstone
 // mask), then the selection.  Both take the same plan; q_padded carries the staged query of a screened search across.
@@ -1435,9 +1472,17 @@ int enqueue_score_half(svs_index* idx, Ctx* c, SearchPlan& p, const float* q_dev
   }
   // (the half's last kernel carries p.pass_stop: the score kernel, or the mask behind it)
   const bool masked = !idx->dead_list.empty(), carry = p.pass_stop && nq == 1;
+  if (p.share) {   // what this pass serves is decided here, on the pass stream, and nowhere else (pass_share.h)
+    const AheadPipe* sp = p.share;
+    hipLaunchKernelGGL(pass_claim_kernel, dim3(1), dim3(64), 0, st, (const MailEntry*)sp->mailbox, sp->share_dev, sp->share_mirror(),
+                       p.share_num, p.share_reach, sp->share_limit, (const v4f*)q_dev, c->scores.p, (uint64_t)(uintptr_t)half_rows_of(idx, p),
+                       (uint64_t)n, p.share_epoch, (uint64_t)idx->ld);
+    g_pass_plan = &sp->share_dev->plan;
+  }
   if (carry && !masked) tail_arm(p.pass_stop);
   if (p.screen) rc = launch_screen_scores(idx, c, q_dev, c->scores, &p.q_padded, st);
   else rc = launch_scores_any(idx, c, q_dev, n, nq, c->scores, p.sstride, FuseLaunch{}, st, !p.staged);
+  g_pass_plan = nullptr;
   if (rc != SVS_OK) {
     (void)tail_take();
     return rc;
@@ -1761,6 +1806,7 @@ bool shadow_eligible(const svs_index* idx) {
 }
 
 void shadow_free(svs_index* idx) {
+  idx->geo_epoch.fetch_add(1);
   (void)hipFree(idx->shadow);
   idx->shadow = nullptr;
   idx->shadow_bytes = 0;
@@ -1802,6 +1848,7 @@ bool shadow_alloc(svs_index* idx, int64_t rows_cap, void** out) {
 // whose flag is read when the staging stream is next drained).  Caller holds the geometry lock exclusively.
 void shadow_ingest(svs_index* idx, int64_t row0, int64_t nrows, int64_t n_total, hipStream_t st, bool sync) {
   idx->scr_paused.store(false);   // new rows: whatever made the fallbacks dominate may be gone
+  idx->geo_epoch.fetch_add(1);    // (every ingest path comes by here: n, the rows or the shadow change)
   if (!shadow_eligible(idx) || idx->screen_mode.load() != 1 || idx->shadow_bad.load() || idx->shadow_gave_up) return;
   if (!idx->shadow) {
     void* sh = nullptr;
@@ -2057,6 +2104,7 @@ int32_t svs_index_reserve(svs_index* idx, int64_t rows_capacity) {
   if (idx->d == 0) return fail(SVS_ERR_SHAPE, "cannot reserve rows of a zero-dimensional index");
   std::unique_lock<std::shared_mutex> geo(idx->rw);
   HIP_TRY(hipSetDevice(idx->device));
+  idx->geo_epoch.fetch_add(1);
   return ensure_capacity(idx, rows_capacity, true);
 }
 
@@ -2158,6 +2206,7 @@ int32_t svs_index_mask_rows(svs_index* idx, const int64_t* rows, int64_t count) 
     }
   }
   if (!changed) return SVS_OK;
+  idx->geo_epoch.fetch_add(1);
   HIP_TRY(hipSetDevice(idx->device));
   {
     int rc = sync_dead_bits(idx);
@@ -2412,7 +2461,14 @@ static int pipe_get(svs_index* idx, hipStream_t caller, AheadPipe** out) {
   p->caller = caller;
   p->tick = ++idx->pipe_tick;
   p->per_pass = g_tune_handover.load() == 1;
+  p->share_limit = (int)g_tune_share.load();
   hipError_t e = hipStreamCreateWithFlags(&p->pass, hipStreamNonBlocking);
+  const size_t mail_bytes = sizeof(MailEntry) * MAILBOX_SIZE + sizeof(uint32_t) * (SHARE_MAX + 1);
+  if (e == hipSuccess) e = hipHostMalloc((void**)&p->mailbox, mail_bytes, hipHostMallocDefault);
+  if (e == hipSuccess) memset(p->mailbox, 0, mail_bytes);
+  else p->mailbox = nullptr;
+  if (e == hipSuccess) e = hipMalloc((void**)&p->share_dev, sizeof(ShareState));
+  if (e == hipSuccess) e = hipMemset(p->share_dev, 0, sizeof(ShareState));
   for (int j = 0; j < AHEAD_RING && e == hipSuccess; ++j) {
     p->ctx[j] = new (std::nothrow) Ctx();
     if (!p->ctx[j]) { e = hipErrorOutOfMemory; break; }
@@ -2479,13 +2535,34 @@ static int enqueue_ahead(svs_index* idx, AheadPipe* pipe, const float* q_dev, in
   const int j = (int)(i % AHEAD_RING);
   Ctx* c = pipe->ctx[j];
   if (query_ready) HIP_TRY(hipStreamWaitEvent(pipe->pass, query_ready, 0));
-  if (pipe->per_pass ? pipe->used[j] : (i >= (uint64_t)AHEAD_RING && i % AHEAD_GROUP == 0)) {
-    const int jw = pipe->per_pass ? j : (int)((i - AHEAD_GROUP - 1) % AHEAD_RING);
-    HIP_TRY(hipStreamWaitEvent(pipe->pass, pipe->sel_done[jw], 0));
+  if (i >= (uint64_t)AHEAD_LAG && (pipe->per_pass || i % AHEAD_GROUP == 0)) {
+    HIP_TRY(hipStreamWaitEvent(pipe->pass, pipe->sel_done[(i - AHEAD_LAG) % AHEAD_RING], 0));
     idx->ahead_waits.fetch_add(1);
+    pipe->covered = i - AHEAD_LAG + 1;
   }
   SearchPlan p;
   int rc = plan_search(idx, c, 1, k, count, pipe->pass, false, &p);
+  // Shared passes (pass_share.h).  The pass is the f16 one-shot kernel of a geometry that shares, over the query as the
+  // caller gave it (a query pad_query would have to copy is not shared: its staged copy lives in the context, which
+  // the next search of the ring slot overwrites).  Published before anything of this call is launched.
+  if (rc == SVS_OK && pipe->share_limit > 1 && !pipe->per_pass && p.path_a &&
+      (p.screen || (idx->dtype == SVS_DTYPE_F16 && idx->ld % 512 == 0)) && idx->ld <= 4096 && f16_rows_share(idx->ld / 512) &&
+      idx->ld == idx->d && (((uintptr_t)q_dev) & 15) == 0) {
+    p.share = pipe;
+    p.share_num = pipe->base + i;
+    p.share_reach = pipe->base + pipe->covered + AHEAD_RING - 1;
+    p.share_epoch = idx->geo_epoch.load();
+    // claimable by an earlier pass: the query is complete now (no event of its own), and no timed step (its events
+    // must bracket a pass that did its work)
+    const bool claimable = !query_ready && !p.timed;
+    MailEntry* m = &pipe->mailbox[p.share_num & (MAILBOX_SIZE - 1)];
+    __atomic_store_n(&m->tag, (uint64_t)0, __ATOMIC_RELAXED);
+    __atomic_thread_fence(__ATOMIC_RELEASE);
+    const uint64_t f[7] = {(uint64_t)(uintptr_t)q_dev, (uint64_t)(uintptr_t)c->scores.p, (uint64_t)(uintptr_t)half_rows_of(idx, p),
+                           (uint64_t)idx->n, p.share_epoch, (uint64_t)idx->ld, claimable ? MAIL_CLAIMABLE : 0u};
+    for (int w = 0; w < 7; ++w) __atomic_store_n(&m->tag + 1 + w, f[w], __ATOMIC_RELAXED);
+    __atomic_store_n(&m->tag, p.share_num + 1, __ATOMIC_RELEASE);
+  }
   if (rc == SVS_OK && p.timed) idx->ahead_records.fetch_add(1);   // (e0: a start event of the extended launch is a marker of its own, so it stays a record)
   hipEvent_t done = rc == SVS_OK && p.timed && !pipe->per_pass ? p.ev.e1 : pipe->pass_done[j];
   if (!pipe->per_pass) p.pass_stop = done;
@@ -2507,6 +2584,7 @@ static int enqueue_ahead(svs_index* idx, AheadPipe* pipe, const float* q_dev, in
   if (rc != SVS_OK) {   // nothing half enqueued outlives a failed call (the drain also starts the ring over)
     (void)hipStreamSynchronize(st);
     (void)pipe_drain(pipe);
+    pipe->base += 1;    // (a pass may have served the search this call published: its number is not used again)
     return rc;
   }
   pipe->used[j] = true;
@@ -2811,6 +2889,7 @@ int32_t svs_internal_tune(int32_t what, int64_t value) {
     case 2: if (value < 0 || value > 1) break; g_tune_spread.store(value); return SVS_OK;
     case 3: if (value < 0 || value > 1) break; g_tune_refuse_shadow.store(value); return SVS_OK;
     case 4: if (value < 0 || value > 1) break; g_tune_handover.store(value); return SVS_OK;
+    case 5: if (value < 1 || value > SHARE_MAX) break; g_tune_share.store(value); return SVS_OK;
     default: break;
   }
   return fail(SVS_ERR_INVALID, "svs_internal_tune(%d, %lld): unknown knob or value", what, (long long)value);
@@ -2839,6 +2918,7 @@ int32_t svs_index_set_screen(svs_index* idx, int32_t mode) {
   int rc = staging_wait(idx);
   if (rc != SVS_OK) return rc;
   idx->screen_mode.store(mode);
+  idx->geo_epoch.fetch_add(1);
   if (mode == 0) {
     HIP_TRY(hipDeviceSynchronize());   // searches enqueued by the device API may still read the shadow
     shadow_free(idx);
@@ -2852,9 +2932,19 @@ int32_t svs_index_set_screen(svs_index* idx, int32_t mode) {
 int32_t svs_internal_ahead_stats(svs_index* idx, int64_t* out, int32_t cap) {
   if (!idx || !out) return fail(SVS_ERR_INVALID, "null argument");
   std::lock_guard<std::mutex> lk(idx->mu);
-  const int64_t v[7] = {idx->ahead_calls.load(), idx->ahead_plain.load(), idx->ahead_retired.load(), (int64_t)idx->pipes.size(),
-                        idx->ahead_bound.load(), idx->ahead_records.load(), idx->ahead_waits.load()};
-  for (int i = 0; i < cap && i < 7; ++i) out[i] = v[i];
+  // shared passes: the claim kernels' counters, read from their pinned mirrors without synchronising
+  int64_t shared = 0, claimed = 0, empty = 0;
+  for (const AheadPipe* p : idx->pipes) {
+    const volatile uint32_t* h = p->share_mirror();
+    empty += h[0];
+    for (int c = 2; c <= SHARE_MAX; ++c) {
+      shared += h[c];
+      claimed += (int64_t)(c - 1) * h[c];
+    }
+  }
+  const int64_t v[10] = {idx->ahead_calls.load(), idx->ahead_plain.load(), idx->ahead_retired.load(), (int64_t)idx->pipes.size(),
+                         idx->ahead_bound.load(), idx->ahead_records.load(), idx->ahead_waits.load(), shared, claimed, empty};
+  for (int i = 0; i < cap && i < 10; ++i) out[i] = v[i];
   return SVS_OK;
 }
 

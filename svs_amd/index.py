@@ -400,15 +400,22 @@ class DeviceIndex:
         _native.check(self._lib.svs_index_set_screen(self._handle(), int(mode)))
         self._refresh()
 
-    def ahead_stats(self) -> dict:
+    def ahead_stats(self, shared: bool = False) -> dict:
         """``search_device_ahead`` on this handle (svs_internal_ahead_stats; tests): single-query calls that went through
         a pipeline, those that were plain calls because every pipeline had work in flight, idle pipelines handed over to
         another stream, pipelines that exist; then what those calls put on their pass streams: passes whose completion
-        event their last kernel carried, event records, waits for a selection."""
-        out = (C.c_int64 * 7)()
-        _native.check(self._lib.svs_internal_ahead_stats(self._handle(), out, 7))
-        return {"ahead": int(out[0]), "plain": int(out[1]), "handed_over": int(out[2]), "pipelines": int(out[3]),
-                "bound": int(out[4]), "pass_records": int(out[5]), "pass_waits": int(out[6])}
+        event their last kernel carried, event records, waits for a selection.
+
+        ``shared=True`` adds the shared passes' counters (written by the claim kernels; drain the stream first):
+        ``shared_passes`` that served more than one search, searches ``claimed`` by the pass of an earlier search, and
+        ``empty_passes`` that found their search served already."""
+        out = (C.c_int64 * 10)()
+        _native.check(self._lib.svs_internal_ahead_stats(self._handle(), out, 10))
+        stats = {"ahead": int(out[0]), "plain": int(out[1]), "handed_over": int(out[2]), "pipelines": int(out[3]),
+                 "bound": int(out[4]), "pass_records": int(out[5]), "pass_waits": int(out[6])}
+        if shared:
+            stats.update(shared_passes=int(out[7]), claimed=int(out[8]), empty_passes=int(out[9]))
+        return stats
 
     def screen_stats(self) -> dict:
         """Counters and state of the screened search (svs_internal_screen_stats; tests).  Drain the stream first."""
