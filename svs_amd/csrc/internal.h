@@ -19,7 +19,10 @@ int32_t svs_internal_coalesce_hold(svs_index* idx, int32_t n);
  *   3  1 = every allocation of an f32 index's half shadow is refused, as if HBM were full (default 0)
  *   4  run-ahead pipelines MADE FROM NOW ON: 0 = a pass's last kernel carries its completion event and the pass stream
  *      waits for a selection once per group of passes (default); 1 = an event record behind every pass and a wait in
- *      front of every pass */
+ *      front of every pass
+ *   5  run-ahead pipelines MADE FROM NOW ON: queries one score pass may serve (1 .. SHARE_MAX; 1 = no shared passes)
+ *   6  run-ahead pipelines, the grid of a shareable search's own pass: 0 = thin (one resident set of workgroups) where the
+ *      host predicts that an earlier pass serves the search (default); 1 = always the one-shot grid; 2 = always thin */
 int32_t svs_internal_tune(int32_t what, int64_t value);
 /* Seconds since the start of the calling thread's last svs_index_search(host batch) at which: [0] scratch was planned,
  * [1] the queries were in pinned memory (and their DMA enqueued), [2] every kernel was enqueued, [3] the stream had
@@ -43,11 +46,15 @@ int32_t svs_internal_last_launches(const char** kernels, int64_t* rows, int32_t*
  * paused until the next ingest (fallbacks dominated), [4] bits of the bound E and [5] candidate count of the calling
  * thread's last screened search, [6..8] bits of the corpus statistics A, B, C. */
 int32_t svs_internal_screen_stats(svs_index* idx, int64_t* out, int32_t cap);
-/* svs_index_search_device_ahead on this handle, up to cap (<= 7) values: [0] single-query calls that went through a
+/* svs_index_search_device_ahead on this handle, up to cap (<= 13) values: [0] single-query calls that went through a
  * pipeline, [1] single-query calls that were plain calls because every pipeline had work in flight, [2] idle
  * pipelines handed over to another caller stream, [3] pipelines that exist, [4] passes whose completion event was
  * carried by their last kernel, [5] event records enqueued on pass streams (the timing events among them), [6] waits
- * enqueued on pass streams, the caller's query_ready_event not counted. */
+ * enqueued on pass streams, the caller's query_ready_event not counted; then the shared passes' counters as the claim
+ * kernels last wrote them to pinned memory (drain the stream first): [7] passes that served more than one search,
+ * [8] searches served by an earlier search's pass, [9] passes that found their search served; [10] passes launched on
+ * a thin grid, [11] those among them that had work after all, [12] workgroups of the thin grid for this index's row
+ * length (0: its passes are never shared). */
 int32_t svs_internal_ahead_stats(svs_index* idx, int64_t* out, int32_t cap);
 /* The top-k stage ALONE on caller-given data (tests/test_select_routes_gpu.py).  The index supplies the device, a search
  * context and, where asked, its tombstone bitmap; n is the caller's, not the index's.  Each hook runs on the context's own

@@ -9,6 +9,12 @@
 // the pass.  All workgroups of the pass read that one decision across the kernel boundary; none of them reads memory
 // the host may still be writing, nothing spins or polls, and the pass grid issues no atomics.
 //
+// Thin grids.  A search that an earlier pass serves still launches its own pass, which returns at c == 0; the host
+// cannot know what the claim kernel will decide, but it can almost always guess (enqueue_ahead keeps its own copy of the
+// rule below) and then launches that pass on one resident set of workgroups instead of the one-shot grid.  The guess
+// is a hint: the kernel walks all row blocks on any grid, so a thin pass that does have work computes the same scores,
+// only slower.  The claim kernel counts the thin passes and those among them that had work.
+//
 // Publication: every shareable call writes its search into the pipeline's mailbox (pinned host memory, indexed by the
 // search number modulo MAILBOX_SIZE) before it launches anything: tag 0, the fields, then tag = number + 1 with
 // release ordering.  The claim kernel reads tag, fields, tag with system-scope loads and takes an entry only when both
@@ -50,23 +56,24 @@ struct MailEntry {
   uint64_t flags;
 };
 static_assert(sizeof(MailEntry) == 64, "claim kernel: eight 8-byte words per entry");
+constexpr int SHARE_MIRROR_WORDS = SHARE_MAX + 1 + 2;   // pinned mirror of ShareState::hist and ::thin, in that order
 
 // Device-side state of one pipeline, touched by its claim kernels only (stream order: one at a time).
 struct ShareState {
   uint64_t served;                 // every search of the pipeline with a number below this has been served by a pass
   uint32_t hist[SHARE_MAX + 1];    // passes that served 0 (empty), 1, 2, ... queries
-  uint32_t pad;
+  uint32_t thin[2];                // passes launched on a thin grid; those among them that served c > 0 queries
   PassPlan plan;                   // of the pass behind the claim kernel that ran last
 };
 
 // Search `num` is about to run its pass (q, scores: its own; rows / n / epoch / ld: what the pass reads).  `reach`:
 // the last search whose context the waits already enqueued in front of this pass let it write.  `limit`: queries the
-// pass may serve (<= SHARE_MAX).  mirror: SHARE_MAX + 1 words of pinned memory that follow st->hist (plain stores, as
-// the re-score kernel's counters).
+// pass may serve (<= SHARE_MAX).  mirror: SHARE_MIRROR_WORDS words of pinned memory that follow st->hist and st->thin
+// (plain stores, as the re-score kernel's counters).  thin: the pass behind this kernel is launched on a thin grid.
 __global__ __launch_bounds__(64) void pass_claim_kernel(const MailEntry* mailbox, ShareState* st, uint32_t* mirror,
                                                         uint64_t num, uint64_t reach, int limit, const v4f* q,
                                                         float* scores, uint64_t rows, uint64_t n, uint64_t epoch,
-                                                        uint64_t ld) {
+                                                        uint64_t ld, int thin) {
   __shared__ uint64_t ent[SHARE_MAX][8];
   const int lane = threadIdx.x;
   const bool served = st->served > num;   // (uniform: an earlier pass took this search)
@@ -106,6 +113,17 @@ __global__ __launch_bounds__(64) void pass_claim_kernel(const MailEntry* mailbox
   const uint32_t h = st->hist[plan.c] + 1u;
   st->hist[plan.c] = h;
   mirror[plan.c] = h;
+  if (thin) {
+    const int w = plan.c ? 1 : 0;   // (a thin pass with work: the host's guess was wrong, the pass strides over the corpus)
+    const uint32_t t = st->thin[0] + 1u;
+    st->thin[0] = t;
+    mirror[SHARE_MAX + 1] = t;
+    if (w) {
+      const uint32_t tw = st->thin[1] + 1u;
+      st->thin[1] = tw;
+      mirror[SHARE_MAX + 2] = tw;
+    }
+  }
 }
 
 }  // namespace svs

@@ -100,6 +100,8 @@ std::atomic<int64_t> g_tune_refuse_shadow{0}; // 1 = every allocation of an f32 
 std::atomic<int64_t> g_tune_handover{0};      // run-ahead pipelines made from now on: 0 = the pass carries its completion event and the pass stream
                                               // waits once per group of passes; 1 = a record and a wait per pass
 std::atomic<int64_t> g_tune_share{SHARE_DEFAULT};  // run-ahead pipelines made from now on: queries one score pass may serve (1: its own search only)
+std::atomic<int64_t> g_tune_thin{0};          // run-ahead pipelines, grid of a shareable search's pass: 0 = thin where the host predicts that an earlier pass
+                                              // serves the search, 1 = always the one-shot grid, 2 = always thin (tests)
 thread_local double g_host_phase[6];          // svs_internal_host_phases: seconds since the call began (last svs_index_search on this thread)
 
 // svs_internal_last_launches: the score kernels the calling thread's last search / scores call enqueued, in order: every
@@ -256,9 +258,24 @@ struct AheadPipe {
   // shared passes (pass_share.h).  Search numbers never start over: number = base + seq.
   uint64_t base = 0;
   int share_limit = 1;                         // svs_internal_tune(5, v) when the pipeline was made
-  MailEntry* mailbox = nullptr;                // pinned: MAILBOX_SIZE entries, then the mirror of ShareState::hist
+  MailEntry* mailbox = nullptr;                // pinned: MAILBOX_SIZE entries, then the mirror of ShareState::hist and ::thin
   ShareState* share_dev = nullptr;
   uint32_t* share_mirror() const { return (uint32_t*)(mailbox + MAILBOX_SIZE); }
+  // The host's copy of the claim rule (enqueue_ahead: which searches get a thin grid).  A hint only: it may disagree
+  // with the device after a wrong guess, until the next search nothing can claim or the next drain.
+  struct Owner {
+    bool valid = false;                        // the last shareable search the host took for served by its own pass ...
+    uint64_t num = 0, next = 0, reach = 0;     // ... its number, the first search behind its run, its reach,
+    uint64_t rows = 0, n = 0, epoch = 0, ld = 0;   // what its pass reads,
+    uint32_t ordinal = 0;                      // and which claim kernel of the pipeline is its own (counted as `claims`)
+  } owner;
+  uint32_t claims = 0;                         // claim kernels enqueued so far; those that have run: the sum of the mirrored hist
+  uint32_t claims_run() const {
+    const volatile uint32_t* h = share_mirror();
+    uint32_t s = 0;
+    for (int c = 0; c <= SHARE_MAX; ++c) s += h[c];
+    return s;
+  }
   uint64_t tick = 0;                           // svs_index::pipe_tick of the last call that looked it up (under svs_index::mu)
 };
 
@@ -374,6 +391,8 @@ hipError_t pipe_drain(AheadPipe* p) {
     p->used[j] = false;
   }
   p->base += p->seq;   // (search numbers go on: a pass that has run never meets a later search under its number)
+  p->owner.valid = false;
+  if (p->mailbox) p->claims = p->claims_run();   // (every claim kernel has run; one whose launch failed never will)
   p->seq = 0;
   p->covered = 0;
   return e;
@@ -660,16 +679,57 @@ template <int NSTEP>
 constexpr KernelName kF16OneshotName = kernel_name("gemv_f16_oneshot_kernel", NSTEP, f16_rows_r(NSTEP), f16_rows_wpb(NSTEP));
 // half_rows: the index's own rows (an f16 index) or the half shadow of an f32 index (screened search)
 // The plan the next f16 one-shot launch of this thread is to serve (enqueue_score_half sets and clears it around the
-// score launch of a shareable pipeline search); null: the launch's own q and scores.
-thread_local const PassPlan* g_pass_plan;
+// score launch of a shareable pipeline search) and the most queries it may hold; no plan: the launch's own q and scores.
+struct PassLaunch {
+  const PassPlan* plan = nullptr;
+  int limit = 0;
+  bool thin = false;   // on one resident set of workgroups instead of the one-shot grid (the host expects c == 0)
+};
+thread_local PassLaunch g_pass;
+// dynamic LDS of a launch under a plan: the plan's queries as halves (gemv_f16.h), at most 4 x 3584 x 2 = 28 KB
+inline unsigned plan_lds_bytes(int limit, int ld) { return (unsigned)limit * (unsigned)ld * 2u; }
+// The thin grid of an instantiation: as many workgroups as the device holds at once (with the LDS of a full plan).
+template <int NSTEP>
+int thin_grid_rows_f16(const svs_index* idx) {
+  constexpr int R = f16_rows_r(NSTEP), WPB = f16_rows_wpb(NSTEP);
+  static std::atomic<int> per_cu{0};
+  int v = per_cu.load(std::memory_order_relaxed);
+  if (!v) {
+    int nb = 0;
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, gemv_f16_oneshot_kernel<NSTEP, R, WPB>, WPB * 64,
+                                                     (size_t)plan_lds_bytes(SHARE_MAX, NSTEP * 512)) != hipSuccess || nb < 1) {
+      (void)hipGetLastError();
+      nb = 1;
+    }
+    per_cu.store(v = nb, std::memory_order_relaxed);
+  }
+  return idx->cu_count * v;
+}
+// ... of the index's shareable passes (0: its row length does not share)
+int thin_grid_of(const svs_index* idx) {
+  if (idx->ld % 512 != 0) return 0;
+  switch (idx->ld / 512) {
+    case 1: return thin_grid_rows_f16<1>(idx);
+    case 2: return thin_grid_rows_f16<2>(idx);
+    case 3: return thin_grid_rows_f16<3>(idx);
+    case 4: return thin_grid_rows_f16<4>(idx);
+    case 5: return thin_grid_rows_f16<5>(idx);
+    case 6: return thin_grid_rows_f16<6>(idx);
+    case 7: return thin_grid_rows_f16<7>(idx);
+    default: return 0;
+  }
+}
 template <int NSTEP>
 void launch_rows_f16(const svs_index* idx, const void* half_rows, const float* q, float* scores, hipStream_t st) {
   constexpr int R = f16_rows_r(NSTEP), WPB = f16_rows_wpb(NSTEP);
   const int64_t rows_per_block = (int64_t)R * WPB;
-  const int64_t blocks = (idx->n + rows_per_block - 1) / rows_per_block;
+  int64_t blocks = (idx->n + rows_per_block - 1) / rows_per_block;
+  const PassLaunch pl = f16_rows_share(NSTEP) ? g_pass : PassLaunch{};
+  if constexpr (f16_rows_share(NSTEP))
+    if (pl.plan && pl.thin) blocks = std::min<int64_t>(blocks, thin_grid_rows_f16<NSTEP>(idx));
   launch_record(kF16OneshotName<NSTEP>.s, idx->n, 1);
-  launch_tail(gemv_f16_oneshot_kernel<NSTEP, R, WPB>, dim3((unsigned)blocks), dim3(WPB * 64), 0, st,
-              (const u32x4*)half_rows, (const v4f*)q, scores, idx->n, g_pass_plan);
+  launch_tail(gemv_f16_oneshot_kernel<NSTEP, R, WPB>, dim3((unsigned)blocks), dim3(WPB * 64), pl.plan ? plan_lds_bytes(pl.limit, NSTEP * 512) : 0u, st,
+              (const u32x4*)half_rows, (const v4f*)q, scores, idx->n, pl.plan);
 }
 
 template <int T>
@@ -1361,6 +1421,7 @@ struct SearchPlan {
   // run-ahead pipeline, shareable search (enqueue_ahead): the claim kernel's launch in front of the pass
   const AheadPipe* share = nullptr;
   uint64_t share_num = 0, share_reach = 0, share_epoch = 0;
+  bool share_thin = false;           // ... and the pass on a thin grid
 };
 
 // Histogram / candidate scratch of run_select's window path (n_eff > SORT_CAP, count <= SEL_KMAX) for nq queries.
@@ -1476,13 +1537,13 @@ int enqueue_score_half(svs_index* idx, Ctx* c, SearchPlan& p, const float* q_dev
     const AheadPipe* sp = p.share;
     hipLaunchKernelGGL(pass_claim_kernel, dim3(1), dim3(64), 0, st, (const MailEntry*)sp->mailbox, sp->share_dev, sp->share_mirror(),
                        p.share_num, p.share_reach, sp->share_limit, (const v4f*)q_dev, c->scores.p, (uint64_t)(uintptr_t)half_rows_of(idx, p),
-                       (uint64_t)n, p.share_epoch, (uint64_t)idx->ld);
-    g_pass_plan = &sp->share_dev->plan;
+                       (uint64_t)n, p.share_epoch, (uint64_t)idx->ld, p.share_thin ? 1 : 0);
+    g_pass = PassLaunch{&sp->share_dev->plan, sp->share_limit, p.share_thin};
   }
   if (carry && !masked) tail_arm(p.pass_stop);
   if (p.screen) rc = launch_screen_scores(idx, c, q_dev, c->scores, &p.q_padded, st);
   else rc = launch_scores_any(idx, c, q_dev, n, nq, c->scores, p.sstride, FuseLaunch{}, st, !p.staged);
-  g_pass_plan = nullptr;
+  g_pass = PassLaunch{};
   if (rc != SVS_OK) {
     (void)tail_take();
     return rc;
@@ -2463,7 +2524,7 @@ static int pipe_get(svs_index* idx, hipStream_t caller, AheadPipe** out) {
   p->per_pass = g_tune_handover.load() == 1;
   p->share_limit = (int)g_tune_share.load();
   hipError_t e = hipStreamCreateWithFlags(&p->pass, hipStreamNonBlocking);
-  const size_t mail_bytes = sizeof(MailEntry) * MAILBOX_SIZE + sizeof(uint32_t) * (SHARE_MAX + 1);
+  const size_t mail_bytes = sizeof(MailEntry) * MAILBOX_SIZE + sizeof(uint32_t) * SHARE_MIRROR_WORDS;
   if (e == hipSuccess) e = hipHostMalloc((void**)&p->mailbox, mail_bytes, hipHostMallocDefault);
   if (e == hipSuccess) memset(p->mailbox, 0, mail_bytes);
   else p->mailbox = nullptr;
@@ -2562,6 +2623,24 @@ static int enqueue_ahead(svs_index* idx, AheadPipe* pipe, const float* q_dev, in
                            (uint64_t)idx->n, p.share_epoch, (uint64_t)idx->ld, claimable ? MAIL_CLAIMABLE : 0u};
     for (int w = 0; w < 7; ++w) __atomic_store_n(&m->tag + 1 + w, f[w], __ATOMIC_RELAXED);
     __atomic_store_n(&m->tag, p.share_num + 1, __ATOMIC_RELEASE);
+    // The grid of this search's own pass.  The claim rule, restated: the search joins the run of the last search the
+    // host took for an owner when it is the next number, the run is short of the limit, it is claimable and within the
+    // owner's reach, and its pass reads what the owner's reads.  The owner's claim kernel will then find it -- it is
+    // published -- unless that kernel has run already: the mirrored counters (plain loads, a hint) say how many have.
+    AheadPipe::Owner& o = pipe->owner;
+    const bool joins = o.valid && p.share_num == o.next && o.next - o.num < (uint64_t)pipe->share_limit && claimable &&
+                       p.share_num <= o.reach && f[2] == o.rows && f[3] == o.n && f[4] == o.epoch && f[5] == o.ld;
+    pipe->claims += 1;   // (this search's own claim kernel: enqueue_score_half launches it first)
+    if (joins && (int32_t)(pipe->claims_run() - o.ordinal) < 0) {
+      o.next += 1;
+      p.share_thin = true;
+    } else {
+      o = AheadPipe::Owner{true, p.share_num, p.share_num + 1, p.share_reach, f[2], f[3], f[4], f[5], pipe->claims};
+    }
+    const int64_t mode = g_tune_thin.load();
+    if (mode) p.share_thin = mode == 2;
+  } else {
+    pipe->owner.valid = false;   // (a search that publishes nothing ends every run)
   }
   if (rc == SVS_OK && p.timed) idx->ahead_records.fetch_add(1);   // (e0: a start event of the extended launch is a marker of its own, so it stays a record)
   hipEvent_t done = rc == SVS_OK && p.timed && !pipe->per_pass ? p.ev.e1 : pipe->pass_done[j];
@@ -2890,6 +2969,7 @@ int32_t svs_internal_tune(int32_t what, int64_t value) {
     case 3: if (value < 0 || value > 1) break; g_tune_refuse_shadow.store(value); return SVS_OK;
     case 4: if (value < 0 || value > 1) break; g_tune_handover.store(value); return SVS_OK;
     case 5: if (value < 1 || value > SHARE_MAX) break; g_tune_share.store(value); return SVS_OK;
+    case 6: if (value < 0 || value > 2) break; g_tune_thin.store(value); return SVS_OK;
     default: break;
   }
   return fail(SVS_ERR_INVALID, "svs_internal_tune(%d, %lld): unknown knob or value", what, (long long)value);
@@ -2933,18 +3013,23 @@ int32_t svs_internal_ahead_stats(svs_index* idx, int64_t* out, int32_t cap) {
   if (!idx || !out) return fail(SVS_ERR_INVALID, "null argument");
   std::lock_guard<std::mutex> lk(idx->mu);
   // shared passes: the claim kernels' counters, read from their pinned mirrors without synchronising
-  int64_t shared = 0, claimed = 0, empty = 0;
+  int64_t shared = 0, claimed = 0, empty = 0, thin = 0, thin_worked = 0;
   for (const AheadPipe* p : idx->pipes) {
     const volatile uint32_t* h = p->share_mirror();
     empty += h[0];
+    thin += h[SHARE_MAX + 1];
+    thin_worked += h[SHARE_MAX + 2];
     for (int c = 2; c <= SHARE_MAX; ++c) {
       shared += h[c];
       claimed += (int64_t)(c - 1) * h[c];
     }
   }
-  const int64_t v[10] = {idx->ahead_calls.load(), idx->ahead_plain.load(), idx->ahead_retired.load(), (int64_t)idx->pipes.size(),
-                         idx->ahead_bound.load(), idx->ahead_records.load(), idx->ahead_waits.load(), shared, claimed, empty};
-  for (int i = 0; i < cap && i < 10; ++i) out[i] = v[i];
+  int64_t thin_grid = 0;
+  if (cap > 12 && hipSetDevice(idx->device) == hipSuccess) thin_grid = thin_grid_of(idx);
+  const int64_t v[13] = {idx->ahead_calls.load(), idx->ahead_plain.load(), idx->ahead_retired.load(), (int64_t)idx->pipes.size(),
+                         idx->ahead_bound.load(), idx->ahead_records.load(), idx->ahead_waits.load(), shared, claimed, empty,
+                         thin, thin_worked, thin_grid};
+  for (int i = 0; i < cap && i < 13; ++i) out[i] = v[i];
   return SVS_OK;
 }
 

@@ -408,13 +408,16 @@ class DeviceIndex:
 
         ``shared=True`` adds the shared passes' counters (written by the claim kernels; drain the stream first):
         ``shared_passes`` that served more than one search, searches ``claimed`` by the pass of an earlier search, and
-        ``empty_passes`` that found their search served already."""
-        out = (C.c_int64 * 10)()
-        _native.check(self._lib.svs_internal_ahead_stats(self._handle(), out, 10))
+        ``empty_passes`` that found their search served already; ``thin_passes`` launched on the thin grid because
+        the host expected them to be empty, ``thin_worked`` among them that had work after all, and ``thin_grid``, the
+        workgroups of such a grid for this index's row length (0: its passes are never shared)."""
+        out = (C.c_int64 * 13)()
+        _native.check(self._lib.svs_internal_ahead_stats(self._handle(), out, 13))
         stats = {"ahead": int(out[0]), "plain": int(out[1]), "handed_over": int(out[2]), "pipelines": int(out[3]),
                  "bound": int(out[4]), "pass_records": int(out[5]), "pass_waits": int(out[6])}
         if shared:
-            stats.update(shared_passes=int(out[7]), claimed=int(out[8]), empty_passes=int(out[9]))
+            stats.update(shared_passes=int(out[7]), claimed=int(out[8]), empty_passes=int(out[9]),
+                         thin_passes=int(out[10]), thin_worked=int(out[11]), thin_grid=int(out[12]))
         return stats
 
     def screen_stats(self) -> dict:
