@@ -149,6 +149,27 @@ int32_t svs_index_staging_finish(svs_index* idx);
  * is unchanged, so results equal those of a rebuilt matrix up to the row numbering. */
 int32_t svs_index_mask_rows(svs_index* idx, const int64_t* rows, int64_t count);
 
+/* Physically removes the tombstoned rows: live local row r becomes r - (dead rows below r); n shrinks by
+ * n_masked, n_masked becomes 0.  Capacity and hbm_bytes are unchanged (the tail serves later appends).
+ * out_old_rows[p] (p < new n) = the GLOBAL row that new local row p was; may be NULL.  If out_capacity <
+ * live rows (and out_old_rows != NULL) nothing is done: SVS_ERR_INVALID, *out_n = live rows.  *out_n
+ * (may be NULL) = rows after the call.  No tombstones: SVS_OK, nothing launched, identity map.
+ *   - The rows move inside the HBM image (the relative order is kept, so the result is the matrix a rebuild from
+ *     the live rows would hold); besides a bounce buffer of about 32 MiB, freed before the call returns, nothing
+ *     is allocated.  Afterwards every entry point works as on an index freshly built from the live rows.
+ *   - Like the ingest calls it holds a reference and the geometry lock exclusively: searches on this handle
+ *     wait, and a search is never half-way through a compaction.  It waits for pending staging copies and for
+ *     everything the device entries have enqueued before the first row moves.
+ *   - RENUMBERING: a row index obtained before the call names another row (or none) after it.  Rows written by
+ *     svs_index_search_device / _ahead searches enqueued BEFORE the call are in the old numbering, those of later
+ *     searches in the new one; a caller that keeps a row -> id table applies out_old_rows to it.
+ *   - Failures: a bad argument, a map that is too small and SVS_ERR_NOMEM (no HBM for a bounce buffer of even one
+ *     row) leave the handle untouched.  SVS_ERR_DEVICE after the first move: the rows are in no defined order and
+ *     the handle is only good for svs_index_release.
+ *   - Not for the shards of an svs_multi (svs_multi_shard): the global numbering of svs_multi_search assumes the
+ *     shard boundaries it was created with. */
+int32_t svs_index_compact(svs_index* idx, int64_t* out_old_rows, int64_t out_capacity, int64_t* out_n);
+
 int32_t svs_index_retain(svs_index* idx);
 /* Drops one reference; HBM is freed when the last holder (including in-flight
  * searches) lets go.  Called from invalidate(), src/svs/kb.py:861-864. */
@@ -216,7 +237,7 @@ int32_t svs_index_search_device(svs_index* idx, const float* dev_queries, int32_
  *     pass).  Results are bit-identical to searches served one by one.  It relies on the rule above: a query
  *     without a ready event must be complete on the device when the call is made, because an EARLIER search's
  *     pass may read it.  A search with a ready event is always served by its own pass.
- * Ingest (append, reserve, staging commit, mask_rows, set_screen) and svs_index_release may be called with
+ * Ingest (append, reserve, staging commit, mask_rows, compact, set_screen) and svs_index_release may be called with
  * such searches enqueued, as with svs_index_search_device: they wait for what they would disturb. */
 int32_t svs_index_search_device_ahead(svs_index* idx, const float* dev_query, int32_t nq, int32_t d, int32_t k,
                                       float* dev_out_scores, int64_t* dev_out_rows, int32_t* out_count,

@@ -75,6 +75,7 @@ SIGNATURES = {
     "svs_multi_coalesce_stats": (C.c_int32, [_P, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
     "svs_multi_shard": (C.c_int32, [_P, C.c_int32, C.POINTER(_P)]),
     "svs_index_mask_rows": (C.c_int32, [_P, _P, C.c_int64]),
+    "svs_index_compact": (C.c_int32, [_P, _P, C.c_int64, C.POINTER(C.c_int64)]),
     "svs_index_retain": (C.c_int32, [_P]),
     "svs_index_release": (C.c_int32, [_P]),
     "svs_index_info": (C.c_int32, [_P, C.POINTER(IndexInfo)]),
@@ -105,6 +106,8 @@ INTERNAL = {
     "svs_internal_kth_value": (C.c_int32, [_P, _P, C.c_int32, C.c_int64, C.c_int32, C.c_int32, _P, C.POINTER(C.c_int64)]),
     "svs_internal_select_candidates": (C.c_int32, [_P, _P, _P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P, _P,
                                                    C.POINTER(C.c_int64)]),
+    "svs_internal_compact_plan": (C.c_int64, [_P, C.c_int64, C.c_int64, C.c_int64, _P, C.c_int64]),
+    "svs_internal_compact": (C.c_int32, [_P, C.c_int64, _P, C.c_int64, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
 }
 
 _lib: Optional[C.CDLL] = None

@@ -77,6 +77,14 @@ int32_t svs_internal_kth_value(svs_index* idx, const float* scores, int32_t nq, 
 int32_t svs_internal_select_candidates(svs_index* idx, const uint64_t* keys, const int64_t* key_offsets, const uint32_t* n_cand,
                                        int32_t nq, int32_t k, int32_t count, int32_t use_dead, float* out_scores,
                                        int64_t* out_rows, int64_t* out_dirty);
+/* The steps of an in-place compaction (compact.h), pure host code: dead_sorted = the ndead tombstoned local rows of an
+ * n-row index, strictly ascending.  steps[3 i ..] = kind (0 DIRECT: one launch, dst0 + count <= source of dst0; 1 BOUNCE:
+ * through the bounce buffer, count <= bounce_rows), dst0, count; ascending and contiguous from the first dead row to
+ * n - ndead.  Up to cap steps are written; returns the number of steps of the plan, or SVS_ERR_INVALID. */
+int64_t svs_internal_compact_plan(const uint32_t* dead_sorted, int64_t ndead, int64_t n, int64_t bounce_rows, int64_t* steps, int64_t cap);
+/* svs_index_compact with a bounce buffer of bounce_rows rows (<= 0: the default).  stats[4] (may be NULL): DIRECT steps,
+ * BOUNCE steps, rows moved, bytes moved (rows, scales and shadow rows, each byte counted once). */
+int32_t svs_internal_compact(svs_index* idx, int64_t bounce_rows, int64_t* out_old_rows, int64_t cap, int64_t* out_n, int64_t* stats);
 /* multi.hip -> svs_amd.hip: carries a worker thread's error message over to the caller's thread */
 int32_t svs_internal_set_error(int32_t code, const char* msg);
 #ifdef __cplusplus

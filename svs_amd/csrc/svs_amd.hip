@@ -35,6 +35,7 @@
 #include "gemv_f32.h"
 #include "select.h"
 #include "screen.h"
+#include "compact.h"
 
 namespace {
 
@@ -2107,6 +2108,147 @@ int append_rows(svs_index* idx, int64_t n_new, const char* what, Copy copy) {
   return sync_dead_bits(idx);
 }
 
+// ---- in-place compaction (compact.h) ----------------------------------------------------------------
+// One launch of a step: destinations [dst0, dst0 + count) of `to` from `from` (gather == true: `from` is the corpus,
+// read at the rows the dead list gives; false: `from` is the bounce buffer, row t for destination dst0 + t).
+template <int FORM>
+void launch_compact_move(const svs_index* idx, bool gather, CompactBufs from, CompactBufs to, const uint32_t* dead, int64_t ndead,
+                         int64_t dst0, int64_t count, int chunks, int shadow_chunks) {
+  int lanes_log2 = 0;
+  while (lanes_log2 < 6 && (1 << lanes_log2) < chunks) ++lanes_log2;   // lanes per row: a power of two, a wave at most
+  // destinations per wave and batch: 64 while such batches still fill the device, fewer for a short step; at least the
+  // rows a wave copies at a time
+  int batch_log2 = 6;
+  while (batch_log2 > 6 - lanes_log2 && (count >> batch_log2) < (int64_t)idx->cu_count * 32) --batch_log2;
+  const int64_t batches = (count + (1 << batch_log2) - 1) >> batch_log2;
+  const int64_t blocks = std::min<int64_t>((batches + 3) / 4, (int64_t)idx->cu_count * 8);
+  if (gather)
+    hipLaunchKernelGGL((compact_move_kernel<FORM, true>), dim3((unsigned)blocks), dim3(256), 0, nullptr, from, to, dead, ndead, dst0, count,
+                       chunks, shadow_chunks, lanes_log2, batch_log2);
+  else
+    hipLaunchKernelGGL((compact_move_kernel<FORM, false>), dim3((unsigned)blocks), dim3(256), 0, nullptr, from, to, dead, ndead, dst0, count,
+                       chunks, shadow_chunks, lanes_log2, batch_log2);
+}
+
+void launch_compact_move(const svs_index* idx, int form, bool gather, CompactBufs from, CompactBufs to, const uint32_t* dead,
+                         int64_t ndead, int64_t dst0, int64_t count, int chunks, int shadow_chunks) {
+  if (form == COMPACT_SCALES) launch_compact_move<COMPACT_SCALES>(idx, gather, from, to, dead, ndead, dst0, count, chunks, shadow_chunks);
+  else if (form == COMPACT_SHADOW) launch_compact_move<COMPACT_SHADOW>(idx, gather, from, to, dead, ndead, dst0, count, chunks, shadow_chunks);
+  else launch_compact_move<COMPACT_PLAIN>(idx, gather, from, to, dead, ndead, dst0, count, chunks, shadow_chunks);
+}
+
+// svs_index_compact / svs_internal_compact.  bounce_rows <= 0: the default, about 32 MiB of rows.  Everything that can
+// fail for want of an argument, of capacity or of memory comes before the first move.
+int compact_index(svs_index* idx, int64_t bounce_rows, int64_t* out_old_rows, int64_t out_capacity, int64_t* out_n, int64_t* stats) {
+  if (stats) stats[0] = stats[1] = stats[2] = stats[3] = 0;
+  if (!idx) return fail(SVS_ERR_INVALID, "null index");
+  RefGuard guard(idx);
+  std::unique_lock<std::shared_mutex> geo(idx->rw);   // no search is enqueuing while the rows move
+  const int64_t n = idx->n, ndead = (int64_t)idx->dead_list.size(), n_live = n - ndead;
+  if (out_n) *out_n = n_live;
+  if (out_old_rows && out_capacity < n_live)
+    return fail(SVS_ERR_INVALID, "svs_index_compact: %lld live rows, the row map holds %lld", (long long)n_live, (long long)out_capacity);
+  if (ndead == 0) {
+    for (int64_t p = 0; out_old_rows && p < n; ++p) out_old_rows[p] = idx->row_offset + p;
+    return SVS_OK;
+  }
+  HIP_TRY(hipSetDevice(idx->device));
+  int rc = staging_wait(idx);
+  if (rc != SVS_OK) return rc;
+  // the dead rows ascending (mask_rows appends them in the caller's order): one pass over the flags, no sort
+  std::vector<uint32_t> dead((size_t)ndead + 1);
+  {
+    size_t j = 0;
+    for (int64_t r = 0; r < n; ++r) {
+      dead[j] = (uint32_t)r;
+      j += idx->dead_flag[(size_t)r] != 0;
+    }
+    dead.resize((size_t)ndead);
+  }
+  const bool shadow = idx->shadow != nullptr;
+  const int form = idx->row_scales ? COMPACT_SCALES : (shadow ? COMPACT_SHADOW : COMPACT_PLAIN);
+  const size_t row_b = (size_t)idx->ld * elem_bytes(idx), shadow_b = shadow ? (size_t)idx->ld * sizeof(_Float16) : 0;
+  const size_t scale_b = idx->row_scales ? sizeof(float) : 0;
+  const int chunks = (int)(row_b / 16), shadow_chunks = (int)(shadow_b / 16);
+  if (bounce_rows <= 0) bounce_rows = (int64_t)std::max<size_t>(1, ((size_t)32 << 20) / std::max<size_t>(row_b, 1));
+  // plan, then the bounce buffer the plan needs; if HBM has no room for it, a smaller one and a new plan
+  DevTmp tmp;
+  std::vector<int64_t> steps;
+  char* bounce = nullptr;
+  for (;; bounce_rows /= 2) {
+    if (row_b == 0) break;   // (a zero-dimensional index: nothing to move)
+    const int64_t ns = compact_plan(dead.data(), ndead, n, bounce_rows, nullptr, 0);
+    if (ns < 0) return fail(SVS_ERR_INVALID, "internal: bad tombstone list");
+    steps.assign((size_t)ns * 3, 0);
+    (void)compact_plan(dead.data(), ndead, n, bounce_rows, steps.data(), ns);
+    bool bounces = false;
+    for (int64_t i = 0; i < ns; ++i) bounces = bounces || steps[3 * i] == COMPACT_BOUNCE;
+    if (!bounces || hipMalloc((void**)&bounce, (size_t)bounce_rows * (row_b + shadow_b + scale_b)) == hipSuccess) break;
+    (void)hipGetLastError();
+    bounce = nullptr;
+    if (bounce_rows == 1) return fail(SVS_ERR_NOMEM, "svs_index_compact: no HBM for a bounce buffer of one row");
+  }
+  if (bounce) tmp.p.push_back(bounce);
+  uint32_t* dead_sorted = nullptr;
+  if (!steps.empty()) {
+    HIP_TRY(tmp.alloc(&dead_sorted, (size_t)ndead * sizeof(uint32_t)));
+    HIP_TRY(hipMemcpy(dead_sorted, dead.data(), (size_t)ndead * sizeof(uint32_t), hipMemcpyHostToDevice));
+  }
+  // work enqueued by the device entries may still read the rows; the pipelines start their rings over
+  HIP_TRY(hipDeviceSynchronize());
+  for (AheadPipe* p : idx->pipes) {
+    std::lock_guard<std::mutex> lk(p->mu);
+    HIP_TRY(pipe_drain(p));
+  }
+  const CompactBufs corpus{(uint4*)idx->rows, idx->row_scales, (uint4*)idx->shadow};
+  CompactBufs bnc{};   // rows, then shadow rows, then scales: every part starts on a 16-byte boundary
+  if (bounce) bnc = CompactBufs{(uint4*)bounce, (float*)(bounce + (size_t)bounce_rows * (row_b + shadow_b)), (uint4*)(bounce + (size_t)bounce_rows * row_b)};
+  int64_t moved = 0, n_direct = 0, n_bounce = 0;
+  for (size_t i = 0; i < steps.size(); i += 3) {
+    const int64_t kind = steps[i], dst0 = steps[i + 1], count = steps[i + 2];
+    const CompactBufs at{corpus.rows + (size_t)dst0 * chunks, corpus.scales ? corpus.scales + dst0 : nullptr,
+                         corpus.shadow ? corpus.shadow + (size_t)dst0 * shadow_chunks : nullptr};
+    if (kind == COMPACT_DIRECT) {
+      launch_compact_move(idx, form, true, corpus, at, dead_sorted, ndead, dst0, count, chunks, shadow_chunks);
+      ++n_direct;
+    } else {
+      launch_compact_move(idx, form, true, corpus, bnc, dead_sorted, ndead, dst0, count, chunks, shadow_chunks);
+      launch_compact_move(idx, form, false, bnc, at, dead_sorted, ndead, dst0, count, chunks, shadow_chunks);
+      ++n_bounce;
+    }
+    moved += count;
+  }
+  hipError_t e = hipGetLastError();
+  if (e == hipSuccess) e = hipDeviceSynchronize();
+  if (e == hipSuccess && idx->dead_bits_dev.cap) e = hipMemset(idx->dead_bits_dev, 0, idx->dead_bits_dev.cap * sizeof(uint32_t));
+  if (e == hipSuccess && idx->dead_dev.cap) e = hipMemset(idx->dead_dev, 0, idx->dead_dev.cap * sizeof(uint32_t));
+  if (e != hipSuccess)
+    return fail(SVS_ERR_DEVICE, "svs_index_compact: %s while rows were moving; the handle is only good for svs_index_release",
+                hipGetErrorString(e));
+  if (out_old_rows) {   // (branch-free: the slot is overwritten until a live row keeps it; the last live row is the last write inside the map)
+    int64_t p = 0;
+    for (int64_t r = 0; r < n && p < n_live; ++r) {
+      out_old_rows[p] = idx->row_offset + r;
+      p += idx->dead_flag[(size_t)r] == 0;
+    }
+  }
+  idx->n = n_live;
+  idx->dead_flag.assign((size_t)n_live, 0);
+  idx->dead_list.clear();
+  idx->dead_bits.clear();
+  {
+    std::lock_guard<std::mutex> lk(idx->pfx_mu);
+    idx->pfx_n = -1;   // (the sample's rows have moved, whatever the row count says after later appends)
+  }
+  idx->scr_paused.store(false);
+  idx->geo_epoch.fetch_add(1);
+  if (stats) {
+    stats[0] = n_direct; stats[1] = n_bounce; stats[2] = moved;
+    stats[3] = moved * (int64_t)(row_b + shadow_b + scale_b);
+  }
+  return SVS_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -2279,6 +2421,20 @@ int32_t svs_index_mask_rows(svs_index* idx, const int64_t* rows, int64_t count) 
   }
   HIP_TRY(hipMemcpy(idx->dead_dev, idx->dead_list.data(), idx->dead_list.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
   return SVS_OK;
+}
+
+int32_t svs_index_compact(svs_index* idx, int64_t* out_old_rows, int64_t out_capacity, int64_t* out_n) {
+  return compact_index(idx, 0, out_old_rows, out_capacity, out_n, nullptr);
+}
+
+int32_t svs_internal_compact(svs_index* idx, int64_t bounce_rows, int64_t* out_old_rows, int64_t cap, int64_t* out_n, int64_t* stats) {
+  return compact_index(idx, bounce_rows, out_old_rows, cap, out_n, stats);
+}
+
+int64_t svs_internal_compact_plan(const uint32_t* dead_sorted, int64_t ndead, int64_t n, int64_t bounce_rows, int64_t* steps, int64_t cap) {
+  const int64_t ns = compact_plan(dead_sorted, ndead, n, bounce_rows, steps, cap);
+  if (ns < 0) return fail(SVS_ERR_INVALID, "svs_internal_compact_plan: the dead rows must ascend strictly inside [0, n), bounce_rows >= 1");
+  return ns;
 }
 
 int32_t svs_index_retain(svs_index* idx) {

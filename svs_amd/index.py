@@ -182,6 +182,37 @@ class DeviceIndex:
         _native.check(self._lib.svs_index_mask_rows(self._handle(), r.ctypes.data_as(C.c_void_p), r.shape[0]))
         self._refresh()
 
+    def compact(self, bounce_rows: int = 0, stats: Optional[list] = None) -> np.ndarray:
+        """Physically removes the tombstoned rows, in place in HBM (svs_index_compact): live row r becomes
+        r - (dead rows below r), ``n`` shrinks, ``n_masked`` becomes 0.  Returns the old GLOBAL row of every new row
+        (i64, one per row left).  Row indices obtained before the call are stale after it.  ``bounce_rows`` / ``stats``
+        (a list that receives DIRECT steps, BOUNCE steps, rows moved, bytes moved) go through svs_internal_compact:
+        tests and tools."""
+        h = self._pinned_handle()
+        try:
+            info = _native.IndexInfo()
+            _native.check(self._quick.svs_index_info(h, C.byref(info)))
+            live = max(int(info.n) - int(info.n_masked), 0)
+            for _ in range(8):
+                # (rows appended through another owner since the map was sized: the call reports the count to retry with)
+                out = np.empty(live, dtype=np.int64)
+                now = C.c_int64(0)
+                if bounce_rows or stats is not None:
+                    st = (C.c_int64 * 4)()
+                    rc = self._lib.svs_internal_compact(h, int(bounce_rows), out.ctypes.data_as(C.c_void_p), live, C.byref(now), st)
+                    if stats is not None:
+                        stats[:] = [int(v) for v in st]
+                else:
+                    rc = self._lib.svs_index_compact(h, out.ctypes.data_as(C.c_void_p), live, C.byref(now))
+                if rc == _native.SVS_OK or now.value <= live:
+                    break
+                live = now.value
+            _native.check(rc)
+        finally:
+            self._unpin(h)
+        self._refresh()
+        return out[:now.value]
+
     def share(self) -> "DeviceIndex":
         """A second owner of the same HBM copy (its own reference): what an
         in-flight AsyncKB search holds so that ``invalidate()`` on another task

@@ -30,7 +30,8 @@ from typing import Any, Awaitable, Callable, Dict, Iterator, List, Optional, Tup
 import numpy as np
 
 from .index import DeviceIndex
-from .matrix import DeviceEmbeddingsMatrix, search_within_held
+from .matrix import (DeviceEmbeddingsMatrix, ids_of_batch, ids_of_pairs, ids_of_rows, search_mapped, search_within_held,
+                     single_search)
 
 _LOG = logging.getLogger(__name__)
 
@@ -584,15 +585,16 @@ class AsyncKB:
             db = await self._ensure_db()
             await self.embeddings_matrix.get(db)
             # own a reference now: a later invalidate() must not affect this search
-            idx, lookup, co = self.embeddings_matrix.hold_search()
+            held = self.embeddings_matrix.hold_search()
+            idx = held[0]
         try:
             query_vec = np.array((await self._embed([query]))[0], dtype=np.float32)
             _LOG.info("got embedding for query!")
 
             def superheavy() -> List[Tuple[float, int]]:
                 # tasks whose searches are in flight together share corpus passes (svs_amd/coalesce.py)
-                res = co.search(idx, query_vec, n) if co is not None else idx.search(query_vec, n)
-                return [(score, int(lookup.arr[row])) for score, row in res]
+                return search_mapped(self.embeddings_matrix.hold_search, held,
+                                     lambda idx, lookup, co: single_search(idx, co, query_vec, n), ids_of_rows)
 
             emb_ids = await loop.run_in_executor(None, superheavy)
             _LOG.info(f"computed {idx.shape[0]} cosine similarities")
@@ -628,7 +630,8 @@ class AsyncKB:
         try:
             query_vec = np.array((await self._embed([query]))[0], dtype=np.float32)
             _LOG.info("got embedding for query!")
-            emb_ids = await loop.run_in_executor(None, lambda: search_within_held(idx, lookup, query_vec, n, emb))
+            emb_ids = await loop.run_in_executor(None, lambda: search_within_held(idx, lookup, query_vec, n, emb,
+                                                                                       self.embeddings_matrix.hold))
             _LOG.info(f"computed {len(emb)} cosine similarities")
         finally:
             idx.release()
@@ -665,9 +668,8 @@ class AsyncKB:
             qmat = np.array(vecs, dtype=np.float32)
 
             def superheavy() -> List[List[Tuple[float, int]]]:
-                scores, rows = idx.search_batch(qmat, n)
-                arr = lookup.arr
-                return [[(float(s), int(arr[r])) for s, r in zip(scores[i], rows[i])] for i in range(len(scores))]
+                return search_mapped(self.embeddings_matrix.hold, (idx, lookup), lambda idx, lookup: idx.search_batch(qmat, n),
+                                     ids_of_batch)
 
             per_query = await loop.run_in_executor(None, superheavy)
             _LOG.info(f"computed {idx.shape[0]} x {len(vecs)} cosine similarities")
@@ -703,9 +705,7 @@ class AsyncKB:
             _LOG.info(f"computing pairwise similarity over {n_docs} documents")
 
             def superheavy() -> List[Tuple[float, int, int]]:
-                res = idx.top_pairs(n)
-                arr = lookup.arr
-                return [(score, int(arr[i]), int(arr[j])) for score, i, j in res]
+                return search_mapped(self.embeddings_matrix.hold, (idx, lookup), lambda idx, lookup: idx.top_pairs(n), ids_of_pairs)
 
             pairs = await loop.run_in_executor(None, superheavy)
             _LOG.info(f"computed {n_docs * n_docs} pairwise cosine similarities")

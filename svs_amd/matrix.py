@@ -42,19 +42,56 @@ def _default_builder(db) -> Tuple[np.ndarray, np.ndarray]:
 
 
 class _Lookup:
-    """Row -> embedding-id table of one loaded matrix.  ``arr`` only ever grows
+    """Row -> embedding-id table of one NUMBERING of a loaded matrix.  ``arr`` only ever grows
     (append) and masked rows are never returned, so a search that started before an
     append can map its rows through the CURRENT array; a search that outlives an
-    ``invalidate()`` keeps this object (and so the right table) alive."""
+    ``invalidate()`` keeps this object (and so the right table) alive.
+
+    An in-place compaction (``DeviceEmbeddingsMatrix.remove``) renumbers the rows of the SAME index:
+    it sets ``stale`` on this object before the rows move, never touches ``arr``, and installs a new
+    ``_Lookup`` for the new numbering.  The index makes a compaction and a search exclude each other,
+    so rows are in this object's numbering exactly when ``stale`` still reads False AFTER the native
+    call that produced them (``search_mapped``)."""
 
     def __init__(self, arr: np.ndarray):
         self.arr = arr
+        self.stale = False
 
 
-def search_within_held(idx, lookup: _Lookup, query_vec: np.ndarray, n: int, emb_ids) -> List[Tuple[float, int]]:
-    """Top-n among ``emb_ids`` on a held (index, lookup): ids -> rows through ``lookup.arr`` (strictly increasing,
-    so one ``searchsorted``, as ``remove`` does), the filtered search, rows -> ids.  KeyError for an id the
-    loaded matrix does not hold."""
+def search_mapped(hold: Callable[[], tuple], held: tuple, native: Callable[..., Any], finish: Callable[[Any, np.ndarray], Any]):
+    """Every search that maps rows through a lookup goes through here.  ``held`` = ``(idx, lookup, ...)`` as
+    ``hold()`` / ``hold_search()`` returned it (the caller owns and releases that reference); ``native(*held)``
+    runs the search and returns rows in the index's numbering; ``finish(result, lookup.arr)`` maps them to ids.
+
+    The native call comes first, the read of ``lookup.stale`` second: False proves that no compaction had
+    begun when the search ran, so its rows are in that lookup's numbering.  True: the rows may be in either
+    numbering (and a search given rows of the old one may have failed on them); they are dropped, a fresh
+    ``hold()`` -- released here -- is taken and the search repeated."""
+    own = None
+    try:
+        while True:
+            lookup = held[1]
+            try:
+                res = native(*held)
+            except Exception:
+                if not lookup.stale:
+                    raise
+                res = None
+            if not lookup.stale:
+                return finish(res, lookup.arr)   # (an append during the search only extends arr)
+            if own is not None:
+                own.release()
+                own = None
+            held = hold()
+            own = held[0]
+    finally:
+        if own is not None:
+            own.release()
+
+
+def _within_rows(idx, lookup: _Lookup, emb_ids) -> np.ndarray:
+    """GLOBAL rows of ``emb_ids`` in the numbering of ``lookup`` (strictly increasing ids: one ``searchsorted``,
+    as ``remove`` does).  KeyError for an id the loaded matrix does not hold."""
     ids = np.asarray(emb_ids if isinstance(emb_ids, np.ndarray) else list(emb_ids), dtype=np.int64).reshape(-1)
     arr = lookup.arr
     pos = np.searchsorted(arr, ids)
@@ -64,17 +101,55 @@ def search_within_held(idx, lookup: _Lookup, query_vec: np.ndarray, n: int, emb_
             bad |= arr[np.minimum(pos, len(arr) - 1)] != ids
         if bad.any():
             raise KeyError(int(ids[np.argmax(bad)]))
-    off = int(getattr(idx, "row_offset", 0))
-    res = idx.search_within(query_vec, n, pos + off)
-    arr = lookup.arr   # (an append during the search only extends it)
-    return [(score, int(arr[row - off])) for score, row in res]
+    return pos + int(getattr(idx, "row_offset", 0))
+
+
+def search_within_held(idx, lookup: _Lookup, query_vec: np.ndarray, n: int, emb_ids,
+                       hold: Optional[Callable[[], tuple]] = None) -> List[Tuple[float, int]]:
+    """Top-n among ``emb_ids`` on a held (index, lookup): ids -> rows through ``lookup.arr``, the filtered search,
+    rows -> ids.  KeyError for an id the loaded matrix does not hold.  ``hold``: where ``search_mapped`` gets a
+    fresh (index, lookup) when a compaction renumbered the rows meanwhile."""
+    def native(idx, lookup, *_):
+        return idx, idx.search_within(query_vec, n, _within_rows(idx, lookup, emb_ids))
+
+    def finish(res, arr):
+        used, rows = res
+        off = int(getattr(used, "row_offset", 0))
+        return [(score, int(arr[row - off])) for score, row in rows]
+
+    return search_mapped(hold if hold is not None else _no_hold, (idx, lookup), native, finish)
+
+
+def _no_hold():
+    raise RuntimeError("the rows of the embeddings matrix were renumbered during the search")
+
+
+def single_search(idx, co, query_vec: np.ndarray, n: int):
+    """One query on a held index: through the generation's coalescer when there is one (concurrent callers --
+    threads of a server, AsyncKB's executor threads -- share corpus passes)."""
+    return co.search(idx, query_vec, n) if co is not None else idx.search(query_vec, n)
+
+
+def ids_of_rows(res, arr: np.ndarray) -> List[Tuple[float, int]]:
+    return [(score, int(arr[row])) for score, row in res]
+
+
+def ids_of_batch(res, arr: np.ndarray) -> List[List[Tuple[float, int]]]:
+    scores, rows = res
+    ids = arr[rows]                                   # (one gather for the whole batch)
+    sc = scores.astype(np.float64)
+    return [list(zip(sc[i].tolist(), ids[i].tolist())) for i in range(len(scores))]
+
+
+def ids_of_pairs(res, arr: np.ndarray) -> List[Tuple[float, int, int]]:
+    return [(score, int(arr[i]), int(arr[j])) for score, i, j in res]
 
 
 class DeviceEmbeddingsMatrix:
     """Lazy cache of (DeviceIndex, emb_id_lookup); drop-in for
     ``svs.kb._EmbeddingsMatrix``."""
 
-    # rebuild from storage instead of tombstoning once this share of the rows is dead
+    # reclaim the dead rows (compaction in place, or a rebuild from storage) once this share of the rows is dead
     COMPACT_AT = 0.25
 
     def __init__(self, device: int = 0, builder: MatrixBuilder = _default_builder,
@@ -221,7 +296,10 @@ class DeviceEmbeddingsMatrix:
 
     def remove(self, emb_ids) -> bool:
         """Embeddings a ``bulk_del_docs`` just committed: their rows are tombstoned in
-        HBM (never returned again, other rows keep their indices)."""
+        HBM (never returned again, other rows keep their indices).  Once ``COMPACT_AT`` of the rows
+        are dead they are reclaimed: in place on the device when the index can (``compact``), no host
+        copy is kept and no ``attach()`` view has handed the lookup array out -- the index object stays,
+        nothing is read from storage -- and by a rebuild from storage otherwise."""
         ids = np.asarray(list(emb_ids), dtype=np.int64)
         rebuild = False
         with self._mu:
@@ -235,10 +313,25 @@ class DeviceEmbeddingsMatrix:
                 rebuild = True
             else:
                 self._n_dead += len(ids)
-                if self._n_dead > self.COMPACT_AT * len(lk.arr) or self.embeddings_matrix is not None:
-                    rebuild = True      # compaction (or a host copy would go stale): rebuild from storage
+                off = int(getattr(idx, "row_offset", 0))
+                if self.embeddings_matrix is not None:
+                    rebuild = True      # a host copy would go stale: rebuild from storage
+                elif self._n_dead <= self.COMPACT_AT * len(lk.arr):
+                    idx.mask_rows(pos + off)
+                elif self._view or not hasattr(idx, "compact"):
+                    rebuild = True      # compaction by a rebuild from storage
                 else:
-                    idx.mask_rows(pos + getattr(idx, "row_offset", 0))
+                    # searches that hold (idx, lk) read the flag AFTER their native call (search_mapped): set
+                    # before the first row moves, and lk.arr stays as it is
+                    lk.stale = True
+                    try:
+                        idx.mask_rows(pos + off)
+                        old_rows = idx.compact()
+                        self._lookup = _Lookup(lk.arr[np.asarray(old_rows, dtype=np.int64) - off])
+                        self._n_dead = 0
+                    except Exception:  # noqa: BLE001 -- e.g. a device error half way: the rows are in no defined order
+                        _LOG.exception("in-place compaction failed; the cached vectors will be re-built")
+                        rebuild = True
         if rebuild:
             self.invalidate()
             return False
@@ -272,45 +365,37 @@ class DeviceEmbeddingsMatrix:
     # -- the superheavy() body ---------------------------------------------
     def search(self, query_vec: np.ndarray, n: int) -> List[Tuple[float, int]]:
         """``superheavy()`` (src/svs/kb.py:1622-1627): [(score, emb_id)]."""
-        idx, lookup, co = self.hold_search()
+        held = self.hold_search()
         try:
-            # concurrent callers (threads of a server, AsyncKB's executor threads) share corpus passes
-            res = co.search(idx, query_vec, n) if co is not None else idx.search(query_vec, n)
-            arr = lookup.arr
-            return [(score, int(arr[row])) for score, row in res]
+            return search_mapped(self.hold_search, held, lambda idx, lookup, co: single_search(idx, co, query_vec, n), ids_of_rows)
         finally:
-            idx.release()
+            held[0].release()
 
     def search_within(self, query_vec: np.ndarray, n: int, emb_ids) -> List[Tuple[float, int]]:
         """``search`` restricted to the listed embedding ids: [(score, emb_id)] (``KB.retrieve_within``)."""
         idx, lookup = self.hold()
         try:
-            return search_within_held(idx, lookup, query_vec, n, emb_ids)
+            return search_within_held(idx, lookup, query_vec, n, emb_ids, self.hold)
         finally:
             idx.release()
 
     def search_many(self, query_vecs: np.ndarray, n: int) -> List[List[Tuple[float, int]]]:
         """Batched ``superheavy()``: one result list per row of ``query_vecs``;
         up to 16 (f32) / 32 (f16) queries share one pass over the corpus."""
-        idx, lookup = self.hold()
+        held = self.hold()
         try:
-            scores, rows = idx.search_batch(query_vecs, n)
-            arr = lookup.arr
-            ids = arr[rows]                                   # (one gather for the whole batch)
-            sc = scores.astype(np.float64)
-            return [list(zip(sc[i].tolist(), ids[i].tolist())) for i in range(len(scores))]
+            return search_mapped(self.hold, held, lambda idx, lookup: idx.search_batch(query_vecs, n), ids_of_batch)
         finally:
-            idx.release()
+            held[0].release()
 
     def top_pairs(self, n: int) -> List[Tuple[float, int, int]]:
         """``superheavy()`` of document_top_pairwise_scores (src/svs/kb.py:1650-1655):
         [(score, emb_id_1, emb_id_2)]."""
-        idx, lookup = self.hold()
+        held = self.hold()
         try:
-            res = idx.top_pairs(n)
-            return [(score, int(lookup.arr[i]), int(lookup.arr[j])) for score, i, j in res]
+            return search_mapped(self.hold, held, lambda idx, lookup: idx.top_pairs(n), ids_of_pairs)
         finally:
-            idx.release()
+            held[0].release()
 
     def hold(self) -> Tuple[Any, _Lookup]:
         """(index, lookup table) with the caller owning a reference to the index, so a
