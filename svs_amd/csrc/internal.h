@@ -40,6 +40,12 @@ int32_t svs_internal_host_phases(double* out, int32_t n);
  * launches after its own.  Up to cap entries (and at most 32) are written; returns the number of launches recorded.
  * Coalesced single-query passes and svs_multi_* launch from other threads: they are not in the caller's record. */
 int32_t svs_internal_last_launches(const char** kernels, int64_t* rows, int32_t* nq, int32_t cap);
+/* The kernel a single query takes on an index of dtype and dimension d under svs_index_set_variant(variant), screened
+ * (screen != 0: an f32 index that has a half shadow) or not: pure host code, no index and no device.  kernel[cap] gets
+ * the name as svs_internal_last_launches spells it, from the dispatch that launches it; *flags: bit 0 = the pass can serve
+ * other searches of a run-ahead pipeline, bit 1 = the kernel reads ld query floats, so the query is copied (zero padded)
+ * when the rows are padded beyond d. */
+int32_t svs_internal_single_route(int32_t dtype, int32_t d, int32_t variant, int32_t screen, char* kernel, int32_t cap, int32_t* flags);
 /* Screened search (screen.h) on this handle, up to cap (<= 9) values: [0] queries answered from the candidate list,
  * [1] queries that took the exact whole-corpus fallback (both as the kernels last wrote them to pinned memory: drain
  * the stream first), [2] shadow: 0 none, 1 valid, 2 invalid for good (an element half cannot hold), [3] 1 = screening

@@ -107,7 +107,7 @@ thread_local double g_host_phase[6];          // svs_internal_host_phases: secon
 
 // svs_internal_last_launches: the score kernels the calling thread's last search / scores call enqueued, in order: every
 // batched launch, and for the single-query kernels a "gemv" entry per loop (launch_scores_any, svs_index_scores_n)
-// followed by the kernel of each query (launch_scores).  Fixed thread-local slots and names that are compile-time
+// followed by the kernel of each query (launch_single).  Fixed thread-local slots and names that are compile-time
 // constants: recording is a few stores, no allocation, no lock; entries past LAUNCH_REC_CAP are dropped.
 struct LaunchRec {
   const char* kernel;
@@ -156,31 +156,27 @@ constexpr KernelName kernel_name(const char* base, A... args) {
   return k;
 }
 
-// The completion event of a score half, carried by its LAST kernel instead of a record behind it (run-ahead pipeline:
-// no packet between consecutive passes).  enqueue_score_half arms the calling thread's slot in front of that launch;
-// the single-query launchers and the tombstone mask launch through launch_tail, which hands an armed event to the
-// extended launch as its stop event.  tail_take() disarms and says whether a launch took it: a route that never
-// came by (or an event nobody armed) leaves the caller to record the event as before.
-struct TailEvent {
-  hipEvent_t stop = nullptr;
-  bool bound = false;
+// What a single-query score launch is given besides its operands: enqueue_score_half -> launch_scores -> the launcher.
+struct PassOpts {
+  hipEvent_t stop = nullptr;       // the completion event of the score half, when this is its LAST kernel (launch_tail)
+  const PassPlan* plan = nullptr;  // f16 one-shot kernel of a geometry that shares: the plan the pass serves (pass_share.h),
+  int limit = 0;                   // ... the most queries it may hold (the launch's dynamic LDS),
+  bool thin = false;               // ... and the pass on one resident set of workgroups instead of the one-shot grid
+  const char** name = nullptr;     // svs_internal_single_route: launch nothing, store the kernel's name here
 };
-thread_local TailEvent g_tail;
-
-inline void tail_arm(hipEvent_t stop) { g_tail = TailEvent{stop, false}; }
-inline bool tail_take() {
-  const bool bound = g_tail.bound;
-  g_tail = TailEvent{};
-  return bound;
-}
+// stop: the completion event of a score half, carried by this launch (an extended launch) instead of a record behind it
 template <class... P, class... A>
-inline void launch_tail(void (*kernel)(P...), dim3 grid, dim3 block, unsigned lds, hipStream_t st, A&&... args) {
-  if (hipEvent_t stop = g_tail.stop) {
-    g_tail = TailEvent{nullptr, true};
-    hipExtLaunchKernelGGL<P...>(kernel, grid, block, lds, st, nullptr, stop, 0, static_cast<P>(args)...);
-  } else {
-    hipLaunchKernelGGL(kernel, grid, block, lds, st, static_cast<P>(args)...);
-  }
+inline void launch_tail(hipEvent_t stop, void (*kernel)(P...), dim3 grid, dim3 block, unsigned lds, hipStream_t st, A&&... args) {
+  if (stop) hipExtLaunchKernelGGL<P...>(kernel, grid, block, lds, st, nullptr, stop, 0, static_cast<P>(args)...);
+  else hipLaunchKernelGGL(kernel, grid, block, lds, st, static_cast<P>(args)...);
+}
+// Every single-query score launch: recorded and launched, or (o.name) named only
+template <class... P, class... A>
+inline void launch_single(const PassOpts& o, const char* name, int64_t rows, void (*kernel)(P...), dim3 grid, dim3 block, unsigned lds,
+                          hipStream_t st, A&&... args) {
+  if (o.name) { *o.name = name; return; }
+  launch_record(name, rows, 1);
+  launch_tail(o.stop, kernel, grid, block, lds, st, static_cast<A&&>(args)...);
 }
 
 struct EvTriple {
@@ -589,7 +585,7 @@ constexpr int query_tile(int nq) { return nq <= 32 ? 32 : (nq <= 64 ? 64 : (nq <
 //   3     launch_rows           one-shot, 2 rows x 16 waves
 //         launch_scores_q16     f32: gemm_f32_q16_kernel (16x16x4 MFMA, half-line loads) for gemm_q16r_kernel
 //   4     launch_rows           one-shot, 1 row x 16 waves, temporal loads
-//         launch_scores         no gemv_unrolled kernels, any dtype: the generic kernels take those rows
+//         single_route          no gemv_unrolled kernels, any dtype: the generic kernels take those rows
 //         launch_scores_q16     2048 rows per workgroup (default 1024)
 //         launch_scores_tiled   f32: 32-query tiles whatever nq
 //         launch_tiled_eb       f16 / fp8: no 128-query phased kernel; 128-row tiles (BM = TG_BM) at 128 / 256 queries per tile
@@ -624,69 +620,60 @@ enum Variant : int {
 
 // ---- score stage launch -----------------------------------------------------
 template <int NSTEP, int R, int WPB, bool NT>
-void launch_oneshot(const svs_index* idx, const float* q, float* scores, hipStream_t st) {
+void launch_oneshot(const svs_index* idx, const float* q, float* scores, hipStream_t st, const PassOpts& o) {
   const int64_t rows_per_block = (int64_t)R * WPB;
   const int64_t blocks = (idx->n + rows_per_block - 1) / rows_per_block;
   static constexpr KernelName name = kernel_name("gemv_f32_oneshot_kernel", NSTEP, R, WPB, NT, false, false);
-  launch_record(name.s, idx->n, 1);
-  launch_tail(gemv_f32_oneshot_kernel<NSTEP, R, WPB, NT, false>, dim3((unsigned)blocks), dim3(WPB * 64), 0, st,
-              (const v4f*)idx->rows, (const v4f*)q, scores, idx->n);
+  launch_single(o, name.s, idx->n, gemv_f32_oneshot_kernel<NSTEP, R, WPB, NT, false>, dim3((unsigned)blocks), dim3(WPB * 64), 0, st,
+                (const v4f*)idx->rows, (const v4f*)q, scores, idx->n);
 }
 
 template <int NSTEP, int R, bool NT>
-void launch_persistent(const svs_index* idx, const float* q, float* scores, hipStream_t st) {
+void launch_persistent(const svs_index* idx, const float* q, float* scores, hipStream_t st, const PassOpts& o) {
   constexpr int WPB = 4;
   const int64_t tiles = (idx->n + R - 1) / R;
   const int blocks = (int)std::min<int64_t>((tiles + WPB - 1) / WPB, (int64_t)idx->cu_count * 4);
   static constexpr KernelName name = kernel_name("gemv_f32_rows_kernel", NSTEP, R, WPB, NT, false);
-  launch_record(name.s, idx->n, 1);
-  launch_tail(gemv_f32_rows_kernel<NSTEP, R, WPB, NT, false>, dim3(blocks), dim3(WPB * 64), 0, st,
-              (const v4f*)idx->rows, (const v4f*)q, scores, idx->n);
+  launch_single(o, name.s, idx->n, gemv_f32_rows_kernel<NSTEP, R, WPB, NT, false>, dim3(blocks), dim3(WPB * 64), 0, st,
+                (const v4f*)idx->rows, (const v4f*)q, scores, idx->n);
 }
 
 // Default geometry per row length (measured at NSTEP = 6: one-shot, 16-wave
 // workgroups, one row per wave, nontemporal loads: 7.2 TB/s on MI355X).
 // Short rows take several rows per wave so a wave still has >= 4 KiB in flight.
 template <int NSTEP>
-void launch_rows(const svs_index* idx, const float* q, float* scores, hipStream_t st, int variant) {
+void launch_rows(const svs_index* idx, const float* q, float* scores, hipStream_t st, int variant, const PassOpts& o) {
   switch (variant) {
-    case VARIANT_GEMV_PERSISTENT_R1: launch_persistent<NSTEP, 1, false>(idx, q, scores, st); return;
-    case VARIANT_GEMV_PERSISTENT_R2: launch_persistent<NSTEP, 2, true>(idx, q, scores, st); return;
-    case VARIANT_GEMV_2X16: launch_oneshot<NSTEP, 2, 16, true>(idx, q, scores, st); return;
-    case VARIANT_ALT_GEOMETRY: launch_oneshot<NSTEP, 1, 16, false>(idx, q, scores, st); return;
-    case VARIANT_GEMV_1X8: launch_oneshot<NSTEP, 1, 8, true>(idx, q, scores, st); return;
+    case VARIANT_GEMV_PERSISTENT_R1: launch_persistent<NSTEP, 1, false>(idx, q, scores, st, o); return;
+    case VARIANT_GEMV_PERSISTENT_R2: launch_persistent<NSTEP, 2, true>(idx, q, scores, st, o); return;
+    case VARIANT_GEMV_2X16: launch_oneshot<NSTEP, 2, 16, true>(idx, q, scores, st, o); return;
+    case VARIANT_ALT_GEOMETRY: launch_oneshot<NSTEP, 1, 16, false>(idx, q, scores, st, o); return;
+    case VARIANT_GEMV_1X8: launch_oneshot<NSTEP, 1, 8, true>(idx, q, scores, st, o); return;
     default: break;
   }
-  if constexpr (NSTEP <= 2) launch_oneshot<NSTEP, 4, 16, true>(idx, q, scores, st);
-  else if constexpr (NSTEP <= 4) launch_oneshot<NSTEP, 2, 16, true>(idx, q, scores, st);
-  else if constexpr (NSTEP <= 6) launch_oneshot<NSTEP, 1, 16, true>(idx, q, scores, st);
-  else launch_oneshot<NSTEP, 1, 8, true>(idx, q, scores, st);
+  if constexpr (NSTEP <= 2) launch_oneshot<NSTEP, 4, 16, true>(idx, q, scores, st, o);
+  else if constexpr (NSTEP <= 4) launch_oneshot<NSTEP, 2, 16, true>(idx, q, scores, st, o);
+  else if constexpr (NSTEP <= 6) launch_oneshot<NSTEP, 1, 16, true>(idx, q, scores, st, o);
+  else launch_oneshot<NSTEP, 1, 8, true>(idx, q, scores, st, o);
+}
+
+// The grid of the loop kernels: T lanes per row, four waves per workgroup, at most eight workgroups per CU
+template <int T>
+int loop_blocks(const svs_index* idx) {
+  return (int)std::min<int64_t>(((idx->n + 64 / T - 1) / (64 / T) + 3) / 4, (int64_t)idx->cu_count * 8);
 }
 
 template <int T>
-void launch_generic(const svs_index* idx, const float* q, float* scores, hipStream_t st) {
-  constexpr int RPW = 64 / T;
-  int64_t waves = (idx->n + RPW - 1) / RPW;
-  int blocks = (int)std::min<int64_t>((waves + 3) / 4, (int64_t)idx->cu_count * 8);
+void launch_generic(const svs_index* idx, const float* q, float* scores, hipStream_t st, const PassOpts& o) {
   static constexpr KernelName name = kernel_name("gemv_f32_generic_kernel", T);
-  launch_record(name.s, idx->n, 1);
-  launch_tail(gemv_f32_generic_kernel<T>, dim3(blocks), dim3(256), 0, st,
-              (const v4f*)idx->rows, q, scores, idx->n, idx->d, idx->ld / 4);
+  launch_single(o, name.s, idx->n, gemv_f32_generic_kernel<T>, dim3(loop_blocks<T>(idx)), dim3(256), 0, st,
+                (const v4f*)idx->rows, q, scores, idx->n, idx->d, idx->ld / 4);
 }
 
 constexpr int f16_rows_r(int nstep) { return nstep <= 1 ? 4 : (nstep <= 3 ? 2 : 1); }
 constexpr int f16_rows_wpb(int nstep) { return nstep <= 6 ? 16 : 8; }
 template <int NSTEP>
 constexpr KernelName kF16OneshotName = kernel_name("gemv_f16_oneshot_kernel", NSTEP, f16_rows_r(NSTEP), f16_rows_wpb(NSTEP));
-// half_rows: the index's own rows (an f16 index) or the half shadow of an f32 index (screened search)
-// The plan the next f16 one-shot launch of this thread is to serve (enqueue_score_half sets and clears it around the
-// score launch of a shareable pipeline search) and the most queries it may hold; no plan: the launch's own q and scores.
-struct PassLaunch {
-  const PassPlan* plan = nullptr;
-  int limit = 0;
-  bool thin = false;   // on one resident set of workgroups instead of the one-shot grid (the host expects c == 0)
-};
-thread_local PassLaunch g_pass;
 // dynamic LDS of a launch under a plan: the plan's queries as halves (gemv_f16.h), at most 4 x 3584 x 2 = 28 KB
 inline unsigned plan_lds_bytes(int limit, int ld) { return (unsigned)limit * (unsigned)ld * 2u; }
 // The thin grid of an instantiation: as many workgroups as the device holds at once (with the LDS of a full plan).
@@ -706,42 +693,40 @@ int thin_grid_rows_f16(const svs_index* idx) {
   }
   return idx->cu_count * v;
 }
-// ... of the index's shareable passes (0: its row length does not share)
-int thin_grid_of(const svs_index* idx) {
-  if (idx->ld % 512 != 0) return 0;
-  switch (idx->ld / 512) {
-    case 1: return thin_grid_rows_f16<1>(idx);
-    case 2: return thin_grid_rows_f16<2>(idx);
-    case 3: return thin_grid_rows_f16<3>(idx);
-    case 4: return thin_grid_rows_f16<4>(idx);
-    case 5: return thin_grid_rows_f16<5>(idx);
-    case 6: return thin_grid_rows_f16<6>(idx);
-    case 7: return thin_grid_rows_f16<7>(idx);
-    default: return 0;
+// f(Int<NSTEP>) for the f16 one-shot kernel of rows of nstep x 512 halves; false: it has none
+template <class F>
+bool for_f16_oneshot(int nstep, F&& f) {
+  switch (nstep) {
+#define SVS_ROWS_CASE(N) case N: f(Int<N>{}); return true;
+    SVS_ROWS_CASE(1) SVS_ROWS_CASE(2) SVS_ROWS_CASE(3) SVS_ROWS_CASE(4) SVS_ROWS_CASE(5) SVS_ROWS_CASE(6) SVS_ROWS_CASE(7) SVS_ROWS_CASE(8)
+#undef SVS_ROWS_CASE
+    default: return false;
   }
 }
+// ... of the index's shareable passes (0: its row length does not share)
+int thin_grid_of(const svs_index* idx) {
+  int grid = 0;
+  if (idx->ld % 512 == 0) for_f16_oneshot(idx->ld / 512, [&](auto ns) { if constexpr (f16_rows_share(ns())) grid = thin_grid_rows_f16<ns()>(idx); });
+  return grid;
+}
+// half_rows: half_rows_of the route; o.plan: the plan the launch serves (a geometry that shares), else its own q and scores
 template <int NSTEP>
-void launch_rows_f16(const svs_index* idx, const void* half_rows, const float* q, float* scores, hipStream_t st) {
+void launch_rows_f16(const svs_index* idx, const void* half_rows, const float* q, float* scores, hipStream_t st, const PassOpts& o) {
   constexpr int R = f16_rows_r(NSTEP), WPB = f16_rows_wpb(NSTEP);
   const int64_t rows_per_block = (int64_t)R * WPB;
   int64_t blocks = (idx->n + rows_per_block - 1) / rows_per_block;
-  const PassLaunch pl = f16_rows_share(NSTEP) ? g_pass : PassLaunch{};
+  const PassPlan* plan = f16_rows_share(NSTEP) ? o.plan : nullptr;
   if constexpr (f16_rows_share(NSTEP))
-    if (pl.plan && pl.thin) blocks = std::min<int64_t>(blocks, thin_grid_rows_f16<NSTEP>(idx));
-  launch_record(kF16OneshotName<NSTEP>.s, idx->n, 1);
-  launch_tail(gemv_f16_oneshot_kernel<NSTEP, R, WPB>, dim3((unsigned)blocks), dim3(WPB * 64), pl.plan ? plan_lds_bytes(pl.limit, NSTEP * 512) : 0u, st,
-              (const u32x4*)half_rows, (const v4f*)q, scores, idx->n, pl.plan);
+    if (plan && o.thin) blocks = std::min<int64_t>(blocks, thin_grid_rows_f16<NSTEP>(idx));
+  launch_single(o, kF16OneshotName<NSTEP>.s, idx->n, gemv_f16_oneshot_kernel<NSTEP, R, WPB>, dim3((unsigned)blocks), dim3(WPB * 64),
+                plan ? plan_lds_bytes(o.limit, NSTEP * 512) : 0u, st, (const u32x4*)half_rows, (const v4f*)q, scores, idx->n, plan);
 }
 
 template <int T>
-void launch_generic_f16(const svs_index* idx, const _Float16* qh, float* scores, hipStream_t st) {
-  constexpr int RPW = 64 / T;
-  int64_t waves = (idx->n + RPW - 1) / RPW;
-  int blocks = (int)std::min<int64_t>((waves + 3) / 4, (int64_t)idx->cu_count * 8);
+void launch_generic_f16(const svs_index* idx, const _Float16* qh, float* scores, hipStream_t st, const PassOpts& o) {
   static constexpr KernelName name = kernel_name("gemv_f16_generic_kernel", T);
-  launch_record(name.s, idx->n, 1);
-  launch_tail(gemv_f16_generic_kernel<T>, dim3(blocks), dim3(256), 0, st, (const u32x4*)idx->rows,
-              (const u32x4*)qh, scores, idx->n, idx->ld / 8);
+  launch_single(o, name.s, idx->n, gemv_f16_generic_kernel<T>, dim3(loop_blocks<T>(idx)), dim3(256), 0, st, (const u32x4*)idx->rows,
+                (const u32x4*)qh, scores, idx->n, idx->ld / 8);
 }
 
 // rounds nq f32 queries to half into c->qh ([rows_alloc][ld], rows >= nq zero)
@@ -775,14 +760,31 @@ int stage_queries_fp8(const svs_index* idx, Ctx* c, const float* q, int nq, int 
 }
 
 template <int T>
-void launch_gemv_fp8(const svs_index* idx, Ctx* c, float* scores, hipStream_t st) {
-  constexpr int RPW = 64 / T;
-  int64_t waves = (idx->n + RPW - 1) / RPW;
-  int blocks = (int)std::min<int64_t>((waves + 3) / 4, (int64_t)idx->cu_count * 8);
+void launch_gemv_fp8(const svs_index* idx, const Ctx* c, float* scores, hipStream_t st, const PassOpts& o) {
   static constexpr KernelName name = kernel_name("gemv_fp8_kernel", T);
-  launch_record(name.s, idx->n, 1);
-  launch_tail(gemv_fp8_kernel<T>, dim3(blocks), dim3(256), 0, st, (const u32x4_t*)idx->rows, idx->row_scales,
-              (const v4f*)c->q8f.p, c->q8s.p, scores, idx->n, idx->ld / 16);
+  launch_single(o, name.s, idx->n, gemv_fp8_kernel<T>, dim3(loop_blocks<T>(idx)), dim3(256), 0, st, (const u32x4_t*)idx->rows, idx->row_scales,
+                (const v4f*)c->q8f.p, c->q8s.p, scores, idx->n, idx->ld / 16);
+}
+
+// f(Int<NSTEP>, Int<LB>, Int<R>) for the hot row lengths (bytes): one-shot grid, 16 waves, nontemporal row loads.  The
+// query stays packed, so several short rows per wave cost no registers (58-66 VGPRs).  false: not one of them
+template <class F>
+bool for_fp8_oneshot(int ld, F&& f) {
+  switch (ld) {
+    case 1024: f(Int<1>{}, Int<16>{}, Int<4>{}); return true;   // >= 4 KiB per wave: 6.5 vs 4.2 TB/s with one row per wave
+    case 2048: f(Int<2>{}, Int<16>{}, Int<2>{}); return true;   // 6.5 vs 5.8
+    case 3072: f(Int<3>{}, Int<16>{}, Int<1>{}); return true;
+    case 4096: f(Int<4>{}, Int<16>{}, Int<1>{}); return true;
+    case 512: f(Int<1>{}, Int<8>{}, Int<4>{}); return true;     // 8-byte loads: several rows per wave keep enough bytes in flight
+    case 1536: f(Int<3>{}, Int<8>{}, Int<2>{}); return true;
+    default: return false;
+  }
+}
+template <int NSTEP, int LB, int R>
+void launch_oneshot_fp8(const svs_index* idx, const Ctx* c, float* scores, hipStream_t st, const PassOpts& o) {
+  static constexpr KernelName name = kernel_name("gemv_fp8_oneshot_kernel", NSTEP, LB, R, 16);
+  launch_single(o, name.s, idx->n, gemv_fp8_oneshot_kernel<NSTEP, LB, R, 16>, dim3((unsigned)((idx->n + R * 16 - 1) / (R * 16))), dim3(16 * 64), 0, st,
+                (const uint8_t*)idx->rows, idx->row_scales, (const uint8_t*)c->q8.p, c->q8s.p, scores, idx->n);
 }
 
 // The Dot argument of gemv_unrolled_kernel as c++filt prints it
@@ -793,7 +795,7 @@ template <> constexpr const char* kDotName<DotFp8> = "svs::DotFp8";
 
 // Rows that are not whole 1 KiB wave loads (gemv_unrolled.h); false: longer than 16 KiB
 template <class Dot>
-bool launch_unrolled(const svs_index* idx, const void* q_staged, int ld16, float* scores, hipStream_t st, Dot dot) {
+bool launch_unrolled(const svs_index* idx, const void* q_staged, int ld16, float* scores, hipStream_t st, Dot dot, const PassOpts& o) {
   const u32x4* M = (const u32x4*)idx->rows;
   const u32x4* q = (const u32x4*)q_staged;
   return for_row_geometry(ld16, [&](auto t, auto nc) {
@@ -801,15 +803,73 @@ bool launch_unrolled(const svs_index* idx, const void* q_staged, int ld16, float
     const int64_t groups = (idx->n + (64 / T) * U - 1) / ((64 / T) * U);
     const int64_t blocks = (groups + UNR_WPB - 1) / UNR_WPB;
     static constexpr KernelName name = kernel_name("gemv_unrolled_kernel", T, NC, U, kDotName<Dot>);
-    launch_record(name.s, idx->n, 1);
-    launch_tail(gemv_unrolled_kernel<T, NC, U, Dot>, dim3((unsigned)blocks), dim3(UNR_WPB * 64), 0, st, M, q, scores, idx->n, ld16, dot);
+    launch_single(o, name.s, idx->n, gemv_unrolled_kernel<T, NC, U, Dot>, dim3((unsigned)blocks), dim3(UNR_WPB * 64), 0, st, M, q, scores, idx->n, ld16, dot);
   });
 }
 
-// The query as the single-query kernels read it: ld floats, 16-byte aligned (rows padded beyond d: zero padded)
+// ---- the route of a single query: decided once (single_route), then staged and launched from that value ----------
+struct SingleRoute {
+  enum Family : uint8_t { F32_ROWS, F32_UNROLLED, F32_GENERIC, F16_ONESHOT, F16_UNROLLED, F16_GENERIC, FP8_ONESHOT, FP8_UNROLLED, FP8_GENERIC } family;
+  // the query as the kernel reads it: the caller's d floats; ld floats, 16-byte aligned (the caller's, or pad_query's
+  // zero-padded copy in Ctx::q16); halves in Ctx::qh; e4m3 in Ctx::q8 with its scale in q8s and the values as f32 in q8f
+  enum Query : uint8_t { AS_GIVEN, PADDED, HALF, FP8 } query;
+  bool shadow;   // the rows it reads: idx->shadow (a screened f32 index takes F16_ONESHOT over it), else idx->rows
+  bool shares;   // its pass can serve other searches of a run-ahead pipeline (pass_share.h)
+  int geo;       // template geometry: NSTEP of the one-shot / persistent kernels, else 16-byte chunks per row
+  int variant;   // svs_index_set_variant when the route was taken (F32_ROWS, launch_rows: one-shot or persistent grid, R x WPB, loads)
+};
+
+// variant: idx->variant, loaded ONCE by whoever plans the search; screen: the search runs over the half shadow
+SingleRoute single_route(const svs_index* idx, int variant, bool screen) {
+  using R = SingleRoute;
+  const int ld = idx->ld;
+  const auto none = [](auto...) {};
+  // other rows of up to 16 KiB: gemv_unrolled.h (f32: the query in 16-byte chunks of the padded row); else the loop kernels
+  const auto unrolled = [&](int ld16) { return variant != VARIANT_ALT_GEOMETRY && for_row_geometry(ld16, none); };
+  if (idx->dtype == SVS_DTYPE_FP8)
+    return R{for_fp8_oneshot(ld, none) ? R::FP8_ONESHOT : (unrolled(ld / 16) ? R::FP8_UNROLLED : R::FP8_GENERIC), R::FP8, false, false, ld / 16, variant};
+  if (screen || (idx->dtype == SVS_DTYPE_F16 && ld % 512 == 0 && ld <= 4096))   // (the kernel rounds ld query floats itself)
+    return R{R::F16_ONESHOT, R::PADDED, screen, f16_rows_share(ld / 512), ld / 512, variant};
+  if (idx->dtype == SVS_DTYPE_F16) return R{unrolled(ld / 8) ? R::F16_UNROLLED : R::F16_GENERIC, R::HALF, false, false, ld / 8, variant};
+  if (ld % 256 == 0 && ld <= 4096) return R{R::F32_ROWS, R::PADDED, false, false, ld / 256, variant};   // (the kernel reads ld query floats)
+  return unrolled(ld / 4) ? R{R::F32_UNROLLED, R::PADDED, false, false, ld / 4, variant} : R{R::F32_GENERIC, R::AS_GIVEN, false, false, ld / 4, variant};
+}
+
+// The rows a route's pass reads: the half shadow (screened f32 index) or the index's own
+inline const void* half_rows_of(const svs_index* idx, const SingleRoute& r) { return r.shadow ? idx->shadow : idx->rows; }
+
+// The route's kernel over q, the query staged as r.query says (FP8: in the context).  o.name: the kernel is named, not launched.
+int launch_route(const svs_index* idx, const Ctx* c, const SingleRoute& r, const void* q, float* scores, hipStream_t st, const PassOpts& o) {
+  bool ok = true;
+  switch (r.family) {
+    case SingleRoute::FP8_ONESHOT: ok = for_fp8_oneshot(idx->ld, [&](auto ns, auto lb, auto rr) { launch_oneshot_fp8<ns(), lb(), rr()>(idx, c, scores, st, o); }); break;
+    case SingleRoute::FP8_UNROLLED: ok = launch_unrolled(idx, q, r.geo, scores, st, DotFp8{idx->row_scales, c->q8s}, o); break;
+    case SingleRoute::FP8_GENERIC: for_width(r.geo, [&](auto t) { launch_gemv_fp8<t()>(idx, c, scores, st, o); }); break;
+    case SingleRoute::F16_ONESHOT: ok = for_f16_oneshot(r.geo, [&](auto ns) { launch_rows_f16<ns()>(idx, half_rows_of(idx, r), (const float*)q, scores, st, o); }); break;
+    case SingleRoute::F16_UNROLLED: ok = launch_unrolled(idx, q, r.geo, scores, st, DotF16{}, o); break;
+    case SingleRoute::F16_GENERIC: for_width(r.geo, [&](auto t) { launch_generic_f16<t()>(idx, (const _Float16*)q, scores, st, o); }); break;
+    case SingleRoute::F32_ROWS:
+      switch (r.geo) {
+#define SVS_ROWS_CASE(N) case N: launch_rows<N>(idx, (const float*)q, scores, st, r.variant, o); break;
+        SVS_ROWS_CASE(1) SVS_ROWS_CASE(2) SVS_ROWS_CASE(3) SVS_ROWS_CASE(4) SVS_ROWS_CASE(5) SVS_ROWS_CASE(6)
+        SVS_ROWS_CASE(7) SVS_ROWS_CASE(8) SVS_ROWS_CASE(9) SVS_ROWS_CASE(10) SVS_ROWS_CASE(11) SVS_ROWS_CASE(12)
+        SVS_ROWS_CASE(13) SVS_ROWS_CASE(14) SVS_ROWS_CASE(15) SVS_ROWS_CASE(16)
+#undef SVS_ROWS_CASE
+        default: ok = false;
+      }
+      break;
+    case SingleRoute::F32_UNROLLED: ok = launch_unrolled(idx, q, r.geo, scores, st, DotF32{}, o); break;
+    case SingleRoute::F32_GENERIC: for_width(r.geo, [&](auto t) { launch_generic<t()>(idx, (const float*)q, scores, st, o); }); break;
+  }
+  return ok ? SVS_OK : fail(SVS_ERR_INVALID, "internal: no single-query kernel for ld %d", idx->ld);
+}
+
+// The query as the single-query kernels read it: ld floats, 16-byte aligned.  Copied (zero padded) when the rows are
+// padded beyond d or the pointer is not aligned
+inline bool query_needs_copy(const svs_index* idx, const float* q) { return idx->ld != idx->d || (((uintptr_t)q) & 15) != 0; }
 int pad_query(const svs_index* idx, Ctx* c, const float* q, const float** out, hipStream_t st) {
   *out = q;
-  if (idx->ld == idx->d && (((uintptr_t)q) & 15) == 0) return SVS_OK;
+  if (!query_needs_copy(idx, q)) return SVS_OK;
   int rc = c->q16.grow((size_t)GQ * idx->ld);
   if (rc != SVS_OK) return rc;
   HIP_TRY(hipMemsetAsync(c->q16, 0, (size_t)idx->ld * sizeof(float), st));
@@ -818,84 +878,17 @@ int pad_query(const svs_index* idx, Ctx* c, const float* q, const float** out, h
   return SVS_OK;
 }
 
-// q: device, d floats (unpadded); scores: device, n floats
-int launch_scores(const svs_index* idx, Ctx* c, const float* q, float* scores, hipStream_t st) {
-  const int variant = idx->variant.load();
-  if (idx->dtype == SVS_DTYPE_FP8) {
-    int rc = stage_queries_fp8(idx, c, q, 1, 1, true, st);
-    if (rc != SVS_OK) return rc;
-    // hot geometries: one-shot grid, 16 waves, nontemporal row loads (as gemv_f32.h)
-#define SVS_FP8_HOT(NSTEP, LB, R)                                                                               \
-  do {                                                                                                          \
-    const int64_t blocks = (idx->n + (R) * 16 - 1) / ((R) * 16);                                                \
-    static constexpr KernelName name = kernel_name("gemv_fp8_oneshot_kernel", NSTEP, LB, R, 16);                \
-    launch_record(name.s, idx->n, 1);                                                                           \
-    launch_tail(gemv_fp8_oneshot_kernel<NSTEP, LB, R, 16>, dim3((unsigned)blocks), dim3(16 * 64), 0, st,          \
-                (const uint8_t*)idx->rows, idx->row_scales, (const uint8_t*)c->q8, c->q8s.p, scores, idx->n);       \
-    return SVS_OK;                                                                                              \
-  } while (0)
-    switch (idx->ld) {
-      // the query stays packed (converted next to the row bytes), so several short rows per
-      // wave cost no registers (58-66 VGPRs)
-      case 1024: SVS_FP8_HOT(1, 16, 4);   // >= 4 KiB per wave: 6.5 vs 4.2 TB/s with one row per wave
-      case 2048: SVS_FP8_HOT(2, 16, 2);   // 6.5 vs 5.8
-      case 3072: SVS_FP8_HOT(3, 16, 1);
-      case 4096: SVS_FP8_HOT(4, 16, 1);
-      case 512: SVS_FP8_HOT(1, 8, 4);    // 8-byte loads: several rows per wave keep enough bytes in flight
-      case 1536: SVS_FP8_HOT(3, 8, 2);
-      default: break;
-    }
-#undef SVS_FP8_HOT
-    const int ld16 = idx->ld / 16;
-    if (variant != VARIANT_ALT_GEOMETRY && launch_unrolled(idx, c->q8, ld16, scores, st, DotFp8{idx->row_scales, c->q8s})) return SVS_OK;
-    for_width(ld16, [&](auto t) { launch_gemv_fp8<t()>(idx, c, scores, st); });
-    return SVS_OK;
-  }
-  if (idx->dtype == SVS_DTYPE_F16) {
-    if (idx->ld % 512 == 0 && idx->ld <= 4096) {
-      const float* qq = nullptr;   // the kernel rounds ld query floats itself: pad them when rows are padded
-      int rc = pad_query(idx, c, q, &qq, st);
-      if (rc != SVS_OK) return rc;
-      switch (idx->ld / 512) {
-#define SVS_ROWS_CASE(N) case N: launch_rows_f16<N>(idx, idx->rows, qq, scores, st); return SVS_OK;
-        SVS_ROWS_CASE(1) SVS_ROWS_CASE(2) SVS_ROWS_CASE(3) SVS_ROWS_CASE(4) SVS_ROWS_CASE(5) SVS_ROWS_CASE(6)
-        SVS_ROWS_CASE(7) SVS_ROWS_CASE(8)
-#undef SVS_ROWS_CASE
-        default: break;
-      }
-    }
-    int rc = stage_queries_f16(idx, c, q, 1, 1, st);
-    if (rc != SVS_OK) return rc;
-    const int ld8 = idx->ld / 8;
-    if (variant != VARIANT_ALT_GEOMETRY && launch_unrolled(idx, c->qh, ld8, scores, st, DotF16{})) return SVS_OK;
-    for_width(ld8, [&](auto t) { launch_generic_f16<t()>(idx, c->qh, scores, st); });
-    return SVS_OK;
-  }
-  if (idx->ld % 256 == 0 && idx->ld <= 4096) {
-    // rows padded beyond d (choose_ld): the kernel reads ld query floats, so pad the query too
-    const float* qq = nullptr;
-    int rc = pad_query(idx, c, q, &qq, st);
-    if (rc != SVS_OK) return rc;
-    switch (idx->ld / 256) {
-#define SVS_ROWS_CASE(N) case N: launch_rows<N>(idx, qq, scores, st, variant); return SVS_OK;
-      SVS_ROWS_CASE(1) SVS_ROWS_CASE(2) SVS_ROWS_CASE(3) SVS_ROWS_CASE(4) SVS_ROWS_CASE(5) SVS_ROWS_CASE(6)
-      SVS_ROWS_CASE(7) SVS_ROWS_CASE(8) SVS_ROWS_CASE(9) SVS_ROWS_CASE(10) SVS_ROWS_CASE(11) SVS_ROWS_CASE(12)
-      SVS_ROWS_CASE(13) SVS_ROWS_CASE(14) SVS_ROWS_CASE(15) SVS_ROWS_CASE(16)
-#undef SVS_ROWS_CASE
-      default: break;
-    }
-  }
-  const int ld4 = idx->ld / 4;
-  if (variant != VARIANT_ALT_GEOMETRY && ld4 <= 1024) {
-    // rows of up to 16 KiB that are not whole wave loads (gemv_unrolled.h): the query is read in
-    // 16-byte chunks of the padded row, so it is padded (and aligned) the same way
-    const float* qq = nullptr;
-    int rc = pad_query(idx, c, q, &qq, st);
-    if (rc != SVS_OK) return rc;
-    if (launch_unrolled(idx, qq, ld4, scores, st, DotF32{})) return SVS_OK;
-  }
-  for_width(ld4, [&](auto t) { launch_generic<t()>(idx, q, scores, st); });
-  return SVS_OK;
+// One query through its route.  q: device, d floats; scores: n floats; q_padded (may be null): the query a PADDED route read
+int launch_scores(const svs_index* idx, Ctx* c, const SingleRoute& r, const float* q, float* scores, hipStream_t st,
+                  const PassOpts& o = {}, const float** q_padded = nullptr) {
+  const float* qq = q;
+  const int rc = r.query == SingleRoute::PADDED ? pad_query(idx, c, q, &qq, st)
+                 : r.query == SingleRoute::HALF ? stage_queries_f16(idx, c, q, 1, 1, st)
+                 : r.query == SingleRoute::FP8  ? stage_queries_fp8(idx, c, q, 1, 1, true, st) : SVS_OK;
+  if (rc != SVS_OK) return rc;
+  if (q_padded) *q_padded = qq;
+  const void* staged = r.query == SingleRoute::HALF ? (const void*)c->qh.p : (r.query == SingleRoute::FP8 ? (const void*)c->q8.p : (const void*)qq);
+  return launch_route(idx, c, r, staged, scores, st, o);
 }
 
 // ---- up to 16 queries per corpus pass (gemm_q16.h) ---------------------------
@@ -1125,16 +1118,24 @@ int launch_scores_tiled(const svs_index* idx, Ctx* c, const float* q_dev, int64_
                                      : launch_tiled_eb<1>(idx, c, n_rows, nq, bn, scores, sstride, fl, st);
 }
 
+// run_select's route over n_eff scores: one workgroup sorts them all; beyond SORT_CAP, up to SEL_KMAX results come from
+// a histogram window and its candidates (the context's hist / cand scratch), more from a global sort (its keys scratch)
+enum class SelectPath { FINAL, WINDOW, SORT };
+constexpr SelectPath select_path(int64_t n_eff, int count) {
+  return n_eff > SORT_CAP && count <= SEL_KMAX ? SelectPath::WINDOW : (n_eff > SORT_CAP ? SelectPath::SORT : SelectPath::FINAL);
+}
+
 // Top-k stage over a materialised score matrix scores[nq][sstride] with n_eff rows.
 int run_select(svs_index* idx, Ctx* c, const float* scores, int64_t n_eff, int64_t sstride, int nq, int k,
                int count, float* out_s, int64_t* out_r, hipStream_t st, int64_t row_offset) {
   int rc;
   uint32_t* hist = c->hist;
   uint64_t* cand = c->cand;
-  if (n_eff <= SORT_CAP) {
+  const SelectPath path = select_path(n_eff, count);
+  if (path == SelectPath::FINAL) {
     hipLaunchKernelGGL(select_final_kernel, dim3(nq), dim3(FINAL_THREADS), 0, st, scores, n_eff, sstride, k, count, 1,
                        (uint32_t*)nullptr, (uint64_t*)nullptr, row_offset, out_s, out_r, (const uint32_t*)nullptr);
-  } else if (count <= SEL_KMAX) {
+  } else if (path == SelectPath::WINDOW) {
     const int64_t per_block = (int64_t)FA_THREADS * SEL_VPT * 4;
     const unsigned blocks = (unsigned)((n_eff + per_block - 1) / per_block);
     hipLaunchKernelGGL(select_window_hist_kernel, dim3(blocks, nq), dim3(FA_THREADS), 0, st, scores, n_eff, sstride, hist);
@@ -1201,21 +1202,7 @@ void screen_review(svs_index* idx) {
 thread_local const svs_index* g_screen_idx;   // svs_internal_screen_stats: the calling thread's last screened search
 thread_local int g_screen_slot;
 
-// step 1: approximate scores of the whole corpus from the half shadow
-int launch_screen_scores(const svs_index* idx, Ctx* c, const float* q, float* scores, const float** q_padded, hipStream_t st) {
-  int rc = pad_query(idx, c, q, q_padded, st);
-  if (rc != SVS_OK) return rc;
-  switch (idx->ld / 512) {
-#define SVS_ROWS_CASE(N) case N: launch_rows_f16<N>(idx, idx->shadow, *q_padded, scores, st); return SVS_OK;
-    SVS_ROWS_CASE(1) SVS_ROWS_CASE(2) SVS_ROWS_CASE(3) SVS_ROWS_CASE(4) SVS_ROWS_CASE(5) SVS_ROWS_CASE(6)
-    SVS_ROWS_CASE(7) SVS_ROWS_CASE(8)
-#undef SVS_ROWS_CASE
-    default: break;
-  }
-  return fail(SVS_ERR_INVALID, "internal: no screen kernel for ld %d", idx->ld);
-}
-
-// steps 2-5: histogram, filter with margin, exact re-score of the candidates, final top-k
+// steps 2-5 (step 1, approximate scores from the half shadow, is the route single_route(idx, variant, true)): histogram, filter with margin, exact re-score of the candidates, final top-k
 int run_select_screened(svs_index* idx, Ctx* c, const float* q_padded, int k, int count, float* out_s, int64_t* out_r,
                         hipStream_t st) {
   const int64_t n = idx->n, sstride = (n + 3) & ~(int64_t)3;
@@ -1350,8 +1337,9 @@ int launch_scores_any(svs_index* idx, Ctx* c, const float* q_dev, int64_t n_rows
   } else {
     if (fl.state || n_rows != idx->n) return fail(SVS_ERR_INVALID, "internal: single-query kernels have no fused / prefix form");
     launch_record("gemv", n_rows, nq);   // (one entry for the per-query loop)
+    const SingleRoute route = single_route(idx, idx->variant.load(), false);
     for (int qi = 0; qi < nq; ++qi) {
-      rc = launch_scores(idx, c, q_dev + (size_t)qi * idx->d, scores + (size_t)qi * sstride, st);
+      rc = launch_scores(idx, c, route, q_dev + (size_t)qi * idx->d, scores + (size_t)qi * sstride, st);
       if (rc != SVS_OK) return rc;
     }
   }
@@ -1415,17 +1403,18 @@ struct SearchPlan {
   bool screen = false;   // one query over an f32 index with a valid half shadow: screen.h
   bool staged = false;   // the caller has staged the queries in the corpus dtype already (search_host, chunk by chunk)
   int64_t n_mat = 0, sstride = 0;
-  const float* q_padded = nullptr;   // screened search: the query as launch_screen_scores staged it (the re-score reads it)
+  SingleRoute route{};               // nq == 1: the score kernel, under the variant the plan was made with (single_route)
+  const float* q_padded = nullptr;   // screened search: the query as launch_scores staged it (the re-score reads it)
   EvTriple ev{};
   hipEvent_t pass_stop = nullptr;    // run-ahead pipeline, one query: the event the LAST kernel of the score half is to carry (launch_tail)
-  bool pass_bound = false;           // ... and it does: nothing was recorded for it
+  bool pass_bound = false;           // ... and it does (enqueue_score_half): nothing was recorded for it
   // run-ahead pipeline, shareable search (enqueue_ahead): the claim kernel's launch in front of the pass
   const AheadPipe* share = nullptr;
   uint64_t share_num = 0, share_reach = 0, share_epoch = 0;
   bool share_thin = false;           // ... and the pass on a thin grid
 };
 
-// Histogram / candidate scratch of run_select's window path (n_eff > SORT_CAP, count <= SEL_KMAX) for nq queries.
+// Histogram / candidate scratch of run_select's window path (SelectPath::WINDOW) for nq queries.
 int grow_select_scratch(Ctx* c, int nq, hipStream_t st) {
   if ((size_t)nq <= c->hist_cap) return SVS_OK;
   c->hist_cap = 0;
@@ -1440,28 +1429,26 @@ int grow_select_scratch(Ctx* c, int nq, hipStream_t st) {
   return SVS_OK;
 }
 
-int plan_search(svs_index* idx, Ctx* c, int nq, int k, int count, hipStream_t st, bool allow_fused, SearchPlan* p) {
+int plan_search(svs_index* idx, Ctx* c, int nq, int k, int count, hipStream_t st, bool allow_fused, int variant, SearchPlan* p) {
   const int64_t n = idx->n;
   int rc;
   if ((rc = staging_wait(idx)) != SVS_OK) return rc;
   p->nq = nq; p->k = k; p->count = count;
-  p->path_a = k > 0 && n > SORT_CAP && count <= SEL_KMAX;
+  p->path_a = k > 0 && select_path(n, count) == SelectPath::WINDOW;
   // Fused top-k epilogue (no score matrix) for the batched kernels; a query whose
   // candidate list overflows comes back marked and is re-run by the caller.  The prefix
   // pass costs ~60 us whatever the batch: measured break-even is 16 queries (f32: 13.2 k vs
   // 12.7 k queries/s at 16, 6.4 k vs 6.5 k at 8; f16 at 32: 49 k vs 41 k; fp8 at 32: 77 k vs 64 k).
   p->fused = allow_fused && p->path_a && is_batched(idx, nq) && nq >= 16 &&
              n >= 8 * FUSE_PREFIX_MIN && (int64_t)n < ((int64_t)1 << 32) &&
-             count <= 256 && idx->variant.load() != VARIANT_NO_FUSION;
-  {
-    const int variant = idx->variant.load();
-    p->screen = nq == 1 && p->path_a && screen_ready(idx) &&
-                variant != VARIANT_SCREEN_OFF && (variant == VARIANT_SCREEN_FORCE || (variant == VARIANT_DEFAULT && n >= screen_min_rows(idx->ld)));
-    if (p->screen) {
-      screen_review(idx);
-      p->screen = !idx->scr_paused.load();
-    }
+             count <= 256 && variant != VARIANT_NO_FUSION;
+  p->screen = nq == 1 && p->path_a && screen_ready(idx) &&
+              variant != VARIANT_SCREEN_OFF && (variant == VARIANT_SCREEN_FORCE || (variant == VARIANT_DEFAULT && n >= screen_min_rows(idx->ld)));
+  if (p->screen) {
+    screen_review(idx);
+    p->screen = !idx->scr_paused.load();
   }
+  if (nq == 1) p->route = single_route(idx, variant, p->screen);
   p->n_mat = p->fused ? fuse_prefix_rows(n) : n;       // rows of the materialised score matrix
   p->sstride = (p->n_mat + 3) & ~(int64_t)3;           // float4-aligned score vectors
   // thresholds: many queries over a short prefix -> one k-th-value kernel (47 vs 62 us at 1024 x 16,384);
@@ -1508,9 +1495,6 @@ int enqueue_prefix(svs_index* idx, Ctx* c, const SearchPlan& p, const float* q_d
   return SVS_OK;
 }
 
-// The half rows a single-query search's f16 one-shot pass reads: the shadow (screened f32 index) or the rows (f16 index)
-inline const void* half_rows_of(const svs_index* idx, const SearchPlan& p) { return p.screen ? idx->shadow : idx->rows; }
-
 // enqueue_main in two halves, so that svs_index_search_device_ahead can put them on two streams: everything up to and
 // including the `e1` timing event (query padding and staging, the screen pass or the score launch, the tombstone
 // mask), then the selection.  Both take the same plan; q_padded carries the staged query of a screened search across.
@@ -1532,29 +1516,28 @@ int enqueue_score_half(svs_index* idx, Ctx* c, SearchPlan& p, const float* q_dev
     if (p.timed) HIP_TRY(hipEventRecord(ev.e1, st));
     return SVS_OK;
   }
-  // (the half's last kernel carries p.pass_stop: the score kernel, or the mask behind it)
+  // (the half's LAST kernel is handed p.pass_stop: the mask when there are tombstones, else the score kernel)
   const bool masked = !idx->dead_list.empty(), carry = p.pass_stop && nq == 1;
-  if (p.share) {   // what this pass serves is decided here, on the pass stream, and nowhere else (pass_share.h)
-    const AheadPipe* sp = p.share;
-    hipLaunchKernelGGL(pass_claim_kernel, dim3(1), dim3(64), 0, st, (const MailEntry*)sp->mailbox, sp->share_dev, sp->share_mirror(),
-                       p.share_num, p.share_reach, sp->share_limit, (const v4f*)q_dev, c->scores.p, (uint64_t)(uintptr_t)half_rows_of(idx, p),
-                       (uint64_t)n, p.share_epoch, (uint64_t)idx->ld, p.share_thin ? 1 : 0);
-    g_pass = PassLaunch{&sp->share_dev->plan, sp->share_limit, p.share_thin};
+  if (nq == 1) {
+    PassOpts o;
+    if (carry && !masked) o.stop = p.pass_stop;
+    if (p.share) {   // what this pass serves is decided here, on the pass stream, and nowhere else (pass_share.h)
+      const AheadPipe* sp = p.share;
+      hipLaunchKernelGGL(pass_claim_kernel, dim3(1), dim3(64), 0, st, (const MailEntry*)sp->mailbox, sp->share_dev, sp->share_mirror(),
+                         p.share_num, p.share_reach, sp->share_limit, (const v4f*)q_dev, c->scores.p, (uint64_t)(uintptr_t)half_rows_of(idx, p.route),
+                         (uint64_t)n, p.share_epoch, (uint64_t)idx->ld, p.share_thin ? 1 : 0);
+      o = PassOpts{o.stop, &sp->share_dev->plan, sp->share_limit, p.share_thin};
+    }
+    if (!p.screen) launch_record("gemv", n, 1);   // (as launch_scores_any announces its per-query loop)
+    rc = launch_scores(idx, c, p.route, q_dev, c->scores, st, o, &p.q_padded);
+  } else {
+    rc = launch_scores_any(idx, c, q_dev, n, nq, c->scores, p.sstride, FuseLaunch{}, st, !p.staged);
   }
-  if (carry && !masked) tail_arm(p.pass_stop);
-  if (p.screen) rc = launch_screen_scores(idx, c, q_dev, c->scores, &p.q_padded, st);
-  else rc = launch_scores_any(idx, c, q_dev, n, nq, c->scores, p.sstride, FuseLaunch{}, st, !p.staged);
-  g_pass = PassLaunch{};
-  if (rc != SVS_OK) {
-    (void)tail_take();
-    return rc;
-  }
-  if (masked) {   // tombstoned rows can never be returned
-    if (carry) tail_arm(p.pass_stop);
-    launch_tail(mask_dead_rows_kernel, dim3(64), dim3(256), 0, st, c->scores.p, p.sstride, nq, idx->dead_dev.p,
+  if (rc != SVS_OK) return rc;
+  if (masked)   // tombstoned rows can never be returned
+    launch_tail(carry ? p.pass_stop : nullptr, mask_dead_rows_kernel, dim3(64), dim3(256), 0, st, c->scores.p, p.sstride, nq, idx->dead_dev.p,
                 (int64_t)idx->dead_list.size(), n, (int64_t)0);
-  }
-  p.pass_bound = tail_take();
+  p.pass_bound = carry;
   if (p.timed && !(p.pass_bound && p.pass_stop == ev.e1)) HIP_TRY(hipEventRecord(ev.e1, st));
   return SVS_OK;
 }
@@ -1592,7 +1575,7 @@ int enqueue_search(svs_index* idx, Ctx* c, const float* q_dev, int nq, int k, in
                    float* out_s, int64_t* out_r, hipStream_t st, bool allow_fused = false) {
   SearchPlan p;
   int rc;
-  if ((rc = plan_search(idx, c, nq, k, count, st, allow_fused, &p)) != SVS_OK) return rc;
+  if ((rc = plan_search(idx, c, nq, k, count, st, allow_fused, idx->variant.load(), &p)) != SVS_OK) return rc;
   if ((rc = enqueue_prefix(idx, c, p, q_dev, st)) != SVS_OK) return rc;
   return enqueue_main(idx, c, p, q_dev, out_s, out_r, st);
 }
@@ -1646,8 +1629,7 @@ int pairs_block_device(svs_index* idx, Ctx* c, int64_t ns, int count, float* S, 
   if (!idx->dead_list.empty())
     hipLaunchKernelGGL(mask_dead_pairs_kernel, dim3(1024), dim3(256), 0, st, S, ns, np, idx->dead_dev, (int64_t)idx->dead_list.size());
   const int64_t flat = ns * np;
-  const bool path_a = flat > SORT_CAP && count <= SEL_KMAX;
-  if (path_a && (rc = grow_select_scratch(c, 1, st)) != SVS_OK) return rc;
+  if (select_path(flat, count) == SelectPath::WINDOW && (rc = grow_select_scratch(c, 1, st)) != SVS_OK) return rc;
   if ((rc = run_select(idx, c, S, flat, flat, 1, count, count, d_s, d_r, st, /*row_offset=*/0)) != SVS_OK) return rc;
   HIP_TRY(hipGetLastError());
   return SVS_OK;
@@ -2485,7 +2467,7 @@ static int32_t search_host(svs_index* idx, const float* queries, int32_t nq, int
   const auto t_begin = std::chrono::steady_clock::now();
   auto stamp = [&](int i) { g_host_phase[i] = std::chrono::duration<double>(std::chrono::steady_clock::now() - t_begin).count(); };
   SearchPlan plan;
-  if ((rc = plan_search(idx, c, nq, count, count, c->stream, true, &plan)) != SVS_OK) return rc;
+  if ((rc = plan_search(idx, c, nq, count, count, c->stream, true, idx->variant.load(), &plan)) != SVS_OK) return rc;
   stamp(0);
   const int64_t mode = g_tune_upload.load();
   // f16 batches: the staging kernel (convert_queries_f16) reads the f32 queries STRAIGHT out of the pinned buffer, over PCIe,
@@ -2702,31 +2684,58 @@ static int pipe_get(svs_index* idx, hipStream_t caller, AheadPipe** out) {
   return SVS_OK;
 }
 
-// Everything a single-query search of this index takes from its context, so that a pipeline's contexts get their
-// scratch TOGETHER (ahead_scratch_ok / enqueue_ahead) and no later call allocates: the scores, the window path's
-// histogram and candidates or path B's sort keys, and the staged query of every score route.
-static size_t ahead_keys_need(const svs_index* idx, int k, int count) {
-  return k > 0 && idx->n > SORT_CAP && count > SEL_KMAX ? (size_t)next_pow2_i64(idx->n) : 0;
+// What a single-query search takes from its context, in elements per buffer (hist: queries): the scores, what the
+// route's staging (launch_scores) and the selection path (run_select) grow.  A pipeline's contexts get it TOGETHER
+// (enqueue_ahead), so those lazy grow calls are no-ops on the ring and free nothing a search in flight reads.
+struct SingleScratch { size_t scores, hist, keys, q16, qh, q8, q8s, q8f; };
+static SingleScratch single_scratch(const svs_index* idx, const SingleRoute& r, SelectPath sel) {
+  const size_t ld = (size_t)idx->ld, half = r.query == SingleRoute::HALF, fp8 = r.query == SingleRoute::FP8;
+  return {(size_t)((idx->n + 3) & ~(int64_t)3), sel == SelectPath::WINDOW, sel == SelectPath::SORT ? (size_t)next_pow2_i64(idx->n) : 0,
+          r.query == SingleRoute::PADDED ? (size_t)GQ * ld : 0, half * ld, fp8 * ld, fp8, fp8 * ld};
 }
-static bool ahead_scratch_ok(const svs_index* idx, const Ctx* c, int k, int count) {
-  const bool path_a = k > 0 && idx->n > SORT_CAP && count <= SEL_KMAX;
-  return (size_t)((idx->n + 3) & ~(int64_t)3) <= c->scores.cap && !(path_a && c->hist_cap < 1) &&
-         ahead_keys_need(idx, k, count) <= c->keys.cap;
+static bool ahead_scratch_ok(const Ctx* c, const SingleScratch& s) {
+  return s.scores <= c->scores.cap && s.hist <= c->hist_cap && s.keys <= c->keys.cap && s.q16 <= c->q16.cap && s.qh <= c->qh.cap &&
+         s.q8 <= c->q8.cap && s.q8s <= c->q8s.cap && s.q8f <= c->q8f.cap;
 }
-static int ahead_scratch_grow(const svs_index* idx, Ctx* c, int k, int count, hipStream_t st) {
-  const bool path_a = k > 0 && idx->n > SORT_CAP && count <= SEL_KMAX;
-  const size_t ld = (size_t)idx->ld;
+static int ahead_scratch_grow(Ctx* c, const SingleScratch& s, hipStream_t st) {
   int rc;
-  if ((rc = c->scores.grow((size_t)((idx->n + 3) & ~(int64_t)3))) != SVS_OK) return rc;
-  if (path_a && (rc = grow_select_scratch(c, 1, st)) != SVS_OK) return rc;
-  if ((rc = c->keys.grow(ahead_keys_need(idx, k, count))) != SVS_OK) return rc;
-  if (idx->dtype == SVS_DTYPE_FP8) {
-    if ((rc = c->q8.grow(ld)) != SVS_OK || (rc = c->q8s.grow(1)) != SVS_OK || (rc = c->q8f.grow(ld)) != SVS_OK) return rc;
+  if ((rc = c->scores.grow(s.scores)) != SVS_OK || (rc = grow_select_scratch(c, (int)s.hist, st)) != SVS_OK ||
+      (rc = c->keys.grow(s.keys)) != SVS_OK || (rc = c->q16.grow(s.q16)) != SVS_OK || (rc = c->qh.grow(s.qh)) != SVS_OK ||
+      (rc = c->q8.grow(s.q8)) != SVS_OK || (rc = c->q8s.grow(s.q8s)) != SVS_OK)
+    return rc;
+  return c->q8f.grow(s.q8f);
+}
+
+// Shared passes (pass_share.h): search pipe->seq, planned as p, goes into the mailbox, and the host's copy of the claim
+// rule says whether its own pass gets a thin grid.  Writes p.share* and the pipeline's owner and claim count; launches nothing.
+static void publish_search(const svs_index* idx, AheadPipe* pipe, const Ctx* c, SearchPlan& p, const float* q_dev, bool claimable) {
+  p.share = pipe;
+  p.share_num = pipe->base + pipe->seq;
+  p.share_reach = pipe->base + pipe->covered + AHEAD_RING - 1;
+  p.share_epoch = idx->geo_epoch.load();
+  MailEntry* m = &pipe->mailbox[p.share_num & (MAILBOX_SIZE - 1)];
+  __atomic_store_n(&m->tag, (uint64_t)0, __ATOMIC_RELAXED);
+  __atomic_thread_fence(__ATOMIC_RELEASE);
+  const uint64_t f[7] = {(uint64_t)(uintptr_t)q_dev, (uint64_t)(uintptr_t)c->scores.p, (uint64_t)(uintptr_t)half_rows_of(idx, p.route),
+                         (uint64_t)idx->n, p.share_epoch, (uint64_t)idx->ld, claimable ? MAIL_CLAIMABLE : 0u};
+  for (int w = 0; w < 7; ++w) __atomic_store_n(&m->tag + 1 + w, f[w], __ATOMIC_RELAXED);
+  __atomic_store_n(&m->tag, p.share_num + 1, __ATOMIC_RELEASE);
+  // The grid of this search's own pass.  The claim rule, restated: the search joins the run of the last search the
+  // host took for an owner when it is the next number, the run is short of the limit, it is claimable and within the
+  // owner's reach, and its pass reads what the owner's reads.  The owner's claim kernel will then find it -- it is
+  // published -- unless that kernel has run already: the mirrored counters (plain loads, a hint) say how many have.
+  AheadPipe::Owner& o = pipe->owner;
+  const bool joins = o.valid && p.share_num == o.next && o.next - o.num < (uint64_t)pipe->share_limit && claimable &&
+                     p.share_num <= o.reach && f[2] == o.rows && f[3] == o.n && f[4] == o.epoch && f[5] == o.ld;
+  pipe->claims += 1;   // (this search's own claim kernel: enqueue_score_half launches it first)
+  if (joins && (int32_t)(pipe->claims_run() - o.ordinal) < 0) {
+    o.next += 1;
+    p.share_thin = true;
   } else {
-    if ((rc = c->q16.grow((size_t)GQ * ld)) != SVS_OK) return rc;
-    if (idx->dtype == SVS_DTYPE_F16 && (rc = c->qh.grow(ld)) != SVS_OK) return rc;
+    o = AheadPipe::Owner{true, p.share_num, p.share_num + 1, p.share_reach, f[2], f[3], f[4], f[5], pipe->claims};
   }
-  return SVS_OK;
+  const int64_t mode = g_tune_thin.load();
+  if (mode) p.share_thin = mode == 2;
 }
 
 // One single-query search through the pipeline: score half on the pass stream (behind the query's event and, once
@@ -2739,12 +2748,15 @@ static int enqueue_ahead(svs_index* idx, AheadPipe* pipe, const float* q_dev, in
   std::lock_guard<std::mutex> lk(pipe->mu);
   // growing scratch frees buffers that earlier searches may still read: drain first, then grow every context of
   // the ring, so that the calls that follow allocate nothing
+  const int variant = idx->variant.load();
+  const SingleRoute plain = single_route(idx, variant, false);   // (screening is decided by the plan, behind the waits)
+  const SingleScratch need = single_scratch(idx, plain, select_path(idx->n, count));
   bool fits = true;
-  for (int j = 0; j < AHEAD_RING; ++j) fits = fits && ahead_scratch_ok(idx, pipe->ctx[j], k, count);
+  for (int j = 0; j < AHEAD_RING; ++j) fits = fits && ahead_scratch_ok(pipe->ctx[j], need);
   if (!fits) {
     if (pipe->seq) HIP_TRY(pipe_drain(pipe));
     for (int j = 0; j < AHEAD_RING; ++j) {
-      const int rc = ahead_scratch_grow(idx, pipe->ctx[j], k, count, pipe->pass);
+      const int rc = ahead_scratch_grow(pipe->ctx[j], need, pipe->pass);
       if (rc != SVS_OK) return rc;
     }
   }
@@ -2758,46 +2770,15 @@ static int enqueue_ahead(svs_index* idx, AheadPipe* pipe, const float* q_dev, in
     pipe->covered = i - AHEAD_LAG + 1;
   }
   SearchPlan p;
-  int rc = plan_search(idx, c, 1, k, count, pipe->pass, false, &p);
-  // Shared passes (pass_share.h).  The pass is the f16 one-shot kernel of a geometry that shares, over the query as the
-  // caller gave it (a query pad_query would have to copy is not shared: its staged copy lives in the context, which
-  // the next search of the ring slot overwrites).  Published before anything of this call is launched.
-  if (rc == SVS_OK && pipe->share_limit > 1 && !pipe->per_pass && p.path_a &&
-      (p.screen || (idx->dtype == SVS_DTYPE_F16 && idx->ld % 512 == 0)) && idx->ld <= 4096 && f16_rows_share(idx->ld / 512) &&
-      idx->ld == idx->d && (((uintptr_t)q_dev) & 15) == 0) {
-    p.share = pipe;
-    p.share_num = pipe->base + i;
-    p.share_reach = pipe->base + pipe->covered + AHEAD_RING - 1;
-    p.share_epoch = idx->geo_epoch.load();
-    // claimable by an earlier pass: the query is complete now (no event of its own), and no timed step (its events
-    // must bracket a pass that did its work)
-    const bool claimable = !query_ready && !p.timed;
-    MailEntry* m = &pipe->mailbox[p.share_num & (MAILBOX_SIZE - 1)];
-    __atomic_store_n(&m->tag, (uint64_t)0, __ATOMIC_RELAXED);
-    __atomic_thread_fence(__ATOMIC_RELEASE);
-    const uint64_t f[7] = {(uint64_t)(uintptr_t)q_dev, (uint64_t)(uintptr_t)c->scores.p, (uint64_t)(uintptr_t)half_rows_of(idx, p),
-                           (uint64_t)idx->n, p.share_epoch, (uint64_t)idx->ld, claimable ? MAIL_CLAIMABLE : 0u};
-    for (int w = 0; w < 7; ++w) __atomic_store_n(&m->tag + 1 + w, f[w], __ATOMIC_RELAXED);
-    __atomic_store_n(&m->tag, p.share_num + 1, __ATOMIC_RELEASE);
-    // The grid of this search's own pass.  The claim rule, restated: the search joins the run of the last search the
-    // host took for an owner when it is the next number, the run is short of the limit, it is claimable and within the
-    // owner's reach, and its pass reads what the owner's reads.  The owner's claim kernel will then find it -- it is
-    // published -- unless that kernel has run already: the mirrored counters (plain loads, a hint) say how many have.
-    AheadPipe::Owner& o = pipe->owner;
-    const bool joins = o.valid && p.share_num == o.next && o.next - o.num < (uint64_t)pipe->share_limit && claimable &&
-                       p.share_num <= o.reach && f[2] == o.rows && f[3] == o.n && f[4] == o.epoch && f[5] == o.ld;
-    pipe->claims += 1;   // (this search's own claim kernel: enqueue_score_half launches it first)
-    if (joins && (int32_t)(pipe->claims_run() - o.ordinal) < 0) {
-      o.next += 1;
-      p.share_thin = true;
-    } else {
-      o = AheadPipe::Owner{true, p.share_num, p.share_num + 1, p.share_reach, f[2], f[3], f[4], f[5], pipe->claims};
-    }
-    const int64_t mode = g_tune_thin.load();
-    if (mode) p.share_thin = mode == 2;
-  } else {
+  int rc = plan_search(idx, c, 1, k, count, pipe->pass, false, variant, &p);
+  if (rc == SVS_OK && p.route.query != plain.query) rc = fail(SVS_ERR_INVALID, "internal: the ring's scratch was sized for another query staging");
+  // Published before anything of this call is launched; not a query pad_query would copy (the copy lives in the context,
+  // which the next search of the ring slot overwrites).  Claimable by an earlier pass: the query is complete now (no
+  // event of its own), and no timed step (its events must bracket a pass that did its work).
+  if (rc == SVS_OK && pipe->share_limit > 1 && !pipe->per_pass && p.path_a && p.route.shares && !query_needs_copy(idx, q_dev))
+    publish_search(idx, pipe, c, p, q_dev, !query_ready && !p.timed);
+  else
     pipe->owner.valid = false;   // (a search that publishes nothing ends every run)
-  }
   if (rc == SVS_OK && p.timed) idx->ahead_records.fetch_add(1);   // (e0: a start event of the extended launch is a marker of its own, so it stays a record)
   hipEvent_t done = rc == SVS_OK && p.timed && !pipe->per_pass ? p.ev.e1 : pipe->pass_done[j];
   if (!pipe->per_pass) p.pass_stop = done;
@@ -2899,7 +2880,7 @@ int32_t svs_index_scores_n(svs_index* idx, const float* query, int32_t d, float*
   if ((rc = c->scores.grow((size_t)((idx->n + 3) & ~(int64_t)3))) != SVS_OK) return rc;
   HIP_TRY(hipMemcpyAsync(c->q_dev, query, (size_t)d * sizeof(float), hipMemcpyHostToDevice, c->stream));
   launch_record("gemv", idx->n, 1);
-  if ((rc = launch_scores(idx, c, c->q_dev, c->scores, c->stream)) != SVS_OK) return rc;
+  if ((rc = launch_scores(idx, c, single_route(idx, idx->variant.load(), false), c->q_dev, c->scores, c->stream)) != SVS_OK) return rc;
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipMemcpyAsync(out_scores, c->scores, (size_t)idx->n * sizeof(float), hipMemcpyDeviceToHost, c->stream));
   HIP_TRY(hipStreamSynchronize(c->stream));
@@ -2971,8 +2952,9 @@ int32_t svs_index_search_rows(svs_index* idx, const float* queries, int32_t nq, 
   // Query chunks whose score matrix (and, for k > SEL_KMAX over more than SORT_CAP rows, sort keys) stays <= 2 GiB
   const int64_t sstride = (m + 3) & ~(int64_t)3;
   int64_t per_q = 4 * sstride;
-  const bool window = m > SORT_CAP && count <= SEL_KMAX;
-  if (m > SORT_CAP && !window) per_q += 8 * next_pow2_i64(m);
+  const SelectPath sel = select_path(m, count);
+  const bool window = sel == SelectPath::WINDOW;
+  if (sel == SelectPath::SORT) per_q += 8 * next_pow2_i64(m);
   const int qc = (int)std::max<int64_t>(1, std::min<int64_t>(nq, ((int64_t)2 << 30) / per_q));
   if ((rc = c->scores.grow((size_t)qc * (size_t)sstride)) != SVS_OK) return rc;
   if (window && (rc = grow_select_scratch(c, qc, st)) != SVS_OK) return rc;
@@ -3136,6 +3118,22 @@ int32_t svs_internal_host_phases(double* out, int32_t n) {
   return SVS_OK;
 }
 
+int32_t svs_internal_single_route(int32_t dtype, int32_t d, int32_t variant, int32_t screen, char* kernel, int32_t cap, int32_t* flags) {
+  svs_index shape;   // (never sees a device: the route and the launchers' names depend on dtype, d and ld alone)
+  shape.dtype = dtype; shape.d = d; shape.ld = choose_ld(d, dtype);
+  if (dtype < SVS_DTYPE_F32 || dtype > SVS_DTYPE_FP8 || d < 1 || variant < VARIANT_DEFAULT || variant > VARIANT_LAST || !kernel || cap < 1 ||
+      !flags || (screen && !shadow_eligible(&shape)))
+    return fail(SVS_ERR_INVALID, "svs_internal_single_route: no index of dtype %d, d %d, variant %d, screen %d", dtype, d, variant, screen);
+  const SingleRoute r = single_route(&shape, variant, screen != 0);
+  const Ctx ctx;
+  const char* name = nullptr;
+  const int rc = launch_route(&shape, &ctx, r, nullptr, nullptr, nullptr, PassOpts{nullptr, nullptr, 0, false, &name});
+  if (rc != SVS_OK) return rc;
+  snprintf(kernel, (size_t)cap, "%s", name);
+  *flags = (r.shares ? 1 : 0) | (r.query == SingleRoute::PADDED ? 2 : 0);
+  return SVS_OK;
+}
+
 int32_t svs_internal_last_launches(const char** kernels, int64_t* rows, int32_t* nq, int32_t cap) {
   for (int i = 0; i < cap && i < g_nlaunch && i < LAUNCH_REC_CAP; ++i) {
     if (kernels) kernels[i] = g_launch[i].kernel;
@@ -3225,7 +3223,7 @@ int32_t svs_internal_select_scores(svs_index* idx, const float* scores, int32_t 
   const int count = (int)std::min<int64_t>(k, n);
   *out_count = count;
   const int64_t sstride = (n + 3) & ~(int64_t)3;   // float4-aligned score vectors, as plan_search lays them out
-  const bool path_a = n > SORT_CAP && count <= SEL_KMAX;
+  const bool path_a = select_path(n, count) == SelectPath::WINDOW;
   Ctx* c = nullptr;
   if ((rc = ctx_acquire(idx, nullptr, true, &c)) != SVS_OK) return rc;
   CtxGuard cg{idx, c};

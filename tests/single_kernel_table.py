@@ -4,8 +4,9 @@ One row per instantiation: (dtype, d, variant, kernel).  `kernel` is what svs_in
 "gemv" entry of a scores call, spelled as c++filt prints it in the build's resource report; `variant` is the
 svs_index_set_variant value under which an index of that dtype and dimension launches it (0: the default rules).
 
-The dispatch rules these rows follow (svs_amd/csrc/svs_amd.hip: choose_ld, launch_scores, launch_rows, launch_unrolled,
-for_row_geometry, for_width):
+The dispatch rules these rows follow (svs_amd/csrc/svs_amd.hip: choose_ld, single_route, launch_route, launch_rows,
+launch_unrolled, for_f16_oneshot, for_fp8_oneshot, for_row_geometry, for_width; tests/test_single_route.py asks the
+library for the route of every row without a device):
   * choose_ld pads a row to whole 1 KiB wave loads (64 chunks of 16 bytes) when that costs at most an eighth more
     bytes, else to whole 128-byte lines (8 chunks) on the same condition, else to whole chunks.  Below, c = ld in chunks.
   * f32, c % 64 == 0, c <= 1024 (ld = NSTEP * 256): gemv_f32_oneshot_kernel<NSTEP, R, WPB, NT, false, false>, by default
