@@ -272,6 +272,35 @@ int32_t svs_index_search_rows(svs_index* idx, const float* queries, int32_t nq, 
                               const int64_t* rows, int64_t nrows,
                               float* out_scores, int64_t* out_rows, int32_t* out_count);
 
+/* ---- neighbours of STORED rows ("more like this", near-duplicates of one document, the kNN graph):
+ *      replaces a loop of np.dot(M, M[i]) + get_top_k per row (src/svs/kb.py:1623, src/svs/util.py:190-203;
+ *      0.24 s per row at 1M x 1536 by the reference's published figure).  The rows are already in HBM in the
+ *      dtype the kernels read: nothing is pulled out, pushed back or filtered on the host.
+ *   rows      GLOBAL rows (row_offset + local, like svs_index_mask_rows), any order, repeats allowed; each
+ *             position is answered on its own.  A row outside [row_offset, row_offset + n) -> SVS_ERR_INVALID;
+ *             a tombstoned source row -> SVS_ERR_INVALID (the message names it); nrows < 0 -> SVS_ERR_INVALID.
+ *             Every argument is validated before anything is launched; a failing call writes no output.
+ *   count   = min(max(k, 0), live rows - 1), the same for every position (a source row is live); *out_count is
+ *             written in every successful case.  nrows == 0 or k <= 0 -> count 0, nothing launched.
+ *   result    position i: the search of stored row rows[i], used as the query, over all live rows EXCEPT rows[i]
+ *             itself, order (score desc, row desc), at out[i*k .. i*k+count); entries past count are not touched
+ *             (as svs_index_search).  Only the row id is excluded, never a score: other rows with the same
+ *             content (exact duplicates) stay in.
+ * Exact definition.  Positions are processed in blocks of SVS_NEIGHBORS_BLOCK consecutive positions.  For a block
+ * with source rows R: svs_index_search(idx, Q, |R|, d, count + 1) with Q = svs_index_debug_dequant of those rows
+ * (coalescing off); in each query's list the entry whose row is the source row is removed, or, if it is absent, the
+ * last entry.  Rows, order and score bits equal that.  (The top count + 1 of all rows, minus the source row if present
+ * and otherwise truncated, IS the top count of the others -- also when the source row is not among them: a short row,
+ * a zero row.)  The block is a normal search: every route is reached unchanged (screened and unscreened single query,
+ * 16-query, tiled, phased, fused), and k + 1 > 256 simply falls off the fused path, as any search with k > 256 does.
+ * Blocking; re-entrant on one handle; holds a reference and the geometry lock shared, like svs_index_search; waits for
+ * pending staging copies; never goes through the coalescer (svs_index_set_coalesce does not affect it).
+ * Out of scope: svs_multi (call it on the shard that holds the row: the neighbours are then that shard's), row-sharded
+ * corpora in several processes, and a device-pointer variant. */
+#define SVS_NEIGHBORS_BLOCK 1024
+int32_t svs_index_neighbors(svs_index* idx, const int64_t* rows, int64_t nrows, int32_t k,
+                            float* out_scores, int64_t* out_rows, int32_t* out_count);
+
 /* ---- pairwise: replaces np.dot(M, M.T) + get_top_pairs of
  *      document_top_pairwise_scores, src/svs/kb.py:1642-1671, src/svs/util.py:206-233 --
  * The k best-scoring row PAIRS (i < j; diagonal and lower triangle ignored), ordered

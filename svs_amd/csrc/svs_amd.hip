@@ -36,6 +36,7 @@
 #include "select.h"
 #include "screen.h"
 #include "compact.h"
+#include "neighbors.h"
 
 namespace {
 
@@ -214,6 +215,12 @@ struct Ctx {
   PinBuf<float> redo_q_pin;                                    // ... and the queries themselves, gathered
   DevBuf<uint32_t> list_dev;    // svs_index_search_rows: the listed local rows (u32)
   PinBuf<uint32_t> list_pin;    // ... built here, uploaded from here
+  // svs_index_neighbors (neighbors.h): the call's local source rows (pinned copy, device copy), the block's search
+  // results at stride count + 1, and the re-run groups' row lists and query panel
+  PinBuf<uint32_t> nb_list_pin; DevBuf<uint32_t> nb_list_dev;
+  DevBuf<float> nb_s;           DevBuf<int64_t> nb_r;
+  PinBuf<uint32_t> nb_redo_pin; DevBuf<uint32_t> nb_redo_dev;
+  DevBuf<float> nb_redo_q;
   // Scratch is reused in stream order.  A context stays with the stream that
   // last used it; handing it to ANOTHER stream first drains the old one.
   hipStream_t last_stream = nullptr;
@@ -2986,6 +2993,146 @@ int32_t svs_index_search_rows(svs_index* idx, const float* queries, int32_t nq, 
       if (p < 0 || p >= m) return fail(SVS_ERR_DEVICE, "search_rows: position %lld outside the %lld listed rows", (long long)p, (long long)m);
       dr[i] = (int64_t)S[p] + lo;
     }
+  }
+  return SVS_OK;
+}
+
+// rows_as_queries_kernel: the f32 panel of nq listed rows (list_dev: local rows on the device) into `panel`
+static void launch_rows_as_queries(const svs_index* idx, const uint32_t* list_dev, int nq, float* panel, hipStream_t st) {
+  const int ld16 = (int)((size_t)idx->ld * elem_bytes(idx) / 16);
+  const int epc = 16 / (int)elem_bytes(idx);
+  const int64_t items = (int64_t)nq * ((idx->d + epc - 1) / epc);
+  const unsigned blocks = (unsigned)std::min<int64_t>(4096, (items + NEIGHBORS_THREADS - 1) / NEIGHBORS_THREADS);
+  launch_record("rows_as_queries_kernel", nq, nq);
+  const u32x4* M = (const u32x4*)idx->rows;
+  if (idx->dtype == SVS_DTYPE_F32)
+    hipLaunchKernelGGL(rows_as_queries_kernel<0>, dim3(blocks), dim3(NEIGHBORS_THREADS), 0, st, M, ld16, (const float*)nullptr, list_dev, nq, idx->d, panel);
+  else if (idx->dtype == SVS_DTYPE_F16)
+    hipLaunchKernelGGL(rows_as_queries_kernel<1>, dim3(blocks), dim3(NEIGHBORS_THREADS), 0, st, M, ld16, (const float*)nullptr, list_dev, nq, idx->d, panel);
+  else
+    hipLaunchKernelGGL(rows_as_queries_kernel<2>, dim3(blocks), dim3(NEIGHBORS_THREADS), 0, st, M, ld16, (const float*)idx->row_scales, list_dev, nq, idx->d, panel);
+}
+
+// drop_self_kernel: nq results at stride count + 1 -> count entries each at stride count
+static void launch_drop_self(const svs_index* idx, const float* in_s, const int64_t* in_r, const uint32_t* list_dev, int nq, int count,
+                             float* out_s, int64_t* out_r, hipStream_t st) {
+  constexpr int WPB = NEIGHBORS_THREADS / 64;
+  launch_record("drop_self_kernel", count + 1, nq);
+  hipLaunchKernelGGL(drop_self_kernel, dim3((unsigned)((nq + WPB - 1) / WPB)), dim3(NEIGHBORS_THREADS), 0, st, in_s, in_r, list_dev,
+                     idx->row_offset, nq, count, out_s, out_r);
+}
+
+int32_t svs_index_neighbors(svs_index* idx, const int64_t* rows, int64_t nrows, int32_t k, float* out_scores, int64_t* out_rows,
+                            int32_t* out_count) {
+  launch_reset();
+  if (!idx) return fail(SVS_ERR_INVALID, "null index");
+  RefGuard guard(idx);
+  std::shared_lock<std::shared_mutex> geo(idx->rw);
+  if (nrows < 0) return fail(SVS_ERR_INVALID, "nrows must be >= 0");
+  if (nrows > 0 && !rows) return fail(SVS_ERR_INVALID, "null row list");
+  const int64_t lo = idx->row_offset, n = idx->n;
+  for (int64_t t = 0; t < nrows; ++t) {
+    const int64_t r = rows[t] - lo;
+    if (r < 0 || r >= n)
+      return fail(SVS_ERR_INVALID, "row %lld out of range [%lld, %lld)", (long long)rows[t], (long long)lo, (long long)(lo + n));
+    if (idx->dead_flag[(size_t)r]) return fail(SVS_ERR_INVALID, "row %lld is tombstoned: it has no neighbours", (long long)rows[t]);
+  }
+  const int64_t live = n - (int64_t)idx->dead_list.size();
+  const int count = (int)std::min<int64_t>(std::max(k, 0), std::max<int64_t>(live - 1, 0));
+  if (out_count) *out_count = count;
+  if (nrows == 0 || count == 0) return SVS_OK;
+  if (!out_scores || !out_rows) return fail(SVS_ERR_INVALID, "null output");
+  if (idx->d == 0) return fail(SVS_ERR_SHAPE, "an index of dimension 0 has no scores");
+  HIP_TRY(hipSetDevice(idx->device));
+  int rc;
+  if ((rc = staging_wait(idx)) != SVS_OK) return rc;
+  Ctx* c = nullptr;
+  if ((rc = ctx_acquire(idx, nullptr, true, &c)) != SVS_OK) return rc;
+  CtxGuard cg{idx, c};
+  hipStream_t st = c->stream;
+  const int kk = count + 1, d = idx->d;   // (kk <= live rows: the search's own count is kk)
+  const int64_t B = SVS_NEIGHBORS_BLOCK;
+  const int bmax = (int)std::min<int64_t>(B, nrows);
+  const size_t on = (size_t)nrows * (size_t)count;
+  if ((rc = c->nb_list_pin.grow((size_t)nrows)) != SVS_OK || (rc = c->nb_list_dev.grow((size_t)nrows)) != SVS_OK) return rc;
+  if ((rc = c->q_dev.grow((size_t)bmax * d)) != SVS_OK) return rc;
+  if ((rc = c->nb_s.grow((size_t)bmax * kk)) != SVS_OK || (rc = c->nb_r.grow((size_t)bmax * kk)) != SVS_OK) return rc;
+  if ((rc = c->out_s_pin.grow(on)) != SVS_OK || (rc = c->out_r_pin.grow(on)) != SVS_OK) return rc;
+  for (int64_t t = 0; t < nrows; ++t) c->nb_list_pin[t] = (uint32_t)(rows[t] - lo);
+  HIP_TRY(hipMemcpyAsync(c->nb_list_dev, c->nb_list_pin, (size_t)nrows * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+  // Block by block on the context's stream: panel, the ordinary search at count + 1 into device scratch, self dropped
+  // into the pinned (device-visible) output.  One wait for the whole call.
+  const int variant = idx->variant.load();
+  for (int64_t b0 = 0; b0 < nrows && rc == SVS_OK; b0 += B) {
+    const int nb = (int)std::min<int64_t>(B, nrows - b0);
+    const uint32_t* list = c->nb_list_dev + b0;
+    SearchPlan plan;
+    if ((rc = plan_search(idx, c, nb, kk, kk, st, true, variant, &plan)) != SVS_OK) break;
+    launch_rows_as_queries(idx, list, nb, c->q_dev, st);
+    if ((rc = enqueue_prefix(idx, c, plan, c->q_dev, st)) == SVS_OK) rc = enqueue_main(idx, c, plan, c->q_dev, c->nb_s, c->nb_r, st);
+    if (rc != SVS_OK) {
+      if (plan.timed && plan.ev.e0) {   // (a failed search keeps no events)
+        std::lock_guard<std::mutex> lk(idx->mu);
+        bool kept = false;
+        for (auto& t : idx->evs) kept = kept || t.e0 == plan.ev.e0;
+        if (!kept) ev_destroy(plan.ev);
+      }
+      break;
+    }
+    launch_drop_self(idx, c->nb_s, c->nb_r, list, nb, count, c->out_s_pin + (size_t)b0 * count, c->out_r_pin + (size_t)b0 * count, st);
+  }
+  if (rc == SVS_OK) {
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) rc = fail(SVS_ERR_DEVICE, "neighbors launch: %s", hipGetErrorString(e));
+  }
+  if (rc != SVS_OK) {
+    (void)hipStreamSynchronize(st);
+    return rc;
+  }
+  HIP_TRY(hipStreamSynchronize(st));
+  // Positions whose fused candidate list overflowed (slot 0 == -2): re-run through the materialised path in the groups
+  // search_host would form for the block (same composition, so the same kernels and the same bits).  There is no host
+  // copy of the queries: the group's rows are turned into a panel of its own.
+  constexpr int REDO_BATCH = 256;
+  const int redo_max = (int)std::min<int64_t>(REDO_BATCH, std::max<int64_t>(1, ((int64_t)2 << 30) / (4 * std::max<int64_t>(n, 1))));
+  int n_redo = 0;
+  for (int64_t b0 = 0; b0 < nrows; b0 += B) {
+    const int64_t b1 = std::min<int64_t>(b0 + B, nrows);
+    for (int64_t q0 = b0; q0 < b1;) {
+      int64_t grp[REDO_BATCH];
+      int m = 0;
+      for (; q0 < b1 && m < redo_max; ++q0)
+        if (c->out_r_pin[(size_t)q0 * count] == -2) grp[m++] = q0;
+      if (m == 0) break;
+      n_redo += m;
+      if ((rc = c->redo_s_pin.grow((size_t)REDO_BATCH * count)) != SVS_OK || (rc = c->redo_r_pin.grow((size_t)REDO_BATCH * count)) != SVS_OK) return rc;
+      if ((rc = c->nb_redo_pin.grow(REDO_BATCH)) != SVS_OK || (rc = c->nb_redo_dev.grow(REDO_BATCH)) != SVS_OK) return rc;
+      if ((rc = c->nb_redo_q.grow((size_t)REDO_BATCH * d)) != SVS_OK) return rc;
+      for (int j = 0; j < m; ++j) c->nb_redo_pin[j] = c->nb_list_pin[grp[j]];
+      HIP_TRY(hipMemcpyAsync(c->nb_redo_dev, c->nb_redo_pin, (size_t)m * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+      launch_rows_as_queries(idx, c->nb_redo_dev, m, c->nb_redo_q, st);
+      if ((rc = enqueue_search(idx, c, c->nb_redo_q, m, kk, kk, c->nb_s, c->nb_r, st, false)) != SVS_OK) {
+        (void)hipStreamSynchronize(st);
+        return rc;
+      }
+      launch_drop_self(idx, c->nb_s, c->nb_r, c->nb_redo_dev, m, count, c->redo_s_pin, c->redo_r_pin, st);
+      HIP_TRY(hipGetLastError());
+      HIP_TRY(hipStreamSynchronize(st));
+      for (int j = 0; j < m; ++j) {
+        memcpy(c->out_s_pin + (size_t)grp[j] * count, c->redo_s_pin + (size_t)j * count, (size_t)count * sizeof(float));
+        memcpy(c->out_r_pin + (size_t)grp[j] * count, c->redo_r_pin + (size_t)j * count, (size_t)count * sizeof(int64_t));
+      }
+    }
+  }
+  g_host_phase[5] = (double)n_redo;
+  if (count == k) {
+    memcpy(out_scores, c->out_s_pin, on * sizeof(float));
+    memcpy(out_rows, c->out_r_pin, on * sizeof(int64_t));
+    return SVS_OK;
+  }
+  for (int64_t qi = 0; qi < nrows; ++qi) {
+    memcpy(out_scores + (size_t)qi * k, c->out_s_pin + (size_t)qi * count, (size_t)count * sizeof(float));
+    memcpy(out_rows + (size_t)qi * k, c->out_r_pin + (size_t)qi * count, (size_t)count * sizeof(int64_t));
   }
   return SVS_OK;
 }

@@ -293,6 +293,30 @@ class DeviceIndex:
         s, r = self.search_batch_within(q[None, :], n, rows)
         return list(zip(s[0].astype(np.float64).tolist(), r[0].tolist()))
 
+    def neighbors(self, rows, n: int) -> Tuple[np.ndarray, np.ndarray]:
+        """The ``n`` nearest stored rows of each listed stored row (GLOBAL indices, any order, repeats allowed), the
+        row itself excluded: (scores f32 (len(rows), count), rows i64 (len(rows), count)), count = min(max(n, 0),
+        live rows - 1), each row ordered (score desc, row desc) -- ``get_top_k(np.dot(M, M[r]), n + 1)`` without
+        r, for every r, on the device (svs_index_neighbors).  A tombstoned or out-of-range row is a ValueError."""
+        assert isinstance(n, int)
+        r = np.ascontiguousarray(rows, dtype=np.int64).reshape(-1)
+        h = self._pinned_handle()
+        try:
+            # (clamped before allocating and before the int32 argument, as in search_batch)
+            info = _native.IndexInfo()
+            _native.check(self._quick.svs_index_info(h, C.byref(info)))
+            k = min(max(n, 0), max(int(info.n) - int(info.n_masked) - 1, 0))
+            scores = np.empty((len(r), k), dtype=np.float32)
+            out_rows = np.empty((len(r), k), dtype=np.int64)
+            count = C.c_int32(0)
+            # (the one call that releases the GIL)
+            _native.check(self._lib.svs_index_neighbors(h, r.ctypes.data, len(r), k, scores.ctypes.data, out_rows.ctypes.data,
+                                                        C.byref(count)))
+        finally:
+            self._unpin(h)
+        c = count.value
+        return (scores, out_rows) if c == k else (scores[:, :c], out_rows[:, :c])
+
     def scores(self, query_vec: np.ndarray) -> np.ndarray:
         """The raw ``np.dot(M, q)`` vector, f32 (N,)."""
         q = np.ascontiguousarray(query_vec, dtype=np.float32)

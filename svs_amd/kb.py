@@ -30,8 +30,8 @@ from typing import Any, Awaitable, Callable, Dict, Iterator, List, Optional, Tup
 import numpy as np
 
 from .index import DeviceIndex
-from .matrix import (DeviceEmbeddingsMatrix, ids_of_batch, ids_of_pairs, ids_of_rows, search_mapped, search_within_held,
-                     single_search)
+from .matrix import (DeviceEmbeddingsMatrix, ids_of_batch, ids_of_pairs, ids_of_rows, neighbors_held, search_mapped,
+                     search_within_held, single_search)
 
 _LOG = logging.getLogger(__name__)
 
@@ -192,6 +192,51 @@ class _Store:
             if doc_id not in found:
                 raise KeyError(doc_id)
         return sorted({e for e in found.values() if e is not None})
+
+    def embedding_of_doc(self, doc_id: int) -> int:
+        """The embedding id of one doc (``retrieve_similar``): KeyError(doc_id) for an unknown doc, like the
+        reference's fetch_doc; ValueError for a doc that was added without an embedding."""
+        row = self.conn.execute("SELECT embedding FROM docs WHERE id = ?", (int(doc_id),)).fetchone()
+        if row is None:
+            raise KeyError(doc_id)
+        if row[0] is None:
+            raise ValueError(f"document {doc_id} has no embedding")
+        return int(row[0])
+
+    def docs_with_embeddings(self, doc_ids: Optional[List[int]] = None) -> List[Tuple[int, int]]:
+        """[(doc_id, emb_id)] (``document_neighbors``).  None: every doc that has an embedding, in embedding-id
+        order.  A list: those docs, in the order given; KeyError(doc_id) for an unknown doc, ValueError for one
+        without an embedding."""
+        if doc_ids is None:
+            return [(int(r[0]), int(r[1])) for r in self.conn.execute(
+                "SELECT id, embedding FROM docs WHERE embedding IS NOT NULL ORDER BY embedding")]
+        ids = [int(x) for x in doc_ids]
+        found: Dict[int, Optional[int]] = {}
+        for c0 in range(0, len(ids), 500):   # stay under SQLITE_MAX_VARIABLE_NUMBER
+            chunk = ids[c0:c0 + 500]
+            marks = ",".join("?" * len(chunk))
+            for row in self.conn.execute(f"SELECT id, embedding FROM docs WHERE id IN ({marks})", chunk):
+                found[row[0]] = row[1]
+        for doc_id in ids:
+            if doc_id not in found:
+                raise KeyError(doc_id)
+            if found[doc_id] is None:
+                raise ValueError(f"document {doc_id} has no embedding")
+        return [(d, int(found[d])) for d in ids]
+
+    def doc_ids_for_embeddings(self, emb_ids: Optional[List[int]] = None) -> Dict[int, int]:
+        """{emb_id: doc_id}, ids only -- no text, no meta (``document_neighbors``: a 1M-doc graph names 100M
+        neighbours).  None: one scan over every doc that has an embedding; a list: ``IN (...)`` per 500 ids."""
+        if emb_ids is None:
+            return {int(r[0]): int(r[1]) for r in self.conn.execute(
+                "SELECT embedding, id FROM docs WHERE embedding IS NOT NULL")}
+        out: Dict[int, int] = {}
+        for c0 in range(0, len(emb_ids), 500):
+            chunk = emb_ids[c0:c0 + 500]
+            marks = ",".join("?" * len(chunk))
+            for row in self.conn.execute(f"SELECT embedding, id FROM docs WHERE embedding IN ({marks})", chunk):
+                out[int(row[0])] = int(row[1])
+        return out
 
     # -- A7: the producer of the matrix ---------------------------------------
     def build_embeddings_matrix(self) -> Tuple[np.ndarray, np.ndarray]:
@@ -420,6 +465,39 @@ class KB:
         res = [{"score": score, "doc": docs[e]} for score, e in emb_ids]
         _LOG.info(f"retrieved top {n} documents")
         return res
+
+    def retrieve_similar(self, doc_id: int, n: int) -> List[Dict[str, Any]]:
+        """"More like this": the n documents nearest to the STORED document ``doc_id``, itself excluded, shaped like
+        ``retrieve`` ([{'score', 'doc'}]).  The reference can only loop ``np.dot(M, M[i])`` + ``get_top_k``
+        (src/svs/kb.py:1623, src/svs/util.py:190-203); here the stored row is the query on the device
+        (svs_index_neighbors).  An unknown doc raises KeyError, a doc without an embedding ValueError."""
+        _LOG.info(f"retrieving {n} documents similar to document {doc_id}")
+        assert self.db is not None
+        self.embeddings_matrix.get_sync(self.db)
+        with self.db.transaction():
+            emb = self.db.embedding_of_doc(doc_id)
+        emb_ids = self.embeddings_matrix.neighbors([emb], n)[0]          # HIP
+        _LOG.info(f"computed {self.embeddings_matrix.index.shape[0]} cosine similarities")
+        with self.db.transaction():
+            docs = self.db.fetch_docs_for_embeddings([e for _, e in emb_ids])
+        res = [{"score": score, "doc": docs[e]} for score, e in emb_ids]
+        _LOG.info(f"retrieved top {n} documents")
+        return res
+
+    def document_neighbors(self, n: int, doc_ids: Optional[List[int]] = None) -> List[Tuple[int, List[Tuple[float, int]]]]:
+        """The kNN graph: [(doc_id, [(score, neighbour_doc_id), ...]), ...] for the listed docs, in the order given;
+        ``doc_ids=None``: every doc that has an embedding, in embedding-id order.  Ids only, no records (feed
+        them to ``fetch`` calls or an edge store as needed).  An unknown doc raises KeyError, a listed doc without
+        an embedding ValueError."""
+        assert self.db is not None
+        self.embeddings_matrix.get_sync(self.db)
+        with self.db.transaction():
+            pairs = self.db.docs_with_embeddings(None if doc_ids is None else list(doc_ids))
+        _LOG.info(f"computing {n} neighbours of {len(pairs)} documents")
+        per_doc = self.embeddings_matrix.neighbors([e for _, e in pairs], n)   # HIP
+        with self.db.transaction():
+            doc_of = self.db.doc_ids_for_embeddings(None if doc_ids is None else sorted({e for lst in per_doc for _, e in lst}))
+        return [(d, [(s, doc_of[e]) for s, e in lst]) for (d, _), lst in zip(pairs, per_doc)]
 
     def document_top_pairwise_scores(self, n: int) -> List[Tuple[float, Dict[str, Any], Dict[str, Any]]]:
         """Reference src/svs/kb.py:1642-1671: the n most similar document pairs,
@@ -689,6 +767,69 @@ class AsyncKB:
             res = await loop.run_in_executor(None, heavy)
         _LOG.info(f"retrieved top {n} documents for {len(queries)} queries")
         return res
+
+    async def retrieve_similar(self, doc_id: int, n: int) -> List[Dict[str, Any]]:
+        """Async twin of ``KB.retrieve_similar``, structured as ``retrieve``: the SQL and the reference to the matrix
+        under the lock, svs_index_neighbors on an executor thread outside it, the docs under the lock."""
+        _LOG.info(f"retrieving {n} documents similar to document {doc_id}")
+        loop = asyncio.get_running_loop()
+        async with self._get_lock():
+            db = await self._ensure_db()
+            await self.embeddings_matrix.get(db)
+
+            def sql() -> int:
+                with db.transaction():
+                    return db.embedding_of_doc(doc_id)
+
+            emb = await loop.run_in_executor(None, sql)
+            idx, lookup = self.embeddings_matrix.hold()
+        try:
+            emb_ids = (await loop.run_in_executor(None, lambda: neighbors_held(idx, lookup, [emb], n,
+                                                                                self.embeddings_matrix.hold)))[0]
+            _LOG.info(f"computed {idx.shape[0]} cosine similarities")
+        finally:
+            idx.release()
+        async with self._get_lock():
+            db = await self._ensure_db()
+
+            def heavy() -> List[Dict[str, Any]]:
+                with db.transaction():
+                    docs = db.fetch_docs_for_embeddings([e for _, e in emb_ids])
+                return [{"score": s, "doc": docs[e]} for s, e in emb_ids]
+
+            res = await loop.run_in_executor(None, heavy)
+        _LOG.info(f"retrieved top {n} documents")
+        return res
+
+    async def document_neighbors(self, n: int, doc_ids: Optional[List[int]] = None) -> List[Tuple[int, List[Tuple[float, int]]]]:
+        """Async twin of ``KB.document_neighbors``: ids only; the native call on an executor thread outside the lock."""
+        loop = asyncio.get_running_loop()
+        ids = None if doc_ids is None else list(doc_ids)
+        async with self._get_lock():
+            db = await self._ensure_db()
+            await self.embeddings_matrix.get(db)
+
+            def sql() -> List[Tuple[int, int]]:
+                with db.transaction():
+                    return db.docs_with_embeddings(ids)
+
+            pairs = await loop.run_in_executor(None, sql)
+            idx, lookup = self.embeddings_matrix.hold()
+        try:
+            _LOG.info(f"computing {n} neighbours of {len(pairs)} documents")
+            per_doc = await loop.run_in_executor(None, lambda: neighbors_held(idx, lookup, [e for _, e in pairs], n,
+                                                                              self.embeddings_matrix.hold))
+        finally:
+            idx.release()
+        async with self._get_lock():
+            db = await self._ensure_db()
+
+            def heavy() -> Dict[int, int]:
+                with db.transaction():
+                    return db.doc_ids_for_embeddings(None if ids is None else sorted({e for lst in per_doc for _, e in lst}))
+
+            doc_of = await loop.run_in_executor(None, heavy)
+        return [(d, [(s, doc_of[e]) for s, e in lst]) for (d, _), lst in zip(pairs, per_doc)]
 
     async def document_top_pairwise_scores(self, n: int) -> List[Tuple[float, Dict[str, Any], Dict[str, Any]]]:
         """Reference src/svs/kb.py:1208-1243 (async twin of :1642-1671): the n most similar document

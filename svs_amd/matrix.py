@@ -120,6 +120,22 @@ def search_within_held(idx, lookup: _Lookup, query_vec: np.ndarray, n: int, emb_
     return search_mapped(hold if hold is not None else _no_hold, (idx, lookup), native, finish)
 
 
+def neighbors_held(idx, lookup: _Lookup, emb_ids, n: int,
+                   hold: Optional[Callable[[], tuple]] = None) -> List[List[Tuple[float, int]]]:
+    """Neighbours of stored embeddings on a held (index, lookup): ids -> rows through ``lookup.arr``,
+    ``idx.neighbors`` (svs_index_neighbors), rows -> ids: one [(score, emb_id)] list per id, in the order given.
+    KeyError for an id the loaded matrix does not hold.  ``hold`` as in ``search_within_held``: the mapping and the
+    call are repeated on a fresh (index, lookup) when a compaction renumbered the rows meanwhile."""
+    def native(idx, lookup, *_):
+        return idx, idx.neighbors(_within_rows(idx, lookup, emb_ids), n)
+
+    def finish(res, arr):
+        used, (scores, rows) = res
+        return ids_of_batch((scores, rows - int(getattr(used, "row_offset", 0))), arr)
+
+    return search_mapped(hold if hold is not None else _no_hold, (idx, lookup), native, finish)
+
+
 def _no_hold():
     raise RuntimeError("the rows of the embeddings matrix were renumbered during the search")
 
@@ -387,6 +403,16 @@ class DeviceEmbeddingsMatrix:
             return search_mapped(self.hold, held, lambda idx, lookup: idx.search_batch(query_vecs, n), ids_of_batch)
         finally:
             held[0].release()
+
+    def neighbors(self, emb_ids, n: int) -> List[List[Tuple[float, int]]]:
+        """The ``n`` nearest stored embeddings of each listed embedding id, itself excluded: one
+        [(score, emb_id)] list per id, in the order given (``KB.retrieve_similar`` / ``document_neighbors``).
+        KeyError for an id the loaded matrix does not hold."""
+        idx, lookup = self.hold()
+        try:
+            return neighbors_held(idx, lookup, emb_ids, n, self.hold)
+        finally:
+            idx.release()
 
     def top_pairs(self, n: int) -> List[Tuple[float, int, int]]:
         """``superheavy()`` of document_top_pairwise_scores (src/svs/kb.py:1650-1655):
