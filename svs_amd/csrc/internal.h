@@ -46,6 +46,13 @@ int32_t svs_internal_last_launches(const char** kernels, int64_t* rows, int32_t*
  * other searches of a run-ahead pipeline, bit 1 = the kernel reads ld query floats, so the query is copied (zero padded)
  * when the rows are padded beyond d. */
 int32_t svs_internal_single_route(int32_t dtype, int32_t d, int32_t variant, int32_t screen, char* kernel, int32_t cap, int32_t* flags);
+/* The groups in which the host re-runs the overflowed positions of [q0, q1) of a result block, pure host code: res_rows =
+ * the block's rows at stride count (a position is marked by -2 in its first entry), max = positions per group
+ * (1 .. 256; a search derives it from the index's row count).  positions[q1 - q0] gets the marked positions, group after
+ * group; sizes[q1 - q0] each group's size, *n_groups their number.  Returns the number of marked positions, or
+ * SVS_ERR_INVALID. */
+int64_t svs_internal_redo_groups(const int64_t* res_rows, int32_t count, int64_t q0, int64_t q1, int32_t max, int64_t* positions,
+                                 int64_t* sizes, int64_t* n_groups);
 /* Screened search (screen.h) on this handle, up to cap (<= 9) values: [0] queries answered from the candidate list,
  * [1] queries that took the exact whole-corpus fallback (both as the kernels last wrote them to pinned memory: drain
  * the stream first), [2] shadow: 0 none, 1 valid, 2 invalid for good (an element half cannot hold), [3] 1 = screening

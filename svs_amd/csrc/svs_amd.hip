@@ -2238,6 +2238,88 @@ int compact_index(svs_index* idx, int64_t bounce_rows, int64_t* out_old_rows, in
   return SVS_OK;
 }
 
+// ---- shared by the host-driven batched searches (search_host, svs_index_neighbors) ----------------------------------------
+// A plan that failed after plan_search created its timing events keeps none of them.
+void plan_abandon(svs_index* idx, SearchPlan& plan) {
+  if (!plan.timed || !plan.ev.e0) return;
+  std::lock_guard<std::mutex> lk(idx->mu);
+  bool kept = false;
+  for (auto& t : idx->evs) kept = kept || t.e0 == plan.ev.e0;
+  if (!kept) ev_destroy(plan.ev);
+}
+
+// Positions per pass of the re-run; fewer where the pass's score matrix would exceed 2 GiB: 256 at 1M rows, 53 at 10M.
+// (Rounds 2-3 re-ran them one by one through the single-query kernels: 0.9 ms each at 1M rows, ~1 s for a 1024-query batch
+//  over a corpus sorted by similarity, against 3 ms normally; in passes of 64 the same call took 55 ms, of 256: see DESIGN 4.)
+constexpr int REDO_BATCH = 256;
+
+// The next group of overflowed positions (first result row -2; results at stride `count`) in [*q, q1): up to `max`, ascending,
+// into grp.  *q ends behind the last position looked at; 0 = none is left.  No HIP in it: svs_internal_redo_groups.
+int next_redo_group(const int64_t* res_rows, int count, int64_t* q, int64_t q1, int max, int64_t* grp) {
+  int m = 0;
+  for (; *q < q1 && m < max; ++*q)
+    if (res_rows[(size_t)*q * count] == -2) grp[m++] = *q;
+  return m;
+}
+
+// Positions [q0, q1) of the pinned result block whose fused candidate list overflowed (rows ordered by similarity to the
+// query, so that the prefix's threshold cuts nothing): exact re-run through the MATERIALISED path, group by group, kk results
+// per query.  stage(grp, m) puts the group's queries into q_buf; the search writes tmp_s / tmp_r and finish(m) enqueues what
+// moves them into redo_s_pin / redo_r_pin -- tmp_s null: the search writes there itself.  *n_redo grows by the positions re-run.
+template <class Stage, class Finish>
+int rerun_overflowed(svs_index* idx, Ctx* c, int64_t q0, int64_t q1, int count, int kk, const DevBuf<float>& q_buf, float* tmp_s,
+                     int64_t* tmp_r, Stage stage, Finish finish, int* n_redo) {
+  const int redo_max = (int)std::min<int64_t>(REDO_BATCH, std::max<int64_t>(1, ((int64_t)2 << 30) / (4 * std::max<int64_t>(idx->n, 1))));
+  int64_t grp[REDO_BATCH];
+  int rc;
+  while (const int m = next_redo_group(c->out_r_pin, count, &q0, q1, redo_max, grp)) {
+    *n_redo += m;
+    if ((rc = c->redo_s_pin.grow((size_t)REDO_BATCH * count)) != SVS_OK || (rc = c->redo_r_pin.grow((size_t)REDO_BATCH * count)) != SVS_OK) return rc;
+    if ((rc = stage(grp, m)) != SVS_OK) return rc;
+    if ((rc = enqueue_search(idx, c, q_buf, m, kk, kk, tmp_s ? tmp_s : c->redo_s_pin.p, tmp_s ? tmp_r : c->redo_r_pin.p, c->stream, false)) != SVS_OK) {
+      (void)hipStreamSynchronize(c->stream);
+      return rc;
+    }
+    finish(m);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    for (int j = 0; j < m; ++j) {
+      memcpy(c->out_s_pin + (size_t)grp[j] * count, c->redo_s_pin + (size_t)j * count, (size_t)count * sizeof(float));
+      memcpy(c->out_r_pin + (size_t)grp[j] * count, c->redo_r_pin + (size_t)j * count, (size_t)count * sizeof(int64_t));
+    }
+  }
+  return SVS_OK;
+}
+
+// The pinned result block (stride `count`) into the caller's (stride k)
+void deliver_results(const Ctx* c, int64_t nq, int count, int k, float* out_scores, int64_t* out_rows) {
+  if (count == k) {   // (one piece each)
+    memcpy(out_scores, c->out_s_pin, (size_t)nq * count * sizeof(float));
+    memcpy(out_rows, c->out_r_pin, (size_t)nq * count * sizeof(int64_t));
+    return;
+  }
+  for (int64_t qi = 0; qi < nq; ++qi) {
+    memcpy(out_scores + (size_t)qi * k, c->out_s_pin + (size_t)qi * count, (size_t)count * sizeof(float));
+    memcpy(out_rows + (size_t)qi * k, c->out_r_pin + (size_t)qi * count, (size_t)count * sizeof(int64_t));
+  }
+}
+
+// A caller's list of global rows: every one a row of this index.  *ascending (may be null): strictly, so that the list
+// needs neither sorting nor deduplication.
+int check_row_list(const svs_index* idx, const int64_t* rows, int64_t nrows, bool* ascending) {
+  if (nrows < 0) return fail(SVS_ERR_INVALID, "nrows must be >= 0");
+  if (nrows > 0 && !rows) return fail(SVS_ERR_INVALID, "null row list");
+  const int64_t lo = idx->row_offset, n = idx->n;
+  if (ascending) *ascending = true;
+  for (int64_t t = 0; t < nrows; ++t) {
+    const int64_t r = rows[t] - lo;
+    if (r < 0 || r >= n)
+      return fail(SVS_ERR_INVALID, "row %lld out of range [%lld, %lld)", (long long)rows[t], (long long)lo, (long long)(lo + n));
+    if (ascending && t && rows[t] <= rows[t - 1]) *ascending = false;
+  }
+  return SVS_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -2515,62 +2597,27 @@ static int32_t search_host(svs_index* idx, const float* queries, int32_t nq, int
   stamp(2);
   if (rc != SVS_OK) {
     (void)hipStreamSynchronize(c->stream);
-    if (plan.timed && plan.ev.e0) {   // (a failed search keeps no events)
-      std::lock_guard<std::mutex> lk(idx->mu);
-      bool kept = false;
-      for (auto& t : idx->evs) kept = kept || t.e0 == plan.ev.e0;
-      if (!kept) ev_destroy(plan.ev);
-    }
+    plan_abandon(idx, plan);
     return rc;
   }
   HIP_TRY(hipStreamSynchronize(c->stream));
   stamp(3);
-  // Queries whose fused candidate list overflowed (marked row -2; rows ordered by similarity to the query, so that the
-  // prefix's threshold cuts nothing): exact re-run through the MATERIALISED path, up to REDO_BATCH of them per pass.
-  // (Rounds 2-3 re-ran them one by one through the single-query kernels: 0.9 ms each at 1M rows, ~1 s for a 1024-query
-  //  batch over a corpus sorted that way, against 3 ms normally; in passes of 64 the same call took 55 ms, of 256: see
-  //  DESIGN 4.)  A pass's score matrix is kept under 2 GiB: 256 queries at 1M rows, 53 at 10M.
-  constexpr int REDO_BATCH = 256;
-  const int redo_max = (int)std::min<int64_t>(REDO_BATCH, std::max<int64_t>(1, ((int64_t)2 << 30) / (4 * std::max<int64_t>(idx->n, 1))));
-  int n_redo = 0;
-  for (int q0 = 0; q0 < nq;) {
-    int grp[REDO_BATCH], m = 0;
-    for (; q0 < nq && m < redo_max; ++q0)
-      if (c->out_r_pin[(size_t)q0 * count] == -2) grp[m++] = q0;
-    if (m == 0) break;
-    n_redo += m;
-    if ((rc = c->redo_s_pin.grow((size_t)REDO_BATCH * count)) != SVS_OK || (rc = c->redo_r_pin.grow((size_t)REDO_BATCH * count)) != SVS_OK) return rc;
-    // (the group's queries go to the front of q_dev in ONE copy -- whatever the main pass kept there is no longer needed,
-    //  the pinned buffer still holds every query of the call; a group that is not one run of queries is gathered first)
+  // The group's queries go to the front of q_dev in ONE copy -- whatever the main pass kept there is no longer needed, the
+  // pinned buffer still holds every query of the call; a group that is not one run of queries is gathered first.
+  auto stage = [&](const int64_t* grp, int m) -> int {
     const float* src = c->q_pin + (size_t)grp[0] * d;
     if (grp[m - 1] - grp[0] != m - 1) {
-      if ((rc = c->redo_q_pin.grow((size_t)REDO_BATCH * d)) != SVS_OK) return rc;
+      if (int rc = c->redo_q_pin.grow((size_t)REDO_BATCH * d); rc != SVS_OK) return rc;
       for (int j = 0; j < m; ++j) memcpy(c->redo_q_pin + (size_t)j * d, c->q_pin + (size_t)grp[j] * d, (size_t)d * sizeof(float));
       src = c->redo_q_pin;
     }
     HIP_TRY(hipMemcpyAsync(c->q_dev, src, (size_t)m * d * sizeof(float), hipMemcpyHostToDevice, c->stream));
-    if ((rc = enqueue_search(idx, c, c->q_dev, m, count, count, c->redo_s_pin, c->redo_r_pin, c->stream, false)) != SVS_OK) {
-      (void)hipStreamSynchronize(c->stream);
-      return rc;
-    }
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    for (int j = 0; j < m; ++j) {
-      memcpy(c->out_s_pin + (size_t)grp[j] * count, c->redo_s_pin + (size_t)j * count, (size_t)count * sizeof(float));
-      memcpy(c->out_r_pin + (size_t)grp[j] * count, c->redo_r_pin + (size_t)j * count, (size_t)count * sizeof(int64_t));
-    }
-  }
-  g_host_phase[5] = (double)n_redo;   // (svs_internal_host_phases: queries of this call that were re-run)
-  // device layout has stride `count`; the caller's has stride k
-  if (count == k) {   // (one piece each)
-    memcpy(out_scores, c->out_s_pin, on * sizeof(float));
-    memcpy(out_rows, c->out_r_pin, on * sizeof(int64_t));
-    stamp(4);
     return SVS_OK;
-  }
-  for (int qi = 0; qi < nq; ++qi) {
-    memcpy(out_scores + (size_t)qi * k, c->out_s_pin + (size_t)qi * count, (size_t)count * sizeof(float));
-    memcpy(out_rows + (size_t)qi * k, c->out_r_pin + (size_t)qi * count, (size_t)count * sizeof(int64_t));
-  }
+  };
+  int n_redo = 0;
+  if ((rc = rerun_overflowed(idx, c, 0, nq, count, count, c->q_dev, nullptr, nullptr, stage, [](int) {}, &n_redo)) != SVS_OK) return rc;
+  g_host_phase[5] = (double)n_redo;   // (svs_internal_host_phases: queries of this call that were re-run)
+  deliver_results(c, nq, count, k, out_scores, out_rows);
   stamp(4);
   return SVS_OK;
 }
@@ -2904,16 +2951,9 @@ int32_t svs_index_search_rows(svs_index* idx, const float* queries, int32_t nq, 
   std::shared_lock<std::shared_mutex> geo(idx->rw);
   int rc = check_query_args(idx, queries, nq, d);
   if (rc != SVS_OK) return rc;
-  if (nrows < 0) return fail(SVS_ERR_INVALID, "nrows must be >= 0");
-  if (nrows > 0 && !rows) return fail(SVS_ERR_INVALID, "null row list");
-  const int64_t lo = idx->row_offset, n = idx->n;
-  bool ascending = true;   // (strictly: then the list needs neither sorting nor deduplication)
-  for (int64_t t = 0; t < nrows; ++t) {
-    const int64_t r = rows[t] - lo;
-    if (r < 0 || r >= n)
-      return fail(SVS_ERR_INVALID, "row %lld out of range [%lld, %lld)", (long long)rows[t], (long long)lo, (long long)(lo + n));
-    if (t && rows[t] <= rows[t - 1]) ascending = false;
-  }
+  const int64_t lo = idx->row_offset;
+  bool ascending;
+  if ((rc = check_row_list(idx, rows, nrows, &ascending)) != SVS_OK) return rc;
   if (nq == 0 || nrows == 0 || k <= 0) return SVS_OK;
   if (!out_scores || !out_rows) return fail(SVS_ERR_INVALID, "null output");
   HIP_TRY(hipSetDevice(idx->device));
@@ -2981,19 +3021,13 @@ int32_t svs_index_search_rows(svs_index* idx, const float* queries, int32_t nq, 
     return rc;
   }
   HIP_TRY(hipStreamSynchronize(st));
-  // positions in S -> global rows; device layout has stride `count`, the caller's stride k
-  for (int qi = 0; qi < nq; ++qi) {
-    const float* ss = c->out_s_pin + (size_t)qi * count;
-    const int64_t* pp = c->out_r_pin + (size_t)qi * count;
-    float* ds = out_scores + (size_t)qi * k;
-    int64_t* dr = out_rows + (size_t)qi * k;
-    memcpy(ds, ss, (size_t)count * sizeof(float));
-    for (int i = 0; i < count; ++i) {
-      const int64_t p = pp[i];
-      if (p < 0 || p >= m) return fail(SVS_ERR_DEVICE, "search_rows: position %lld outside the %lld listed rows", (long long)p, (long long)m);
-      dr[i] = (int64_t)S[p] + lo;
-    }
+  // positions in S -> global rows, in the pinned block
+  for (size_t i = 0; i < on; ++i) {
+    const int64_t p = c->out_r_pin[i];
+    if (p < 0 || p >= m) return fail(SVS_ERR_DEVICE, "search_rows: position %lld outside the %lld listed rows", (long long)p, (long long)m);
+    c->out_r_pin[i] = (int64_t)S[p] + lo;
   }
+  deliver_results(c, nq, count, k, out_scores, out_rows);
   return SVS_OK;
 }
 
@@ -3028,15 +3062,15 @@ int32_t svs_index_neighbors(svs_index* idx, const int64_t* rows, int64_t nrows, 
   if (!idx) return fail(SVS_ERR_INVALID, "null index");
   RefGuard guard(idx);
   std::shared_lock<std::shared_mutex> geo(idx->rw);
-  if (nrows < 0) return fail(SVS_ERR_INVALID, "nrows must be >= 0");
-  if (nrows > 0 && !rows) return fail(SVS_ERR_INVALID, "null row list");
   const int64_t lo = idx->row_offset, n = idx->n;
-  for (int64_t t = 0; t < nrows; ++t) {
+  // (the first offending row of the list decides the error: a tombstoned row in front of the first row out of range wins)
+  for (int64_t t = 0; rows && t < nrows; ++t) {
     const int64_t r = rows[t] - lo;
-    if (r < 0 || r >= n)
-      return fail(SVS_ERR_INVALID, "row %lld out of range [%lld, %lld)", (long long)rows[t], (long long)lo, (long long)(lo + n));
+    if (r < 0 || r >= n) break;
     if (idx->dead_flag[(size_t)r]) return fail(SVS_ERR_INVALID, "row %lld is tombstoned: it has no neighbours", (long long)rows[t]);
   }
+  int rc = check_row_list(idx, rows, nrows, nullptr);
+  if (rc != SVS_OK) return rc;
   const int64_t live = n - (int64_t)idx->dead_list.size();
   const int count = (int)std::min<int64_t>(std::max(k, 0), std::max<int64_t>(live - 1, 0));
   if (out_count) *out_count = count;
@@ -3044,7 +3078,6 @@ int32_t svs_index_neighbors(svs_index* idx, const int64_t* rows, int64_t nrows, 
   if (!out_scores || !out_rows) return fail(SVS_ERR_INVALID, "null output");
   if (idx->d == 0) return fail(SVS_ERR_SHAPE, "an index of dimension 0 has no scores");
   HIP_TRY(hipSetDevice(idx->device));
-  int rc;
   if ((rc = staging_wait(idx)) != SVS_OK) return rc;
   Ctx* c = nullptr;
   if ((rc = ctx_acquire(idx, nullptr, true, &c)) != SVS_OK) return rc;
@@ -3071,12 +3104,7 @@ int32_t svs_index_neighbors(svs_index* idx, const int64_t* rows, int64_t nrows, 
     launch_rows_as_queries(idx, list, nb, c->q_dev, st);
     if ((rc = enqueue_prefix(idx, c, plan, c->q_dev, st)) == SVS_OK) rc = enqueue_main(idx, c, plan, c->q_dev, c->nb_s, c->nb_r, st);
     if (rc != SVS_OK) {
-      if (plan.timed && plan.ev.e0) {   // (a failed search keeps no events)
-        std::lock_guard<std::mutex> lk(idx->mu);
-        bool kept = false;
-        for (auto& t : idx->evs) kept = kept || t.e0 == plan.ev.e0;
-        if (!kept) ev_destroy(plan.ev);
-      }
+      plan_abandon(idx, plan);
       break;
     }
     launch_drop_self(idx, c->nb_s, c->nb_r, list, nb, count, c->out_s_pin + (size_t)b0 * count, c->out_r_pin + (size_t)b0 * count, st);
@@ -3090,50 +3118,24 @@ int32_t svs_index_neighbors(svs_index* idx, const int64_t* rows, int64_t nrows, 
     return rc;
   }
   HIP_TRY(hipStreamSynchronize(st));
-  // Positions whose fused candidate list overflowed (slot 0 == -2): re-run through the materialised path in the groups
-  // search_host would form for the block (same composition, so the same kernels and the same bits).  There is no host
-  // copy of the queries: the group's rows are turned into a panel of its own.
-  constexpr int REDO_BATCH = 256;
-  const int redo_max = (int)std::min<int64_t>(REDO_BATCH, std::max<int64_t>(1, ((int64_t)2 << 30) / (4 * std::max<int64_t>(n, 1))));
-  int n_redo = 0;
-  for (int64_t b0 = 0; b0 < nrows; b0 += B) {
-    const int64_t b1 = std::min<int64_t>(b0 + B, nrows);
-    for (int64_t q0 = b0; q0 < b1;) {
-      int64_t grp[REDO_BATCH];
-      int m = 0;
-      for (; q0 < b1 && m < redo_max; ++q0)
-        if (c->out_r_pin[(size_t)q0 * count] == -2) grp[m++] = q0;
-      if (m == 0) break;
-      n_redo += m;
-      if ((rc = c->redo_s_pin.grow((size_t)REDO_BATCH * count)) != SVS_OK || (rc = c->redo_r_pin.grow((size_t)REDO_BATCH * count)) != SVS_OK) return rc;
-      if ((rc = c->nb_redo_pin.grow(REDO_BATCH)) != SVS_OK || (rc = c->nb_redo_dev.grow(REDO_BATCH)) != SVS_OK) return rc;
-      if ((rc = c->nb_redo_q.grow((size_t)REDO_BATCH * d)) != SVS_OK) return rc;
-      for (int j = 0; j < m; ++j) c->nb_redo_pin[j] = c->nb_list_pin[grp[j]];
-      HIP_TRY(hipMemcpyAsync(c->nb_redo_dev, c->nb_redo_pin, (size_t)m * sizeof(uint32_t), hipMemcpyHostToDevice, st));
-      launch_rows_as_queries(idx, c->nb_redo_dev, m, c->nb_redo_q, st);
-      if ((rc = enqueue_search(idx, c, c->nb_redo_q, m, kk, kk, c->nb_s, c->nb_r, st, false)) != SVS_OK) {
-        (void)hipStreamSynchronize(st);
-        return rc;
-      }
-      launch_drop_self(idx, c->nb_s, c->nb_r, c->nb_redo_dev, m, count, c->redo_s_pin, c->redo_r_pin, st);
-      HIP_TRY(hipGetLastError());
-      HIP_TRY(hipStreamSynchronize(st));
-      for (int j = 0; j < m; ++j) {
-        memcpy(c->out_s_pin + (size_t)grp[j] * count, c->redo_s_pin + (size_t)j * count, (size_t)count * sizeof(float));
-        memcpy(c->out_r_pin + (size_t)grp[j] * count, c->redo_r_pin + (size_t)j * count, (size_t)count * sizeof(int64_t));
-      }
-    }
-  }
-  g_host_phase[5] = (double)n_redo;
-  if (count == k) {
-    memcpy(out_scores, c->out_s_pin, on * sizeof(float));
-    memcpy(out_rows, c->out_r_pin, on * sizeof(int64_t));
+  // Overflowed positions: rerun_overflowed block by block, so in the groups search_host forms for the block (the same
+  // kernels, the same bits).  There is no host copy of the queries: the group's rows are turned into a panel of its own,
+  // and the search's count + 1 results per row go through drop_self like the block's.
+  auto stage = [&](const int64_t* grp, int m) -> int {
+    int rc;
+    if ((rc = c->nb_redo_pin.grow(REDO_BATCH)) != SVS_OK || (rc = c->nb_redo_dev.grow(REDO_BATCH)) != SVS_OK) return rc;
+    if ((rc = c->nb_redo_q.grow((size_t)REDO_BATCH * d)) != SVS_OK) return rc;
+    for (int j = 0; j < m; ++j) c->nb_redo_pin[j] = c->nb_list_pin[grp[j]];
+    HIP_TRY(hipMemcpyAsync(c->nb_redo_dev, c->nb_redo_pin, (size_t)m * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+    launch_rows_as_queries(idx, c->nb_redo_dev, m, c->nb_redo_q, st);
     return SVS_OK;
-  }
-  for (int64_t qi = 0; qi < nrows; ++qi) {
-    memcpy(out_scores + (size_t)qi * k, c->out_s_pin + (size_t)qi * count, (size_t)count * sizeof(float));
-    memcpy(out_rows + (size_t)qi * k, c->out_r_pin + (size_t)qi * count, (size_t)count * sizeof(int64_t));
-  }
+  };
+  auto finish = [&](int m) { launch_drop_self(idx, c->nb_s, c->nb_r, c->nb_redo_dev, m, count, c->redo_s_pin, c->redo_r_pin, st); };
+  int n_redo = 0;
+  for (int64_t b0 = 0; b0 < nrows; b0 += B)
+    if ((rc = rerun_overflowed(idx, c, b0, std::min<int64_t>(b0 + B, nrows), count, kk, c->nb_redo_q, c->nb_s, c->nb_r, stage, finish, &n_redo)) != SVS_OK) return rc;
+  g_host_phase[5] = (double)n_redo;
+  deliver_results(c, nrows, count, k, out_scores, out_rows);
   return SVS_OK;
 }
 
@@ -3263,6 +3265,19 @@ int32_t svs_internal_tune(int32_t what, int64_t value) {
 int32_t svs_internal_host_phases(double* out, int32_t n) {
   for (int i = 0; i < n && i < 6; ++i) out[i] = g_host_phase[i];
   return SVS_OK;
+}
+
+int64_t svs_internal_redo_groups(const int64_t* res_rows, int32_t count, int64_t q0, int64_t q1, int32_t max, int64_t* positions,
+                                 int64_t* sizes, int64_t* n_groups) {
+  if (!res_rows || count < 1 || q0 < 0 || q1 < q0 || max < 1 || max > REDO_BATCH || !positions || !sizes || !n_groups)
+    return fail(SVS_ERR_INVALID, "svs_internal_redo_groups: 0 <= q0 <= q1, count >= 1, 1 <= max <= %d", REDO_BATCH);
+  int64_t found = 0, groups = 0;
+  while (const int m = next_redo_group(res_rows, count, &q0, q1, max, positions + found)) {
+    sizes[groups++] = m;
+    found += m;
+  }
+  *n_groups = groups;
+  return found;
 }
 
 int32_t svs_internal_single_route(int32_t dtype, int32_t d, int32_t variant, int32_t screen, char* kernel, int32_t cap, int32_t* flags) {

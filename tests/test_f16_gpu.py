@@ -114,6 +114,52 @@ def test_f16_fused_overflow_falls_back_exactly(gpu, first_rows_thresholds):
     idx.release()
 
 
+def test_f16_scattered_overflowing_queries_are_gathered_and_scattered_back(gpu, first_rows_thresholds):
+    """The re-run group that is NOT one run of queries: the adversarial query at positions 0, 5, 17 and 31 of a 32-query
+    batch (first, last, two in the middle, no two adjacent) is gathered into one group, re-run through the materialised
+    path and scattered back -- into those four slots alone: their neighbours 4, 6 and 30 keep, bit for bit, what the same
+    call gives them when nothing overflows."""
+    import ctypes as C
+    from batch_kernel_table import NF1
+    from svs_amd import DeviceIndex, _native
+    CAND_CAP, PREFIX = 32768, 16384
+    rng = np.random.default_rng(11)
+    n, d, nq, k = NF1, 64, 32, 50                           # NF1 >= 8 * PREFIX: the fused path
+    hot, near = (0, 5, 17, 31), (4, 6, 30)
+    u = rng.standard_normal(d); u /= np.linalg.norm(u)
+    v = rng.standard_normal((n, d)); v -= np.outer(v @ u, u); v /= np.linalg.norm(v, axis=1, keepdims=True)
+    c = np.linspace(0.05, 0.95, n)[:, None]                 # cosine to u grows with the row
+    m = (c * u[None, :] + np.sqrt(1 - c * c) * v).astype(np.float32)
+    plain = rng.standard_normal((nq, d)); plain /= np.linalg.norm(plain, axis=1, keepdims=True)
+    plain = plain.astype(np.float32)
+    qs = plain.copy()
+    qs[list(hot)] = u
+    md = _deq(m)
+    # the construction, on the CPU: rows that beat the k-th best score of the threshold prefix (the first 16,384 rows)
+    sc = md @ _deq(qs).T
+    passing = (sc > np.sort(sc[:PREFIX], axis=0)[-k]).sum(axis=0)
+    assert all(passing[q] > 2 * CAND_CAP for q in hot), passing
+    assert all(passing[q] < CAND_CAP // 2 for q in range(nq) if q not in hot), passing
+    sc = md @ _deq(plain).T
+    assert ((sc > np.sort(sc[:PREFIX], axis=0)[-k]).sum(axis=0) < CAND_CAP // 2).all()
+    idx = DeviceIndex(m, dtype="f16")
+    ph = (C.c_double * 6)()
+    bs, br = idx.search_batch(qs, k)
+    _native.load().svs_internal_host_phases(ph, 6)
+    assert ph[5] >= len(hot), ph[5]
+    ps, pr = idx.search_batch(plain, k)
+    _native.load().svs_internal_host_phases(ph, 6)
+    assert ph[5] == 0, ph[5]
+    idx.release()
+    for qi in hot + near:
+        qd = _deq(qs[qi])
+        exp = oracle.cpu_search(md, qd, k)
+        assert_topk_parity(bs[qi], br[qi], [s for s, _ in exp], [i for _, i in exp],
+                           oracle.cpu_scores_f64(md, qd), label=f"scattered overflow q{qi}")
+    for qi in near:
+        assert np.array_equal(bs[qi].view(np.uint32), ps[qi].view(np.uint32)) and np.array_equal(br[qi], pr[qi]), qi
+
+
 def test_f16_a_whole_batch_of_overflowing_queries_is_rerun_in_batches(gpu, first_rows_thresholds):
     """A corpus SORTED by similarity to the queries (every query's candidate list overflows): the host entry re-runs
     them through the materialised path, 64 per pass, not one single-query search each -- exact, and the call stays
