@@ -226,7 +226,7 @@ def device_memory(device: int = 0):
 def last_launches():
     """[(kernel, rows, queries)]: the score kernels this thread's last search / scores call enqueued, in order
     (svs_internal_last_launches; tests)."""
-    cap = 32
+    cap = 64   # (LAUNCH_REC_CAP of the library)
     names, rows, nq = (C.c_char_p * cap)(), (C.c_int64 * cap)(), (C.c_int32 * cap)()
     total = int(load().svs_internal_last_launches(names, rows, nq, cap))
     return [(names[i].decode(), int(rows[i]), int(nq[i])) for i in range(min(total, cap))]

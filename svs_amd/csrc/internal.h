@@ -37,7 +37,7 @@ int32_t svs_internal_host_phases(double* out, int32_t n);
  * query's launch_scores enqueued (nq = 1); a screened search lists its gemv_f16_oneshot_kernel and rescore_f32_kernel
  * without a "gemv" entry.  rows[i] is the entry's row count (a fused search's threshold pass covers fewer rows than
  * the corpus); nq[i] its query count.  A fused search whose candidate lists overflowed lists the materialised re-run's
- * launches after its own.  Up to cap entries (and at most 32) are written; returns the number of launches recorded.
+ * launches after its own.  Up to cap entries (and at most 64) are written; returns the number of launches recorded.
  * Coalesced single-query passes and svs_multi_* launch from other threads: they are not in the caller's record. */
 int32_t svs_internal_last_launches(const char** kernels, int64_t* rows, int32_t* nq, int32_t cap);
 /* The kernel a single query takes on an index of dtype and dimension d under svs_index_set_variant(variant), screened

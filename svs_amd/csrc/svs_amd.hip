@@ -115,7 +115,7 @@ struct LaunchRec {
   int64_t rows;
   int32_t nq;
 };
-constexpr int LAUNCH_REC_CAP = 32;
+constexpr int LAUNCH_REC_CAP = 64;   // (svs_index_top_pairs over 17 k rows: 17 prefix + 17 pair-mode launches)
 thread_local LaunchRec g_launch[LAUNCH_REC_CAP];
 thread_local int32_t g_nlaunch;                // launches since the reset (may exceed LAUNCH_REC_CAP: those are not kept)
 
@@ -1320,6 +1320,9 @@ int staged_rows(const svs_index* idx, int nq) {
 int launch_scores_any(svs_index* idx, Ctx* c, const float* q_dev, int64_t n_rows, int nq, float* scores, int64_t sstride,
                       FuseLaunch fl, hipStream_t st, bool restage = true) {
   int rc;
+  // The 16-query kernels have no pair mode: launch_q16_kernel does not pass fl.pairs on, so they would offer (i, i) and
+  // j < i as candidates.  svs_index_top_pairs keeps corpora that form such chunks on the materialised path.
+  if (fl.pairs.on && uses_q16(idx, nq)) return fail(SVS_ERR_INVALID, "internal: the 16-query kernels have no pair mode");
   // f32: up to 16 queries -> the 16-query streaming kernel; more -> the tiled kernel at 32
   // queries per pass (bound by the f32 MFMA rate)
   if (uses_q16(idx, nq)) {
@@ -3142,6 +3145,7 @@ int32_t svs_index_neighbors(svs_index* idx, const int64_t* rows, int64_t nrows, 
 int32_t svs_index_top_pairs(svs_index* idx, int32_t k, float* out_scores, int64_t* out_i, int64_t* out_j,
                             int32_t* out_count) {
   if (!idx) return fail(SVS_ERR_INVALID, "null index");
+  launch_reset();
   RefGuard guard(idx);
   std::shared_lock<std::shared_mutex> geo(idx->rw);
   const int64_t n = idx->n;
@@ -3161,7 +3165,9 @@ int32_t svs_index_top_pairs(svs_index* idx, int32_t k, float* out_scores, int64_
   // Small corpora: materialise n x n like the reference (src/svs/kb.py:1651).  Past n^2 = 2^32 scores
   // (or with variant 1, for A/B and tests): tiled GEMM with the i < j mask and a threshold in the
   // fused epilogue, nothing materialised but a prefix block.
-  if (n * np <= 0xffffffffll && idx->variant.load() != VARIANT_GEMV_PERSISTENT_R1)
+  // (Up to GQ rows always: the one query chunk of such a corpus would take the 16-query kernels, which have no pair mode
+  //  -- under variant 1 they returned (i, i) and both (i, j) and (j, i).)
+  if (n * np <= 0xffffffffll && (idx->variant.load() != VARIANT_GEMV_PERSISTENT_R1 || n <= GQ))
     return top_pairs_materialised(idx, c, n, count, out_scores, out_i, out_j);
   return top_pairs_tiled(idx, c, count, out_scores, out_i, out_j);
 }
