@@ -101,6 +101,8 @@ INTERNAL = {
     "svs_internal_host_phases": (C.c_int32, [C.POINTER(C.c_double), C.c_int32]),
     "svs_internal_last_launches": (C.c_int32, [C.POINTER(C.c_char_p), C.POINTER(C.c_int64), C.POINTER(C.c_int32), C.c_int32]),
     "svs_internal_single_route": (C.c_int32, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_char_p, C.c_int32, C.POINTER(C.c_int32)]),
+    "svs_internal_batch_route": (C.c_int32, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int64, C.c_int32, C.c_char_p, C.c_int32,
+                                             C.POINTER(C.c_int32)]),
     "svs_internal_redo_groups": (C.c_int64, [_P, C.c_int32, C.c_int64, C.c_int64, C.c_int32, _P, _P, C.POINTER(C.c_int64)]),
     "svs_internal_screen_stats": (C.c_int32, [_P, C.POINTER(C.c_int64), C.c_int32]),
     "svs_internal_ahead_stats": (C.c_int32, [_P, C.POINTER(C.c_int64), C.c_int32]),

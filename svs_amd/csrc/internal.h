@@ -46,6 +46,18 @@ int32_t svs_internal_last_launches(const char** kernels, int64_t* rows, int32_t*
  * other searches of a run-ahead pipeline, bit 1 = the kernel reads ld query floats, so the query is copied (zero padded)
  * when the rows are padded beyond d. */
 int32_t svs_internal_single_route(int32_t dtype, int32_t d, int32_t variant, int32_t screen, char* kernel, int32_t cap, int32_t* flags);
+/* The kernel one pass of a batch of nq >= 2 queries takes on an index of dtype and dimension d under
+ * svs_index_set_variant(variant): pure host code, no index and no device, through the dispatch that launches (batch_route,
+ * launch_batch in its name-only mode).  n_rows >= 1: the rows the pass covers (a fused search's threshold pass covers
+ * fewer than the corpus); flags: bit 0 = the fused epilogue, bit 1 = pair mode (svs_index_top_pairs).  kernel[cap] gets the
+ * name as svs_internal_last_launches spells it, "gemv" for the per-query loop of the single-query kernels.  info[3], what
+ * the call decides once for all its passes: [0] family (0 per-query loop, 1 the 16-query kernels, 2 the f32 tiled kernel,
+ * 3 the f16 / fp8 tiled and phased kernels), [1] queries per group or query tile (1 for the loop), [2] rows of the staged
+ * query image (nq rounded up to [1]).  SVS_ERR_INVALID for what no index has (dtype, d < 1, variant, nq < 2) and for pair
+ * mode on the 16-query family, which has none. */
+int32_t svs_internal_batch_route(int32_t dtype, int32_t d, int32_t variant, int32_t nq, int64_t n_rows,
+                                 int32_t flags /* bit 0 fused, bit 1 pair mode */, char* kernel, int32_t cap,
+                                 int32_t* info /* [0] family, [1] queries per tile, [2] staged rows */);
 /* The groups in which the host re-runs the overflowed positions of [q0, q1) of a result block, pure host code: res_rows =
  * the block's rows at stride count (a position is marked by -2 in its first entry), max = positions per group
  * (1 .. 256; a search derives it from the index's row count).  positions[q1 - q0] gets the marked positions, group after

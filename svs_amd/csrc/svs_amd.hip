@@ -107,8 +107,8 @@ std::atomic<int64_t> g_tune_thin{0};          // run-ahead pipelines, grid of a 
 thread_local double g_host_phase[6];          // svs_internal_host_phases: seconds since the call began (last svs_index_search on this thread)
 
 // svs_internal_last_launches: the score kernels the calling thread's last search / scores call enqueued, in order: every
-// batched launch, and for the single-query kernels a "gemv" entry per loop (launch_scores_any, svs_index_scores_n)
-// followed by the kernel of each query (launch_single).  Fixed thread-local slots and names that are compile-time
+// batched launch (launch_batched), and for the single-query kernels a "gemv" entry per loop (launch_batch,
+// svs_index_scores_n) followed by the kernel of each query (launch_single).  Fixed thread-local slots and names that are compile-time
 // constants: recording is a few stores, no allocation, no lock; entries past LAUNCH_REC_CAP are dropped.
 struct LaunchRec {
   const char* kernel;
@@ -179,6 +179,18 @@ inline void launch_single(const PassOpts& o, const char* name, int64_t rows, voi
   launch_record(name, rows, 1);
   launch_tail(o.stop, kernel, grid, block, lds, st, static_cast<A&&>(args)...);
 }
+// Every batched score launch (gemm_q16.h, gemm_tiled.h, gemm_phased.h): named only (name_only, svs_internal_batch_route:
+// before anything here touches HIP), or recorded and launched -- the first launch of a kernel raises its dynamic-LDS
+// limit to lds_max
+template <auto Kernel, class... A>
+inline void launch_batched(const char** name_only, const char* name, int lds_max, int64_t rows, int nq, dim3 grid, dim3 block, size_t lds,
+                           hipStream_t st, A... args) {
+  if (name_only) { *name_only = name; return; }
+  static std::once_flag once;
+  std::call_once(once, [&] { (void)hipFuncSetAttribute((const void*)Kernel, hipFuncAttributeMaxDynamicSharedMemorySize, lds_max); });
+  launch_record(name, rows, nq);
+  hipLaunchKernelGGL(Kernel, grid, block, lds, st, args...);
+}
 
 struct EvTriple {
   hipEvent_t e0, e1, e2;
@@ -201,7 +213,6 @@ struct Ctx {
   DevBuf<uint8_t> q8;           // e4m3 queries [rows][ld], zero padded
   DevBuf<float> q8f;            // the same values as f32 (single-query kernel)
   DevBuf<float> q8s;            // query scales
-  const float* q_f32 = nullptr; // staged f32 queries (q16 or the caller's buffer)
   DevBuf<float> pref_s;         // fused GEMM: top-k of the prefix rows (thresholds)
   DevBuf<int64_t> pref_r;
   DevBuf<float> scores;
@@ -590,18 +601,17 @@ constexpr int query_tile(int nq) { return nq <= 32 ? 32 : (nq <= 64 ? 64 : (nq <
 //   2     launch_rows           persistent grid, 2 rows per wave
 //         phased_ok             false: no phased kernel (the tiled kernels take its batches)
 //   3     launch_rows           one-shot, 2 rows x 16 waves
-//         launch_scores_q16     f32: gemm_f32_q16_kernel (16x16x4 MFMA, half-line loads) for gemm_q16r_kernel
+//         launch_q16            f32: gemm_f32_q16_kernel (16x16x4 MFMA, half-line loads) for gemm_q16r_kernel
 //   4     launch_rows           one-shot, 1 row x 16 waves, temporal loads
 //         single_route          no gemv_unrolled kernels, any dtype: the generic kernels take those rows
-//         launch_scores_q16     2048 rows per workgroup (default 1024)
-//         launch_scores_tiled   f32: 32-query tiles whatever nq
+//         launch_q16_kernel     2048 rows per workgroup (default 1024)
+//         batch_route           f32: 32-query tiles whatever nq
 //         launch_tiled_eb       f16 / fp8: no 128-query phased kernel; 128-row tiles (BM = TG_BM) at 128 / 256 queries per tile
 //   5     launch_rows           one-shot, 1 row x 8 waves
-//         launch_scores_q16     512 rows per workgroup
-//         uses_q16              f16 batches never take the q16 kernel; f32 batches take it whatever nq
-//         tiled_ok              f32: false
+//         launch_q16_kernel     512 rows per workgroup
+//         batch_route           f16 batches never take the q16 kernel; f32 batches take it whatever nq, never the tiled kernel
 //   6     plan_search           no fused epilogue
-//   7     batch_kernel_ok, tiled_ok   false: no batched kernels, a per-query gemv loop
+//   7     batch_route           no batched kernels, a per-query gemv loop
 //   8     launch_tiled_eb       fused phased kernel: LDS-DMA pieces issued with the fragment reads (EXP 30)
 //   9     launch_tiled_eb       fused phased kernel: epilogue with a branch per register (EXP 31), never the nontemporal form
 //  10     launch_tiled_eb       fused phased kernel: nontemporal corpus pieces (EXP 20) with several query tiles too
@@ -898,13 +908,42 @@ int launch_scores(const svs_index* idx, Ctx* c, const SingleRoute& r, const floa
   return launch_route(idx, c, r, staged, scores, st, o);
 }
 
-// ---- up to 16 queries per corpus pass (gemm_q16.h) ---------------------------
-bool batch_kernel_ok(const svs_index* idx) {
-  if (idx->variant.load() == VARIANT_NO_BATCH_KERNELS) return false;
-  // the query image (16 x row bytes) must fit the LDS beside the fused candidate list
-  if (idx->dtype == SVS_DTYPE_F32) return idx->ld % 128 == 0 && idx->ld <= 2304;
-  if (idx->dtype == SVS_DTYPE_F16) return idx->ld % 256 == 0 && idx->ld <= 4608;   // whole pairs of 256-byte steps
-  return false;
+// ---- the route of a batch (two or more queries): decided once per call (batch_route), staged once (stage_batch),
+// ---- launched pass by pass (launch_batch) ------------------------------------------------------------------------
+struct BatchRoute {
+  // the per-query loop of the single-query kernels (`single`), the 16-query kernels (gemm_q16.h), the f32 tiled kernel,
+  // the f16 / fp8 tiled and phased kernels (gemm_tiled.h, gemm_phased.h)
+  enum Family : uint8_t { LOOP, Q16, TILED_F32, TILED_EB } family = LOOP;
+  // the queries as the family's kernels read them, [rows()][ld] zero padded: f32 (the caller's buffer where it has that
+  // shape, else Ctx::q16), halves in Ctx::qh, e4m3 in Ctx::q8 with their scales in q8s; LOOP: launch_scores stages each
+  enum Query : uint8_t { PER_QUERY, PADDED_F32, HALF, FP8 } query = PER_QUERY;
+  int nq = 0;
+  int tile = 1;           // queries per group (Q16: GQ) or query tile (f32: 32 / 64; f16, fp8: query_tile(nq)); LOOP: 1
+  int variant = 0;        // svs_index_set_variant when the route was taken: every pass's launcher decides by THIS value
+  SingleRoute single{};   // LOOP: the route of each query
+  int rows() const { return (nq + tile - 1) / tile * tile; }   // rows of the staged image: the one statement of its padding
+};
+
+// variant: idx->variant, loaded ONCE by the entry point.  What depends on the pass -- fused or not, pair mode, phased or
+// tiled (phased_ok: n_rows) -- is resolved by launch_batch from the route and the pass's own arguments.
+BatchRoute batch_route(const svs_index* idx, int variant, int nq) {
+  using R = BatchRoute;
+  const int ld = idx->ld;
+  const bool f32 = idx->dtype == SVS_DTYPE_F32, f16 = idx->dtype == SVS_DTYPE_F16;
+  const bool kernels = nq >= 2 && variant != VARIANT_NO_BATCH_KERNELS;
+  // 16-query kernels: the query image (16 x row bytes) must fit the LDS beside the fused candidate list (f16: rows of
+  // whole pairs of 256-byte steps); tiled kernels: rows of whole 128-byte k-tiles (f32: not under variant 5, A/B)
+  const bool q16 = kernels && (f32 ? ld % 128 == 0 && ld <= 2304 : f16 && ld % 256 == 0 && ld <= 4608);
+  const bool tiled = kernels && ((size_t)ld * elem_bytes(idx)) % TG_BKB == 0 && !(f32 && variant == VARIANT_GEMV_1X8);
+  const R::Query staged = f32 ? R::PADDED_F32 : (f16 ? R::HALF : R::FP8);
+  // up to 16 queries; f32 also every batch the tiled kernel does not take; f16 under variant 5 never (tiled kernel, A/B)
+  if (q16 && (f32 ? nq <= GQ || !tiled : nq <= GQ && variant != VARIANT_GEMV_1X8)) return R{R::Q16, staged, nq, GQ, variant};
+  if (!tiled) return R{R::LOOP, R::PER_QUERY, nq, 1, variant, single_route(idx, variant, false)};
+  // exact-f32 MFMA runs at the vector rate: 32 queries per pass keep the kernel HBM-bound (62 % of the matrix pipe);
+  // larger batches are more query tiles of the same launch (grid y).  64 queries per tile from 33 queries up (256
+  // queries: 6.7 vs 7.3 ms with 32; 128-query tiles measured the same as 64: ~125 TFLOP/s of the 157 TF f32 MFMA peak)
+  if (f32) return R{R::TILED_F32, staged, nq, nq > 32 && variant != VARIANT_ALT_GEOMETRY ? 64 : 32, variant};   // (32-query tiles, A/B)
+  return R{R::TILED_EB, staged, nq, query_tile(nq), variant};
 }
 
 struct FuseLaunch {   // non-null state: fused top-k epilogue, no score matrix
@@ -926,11 +965,10 @@ struct FuseLaunch {   // non-null state: fused top-k epilogue, no score matrix
 inline const void* FuseLaunch::rows_of(const svs_index* idx) const { return rows ? rows : idx->rows; }
 inline const float* FuseLaunch::scales_of(const svs_index* idx) const { return rows ? row_scales : idx->row_scales; }
 
-// f32 queries as the batched kernels read them: [nq rounded up to `group`][ld], zero padded.
+// f32 queries as the batched kernels read them: [nq_pad][ld], zero padded (rows >= nq zero).
 // Returns the caller's buffer itself when it already has that shape.
-int stage_queries_f32(const svs_index* idx, Ctx* c, const float* q_dev, int nq, int group, const float** out, hipStream_t st) {
+int stage_queries_f32(const svs_index* idx, Ctx* c, const float* q_dev, int nq, int nq_pad, const float** out, hipStream_t st) {
   const int ld = idx->ld;
-  const int nq_pad = (nq + group - 1) / group * group;
   if (nq_pad == nq && ld == idx->d && !(((uintptr_t)q_dev) & 15)) { *out = q_dev; return SVS_OK; }
   int rc = c->q16.grow((size_t)nq_pad * ld);
   if (rc != SVS_OK) return rc;
@@ -946,183 +984,188 @@ constexpr KernelName kQ16rName = kernel_name("gemm_q16r_kernel", FUSE, EB, G4_RG
 template <bool FUSE>
 constexpr KernelName kF32Q16Name = kernel_name("gemm_f32_q16_kernel", false, 2, GEMM_PF, FUSE);
 
-// (name: the kernel as svs_internal_last_launches reports it)
-template <class K, class P>
-void launch_q16_kernel(K kernel, const char* name, const svs_index* idx, const P* rows, const P* q16, int ld_units, size_t row_bytes, int nq_g,
-                       int64_t n_rows, float* scores, int64_t sstride, int rows_per_block, FuseLaunch fl, hipStream_t st) {
-  launch_record(name, n_rows, nq_g);
-  const unsigned blocks = (unsigned)((n_rows + rows_per_block - 1) / rows_per_block);
-  const size_t lds = row_bytes * 16 + (fl.state ? GEMM_FUSE_LDS : 0);   // 16 queries x row bytes
-  hipLaunchKernelGGL(kernel, dim3(blocks), dim3(GEMM_WAVES * 64), lds, st,
-                     rows, q16, scores, n_rows, ld_units, sstride, nq_g, rows_per_block,
-                     fl.state, (int)SCR_WORDS, fl.cand, (uint32_t)CAND_CAP, fl.thr, fl.thr_stride);
-}
+// What a batched pass is launched with besides the route: the staged queries, the row range, where the scores go
+// (null with fl.state: the fused epilogue keeps candidates instead), and name -- the kernel is named, not launched
+struct BatchPass {
+  const void* q;
+  int64_t n_rows;
+  float* scores;
+  int64_t sstride;
+  FuseLaunch fl;
+  hipStream_t st;
+  const char** name;
+};
 
-// q16: 16 staged queries ([16][ld] in the corpus dtype: f32, or halves for an f16 corpus); rows [0, n_rows)
-int launch_scores_q16(const svs_index* idx, const void* q16, int nq_g, int64_t n_rows, float* scores,
-                      int64_t sstride, FuseLaunch fl, hipStream_t st) {
-  static std::once_flag once;
-  std::call_once(once, [] {
-    const int lds = 2304 * 64 + GEMM_FUSE_LDS;
-    (void)hipFuncSetAttribute((const void*)gemm_q16r_kernel<false, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-    (void)hipFuncSetAttribute((const void*)gemm_q16r_kernel<true, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-    (void)hipFuncSetAttribute((const void*)gemm_q16r_kernel<false, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-    (void)hipFuncSetAttribute((const void*)gemm_q16r_kernel<true, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-    (void)hipFuncSetAttribute((const void*)gemm_f32_q16_kernel<false, 2, GEMM_PF, false>, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-    (void)hipFuncSetAttribute((const void*)gemm_f32_q16_kernel<false, 2, GEMM_PF, true>, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-  });
-  const int variant = idx->variant.load();
+// ---- up to 16 queries per corpus pass (gemm_q16.h) ---------------------------
+// One group: q16 = 16 staged queries ([16][ld] in the corpus dtype: f32, or halves for an f16 corpus), nq_g of them real
+template <auto Kernel, class P>
+void launch_q16_kernel(const char* name, const svs_index* idx, int variant, const void* q16, int ld_units, int nq_g, float* scores,
+                       const FuseLaunch& fl, const BatchPass& p) {
   // 1024 rows (6 MB at d = 1536) per workgroup amortise the 96 KiB query staging; short
   // row ranges (the fused path's prefix) take smaller blocks so that every CU gets one.
   int rows_per_block = variant == VARIANT_ALT_GEOMETRY ? 2048 : (variant == VARIANT_GEMV_1X8 ? 512 : 1024);
-  while (rows_per_block > 64 && (n_rows + rows_per_block - 1) / rows_per_block < 512) rows_per_block /= 2;
+  while (rows_per_block > 64 && (p.n_rows + rows_per_block - 1) / rows_per_block < 512) rows_per_block /= 2;
+  const unsigned blocks = (unsigned)((p.n_rows + rows_per_block - 1) / rows_per_block);
   const size_t row_bytes = (size_t)idx->ld * elem_bytes(idx);
-  const int ld16 = (int)(row_bytes / 16);
-  with_bool(fl.state != nullptr, [&](auto fuse) {
+  const size_t lds = row_bytes * 16 + (fl.state ? GEMM_FUSE_LDS : 0);   // 16 queries x row bytes
+  launch_batched<Kernel>(p.name, name, 2304 * 64 + GEMM_FUSE_LDS, p.n_rows, nq_g, dim3(blocks), dim3(GEMM_WAVES * 64), lds, p.st,
+                         (const P*)fl.rows_of(idx), (const P*)q16, scores, p.n_rows, ld_units, p.sstride, nq_g, rows_per_block,
+                         fl.state, (int)SCR_WORDS, fl.cand, (uint32_t)CAND_CAP, fl.thr, fl.thr_stride);
+}
+
+// (Kernels are emitted in the order they are first named.  The six 16-query kernels are named here in the order the
+//  library has always had them, so that the device code keeps its layout whatever order launch_q16 reaches them in.)
+template <auto... K> struct KernelOrder {};
+using Q16KernelOrder = KernelOrder<gemm_q16r_kernel<false, 4>, gemm_q16r_kernel<true, 4>, gemm_q16r_kernel<false, 2>, gemm_q16r_kernel<true, 2>,
+                                   gemm_f32_q16_kernel<false, 2, GEMM_PF, false>, gemm_f32_q16_kernel<false, 2, GEMM_PF, true>>;
+
+// The groups of 16 of a Q16 route, one launch each
+void launch_q16(const svs_index* idx, const BatchRoute& r, const BatchPass& p) {
+  const size_t group_bytes = (size_t)GQ * idx->ld * elem_bytes(idx);
+  const int ld16 = (int)(group_bytes / GQ / 16);
+  with_bool(p.fl.state != nullptr, [&](auto fuse) {
     constexpr bool F = fuse();
-    if (idx->dtype == SVS_DTYPE_F16)
-      launch_q16_kernel(gemm_q16r_kernel<F, 2>, kQ16rName<F, 2>.s, idx, (const v4f*)fl.rows_of(idx), (const v4f*)q16, ld16, row_bytes, nq_g, n_rows, scores, sstride, rows_per_block, fl, st);
-    else if (variant == VARIANT_GEMV_2X16)   // A/B: the 16x16x4 kernel (half-line loads)
-      launch_q16_kernel(gemm_f32_q16_kernel<false, 2, GEMM_PF, F>, kF32Q16Name<F>.s, idx, (const float*)fl.rows_of(idx), (const float*)q16, idx->ld, row_bytes, nq_g, n_rows, scores, sstride, rows_per_block, fl, st);
-    else
-      launch_q16_kernel(gemm_q16r_kernel<F, 4>, kQ16rName<F, 4>.s, idx, (const v4f*)fl.rows_of(idx), (const v4f*)q16, ld16, row_bytes, nq_g, n_rows, scores, sstride, rows_per_block, fl, st);
+    for (int q0 = 0; q0 < r.nq; q0 += GQ) {
+      const void* qg = (const uint8_t*)p.q + (size_t)(q0 / GQ) * group_bytes;
+      float* sg = p.scores ? p.scores + (size_t)q0 * p.sstride : nullptr;
+      const int nq_g = std::min(GQ, r.nq - q0);
+      if (idx->dtype == SVS_DTYPE_F16)
+        launch_q16_kernel<gemm_q16r_kernel<F, 2>, v4f>(kQ16rName<F, 2>.s, idx, r.variant, qg, ld16, nq_g, sg, p.fl.at(q0), p);
+      else if (r.variant == VARIANT_GEMV_2X16)   // A/B: the 16x16x4 kernel (half-line loads)
+        launch_q16_kernel<gemm_f32_q16_kernel<false, 2, GEMM_PF, F>, float>(kF32Q16Name<F>.s, idx, r.variant, qg, idx->ld, nq_g, sg, p.fl.at(q0), p);
+      else
+        launch_q16_kernel<gemm_q16r_kernel<F, 4>, v4f>(kQ16rName<F, 4>.s, idx, r.variant, qg, ld16, nq_g, sg, p.fl.at(q0), p);
+      if (p.name) break;   // (named once: every group takes the same kernel)
+    }
   });
-  return SVS_OK;
 }
 
-// ---- LDS-tiled MFMA GEMM, f16 / fp8 corpus (gemm_tiled.h) ----------------------
-bool tiled_ok(const svs_index* idx) {
-  if (idx->variant.load() == VARIANT_NO_BATCH_KERNELS) return false;
-  if (idx->dtype == SVS_DTYPE_F32) return (idx->ld * 4) % TG_BKB == 0 && idx->variant.load() != VARIANT_GEMV_1X8;
-  if (idx->dtype == SVS_DTYPE_F16) return (idx->ld * 2) % TG_BKB == 0;
-  if (idx->dtype == SVS_DTYPE_FP8) return idx->ld % TG_BKB == 0;
-  return false;
-}
-
+// ---- LDS-tiled MFMA GEMM (gemm_tiled.h): f32 (EB 4), f16 (2), fp8 (1); nq queries at BN per tile ----------------------
 template <int BN, bool FUSE, int EB, int BM = TG_BM>
-int launch_tiled_bn(const svs_index* idx, Ctx* c, int64_t n_rows, int nq, float* scores, int64_t sstride,
-                    FuseLaunch fl, hipStream_t st) {
-  static std::once_flag once;
-  const size_t lds = (size_t)tg_lds_bytes(BM, BN);
-  std::call_once(once, [] {
-    (void)hipFuncSetAttribute((const void*)gemm_tiled_kernel<BN, FUSE, EB, BM>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                              tg_lds_bytes(BM, BN));
-  });
+void launch_tiled_bn(const svs_index* idx, const Ctx* c, int nq, const BatchPass& p) {
   static constexpr KernelName name = kernel_name("gemm_tiled_kernel", BN, FUSE, EB, BM);
-  launch_record(name.s, n_rows, nq);
-  const unsigned gx = (unsigned)((n_rows + BM - 1) / BM), gy = (unsigned)((nq + BN - 1) / BN);
-  const uint8_t* Q = EB == 2 ? (const uint8_t*)c->qh.p : (EB == 1 ? (const uint8_t*)c->q8.p : (const uint8_t*)c->q_f32);
+  const FuseLaunch& fl = p.fl;
+  const unsigned gx = (unsigned)((p.n_rows + BM - 1) / BM), gy = (unsigned)((nq + BN - 1) / BN);
   // pair mode: the row operand starts at global row fl.pairs.row_base (n_rows counts from there)
   const int64_t rb = fl.pairs.on ? fl.pairs.row_base : 0;
-  hipLaunchKernelGGL((gemm_tiled_kernel<BN, FUSE, EB, BM>), dim3(gx, gy), dim3(TG_WAVES * 64), lds, st,
-                     (const uint8_t*)fl.rows_of(idx) + (size_t)rb * idx->ld * EB, Q, scores, n_rows, (int64_t)idx->ld * EB, sstride, nq,
-                     fl.state, (int)SCR_WORDS, fl.cand, (uint32_t)CAND_CAP, fl.thr, fl.thr_stride,
-                     (const float*)(fl.scales_of(idx) ? fl.scales_of(idx) + rb : nullptr), (const float*)c->q8s, fl.pairs);
-  return SVS_OK;
+  launch_batched<gemm_tiled_kernel<BN, FUSE, EB, BM>>(
+      p.name, name.s, tg_lds_bytes(BM, BN), p.n_rows, nq, dim3(gx, gy), dim3(TG_WAVES * 64), (size_t)tg_lds_bytes(BM, BN), p.st,
+      (const uint8_t*)fl.rows_of(idx) + (size_t)rb * idx->ld * EB, (const uint8_t*)p.q, p.scores, p.n_rows, (int64_t)idx->ld * EB, p.sstride, nq,
+      fl.state, (int)SCR_WORDS, fl.cand, (uint32_t)CAND_CAP, fl.thr, fl.thr_stride,
+      (const float*)(fl.scales_of(idx) ? fl.scales_of(idx) + rb : nullptr), (const float*)c->q8s.p, fl.pairs);
 }
 
 // 256 x 256 output tiles, persistent workgroups, four-phase k-tiles (gemm_phased.h)
 template <bool FUSE, int EB, int EXP = 0, int QT = PG_TILE>
-int launch_phased(const svs_index* idx, Ctx* c, int64_t n_rows, int nq, float* scores, int64_t sstride,
-                  FuseLaunch fl, hipStream_t st) {
-  static std::once_flag once;
-  std::call_once(once, [] {
-    (void)hipFuncSetAttribute((const void*)gemm_phased_kernel<FUSE, EB, EXP, QT>, hipFuncAttributeMaxDynamicSharedMemorySize, PG_LDS_TOTAL);
-  });
+void launch_phased(const svs_index* idx, const Ctx* c, int nq, const BatchPass& p) {
   static constexpr KernelName name = kernel_name("gemm_phased_kernel", FUSE, EB, EXP, QT);
-  launch_record(name.s, n_rows, nq);
-  const int gx = (int)((n_rows + PG_TILE - 1) / PG_TILE), gy = (nq + QT - 1) / QT;
+  const FuseLaunch& fl = p.fl;
+  const int gx = (int)((p.n_rows + PG_TILE - 1) / PG_TILE), gy = (nq + QT - 1) / QT;
   const int64_t total = (int64_t)gx * gy;
   const unsigned grid = (unsigned)std::min<int64_t>(total, idx->cu_count);   // one persistent workgroup per CU
-  const uint8_t* Q = EB == 2 ? (const uint8_t*)c->qh.p : (const uint8_t*)c->q8.p;
   // pair mode: the row operand starts at global row fl.pairs.row_base (n_rows counts from there)
   const int64_t rb = fl.pairs.on ? fl.pairs.row_base : 0;
-  hipLaunchKernelGGL((gemm_phased_kernel<FUSE, EB, EXP, QT>), dim3(grid), dim3(PG_THREADS), PG_LDS_TOTAL, st,
-                     (const uint8_t*)fl.rows_of(idx) + (size_t)rb * idx->ld * EB, Q, scores, n_rows, (int)(idx->ld * EB), sstride, nq, gx, gy,
-                     fl.state, (int)SCR_WORDS, fl.cand, (uint32_t)CAND_CAP, fl.thr, fl.thr_stride,
-                     (const float*)(fl.scales_of(idx) ? fl.scales_of(idx) + rb : nullptr), (const float*)c->q8s, fl.pairs);
-  return SVS_OK;
+  launch_batched<gemm_phased_kernel<FUSE, EB, EXP, QT>>(
+      p.name, name.s, PG_LDS_TOTAL, p.n_rows, nq, dim3(grid), dim3(PG_THREADS), (size_t)PG_LDS_TOTAL, p.st,
+      (const uint8_t*)fl.rows_of(idx) + (size_t)rb * idx->ld * EB, (const uint8_t*)p.q, p.scores, p.n_rows, (int)(idx->ld * EB), p.sstride, nq, gx, gy,
+      fl.state, (int)SCR_WORDS, fl.cand, (uint32_t)CAND_CAP, fl.thr, fl.thr_stride,
+      (const float*)(fl.scales_of(idx) ? fl.scales_of(idx) + rb : nullptr), (const float*)c->q8s.p, fl.pairs);
 }
 
-// the phased kernel's preconditions: an even number (>= 6) of 128-byte k-tiles per row, tile bytes
+// the phased kernel's preconditions (f16 / fp8 rows): an even number (>= 6) of 128-byte k-tiles per row, tile bytes
 // and tile counts inside 32-bit descriptors / ints
-bool phased_ok(const svs_index* idx, int64_t n_rows, int nq) {
+bool phased_ok(const svs_index* idx, int variant, int64_t n_rows, int nq) {
   const int64_t ldb = (int64_t)idx->ld * (int64_t)elem_bytes(idx);
-  return idx->variant.load() != VARIANT_GEMV_PERSISTENT_R2 && (idx->dtype == SVS_DTYPE_F16 || idx->dtype == SVS_DTYPE_FP8) && ldb % (2 * TG_BKB) == 0 && ldb >= PG_MIN_KT * TG_BKB && ldb <= (1 << 20) &&
+  return variant != VARIANT_GEMV_PERSISTENT_R2 && ldb % (2 * TG_BKB) == 0 && ldb >= PG_MIN_KT * TG_BKB && ldb <= (1 << 20) &&
          ((n_rows + PG_TILE - 1) / PG_TILE) * ((nq + PG_TILE - 1) / PG_TILE) < (1ll << 30);
 }
 
+// A TILED_EB route's pass: phased or tiled by the pass's rows, the fused forms by the route's variant
 template <int EB>
-int launch_tiled_eb(const svs_index* idx, Ctx* c, int64_t n_rows, int nq, int bn, float* scores, int64_t sstride,
-                    FuseLaunch fl, hipStream_t st) {
-  const int variant = idx->variant.load();
-  return with_bool(fl.state != nullptr, [&](auto fuse) -> int {
+void launch_tiled_eb(const svs_index* idx, const Ctx* c, const BatchRoute& r, const BatchPass& p) {
+  const int variant = r.variant, nq = r.nq, bn = r.tile;
+  with_bool(p.fl.state != nullptr, [&](auto fuse) {
     constexpr bool F = fuse();
-    if constexpr (EB != 4) {
-      if (bn == 256 && phased_ok(idx, n_rows, nq)) {
-        if constexpr (F) {
-          if (variant == VARIANT_PHASED_DMA_WITH_READS)   // A/B: LDS-DMA pieces issued with the fragment reads
-            return launch_phased<true, EB, 30>(idx, c, n_rows, nq, scores, sstride, fl, st);
-          if (variant == VARIANT_PHASED_BRANCHY_EPILOGUE)   // A/B: fused epilogue with a branch per register
-            return launch_phased<true, EB, 31>(idx, c, n_rows, nq, scores, sstride, fl, st);
-          // One query tile (up to 256 queries): every corpus byte is used by exactly one workgroup, so its LDS-DMA
-          // pieces are issued nontemporal (EXP 20) and leave the L2 to the queries (configs[4]: 7.63 vs 7.89-8.0 ms in
-          // tools/gemm_phased_bench; with several query tiles the corpus tile is SHARED through the L2: not there).
-          if (nq <= PG_TILE || variant == VARIANT_PHASED_NONTEMPORAL)   // (nontemporal with several query tiles too, A/B)
-            return launch_phased<true, EB, 20>(idx, c, n_rows, nq, scores, sstride, fl, st);
-        }
-        return launch_phased<F, EB>(idx, c, n_rows, nq, scores, sstride, fl, st);
+    if (bn == 256 && phased_ok(idx, variant, p.n_rows, nq)) {
+      if constexpr (F) {
+        if (variant == VARIANT_PHASED_DMA_WITH_READS)   // A/B: LDS-DMA pieces issued with the fragment reads
+          return launch_phased<true, EB, 30>(idx, c, nq, p);
+        if (variant == VARIANT_PHASED_BRANCHY_EPILOGUE)   // A/B: fused epilogue with a branch per register
+          return launch_phased<true, EB, 31>(idx, c, nq, p);
+        // One query tile (up to 256 queries): every corpus byte is used by exactly one workgroup, so its LDS-DMA
+        // pieces are issued nontemporal (EXP 20) and leave the L2 to the queries (configs[4]: 7.63 vs 7.89-8.0 ms in
+        // tools/gemm_phased_bench; with several query tiles the corpus tile is SHARED through the L2: not there).
+        if (nq <= PG_TILE || variant == VARIANT_PHASED_NONTEMPORAL)   // (nontemporal with several query tiles too, A/B)
+          return launch_phased<true, EB, 20>(idx, c, nq, p);
       }
-      // 65 .. 128 queries (one query tile: the batches a coalescer forms on a reduced-precision index): the phased
-      // kernel at 128-query tiles, corpus pieces nontemporal -- HBM-bound, every corpus byte used once
-      if (bn == 128 && !fl.pairs.on && variant != VARIANT_ALT_GEOMETRY && phased_ok(idx, n_rows, nq))
-        return launch_phased<F, EB, F ? 20 : 0, 128>(idx, c, n_rows, nq, scores, sstride, fl, st);
+      return launch_phased<F, EB>(idx, c, nq, p);
     }
+    // 65 .. 128 queries (one query tile: the batches a coalescer forms on a reduced-precision index): the phased
+    // kernel at 128-query tiles, corpus pieces nontemporal -- HBM-bound, every corpus byte used once
+    if (bn == 128 && !p.fl.pairs.on && variant != VARIANT_ALT_GEOMETRY && phased_ok(idx, variant, p.n_rows, nq))
+      return launch_phased<F, EB, F ? 20 : 0, 128>(idx, c, nq, p);
     switch (bn) {
-      case 32: return launch_tiled_bn<32, F, EB>(idx, c, n_rows, nq, scores, sstride, fl, st);
+      case 32: return launch_tiled_bn<32, F, EB>(idx, c, nq, p);
       case 64:   // (256-row tiles measured 2-5 % slower here)
-        return launch_tiled_bn<64, F, EB>(idx, c, n_rows, nq, scores, sstride, fl, st);
+        return launch_tiled_bn<64, F, EB>(idx, c, nq, p);
       case 128:
         if (variant == VARIANT_ALT_GEOMETRY)   // A/B: 128-row tiles (0.87 vs 0.76 ms at 1M x 1536 f16)
-          return launch_tiled_bn<128, F, EB>(idx, c, n_rows, nq, scores, sstride, fl, st);
-        return launch_tiled_bn<128, F, EB, 256>(idx, c, n_rows, nq, scores, sstride, fl, st);
+          return launch_tiled_bn<128, F, EB>(idx, c, nq, p);
+        return launch_tiled_bn<128, F, EB, 256>(idx, c, nq, p);
       default:
         if (variant == VARIANT_ALT_GEOMETRY)   // A/B: 128-row tiles, three-stage ring
-          return launch_tiled_bn<256, F, EB>(idx, c, n_rows, nq, scores, sstride, fl, st);
-        return launch_tiled_bn<256, F, EB, 256>(idx, c, n_rows, nq, scores, sstride, fl, st);
+          return launch_tiled_bn<256, F, EB>(idx, c, nq, p);
+        return launch_tiled_bn<256, F, EB, 256>(idx, c, nq, p);
     }
   });
 }
 
-// rows [0, n_rows) of the corpus; restage == false reuses the quantised queries already staged in the context
-int launch_scores_tiled(const svs_index* idx, Ctx* c, const float* q_dev, int64_t n_rows, int nq, float* scores,
-                        int64_t sstride, FuseLaunch fl, hipStream_t st, bool restage = true) {
-  if (idx->dtype == SVS_DTYPE_F32) {
-    // exact-f32 MFMA runs at the vector rate: 32 queries per pass keep the kernel HBM-bound
-    // (62 % of the matrix pipe); larger batches are more query tiles of the same launch (grid y).
-    // 64 queries per tile from 33 queries up (256 queries: 6.7 vs 7.3 ms with 32; 128-query tiles
-    // measured the same as 64: ~125 TFLOP/s of the 157 TF f32 MFMA peak)
-    const bool wide = nq > 32 && idx->variant.load() != VARIANT_ALT_GEOMETRY;   // (32-query tiles, A/B)
-    if (restage) {
-      const float* qs = nullptr;
-      int rc = stage_queries_f32(idx, c, q_dev, nq, wide ? 64 : 32, &qs, st);
-      if (rc != SVS_OK) return rc;
-      c->q_f32 = qs;
-    }
-    return with_bool(fl.state != nullptr, [&](auto fuse) {
-      return wide ? launch_tiled_bn<64, fuse(), 4>(idx, c, n_rows, nq, scores, sstride, fl, st)
-                  : launch_tiled_bn<32, fuse(), 4>(idx, c, n_rows, nq, scores, sstride, fl, st);
-    });
+// The call's queries (q_dev: [nq][d] f32, device -- or device-visible for the half image) as the route's kernels read
+// them, once per call.  *staged: what every pass of the call is launched with.
+int stage_batch(const svs_index* idx, Ctx* c, const BatchRoute& r, const float* q_dev, hipStream_t st, const void** staged) {
+  int rc = SVS_OK;
+  const float* qs = q_dev;   // (PER_QUERY: launch_scores stages each query as r.single says)
+  switch (r.query) {
+    case BatchRoute::PER_QUERY: break;
+    case BatchRoute::PADDED_F32: rc = stage_queries_f32(idx, c, q_dev, r.nq, r.rows(), &qs, st); break;
+    case BatchRoute::HALF: rc = stage_queries_f16(idx, c, q_dev, r.nq, r.rows(), st); break;
+    case BatchRoute::FP8: rc = stage_queries_fp8(idx, c, q_dev, r.nq, r.rows(), false, st); break;
   }
-  const int bn = query_tile(nq);
-  const int nq_pad = (nq + bn - 1) / bn * bn;
-  if (restage) {
-    int rc = idx->dtype == SVS_DTYPE_F16 ? stage_queries_f16(idx, c, q_dev, nq, nq_pad, st)
-                                         : stage_queries_fp8(idx, c, q_dev, nq, nq_pad, false, st);
-    if (rc != SVS_OK) return rc;
+  *staged = r.query == BatchRoute::HALF ? (const void*)c->qh.p : (r.query == BatchRoute::FP8 ? (const void*)c->q8.p : (const void*)qs);
+  return rc;
+}
+
+// One pass of the route over rows [0, n_rows) of the corpus (or of fl.rows).  q: the queries as stage_batch left them;
+// fl.state != null: fused epilogue (batched kernels only); name (svs_internal_batch_route): the pass's kernel is named, not launched
+int launch_batch(const svs_index* idx, Ctx* c, const BatchRoute& r, const void* q, int64_t n_rows, float* scores, int64_t sstride,
+                 FuseLaunch fl, hipStream_t st, const char** name = nullptr) {
+  const BatchPass p{q, n_rows, scores, sstride, fl, st, name};
+  switch (r.family) {
+    case BatchRoute::Q16:
+      // The 16-query kernels have no pair mode: launch_q16_kernel does not pass fl.pairs on, so they would offer (i, i) and
+      // j < i as candidates.  svs_index_top_pairs keeps corpora that form such chunks on the materialised path.
+      if (fl.pairs.on) return fail(SVS_ERR_INVALID, "internal: the 16-query kernels have no pair mode");
+      launch_q16(idx, r, p);
+      break;
+    case BatchRoute::TILED_F32:
+      with_bool(fl.state != nullptr, [&](auto fuse) {
+        r.tile == 64 ? launch_tiled_bn<64, fuse(), 4>(idx, c, r.nq, p) : launch_tiled_bn<32, fuse(), 4>(idx, c, r.nq, p);
+      });
+      break;
+    case BatchRoute::TILED_EB:
+      idx->dtype == SVS_DTYPE_F16 ? launch_tiled_eb<2>(idx, c, r, p) : launch_tiled_eb<1>(idx, c, r, p);
+      break;
+    case BatchRoute::LOOP:
+      if (name) { *name = "gemv"; break; }
+      if (fl.state || n_rows != idx->n) return fail(SVS_ERR_INVALID, "internal: single-query kernels have no fused / prefix form");
+      launch_record("gemv", n_rows, r.nq);   // (one entry for the per-query loop)
+      for (int qi = 0; qi < r.nq; ++qi) {
+        const int rc = launch_scores(idx, c, r.single, (const float*)q + (size_t)qi * idx->d, scores + (size_t)qi * sstride, st);
+        if (rc != SVS_OK) return rc;
+      }
+      break;
   }
-  return idx->dtype == SVS_DTYPE_F16 ? launch_tiled_eb<2>(idx, c, n_rows, nq, bn, scores, sstride, fl, st)
-                                     : launch_tiled_eb<1>(idx, c, n_rows, nq, bn, scores, sstride, fl, st);
+  return SVS_OK;
 }
 
 // run_select's route over n_eff scores: one workgroup sorts them all; beyond SORT_CAP, up to SEL_KMAX results come from
@@ -1284,7 +1327,7 @@ int launch_gather(const svs_index* idx, Ctx* c, const float* q_dev, int nq, cons
   int rc;
   if (idx->dtype == SVS_DTYPE_F32) {
     const float* qs = nullptr;
-    if ((rc = stage_queries_f32(idx, c, q_dev, nq, 1, &qs, st)) != SVS_OK) return rc;
+    if ((rc = stage_queries_f32(idx, c, q_dev, nq, nq, &qs, st)) != SVS_OK) return rc;
     return launch_gather_dt<0>(idx, qs, nullptr, nq, list, m, scores, sstride, st);
   }
   if (idx->dtype == SVS_DTYPE_F16) {
@@ -1295,67 +1338,17 @@ int launch_gather(const svs_index* idx, Ctx* c, const float* q_dev, int nq, cons
   return launch_gather_dt<2>(idx, c->q8, c->q8s, nq, list, m, scores, sstride, st);
 }
 
+// One batch through a route of its own -- decided, staged, launched (the pair paths, chunk by chunk).  variant: the call's
+int score_batch(const svs_index* idx, Ctx* c, int variant, const float* q_dev, int nq, int64_t n_rows, float* scores, int64_t sstride,
+                FuseLaunch fl, hipStream_t st) {
+  const BatchRoute r = batch_route(idx, variant, nq);
+  const void* q = nullptr;
+  const int rc = stage_batch(idx, c, r, q_dev, st, &q);
+  return rc != SVS_OK ? rc : launch_batch(idx, c, r, q, n_rows, scores, sstride, fl, st);
+}
+
 // rows whose exact k-th best seeds the fused epilogue's thresholds: about k * n / prefix
 // candidates per query survive, so the prefix grows with n (n/64 -> ~64 k survivors)
-// Materialised scores of nq queries: scores[q][sstride] (the non-fused score stage).
-bool uses_q16(const svs_index* idx, int nq) {
-  if (nq < 2 || !batch_kernel_ok(idx)) return false;
-  if (idx->dtype == SVS_DTYPE_F16) return nq <= GQ && idx->variant.load() != VARIANT_GEMV_1X8;   // (tiled kernel, A/B)
-  return nq <= GQ || idx->variant.load() == VARIANT_GEMV_1X8 || !tiled_ok(idx);
-}
-
-// nq queries go through a batched kernel (q16 or tiled), not the per-query gemv loop: launch_scores_any's first two branches
-bool is_batched(const svs_index* idx, int nq) { return uses_q16(idx, nq) || (nq >= 2 && tiled_ok(idx)); }
-
-// Rows of the staged (half / e4m3) query image the batched kernels read for nq queries: the batch padded to the
-// query tile of the kernel that will take it (launch_scores_any / launch_scores_tiled use the same rule).
-int staged_rows(const svs_index* idx, int nq) {
-  if (uses_q16(idx, nq)) return (nq + GQ - 1) / GQ * GQ;
-  const int bn = query_tile(nq);
-  return (nq + bn - 1) / bn * bn;
-}
-
-// rows [0, n_rows); fl.state != null: fused epilogue (batched kernels only); restage == false
-// reuses the queries staged by the previous call on this context.
-int launch_scores_any(svs_index* idx, Ctx* c, const float* q_dev, int64_t n_rows, int nq, float* scores, int64_t sstride,
-                      FuseLaunch fl, hipStream_t st, bool restage = true) {
-  int rc;
-  // The 16-query kernels have no pair mode: launch_q16_kernel does not pass fl.pairs on, so they would offer (i, i) and
-  // j < i as candidates.  svs_index_top_pairs keeps corpora that form such chunks on the materialised path.
-  if (fl.pairs.on && uses_q16(idx, nq)) return fail(SVS_ERR_INVALID, "internal: the 16-query kernels have no pair mode");
-  // f32: up to 16 queries -> the 16-query streaming kernel; more -> the tiled kernel at 32
-  // queries per pass (bound by the f32 MFMA rate)
-  if (uses_q16(idx, nq)) {
-    const bool f16 = idx->dtype == SVS_DTYPE_F16;
-    if (restage) {
-      if (f16) {
-        if ((rc = stage_queries_f16(idx, c, q_dev, nq, (nq + GQ - 1) / GQ * GQ, st)) != SVS_OK) return rc;
-      } else {
-        const float* qs = nullptr;
-        if ((rc = stage_queries_f32(idx, c, q_dev, nq, GQ, &qs, st)) != SVS_OK) return rc;
-        c->q_f32 = qs;
-      }
-    }
-    for (int q0 = 0; q0 < nq; q0 += GQ) {
-      const void* qg = f16 ? (const void*)((const _Float16*)c->qh + (size_t)q0 * idx->ld) : (const void*)(c->q_f32 + (size_t)q0 * idx->ld);
-      rc = launch_scores_q16(idx, qg, std::min(GQ, nq - q0), n_rows,
-                             scores ? scores + (size_t)q0 * sstride : nullptr, sstride, fl.at(q0), st);
-      if (rc != SVS_OK) return rc;
-    }
-  } else if (is_batched(idx, nq)) {
-    if ((rc = launch_scores_tiled(idx, c, q_dev, n_rows, nq, scores, sstride, fl, st, restage)) != SVS_OK) return rc;
-  } else {
-    if (fl.state || n_rows != idx->n) return fail(SVS_ERR_INVALID, "internal: single-query kernels have no fused / prefix form");
-    launch_record("gemv", n_rows, nq);   // (one entry for the per-query loop)
-    const SingleRoute route = single_route(idx, idx->variant.load(), false);
-    for (int qi = 0; qi < nq; ++qi) {
-      rc = launch_scores(idx, c, route, q_dev + (size_t)qi * idx->d, scores + (size_t)qi * sstride, st);
-      if (rc != SVS_OK) return rc;
-    }
-  }
-  return SVS_OK;
-}
-
 constexpr int64_t FUSE_PREFIX_MIN = 16384;
 constexpr int64_t PFX_BLOCK = 256;   // rows per block of the threshold sample (one row tile of the MFMA kernels)
 inline int64_t fuse_prefix_rows(int64_t n) {
@@ -1411,9 +1404,11 @@ struct SearchPlan {
   int nq = 0, k = 0, count = 0;
   bool path_a = false, fused = false, kth = false, timed = false;
   bool screen = false;   // one query over an f32 index with a valid half shadow: screen.h
-  bool staged = false;   // the caller has staged the queries in the corpus dtype already (search_host, chunk by chunk)
   int64_t n_mat = 0, sstride = 0;
   SingleRoute route{};               // nq == 1: the score kernel, under the variant the plan was made with (single_route)
+  BatchRoute batch{};                // nq >= 2: family, query tile and staging of every pass of the call (batch_route)
+  const void* q_staged = nullptr;    // ... and the queries as its kernels read them: null until stage_batch (or search_host,
+                                     // chunk by chunk) has staged them, in front of the call's first pass
   const float* q_padded = nullptr;   // screened search: the query as launch_scores staged it (the re-score reads it)
   EvTriple ev{};
   hipEvent_t pass_stop = nullptr;    // run-ahead pipeline, one query: the event the LAST kernel of the score half is to carry (launch_tail)
@@ -1449,7 +1444,8 @@ int plan_search(svs_index* idx, Ctx* c, int nq, int k, int count, hipStream_t st
   // candidate list overflows comes back marked and is re-run by the caller.  The prefix
   // pass costs ~60 us whatever the batch: measured break-even is 16 queries (f32: 13.2 k vs
   // 12.7 k queries/s at 16, 6.4 k vs 6.5 k at 8; f16 at 32: 49 k vs 41 k; fp8 at 32: 77 k vs 64 k).
-  p->fused = allow_fused && p->path_a && is_batched(idx, nq) && nq >= 16 &&
+  if (nq != 1) p->batch = batch_route(idx, variant, nq);
+  p->fused = allow_fused && p->path_a && p->batch.family != BatchRoute::LOOP && nq >= 16 &&
              n >= 8 * FUSE_PREFIX_MIN && (int64_t)n < ((int64_t)1 << 32) &&
              count <= 256 && variant != VARIANT_NO_FUSION;
   p->screen = nq == 1 && p->path_a && screen_ready(idx) &&
@@ -1482,7 +1478,7 @@ int plan_search(svs_index* idx, Ctx* c, int nq, int k, int count, hipStream_t st
   return SVS_OK;
 }
 
-int enqueue_prefix(svs_index* idx, Ctx* c, const SearchPlan& p, const float* q_dev, hipStream_t st) {
+int enqueue_prefix(svs_index* idx, Ctx* c, SearchPlan& p, const float* q_dev, hipStream_t st) {
   if (!p.fused) return SVS_OK;
   int rc;
   const int nq = p.nq, count = p.count;
@@ -1494,7 +1490,8 @@ int enqueue_prefix(svs_index* idx, Ctx* c, const SearchPlan& p, const float* q_d
     sample.row_scales = idx->pfx_scales;
     blk_stride = idx->pfx_stride;
   }
-  if ((rc = launch_scores_any(idx, c, q_dev, p.n_mat, nq, c->scores, p.sstride, sample, st, !p.staged)) != SVS_OK) return rc;
+  if (!p.q_staged && (rc = stage_batch(idx, c, p.batch, q_dev, st, &p.q_staged)) != SVS_OK) return rc;
+  if ((rc = launch_batch(idx, c, p.batch, p.q_staged, p.n_mat, c->scores, p.sstride, sample, st)) != SVS_OK) return rc;
   if (!idx->dead_list.empty())   // thresholds must come from LIVE rows: masked sample rows -> -inf (rows outside the sample are skipped)
     hipLaunchKernelGGL(mask_dead_rows_kernel, dim3(64), dim3(256), 0, st, c->scores, p.sstride, nq, idx->dead_dev,
                        (int64_t)idx->dead_list.size(), p.n_mat, blk_stride);
@@ -1521,7 +1518,7 @@ int enqueue_score_half(svs_index* idx, Ctx* c, SearchPlan& p, const float* q_dev
       HIP_TRY(hipEventCreate(&ev.d1));
       HIP_TRY(hipEventRecord(ev.d0, st));
     }
-    if ((rc = launch_scores_any(idx, c, q_dev, n, nq, nullptr, 0, fl, st, false)) != SVS_OK) return rc;
+    if ((rc = launch_batch(idx, c, p.batch, p.q_staged, n, nullptr, 0, fl, st)) != SVS_OK) return rc;
     if (p.timed) HIP_TRY(hipEventRecord(ev.d1, st));
     if (p.timed) HIP_TRY(hipEventRecord(ev.e1, st));
     return SVS_OK;
@@ -1538,10 +1535,10 @@ int enqueue_score_half(svs_index* idx, Ctx* c, SearchPlan& p, const float* q_dev
                          (uint64_t)n, p.share_epoch, (uint64_t)idx->ld, p.share_thin ? 1 : 0);
       o = PassOpts{o.stop, &sp->share_dev->plan, sp->share_limit, p.share_thin};
     }
-    if (!p.screen) launch_record("gemv", n, 1);   // (as launch_scores_any announces its per-query loop)
+    if (!p.screen) launch_record("gemv", n, 1);   // (as launch_batch announces its per-query loop)
     rc = launch_scores(idx, c, p.route, q_dev, c->scores, st, o, &p.q_padded);
-  } else {
-    rc = launch_scores_any(idx, c, q_dev, n, nq, c->scores, p.sstride, FuseLaunch{}, st, !p.staged);
+  } else if (p.q_staged || (rc = stage_batch(idx, c, p.batch, q_dev, st, &p.q_staged)) == SVS_OK) {
+    rc = launch_batch(idx, c, p.batch, p.q_staged, n, c->scores, p.sstride, FuseLaunch{}, st);
   }
   if (rc != SVS_OK) return rc;
   if (masked)   // tombstoned rows can never be returned
@@ -1626,14 +1623,14 @@ int dequant_rows_to(svs_index* idx, int64_t r0, int64_t nrows, float* out, hipSt
 // Top `count` pairs among rows [0, ns) (ns * ns_padded <= 2^32): S = M M^T materialised, strict upper
 // triangle, the ordinary top-k stage over the flattened matrix (flat index i * np + j reproduces the
 // reference's tie order).  Results (scores, flat indices) stay on the device.
-int pairs_block_device(svs_index* idx, Ctx* c, int64_t ns, int count, float* S, float* qbuf, float* d_s, int64_t* d_r, hipStream_t st) {
+int pairs_block_device(svs_index* idx, Ctx* c, int variant, int64_t ns, int count, float* S, float* qbuf, float* d_s, int64_t* d_r, hipStream_t st) {
   const int64_t np = (ns + 3) & ~(int64_t)3;
   int rc;
   const int chunk = 1024;
   for (int64_t q0 = 0; q0 < ns; q0 += chunk) {
     const int nq = (int)std::min<int64_t>(chunk, ns - q0);
     if ((rc = dequant_rows_to(idx, q0, nq, qbuf, st)) != SVS_OK) return rc;
-    if ((rc = launch_scores_any(idx, c, qbuf, ns, nq, S + q0 * np, np, FuseLaunch{}, st)) != SVS_OK) return rc;
+    if ((rc = score_batch(idx, c, variant, qbuf, nq, ns, S + q0 * np, np, FuseLaunch{}, st)) != SVS_OK) return rc;
   }
   hipLaunchKernelGGL(mask_upper_triangle_kernel, dim3(4096), dim3(256), 0, st, S, ns, np);
   if (!idx->dead_list.empty())
@@ -1655,7 +1652,7 @@ struct DevTmp {   // frees on scope exit
   ~DevTmp() { for (void* q : p) (void)hipFree(q); }
 };
 
-int top_pairs_materialised(svs_index* idx, Ctx* c, int64_t n, int count, float* out_scores, int64_t* out_i, int64_t* out_j) {
+int top_pairs_materialised(svs_index* idx, Ctx* c, int variant, int64_t n, int count, float* out_scores, int64_t* out_i, int64_t* out_j) {
   const int64_t np = (n + 3) & ~(int64_t)3;
   hipStream_t st = c->stream;
   DevTmp tmp;
@@ -1665,7 +1662,7 @@ int top_pairs_materialised(svs_index* idx, Ctx* c, int64_t n, int count, float* 
   HIP_TRY(tmp.alloc(&S, (size_t)n * np * sizeof(float)));
   HIP_TRY(tmp.alloc(&d_s, (size_t)count * sizeof(float)));
   HIP_TRY(tmp.alloc(&d_r, (size_t)count * sizeof(int64_t)));
-  int rc = pairs_block_device(idx, c, n, count, S, qbuf, d_s, d_r, st);
+  int rc = pairs_block_device(idx, c, variant, n, count, S, qbuf, d_s, d_r, st);
   if (rc != SVS_OK) return rc;
   std::vector<int64_t> flat_rows((size_t)count);
   HIP_TRY(hipMemcpyAsync(out_scores, d_s, (size_t)count * sizeof(float), hipMemcpyDeviceToHost, st));
@@ -1686,9 +1683,12 @@ int top_pairs_materialised(svs_index* idx, Ctx* c, int64_t n, int count, float* 
 // after each chunk they are appended to one global (score, i, j) list.  (3) The host orders the
 // list by (score desc, i desc, j desc) -- the reference's flat upper-triangle index, descending --
 // and keeps `count`.  Exact; the list holds about count * (n / P)^2 pairs.
-int top_pairs_tiled(svs_index* idx, Ctx* c, int count, float* out_scores, int64_t* out_i, int64_t* out_j) {
+int top_pairs_tiled(svs_index* idx, Ctx* c, int variant, int count, float* out_scores, int64_t* out_i, int64_t* out_j) {
   const int64_t n = idx->n;
-  if (!tiled_ok(idx)) return fail(SVS_ERR_UNSUPPORTED, "pairwise scores over %lld rows need rows of whole 128-byte lines (d = %d)", (long long)n, idx->d);
+  constexpr int QC = 1024;                 // query rows per chunk
+  // (every chunk holds more than GQ queries, so all take the family of a full one: it must have a pair mode)
+  const BatchRoute::Family fam = batch_route(idx, variant, QC).family;
+  if (fam != BatchRoute::TILED_F32 && fam != BatchRoute::TILED_EB) return fail(SVS_ERR_UNSUPPORTED, "pairwise scores over %lld rows need rows of whole 128-byte lines (d = %d)", (long long)n, idx->d);
   hipStream_t st = c->stream;
   int rc;
   // prefix block: at least `count` live pairs inside it
@@ -1696,7 +1696,6 @@ int top_pairs_tiled(svs_index* idx, Ctx* c, int count, float* out_scores, int64_
   while (P < n && (P - (int64_t)idx->dead_list.size()) * (P - (int64_t)idx->dead_list.size() - 1) / 2 < count) P = std::min<int64_t>(n, P * 2);
   const int64_t Pp = (P + 3) & ~(int64_t)3;
   if (P * Pp > 0xffffffffll) return fail(SVS_ERR_UNSUPPORTED, "top_pairs: k = %d needs a prefix block past 2^32 scores", count);
-  constexpr int QC = 1024;                 // query rows per chunk
   constexpr uint32_t LIST_CAP = 8u << 20;  // global pair list (96 MB)
   DevTmp tmp;
   float *qbuf = nullptr, *S = nullptr, *d_s = nullptr;
@@ -1711,7 +1710,7 @@ int top_pairs_tiled(svs_index* idx, Ctx* c, int count, float* out_scores, int64_
   HIP_TRY(tmp.alloc(&l_i, (size_t)LIST_CAP * 4));
   HIP_TRY(tmp.alloc(&l_j, (size_t)LIST_CAP * 4));
   HIP_TRY(hipMemsetAsync(gstate, 0, 16, st));
-  if ((rc = pairs_block_device(idx, c, P, count, S, qbuf, d_s, d_r, st)) != SVS_OK) return rc;
+  if ((rc = pairs_block_device(idx, c, variant, P, count, S, qbuf, d_s, d_r, st)) != SVS_OK) return rc;
   const float* thr = d_s + (count - 1);    // the bound, read by the epilogue with stride 0
   // per-query candidate scratch for one chunk
   if ((rc = grow_select_scratch(c, QC, st)) != SVS_OK) return rc;
@@ -1722,7 +1721,7 @@ int top_pairs_tiled(svs_index* idx, Ctx* c, int count, float* out_scores, int64_
     const int64_t row_base = (qs + 1) & ~(int64_t)3;          // rows above the chunk's first query (4-aligned: fp8 row scales)
     if ((rc = dequant_rows_to(idx, qs, nq, qbuf, st)) != SVS_OK) return rc;
     FuseLaunch fl{c->hist, c->cand, thr, 0, TgPairs{(long long)qs, (long long)row_base, (long long)q0, 1}};
-    if ((rc = launch_scores_any(idx, c, qbuf, n - row_base, nq, nullptr, 0, fl, st)) != SVS_OK) return rc;
+    if ((rc = score_batch(idx, c, variant, qbuf, nq, n - row_base, nullptr, 0, fl, st)) != SVS_OK) return rc;
     hipLaunchKernelGGL(collect_pairs_kernel, dim3(nq), dim3(256), 0, st, c->hist, (const uint64_t*)c->cand, (long long)qs, (long long)q0,
                        (const uint32_t*)(idx->dead_list.empty() ? nullptr : idx->dead_bits_dev.p), gstate, LIST_CAP, l_key, l_i, l_j);
   }
@@ -2571,10 +2570,10 @@ static int32_t search_host(svs_index* idx, const float* queries, int32_t nq, int
   // ones: quantize_rows_fp8 reads its source twice -- row maximum, then the bytes -- and over the bus that cost configs[4]
   // 0.03-0.05 ms per call.  (Also measured and dropped: helper threads sharing the host copy -- their hand-offs cost what
   // they saved, 0.112 vs 0.088 ms to fill the pinned buffer; and the prefix pass per query tile, see SearchPlan.)
-  const bool pull = mode == 0 && idx->dtype == SVS_DTYPE_F16 && is_batched(idx, nq);
+  const bool pull = mode == 0 && plan.batch.query == BatchRoute::HALF;
   const float* q_src = pull ? c->q_pin.p : c->q_dev.p;
   if (pull) {
-    const int rows_total = staged_rows(idx, nq);            // the image of the WHOLE batch: sized once, before the first chunk
+    const int rows_total = plan.batch.rows();               // the image of the WHOLE batch: sized once, before the first chunk
     rc = c->qh.grow((size_t)rows_total * idx->ld);
     int cq = 256;                                           // queries per chunk: <= 1 MiB, a power of two
     while (cq > 1 && (size_t)cq * d * sizeof(float) > ((size_t)1 << 20)) cq >>= 1;
@@ -2585,7 +2584,7 @@ static int32_t search_host(svs_index* idx, const float* queries, int32_t nq, int
       // (rows [q0, q0 + nc) of the image; the last chunk also zeroes the padding rows behind the batch)
       rc = stage_queries_f16(idx, c, c->q_pin + off, nc, q0 + nc == nq ? rows_total : q0 + nc, c->stream, q0);
     }
-    plan.staged = true;
+    plan.q_staged = c->qh.p;
   } else {
     // queries -> pinned staging -> HBM, in 1 MiB pieces: the DMA of piece i runs under the host copy of piece i + 1
     for (size_t off = 0; off < qn; off += (size_t)262144) {
@@ -3167,9 +3166,10 @@ int32_t svs_index_top_pairs(svs_index* idx, int32_t k, float* out_scores, int64_
   // fused epilogue, nothing materialised but a prefix block.
   // (Up to GQ rows always: the one query chunk of such a corpus would take the 16-query kernels, which have no pair mode
   //  -- under variant 1 they returned (i, i) and both (i, j) and (j, i).)
-  if (n * np <= 0xffffffffll && (idx->variant.load() != VARIANT_GEMV_PERSISTENT_R1 || n <= GQ))
-    return top_pairs_materialised(idx, c, n, count, out_scores, out_i, out_j);
-  return top_pairs_tiled(idx, c, count, out_scores, out_i, out_j);
+  const int variant = idx->variant.load();   // (once: every chunk of either path takes its route under this value)
+  if (n * np <= 0xffffffffll && (variant != VARIANT_GEMV_PERSISTENT_R1 || n <= GQ))
+    return top_pairs_materialised(idx, c, variant, n, count, out_scores, out_i, out_j);
+  return top_pairs_tiled(idx, c, variant, count, out_scores, out_i, out_j);
 }
 
 int32_t svs_index_debug_dequant(svs_index* idx, int64_t row0, int64_t nrows, float* out) {
@@ -3299,6 +3299,27 @@ int32_t svs_internal_single_route(int32_t dtype, int32_t d, int32_t variant, int
   if (rc != SVS_OK) return rc;
   snprintf(kernel, (size_t)cap, "%s", name);
   *flags = (r.shares ? 1 : 0) | (r.query == SingleRoute::PADDED ? 2 : 0);
+  return SVS_OK;
+}
+
+int32_t svs_internal_batch_route(int32_t dtype, int32_t d, int32_t variant, int32_t nq, int64_t n_rows, int32_t flags, char* kernel, int32_t cap,
+                                 int32_t* info) {
+  if (dtype < SVS_DTYPE_F32 || dtype > SVS_DTYPE_FP8 || d < 1 || variant < VARIANT_DEFAULT || variant > VARIANT_LAST || nq < 2 || n_rows < 1 ||
+      (flags & ~3) || !kernel || cap < 1 || !info)
+    return fail(SVS_ERR_INVALID, "svs_internal_batch_route: no batch of %d queries on an index of dtype %d, d %d, variant %d", nq, dtype, d, variant);
+  svs_index shape;   // (never sees a device: the route and the launchers' names depend on dtype, d and ld alone)
+  shape.dtype = dtype; shape.d = d; shape.ld = choose_ld(d, dtype);
+  const BatchRoute r = batch_route(&shape, variant, nq);
+  Ctx ctx;
+  static uint32_t fused_state;   // (its address only: a non-null FuseLaunch::state selects the fused forms)
+  FuseLaunch fl{};
+  if (flags & 1) fl.state = &fused_state;
+  fl.pairs.on = (flags >> 1) & 1;
+  const char* name = nullptr;
+  const int rc = launch_batch(&shape, &ctx, r, nullptr, n_rows, nullptr, 0, fl, nullptr, &name);
+  if (rc != SVS_OK) return rc;
+  snprintf(kernel, (size_t)cap, "%s", name);
+  info[0] = r.family; info[1] = r.tile; info[2] = r.rows();
   return SVS_OK;
 }
 

@@ -8,8 +8,9 @@ rows) as svs_internal_last_launches and c++filt spell it; "gemv" is the per-quer
   * "materialised+norms": the same, on a corpus whose row norms span 1e-2 .. 1e2 (relative bound);
   * "fused": the fused top-k epilogue (n >= 131,072, nq >= 16, k <= 256) on a corpus with planted rows in every tile.
 
-The dispatch rules these rows follow (svs_amd/csrc/svs_amd.hip: batch_kernel_ok, uses_q16, tiled_ok, phased_ok,
-launch_tiled_eb, launch_scores_tiled, plan_search):
+The dispatch rules these rows follow (svs_amd/csrc/svs_amd.hip: batch_route decides family, query tile and staging once
+per call; launch_batch, launch_q16, launch_tiled_eb and phased_ok pick each pass's kernel from that route; plan_search
+decides fused or not; tests/test_batch_route.py asks the same dispatch for these names without a device):
   * f32: 2-16 queries and ld % 128 == 0, ld <= 2304 -> gemm_q16r_kernel<F, 4, ...>; otherwise 17-32 queries -> the
     tiled kernel at 32-query tiles, more -> 64-query tiles; rows that are not whole 128-byte lines -> gemv.
   * f16: 2-16 queries and ld % 256 == 0, ld <= 4608 -> gemm_q16r_kernel<F, 2, ...>; otherwise tiled at 32 / 64 queries;
@@ -122,6 +123,19 @@ AB_ONLY = {
     **{_tiled(bn, f, eb, 128): 4 for bn in (128, 256) for f in (False, True) for eb in (1, 2)},
     **{_phased(True, eb, exp, 256): {30: 8, 31: 9}[exp] for eb in (1, 2) for exp in (30, 31)},
 }
+
+
+def _ab_shape(kernel):
+    """(dtype, d, n, nq) that reaches `kernel` under its A/B variant (svs_amd.hip: launch_q16 variant 3,
+    launch_tiled_eb variants 4 / 8 / 9)."""
+    args = kernel[kernel.index("<") + 1:-1].split(", ")
+    if kernel.startswith("gemm_f32_q16_kernel"):
+        return "f32", 128, NF1 if args[3] == "true" else 3000, 16
+    if kernel.startswith("gemm_tiled_kernel"):      # rows of 2 k-tiles: not the phased kernel's
+        bn, fused, eb = int(args[0]), args[1] == "true", int(args[2])
+        return "f16" if eb == 2 else "fp8", 256, NF1 if fused else 3000, 65 if bn == 128 else 129
+    eb = int(args[1])                                # phased EXP 30 / 31: fused, 256-query tiles
+    return "f16" if eb == 2 else "fp8", 768, NF1, 129
 
 
 def case_id(case):

@@ -35,7 +35,7 @@ def _phased(eb):
 
 
 # (name, dtype, d, n, nominal k, pair-mode kernel of a 1024-query chunk).  n is no multiple of 4, 256 or 1024 and covers
-# n % 4 = 1, 2, 3; the larger d go with the smaller n.  Kernel per launch_scores_tiled / launch_tiled_eb / phased_ok:
+# n % 4 = 1, 2, 3; the larger d go with the smaller n.  Kernel per batch_route / launch_tiled_eb / phased_ok:
 #   f32: 64-query tiles; f16 / fp8: 256-query tiles, the phased kernel when a row is an even number (>= 6) of 128-byte
 #   k-tiles, else the tiled kernel at 256 x 256 (fp8: the instantiation that spills).
 CASES = [

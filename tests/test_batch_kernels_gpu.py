@@ -14,7 +14,7 @@ import ctypes
 import numpy as np
 import pytest
 
-from batch_kernel_table import AB_ONLY, CASES, FUSED, MAT, NF1, NORMS, case_id
+from batch_kernel_table import AB_ONLY, CASES, FUSED, MAT, NF1, NORMS, _ab_shape, case_id
 from compare import assert_topk_parity
 from oracle import svs_oracle as oracle
 from synth import corpus_and_query
@@ -200,19 +200,6 @@ def test_fused_planted_rows_in_every_tile(gpu, fused_corpora, case):
 
 
 # ---- kernels only an A/B variant reaches: the variant the table names reaches them, and they answer correctly --------
-def _ab_shape(kernel):
-    """(dtype, d, n, nq) that reaches `kernel` under its A/B variant (svs_amd.hip: launch_scores_q16 variant 3,
-    launch_tiled_eb variants 4 / 8 / 9)."""
-    args = kernel[kernel.index("<") + 1:-1].split(", ")
-    if kernel.startswith("gemm_f32_q16_kernel"):
-        return "f32", 128, NF1 if args[3] == "true" else 3000, 16
-    if kernel.startswith("gemm_tiled_kernel"):      # rows of 2 k-tiles: not the phased kernel's
-        bn, fused, eb = int(args[0]), args[1] == "true", int(args[2])
-        return "f16" if eb == 2 else "fp8", 256, NF1 if fused else 3000, 65 if bn == 128 else 129
-    eb = int(args[1])                                # phased EXP 30 / 31: fused, 256-query tiles
-    return "f16" if eb == 2 else "fp8", 768, NF1, 129
-
-
 @pytest.mark.parametrize("kernel", sorted(AB_ONLY))
 def test_ab_only_kernels_reached_by_their_variant(gpu, fused_corpora, kernel):
     from svs_amd import DeviceIndex

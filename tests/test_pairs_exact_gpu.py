@@ -200,7 +200,7 @@ def test_refuses_more_pairs_than_the_list_holds(gpu, dtype, d, kernel):
 
 @pytest.mark.parametrize("dtype,d", [("f16", 100), ("f32", 100), ("fp8", 100)])
 def test_refuses_rows_that_are_not_whole_lines(gpu, dtype, d):
-    """d = 100 is stored with rows that are no multiple of 128 bytes (tiled_ok is false): the tiled path refuses before
+    """d = 100 is stored with rows that are no multiple of 128 bytes (batch_route: no tiled family): the tiled path refuses before
     it launches anything, and the handle then answers a batch search like a fresh index and the materialised path
     exactly.  (No fused search exists for such rows: plan_search fuses only what the batched kernels take.)"""
     from svs_amd import DeviceIndex, _native
@@ -232,7 +232,7 @@ def test_refuses_rows_that_are_not_whole_lines(gpu, dtype, d):
 @pytest.mark.parametrize("n", [2, 3, 5, 16, 17, 33])
 @pytest.mark.parametrize("dtype,d", [("f32", 128), ("f16", 128), ("f16", 256)])
 def test_tiny_corpora_tiled(gpu, dtype, d, n):
-    """Up to 16 rows the one query chunk would take the 16-query kernels (f32 d = 128, f16 d = 256: batch_kernel_ok),
+    """Up to 16 rows the one query chunk would take the 16-query kernels (f32 d = 128, f16 d = 256: batch_route),
     which have no pair mode -- they returned (i, i) and both (i, j) and (j, i) -- so svs_index_top_pairs keeps such
     corpora on the materialised path; from 17 rows on the tiled kernels run in pair mode."""
     from svs_amd import DeviceIndex
