@@ -272,6 +272,38 @@ int32_t svs_index_search_rows(svs_index* idx, const float* queries, int32_t nq, 
                               const int64_t* rows, int64_t nrows,
                               float* out_scores, int64_t* out_rows, int32_t* out_count);
 
+/* Segmented filtered search: MANY row lists in one call, each with its own query -- the drill-down of a document
+ * tree (one query, the children of each of the 50-500 best sections) and per-request scopes (one list per query),
+ * which are otherwise a host loop of svs_index_search_rows: a validation, an upload, two or more small launches
+ * and a stream synchronisation per list.
+ *   rows, seg_begin   segment s is the list rows[seg_begin[s] .. seg_begin[s+1]) (seg_begin has nseg + 1 entries,
+ *                     seg_begin[0] == 0, never decreasing); GLOBAL rows in any order, duplicates allowed,
+ *                     tombstoned rows drop out, as svs_index_search_rows.  The same row may appear in any
+ *                     number of segments.
+ *   seg_query         segment s is searched with query seg_query[s]; NULL: with query s, and nseg must equal nq.
+ * Exact definition.  At out_*[s*k .. s*k + out_counts[s]) the result is what
+ *   svs_index_search_rows(idx, queries + seg_query[s]*d, 1, d, k, rows + seg_begin[s], seg_begin[s+1] - seg_begin[s], ...)
+ * writes: the same rows, order (score desc, row desc) and score bits; out_counts[s] = min(max(k, 0), live listed
+ * rows of s, duplicates collapsed); entries past the count are not touched.  Nothing is grouped, merged or
+ * deduplicated ACROSS segments, and a segment's result does not depend on which other segments are in the call, or
+ * on their order.
+ * Errors: everything is validated before anything is launched, and a failing call writes no output.  d != index d
+ * -> SVS_ERR_SHAPE.  SVS_ERR_INVALID: nseg < 0, seg_begin[0] != 0, a decreasing seg_begin, a seg_query entry
+ * outside [0, nq), seg_query == NULL with nseg != nq, a row outside [row_offset, row_offset + n) (the message
+ * names the first offending segment and row), a null output with work to do.  Rows of more than 16 KiB, or 2^31
+ * or more live rows in the segments of up to 4096 rows -> SVS_ERR_UNSUPPORTED.  nseg == 0, k <= 0 or no live
+ * listed row anywhere -> SVS_OK, all written counts 0, nothing launched.
+ * The segments of 1 .. 4096 live rows are scored by ONE launch and ranked by one more, their rows mapped on the
+ * device; a larger segment is served inside the same call by svs_index_search_rows' own kernels.
+ * Blocking; re-entrant on one handle; holds a reference and the geometry lock shared; waits for pending staging
+ * copies; never goes through the coalescer: all as svs_index_search_rows.
+ * Out of scope: svs_multi / row-sharded corpora, a device-pointer variant, coalescing concurrent filtered callers
+ * into one segmented call; svs_index_search_rows, its kernels and the top-k stage are unchanged. */
+int32_t svs_index_search_segments(svs_index* idx, const float* queries, int32_t nq, int32_t d, int32_t k,
+                                  const int64_t* rows, const int64_t* seg_begin /* nseg + 1 */,
+                                  const int32_t* seg_query /* nseg, or NULL */, int32_t nseg,
+                                  float* out_scores, int64_t* out_rows, int32_t* out_counts /* nseg */);
+
 /* ---- neighbours of STORED rows ("more like this", near-duplicates of one document, the kNN graph):
  *      replaces a loop of np.dot(M, M[i]) + get_top_k per row (src/svs/kb.py:1623, src/svs/util.py:190-203;
  *      0.24 s per row at 1M x 1536 by the reference's published figure).  The rows are already in HBM in the

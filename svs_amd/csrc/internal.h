@@ -110,6 +110,15 @@ int64_t svs_internal_compact_plan(const uint32_t* dead_sorted, int64_t ndead, in
 /* svs_index_compact with a bounce buffer of bounce_rows rows (<= 0: the default).  stats[4] (may be NULL): DIRECT steps,
  * BOUNCE steps, rows moved, bytes moved (rows, scales and shadow rows, each byte counted once). */
 int32_t svs_internal_compact(svs_index* idx, int64_t bounce_rows, int64_t* out_old_rows, int64_t cap, int64_t* out_n, int64_t* stats);
+/* The tile table of svs_index_search_segments (segments.h), pure host code, no index: sizes[nseg] = live rows per
+ * segment, seg_query[nseg] or NULL (segment s takes query s), w = rows a wave of the score kernel takes.  Segments of
+ * 1 .. 4096 rows get ceil(size / w) tiles at consecutive list offsets in segment order, the others none.
+ * tiles[4 i ..] = list (and score) offset, rows in the tile (1 .. w), query, segment; up to cap tiles are written.
+ * seg_off[nseg] (may be NULL): a tiled segment's list offset, -1 for the others; *total_rows (may be NULL): the rows
+ * the tiles cover.  Returns the number of tiles of the plan, SVS_ERR_UNSUPPORTED when they cover 2^31 rows or more,
+ * or SVS_ERR_INVALID. */
+int64_t svs_internal_segments_plan(const int64_t* sizes, const int32_t* seg_query, int64_t nseg, int32_t w, int64_t* tiles, int64_t cap,
+                                   int64_t* seg_off, int64_t* total_rows);
 /* multi.hip -> svs_amd.hip: carries a worker thread's error message over to the caller's thread */
 int32_t svs_internal_set_error(int32_t code, const char* msg);
 #ifdef __cplusplus

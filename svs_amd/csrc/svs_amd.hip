@@ -37,6 +37,7 @@
 #include "screen.h"
 #include "compact.h"
 #include "neighbors.h"
+#include "segments.h"
 
 namespace {
 
@@ -232,6 +233,10 @@ struct Ctx {
   DevBuf<float> nb_s;           DevBuf<int64_t> nb_r;
   PinBuf<uint32_t> nb_redo_pin; DevBuf<uint32_t> nb_redo_dev;
   DevBuf<float> nb_redo_q;
+  // svs_index_search_segments (segments.h): the tile table followed by the small segments' table (16-byte entries,
+  // pinned copy and device copy), and the result block -- int64 rows, then f32 scores -- that comes back in one copy
+  PinBuf<SegTile> seg_plan_pin; DevBuf<SegTile> seg_plan_dev;
+  DevBuf<int64_t> seg_res_dev;  PinBuf<int64_t> seg_res_pin;
   // Scratch is reused in stream order.  A context stays with the stream that
   // last used it; handing it to ANOTHER stream first drains the old one.
   hipStream_t last_stream = nullptr;
@@ -1336,6 +1341,49 @@ int launch_gather(const svs_index* idx, Ctx* c, const float* q_dev, int nq, cons
   }
   if ((rc = stage_queries_fp8(idx, c, q_dev, nq, nq, false, st)) != SVS_OK) return rc;
   return launch_gather_dt<2>(idx, c->q8, c->q8s, nq, list, m, scores, sstride, st);
+}
+
+// ---- segmented filtered search: the small segments of a call in two launches (segments.h) -----------
+template <int DT, int T, int NC, int U>
+constexpr KernelName kGatherSegName = kernel_name("gather_segments_kernel", DT, T, NC, U);
+
+// Rows a wave of the gather kernels takes on this index (0: rows longer than 16 KiB, which they do not take)
+int gather_rows_per_wave(const svs_index* idx) {
+  int w = 0;
+  for_row_geometry((int)((size_t)idx->ld * elem_bytes(idx) / 16), [&](auto t, auto nc) { w = 64 / t() * gather_u(nc()); });
+  return w;
+}
+
+// q: the call's staged queries ([nq][ld] in the corpus dtype); list, tiles: on the device; total_rows, nseg: what the
+// tiles cover (the launch record)
+template <int DT>
+void launch_gather_segments_dt(const svs_index* idx, const void* q, const float* q_scales, const uint32_t* list, const SegTile* tiles,
+                               int64_t ntiles, int64_t total_rows, int nseg, float* scores, hipStream_t st) {
+  const int ld16 = (int)((size_t)idx->ld * elem_bytes(idx) / 16);
+  for_row_geometry(ld16, [&](auto t, auto nc) {
+    constexpr int T = t(), NC = nc(), U = gather_u(NC), WPB = gather_wpb(NC);
+    launch_record(kGatherSegName<DT, T, NC, U>.s, total_rows, nseg);
+    hipLaunchKernelGGL((gather_segments_kernel<DT, T, NC, U>), dim3((unsigned)((ntiles + WPB - 1) / WPB)), dim3(WPB * 64), 0, st,
+                       (const u32x4*)idx->rows, ld16, list, tiles, ntiles, (const u32x4*)q, idx->row_scales, q_scales, scores);
+  });
+}
+
+// Stages the call's nq queries (f32 in q_dev) in the corpus dtype, once, and scores every tile
+int launch_gather_segments(const svs_index* idx, Ctx* c, const float* q_dev, int nq, const uint32_t* list, const SegTile* tiles,
+                           int64_t ntiles, int64_t total_rows, int nseg, float* scores, hipStream_t st) {
+  int rc;
+  if (idx->dtype == SVS_DTYPE_F32) {
+    const float* qs = nullptr;
+    if ((rc = stage_queries_f32(idx, c, q_dev, nq, nq, &qs, st)) != SVS_OK) return rc;
+    launch_gather_segments_dt<0>(idx, qs, nullptr, list, tiles, ntiles, total_rows, nseg, scores, st);
+  } else if (idx->dtype == SVS_DTYPE_F16) {
+    if ((rc = stage_queries_f16(idx, c, q_dev, nq, nq, st)) != SVS_OK) return rc;
+    launch_gather_segments_dt<1>(idx, c->qh, nullptr, list, tiles, ntiles, total_rows, nseg, scores, st);
+  } else {
+    if ((rc = stage_queries_fp8(idx, c, q_dev, nq, nq, false, st)) != SVS_OK) return rc;
+    launch_gather_segments_dt<2>(idx, c->q8, c->q8s, list, tiles, ntiles, total_rows, nseg, scores, st);
+  }
+  return SVS_OK;
 }
 
 // One batch through a route of its own -- decided, staged, launched (the pair paths, chunk by chunk).  variant: the call's
@@ -2510,6 +2558,33 @@ int64_t svs_internal_compact_plan(const uint32_t* dead_sorted, int64_t ndead, in
   return ns;
 }
 
+int64_t svs_internal_segments_plan(const int64_t* sizes, const int32_t* seg_query, int64_t nseg, int32_t w, int64_t* tiles, int64_t cap,
+                                   int64_t* seg_off, int64_t* total_rows) {
+  if (nseg < 0 || w < 1 || cap < 0 || (nseg > 0 && !sizes) || (cap > 0 && !tiles))
+    return fail(SVS_ERR_INVALID, "svs_internal_segments_plan: nseg >= 0, w >= 1, cap >= 0");
+  for (int64_t s = 0; s < nseg; ++s)
+    if (sizes[s] < 0) return fail(SVS_ERR_INVALID, "svs_internal_segments_plan: segment %lld has a negative size", (long long)s);
+  const int64_t nt = seg_tile_plan(sizes, seg_query, nseg, w, nullptr, 0, seg_off, total_rows);
+  if (nt < 0) return fail(SVS_ERR_UNSUPPORTED, "svs_internal_segments_plan: 2^31 or more live rows in the small segments");
+  const int64_t keep = std::min(nt, cap);
+  if (keep > 0) {
+    std::vector<SegTile> t;
+    try {
+      t.resize((size_t)keep);
+    } catch (const std::bad_alloc&) {
+      return fail(SVS_ERR_NOMEM, "out of host memory for %lld tiles", (long long)keep);
+    }
+    (void)seg_tile_plan(sizes, seg_query, nseg, w, t.data(), keep, nullptr, nullptr);
+    for (int64_t i = 0; i < keep; ++i) {
+      tiles[4 * i] = t[(size_t)i].off;
+      tiles[4 * i + 1] = t[(size_t)i].rows;
+      tiles[4 * i + 2] = t[(size_t)i].query;
+      tiles[4 * i + 3] = t[(size_t)i].seg;
+    }
+  }
+  return nt;
+}
+
 int32_t svs_index_retain(svs_index* idx) {
   if (!idx) return fail(SVS_ERR_INVALID, "null index");
   idx->refs.fetch_add(1);
@@ -3030,6 +3105,232 @@ int32_t svs_index_search_rows(svs_index* idx, const float* queries, int32_t nq, 
     c->out_r_pin[i] = (int64_t)S[p] + lo;
   }
   deliver_results(c, nq, count, k, out_scores, out_rows);
+  return SVS_OK;
+}
+
+int32_t svs_index_search_segments(svs_index* idx, const float* queries, int32_t nq, int32_t d, int32_t k, const int64_t* rows,
+                                  const int64_t* seg_begin, const int32_t* seg_query, int32_t nseg, float* out_scores,
+                                  int64_t* out_rows, int32_t* out_counts) {
+  launch_reset();
+  if (!idx) return fail(SVS_ERR_INVALID, "null index");
+  RefGuard guard(idx);
+  std::shared_lock<std::shared_mutex> geo(idx->rw);
+  // ---- everything is validated before anything is written or launched
+  int rc = check_query_args(idx, queries, nq, d);
+  if (rc != SVS_OK) return rc;
+  if (nseg < 0) return fail(SVS_ERR_INVALID, "nseg must be >= 0");
+  if (!seg_query && nseg != nq)
+    return fail(SVS_ERR_INVALID, "svs_index_search_segments: %d segments for %d queries and no seg_query", nseg, nq);
+  if (nseg == 0) return SVS_OK;
+  if (!seg_begin) return fail(SVS_ERR_INVALID, "null seg_begin");
+  if (seg_begin[0] != 0) return fail(SVS_ERR_INVALID, "seg_begin[0] must be 0, not %lld", (long long)seg_begin[0]);
+  for (int32_t s = 0; s < nseg; ++s) {
+    if (seg_begin[s + 1] < seg_begin[s])
+      return fail(SVS_ERR_INVALID, "seg_begin decreases at segment %d (%lld after %lld)", s, (long long)seg_begin[s + 1], (long long)seg_begin[s]);
+    if (seg_query && (seg_query[s] < 0 || seg_query[s] >= nq))
+      return fail(SVS_ERR_INVALID, "segment %d: query %d outside [0, %d)", s, seg_query[s], nq);
+  }
+  const int64_t total = seg_begin[nseg];
+  if (total > 0 && !rows) return fail(SVS_ERR_INVALID, "null row list");
+  const int64_t lo = idx->row_offset, n = idx->n;
+  std::vector<uint8_t> ascending;
+  std::vector<int64_t> m_of, off_of;
+  std::vector<uint32_t> tmp, big;   // an unsorted segment's rows; the lists of the large segments, one after the other
+  try {
+    ascending.assign((size_t)nseg, 1);
+    m_of.assign((size_t)nseg, 0);
+    off_of.assign((size_t)nseg, -1);
+  } catch (const std::bad_alloc&) {
+    return fail(SVS_ERR_NOMEM, "out of host memory for %d segments", nseg);
+  }
+  for (int32_t s = 0; s < nseg; ++s)
+    for (int64_t t = seg_begin[s]; t < seg_begin[s + 1]; ++t) {
+      const int64_t r = rows[t] - lo;
+      if (r < 0 || r >= n)
+        return fail(SVS_ERR_INVALID, "segment %d: row %lld out of range [%lld, %lld)", s, (long long)rows[t], (long long)lo, (long long)(lo + n));
+      if (t > seg_begin[s] && rows[t] <= rows[t - 1]) ascending[(size_t)s] = 0;
+    }
+  if (!out_counts) return fail(SVS_ERR_INVALID, "null out_counts");
+  if (k > 0 && total > 0 && (!out_scores || !out_rows)) return fail(SVS_ERR_INVALID, "null output");
+  const int ld16 = (int)((size_t)idx->ld * elem_bytes(idx) / 16);
+  const int W = gather_rows_per_wave(idx);
+  if (k > 0 && total > 0 && W == 0)
+    return fail(SVS_ERR_UNSUPPORTED, "svs_index_search_segments: rows of %d bytes; the gather kernels take rows of up to 16 KiB", ld16 * 16);
+  if (k <= 0 || total == 0) {
+    for (int32_t s = 0; s < nseg; ++s) out_counts[s] = 0;
+    return SVS_OK;
+  }
+  HIP_TRY(hipSetDevice(idx->device));
+  if ((rc = staging_wait(idx)) != SVS_OK) return rc;
+  Ctx* c = nullptr;
+  if ((rc = ctx_acquire(idx, nullptr, true, &c)) != SVS_OK) return rc;
+  CtxGuard cg{idx, c};
+  // ---- host plan: S = the live rows of every segment, ascending inside it, as local u32 rows in pinned memory --
+  // the small segments (1 .. SORT_CAP live rows) first, in segment order, then the large ones
+  if ((rc = c->list_pin.grow((size_t)total)) != SVS_OK) return rc;
+  uint32_t* S = c->list_pin;
+  const uint8_t* dead = idx->dead_flag.data();
+  int64_t small_rows = 0, max_small = 0, max_large = 0, n_small = 0, n_large = 0, large_out = 0;
+  try {
+    for (int32_t s = 0; s < nseg; ++s) {
+      const int64_t b = seg_begin[s], nr = seg_begin[s + 1] - b;
+      // (a segment that lists more than SORT_CAP rows may be large: it is built aside and placed once its size is known)
+      const bool aside = nr > SORT_CAP;
+      if (aside) big.resize(big.size() + (size_t)nr);
+      uint32_t* dst = aside ? big.data() + (big.size() - (size_t)nr) : S + small_rows;
+      int64_t m = 0;
+      if (ascending[(size_t)s]) {
+        for (int64_t t = 0; t < nr; ++t) {
+          const uint32_t r = (uint32_t)(rows[b + t] - lo);
+          if (!dead[r]) dst[m++] = r;
+        }
+      } else {
+        tmp.resize((size_t)nr);
+        for (int64_t t = 0; t < nr; ++t) tmp[(size_t)t] = (uint32_t)(rows[b + t] - lo);
+        std::sort(tmp.begin(), tmp.end());
+        const size_t u = (size_t)(std::unique(tmp.begin(), tmp.end()) - tmp.begin());
+        for (size_t t = 0; t < u; ++t)
+          if (!dead[tmp[t]]) dst[m++] = tmp[t];
+      }
+      m_of[(size_t)s] = m;
+      if (aside && m <= SORT_CAP) {   // small after all
+        memcpy(S + small_rows, dst, (size_t)m * sizeof(uint32_t));
+        big.resize(big.size() - (size_t)nr);
+      } else if (aside) {
+        big.resize(big.size() - (size_t)(nr - m));
+        ++n_large;
+        max_large = std::max(max_large, m);
+        large_out += std::min<int64_t>(k, m);
+      }
+      if (m >= 1 && m <= SORT_CAP) {
+        small_rows += m;
+        ++n_small;
+        max_small = std::max(max_small, m);
+      }
+    }
+  } catch (const std::bad_alloc&) {
+    return fail(SVS_ERR_NOMEM, "out of host memory for a %lld-row list", (long long)total);
+  }
+  if (n_small == 0 && n_large == 0) {
+    for (int32_t s = 0; s < nseg; ++s) out_counts[s] = 0;
+    return SVS_OK;
+  }
+  const int64_t ntiles = seg_tile_plan(m_of.data(), seg_query, nseg, W, nullptr, 0, off_of.data(), nullptr);
+  if (ntiles < 0)
+    return fail(SVS_ERR_UNSUPPORTED, "svs_index_search_segments: the small segments list %lld live rows; one call takes fewer than 2^31",
+                (long long)small_rows);
+  if (!big.empty()) memcpy(S + small_rows, big.data(), big.size() * sizeof(uint32_t));
+  const int64_t listed = small_rows + (int64_t)big.size();
+  const int kk = (int)std::min<int64_t>(k, max_small);   // the small segments' result stride
+  const size_t plan_n = (size_t)ntiles + (size_t)n_small;
+  if ((rc = c->seg_plan_pin.grow(std::max<size_t>(plan_n, 1))) != SVS_OK || (rc = c->seg_plan_dev.grow(std::max<size_t>(plan_n, 1))) != SVS_OK) return rc;
+  SegTile* tiles = c->seg_plan_pin;
+  SegDesc* segs = reinterpret_cast<SegDesc*>(tiles + ntiles);
+  (void)seg_tile_plan(m_of.data(), seg_query, nseg, W, tiles, ntiles, nullptr, nullptr);
+  {
+    int64_t j = 0;
+    for (int32_t s = 0; s < nseg; ++s)
+      if (off_of[(size_t)s] >= 0)
+        segs[j++] = SegDesc{(uint32_t)off_of[(size_t)s], (uint32_t)m_of[(size_t)s], (uint32_t)std::min<int64_t>(k, m_of[(size_t)s]), (uint32_t)s};
+  }
+  // the result block: rows (int64) of the small segments at stride kk, then of the large ones, count by count; the
+  // scores (f32) behind them in the same order
+  const size_t res_n = (size_t)n_small * (size_t)kk + (size_t)large_out;
+  const size_t res_words = res_n + (res_n + 1) / 2;
+  hipStream_t st = c->stream;
+  const size_t qn = (size_t)nq * (size_t)d;
+  if ((rc = c->q_dev.grow(qn)) != SVS_OK || (rc = c->q_pin.grow(qn)) != SVS_OK) return rc;
+  if ((rc = c->list_dev.grow((size_t)listed)) != SVS_OK) return rc;
+  if ((rc = c->seg_res_dev.grow(res_words)) != SVS_OK || (rc = c->seg_res_pin.grow(res_words)) != SVS_OK) return rc;
+  const int64_t small_stride = (small_rows + 3) & ~(int64_t)3, large_stride = (max_large + 3) & ~(int64_t)3;
+  if ((rc = c->scores.grow((size_t)std::max(small_stride, large_stride))) != SVS_OK) return rc;
+  bool window = false;
+  for (int32_t s = 0; s < nseg && !window; ++s)
+    window = m_of[(size_t)s] > SORT_CAP && select_path(m_of[(size_t)s], (int)std::min<int64_t>(k, m_of[(size_t)s])) == SelectPath::WINDOW;
+  if (window && (rc = grow_select_scratch(c, 1, st)) != SVS_OK) return rc;
+  int64_t* res_r = c->seg_res_dev;
+  float* res_s = reinterpret_cast<float*>(res_r + res_n);
+  memcpy(c->q_pin, queries, qn * sizeof(float));
+  HIP_TRY(hipMemcpyAsync(c->q_dev, c->q_pin, qn * sizeof(float), hipMemcpyHostToDevice, st));
+  HIP_TRY(hipMemcpyAsync(c->list_dev, S, (size_t)listed * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+  if (n_small) {
+    HIP_TRY(hipMemcpyAsync(c->seg_plan_dev, tiles, plan_n * sizeof(SegTile), hipMemcpyHostToDevice, st));
+    const SegTile* tiles_dev = c->seg_plan_dev;
+    rc = launch_gather_segments(idx, c, c->q_dev, nq, c->list_dev, tiles_dev, ntiles, small_rows, (int)n_small, c->scores, st);
+    if (rc == SVS_OK) {
+      launch_record("select_segments_kernel", small_rows, (int)n_small);
+      hipLaunchKernelGGL(select_segments_kernel, dim3((unsigned)n_small), dim3(FINAL_THREADS), 0, st, (const float*)c->scores,
+                         (const uint32_t*)c->list_dev, reinterpret_cast<const SegDesc*>(tiles_dev + ntiles), kk, lo, res_s, res_r);
+    }
+  }
+  // The large segments, one after the other behind the small ones' two kernels on the same stream, exactly as
+  // svs_index_search_rows serves them: launch_gather re-stages its query into the buffers the small segments' kernel
+  // read its queries from, and the scores are reused -- both in stream order, behind their readers.
+  {
+    int64_t loff = small_rows;
+    size_t o = (size_t)n_small * (size_t)kk;
+    for (int32_t s = 0; s < nseg && rc == SVS_OK; ++s) {
+      const int64_t m = m_of[(size_t)s];
+      if (m <= SORT_CAP) continue;
+      const int count = (int)std::min<int64_t>(k, m);
+      const int sq = seg_query ? seg_query[s] : s;
+      const int64_t sstride = (m + 3) & ~(int64_t)3;
+      rc = launch_gather(idx, c, c->q_dev + (size_t)sq * d, 1, c->list_dev + loff, m, c->scores, sstride, st);
+      if (rc == SVS_OK) rc = run_select(idx, c, c->scores, m, sstride, 1, count, count, res_s + o, res_r + o, st, 0);
+      loff += m;
+      o += (size_t)count;
+    }
+  }
+  if (rc == SVS_OK) {
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) rc = fail(SVS_ERR_DEVICE, "search_segments launch: %s", hipGetErrorString(e));
+  }
+  if (rc != SVS_OK) {
+    (void)hipStreamSynchronize(st);
+    return rc;
+  }
+  HIP_TRY(hipMemcpyAsync(c->seg_res_pin, c->seg_res_dev, res_n * sizeof(int64_t) + res_n * sizeof(float), hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipStreamSynchronize(st));
+  // ---- delivery: count_s entries per segment at the caller's stride k; the large segments' positions -> rows
+  const int64_t* pr = c->seg_res_pin;
+  const float* ps = reinterpret_cast<const float*>(pr + res_n);
+  {
+    int64_t loff = small_rows;
+    size_t o = (size_t)n_small * (size_t)kk;
+    for (int32_t s = 0; s < nseg; ++s) {
+      const int64_t m = m_of[(size_t)s];
+      if (m <= SORT_CAP) continue;
+      const int count = (int)std::min<int64_t>(k, m);
+      for (int i = 0; i < count; ++i) {
+        const int64_t p = pr[o + i];
+        if (p < 0 || p >= m)
+          return fail(SVS_ERR_DEVICE, "search_segments: position %lld outside the %lld listed rows of segment %d", (long long)p, (long long)m, s);
+      }
+      loff += m;
+      o += (size_t)count;
+    }
+    loff = small_rows;
+    o = (size_t)n_small * (size_t)kk;
+    size_t j = 0;
+    for (int32_t s = 0; s < nseg; ++s) {
+      const int64_t m = m_of[(size_t)s];
+      const int count = (int)std::min<int64_t>(k, m);
+      out_counts[s] = count;
+      if (m == 0) continue;
+      float* os = out_scores + (size_t)s * k;
+      int64_t* orow = out_rows + (size_t)s * k;
+      if (m <= SORT_CAP) {
+        memcpy(os, ps + j * kk, (size_t)count * sizeof(float));
+        memcpy(orow, pr + j * kk, (size_t)count * sizeof(int64_t));
+        ++j;
+      } else {
+        memcpy(os, ps + o, (size_t)count * sizeof(float));
+        for (int i = 0; i < count; ++i) orow[i] = (int64_t)S[loff + pr[o + i]] + lo;
+        loff += m;
+        o += (size_t)count;
+      }
+    }
+  }
   return SVS_OK;
 }
 

@@ -293,6 +293,44 @@ class DeviceIndex:
         s, r = self.search_batch_within(q[None, :], n, rows)
         return list(zip(s[0].astype(np.float64).tolist(), r[0].tolist()))
 
+    def search_segments(self, queries: np.ndarray, n: int, row_lists, seg_query=None) -> List[Tuple[np.ndarray, np.ndarray]]:
+        """``search_within`` for MANY row lists in one call (svs_index_search_segments): segment s is
+        ``row_lists[s]`` (GLOBAL rows, any order, duplicates allowed, masked rows drop out) searched with query
+        ``seg_query[s]`` of ``queries`` (nq, D) -- ``seg_query=None``: with query s, one list per query.  Returns one
+        ``(scores f32 (count_s,), rows i64 (count_s,))`` per segment, count_s = min(max(n, 0), live listed rows of s),
+        ordered (score desc, row desc): the rows and score bits ``search_within(queries[seg_query[s]], n,
+        row_lists[s])`` gives.  Nothing is merged across segments."""
+        assert isinstance(n, int)
+        q = np.ascontiguousarray(queries, dtype=np.float32)
+        if q.ndim != 2:
+            raise ValueError(f"queries must be 2-D, got shape {q.shape}")
+        lists = [np.asarray(r, dtype=np.int64).reshape(-1) for r in row_lists]
+        nseg = len(lists)
+        nq, d = q.shape
+        begin = np.zeros(nseg + 1, dtype=np.int64)
+        if nseg:
+            np.cumsum([len(r) for r in lists], out=begin[1:])
+        rows = np.concatenate(lists) if nseg else np.zeros(0, dtype=np.int64)
+        rows = np.ascontiguousarray(rows, dtype=np.int64)
+        sq = None
+        if seg_query is not None:
+            sq = np.ascontiguousarray(seg_query, dtype=np.int32).reshape(-1)
+            if len(sq) != nseg:
+                raise ValueError(f"seg_query has {len(sq)} entries for {nseg} row lists")
+        longest = max((len(r) for r in lists), default=0)
+        k = min(max(n, 0), longest, 2 ** 31 - 1)   # (count_s <= listed rows of s: clamp before allocating)
+        scores = np.empty((nseg, k), dtype=np.float32)
+        out_rows = np.empty((nseg, k), dtype=np.int64)
+        counts = np.zeros(nseg, dtype=np.int32)
+        h = self._pinned_handle()
+        try:
+            _native.check(self._lib.svs_index_search_segments(h, q.ctypes.data, nq, d, k, rows.ctypes.data, begin.ctypes.data,
+                                                              None if sq is None else sq.ctypes.data, nseg, scores.ctypes.data,
+                                                              out_rows.ctypes.data, counts.ctypes.data))
+        finally:
+            self._unpin(h)
+        return [(scores[s, :c], out_rows[s, :c]) for s, c in enumerate(counts.tolist())]
+
     def neighbors(self, rows, n: int) -> Tuple[np.ndarray, np.ndarray]:
         """The ``n`` nearest stored rows of each listed stored row (GLOBAL indices, any order, repeats allowed), the
         row itself excluded: (scores f32 (len(rows), count), rows i64 (len(rows), count)), count = min(max(n, 0),

@@ -31,7 +31,7 @@ import numpy as np
 
 from .index import DeviceIndex
 from .matrix import (DeviceEmbeddingsMatrix, ids_of_batch, ids_of_pairs, ids_of_rows, neighbors_held, search_mapped,
-                     search_within_held, single_search)
+                     search_within_held, search_within_many_held, single_search)
 
 _LOG = logging.getLogger(__name__)
 
@@ -535,6 +535,60 @@ class KB:
                 out.append([{"score": s, "doc": docs[e]} for s, e in emb_ids])
         return out
 
+    def retrieve_many_within(self, queries: List[str], n: int, doc_id_lists: List[List[int]]) -> List[List[Dict[str, Any]]]:
+        """``retrieve_within`` for many (query, doc list) pairs -- requests that each carry their own tenant, book or
+        level: the queries are embedded in chunks of 200 like ``retrieve_many``, every list is scored and ranked in ONE
+        native call (svs_index_search_segments) and fetched with one SQL statement.  Element i equals
+        ``retrieve_within(queries[i], n, doc_id_lists[i])``.  An unknown doc id raises KeyError; docs without an
+        embedding are skipped."""
+        _LOG.info(f"retrieving {n} documents for each of {len(queries)} query strings, each within its own documents")
+        if len(queries) != len(doc_id_lists):
+            raise ValueError(f"{len(queries)} queries for {len(doc_id_lists)} document lists")
+        assert self.db is not None
+        self.embeddings_matrix.get_sync(self.db)
+        with self.db.transaction():
+            embs = [self.db.embeddings_for_docs(list(ids)) for ids in doc_id_lists]
+        vecs: List[List[float]] = []
+        for c0 in range(0, len(queries), BULK_EMBEDDING_CHUNK_SIZE):
+            vecs.extend(self._embed(queries[c0:c0 + BULK_EMBEDDING_CHUNK_SIZE]))
+        if not vecs:
+            return []
+        _LOG.info("got embeddings for the queries!")
+        per_list = self.embeddings_matrix.search_within_many(np.array(vecs, dtype=np.float32), n, embs)   # HIP
+        _LOG.info(f"computed {sum(len(e) for e in embs)} cosine similarities")
+        res = self._fetch_lists(per_list)
+        _LOG.info(f"retrieved top {n} documents for {len(queries)} queries")
+        return res
+
+    def retrieve_within_each(self, query: str, n: int, doc_id_lists: List[List[int]]) -> List[List[Dict[str, Any]]]:
+        """The drill-down: ONE query against many doc lists (the children of each of the best sections), one
+        embedding call and one native call (svs_index_search_segments).  Element g equals
+        ``retrieve_within(query, n, doc_id_lists[g])``; nothing is merged across the lists.  An unknown doc id raises
+        KeyError; docs without an embedding are skipped."""
+        _LOG.info(f"retrieving {n} documents within each of {len(doc_id_lists)} document lists with query string: {query}")
+        assert self.db is not None
+        self.embeddings_matrix.get_sync(self.db)
+        with self.db.transaction():
+            embs = [self.db.embeddings_for_docs(list(ids)) for ids in doc_id_lists]
+        if not embs:
+            return []
+        query_vec = np.array(self._embed([query])[0], dtype=np.float32)
+        _LOG.info("got embedding for query!")
+        per_list = self.embeddings_matrix.search_within_many(query_vec[None, :], n, embs, [0] * len(embs))   # HIP
+        _LOG.info(f"computed {sum(len(e) for e in embs)} cosine similarities")
+        res = self._fetch_lists(per_list)
+        _LOG.info(f"retrieved top {n} documents for {len(embs)} lists")
+        return res
+
+    def _fetch_lists(self, per_list: List[List[Tuple[float, int]]]) -> List[List[Dict[str, Any]]]:
+        """[(score, emb id)] lists -> ``Retrieval`` lists, one SQL fetch per list (as ``retrieve_many``)."""
+        out: List[List[Dict[str, Any]]] = []
+        with self.db.transaction():
+            for emb_ids in per_list:
+                docs = self.db.fetch_docs_for_embeddings([e for _, e in emb_ids])
+                out.append([{"score": s, "doc": docs[e]} for s, e in emb_ids])
+        return out
+
 
 class AsyncKB:
     """Async twin (reference src/svs/kb.py:925-1206): the matrix is fetched under
@@ -767,6 +821,66 @@ class AsyncKB:
             res = await loop.run_in_executor(None, heavy)
         _LOG.info(f"retrieved top {n} documents for {len(queries)} queries")
         return res
+
+    async def _retrieve_segments(self, texts: List[str], n: int, doc_id_lists: List[List[int]], one_query: bool,
+                                 embedded: str, done: str) -> List[List[Dict[str, Any]]]:
+        """The body of ``retrieve_many_within`` (one query per list) and ``retrieve_within_each`` (``one_query``),
+        structured as ``retrieve_within``: the SQL and the reference to the matrix under the lock, the segmented
+        search on an executor thread outside it, the docs under the lock."""
+        loop = asyncio.get_running_loop()
+        lists = [list(ids) for ids in doc_id_lists]
+        async with self._get_lock():
+            db = await self._ensure_db()
+            await self.embeddings_matrix.get(db)
+
+            def sql() -> List[List[int]]:
+                with db.transaction():
+                    return [db.embeddings_for_docs(ids) for ids in lists]
+
+            embs = await loop.run_in_executor(None, sql)
+            idx, lookup = self.embeddings_matrix.hold()
+        try:
+            if not embs:
+                return []
+            vecs: List[List[float]] = []
+            for c0 in range(0, len(texts), BULK_EMBEDDING_CHUNK_SIZE):
+                vecs.extend(await self._embed(texts[c0:c0 + BULK_EMBEDDING_CHUNK_SIZE]))
+            _LOG.info(embedded)
+            qmat = np.array(vecs, dtype=np.float32)
+            seg_query = [0] * len(embs) if one_query else None
+            per_list = await loop.run_in_executor(None, lambda: search_within_many_held(idx, lookup, qmat, n, embs, seg_query,
+                                                                                         self.embeddings_matrix.hold))
+            _LOG.info(f"computed {sum(len(e) for e in embs)} cosine similarities")
+        finally:
+            idx.release()
+        async with self._get_lock():
+            db = await self._ensure_db()
+
+            def heavy() -> List[List[Dict[str, Any]]]:
+                out: List[List[Dict[str, Any]]] = []
+                with db.transaction():
+                    for emb_ids in per_list:
+                        docs = db.fetch_docs_for_embeddings([e for _, e in emb_ids])
+                        out.append([{"score": s, "doc": docs[e]} for s, e in emb_ids])
+                return out
+
+            res = await loop.run_in_executor(None, heavy)
+        _LOG.info(done)
+        return res
+
+    async def retrieve_many_within(self, queries: List[str], n: int, doc_id_lists: List[List[int]]) -> List[List[Dict[str, Any]]]:
+        """Async twin of ``KB.retrieve_many_within``: element i equals ``retrieve_within(queries[i], n, doc_id_lists[i])``."""
+        _LOG.info(f"retrieving {n} documents for each of {len(queries)} query strings, each within its own documents")
+        if len(queries) != len(doc_id_lists):
+            raise ValueError(f"{len(queries)} queries for {len(doc_id_lists)} document lists")
+        return await self._retrieve_segments(list(queries), n, doc_id_lists, False, "got embeddings for the queries!",
+                                             f"retrieved top {n} documents for {len(queries)} queries")
+
+    async def retrieve_within_each(self, query: str, n: int, doc_id_lists: List[List[int]]) -> List[List[Dict[str, Any]]]:
+        """Async twin of ``KB.retrieve_within_each``: element g equals ``retrieve_within(query, n, doc_id_lists[g])``."""
+        _LOG.info(f"retrieving {n} documents within each of {len(doc_id_lists)} document lists with query string: {query}")
+        return await self._retrieve_segments([query], n, doc_id_lists, True, "got embedding for query!",
+                                             f"retrieved top {n} documents for {len(doc_id_lists)} lists")
 
     async def retrieve_similar(self, doc_id: int, n: int) -> List[Dict[str, Any]]:
         """Async twin of ``KB.retrieve_similar``, structured as ``retrieve``: the SQL and the reference to the matrix

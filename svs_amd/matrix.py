@@ -120,6 +120,25 @@ def search_within_held(idx, lookup: _Lookup, query_vec: np.ndarray, n: int, emb_
     return search_mapped(hold if hold is not None else _no_hold, (idx, lookup), native, finish)
 
 
+def search_within_many_held(idx, lookup: _Lookup, query_vecs: np.ndarray, n: int, emb_id_lists, seg_query=None,
+                            hold: Optional[Callable[[], tuple]] = None) -> List[List[Tuple[float, int]]]:
+    """``search_within_held`` for many id lists in one native call (``idx.search_segments``,
+    svs_index_search_segments): list s is searched with query ``seg_query[s]`` of ``query_vecs`` (None: query s).
+    One [(score, emb_id)] list per id list.  KeyError for an id the loaded matrix does not hold; ``hold`` as in
+    ``search_within_held``."""
+    id_lists = [e if isinstance(e, np.ndarray) else list(e) for e in emb_id_lists]
+
+    def native(idx, lookup, *_):
+        return idx, idx.search_segments(query_vecs, n, [_within_rows(idx, lookup, e) for e in id_lists], seg_query)
+
+    def finish(res, arr):
+        used, per_seg = res
+        off = int(getattr(used, "row_offset", 0))
+        return [list(zip(s.astype(np.float64).tolist(), arr[r - off].tolist())) for s, r in per_seg]
+
+    return search_mapped(hold if hold is not None else _no_hold, (idx, lookup), native, finish)
+
+
 def neighbors_held(idx, lookup: _Lookup, emb_ids, n: int,
                    hold: Optional[Callable[[], tuple]] = None) -> List[List[Tuple[float, int]]]:
     """Neighbours of stored embeddings on a held (index, lookup): ids -> rows through ``lookup.arr``,
@@ -392,6 +411,16 @@ class DeviceEmbeddingsMatrix:
         idx, lookup = self.hold()
         try:
             return search_within_held(idx, lookup, query_vec, n, emb_ids, self.hold)
+        finally:
+            idx.release()
+
+    def search_within_many(self, query_vecs: np.ndarray, n: int, emb_id_lists, seg_query=None) -> List[List[Tuple[float, int]]]:
+        """``search_within`` for many id lists in one call: list s against query ``seg_query[s]`` of ``query_vecs``
+        (None: query s).  One [(score, emb_id)] list per id list (``KB.retrieve_many_within`` /
+        ``KB.retrieve_within_each``)."""
+        idx, lookup = self.hold()
+        try:
+            return search_within_many_held(idx, lookup, query_vecs, n, emb_id_lists, seg_query, self.hold)
         finally:
             idx.release()
 
