@@ -304,6 +304,44 @@ int32_t svs_index_search_segments(svs_index* idx, const float* queries, int32_t 
                                   const int32_t* seg_query /* nseg, or NULL */, int32_t nseg,
                                   float* out_scores, int64_t* out_rows, int32_t* out_counts /* nseg */);
 
+/* Threshold search: every live row that scores at or above a cut-off, best first, and how many there are -- "all
+ * documents with cosine >= 0.8", "how many would qualify", "drop the weak tail by score, not by rank" -- without
+ * guessing a k and without pulling the score vector to the host.
+ * Exact definition.  For query q of the call let s be the vector svs_index_scores_n(idx, query q) returns at that
+ * moment (the unscreened single-query score kernel of the index's dtype), L the live (not tombstoned) local rows, and
+ *   A = { r in L : score_key(s[r]) >= score_key(min_scores[q]) }
+ * with the orderable key of the top-k order (svs_amd/csrc/keys.h).  The comparison is made in KEY space, the space the
+ * order is defined in: -0.0 and +0.0 are one value; a NaN SCORE maps to the largest key, so it qualifies for every
+ * cut-off and sorts first, exactly as in svs_index_search; a cut-off of -inf admits every live row.  Tombstoned rows are
+ * excluded by the dead-row bitmap, never by their score.
+ *   out_totals[q]   = |A|, always exact, also beyond `limit` and beyond every internal capacity; may be NULL
+ *   out_counts[q]   = min(max(limit, 0), |A|)
+ *   out_*[q*limit .. q*limit + out_counts[q])   the first out_counts[q] elements of A in descending
+ *                     make_key(s[r], r), that is (score desc, row desc): scores are the bits of s, rows are
+ *                     row_offset + r (a NaN comes back as the quiet NaN 0x7fc00000, as from every search); entries
+ *                     past the count are not touched
+ * A query's result does not depend on nq, on the other queries of the call or on their order.
+ * Errors: everything is validated before anything is launched, and a failing call writes no output.  d != index d or
+ * an empty index -> SVS_ERR_SHAPE.  SVS_ERR_INVALID: nq < 0, null queries or min_scores with nq > 0, a NaN in
+ * min_scores (the message names the query), null out_counts, null out_scores / out_rows with limit > 0 and nq > 0.
+ * limit <= 0 is a COUNT-ONLY call: the totals are computed, every count is 0, out_scores / out_rows may be NULL --
+ * the one place where a non-positive limit still launches work.  nq == 0 -> SVS_OK, nothing launched.
+ * Each query costs one single-query corpus pass plus two small launches (a filter over the score vector, one
+ * workgroup that orders the survivors); up to 32,768 qualifying rows with min(limit, total) <= 4096 are finished on
+ * the device, beyond that the query is re-run through the exact top-k stage with k = min(limit, total) after the
+ * call's one wait: the same answer by definition.  (In that re-run a LIVE row whose score is -inf itself ties with the
+ * masked rows; finite rows and queries never produce one.)
+ * Blocking; re-entrant on one handle; holds a reference and the geometry lock shared; waits for pending staging
+ * copies; never goes through the coalescer, the run-ahead pipelines or shared passes: all as svs_index_scores_n and
+ * svs_index_search_rows.
+ * Out of scope: svs_multi / row-sharded corpora, a device-pointer variant, the batched GEMM score routes (every
+ * query is one single-query pass), and the screened route: an f32 index reads its f32 rows here, not the half shadow
+ * (screening a cut-off with the shadow's error bound is the natural follow-up). */
+int32_t svs_index_search_above(svs_index* idx, const float* queries, int32_t nq, int32_t d,
+                               const float* min_scores /* nq */, int32_t limit,
+                               float* out_scores, int64_t* out_rows /* stride limit */,
+                               int32_t* out_counts /* nq */, int64_t* out_totals /* nq, or NULL */);
+
 /* ---- neighbours of STORED rows ("more like this", near-duplicates of one document, the kNN graph):
  *      replaces a loop of np.dot(M, M[i]) + get_top_k per row (src/svs/kb.py:1623, src/svs/util.py:190-203;
  *      0.24 s per row at 1M x 1536 by the reference's published figure).  The rows are already in HBM in the

@@ -38,6 +38,7 @@
 #include "compact.h"
 #include "neighbors.h"
 #include "segments.h"
+#include "above.h"
 
 namespace {
 
@@ -237,6 +238,8 @@ struct Ctx {
   // pinned copy and device copy), and the result block -- int64 rows, then f32 scores -- that comes back in one copy
   PinBuf<SegTile> seg_plan_pin; DevBuf<SegTile> seg_plan_dev;
   DevBuf<int64_t> seg_res_dev;  PinBuf<int64_t> seg_res_pin;
+  // svs_index_search_above (above.h): per query, the entries the device wrote (-1: re-run on the host) and the total
+  PinBuf<int32_t> above_cnt_pin; PinBuf<int64_t> above_tot_pin;
   // Scratch is reused in stream order.  A context stays with the stream that
   // last used it; handing it to ANOTHER stream first drains the old one.
   hipStream_t last_stream = nullptr;
@@ -3105,6 +3108,103 @@ int32_t svs_index_search_rows(svs_index* idx, const float* queries, int32_t nq, 
     c->out_r_pin[i] = (int64_t)S[p] + lo;
   }
   deliver_results(c, nq, count, k, out_scores, out_rows);
+  return SVS_OK;
+}
+
+int32_t svs_index_search_above(svs_index* idx, const float* queries, int32_t nq, int32_t d, const float* min_scores, int32_t limit,
+                               float* out_scores, int64_t* out_rows, int32_t* out_counts, int64_t* out_totals) {
+  launch_reset();
+  if (!idx) return fail(SVS_ERR_INVALID, "null index");
+  RefGuard guard(idx);
+  std::shared_lock<std::shared_mutex> geo(idx->rw);
+  int rc = check_query_args(idx, queries, nq, d);
+  if (rc != SVS_OK) return rc;
+  if (nq > 0 && !min_scores) return fail(SVS_ERR_INVALID, "null min_scores");
+  for (int32_t q = 0; q < nq; ++q)
+    if (min_scores[q] != min_scores[q]) return fail(SVS_ERR_INVALID, "svs_index_search_above: the cut-off of query %d is NaN", (int)q);
+  if (!out_counts) return fail(SVS_ERR_INVALID, "null out_counts");
+  if (limit > 0 && nq > 0 && (!out_scores || !out_rows)) return fail(SVS_ERR_INVALID, "null output");
+  if (nq == 0) return SVS_OK;
+  const int64_t n = idx->n;
+  const int64_t live = n - (int64_t)idx->dead_list.size();
+  const int lim = (int)std::min<int64_t>(std::max(limit, 0), live);   // entries a query can have
+  const int ls = std::min(lim, SORT_CAP);                              // ... and the most the device writes for one
+  HIP_TRY(hipSetDevice(idx->device));
+  if ((rc = staging_wait(idx)) != SVS_OK) return rc;
+  Ctx* c = nullptr;
+  if ((rc = ctx_acquire(idx, nullptr, true, &c)) != SVS_OK) return rc;
+  CtxGuard cg{idx, c};
+  hipStream_t st = c->stream;
+  const size_t qn = (size_t)nq * (size_t)d, on = std::max<size_t>((size_t)nq * (size_t)ls, 1);
+  const int64_t sstride = (n + 3) & ~(int64_t)3;
+  if ((rc = c->q_dev.grow(qn)) != SVS_OK || (rc = c->q_pin.grow(qn)) != SVS_OK) return rc;
+  if ((rc = c->out_s_pin.grow(on)) != SVS_OK || (rc = c->out_r_pin.grow(on)) != SVS_OK) return rc;
+  if ((rc = c->above_cnt_pin.grow((size_t)nq)) != SVS_OK || (rc = c->above_tot_pin.grow((size_t)nq)) != SVS_OK) return rc;
+  if ((rc = c->scores.grow((size_t)sstride)) != SVS_OK) return rc;
+  if ((rc = grow_select_scratch(c, 1, st)) != SVS_OK) return rc;
+  const SingleRoute route = single_route(idx, idx->variant.load(), false);   // the kernel svs_index_scores_n runs
+  const bool masked = !idx->dead_list.empty();
+  const uint32_t* dead_bits = masked ? idx->dead_bits_dev.p : nullptr;
+  const int64_t per_block = (int64_t)FA_THREADS * SEL_VPT * 4;
+  const unsigned blocks = (unsigned)((n + per_block - 1) / per_block);
+  memcpy(c->q_pin, queries, qn * sizeof(float));
+  HIP_TRY(hipMemcpyAsync(c->q_dev, c->q_pin, qn * sizeof(float), hipMemcpyHostToDevice, st));
+  // every query back to back: score pass, filter, final -- the context's one score vector, header and candidate list
+  // are reused in stream order; no host wait in between
+  for (int32_t q = 0; q < nq && rc == SVS_OK; ++q) {
+    launch_record("gemv", n, 1);
+    if ((rc = launch_scores(idx, c, route, c->q_dev + (size_t)q * d, c->scores, st)) != SVS_OK) break;
+    launch_record("above_filter_kernel", n, 1);
+    hipLaunchKernelGGL(above_filter_kernel, dim3(blocks), dim3(FA_THREADS), 0, st, (const float*)c->scores.p, n, score_key(min_scores[q]),
+                       dead_bits, c->hist.p, c->cand.p);
+    hipLaunchKernelGGL(above_final_kernel, dim3(1), dim3(FINAL_THREADS), 0, st, c->hist.p, (const uint64_t*)c->cand.p, lim, idx->row_offset,
+                       c->out_s_pin + (size_t)q * ls, c->out_r_pin + (size_t)q * ls, c->above_cnt_pin + q, c->above_tot_pin + q);
+  }
+  if (rc == SVS_OK) {
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) rc = fail(SVS_ERR_DEVICE, "search_above launch: %s", hipGetErrorString(e));
+  }
+  if (rc != SVS_OK) {
+    (void)hipStreamSynchronize(st);
+    return rc;
+  }
+  HIP_TRY(hipStreamSynchronize(st));
+  for (int32_t q = 0; q < nq; ++q) {
+    const int64_t total = c->above_tot_pin[q];
+    int count = c->above_cnt_pin[q];
+    if (count < 0) {
+      // Outside the device-complete zone (the list overflowed, or the wanted prefix is longer than the LDS sort): the
+      // exact top-k stage over the same score vector, masked, with k = min(limit, total) -- the best that many live
+      // rows are the first that many rows at or above the cut-off.
+      count = (int)std::min<int64_t>(lim, total);
+      if ((rc = c->redo_s_pin.grow((size_t)count)) != SVS_OK || (rc = c->redo_r_pin.grow((size_t)count)) != SVS_OK) return rc;
+      launch_record("gemv", n, 1);
+      if ((rc = launch_scores(idx, c, route, c->q_dev + (size_t)q * d, c->scores, st)) == SVS_OK) {
+        if (masked)
+          hipLaunchKernelGGL(mask_dead_rows_kernel, dim3(64), dim3(256), 0, st, c->scores.p, sstride, 1, (const uint32_t*)idx->dead_dev.p,
+                             (int64_t)idx->dead_list.size(), n, (int64_t)0);
+        const SelectPath path = select_path(n, count);   // (recorded: which stage the re-run took)
+        launch_record(path == SelectPath::WINDOW ? "select_window_hist_kernel" : (path == SelectPath::SORT ? "keys_build_kernel" : "select_final_kernel"), n, 1);
+        rc = run_select(idx, c, c->scores, n, sstride, 1, count, count, c->redo_s_pin, c->redo_r_pin, st, idx->row_offset);
+      }
+      if (rc == SVS_OK) {
+        hipError_t e = hipGetLastError();
+        if (e != hipSuccess) rc = fail(SVS_ERR_DEVICE, "search_above re-run: %s", hipGetErrorString(e));
+      }
+      if (rc != SVS_OK) {
+        (void)hipStreamSynchronize(st);
+        return rc;
+      }
+      HIP_TRY(hipStreamSynchronize(st));
+      memcpy(out_scores + (size_t)q * limit, c->redo_s_pin, (size_t)count * sizeof(float));
+      memcpy(out_rows + (size_t)q * limit, c->redo_r_pin, (size_t)count * sizeof(int64_t));
+    } else if (count > 0) {
+      memcpy(out_scores + (size_t)q * limit, c->out_s_pin + (size_t)q * ls, (size_t)count * sizeof(float));
+      memcpy(out_rows + (size_t)q * limit, c->out_r_pin + (size_t)q * ls, (size_t)count * sizeof(int64_t));
+    }
+    out_counts[q] = count;
+    if (out_totals) out_totals[q] = total;
+  }
   return SVS_OK;
 }
 

@@ -331,6 +331,50 @@ class DeviceIndex:
             self._unpin(h)
         return [(scores[s, :c], out_rows[s, :c]) for s, c in enumerate(counts.tolist())]
 
+    def search_batch_above(self, queries: np.ndarray, min_scores, limit: int) -> List[Tuple[np.ndarray, np.ndarray, int]]:
+        """Threshold search (svs_index_search_above): for each row of ``queries`` (nq, D) every live row whose score
+        is at or above ``min_scores[q]`` -- compared in the key space of the top-k order: -0.0 == +0.0, a NaN score
+        qualifies for every cut-off and sorts first -- best first, at most ``limit`` of them.  Returns one
+        ``(scores f32 (count,), rows i64 (count,), total)`` per query: count = min(max(limit, 0), total), total = the
+        number of qualifying rows, exact however large.  ``limit=0`` only counts.  A NaN cut-off is a ValueError."""
+        assert isinstance(limit, int)
+        q = np.ascontiguousarray(queries, dtype=np.float32)
+        if q.ndim != 2:
+            raise ValueError(f"queries must be 2-D, got shape {q.shape}")
+        nq, d = q.shape
+        cut = np.ascontiguousarray(min_scores, dtype=np.float32).reshape(-1)
+        if len(cut) != nq:
+            raise ValueError(f"min_scores has {len(cut)} entries for {nq} queries")
+        if np.isnan(cut).any():
+            raise ValueError(f"the cut-off of query {int(np.argmax(np.isnan(cut)))} is NaN")
+        h = self._pinned_handle()
+        try:
+            # (clamped before allocating and before the int32 argument, as in search_batch)
+            info = _native.IndexInfo()
+            _native.check(self._quick.svs_index_info(h, C.byref(info)))
+            k = min(max(limit, 0), max(int(info.n) - int(info.n_masked), 0))
+            scores = np.empty((nq, k), dtype=np.float32)
+            rows = np.empty((nq, k), dtype=np.int64)
+            counts = np.zeros(nq, dtype=np.int32)
+            totals = np.zeros(nq, dtype=np.int64)
+            # (the one call that releases the GIL; a count-only call passes no result buffers)
+            _native.check(self._lib.svs_index_search_above(h, q.ctypes.data, nq, d, cut.ctypes.data, k,
+                                                           scores.ctypes.data if k else None, rows.ctypes.data if k else None,
+                                                           counts.ctypes.data, totals.ctypes.data))
+        finally:
+            self._unpin(h)
+        return [(scores[i, :c], rows[i, :c], t) for i, (c, t) in enumerate(zip(counts.tolist(), totals.tolist()))]
+
+    def search_above(self, query_vec: np.ndarray, min_score: float, limit: int) -> Tuple[List[Tuple[float, int]], int]:
+        """Every live row scoring at or above ``min_score``, best first, at most ``limit``: ([(score, row)], total),
+        total = how many rows qualify (``limit=0``: only that).  See ``search_batch_above``."""
+        assert isinstance(limit, int)
+        q = np.asarray(query_vec, dtype=np.float32)
+        if q.ndim != 1:
+            raise ValueError(f"query must be 1-D, got shape {q.shape}")
+        s, r, total = self.search_batch_above(q[None, :], [min_score], limit)[0]
+        return list(zip(s.astype(np.float64).tolist(), r.tolist())), total
+
     def neighbors(self, rows, n: int) -> Tuple[np.ndarray, np.ndarray]:
         """The ``n`` nearest stored rows of each listed stored row (GLOBAL indices, any order, repeats allowed), the
         row itself excluded: (scores f32 (len(rows), count), rows i64 (len(rows), count)), count = min(max(n, 0),

@@ -31,7 +31,7 @@ import numpy as np
 
 from .index import DeviceIndex
 from .matrix import (DeviceEmbeddingsMatrix, ids_of_batch, ids_of_pairs, ids_of_rows, neighbors_held, search_mapped,
-                     search_within_held, search_within_many_held, single_search)
+                     search_above_held, search_within_held, search_within_many_held, single_search)
 
 _LOG = logging.getLogger(__name__)
 
@@ -466,6 +466,26 @@ class KB:
         _LOG.info(f"retrieved top {n} documents")
         return res
 
+    def retrieve_above(self, query: str, min_score: float, n: int) -> Tuple[List[Dict[str, Any]], int]:
+        """Every document whose score is at or above ``min_score``, best first, at most ``n`` of them, and how many
+        qualify in all: (``retrieve``-shaped list, total).  ``n=0`` only counts.  The cut is made on the device
+        (svs_index_search_above): neither a guessed ``n`` nor the score vector crosses the bus.  A NaN cut-off
+        raises ValueError."""
+        if min_score != min_score:
+            raise ValueError("min_score is NaN")
+        _LOG.info(f"retrieving {n} documents with query string: {query}")
+        assert self.db is not None
+        self.embeddings_matrix.get_sync(self.db)
+        query_vec = np.array(self._embed([query])[0], dtype=np.float32)
+        _LOG.info("got embedding for query!")
+        emb_ids, total = self.embeddings_matrix.search_above(query_vec, float(min_score), n)   # HIP
+        _LOG.info(f"computed {self.embeddings_matrix.index.shape[0]} cosine similarities")
+        with self.db.transaction():
+            docs = self.db.fetch_docs_for_embeddings([e for _, e in emb_ids])
+        res = [{"score": score, "doc": docs[e]} for score, e in emb_ids]
+        _LOG.info(f"retrieved top {n} documents")
+        return res, total
+
     def retrieve_similar(self, doc_id: int, n: int) -> List[Dict[str, Any]]:
         """"More like this": the n documents nearest to the STORED document ``doc_id``, itself excluded, shaped like
         ``retrieve`` ([{'score', 'doc'}]).  The reference can only loop ``np.dot(M, M[i])`` + ``get_top_k``
@@ -778,6 +798,37 @@ class AsyncKB:
             res = await loop.run_in_executor(None, heavy)
         _LOG.info(f"retrieved top {n} documents")
         return res
+
+    async def retrieve_above(self, query: str, min_score: float, n: int) -> Tuple[List[Dict[str, Any]], int]:
+        """Async twin of ``KB.retrieve_above``, structured as ``retrieve``: the reference to the matrix under the
+        lock, the threshold search on an executor thread outside it, the docs under the lock."""
+        if min_score != min_score:
+            raise ValueError("min_score is NaN")
+        _LOG.info(f"retrieving {n} documents with query string: {query}")
+        loop = asyncio.get_running_loop()
+        async with self._get_lock():
+            db = await self._ensure_db()
+            await self.embeddings_matrix.get(db)
+            idx, lookup = self.embeddings_matrix.hold()
+        try:
+            query_vec = np.array((await self._embed([query]))[0], dtype=np.float32)
+            _LOG.info("got embedding for query!")
+            emb_ids, total = await loop.run_in_executor(None, lambda: search_above_held(idx, lookup, query_vec, float(min_score), n,
+                                                                                              self.embeddings_matrix.hold))
+            _LOG.info(f"computed {idx.shape[0]} cosine similarities")
+        finally:
+            idx.release()
+        async with self._get_lock():
+            db = await self._ensure_db()
+
+            def heavy() -> List[Dict[str, Any]]:
+                with db.transaction():
+                    docs = db.fetch_docs_for_embeddings([e for _, e in emb_ids])
+                return [{"score": s, "doc": docs[e]} for s, e in emb_ids]
+
+            res = await loop.run_in_executor(None, heavy)
+        _LOG.info(f"retrieved top {n} documents")
+        return res, total
 
     async def retrieve_many(self, queries: List[str], n: int) -> List[List[Dict[str, Any]]]:
         """Async twin of ``KB.retrieve_many``.  Same structure as

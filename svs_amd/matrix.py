@@ -155,6 +155,21 @@ def neighbors_held(idx, lookup: _Lookup, emb_ids, n: int,
     return search_mapped(hold if hold is not None else _no_hold, (idx, lookup), native, finish)
 
 
+def search_above_held(idx, lookup: _Lookup, query_vec: np.ndarray, min_score: float, n: int,
+                      hold: Optional[Callable[[], tuple]] = None) -> Tuple[List[Tuple[float, int]], int]:
+    """Threshold search on a held (index, lookup): ``idx.search_above`` (svs_index_search_above), rows -> ids:
+    ([(score, emb_id)], total).  ``hold`` as in ``search_within_held``."""
+    def native(idx, lookup, *_):
+        return idx, idx.search_above(query_vec, min_score, n)
+
+    def finish(res, arr):
+        used, (rows, total) = res
+        off = int(getattr(used, "row_offset", 0))
+        return [(score, int(arr[row - off])) for score, row in rows], int(total)
+
+    return search_mapped(hold if hold is not None else _no_hold, (idx, lookup), native, finish)
+
+
 def _no_hold():
     raise RuntimeError("the rows of the embeddings matrix were renumbered during the search")
 
@@ -411,6 +426,15 @@ class DeviceEmbeddingsMatrix:
         idx, lookup = self.hold()
         try:
             return search_within_held(idx, lookup, query_vec, n, emb_ids, self.hold)
+        finally:
+            idx.release()
+
+    def search_above(self, query_vec: np.ndarray, min_score: float, n: int) -> Tuple[List[Tuple[float, int]], int]:
+        """Every stored embedding scoring at or above ``min_score``, best first, at most ``n``:
+        ([(score, emb_id)], total qualifying) (``KB.retrieve_above``)."""
+        idx, lookup = self.hold()
+        try:
+            return search_above_held(idx, lookup, query_vec, min_score, n, self.hold)
         finally:
             idx.release()
 

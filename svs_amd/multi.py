@@ -206,6 +206,9 @@ class MultiDeviceIndex:
             if np.any((r < 0) | (r >= self.n)):
                 raise ValueError("row out of range")
 
+    def search_above(self, query_vec: np.ndarray, min_score: float, limit: int):
+        raise NotImplementedError("threshold search is per device: call search_above on a DeviceIndex (a shard's totals and lists are its own)")
+
     def top_pairs(self, n: int):
         raise NotImplementedError("pairwise scores need the whole corpus on one device; build a DeviceIndex for it")
 
