@@ -115,6 +115,7 @@ INTERNAL = {
                                                    C.POINTER(C.c_int64)]),
     "svs_internal_compact_plan": (C.c_int64, [_P, C.c_int64, C.c_int64, C.c_int64, _P, C.c_int64]),
     "svs_internal_segments_plan": (C.c_int64, [_P, _P, C.c_int64, C.c_int32, _P, C.c_int64, _P, C.POINTER(C.c_int64)]),
+    "svs_internal_live_rows": (C.c_int64, [_P, C.c_int64, C.c_int64, C.c_int64, _P, _P, C.c_int64]),
     "svs_internal_compact": (C.c_int32, [_P, C.c_int64, _P, C.c_int64, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
 }
 

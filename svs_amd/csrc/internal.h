@@ -119,6 +119,12 @@ int32_t svs_internal_compact(svs_index* idx, int64_t bounce_rows, int64_t* out_o
  * or SVS_ERR_INVALID. */
 int64_t svs_internal_segments_plan(const int64_t* sizes, const int32_t* seg_query, int64_t nseg, int32_t w, int64_t* tiles, int64_t cap,
                                    int64_t* seg_off, int64_t* total_rows);
+/* The device row list of svs_index_search_rows and of every segment of svs_index_search_segments, pure host code, no
+ * index: rows[nrows] = global rows in any order, repeats allowed, every one in [row_offset, row_offset + n);
+ * dead_flags[n] = non-zero for a tombstoned local row.  out[0 .. m) gets the distinct live listed rows as local rows,
+ * ascending; cap = the room in out, at least nrows.  Returns m, or SVS_ERR_INVALID with out untouched. */
+int64_t svs_internal_live_rows(const int64_t* rows, int64_t nrows, int64_t row_offset, int64_t n, const uint8_t* dead_flags, uint32_t* out,
+                               int64_t cap);
 /* multi.hip -> svs_amd.hip: carries a worker thread's error message over to the caller's thread */
 int32_t svs_internal_set_error(int32_t code, const char* msg);
 #ifdef __cplusplus

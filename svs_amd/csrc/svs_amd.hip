@@ -1329,21 +1329,63 @@ int launch_gather_dt(const svs_index* idx, const void* q, const float* q_scales,
               ld16 * 16);
 }
 
-// Stages queries [q0, q0 + nq) of the call (f32 in c->q_dev) in the corpus dtype and scores them over the list.
-int launch_gather(const svs_index* idx, Ctx* c, const float* q_dev, int nq, const uint32_t* list, int64_t m, float* scores,
-                  int64_t sstride, hipStream_t st) {
+// nq f32 queries on the device as the gather kernels read them: [nq][ld] in the corpus dtype, zero padded, in the
+// context's staging buffers.  *q_scales: their scales (fp8), else null.
+int stage_gather_queries(const svs_index* idx, Ctx* c, const float* q_dev, int nq, const void** q, const float** q_scales, hipStream_t st) {
   int rc;
+  *q_scales = nullptr;
   if (idx->dtype == SVS_DTYPE_F32) {
     const float* qs = nullptr;
     if ((rc = stage_queries_f32(idx, c, q_dev, nq, nq, &qs, st)) != SVS_OK) return rc;
-    return launch_gather_dt<0>(idx, qs, nullptr, nq, list, m, scores, sstride, st);
-  }
-  if (idx->dtype == SVS_DTYPE_F16) {
+    *q = qs;
+  } else if (idx->dtype == SVS_DTYPE_F16) {
     if ((rc = stage_queries_f16(idx, c, q_dev, nq, nq, st)) != SVS_OK) return rc;
-    return launch_gather_dt<1>(idx, c->qh, nullptr, nq, list, m, scores, sstride, st);
+    *q = c->qh.p;
+  } else {
+    if ((rc = stage_queries_fp8(idx, c, q_dev, nq, nq, false, st)) != SVS_OK) return rc;
+    *q = c->q8.p;
+    *q_scales = c->q8s.p;
   }
-  if ((rc = stage_queries_fp8(idx, c, q_dev, nq, nq, false, st)) != SVS_OK) return rc;
-  return launch_gather_dt<2>(idx, c->q8, c->q8s, nq, list, m, scores, sstride, st);
+  return SVS_OK;
+}
+
+// f(Int<DT>): the corpus dtype as the gather kernels' template argument
+template <class F>
+auto for_gather_dtype(const svs_index* idx, F&& f) {
+  return idx->dtype == SVS_DTYPE_F32 ? f(Int<0>{}) : (idx->dtype == SVS_DTYPE_F16 ? f(Int<1>{}) : f(Int<2>{}));
+}
+
+// Stages queries [q0, q0 + nq) of the call (f32 in c->q_dev) in the corpus dtype and scores them over the list.
+int launch_gather(const svs_index* idx, Ctx* c, const float* q_dev, int nq, const uint32_t* list, int64_t m, float* scores,
+                  int64_t sstride, hipStream_t st) {
+  const void* q = nullptr;
+  const float* qs = nullptr;
+  const int rc = stage_gather_queries(idx, c, q_dev, nq, &q, &qs, st);
+  if (rc != SVS_OK) return rc;
+  return for_gather_dtype(idx, [&](auto dt) { return launch_gather_dt<dt()>(idx, q, qs, nq, list, m, scores, sstride, st); });
+}
+
+// Top `count` of nq queries (f32 on the device) over a device row list: m local rows, ascending.  The context's score
+// matrix and select scratch are the caller's to size.  out_r receives POSITIONS in the list: list_positions_to_rows.
+int enqueue_list_search(svs_index* idx, Ctx* c, const float* q_dev, int nq, const uint32_t* list, int64_t m, int count, float* out_s,
+                        int64_t* out_r, hipStream_t st) {
+  const int64_t sstride = (m + 3) & ~(int64_t)3;
+  const int rc = launch_gather(idx, c, q_dev, nq, list, m, c->scores, sstride, st);
+  return rc != SVS_OK ? rc : run_select(idx, c, c->scores, m, sstride, nq, count, count, out_s, out_r, st, 0);
+}
+
+// ... and, once they have arrived in pinned memory, the positions -> global rows, in place.  S: the list on the host;
+// seg: the segment it belongs to (the error's text), -1 for the one list of svs_index_search_rows.
+int list_positions_to_rows(int64_t* r, size_t cnt, const uint32_t* S, int64_t m, int64_t lo, int seg) {
+  for (size_t i = 0; i < cnt; ++i) {
+    const int64_t p = r[i];
+    if (p < 0 || p >= m)
+      return seg < 0 ? fail(SVS_ERR_DEVICE, "search_rows: position %lld outside the %lld listed rows", (long long)p, (long long)m)
+                     : fail(SVS_ERR_DEVICE, "search_segments: position %lld outside the %lld listed rows of segment %d", (long long)p,
+                            (long long)m, seg);
+    r[i] = (int64_t)S[p] + lo;
+  }
+  return SVS_OK;
 }
 
 // ---- segmented filtered search: the small segments of a call in two launches (segments.h) -----------
@@ -1374,18 +1416,11 @@ void launch_gather_segments_dt(const svs_index* idx, const void* q, const float*
 // Stages the call's nq queries (f32 in q_dev) in the corpus dtype, once, and scores every tile
 int launch_gather_segments(const svs_index* idx, Ctx* c, const float* q_dev, int nq, const uint32_t* list, const SegTile* tiles,
                            int64_t ntiles, int64_t total_rows, int nseg, float* scores, hipStream_t st) {
-  int rc;
-  if (idx->dtype == SVS_DTYPE_F32) {
-    const float* qs = nullptr;
-    if ((rc = stage_queries_f32(idx, c, q_dev, nq, nq, &qs, st)) != SVS_OK) return rc;
-    launch_gather_segments_dt<0>(idx, qs, nullptr, list, tiles, ntiles, total_rows, nseg, scores, st);
-  } else if (idx->dtype == SVS_DTYPE_F16) {
-    if ((rc = stage_queries_f16(idx, c, q_dev, nq, nq, st)) != SVS_OK) return rc;
-    launch_gather_segments_dt<1>(idx, c->qh, nullptr, list, tiles, ntiles, total_rows, nseg, scores, st);
-  } else {
-    if ((rc = stage_queries_fp8(idx, c, q_dev, nq, nq, false, st)) != SVS_OK) return rc;
-    launch_gather_segments_dt<2>(idx, c->q8, c->q8s, list, tiles, ntiles, total_rows, nseg, scores, st);
-  }
+  const void* q = nullptr;
+  const float* qs = nullptr;
+  const int rc = stage_gather_queries(idx, c, q_dev, nq, &q, &qs, st);
+  if (rc != SVS_OK) return rc;
+  for_gather_dtype(idx, [&](auto dt) { launch_gather_segments_dt<dt()>(idx, q, qs, list, tiles, ntiles, total_rows, nseg, scores, st); });
   return SVS_OK;
 }
 
@@ -1657,6 +1692,43 @@ struct CtxGuard {
   ~CtxGuard() { ctx_release(i, c); }
 };
 
+// A host-driven call's hold on a search context and the context's own stream.  Declared after validation, under the
+// entry's RefGuard and geometry lock, and opened at once.  What it guarantees: no context returns to the free list with
+// work in flight -- whatever the call enqueued has drained when the frame goes, on EVERY exit.  A context taken from the
+// list with async_pending false is therefore idle, and the next host call may memcpy into its pinned buffers at once.
+struct HostCall {
+  svs_index* idx;
+  Ctx* c = nullptr;
+  bool busy = false;   // enqueued since the last wait
+  explicit HostCall(svs_index* i) : idx(i) {}
+  HostCall(const HostCall&) = delete;
+  ~HostCall() {
+    if (c && busy) (void)hipStreamSynchronize(c->stream);
+    if (c) ctx_release(idx, c);
+  }
+  int open() {
+    HIP_TRY(hipSetDevice(idx->device));
+    const int rc = staging_wait(idx);
+    return rc != SVS_OK ? rc : ctx_acquire(idx, nullptr, true, &c);
+  }
+  // The stream to enqueue on.  Asking for it marks the call as having work in flight: an exit before that pays no
+  // synchronise, one after it drains -- so ask again for what is enqueued behind a wait().
+  hipStream_t stream() { busy = true; return c->stream; }
+  // The launches so far were accepted ("<entry> launch: ..." / "<entry> re-run: ..."); a refused one drains the stream.
+  int launched(const char* entry, bool rerun = false) {
+    const hipError_t e = hipGetLastError();
+    if (e == hipSuccess) return SVS_OK;
+    (void)wait();
+    return fail(SVS_ERR_DEVICE, rerun ? "%s re-run: %s" : "%s launch: %s", entry, hipGetErrorString(e));
+  }
+  int wait() {
+    busy = false;   // (a stream whose wait failed has nothing left to wait for either)
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return SVS_OK;
+  }
+  int close(const char* entry, bool rerun = false) { const int rc = launched(entry, rerun); return rc != SVS_OK ? rc : wait(); }
+};
+
 // ---- pairwise (document_top_pairwise_scores, src/svs/kb.py:1642-1671) -----------------------
 // rows [r0, r0 + nrows) of the corpus as f32 queries (what the index holds), [nrows][d]
 int dequant_rows_to(svs_index* idx, int64_t r0, int64_t nrows, float* out, hipStream_t st) {
@@ -1703,9 +1775,10 @@ struct DevTmp {   // frees on scope exit
   ~DevTmp() { for (void* q : p) (void)hipFree(q); }
 };
 
-int top_pairs_materialised(svs_index* idx, Ctx* c, int variant, int64_t n, int count, float* out_scores, int64_t* out_i, int64_t* out_j) {
+int top_pairs_materialised(svs_index* idx, HostCall& fr, int variant, int64_t n, int count, float* out_scores, int64_t* out_i, int64_t* out_j) {
   const int64_t np = (n + 3) & ~(int64_t)3;
-  hipStream_t st = c->stream;
+  Ctx* const c = fr.c;
+  const hipStream_t st = fr.stream();
   DevTmp tmp;
   float *qbuf = nullptr, *S = nullptr, *d_s = nullptr;
   int64_t* d_r = nullptr;
@@ -1718,7 +1791,7 @@ int top_pairs_materialised(svs_index* idx, Ctx* c, int variant, int64_t n, int c
   std::vector<int64_t> flat_rows((size_t)count);
   HIP_TRY(hipMemcpyAsync(out_scores, d_s, (size_t)count * sizeof(float), hipMemcpyDeviceToHost, st));
   HIP_TRY(hipMemcpyAsync(flat_rows.data(), d_r, (size_t)count * sizeof(int64_t), hipMemcpyDeviceToHost, st));
-  HIP_TRY(hipStreamSynchronize(st));
+  if ((rc = fr.wait()) != SVS_OK) return rc;
   for (int t = 0; t < count; ++t) {
     out_i[t] = flat_rows[t] / np + idx->row_offset;
     out_j[t] = flat_rows[t] % np + idx->row_offset;
@@ -1734,13 +1807,14 @@ int top_pairs_materialised(svs_index* idx, Ctx* c, int variant, int64_t n, int c
 // after each chunk they are appended to one global (score, i, j) list.  (3) The host orders the
 // list by (score desc, i desc, j desc) -- the reference's flat upper-triangle index, descending --
 // and keeps `count`.  Exact; the list holds about count * (n / P)^2 pairs.
-int top_pairs_tiled(svs_index* idx, Ctx* c, int variant, int count, float* out_scores, int64_t* out_i, int64_t* out_j) {
+int top_pairs_tiled(svs_index* idx, HostCall& fr, int variant, int count, float* out_scores, int64_t* out_i, int64_t* out_j) {
   const int64_t n = idx->n;
   constexpr int QC = 1024;                 // query rows per chunk
   // (every chunk holds more than GQ queries, so all take the family of a full one: it must have a pair mode)
   const BatchRoute::Family fam = batch_route(idx, variant, QC).family;
   if (fam != BatchRoute::TILED_F32 && fam != BatchRoute::TILED_EB) return fail(SVS_ERR_UNSUPPORTED, "pairwise scores over %lld rows need rows of whole 128-byte lines (d = %d)", (long long)n, idx->d);
-  hipStream_t st = c->stream;
+  Ctx* const c = fr.c;
+  const hipStream_t st = fr.stream();
   int rc;
   // prefix block: at least `count` live pairs inside it
   int64_t P = std::min<int64_t>(n, count > SEL_KMAX ? 8192 : 16384);
@@ -1779,7 +1853,7 @@ int top_pairs_tiled(svs_index* idx, Ctx* c, int variant, int count, float* out_s
   HIP_TRY(hipGetLastError());
   uint32_t hs[4] = {0, 0, 0, 0};
   HIP_TRY(hipMemcpyAsync(hs, gstate, 16, hipMemcpyDeviceToHost, st));
-  HIP_TRY(hipStreamSynchronize(st));
+  if ((rc = fr.wait()) != SVS_OK) return rc;
   if (hs[1] || hs[0] > LIST_CAP)
     return fail(SVS_ERR_UNSUPPORTED, "top_pairs: more than %u pairs (or 32,768 for one row) score at least the %d-th best of the first %lld rows: "
                                       "near-duplicate documents en masse", LIST_CAP, count, (long long)P);
@@ -2320,22 +2394,20 @@ int next_redo_group(const int64_t* res_rows, int count, int64_t* q, int64_t q1, 
 // per query.  stage(grp, m) puts the group's queries into q_buf; the search writes tmp_s / tmp_r and finish(m) enqueues what
 // moves them into redo_s_pin / redo_r_pin -- tmp_s null: the search writes there itself.  *n_redo grows by the positions re-run.
 template <class Stage, class Finish>
-int rerun_overflowed(svs_index* idx, Ctx* c, int64_t q0, int64_t q1, int count, int kk, const DevBuf<float>& q_buf, float* tmp_s,
+int rerun_overflowed(svs_index* idx, HostCall& fr, int64_t q0, int64_t q1, int count, int kk, const DevBuf<float>& q_buf, float* tmp_s,
                      int64_t* tmp_r, Stage stage, Finish finish, int* n_redo) {
   const int redo_max = (int)std::min<int64_t>(REDO_BATCH, std::max<int64_t>(1, ((int64_t)2 << 30) / (4 * std::max<int64_t>(idx->n, 1))));
+  Ctx* c = fr.c;
   int64_t grp[REDO_BATCH];
   int rc;
   while (const int m = next_redo_group(c->out_r_pin, count, &q0, q1, redo_max, grp)) {
     *n_redo += m;
     if ((rc = c->redo_s_pin.grow((size_t)REDO_BATCH * count)) != SVS_OK || (rc = c->redo_r_pin.grow((size_t)REDO_BATCH * count)) != SVS_OK) return rc;
+    const hipStream_t st = fr.stream();   // (asked for per group: each one ends in a wait)
     if ((rc = stage(grp, m)) != SVS_OK) return rc;
-    if ((rc = enqueue_search(idx, c, q_buf, m, kk, kk, tmp_s ? tmp_s : c->redo_s_pin.p, tmp_s ? tmp_r : c->redo_r_pin.p, c->stream, false)) != SVS_OK) {
-      (void)hipStreamSynchronize(c->stream);
-      return rc;
-    }
+    if ((rc = enqueue_search(idx, c, q_buf, m, kk, kk, tmp_s ? tmp_s : c->redo_s_pin.p, tmp_s ? tmp_r : c->redo_r_pin.p, st, false)) != SVS_OK) return rc;
     finish(m);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipStreamSynchronize(c->stream));
+    if ((rc = fr.close("search", true)) != SVS_OK) return rc;
     for (int j = 0; j < m; ++j) {
       memcpy(c->out_s_pin + (size_t)grp[j] * count, c->redo_s_pin + (size_t)j * count, (size_t)count * sizeof(float));
       memcpy(c->out_r_pin + (size_t)grp[j] * count, c->redo_r_pin + (size_t)j * count, (size_t)count * sizeof(int64_t));
@@ -2357,12 +2429,11 @@ void deliver_results(const Ctx* c, int64_t nq, int count, int k, float* out_scor
   }
 }
 
-// A caller's list of global rows: every one a row of this index.  *ascending (may be null): strictly, so that the list
-// needs neither sorting nor deduplication.
-int check_row_list(const svs_index* idx, const int64_t* rows, int64_t nrows, bool* ascending) {
+// A caller's list of global rows: every one a row of an index of n rows from row `lo`.  *ascending (may be null):
+// strictly, so that the list needs neither sorting nor deduplication.
+int check_row_list(const int64_t* rows, int64_t nrows, int64_t lo, int64_t n, bool* ascending) {
   if (nrows < 0) return fail(SVS_ERR_INVALID, "nrows must be >= 0");
   if (nrows > 0 && !rows) return fail(SVS_ERR_INVALID, "null row list");
-  const int64_t lo = idx->row_offset, n = idx->n;
   if (ascending) *ascending = true;
   for (int64_t t = 0; t < nrows; ++t) {
     const int64_t r = rows[t] - lo;
@@ -2370,6 +2441,37 @@ int check_row_list(const svs_index* idx, const int64_t* rows, int64_t nrows, boo
       return fail(SVS_ERR_INVALID, "row %lld out of range [%lld, %lld)", (long long)rows[t], (long long)lo, (long long)(lo + n));
     if (ascending && t && rows[t] <= rows[t - 1]) *ascending = false;
   }
+  return SVS_OK;
+}
+
+// The live rows of a checked list of global rows, as local u32 rows, ascending and without repeats, into dst (room for
+// nrows); returns how many.  ascending: the list is strictly so already (check_row_list) and is filtered as it stands;
+// otherwise it is sorted in tmp first, which may throw std::bad_alloc.  No HIP in it: svs_internal_live_rows.
+int64_t live_rows_ascending(const int64_t* rows, int64_t nrows, int64_t lo, const uint8_t* dead_flag, bool ascending,
+                            std::vector<uint32_t>& tmp, uint32_t* dst) {
+  int64_t m = 0;
+  if (ascending) {
+    for (int64_t t = 0; t < nrows; ++t) {
+      const uint32_t r = (uint32_t)(rows[t] - lo);
+      if (!dead_flag[r]) dst[m++] = r;
+    }
+    return m;
+  }
+  tmp.resize((size_t)nrows);
+  for (int64_t t = 0; t < nrows; ++t) tmp[(size_t)t] = (uint32_t)(rows[t] - lo);
+  std::sort(tmp.begin(), tmp.end());
+  const size_t u = (size_t)(std::unique(tmp.begin(), tmp.end()) - tmp.begin());
+  for (size_t t = 0; t < u; ++t)
+    if (!dead_flag[tmp[t]]) dst[m++] = tmp[t];
+  return m;
+}
+
+// The call's qn query floats: caller -> pinned staging -> c->q_dev, one copy each
+int upload_queries(Ctx* c, const float* queries, size_t qn, hipStream_t st) {
+  int rc;
+  if ((rc = c->q_dev.grow(qn)) != SVS_OK || (rc = c->q_pin.grow(qn)) != SVS_OK) return rc;
+  memcpy(c->q_pin, queries, qn * sizeof(float));
+  HIP_TRY(hipMemcpyAsync(c->q_dev, c->q_pin, qn * sizeof(float), hipMemcpyHostToDevice, st));
   return SVS_OK;
 }
 
@@ -2623,20 +2725,20 @@ static int32_t search_host(svs_index* idx, const float* queries, int32_t nq, int
   if (out_count) *out_count = count;
   if (nq == 0 || count == 0) return SVS_OK;
   if (!out_scores || !out_rows) return fail(SVS_ERR_INVALID, "null output");
-  HIP_TRY(hipSetDevice(idx->device));
-  Ctx* c = nullptr;
-  if ((rc = ctx_acquire(idx, nullptr, true, &c)) != SVS_OK) return rc;
-  CtxGuard cg{idx, c};
+  HostCall fr(idx);
+  if ((rc = fr.open()) != SVS_OK) return rc;
+  Ctx* const c = fr.c;
   const size_t qn = (size_t)nq * (size_t)d, on = (size_t)nq * (size_t)count;
   if ((rc = c->q_dev.grow(qn)) != SVS_OK) return rc;
   if ((rc = c->q_pin.grow(qn)) != SVS_OK) return rc;
   if ((rc = c->out_s_pin.grow(on)) != SVS_OK || (rc = c->out_r_pin.grow(on)) != SVS_OK) return rc;
+  const hipStream_t st = fr.stream();
   // The final top-k kernel stores its k results straight into the pinned host
   // buffers (device-visible, zero-copy): no D2H copies on the latency path.
   const auto t_begin = std::chrono::steady_clock::now();
   auto stamp = [&](int i) { g_host_phase[i] = std::chrono::duration<double>(std::chrono::steady_clock::now() - t_begin).count(); };
   SearchPlan plan;
-  if ((rc = plan_search(idx, c, nq, count, count, c->stream, true, idx->variant.load(), &plan)) != SVS_OK) return rc;
+  if ((rc = plan_search(idx, c, nq, count, count, st, true, idx->variant.load(), &plan)) != SVS_OK) return rc;
   stamp(0);
   const int64_t mode = g_tune_upload.load();
   // f16 batches: the staging kernel (convert_queries_f16) reads the f32 queries STRAIGHT out of the pinned buffer, over PCIe,
@@ -2660,7 +2762,7 @@ static int32_t search_host(svs_index* idx, const float* queries, int32_t nq, int
       const size_t off = (size_t)q0 * d;
       memcpy(c->q_pin + off, queries + off, (size_t)nc * d * sizeof(float));
       // (rows [q0, q0 + nc) of the image; the last chunk also zeroes the padding rows behind the batch)
-      rc = stage_queries_f16(idx, c, c->q_pin + off, nc, q0 + nc == nq ? rows_total : q0 + nc, c->stream, q0);
+      rc = stage_queries_f16(idx, c, c->q_pin + off, nc, q0 + nc == nq ? rows_total : q0 + nc, st, q0);
     }
     plan.q_staged = c->qh.p;
   } else {
@@ -2668,19 +2770,18 @@ static int32_t search_host(svs_index* idx, const float* queries, int32_t nq, int
     for (size_t off = 0; off < qn; off += (size_t)262144) {
       const size_t len = std::min((size_t)262144, qn - off);
       memcpy(c->q_pin + off, queries + off, len * sizeof(float));
-      HIP_TRY(hipMemcpyAsync(c->q_dev + off, c->q_pin + off, len * sizeof(float), hipMemcpyHostToDevice, c->stream));
+      HIP_TRY(hipMemcpyAsync(c->q_dev + off, c->q_pin + off, len * sizeof(float), hipMemcpyHostToDevice, st));
     }
   }
   stamp(1);
-  if (rc == SVS_OK) rc = enqueue_prefix(idx, c, plan, q_src, c->stream);
-  if (rc == SVS_OK) rc = enqueue_main(idx, c, plan, q_src, c->out_s_pin, c->out_r_pin, c->stream);
+  if (rc == SVS_OK) rc = enqueue_prefix(idx, c, plan, q_src, st);
+  if (rc == SVS_OK) rc = enqueue_main(idx, c, plan, q_src, c->out_s_pin, c->out_r_pin, st);
   stamp(2);
+  if (rc == SVS_OK) rc = fr.wait();
   if (rc != SVS_OK) {
-    (void)hipStreamSynchronize(c->stream);
     plan_abandon(idx, plan);
     return rc;
   }
-  HIP_TRY(hipStreamSynchronize(c->stream));
   stamp(3);
   // The group's queries go to the front of q_dev in ONE copy -- whatever the main pass kept there is no longer needed, the
   // pinned buffer still holds every query of the call; a group that is not one run of queries is gathered first.
@@ -2691,11 +2792,11 @@ static int32_t search_host(svs_index* idx, const float* queries, int32_t nq, int
       for (int j = 0; j < m; ++j) memcpy(c->redo_q_pin + (size_t)j * d, c->q_pin + (size_t)grp[j] * d, (size_t)d * sizeof(float));
       src = c->redo_q_pin;
     }
-    HIP_TRY(hipMemcpyAsync(c->q_dev, src, (size_t)m * d * sizeof(float), hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync(c->q_dev, src, (size_t)m * d * sizeof(float), hipMemcpyHostToDevice, st));
     return SVS_OK;
   };
   int n_redo = 0;
-  if ((rc = rerun_overflowed(idx, c, 0, nq, count, count, c->q_dev, nullptr, nullptr, stage, [](int) {}, &n_redo)) != SVS_OK) return rc;
+  if ((rc = rerun_overflowed(idx, fr, 0, nq, count, count, c->q_dev, nullptr, nullptr, stage, [](int) {}, &n_redo)) != SVS_OK) return rc;
   g_host_phase[5] = (double)n_redo;   // (svs_internal_host_phases: queries of this call that were re-run)
   deliver_results(c, nq, count, k, out_scores, out_rows);
   stamp(4);
@@ -3005,20 +3106,18 @@ int32_t svs_index_scores_n(svs_index* idx, const float* query, int32_t d, float*
   if (out_capacity < idx->n)
     return fail(SVS_ERR_INVALID, "svs_index_scores_n: the index holds %lld rows, the output buffer %lld floats "
                                  "(rows were appended since it was sized?)", (long long)idx->n, (long long)out_capacity);
-  HIP_TRY(hipSetDevice(idx->device));
-  if ((rc = staging_wait(idx)) != SVS_OK) return rc;
-  Ctx* c = nullptr;
-  if ((rc = ctx_acquire(idx, nullptr, true, &c)) != SVS_OK) return rc;
-  CtxGuard cg{idx, c};
+  HostCall fr(idx);
+  if ((rc = fr.open()) != SVS_OK) return rc;
+  Ctx* const c = fr.c;
   if ((rc = c->q_dev.grow((size_t)d)) != SVS_OK) return rc;
   if ((rc = c->scores.grow((size_t)((idx->n + 3) & ~(int64_t)3))) != SVS_OK) return rc;
-  HIP_TRY(hipMemcpyAsync(c->q_dev, query, (size_t)d * sizeof(float), hipMemcpyHostToDevice, c->stream));
+  const hipStream_t st = fr.stream();
+  HIP_TRY(hipMemcpyAsync(c->q_dev, query, (size_t)d * sizeof(float), hipMemcpyHostToDevice, st));
   launch_record("gemv", idx->n, 1);
-  if ((rc = launch_scores(idx, c, single_route(idx, idx->variant.load(), false), c->q_dev, c->scores, c->stream)) != SVS_OK) return rc;
+  if ((rc = launch_scores(idx, c, single_route(idx, idx->variant.load(), false), c->q_dev, c->scores, st)) != SVS_OK) return rc;
   HIP_TRY(hipGetLastError());
-  HIP_TRY(hipMemcpyAsync(out_scores, c->scores, (size_t)idx->n * sizeof(float), hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(hipStreamSynchronize(c->stream));
-  return SVS_OK;
+  HIP_TRY(hipMemcpyAsync(out_scores, c->scores, (size_t)idx->n * sizeof(float), hipMemcpyDeviceToHost, st));
+  return fr.wait();
 }
 
 int32_t svs_index_search_rows(svs_index* idx, const float* queries, int32_t nq, int32_t d, int32_t k,
@@ -3033,48 +3132,30 @@ int32_t svs_index_search_rows(svs_index* idx, const float* queries, int32_t nq, 
   if (rc != SVS_OK) return rc;
   const int64_t lo = idx->row_offset;
   bool ascending;
-  if ((rc = check_row_list(idx, rows, nrows, &ascending)) != SVS_OK) return rc;
+  if ((rc = check_row_list(rows, nrows, lo, idx->n, &ascending)) != SVS_OK) return rc;
   if (nq == 0 || nrows == 0 || k <= 0) return SVS_OK;
   if (!out_scores || !out_rows) return fail(SVS_ERR_INVALID, "null output");
-  HIP_TRY(hipSetDevice(idx->device));
-  if ((rc = staging_wait(idx)) != SVS_OK) return rc;
-  Ctx* c = nullptr;
-  if ((rc = ctx_acquire(idx, nullptr, true, &c)) != SVS_OK) return rc;
-  CtxGuard cg{idx, c};
+  HostCall fr(idx);
+  if ((rc = fr.open()) != SVS_OK) return rc;
+  Ctx* const c = fr.c;
   // S = the live listed rows, ascending, as local u32 rows in pinned memory (the upload's source)
   if ((rc = c->list_pin.grow((size_t)nrows)) != SVS_OK) return rc;
   uint32_t* S = c->list_pin;
   int64_t m = 0;
-  const uint8_t* dead = idx->dead_flag.data();
-  if (ascending) {
-    for (int64_t t = 0; t < nrows; ++t) {
-      const uint32_t r = (uint32_t)(rows[t] - lo);
-      if (!dead[r]) S[m++] = r;
-    }
-  } else {
+  try {
     std::vector<uint32_t> tmp;
-    try {
-      tmp.resize((size_t)nrows);
-    } catch (const std::bad_alloc&) {
-      return fail(SVS_ERR_NOMEM, "out of host memory for a %lld-row list", (long long)nrows);
-    }
-    for (int64_t t = 0; t < nrows; ++t) tmp[(size_t)t] = (uint32_t)(rows[t] - lo);
-    std::sort(tmp.begin(), tmp.end());
-    const size_t u = (size_t)(std::unique(tmp.begin(), tmp.end()) - tmp.begin());
-    for (size_t t = 0; t < u; ++t)
-      if (!dead[tmp[t]]) S[m++] = tmp[t];
+    m = live_rows_ascending(rows, nrows, lo, idx->dead_flag.data(), ascending, tmp, S);
+  } catch (const std::bad_alloc&) {
+    return fail(SVS_ERR_NOMEM, "out of host memory for a %lld-row list", (long long)nrows);
   }
   const int count = (int)std::min<int64_t>(k, m);
   if (out_count) *out_count = count;
   if (count == 0) return SVS_OK;
-  hipStream_t st = c->stream;
   const size_t qn = (size_t)nq * (size_t)d, on = (size_t)nq * (size_t)count;
-  if ((rc = c->q_dev.grow(qn)) != SVS_OK) return rc;
   if ((rc = c->list_dev.grow((size_t)m)) != SVS_OK) return rc;
-  if ((rc = c->q_pin.grow(qn)) != SVS_OK) return rc;
   if ((rc = c->out_s_pin.grow(on)) != SVS_OK || (rc = c->out_r_pin.grow(on)) != SVS_OK) return rc;
-  memcpy(c->q_pin, queries, qn * sizeof(float));
-  HIP_TRY(hipMemcpyAsync(c->q_dev, c->q_pin, qn * sizeof(float), hipMemcpyHostToDevice, st));
+  const hipStream_t st = fr.stream();
+  if ((rc = upload_queries(c, queries, qn, st)) != SVS_OK) return rc;
   HIP_TRY(hipMemcpyAsync(c->list_dev, S, (size_t)m * sizeof(uint32_t), hipMemcpyHostToDevice, st));
   // Query chunks whose score matrix (and, for k > SEL_KMAX over more than SORT_CAP rows, sort keys) stays <= 2 GiB
   const int64_t sstride = (m + 3) & ~(int64_t)3;
@@ -3085,28 +3166,14 @@ int32_t svs_index_search_rows(svs_index* idx, const float* queries, int32_t nq, 
   const int qc = (int)std::max<int64_t>(1, std::min<int64_t>(nq, ((int64_t)2 << 30) / per_q));
   if ((rc = c->scores.grow((size_t)qc * (size_t)sstride)) != SVS_OK) return rc;
   if (window && (rc = grow_select_scratch(c, qc, st)) != SVS_OK) return rc;
-  for (int q0 = 0; q0 < nq && rc == SVS_OK; q0 += qc) {
+  for (int q0 = 0; q0 < nq; q0 += qc) {
     const int nc = std::min(qc, nq - q0);
-    rc = launch_gather(idx, c, c->q_dev + (size_t)q0 * d, nc, c->list_dev, m, c->scores, sstride, st);
-    if (rc == SVS_OK)
-      rc = run_select(idx, c, c->scores, m, sstride, nc, count, count, c->out_s_pin + (size_t)q0 * count,
-                      c->out_r_pin + (size_t)q0 * count, st, 0);
+    if ((rc = enqueue_list_search(idx, c, c->q_dev + (size_t)q0 * d, nc, c->list_dev, m, count, c->out_s_pin + (size_t)q0 * count,
+                                  c->out_r_pin + (size_t)q0 * count, st)) != SVS_OK)
+      return rc;
   }
-  if (rc == SVS_OK) {
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) rc = fail(SVS_ERR_DEVICE, "search_rows launch: %s", hipGetErrorString(e));
-  }
-  if (rc != SVS_OK) {
-    (void)hipStreamSynchronize(st);
-    return rc;
-  }
-  HIP_TRY(hipStreamSynchronize(st));
-  // positions in S -> global rows, in the pinned block
-  for (size_t i = 0; i < on; ++i) {
-    const int64_t p = c->out_r_pin[i];
-    if (p < 0 || p >= m) return fail(SVS_ERR_DEVICE, "search_rows: position %lld outside the %lld listed rows", (long long)p, (long long)m);
-    c->out_r_pin[i] = (int64_t)S[p] + lo;
-  }
+  if ((rc = fr.close("search_rows")) != SVS_OK) return rc;
+  if ((rc = list_positions_to_rows(c->out_r_pin, on, S, m, lo, -1)) != SVS_OK) return rc;
   deliver_results(c, nq, count, k, out_scores, out_rows);
   return SVS_OK;
 }
@@ -3129,15 +3196,12 @@ int32_t svs_index_search_above(svs_index* idx, const float* queries, int32_t nq,
   const int64_t live = n - (int64_t)idx->dead_list.size();
   const int lim = (int)std::min<int64_t>(std::max(limit, 0), live);   // entries a query can have
   const int ls = std::min(lim, SORT_CAP);                              // ... and the most the device writes for one
-  HIP_TRY(hipSetDevice(idx->device));
-  if ((rc = staging_wait(idx)) != SVS_OK) return rc;
-  Ctx* c = nullptr;
-  if ((rc = ctx_acquire(idx, nullptr, true, &c)) != SVS_OK) return rc;
-  CtxGuard cg{idx, c};
-  hipStream_t st = c->stream;
+  HostCall fr(idx);
+  if ((rc = fr.open()) != SVS_OK) return rc;
+  Ctx* const c = fr.c;
+  hipStream_t st = fr.stream();
   const size_t qn = (size_t)nq * (size_t)d, on = std::max<size_t>((size_t)nq * (size_t)ls, 1);
   const int64_t sstride = (n + 3) & ~(int64_t)3;
-  if ((rc = c->q_dev.grow(qn)) != SVS_OK || (rc = c->q_pin.grow(qn)) != SVS_OK) return rc;
   if ((rc = c->out_s_pin.grow(on)) != SVS_OK || (rc = c->out_r_pin.grow(on)) != SVS_OK) return rc;
   if ((rc = c->above_cnt_pin.grow((size_t)nq)) != SVS_OK || (rc = c->above_tot_pin.grow((size_t)nq)) != SVS_OK) return rc;
   if ((rc = c->scores.grow((size_t)sstride)) != SVS_OK) return rc;
@@ -3147,28 +3211,19 @@ int32_t svs_index_search_above(svs_index* idx, const float* queries, int32_t nq,
   const uint32_t* dead_bits = masked ? idx->dead_bits_dev.p : nullptr;
   const int64_t per_block = (int64_t)FA_THREADS * SEL_VPT * 4;
   const unsigned blocks = (unsigned)((n + per_block - 1) / per_block);
-  memcpy(c->q_pin, queries, qn * sizeof(float));
-  HIP_TRY(hipMemcpyAsync(c->q_dev, c->q_pin, qn * sizeof(float), hipMemcpyHostToDevice, st));
+  if ((rc = upload_queries(c, queries, qn, st)) != SVS_OK) return rc;
   // every query back to back: score pass, filter, final -- the context's one score vector, header and candidate list
   // are reused in stream order; no host wait in between
-  for (int32_t q = 0; q < nq && rc == SVS_OK; ++q) {
+  for (int32_t q = 0; q < nq; ++q) {
     launch_record("gemv", n, 1);
-    if ((rc = launch_scores(idx, c, route, c->q_dev + (size_t)q * d, c->scores, st)) != SVS_OK) break;
+    if ((rc = launch_scores(idx, c, route, c->q_dev + (size_t)q * d, c->scores, st)) != SVS_OK) return rc;
     launch_record("above_filter_kernel", n, 1);
     hipLaunchKernelGGL(above_filter_kernel, dim3(blocks), dim3(FA_THREADS), 0, st, (const float*)c->scores.p, n, score_key(min_scores[q]),
                        dead_bits, c->hist.p, c->cand.p);
     hipLaunchKernelGGL(above_final_kernel, dim3(1), dim3(FINAL_THREADS), 0, st, c->hist.p, (const uint64_t*)c->cand.p, lim, idx->row_offset,
                        c->out_s_pin + (size_t)q * ls, c->out_r_pin + (size_t)q * ls, c->above_cnt_pin + q, c->above_tot_pin + q);
   }
-  if (rc == SVS_OK) {
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) rc = fail(SVS_ERR_DEVICE, "search_above launch: %s", hipGetErrorString(e));
-  }
-  if (rc != SVS_OK) {
-    (void)hipStreamSynchronize(st);
-    return rc;
-  }
-  HIP_TRY(hipStreamSynchronize(st));
+  if ((rc = fr.close("search_above")) != SVS_OK) return rc;
   for (int32_t q = 0; q < nq; ++q) {
     const int64_t total = c->above_tot_pin[q];
     int count = c->above_cnt_pin[q];
@@ -3178,24 +3233,16 @@ int32_t svs_index_search_above(svs_index* idx, const float* queries, int32_t nq,
       // rows are the first that many rows at or above the cut-off.
       count = (int)std::min<int64_t>(lim, total);
       if ((rc = c->redo_s_pin.grow((size_t)count)) != SVS_OK || (rc = c->redo_r_pin.grow((size_t)count)) != SVS_OK) return rc;
+      st = fr.stream();
       launch_record("gemv", n, 1);
-      if ((rc = launch_scores(idx, c, route, c->q_dev + (size_t)q * d, c->scores, st)) == SVS_OK) {
-        if (masked)
-          hipLaunchKernelGGL(mask_dead_rows_kernel, dim3(64), dim3(256), 0, st, c->scores.p, sstride, 1, (const uint32_t*)idx->dead_dev.p,
-                             (int64_t)idx->dead_list.size(), n, (int64_t)0);
-        const SelectPath path = select_path(n, count);   // (recorded: which stage the re-run took)
-        launch_record(path == SelectPath::WINDOW ? "select_window_hist_kernel" : (path == SelectPath::SORT ? "keys_build_kernel" : "select_final_kernel"), n, 1);
-        rc = run_select(idx, c, c->scores, n, sstride, 1, count, count, c->redo_s_pin, c->redo_r_pin, st, idx->row_offset);
-      }
-      if (rc == SVS_OK) {
-        hipError_t e = hipGetLastError();
-        if (e != hipSuccess) rc = fail(SVS_ERR_DEVICE, "search_above re-run: %s", hipGetErrorString(e));
-      }
-      if (rc != SVS_OK) {
-        (void)hipStreamSynchronize(st);
-        return rc;
-      }
-      HIP_TRY(hipStreamSynchronize(st));
+      if ((rc = launch_scores(idx, c, route, c->q_dev + (size_t)q * d, c->scores, st)) != SVS_OK) return rc;
+      if (masked)
+        hipLaunchKernelGGL(mask_dead_rows_kernel, dim3(64), dim3(256), 0, st, c->scores.p, sstride, 1, (const uint32_t*)idx->dead_dev.p,
+                           (int64_t)idx->dead_list.size(), n, (int64_t)0);
+      const SelectPath path = select_path(n, count);   // (recorded: which stage the re-run took)
+      launch_record(path == SelectPath::WINDOW ? "select_window_hist_kernel" : (path == SelectPath::SORT ? "keys_build_kernel" : "select_final_kernel"), n, 1);
+      if ((rc = run_select(idx, c, c->scores, n, sstride, 1, count, count, c->redo_s_pin, c->redo_r_pin, st, idx->row_offset)) != SVS_OK) return rc;
+      if ((rc = fr.close("search_above", true)) != SVS_OK) return rc;
       memcpy(out_scores + (size_t)q * limit, c->redo_s_pin, (size_t)count * sizeof(float));
       memcpy(out_rows + (size_t)q * limit, c->redo_r_pin, (size_t)count * sizeof(int64_t));
     } else if (count > 0) {
@@ -3234,12 +3281,13 @@ int32_t svs_index_search_segments(svs_index* idx, const float* queries, int32_t 
   if (total > 0 && !rows) return fail(SVS_ERR_INVALID, "null row list");
   const int64_t lo = idx->row_offset, n = idx->n;
   std::vector<uint8_t> ascending;
-  std::vector<int64_t> m_of, off_of;
+  std::vector<int64_t> m_of, off_of, res_of;   // per segment: live rows, where its list begins in S, its results in the result block
   std::vector<uint32_t> tmp, big;   // an unsorted segment's rows; the lists of the large segments, one after the other
   try {
     ascending.assign((size_t)nseg, 1);
     m_of.assign((size_t)nseg, 0);
     off_of.assign((size_t)nseg, -1);
+    res_of.assign((size_t)nseg, 0);
   } catch (const std::bad_alloc&) {
     return fail(SVS_ERR_NOMEM, "out of host memory for %d segments", nseg);
   }
@@ -3260,11 +3308,9 @@ int32_t svs_index_search_segments(svs_index* idx, const float* queries, int32_t 
     for (int32_t s = 0; s < nseg; ++s) out_counts[s] = 0;
     return SVS_OK;
   }
-  HIP_TRY(hipSetDevice(idx->device));
-  if ((rc = staging_wait(idx)) != SVS_OK) return rc;
-  Ctx* c = nullptr;
-  if ((rc = ctx_acquire(idx, nullptr, true, &c)) != SVS_OK) return rc;
-  CtxGuard cg{idx, c};
+  HostCall fr(idx);
+  if ((rc = fr.open()) != SVS_OK) return rc;
+  Ctx* const c = fr.c;
   // ---- host plan: S = the live rows of every segment, ascending inside it, as local u32 rows in pinned memory --
   // the small segments (1 .. SORT_CAP live rows) first, in segment order, then the large ones
   if ((rc = c->list_pin.grow((size_t)total)) != SVS_OK) return rc;
@@ -3278,20 +3324,7 @@ int32_t svs_index_search_segments(svs_index* idx, const float* queries, int32_t 
       const bool aside = nr > SORT_CAP;
       if (aside) big.resize(big.size() + (size_t)nr);
       uint32_t* dst = aside ? big.data() + (big.size() - (size_t)nr) : S + small_rows;
-      int64_t m = 0;
-      if (ascending[(size_t)s]) {
-        for (int64_t t = 0; t < nr; ++t) {
-          const uint32_t r = (uint32_t)(rows[b + t] - lo);
-          if (!dead[r]) dst[m++] = r;
-        }
-      } else {
-        tmp.resize((size_t)nr);
-        for (int64_t t = 0; t < nr; ++t) tmp[(size_t)t] = (uint32_t)(rows[b + t] - lo);
-        std::sort(tmp.begin(), tmp.end());
-        const size_t u = (size_t)(std::unique(tmp.begin(), tmp.end()) - tmp.begin());
-        for (size_t t = 0; t < u; ++t)
-          if (!dead[tmp[t]]) dst[m++] = tmp[t];
-      }
+      const int64_t m = live_rows_ascending(rows + b, nr, lo, dead, ascending[(size_t)s] != 0, tmp, dst);
       m_of[(size_t)s] = m;
       if (aside && m <= SORT_CAP) {   // small after all
         memcpy(S + small_rows, dst, (size_t)m * sizeof(uint32_t));
@@ -3327,19 +3360,25 @@ int32_t svs_index_search_segments(svs_index* idx, const float* queries, int32_t 
   SegTile* tiles = c->seg_plan_pin;
   SegDesc* segs = reinterpret_cast<SegDesc*>(tiles + ntiles);
   (void)seg_tile_plan(m_of.data(), seg_query, nseg, W, tiles, ntiles, nullptr, nullptr);
-  {
-    int64_t j = 0;
-    for (int32_t s = 0; s < nseg; ++s)
-      if (off_of[(size_t)s] >= 0)
-        segs[j++] = SegDesc{(uint32_t)off_of[(size_t)s], (uint32_t)m_of[(size_t)s], (uint32_t)std::min<int64_t>(k, m_of[(size_t)s]), (uint32_t)s};
-  }
   // the result block: rows (int64) of the small segments at stride kk, then of the large ones, count by count; the
   // scores (f32) behind them in the same order
   const size_t res_n = (size_t)n_small * (size_t)kk + (size_t)large_out;
+  {
+    int64_t j = 0, loff = small_rows, o = n_small * kk;
+    for (size_t s = 0; s < (size_t)nseg; ++s) {
+      const int64_t m = m_of[s], count = std::min<int64_t>(k, m);
+      if (m > SORT_CAP) {   // (the large segments' lists lie behind the small ones', in segment order)
+        off_of[s] = loff;
+        res_of[s] = o;
+        loff += m;
+        o += count;
+      } else if (m >= 1) {
+        res_of[s] = j * kk;
+        segs[j++] = SegDesc{(uint32_t)off_of[s], (uint32_t)m, (uint32_t)count, (uint32_t)s};
+      }
+    }
+  }
   const size_t res_words = res_n + (res_n + 1) / 2;
-  hipStream_t st = c->stream;
-  const size_t qn = (size_t)nq * (size_t)d;
-  if ((rc = c->q_dev.grow(qn)) != SVS_OK || (rc = c->q_pin.grow(qn)) != SVS_OK) return rc;
   if ((rc = c->list_dev.grow((size_t)listed)) != SVS_OK) return rc;
   if ((rc = c->seg_res_dev.grow(res_words)) != SVS_OK || (rc = c->seg_res_pin.grow(res_words)) != SVS_OK) return rc;
   const int64_t small_stride = (small_rows + 3) & ~(int64_t)3, large_stride = (max_large + 3) & ~(int64_t)3;
@@ -3347,89 +3386,48 @@ int32_t svs_index_search_segments(svs_index* idx, const float* queries, int32_t 
   bool window = false;
   for (int32_t s = 0; s < nseg && !window; ++s)
     window = m_of[(size_t)s] > SORT_CAP && select_path(m_of[(size_t)s], (int)std::min<int64_t>(k, m_of[(size_t)s])) == SelectPath::WINDOW;
+  const hipStream_t st = fr.stream();
   if (window && (rc = grow_select_scratch(c, 1, st)) != SVS_OK) return rc;
   int64_t* res_r = c->seg_res_dev;
   float* res_s = reinterpret_cast<float*>(res_r + res_n);
-  memcpy(c->q_pin, queries, qn * sizeof(float));
-  HIP_TRY(hipMemcpyAsync(c->q_dev, c->q_pin, qn * sizeof(float), hipMemcpyHostToDevice, st));
+  if ((rc = upload_queries(c, queries, (size_t)nq * (size_t)d, st)) != SVS_OK) return rc;
   HIP_TRY(hipMemcpyAsync(c->list_dev, S, (size_t)listed * sizeof(uint32_t), hipMemcpyHostToDevice, st));
   if (n_small) {
     HIP_TRY(hipMemcpyAsync(c->seg_plan_dev, tiles, plan_n * sizeof(SegTile), hipMemcpyHostToDevice, st));
     const SegTile* tiles_dev = c->seg_plan_dev;
-    rc = launch_gather_segments(idx, c, c->q_dev, nq, c->list_dev, tiles_dev, ntiles, small_rows, (int)n_small, c->scores, st);
-    if (rc == SVS_OK) {
-      launch_record("select_segments_kernel", small_rows, (int)n_small);
-      hipLaunchKernelGGL(select_segments_kernel, dim3((unsigned)n_small), dim3(FINAL_THREADS), 0, st, (const float*)c->scores,
-                         (const uint32_t*)c->list_dev, reinterpret_cast<const SegDesc*>(tiles_dev + ntiles), kk, lo, res_s, res_r);
-    }
+    if ((rc = launch_gather_segments(idx, c, c->q_dev, nq, c->list_dev, tiles_dev, ntiles, small_rows, (int)n_small, c->scores, st)) != SVS_OK)
+      return rc;
+    launch_record("select_segments_kernel", small_rows, (int)n_small);
+    hipLaunchKernelGGL(select_segments_kernel, dim3((unsigned)n_small), dim3(FINAL_THREADS), 0, st, (const float*)c->scores,
+                       (const uint32_t*)c->list_dev, reinterpret_cast<const SegDesc*>(tiles_dev + ntiles), kk, lo, res_s, res_r);
   }
-  // The large segments, one after the other behind the small ones' two kernels on the same stream, exactly as
-  // svs_index_search_rows serves them: launch_gather re-stages its query into the buffers the small segments' kernel
-  // read its queries from, and the scores are reused -- both in stream order, behind their readers.
-  {
-    int64_t loff = small_rows;
-    size_t o = (size_t)n_small * (size_t)kk;
-    for (int32_t s = 0; s < nseg && rc == SVS_OK; ++s) {
-      const int64_t m = m_of[(size_t)s];
-      if (m <= SORT_CAP) continue;
-      const int count = (int)std::min<int64_t>(k, m);
-      const int sq = seg_query ? seg_query[s] : s;
-      const int64_t sstride = (m + 3) & ~(int64_t)3;
-      rc = launch_gather(idx, c, c->q_dev + (size_t)sq * d, 1, c->list_dev + loff, m, c->scores, sstride, st);
-      if (rc == SVS_OK) rc = run_select(idx, c, c->scores, m, sstride, 1, count, count, res_s + o, res_r + o, st, 0);
-      loff += m;
-      o += (size_t)count;
-    }
+  // The large segments, one after the other behind the small ones' two kernels on the same stream, each the search
+  // svs_index_search_rows makes over its one list: launch_gather re-stages its query into the buffers the small segments'
+  // kernel read its queries from, and the scores are reused -- both in stream order, behind their readers.
+  for (int32_t s = 0; s < nseg; ++s) {
+    const int64_t m = m_of[(size_t)s], o = res_of[(size_t)s];
+    if (m <= SORT_CAP) continue;
+    const int sq = seg_query ? seg_query[s] : s;
+    if ((rc = enqueue_list_search(idx, c, c->q_dev + (size_t)sq * d, 1, c->list_dev + off_of[(size_t)s], m, (int)std::min<int64_t>(k, m),
+                                  res_s + o, res_r + o, st)) != SVS_OK)
+      return rc;
   }
-  if (rc == SVS_OK) {
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) rc = fail(SVS_ERR_DEVICE, "search_segments launch: %s", hipGetErrorString(e));
-  }
-  if (rc != SVS_OK) {
-    (void)hipStreamSynchronize(st);
-    return rc;
-  }
+  if ((rc = fr.launched("search_segments")) != SVS_OK) return rc;
   HIP_TRY(hipMemcpyAsync(c->seg_res_pin, c->seg_res_dev, res_n * sizeof(int64_t) + res_n * sizeof(float), hipMemcpyDeviceToHost, st));
-  HIP_TRY(hipStreamSynchronize(st));
-  // ---- delivery: count_s entries per segment at the caller's stride k; the large segments' positions -> rows
-  const int64_t* pr = c->seg_res_pin;
+  if ((rc = fr.wait()) != SVS_OK) return rc;
+  // ---- delivery: the large segments' positions -> rows in the pinned block, every one checked; then count_s entries per
+  // segment at the caller's stride k
+  int64_t* pr = c->seg_res_pin;
   const float* ps = reinterpret_cast<const float*>(pr + res_n);
-  {
-    int64_t loff = small_rows;
-    size_t o = (size_t)n_small * (size_t)kk;
-    for (int32_t s = 0; s < nseg; ++s) {
-      const int64_t m = m_of[(size_t)s];
-      if (m <= SORT_CAP) continue;
-      const int count = (int)std::min<int64_t>(k, m);
-      for (int i = 0; i < count; ++i) {
-        const int64_t p = pr[o + i];
-        if (p < 0 || p >= m)
-          return fail(SVS_ERR_DEVICE, "search_segments: position %lld outside the %lld listed rows of segment %d", (long long)p, (long long)m, s);
-      }
-      loff += m;
-      o += (size_t)count;
-    }
-    loff = small_rows;
-    o = (size_t)n_small * (size_t)kk;
-    size_t j = 0;
-    for (int32_t s = 0; s < nseg; ++s) {
-      const int64_t m = m_of[(size_t)s];
-      const int count = (int)std::min<int64_t>(k, m);
-      out_counts[s] = count;
-      if (m == 0) continue;
-      float* os = out_scores + (size_t)s * k;
-      int64_t* orow = out_rows + (size_t)s * k;
-      if (m <= SORT_CAP) {
-        memcpy(os, ps + j * kk, (size_t)count * sizeof(float));
-        memcpy(orow, pr + j * kk, (size_t)count * sizeof(int64_t));
-        ++j;
-      } else {
-        memcpy(os, ps + o, (size_t)count * sizeof(float));
-        for (int i = 0; i < count; ++i) orow[i] = (int64_t)S[loff + pr[o + i]] + lo;
-        loff += m;
-        o += (size_t)count;
-      }
-    }
+  for (size_t s = 0; s < (size_t)nseg; ++s)
+    if (m_of[s] > SORT_CAP &&
+        (rc = list_positions_to_rows(pr + res_of[s], (size_t)std::min<int64_t>(k, m_of[s]), S + off_of[s], m_of[s], lo, (int)s)) != SVS_OK)
+      return rc;
+  for (size_t s = 0; s < (size_t)nseg; ++s) {
+    const size_t count = (size_t)std::min<int64_t>(k, m_of[s]);
+    out_counts[s] = (int32_t)count;
+    memcpy(out_scores + s * k, ps + res_of[s], count * sizeof(float));
+    memcpy(out_rows + s * k, pr + res_of[s], count * sizeof(int64_t));
   }
   return SVS_OK;
 }
@@ -3472,7 +3470,7 @@ int32_t svs_index_neighbors(svs_index* idx, const int64_t* rows, int64_t nrows, 
     if (r < 0 || r >= n) break;
     if (idx->dead_flag[(size_t)r]) return fail(SVS_ERR_INVALID, "row %lld is tombstoned: it has no neighbours", (long long)rows[t]);
   }
-  int rc = check_row_list(idx, rows, nrows, nullptr);
+  int rc = check_row_list(rows, nrows, lo, n, nullptr);
   if (rc != SVS_OK) return rc;
   const int64_t live = n - (int64_t)idx->dead_list.size();
   const int count = (int)std::min<int64_t>(std::max(k, 0), std::max<int64_t>(live - 1, 0));
@@ -3480,12 +3478,10 @@ int32_t svs_index_neighbors(svs_index* idx, const int64_t* rows, int64_t nrows, 
   if (nrows == 0 || count == 0) return SVS_OK;
   if (!out_scores || !out_rows) return fail(SVS_ERR_INVALID, "null output");
   if (idx->d == 0) return fail(SVS_ERR_SHAPE, "an index of dimension 0 has no scores");
-  HIP_TRY(hipSetDevice(idx->device));
-  if ((rc = staging_wait(idx)) != SVS_OK) return rc;
-  Ctx* c = nullptr;
-  if ((rc = ctx_acquire(idx, nullptr, true, &c)) != SVS_OK) return rc;
-  CtxGuard cg{idx, c};
-  hipStream_t st = c->stream;
+  HostCall fr(idx);
+  if ((rc = fr.open()) != SVS_OK) return rc;
+  Ctx* const c = fr.c;
+  const hipStream_t st = fr.stream();
   const int kk = count + 1, d = idx->d;   // (kk <= live rows: the search's own count is kk)
   const int64_t B = SVS_NEIGHBORS_BLOCK;
   const int bmax = (int)std::min<int64_t>(B, nrows);
@@ -3499,28 +3495,20 @@ int32_t svs_index_neighbors(svs_index* idx, const int64_t* rows, int64_t nrows, 
   // Block by block on the context's stream: panel, the ordinary search at count + 1 into device scratch, self dropped
   // into the pinned (device-visible) output.  One wait for the whole call.
   const int variant = idx->variant.load();
-  for (int64_t b0 = 0; b0 < nrows && rc == SVS_OK; b0 += B) {
+  for (int64_t b0 = 0; b0 < nrows; b0 += B) {
     const int nb = (int)std::min<int64_t>(B, nrows - b0);
     const uint32_t* list = c->nb_list_dev + b0;
     SearchPlan plan;
-    if ((rc = plan_search(idx, c, nb, kk, kk, st, true, variant, &plan)) != SVS_OK) break;
+    if ((rc = plan_search(idx, c, nb, kk, kk, st, true, variant, &plan)) != SVS_OK) return rc;
     launch_rows_as_queries(idx, list, nb, c->q_dev, st);
     if ((rc = enqueue_prefix(idx, c, plan, c->q_dev, st)) == SVS_OK) rc = enqueue_main(idx, c, plan, c->q_dev, c->nb_s, c->nb_r, st);
     if (rc != SVS_OK) {
       plan_abandon(idx, plan);
-      break;
+      return rc;
     }
     launch_drop_self(idx, c->nb_s, c->nb_r, list, nb, count, c->out_s_pin + (size_t)b0 * count, c->out_r_pin + (size_t)b0 * count, st);
   }
-  if (rc == SVS_OK) {
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) rc = fail(SVS_ERR_DEVICE, "neighbors launch: %s", hipGetErrorString(e));
-  }
-  if (rc != SVS_OK) {
-    (void)hipStreamSynchronize(st);
-    return rc;
-  }
-  HIP_TRY(hipStreamSynchronize(st));
+  if ((rc = fr.close("neighbors")) != SVS_OK) return rc;
   // Overflowed positions: rerun_overflowed block by block, so in the groups search_host forms for the block (the same
   // kernels, the same bits).  There is no host copy of the queries: the group's rows are turned into a panel of its own,
   // and the search's count + 1 results per row go through drop_self like the block's.
@@ -3536,7 +3524,7 @@ int32_t svs_index_neighbors(svs_index* idx, const int64_t* rows, int64_t nrows, 
   auto finish = [&](int m) { launch_drop_self(idx, c->nb_s, c->nb_r, c->nb_redo_dev, m, count, c->redo_s_pin, c->redo_r_pin, st); };
   int n_redo = 0;
   for (int64_t b0 = 0; b0 < nrows; b0 += B)
-    if ((rc = rerun_overflowed(idx, c, b0, std::min<int64_t>(b0 + B, nrows), count, kk, c->nb_redo_q, c->nb_s, c->nb_r, stage, finish, &n_redo)) != SVS_OK) return rc;
+    if ((rc = rerun_overflowed(idx, fr, b0, std::min<int64_t>(b0 + B, nrows), count, kk, c->nb_redo_q, c->nb_s, c->nb_r, stage, finish, &n_redo)) != SVS_OK) return rc;
   g_host_phase[5] = (double)n_redo;
   deliver_results(c, nrows, count, k, out_scores, out_rows);
   return SVS_OK;
@@ -3556,12 +3544,8 @@ int32_t svs_index_top_pairs(svs_index* idx, int32_t k, float* out_scores, int64_
   if (out_count) *out_count = count;
   if (count == 0) return SVS_OK;
   if (!out_scores || !out_i || !out_j) return fail(SVS_ERR_INVALID, "null output");
-  HIP_TRY(hipSetDevice(idx->device));
-  Ctx* c = nullptr;
-  int rc;
-  if ((rc = staging_wait(idx)) != SVS_OK) return rc;
-  if ((rc = ctx_acquire(idx, nullptr, true, &c)) != SVS_OK) return rc;
-  CtxGuard cg{idx, c};
+  HostCall fr(idx);
+  if (const int rc = fr.open(); rc != SVS_OK) return rc;
   // Small corpora: materialise n x n like the reference (src/svs/kb.py:1651).  Past n^2 = 2^32 scores
   // (or with variant 1, for A/B and tests): tiled GEMM with the i < j mask and a threshold in the
   // fused epilogue, nothing materialised but a prefix block.
@@ -3569,8 +3553,8 @@ int32_t svs_index_top_pairs(svs_index* idx, int32_t k, float* out_scores, int64_
   //  -- under variant 1 they returned (i, i) and both (i, j) and (j, i).)
   const int variant = idx->variant.load();   // (once: every chunk of either path takes its route under this value)
   if (n * np <= 0xffffffffll && (variant != VARIANT_GEMV_PERSISTENT_R1 || n <= GQ))
-    return top_pairs_materialised(idx, c, variant, n, count, out_scores, out_i, out_j);
-  return top_pairs_tiled(idx, c, variant, count, out_scores, out_i, out_j);
+    return top_pairs_materialised(idx, fr, variant, n, count, out_scores, out_i, out_j);
+  return top_pairs_tiled(idx, fr, variant, count, out_scores, out_i, out_j);
 }
 
 int32_t svs_index_debug_dequant(svs_index* idx, int64_t row0, int64_t nrows, float* out) {
@@ -3687,6 +3671,20 @@ int64_t svs_internal_redo_groups(const int64_t* res_rows, int32_t count, int64_t
   return found;
 }
 
+int64_t svs_internal_live_rows(const int64_t* rows, int64_t nrows, int64_t row_offset, int64_t n, const uint8_t* dead_flags, uint32_t* out,
+                               int64_t cap) {
+  if (n < 0 || n > ((int64_t)1 << 32) || cap < nrows || (nrows > 0 && (!dead_flags || !out)))
+    return fail(SVS_ERR_INVALID, "svs_internal_live_rows: nrows <= cap, 0 <= n <= 2^32, no null array");
+  bool ascending;
+  if (const int rc = check_row_list(rows, nrows, row_offset, n, &ascending); rc != SVS_OK) return rc;
+  try {
+    std::vector<uint32_t> tmp;
+    return live_rows_ascending(rows, nrows, row_offset, dead_flags, ascending, tmp, out);
+  } catch (const std::bad_alloc&) {
+    return fail(SVS_ERR_NOMEM, "out of host memory for a %lld-row list", (long long)nrows);
+  }
+}
+
 int32_t svs_internal_single_route(int32_t dtype, int32_t d, int32_t variant, int32_t screen, char* kernel, int32_t cap, int32_t* flags) {
   svs_index shape;   // (never sees a device: the route and the launchers' names depend on dtype, d and ld alone)
   shape.dtype = dtype; shape.d = d; shape.ld = choose_ld(d, dtype);
@@ -3784,15 +3782,16 @@ namespace {
 constexpr int64_t HOOK_MAX_N = (int64_t)1 << 26;   // rows / k a hook accepts (the kernels themselves go to 2^32 rows)
 
 // Non-zero words among the first nq * SCR_WORDS words of the context's select scratch, read back behind everything
-// enqueued on st (also drains st).  A context whose scratch holds fewer than nq queries was not touched: 0.
-int scratch_dirty(Ctx* c, int nq, hipStream_t st, int64_t* out) {
+// enqueued by the call (also waits for it).  A context whose scratch holds fewer than nq queries was not touched: 0.
+int scratch_dirty(HostCall& fr, int nq, int64_t* out) {
   *out = 0;
+  Ctx* const c = fr.c;
   std::vector<uint32_t> w;
   if ((size_t)nq <= c->hist_cap) {
     w.resize((size_t)nq * SCR_WORDS);
-    HIP_TRY(hipMemcpyAsync(w.data(), c->hist, w.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(w.data(), c->hist, w.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, fr.stream()));
   }
-  HIP_TRY(hipStreamSynchronize(st));
+  if (const int rc = fr.wait(); rc != SVS_OK) return rc;
   int64_t d = 0;
   for (uint32_t x : w) d += x != 0u;
   *out = d;
@@ -3807,17 +3806,15 @@ int32_t svs_internal_select_scores(svs_index* idx, const float* scores, int32_t 
     return fail(SVS_ERR_INVALID, "svs_internal_select_scores: nq %d, n %lld, k %d out of range", nq, (long long)n, k);
   RefGuard guard(idx);
   std::shared_lock<std::shared_mutex> geo(idx->rw);
-  HIP_TRY(hipSetDevice(idx->device));
-  int rc;
-  if ((rc = staging_wait(idx)) != SVS_OK) return rc;
   const int count = (int)std::min<int64_t>(k, n);
   *out_count = count;
   const int64_t sstride = (n + 3) & ~(int64_t)3;   // float4-aligned score vectors, as plan_search lays them out
   const bool path_a = select_path(n, count) == SelectPath::WINDOW;
-  Ctx* c = nullptr;
-  if ((rc = ctx_acquire(idx, nullptr, true, &c)) != SVS_OK) return rc;
-  CtxGuard cg{idx, c};
-  hipStream_t st = c->stream;
+  HostCall fr(idx);
+  int rc;
+  if ((rc = fr.open()) != SVS_OK) return rc;
+  Ctx* const c = fr.c;
+  const hipStream_t st = fr.stream();
   if ((rc = c->scores.grow((size_t)nq * (size_t)sstride)) != SVS_OK) return rc;
   if (path_a && (rc = grow_select_scratch(c, nq, st)) != SVS_OK) return rc;
   DevTmp tmp;
@@ -3831,7 +3828,7 @@ int32_t svs_internal_select_scores(svs_index* idx, const float* scores, int32_t 
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipMemcpyAsync(out_scores, d_s, (size_t)nq * k * sizeof(float), hipMemcpyDeviceToHost, st));
   HIP_TRY(hipMemcpyAsync(out_rows, d_r, (size_t)nq * k * sizeof(int64_t), hipMemcpyDeviceToHost, st));
-  return scratch_dirty(c, nq, st, out_dirty);
+  return scratch_dirty(fr, nq, out_dirty);
 }
 
 int32_t svs_internal_kth_value(svs_index* idx, const float* scores, int32_t nq, int64_t n, int32_t k, int32_t misalign,
@@ -3841,14 +3838,12 @@ int32_t svs_internal_kth_value(svs_index* idx, const float* scores, int32_t nq, 
     return fail(SVS_ERR_INVALID, "svs_internal_kth_value: nq %d, n %lld, k %d out of range (1 <= k <= n)", nq, (long long)n, k);
   RefGuard guard(idx);
   std::shared_lock<std::shared_mutex> geo(idx->rw);
-  HIP_TRY(hipSetDevice(idx->device));
-  int rc;
-  if ((rc = staging_wait(idx)) != SVS_OK) return rc;
   const int64_t sstride = (n + 3) & ~(int64_t)3;
-  Ctx* c = nullptr;
-  if ((rc = ctx_acquire(idx, nullptr, true, &c)) != SVS_OK) return rc;
-  CtxGuard cg{idx, c};
-  hipStream_t st = c->stream;
+  HostCall fr(idx);
+  int rc;
+  if ((rc = fr.open()) != SVS_OK) return rc;
+  Ctx* const c = fr.c;
+  const hipStream_t st = fr.stream();
   if ((rc = c->scores.grow((size_t)nq * (size_t)sstride + 4)) != SVS_OK) return rc;
   if ((rc = c->pref_s.grow((size_t)nq)) != SVS_OK) return rc;
   float* base = c->scores.p + (misalign ? 1 : 0);   // one float off a 16-byte boundary: the kernel's streaming branch
@@ -3858,7 +3853,7 @@ int32_t svs_internal_kth_value(svs_index* idx, const float* scores, int32_t nq, 
   hipLaunchKernelGGL(prefix_kth_kernel, dim3(nq), dim3(FINAL_THREADS), 0, st, (const float*)base, n, sstride, k, c->pref_s.p);
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipMemcpyAsync(out_thr, c->pref_s, (size_t)nq * sizeof(float), hipMemcpyDeviceToHost, st));
-  return scratch_dirty(c, nq, st, out_dirty);
+  return scratch_dirty(fr, nq, out_dirty);
 }
 
 int32_t svs_internal_select_candidates(svs_index* idx, const uint64_t* keys, const int64_t* key_offsets, const uint32_t* n_cand,
@@ -3880,13 +3875,11 @@ int32_t svs_internal_select_candidates(svs_index* idx, const uint64_t* keys, con
         if ((int64_t)(uint32_t)keys[i] >= idx->n)
           return fail(SVS_ERR_INVALID, "svs_internal_select_candidates: row %u outside the index", (uint32_t)keys[i]);
   }
-  HIP_TRY(hipSetDevice(idx->device));
+  HostCall fr(idx);
   int rc;
-  if ((rc = staging_wait(idx)) != SVS_OK) return rc;
-  Ctx* c = nullptr;
-  if ((rc = ctx_acquire(idx, nullptr, true, &c)) != SVS_OK) return rc;
-  CtxGuard cg{idx, c};
-  hipStream_t st = c->stream;
+  if ((rc = fr.open()) != SVS_OK) return rc;
+  Ctx* const c = fr.c;
+  const hipStream_t st = fr.stream();
   if ((rc = grow_select_scratch(c, nq, st)) != SVS_OK) return rc;
   DevTmp tmp;
   float* d_s = nullptr;
@@ -3908,14 +3901,14 @@ int32_t svs_internal_select_candidates(svs_index* idx, const uint64_t* keys, con
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipMemcpyAsync(out_scores, d_s, (size_t)nq * k * sizeof(float), hipMemcpyDeviceToHost, st));
     HIP_TRY(hipMemcpyAsync(out_rows, d_r, (size_t)nq * k * sizeof(int64_t), hipMemcpyDeviceToHost, st));
-    return scratch_dirty(c, nq, st, out_dirty);
+    return scratch_dirty(fr, nq, out_dirty);
   };
   rc = run();
   if (rc != SVS_OK) {
     // A failed hook must not hand the context back with the headers it uploaded: the next search on it relies on an
-    // all-zero scratch.  (Best effort, behind whatever is still queued; the first error stays the one reported.)
-    (void)hipMemset2DAsync(c->hist.p, (size_t)SCR_WORDS * sizeof(uint32_t), 0, sizeof(SelHeader), (size_t)nq, st);
-    (void)hipStreamSynchronize(st);
+    // all-zero scratch.  (Best effort, behind whatever is still queued and drained by the frame; the first error stays
+    // the one reported.)
+    (void)hipMemset2DAsync(c->hist.p, (size_t)SCR_WORDS * sizeof(uint32_t), 0, sizeof(SelHeader), (size_t)nq, fr.stream());
   }
   return rc;
 }

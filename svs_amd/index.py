@@ -105,12 +105,25 @@ class DeviceIndex:
         except Exception:
             pass
 
-    def _live_rows(self) -> int:
+    def _live_rows(self, h: Optional[int] = None) -> int:
         """Rows a search can return right now (the handle may have been appended to or
-        masked through another owner since this object last looked)."""
+        masked through another owner since this object last looked).  ``h``: a pinned handle to ask."""
         info = _native.IndexInfo()
-        _native.check(self._quick.svs_index_info(self._handle(), C.byref(info)))
+        _native.check(self._quick.svs_index_info(self._handle() if h is None else h, C.byref(info)))
         return max(int(info.n) - int(info.n_masked), 0)
+
+    @staticmethod
+    def _queries_2d(queries) -> np.ndarray:
+        """The queries of a batched search as a C-contiguous f32 (nq, D) array."""
+        q = np.ascontiguousarray(queries, dtype=np.float32)
+        if q.ndim != 2:
+            raise ValueError(f"queries must be 2-D, got shape {q.shape}")
+        return q
+
+    @staticmethod
+    def _trimmed(scores: np.ndarray, rows: np.ndarray, count: int) -> Tuple[np.ndarray, np.ndarray]:
+        """Both (nq, k) result arrays cut to the ``count`` entries per query the library wrote."""
+        return (scores, rows) if count == scores.shape[1] else (scores[:, :count], rows[:, :count])
 
     def _pinned_handle(self) -> int:
         """retain() under the lock so a concurrent release() cannot free the
@@ -190,9 +203,7 @@ class DeviceIndex:
         tests and tools."""
         h = self._pinned_handle()
         try:
-            info = _native.IndexInfo()
-            _native.check(self._quick.svs_index_info(h, C.byref(info)))
-            live = max(int(info.n) - int(info.n_masked), 0)
+            live = self._live_rows(h)
             for _ in range(8):
                 # (rows appended through another owner since the map was sized: the call reports the count to retry with)
                 out = np.empty(live, dtype=np.int64)
@@ -226,18 +237,14 @@ class DeviceIndex:
         (scores f32 (nq, count), rows i64 (nq, count)), count = min(max(n,0), N),
         each row ordered (score desc, row desc)."""
         assert isinstance(n, int)  # reference src/svs/util.py:197
-        q = np.ascontiguousarray(queries, dtype=np.float32)
-        if q.ndim != 2:
-            raise ValueError(f"queries must be 2-D, got shape {q.shape}")
+        q = self._queries_2d(queries)
         nq, d = q.shape
         h = self._pinned_handle()
         try:
             # clamp before allocating and before the int32 argument (reference src/svs/util.py:198-199
             # clamps top_k to len(scores) first): k = 2**32 must mean "rank everything", not 0.  (The row count is
             # read through the pinned handle: the index may have been appended to or masked through another owner.)
-            info = _native.IndexInfo()
-            _native.check(self._quick.svs_index_info(h, C.byref(info)))
-            k = min(max(n, 0), max(int(info.n) - int(info.n_masked), 0))
+            k = min(max(n, 0), self._live_rows(h))
             scores = np.empty((nq, k), dtype=np.float32)
             rows = np.empty((nq, k), dtype=np.int64)
             count = C.c_int32(0)
@@ -246,8 +253,7 @@ class DeviceIndex:
                                                      C.byref(count)))
         finally:
             self._unpin(h)
-        c = count.value
-        return (scores, rows) if c == k else (scores[:, :c], rows[:, :c])
+        return self._trimmed(scores, rows, count.value)
 
     def search(self, query_vec: np.ndarray, n: int) -> List[Tuple[float, int]]:
         """``get_top_k(np.dot(M, query_vec), n)``: list of (score, row index),
@@ -266,9 +272,7 @@ class DeviceIndex:
         live listed rows), each row ordered (score desc, row desc) -- ``get_top_k(np.dot(M[S], q), n)``
         with positions mapped back to rows S (svs_index_search_rows)."""
         assert isinstance(n, int)
-        q = np.ascontiguousarray(queries, dtype=np.float32)
-        if q.ndim != 2:
-            raise ValueError(f"queries must be 2-D, got shape {q.shape}")
+        q = self._queries_2d(queries)
         r = np.ascontiguousarray(rows, dtype=np.int64).reshape(-1)
         nq, d = q.shape
         k = min(max(n, 0), len(r), 2 ** 31 - 1)   # (count <= listed rows: clamp before allocating)
@@ -281,8 +285,7 @@ class DeviceIndex:
                                                           scores.ctypes.data, out_rows.ctypes.data, C.byref(count)))
         finally:
             self._unpin(h)
-        c = count.value
-        return (scores, out_rows) if c == k else (scores[:, :c], out_rows[:, :c])
+        return self._trimmed(scores, out_rows, count.value)
 
     def search_within(self, query_vec: np.ndarray, n: int, rows) -> List[Tuple[float, int]]:
         """``search`` restricted to the listed rows (see ``search_batch_within``): [(score, row)]."""
@@ -301,9 +304,7 @@ class DeviceIndex:
         ordered (score desc, row desc): the rows and score bits ``search_within(queries[seg_query[s]], n,
         row_lists[s])`` gives.  Nothing is merged across segments."""
         assert isinstance(n, int)
-        q = np.ascontiguousarray(queries, dtype=np.float32)
-        if q.ndim != 2:
-            raise ValueError(f"queries must be 2-D, got shape {q.shape}")
+        q = self._queries_2d(queries)
         lists = [np.asarray(r, dtype=np.int64).reshape(-1) for r in row_lists]
         nseg = len(lists)
         nq, d = q.shape
@@ -338,9 +339,7 @@ class DeviceIndex:
         ``(scores f32 (count,), rows i64 (count,), total)`` per query: count = min(max(limit, 0), total), total = the
         number of qualifying rows, exact however large.  ``limit=0`` only counts.  A NaN cut-off is a ValueError."""
         assert isinstance(limit, int)
-        q = np.ascontiguousarray(queries, dtype=np.float32)
-        if q.ndim != 2:
-            raise ValueError(f"queries must be 2-D, got shape {q.shape}")
+        q = self._queries_2d(queries)
         nq, d = q.shape
         cut = np.ascontiguousarray(min_scores, dtype=np.float32).reshape(-1)
         if len(cut) != nq:
@@ -350,9 +349,7 @@ class DeviceIndex:
         h = self._pinned_handle()
         try:
             # (clamped before allocating and before the int32 argument, as in search_batch)
-            info = _native.IndexInfo()
-            _native.check(self._quick.svs_index_info(h, C.byref(info)))
-            k = min(max(limit, 0), max(int(info.n) - int(info.n_masked), 0))
+            k = min(max(limit, 0), self._live_rows(h))
             scores = np.empty((nq, k), dtype=np.float32)
             rows = np.empty((nq, k), dtype=np.int64)
             counts = np.zeros(nq, dtype=np.int32)
@@ -385,9 +382,7 @@ class DeviceIndex:
         h = self._pinned_handle()
         try:
             # (clamped before allocating and before the int32 argument, as in search_batch)
-            info = _native.IndexInfo()
-            _native.check(self._quick.svs_index_info(h, C.byref(info)))
-            k = min(max(n, 0), max(int(info.n) - int(info.n_masked) - 1, 0))
+            k = min(max(n, 0), max(self._live_rows(h) - 1, 0))
             scores = np.empty((len(r), k), dtype=np.float32)
             out_rows = np.empty((len(r), k), dtype=np.int64)
             count = C.c_int32(0)
@@ -396,8 +391,7 @@ class DeviceIndex:
                                                         C.byref(count)))
         finally:
             self._unpin(h)
-        c = count.value
-        return (scores, out_rows) if c == k else (scores[:, :c], out_rows[:, :c])
+        return self._trimmed(scores, out_rows, count.value)
 
     def scores(self, query_vec: np.ndarray) -> np.ndarray:
         """The raw ``np.dot(M, q)`` vector, f32 (N,)."""

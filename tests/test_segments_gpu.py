@@ -347,6 +347,57 @@ def test_tombstones_row_offset_and_compaction(gpu):
         idx.release()
 
 
+def test_placement_of_segments_around_sort_cap(gpu):
+    """Where a segment goes is decided by its LIVE DISTINCT rows, known only once its list is built: segments that list
+    more than SORT_CAP rows and are small after all (repeats, tombstones), an unsorted large one, two large ones in a
+    call, a small one behind a large one.  At k = 50 against search_within and the launch records; at k >= every live
+    count against numpy (the list builder is shared with search_within) and the f64 dot products of the stored rows:
+    2e-6, the f32 bound for unit-norm rows."""
+    from svs_amd import DeviceIndex
+    rng = np.random.default_rng(48)
+    n, d, off = 12_000, 768, 1_000_000
+    m, qs = _unit(rng, n, d), _unit(rng, 2, d)
+    kernel = "gather_scores_kernel<0, 64, 3, 4, 1>"
+    gone = rng.choice(n, 3_000, replace=False)
+    dead = np.zeros(n, dtype=bool)
+    dead[gone] = True
+    alive = np.flatnonzero(~dead)
+    distinct2 = np.concatenate([rng.choice(alive, 6_500, replace=False), rng.choice(gone, 500, replace=False)])
+    lists = [
+        rng.choice(rng.choice(n, 3_000, replace=False), 5_000),                                       # small after all: repeats
+        rng.permutation(np.concatenate([rng.choice(alive, 3_500, replace=False), rng.choice(gone, 2_500, replace=False)])),   # ... tombstones
+        rng.permutation(np.concatenate([distinct2, rng.choice(distinct2, 2_000)])),                   # large, unsorted
+        np.sort(rng.choice(alive, 30, replace=False)),                                                # small, behind a large one
+        np.sort(rng.choice(alive, 5_000, replace=False)),                                             # large, ascending
+        rng.choice(gone, 100, replace=False),                                                         # dead rows only
+    ]
+    lists = [off + np.asarray(r, dtype=np.int64) for r in lists]
+    seg_query = [0, 1, 1, 0, 1, 0]
+    live = [_live(dead, off, r) for r in lists]
+    assert [len(r) > SORT_CAP for r in lists] == [True, True, True, False, True, False]
+    assert [len(u) for u in live][1:] == [3_500, 6_500, 30, 5_000, 0] and 0 < len(live[0]) <= 3_000
+    idx = DeviceIndex(m, row_offset=off)
+    try:
+        idx.mask_rows(off + gone)
+        got = idx.search_segments(qs, 50, lists, seg_query)
+        _assert_launches(idx, lists, kernel, dead=dead)
+        for s in range(6):
+            _assert_equal(got[s], _reference(idx, qs[seg_query[s]], 50, lists[s]), f"placement, segment {s}")
+        full = idx.search_segments(qs, 8_000, lists, seg_query)
+        for s in range(6):
+            sc, rr = full[s]
+            assert len(rr) == len(live[s]), f"segment {s}: {len(rr)} results for {len(live[s])} distinct live listed rows"
+            assert np.array_equal(np.sort(rr), live[s]), f"segment {s}: other rows than the distinct live listed ones"
+            tie = sc[:-1] == sc[1:]
+            assert np.all((sc[:-1] > sc[1:]) | (tie & (rr[:-1] > rr[1:]))), f"segment {s}: not ordered (score desc, row desc)"
+            truth = m[rr - off].astype(np.float64) @ qs[seg_query[s]].astype(np.float64)
+            err = float(np.max(np.abs(sc.astype(np.float64) - truth))) if len(rr) else 0.0
+            print(f"placement segment {s} ({len(rr)} rows): max |score - f64| = {err:.3g}")
+            assert err <= 2e-6, (s, err)
+    finally:
+        idx.release()
+
+
 # ---- e. errors ----------------------------------------------------------------------------------------------------------
 def test_errors_write_nothing(gpu):
     from svs_amd import DeviceIndex, _native
