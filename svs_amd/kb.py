@@ -30,8 +30,7 @@ from typing import Any, Awaitable, Callable, Dict, Iterator, List, Optional, Tup
 import numpy as np
 
 from .index import DeviceIndex
-from .matrix import (DeviceEmbeddingsMatrix, ids_of_batch, ids_of_pairs, ids_of_rows, neighbors_held, search_mapped,
-                     search_above_held, search_within_held, search_within_many_held, single_search)
+from .matrix import DeviceEmbeddingsMatrix, above_op, batch_op, neighbors_op, pairs_op, segments_op, single_op, within_op
 
 _LOG = logging.getLogger(__name__)
 
@@ -322,6 +321,31 @@ def _blocks_from_store(store: _Store, acquire=None):
         yield from store.embedding_blocks(acquire=acquire)
 
 
+def _device_matrix(device: int, index_factory: Callable[..., Any], dtype: str) -> DeviceEmbeddingsMatrix:
+    """The matrix cache of ``KB`` / ``AsyncKB``: built from the store, streamed, no host copy."""
+    if dtype != "f32":   # storage dtype of the HBM copy ("f16", "fp8"); f32 is the reference's arithmetic
+        import functools
+        index_factory = functools.partial(index_factory, dtype=dtype)
+    return DeviceEmbeddingsMatrix(device=device, builder=_build_from_store, index_factory=index_factory,
+                                  keep_host_matrix=False, block_builder=_blocks_from_store)
+
+
+def _chunks(texts: List[str]) -> List[List[str]]:
+    """``texts`` in slices of ``BULK_EMBEDDING_CHUNK_SIZE`` (as it reads now), the way bulk_add_docs embeds."""
+    return [texts[c0:c0 + BULK_EMBEDDING_CHUNK_SIZE] for c0 in range(0, len(texts), BULK_EMBEDDING_CHUNK_SIZE)]
+
+
+def _fetch_list(db: _Store, emb_ids: List[Tuple[float, int]]) -> List[Dict[str, Any]]:
+    """[(score, emb id)] -> ``Retrieval`` list, the docs fetched with one SQL statement; call it in a transaction."""
+    docs = db.fetch_docs_for_embeddings([e for _, e in emb_ids])
+    return [{"score": s, "doc": docs[e]} for s, e in emb_ids]
+
+
+def _fetch_lists(db: _Store, per_list: List[List[Tuple[float, int]]]) -> List[List[Dict[str, Any]]]:
+    """``_fetch_list`` of every list: one SQL fetch per list (as ``retrieve_many``)."""
+    return [_fetch_list(db, emb_ids) for emb_ids in per_list]
+
+
 class KB:
     """Sync knowledge base, retrieve() path only.  Mirrors reference
     src/svs/kb.py:1407-1640."""
@@ -332,12 +356,7 @@ class KB:
             raise RuntimeError("No embedding function. You must pass the embedding function you want to use.")
         self.embedding_func = embedding_func
         self.db: Optional[_Store] = _Store(local_path)
-        if dtype != "f32":   # storage dtype of the HBM copy ("f16", "fp8"); f32 is the reference's arithmetic
-            import functools
-            index_factory = functools.partial(index_factory, dtype=dtype)
-        self.embeddings_matrix = DeviceEmbeddingsMatrix(device=device, builder=_build_from_store,
-                                                        index_factory=index_factory, keep_host_matrix=False,
-                                                        block_builder=_blocks_from_store)
+        self.embeddings_matrix = _device_matrix(device, index_factory, dtype)
         self._loop = asyncio.new_event_loop()
 
     # -- embedding helpers (A8) -------------------------------------------------
@@ -347,6 +366,9 @@ class KB:
         vectors = self._loop.run_until_complete(awaitable)
         check_magnitude(vectors)
         return vectors
+
+    def _embed_chunked(self, texts: List[str]) -> List[List[float]]:
+        return [vec for chunk in _chunks(texts) for vec in self._embed(chunk)]
 
     def __len__(self) -> int:
         assert self.db is not None
@@ -446,7 +468,6 @@ class KB:
         _LOG.info(f"retrieved top {n} documents")
         return res
 
-
     def retrieve_within(self, query: str, n: int, doc_ids: List[int]) -> List[Dict[str, Any]]:
         """``retrieve`` restricted to the documents ``doc_ids`` (the children of one parent, the docs of one
         level, ...): the top n of those docs, same log lines and result shape.  Only their rows are scored
@@ -461,8 +482,7 @@ class KB:
         emb_ids = self.embeddings_matrix.search_within(query_vec, n, emb)   # superheavy() over the listed rows: HIP
         _LOG.info(f"computed {len(emb)} cosine similarities")
         with self.db.transaction():
-            docs = self.db.fetch_docs_for_embeddings([e for _, e in emb_ids])
-        res = [{"score": score, "doc": docs[e]} for score, e in emb_ids]
+            res = _fetch_list(self.db, emb_ids)
         _LOG.info(f"retrieved top {n} documents")
         return res
 
@@ -481,8 +501,7 @@ class KB:
         emb_ids, total = self.embeddings_matrix.search_above(query_vec, float(min_score), n)   # HIP
         _LOG.info(f"computed {self.embeddings_matrix.index.shape[0]} cosine similarities")
         with self.db.transaction():
-            docs = self.db.fetch_docs_for_embeddings([e for _, e in emb_ids])
-        res = [{"score": score, "doc": docs[e]} for score, e in emb_ids]
+            res = _fetch_list(self.db, emb_ids)
         _LOG.info(f"retrieved top {n} documents")
         return res, total
 
@@ -499,8 +518,7 @@ class KB:
         emb_ids = self.embeddings_matrix.neighbors([emb], n)[0]          # HIP
         _LOG.info(f"computed {self.embeddings_matrix.index.shape[0]} cosine similarities")
         with self.db.transaction():
-            docs = self.db.fetch_docs_for_embeddings([e for _, e in emb_ids])
-        res = [{"score": score, "doc": docs[e]} for score, e in emb_ids]
+            res = _fetch_list(self.db, emb_ids)
         _LOG.info(f"retrieved top {n} documents")
         return res
 
@@ -542,18 +560,12 @@ class KB:
         _LOG.info(f"retrieving {n} documents for each of {len(queries)} query strings")
         assert self.db is not None
         self.embeddings_matrix.get_sync(self.db)
-        vecs: List[List[float]] = []
-        for c0 in range(0, len(queries), BULK_EMBEDDING_CHUNK_SIZE):
-            vecs.extend(self._embed(queries[c0:c0 + BULK_EMBEDDING_CHUNK_SIZE]))
+        vecs = self._embed_chunked(queries)
         if not vecs:
             return []
         per_query = self.embeddings_matrix.search_many(np.array(vecs, dtype=np.float32), n)
-        out: List[List[Dict[str, Any]]] = []
         with self.db.transaction():
-            for emb_ids in per_query:
-                docs = self.db.fetch_docs_for_embeddings([e for _, e in emb_ids])
-                out.append([{"score": s, "doc": docs[e]} for s, e in emb_ids])
-        return out
+            return _fetch_lists(self.db, per_query)
 
     def retrieve_many_within(self, queries: List[str], n: int, doc_id_lists: List[List[int]]) -> List[List[Dict[str, Any]]]:
         """``retrieve_within`` for many (query, doc list) pairs -- requests that each carry their own tenant, book or
@@ -568,15 +580,14 @@ class KB:
         self.embeddings_matrix.get_sync(self.db)
         with self.db.transaction():
             embs = [self.db.embeddings_for_docs(list(ids)) for ids in doc_id_lists]
-        vecs: List[List[float]] = []
-        for c0 in range(0, len(queries), BULK_EMBEDDING_CHUNK_SIZE):
-            vecs.extend(self._embed(queries[c0:c0 + BULK_EMBEDDING_CHUNK_SIZE]))
+        vecs = self._embed_chunked(queries)
         if not vecs:
             return []
         _LOG.info("got embeddings for the queries!")
         per_list = self.embeddings_matrix.search_within_many(np.array(vecs, dtype=np.float32), n, embs)   # HIP
         _LOG.info(f"computed {sum(len(e) for e in embs)} cosine similarities")
-        res = self._fetch_lists(per_list)
+        with self.db.transaction():
+            res = _fetch_lists(self.db, per_list)
         _LOG.info(f"retrieved top {n} documents for {len(queries)} queries")
         return res
 
@@ -596,18 +607,10 @@ class KB:
         _LOG.info("got embedding for query!")
         per_list = self.embeddings_matrix.search_within_many(query_vec[None, :], n, embs, [0] * len(embs))   # HIP
         _LOG.info(f"computed {sum(len(e) for e in embs)} cosine similarities")
-        res = self._fetch_lists(per_list)
+        with self.db.transaction():
+            res = _fetch_lists(self.db, per_list)
         _LOG.info(f"retrieved top {n} documents for {len(embs)} lists")
         return res
-
-    def _fetch_lists(self, per_list: List[List[Tuple[float, int]]]) -> List[List[Dict[str, Any]]]:
-        """[(score, emb id)] lists -> ``Retrieval`` lists, one SQL fetch per list (as ``retrieve_many``)."""
-        out: List[List[Dict[str, Any]]] = []
-        with self.db.transaction():
-            for emb_ids in per_list:
-                docs = self.db.fetch_docs_for_embeddings([e for _, e in emb_ids])
-                out.append([{"score": s, "doc": docs[e]} for s, e in emb_ids])
-        return out
 
 
 class AsyncKB:
@@ -624,12 +627,7 @@ class AsyncKB:
         self._path = local_path
         self.db: Optional[_Store] = None
         self._lock: Optional[asyncio.Lock] = None
-        if dtype != "f32":   # storage dtype of the HBM copy ("f16", "fp8"); f32 is the reference's arithmetic
-            import functools
-            index_factory = functools.partial(index_factory, dtype=dtype)
-        self.embeddings_matrix = DeviceEmbeddingsMatrix(device=device, builder=_build_from_store,
-                                                        index_factory=index_factory, keep_host_matrix=False,
-                                                        block_builder=_blocks_from_store)
+        self.embeddings_matrix = _device_matrix(device, index_factory, dtype)
 
     def _get_lock(self) -> asyncio.Lock:
         if self._lock is None:
@@ -646,6 +644,46 @@ class AsyncKB:
         vectors = await self.embedding_func(texts)
         check_magnitude(vectors)
         return vectors
+
+    async def _embed_chunked(self, texts: List[str]) -> List[List[float]]:
+        return [vec for chunk in _chunks(texts) for vec in await self._embed(chunk)]
+
+    # -- the frame of every retrieval: SQL and the reference to the index under the lock, the embedding and the search
+    # -- outside it, the documents under the lock again (reference src/svs/kb.py:1171-1206)
+    @staticmethod
+    async def _in_transaction(db: _Store, work: Callable[[_Store], Any]) -> Any:
+        """``work(db)`` inside one transaction, on an executor thread; the caller holds the lock."""
+        def run():
+            with db.transaction():
+                return work(db)
+
+        return await asyncio.get_running_loop().run_in_executor(None, run)
+
+    @asynccontextmanager
+    async def _held(self, sql: Optional[Callable[[_Store], Any]] = None, single: bool = False):
+        """Entry, under the lock: the store, the loaded matrix, ``sql(db)`` (if given: the doc id -> embedding id
+        queries, in a transaction on an executor thread; what it raises leaves before any reference is taken), then
+        ``hold()`` -- ``hold_search()`` for ``single`` -- so that a later invalidate() cannot affect this search.
+        Yields (held, what ``sql`` returned) with the lock FREE: the body embeds and searches while other tasks use
+        the KB.  Releases the index however the body ends: a return, an exception, a cancellation."""
+        async with self._get_lock():
+            db = await self._ensure_db()
+            await self.embeddings_matrix.get(db)
+            found = await self._in_transaction(db, sql) if sql is not None else None
+            held = self.embeddings_matrix.hold_search() if single else self.embeddings_matrix.hold()
+        try:
+            yield held, found
+        finally:
+            held[0].release()
+
+    async def _search(self, held: tuple, op, single: bool = False):
+        """One mapped search of svs_amd.matrix on an executor thread, against the reference ``_held`` yielded."""
+        return await asyncio.get_running_loop().run_in_executor(None, lambda: self.embeddings_matrix.run_mapped(op, held, single))
+
+    async def _fetch(self, work: Callable[[_Store], Any]) -> Any:
+        """``heavy()``: ``work(db)`` under the lock, inside one transaction, on an executor thread."""
+        async with self._get_lock():
+            return await self._in_transaction(await self._ensure_db(), work)
 
     async def load(self) -> None:
         async with self._get_lock():
@@ -732,34 +770,13 @@ class AsyncKB:
     async def retrieve(self, query: str, n: int) -> List[Dict[str, Any]]:
         """Reference src/svs/kb.py:1171-1206."""
         _LOG.info(f"retrieving {n} documents with query string: {query}")
-        loop = asyncio.get_running_loop()
-        async with self._get_lock():
-            db = await self._ensure_db()
-            await self.embeddings_matrix.get(db)
-            # own a reference now: a later invalidate() must not affect this search
-            held = self.embeddings_matrix.hold_search()
-            idx = held[0]
-        try:
+        async with self._held(single=True) as (held, _):
             query_vec = np.array((await self._embed([query]))[0], dtype=np.float32)
             _LOG.info("got embedding for query!")
-
-            def superheavy() -> List[Tuple[float, int]]:
-                # tasks whose searches are in flight together share corpus passes (svs_amd/coalesce.py)
-                return search_mapped(self.embeddings_matrix.hold_search, held,
-                                     lambda idx, lookup, co: single_search(idx, co, query_vec, n), ids_of_rows)
-
-            emb_ids = await loop.run_in_executor(None, superheavy)
-            _LOG.info(f"computed {idx.shape[0]} cosine similarities")
-        finally:
-            idx.release()
-        async with self._get_lock():
-            db = await self._ensure_db()
-
-            def heavy() -> List[Dict[str, Any]]:
-                with db.transaction():
-                    return [{"score": s, "doc": db.fetch_doc_for_embedding(e)} for s, e in emb_ids]
-
-            res = await loop.run_in_executor(None, heavy)
+            # tasks whose searches are in flight together share corpus passes (svs_amd/coalesce.py)
+            emb_ids = await self._search(held, single_op(query_vec, n), single=True)
+            _LOG.info(f"computed {held[0].shape[0]} cosine similarities")
+        res = await self._fetch(lambda db: [{"score": s, "doc": db.fetch_doc_for_embedding(e)} for s, e in emb_ids])
         _LOG.info(f"retrieved top {n} documents")
         return res
 
@@ -767,35 +784,13 @@ class AsyncKB:
         """Async twin of ``KB.retrieve_within``, structured as ``retrieve``: the SQL and the reference to the
         matrix under the lock, the filtered search on an executor thread outside it, the docs under the lock."""
         _LOG.info(f"retrieving {n} documents with query string: {query}")
-        loop = asyncio.get_running_loop()
         ids = list(doc_ids)
-        async with self._get_lock():
-            db = await self._ensure_db()
-            await self.embeddings_matrix.get(db)
-
-            def sql() -> List[int]:
-                with db.transaction():
-                    return db.embeddings_for_docs(ids)
-
-            emb = await loop.run_in_executor(None, sql)
-            idx, lookup = self.embeddings_matrix.hold()
-        try:
+        async with self._held(lambda db: db.embeddings_for_docs(ids)) as (held, emb):
             query_vec = np.array((await self._embed([query]))[0], dtype=np.float32)
             _LOG.info("got embedding for query!")
-            emb_ids = await loop.run_in_executor(None, lambda: search_within_held(idx, lookup, query_vec, n, emb,
-                                                                                       self.embeddings_matrix.hold))
+            emb_ids = await self._search(held, within_op(query_vec, n, emb))
             _LOG.info(f"computed {len(emb)} cosine similarities")
-        finally:
-            idx.release()
-        async with self._get_lock():
-            db = await self._ensure_db()
-
-            def heavy() -> List[Dict[str, Any]]:
-                with db.transaction():
-                    docs = db.fetch_docs_for_embeddings([e for _, e in emb_ids])
-                return [{"score": s, "doc": docs[e]} for s, e in emb_ids]
-
-            res = await loop.run_in_executor(None, heavy)
+        res = await self._fetch(lambda db: _fetch_list(db, emb_ids))
         _LOG.info(f"retrieved top {n} documents")
         return res
 
@@ -805,28 +800,12 @@ class AsyncKB:
         if min_score != min_score:
             raise ValueError("min_score is NaN")
         _LOG.info(f"retrieving {n} documents with query string: {query}")
-        loop = asyncio.get_running_loop()
-        async with self._get_lock():
-            db = await self._ensure_db()
-            await self.embeddings_matrix.get(db)
-            idx, lookup = self.embeddings_matrix.hold()
-        try:
+        async with self._held() as (held, _):
             query_vec = np.array((await self._embed([query]))[0], dtype=np.float32)
             _LOG.info("got embedding for query!")
-            emb_ids, total = await loop.run_in_executor(None, lambda: search_above_held(idx, lookup, query_vec, float(min_score), n,
-                                                                                              self.embeddings_matrix.hold))
-            _LOG.info(f"computed {idx.shape[0]} cosine similarities")
-        finally:
-            idx.release()
-        async with self._get_lock():
-            db = await self._ensure_db()
-
-            def heavy() -> List[Dict[str, Any]]:
-                with db.transaction():
-                    docs = db.fetch_docs_for_embeddings([e for _, e in emb_ids])
-                return [{"score": s, "doc": docs[e]} for s, e in emb_ids]
-
-            res = await loop.run_in_executor(None, heavy)
+            emb_ids, total = await self._search(held, above_op(query_vec, float(min_score), n))
+            _LOG.info(f"computed {held[0].shape[0]} cosine similarities")
+        res = await self._fetch(lambda db: _fetch_list(db, emb_ids))
         _LOG.info(f"retrieved top {n} documents")
         return res, total
 
@@ -836,40 +815,14 @@ class AsyncKB:
         batched search runs on an executor thread OUTSIDE it on a held reference, and every result
         list is fetched with one ``IN (...)`` statement.  Element i equals ``retrieve(queries[i], n)``."""
         _LOG.info(f"retrieving {n} documents for each of {len(queries)} query strings")
-        loop = asyncio.get_running_loop()
-        async with self._get_lock():
-            db = await self._ensure_db()
-            await self.embeddings_matrix.get(db)
-            idx, lookup = self.embeddings_matrix.hold()
-        try:
-            vecs: List[List[float]] = []
-            for c0 in range(0, len(queries), BULK_EMBEDDING_CHUNK_SIZE):
-                vecs.extend(await self._embed(queries[c0:c0 + BULK_EMBEDDING_CHUNK_SIZE]))
+        async with self._held() as (held, _):
+            vecs = await self._embed_chunked(queries)
             if not vecs:
                 return []
             _LOG.info("got embeddings for the queries!")
-            qmat = np.array(vecs, dtype=np.float32)
-
-            def superheavy() -> List[List[Tuple[float, int]]]:
-                return search_mapped(self.embeddings_matrix.hold, (idx, lookup), lambda idx, lookup: idx.search_batch(qmat, n),
-                                     ids_of_batch)
-
-            per_query = await loop.run_in_executor(None, superheavy)
-            _LOG.info(f"computed {idx.shape[0]} x {len(vecs)} cosine similarities")
-        finally:
-            idx.release()
-        async with self._get_lock():
-            db = await self._ensure_db()
-
-            def heavy() -> List[List[Dict[str, Any]]]:
-                out: List[List[Dict[str, Any]]] = []
-                with db.transaction():
-                    for emb_ids in per_query:
-                        docs = db.fetch_docs_for_embeddings([e for _, e in emb_ids])
-                        out.append([{"score": s, "doc": docs[e]} for s, e in emb_ids])
-                return out
-
-            res = await loop.run_in_executor(None, heavy)
+            per_query = await self._search(held, batch_op(np.array(vecs, dtype=np.float32), n))
+            _LOG.info(f"computed {held[0].shape[0]} x {len(vecs)} cosine similarities")
+        res = await self._fetch(lambda db: _fetch_lists(db, per_query))
         _LOG.info(f"retrieved top {n} documents for {len(queries)} queries")
         return res
 
@@ -878,44 +831,16 @@ class AsyncKB:
         """The body of ``retrieve_many_within`` (one query per list) and ``retrieve_within_each`` (``one_query``),
         structured as ``retrieve_within``: the SQL and the reference to the matrix under the lock, the segmented
         search on an executor thread outside it, the docs under the lock."""
-        loop = asyncio.get_running_loop()
         lists = [list(ids) for ids in doc_id_lists]
-        async with self._get_lock():
-            db = await self._ensure_db()
-            await self.embeddings_matrix.get(db)
-
-            def sql() -> List[List[int]]:
-                with db.transaction():
-                    return [db.embeddings_for_docs(ids) for ids in lists]
-
-            embs = await loop.run_in_executor(None, sql)
-            idx, lookup = self.embeddings_matrix.hold()
-        try:
+        async with self._held(lambda db: [db.embeddings_for_docs(ids) for ids in lists]) as (held, embs):
             if not embs:
                 return []
-            vecs: List[List[float]] = []
-            for c0 in range(0, len(texts), BULK_EMBEDDING_CHUNK_SIZE):
-                vecs.extend(await self._embed(texts[c0:c0 + BULK_EMBEDDING_CHUNK_SIZE]))
+            vecs = await self._embed_chunked(texts)
             _LOG.info(embedded)
-            qmat = np.array(vecs, dtype=np.float32)
             seg_query = [0] * len(embs) if one_query else None
-            per_list = await loop.run_in_executor(None, lambda: search_within_many_held(idx, lookup, qmat, n, embs, seg_query,
-                                                                                         self.embeddings_matrix.hold))
+            per_list = await self._search(held, segments_op(np.array(vecs, dtype=np.float32), n, embs, seg_query))
             _LOG.info(f"computed {sum(len(e) for e in embs)} cosine similarities")
-        finally:
-            idx.release()
-        async with self._get_lock():
-            db = await self._ensure_db()
-
-            def heavy() -> List[List[Dict[str, Any]]]:
-                out: List[List[Dict[str, Any]]] = []
-                with db.transaction():
-                    for emb_ids in per_list:
-                        docs = db.fetch_docs_for_embeddings([e for _, e in emb_ids])
-                        out.append([{"score": s, "doc": docs[e]} for s, e in emb_ids])
-                return out
-
-            res = await loop.run_in_executor(None, heavy)
+        res = await self._fetch(lambda db: _fetch_lists(db, per_list))
         _LOG.info(done)
         return res
 
@@ -937,63 +862,21 @@ class AsyncKB:
         """Async twin of ``KB.retrieve_similar``, structured as ``retrieve``: the SQL and the reference to the matrix
         under the lock, svs_index_neighbors on an executor thread outside it, the docs under the lock."""
         _LOG.info(f"retrieving {n} documents similar to document {doc_id}")
-        loop = asyncio.get_running_loop()
-        async with self._get_lock():
-            db = await self._ensure_db()
-            await self.embeddings_matrix.get(db)
-
-            def sql() -> int:
-                with db.transaction():
-                    return db.embedding_of_doc(doc_id)
-
-            emb = await loop.run_in_executor(None, sql)
-            idx, lookup = self.embeddings_matrix.hold()
-        try:
-            emb_ids = (await loop.run_in_executor(None, lambda: neighbors_held(idx, lookup, [emb], n,
-                                                                                self.embeddings_matrix.hold)))[0]
-            _LOG.info(f"computed {idx.shape[0]} cosine similarities")
-        finally:
-            idx.release()
-        async with self._get_lock():
-            db = await self._ensure_db()
-
-            def heavy() -> List[Dict[str, Any]]:
-                with db.transaction():
-                    docs = db.fetch_docs_for_embeddings([e for _, e in emb_ids])
-                return [{"score": s, "doc": docs[e]} for s, e in emb_ids]
-
-            res = await loop.run_in_executor(None, heavy)
+        async with self._held(lambda db: db.embedding_of_doc(doc_id)) as (held, emb):
+            emb_ids = (await self._search(held, neighbors_op([emb], n)))[0]
+            _LOG.info(f"computed {held[0].shape[0]} cosine similarities")
+        res = await self._fetch(lambda db: _fetch_list(db, emb_ids))
         _LOG.info(f"retrieved top {n} documents")
         return res
 
     async def document_neighbors(self, n: int, doc_ids: Optional[List[int]] = None) -> List[Tuple[int, List[Tuple[float, int]]]]:
         """Async twin of ``KB.document_neighbors``: ids only; the native call on an executor thread outside the lock."""
-        loop = asyncio.get_running_loop()
         ids = None if doc_ids is None else list(doc_ids)
-        async with self._get_lock():
-            db = await self._ensure_db()
-            await self.embeddings_matrix.get(db)
-
-            def sql() -> List[Tuple[int, int]]:
-                with db.transaction():
-                    return db.docs_with_embeddings(ids)
-
-            pairs = await loop.run_in_executor(None, sql)
-            idx, lookup = self.embeddings_matrix.hold()
-        try:
+        async with self._held(lambda db: db.docs_with_embeddings(ids)) as (held, pairs):
             _LOG.info(f"computing {n} neighbours of {len(pairs)} documents")
-            per_doc = await loop.run_in_executor(None, lambda: neighbors_held(idx, lookup, [e for _, e in pairs], n,
-                                                                              self.embeddings_matrix.hold))
-        finally:
-            idx.release()
-        async with self._get_lock():
-            db = await self._ensure_db()
-
-            def heavy() -> Dict[int, int]:
-                with db.transaction():
-                    return db.doc_ids_for_embeddings(None if ids is None else sorted({e for lst in per_doc for _, e in lst}))
-
-            doc_of = await loop.run_in_executor(None, heavy)
+            per_doc = await self._search(held, neighbors_op([e for _, e in pairs], n))
+        doc_of = await self._fetch(lambda db: db.doc_ids_for_embeddings(
+            None if ids is None else sorted({e for lst in per_doc for _, e in lst})))
         return [(d, [(s, doc_of[e]) for s, e in lst]) for (d, _), lst in zip(pairs, per_doc)]
 
     async def document_top_pairwise_scores(self, n: int) -> List[Tuple[float, Dict[str, Any], Dict[str, Any]]]:
@@ -1001,29 +884,11 @@ class AsyncKB:
         pairs, [(score, doc_1, doc_2)].  ``superheavy`` -- there ``np.dot(M, M.T)`` + ``get_top_pairs``
         (src/svs/kb.py:1219, src/svs/util.py:206-233) -- is svs_index_top_pairs on an executor
         thread, outside the lock, on a held reference."""
-        loop = asyncio.get_running_loop()
-        async with self._get_lock():
-            db = await self._ensure_db()
-            await self.embeddings_matrix.get(db)
-            idx, lookup = self.embeddings_matrix.hold()
-        try:
-            n_docs = idx.shape[0]
+        async with self._held() as (held, _):
+            n_docs = held[0].shape[0]
             _LOG.info(f"computing pairwise similarity over {n_docs} documents")
-
-            def superheavy() -> List[Tuple[float, int, int]]:
-                return search_mapped(self.embeddings_matrix.hold, (idx, lookup), lambda idx, lookup: idx.top_pairs(n), ids_of_pairs)
-
-            pairs = await loop.run_in_executor(None, superheavy)
+            pairs = await self._search(held, pairs_op(n))
             _LOG.info(f"computed {n_docs * n_docs} pairwise cosine similarities")
-        finally:
-            idx.release()
-        async with self._get_lock():
-            db = await self._ensure_db()
-
-            def heavy() -> Dict[int, Dict[str, Any]]:
-                with db.transaction():
-                    return db.fetch_docs_for_embeddings(sorted({e for _, a, b in pairs for e in (a, b)}))
-
-            docs = await loop.run_in_executor(None, heavy)
+        docs = await self._fetch(lambda db: db.fetch_docs_for_embeddings(sorted({e for _, a, b in pairs for e in (a, b)})))
         _LOG.info(f"retrieved top {n} document pairs")
         return [(score, docs[a], docs[b]) for score, a, b in pairs]

@@ -104,11 +104,32 @@ def _within_rows(idx, lookup: _Lookup, emb_ids) -> np.ndarray:
     return pos + int(getattr(idx, "row_offset", 0))
 
 
-def search_within_held(idx, lookup: _Lookup, query_vec: np.ndarray, n: int, emb_ids,
-                       hold: Optional[Callable[[], tuple]] = None) -> List[Tuple[float, int]]:
-    """Top-n among ``emb_ids`` on a held (index, lookup): ids -> rows through ``lookup.arr``, the filtered search,
-    rows -> ids.  KeyError for an id the loaded matrix does not hold.  ``hold``: where ``search_mapped`` gets a
-    fresh (index, lookup) when a compaction renumbered the rows meanwhile."""
+# The mapped searches: each returns its (native, finish) pair for ``search_mapped`` -- ``native(idx, lookup[, co])`` maps
+# embedding ids to rows of THAT lookup and runs the search, ``finish(result, lookup.arr)`` maps the rows back to ids.
+# ``DeviceEmbeddingsMatrix.run_mapped`` runs one.
+
+def single_op(query_vec: np.ndarray, n: int):
+    """One query: [(score, emb_id)].  Through the generation's coalescer when ``hold_search`` gave one (concurrent
+    callers -- threads of a server, AsyncKB's executor threads -- share corpus passes)."""
+    def native(idx, lookup, co):
+        return co.search(idx, query_vec, n) if co is not None else idx.search(query_vec, n)
+
+    return native, ids_of_rows
+
+
+def batch_op(query_vecs: np.ndarray, n: int):
+    """``idx.search_batch``: one [(score, emb_id)] list per row of ``query_vecs``."""
+    return (lambda idx, lookup: idx.search_batch(query_vecs, n)), ids_of_batch
+
+
+def pairs_op(n: int):
+    """``idx.top_pairs`` (svs_index_top_pairs): [(score, emb_id_1, emb_id_2)]."""
+    return (lambda idx, lookup: idx.top_pairs(n)), ids_of_pairs
+
+
+def within_op(query_vec: np.ndarray, n: int, emb_ids):
+    """Top-n among ``emb_ids``: ids -> rows through ``lookup.arr``, the filtered search, rows -> ids.  KeyError for an
+    id the loaded matrix does not hold."""
     def native(idx, lookup, *_):
         return idx, idx.search_within(query_vec, n, _within_rows(idx, lookup, emb_ids))
 
@@ -117,15 +138,13 @@ def search_within_held(idx, lookup: _Lookup, query_vec: np.ndarray, n: int, emb_
         off = int(getattr(used, "row_offset", 0))
         return [(score, int(arr[row - off])) for score, row in rows]
 
-    return search_mapped(hold if hold is not None else _no_hold, (idx, lookup), native, finish)
+    return native, finish
 
 
-def search_within_many_held(idx, lookup: _Lookup, query_vecs: np.ndarray, n: int, emb_id_lists, seg_query=None,
-                            hold: Optional[Callable[[], tuple]] = None) -> List[List[Tuple[float, int]]]:
-    """``search_within_held`` for many id lists in one native call (``idx.search_segments``,
-    svs_index_search_segments): list s is searched with query ``seg_query[s]`` of ``query_vecs`` (None: query s).
-    One [(score, emb_id)] list per id list.  KeyError for an id the loaded matrix does not hold; ``hold`` as in
-    ``search_within_held``."""
+def segments_op(query_vecs: np.ndarray, n: int, emb_id_lists, seg_query=None):
+    """``within_op`` for many id lists in one native call (``idx.search_segments``, svs_index_search_segments): list s
+    is searched with query ``seg_query[s]`` of ``query_vecs`` (None: query s).  One [(score, emb_id)] list per id list.
+    KeyError for an id the loaded matrix does not hold."""
     id_lists = [e if isinstance(e, np.ndarray) else list(e) for e in emb_id_lists]
 
     def native(idx, lookup, *_):
@@ -136,15 +155,13 @@ def search_within_many_held(idx, lookup: _Lookup, query_vecs: np.ndarray, n: int
         off = int(getattr(used, "row_offset", 0))
         return [list(zip(s.astype(np.float64).tolist(), arr[r - off].tolist())) for s, r in per_seg]
 
-    return search_mapped(hold if hold is not None else _no_hold, (idx, lookup), native, finish)
+    return native, finish
 
 
-def neighbors_held(idx, lookup: _Lookup, emb_ids, n: int,
-                   hold: Optional[Callable[[], tuple]] = None) -> List[List[Tuple[float, int]]]:
-    """Neighbours of stored embeddings on a held (index, lookup): ids -> rows through ``lookup.arr``,
-    ``idx.neighbors`` (svs_index_neighbors), rows -> ids: one [(score, emb_id)] list per id, in the order given.
-    KeyError for an id the loaded matrix does not hold.  ``hold`` as in ``search_within_held``: the mapping and the
-    call are repeated on a fresh (index, lookup) when a compaction renumbered the rows meanwhile."""
+def neighbors_op(emb_ids, n: int):
+    """Neighbours of stored embeddings: ids -> rows through ``lookup.arr``, ``idx.neighbors`` (svs_index_neighbors),
+    rows -> ids: one [(score, emb_id)] list per id, in the order given.  KeyError for an id the loaded matrix does not
+    hold."""
     def native(idx, lookup, *_):
         return idx, idx.neighbors(_within_rows(idx, lookup, emb_ids), n)
 
@@ -152,13 +169,11 @@ def neighbors_held(idx, lookup: _Lookup, emb_ids, n: int,
         used, (scores, rows) = res
         return ids_of_batch((scores, rows - int(getattr(used, "row_offset", 0))), arr)
 
-    return search_mapped(hold if hold is not None else _no_hold, (idx, lookup), native, finish)
+    return native, finish
 
 
-def search_above_held(idx, lookup: _Lookup, query_vec: np.ndarray, min_score: float, n: int,
-                      hold: Optional[Callable[[], tuple]] = None) -> Tuple[List[Tuple[float, int]], int]:
-    """Threshold search on a held (index, lookup): ``idx.search_above`` (svs_index_search_above), rows -> ids:
-    ([(score, emb_id)], total).  ``hold`` as in ``search_within_held``."""
+def above_op(query_vec: np.ndarray, min_score: float, n: int):
+    """Threshold search: ``idx.search_above`` (svs_index_search_above), rows -> ids: ([(score, emb_id)], total)."""
     def native(idx, lookup, *_):
         return idx, idx.search_above(query_vec, min_score, n)
 
@@ -167,17 +182,7 @@ def search_above_held(idx, lookup: _Lookup, query_vec: np.ndarray, min_score: fl
         off = int(getattr(used, "row_offset", 0))
         return [(score, int(arr[row - off])) for score, row in rows], int(total)
 
-    return search_mapped(hold if hold is not None else _no_hold, (idx, lookup), native, finish)
-
-
-def _no_hold():
-    raise RuntimeError("the rows of the embeddings matrix were renumbered during the search")
-
-
-def single_search(idx, co, query_vec: np.ndarray, n: int):
-    """One query on a held index: through the generation's coalescer when there is one (concurrent callers --
-    threads of a server, AsyncKB's executor threads -- share corpus passes)."""
-    return co.search(idx, query_vec, n) if co is not None else idx.search(query_vec, n)
+    return native, finish
 
 
 def ids_of_rows(res, arr: np.ndarray) -> List[Tuple[float, int]]:
@@ -413,86 +418,75 @@ class DeviceEmbeddingsMatrix:
         return self._result()
 
     # -- the superheavy() body ---------------------------------------------
-    def search(self, query_vec: np.ndarray, n: int) -> List[Tuple[float, int]]:
-        """``superheavy()`` (src/svs/kb.py:1622-1627): [(score, emb_id)]."""
-        held = self.hold_search()
+    def run_mapped(self, op, held: Optional[tuple] = None, single: bool = False):
+        """Runs one mapped search (``single_op`` ... ``above_op``) through ``search_mapped``.  ``held``: the caller's own
+        ``hold()`` -- ``hold_search()`` for ``single`` -- which the caller releases; None: one is taken and released
+        here.  Either way the fresh holds of a retry after a compaction come from the same source and are released by
+        ``search_mapped``."""
+        hold = self.hold_search if single else self.hold
+        if held is not None:
+            return search_mapped(hold, held, *op)
+        held = hold()
         try:
-            return search_mapped(self.hold_search, held, lambda idx, lookup, co: single_search(idx, co, query_vec, n), ids_of_rows)
+            return search_mapped(hold, held, *op)
         finally:
             held[0].release()
 
+    def search(self, query_vec: np.ndarray, n: int) -> List[Tuple[float, int]]:
+        """``superheavy()`` (src/svs/kb.py:1622-1627): [(score, emb_id)]."""
+        return self.run_mapped(single_op(query_vec, n), single=True)
+
     def search_within(self, query_vec: np.ndarray, n: int, emb_ids) -> List[Tuple[float, int]]:
         """``search`` restricted to the listed embedding ids: [(score, emb_id)] (``KB.retrieve_within``)."""
-        idx, lookup = self.hold()
-        try:
-            return search_within_held(idx, lookup, query_vec, n, emb_ids, self.hold)
-        finally:
-            idx.release()
+        return self.run_mapped(within_op(query_vec, n, emb_ids))
 
     def search_above(self, query_vec: np.ndarray, min_score: float, n: int) -> Tuple[List[Tuple[float, int]], int]:
         """Every stored embedding scoring at or above ``min_score``, best first, at most ``n``:
         ([(score, emb_id)], total qualifying) (``KB.retrieve_above``)."""
-        idx, lookup = self.hold()
-        try:
-            return search_above_held(idx, lookup, query_vec, min_score, n, self.hold)
-        finally:
-            idx.release()
+        return self.run_mapped(above_op(query_vec, min_score, n))
 
     def search_within_many(self, query_vecs: np.ndarray, n: int, emb_id_lists, seg_query=None) -> List[List[Tuple[float, int]]]:
         """``search_within`` for many id lists in one call: list s against query ``seg_query[s]`` of ``query_vecs``
         (None: query s).  One [(score, emb_id)] list per id list (``KB.retrieve_many_within`` /
         ``KB.retrieve_within_each``)."""
-        idx, lookup = self.hold()
-        try:
-            return search_within_many_held(idx, lookup, query_vecs, n, emb_id_lists, seg_query, self.hold)
-        finally:
-            idx.release()
+        return self.run_mapped(segments_op(query_vecs, n, emb_id_lists, seg_query))
 
     def search_many(self, query_vecs: np.ndarray, n: int) -> List[List[Tuple[float, int]]]:
         """Batched ``superheavy()``: one result list per row of ``query_vecs``;
         up to 16 (f32) / 32 (f16) queries share one pass over the corpus."""
-        held = self.hold()
-        try:
-            return search_mapped(self.hold, held, lambda idx, lookup: idx.search_batch(query_vecs, n), ids_of_batch)
-        finally:
-            held[0].release()
+        return self.run_mapped(batch_op(query_vecs, n))
 
     def neighbors(self, emb_ids, n: int) -> List[List[Tuple[float, int]]]:
         """The ``n`` nearest stored embeddings of each listed embedding id, itself excluded: one
         [(score, emb_id)] list per id, in the order given (``KB.retrieve_similar`` / ``document_neighbors``).
         KeyError for an id the loaded matrix does not hold."""
-        idx, lookup = self.hold()
-        try:
-            return neighbors_held(idx, lookup, emb_ids, n, self.hold)
-        finally:
-            idx.release()
+        return self.run_mapped(neighbors_op(emb_ids, n))
 
     def top_pairs(self, n: int) -> List[Tuple[float, int, int]]:
         """``superheavy()`` of document_top_pairwise_scores (src/svs/kb.py:1650-1655):
         [(score, emb_id_1, emb_id_2)]."""
-        held = self.hold()
-        try:
-            return search_mapped(self.hold, held, lambda idx, lookup: idx.top_pairs(n), ids_of_pairs)
-        finally:
-            held[0].release()
+        return self.run_mapped(pairs_op(n))
+
+    def _loaded(self) -> Tuple[Any, _Lookup]:
+        """(index, lookup) of the loaded matrix, no reference taken; call it under ``_mu``."""
+        idx, lookup = self.index, self._lookup
+        if idx is None or lookup is None:
+            raise RuntimeError("embeddings matrix is not loaded (call get_sync/get first)")
+        return idx, lookup
 
     def hold(self) -> Tuple[Any, _Lookup]:
         """(index, lookup table) with the caller owning a reference to the index, so a
         concurrent ``invalidate()`` cannot free it mid-search.  Map rows through
         ``lookup.arr`` AFTER the search returns; release the index."""
         with self._mu:
-            idx, lookup = self.index, self._lookup
-            if idx is None or lookup is None:
-                raise RuntimeError("embeddings matrix is not loaded (call get_sync/get first)")
+            idx, lookup = self._loaded()
             return idx.share(), lookup
 
     def hold_search(self) -> Tuple[Any, _Lookup, Optional[SearchCoalescer]]:
         """``hold()`` plus the generation's coalescer (None when switched off): what ``retrieve``
         uses for its single-query search."""
         with self._mu:
-            idx, lookup = self.index, self._lookup
-            if idx is None or lookup is None:
-                raise RuntimeError("embeddings matrix is not loaded (call get_sync/get first)")
+            idx, lookup = self._loaded()
             if hasattr(idx, "set_coalesce"):
                 # a DeviceIndex coalesces inside the library (svs_index_set_coalesce): the waiting threads
                 # block in C, without the GIL -- 64 callers: 20 k queries/s where the Python class below gets 12.6 k

@@ -8,6 +8,7 @@ import threading
 import numpy as np
 import pytest
 
+import above_model
 from fake_backend import OracleIndex
 from oracle import svs_oracle as oracle
 
@@ -16,7 +17,7 @@ from svs_amd import matrix as mx
 
 
 class CompactingOracleIndex(OracleIndex):
-    """OracleIndex with ``compact()`` (and ``search_within``).  Like the library, a compaction and a search exclude
+    """OracleIndex with ``compact()`` (and ``search_within``, ``search_segments``, ``search_above``).  Like the library, a compaction and a search exclude
     each other.  ``gate = (entered, go)`` parks the NEXT native search call of any owner: it sets ``entered`` and
     waits for ``go`` before it computes anything, i.e. it sits between ``hold()`` and the native call."""
 
@@ -68,6 +69,29 @@ class CompactingOracleIndex(OracleIndex):
                 raise ValueError("row out of range")
             s = local[~self._st[1][local]]
             return [(sc, int(s[p]) + self.row_offset) for sc, p in oracle.cpu_search(self._m[s], np.asarray(q, dtype=np.float32), n)]
+
+    def search_segments(self, queries, n, row_lists, seg_query=None):
+        self._park()
+        with CompactingOracleIndex._geo:
+            q = np.ascontiguousarray(queries, dtype=np.float32)
+            row_lists = list(row_lists)
+            if seg_query is None:
+                if len(row_lists) != len(q):
+                    raise ValueError("one row list per query")
+                seg_query = range(len(q))
+            out = []
+            for rows, j in zip(row_lists, seg_query):
+                res = self.search_within(q[j], n, rows)
+                out.append((np.array([a for a, _ in res], dtype=np.float32), np.array([b for _, b in res], dtype=np.int64)))
+            return out
+
+    def search_above(self, q, min_score, limit):
+        self._park()
+        with CompactingOracleIndex._geo:
+            self._check()
+            q = np.asarray(q, dtype=np.float32)
+            rows, sc, total = above_model.above(oracle.cpu_scores(self._m, q), self._st[1], np.float32(min_score), limit)
+            return list(zip(sc.astype(np.float64).tolist(), (rows + self.row_offset).tolist())), total
 
 
 N_DOCS, DIM = 240, 24
@@ -162,7 +186,7 @@ def test_deletes_past_the_threshold_compact_in_place(tmp_path):
     assert OracleIndex.live == 0
 
 
-@pytest.mark.parametrize("what", ["search", "search_within", "search_many", "top_pairs"])
+@pytest.mark.parametrize("what", ["search", "search_within", "search_many", "top_pairs", "search_within_many", "search_above"])
 def test_search_parked_across_a_compaction_retries(tmp_path, what):
     """The search holds (index, old lookup) and is parked in front of its native call; the compaction renumbers the
     rows; the search then runs on the new numbering, finds its lookup stale and repeats on a fresh hold."""
@@ -172,8 +196,13 @@ def test_search_parked_across_a_compaction_retries(tmp_path, what):
     first, old_lookup = cache.index, cache._lookup
     q = np.array(TABLE["doc 200"], dtype=np.float32)
     keep_ids = [int(e) for e in cache.emb_id_lookup[150:240:2]]
-    calls = {"search": lambda: cache.search(q, 8), "search_within": lambda: cache.search_within(q, 8, keep_ids),
-             "search_many": lambda: cache.search_many(np.stack([q, -q]), 8), "top_pairs": lambda: cache.top_pairs(8)}
+    def calls_on(c):
+        return {"search": lambda: c.search(q, 8), "search_within": lambda: c.search_within(q, 8, keep_ids),
+                "search_many": lambda: c.search_many(np.stack([q, -q]), 8), "top_pairs": lambda: c.top_pairs(8),
+                "search_within_many": lambda: c.search_within_many(np.stack([q, -q]), 8, [keep_ids, keep_ids[::3]]),
+                "search_above": lambda: c.search_above(q, 0.1, 8)}
+
+    calls = calls_on(cache)
     entered, go = threading.Event(), threading.Event()
     CompactingOracleIndex.gate = (entered, go)
     out = {}
@@ -200,9 +229,7 @@ def test_search_parked_across_a_compaction_retries(tmp_path, what):
     assert out["res"] == calls[what]()                       # the same call on the settled cache
     fresh = svs_amd.KB(path, _ef, index_factory=CompactingOracleIndex)
     fresh.load()
-    fc = fresh.embeddings_matrix
-    want = {"search": lambda: fc.search(q, 8), "search_within": lambda: fc.search_within(q, 8, keep_ids),
-            "search_many": lambda: fc.search_many(np.stack([q, -q]), 8), "top_pairs": lambda: fc.top_pairs(8)}[what]()
+    want = calls_on(fresh.embeddings_matrix)[what]()
     assert out["res"] == want and len(built) == 1
     kb.close(); fresh.close()
     assert OracleIndex.live == 0
