@@ -342,6 +342,47 @@ int32_t svs_index_search_above(svs_index* idx, const float* queries, int32_t nq,
                                float* out_scores, int64_t* out_rows /* stride limit */,
                                int32_t* out_counts /* nq */, int64_t* out_totals /* nq, or NULL */);
 
+/* Diverse retrieval: maximal-marginal-relevance (MMR) re-ranking of the fetch_k best rows, on the device -- the answer
+ * to "the top 10 are ten versions of one paragraph" in a corpus of chunked documents, overlapping windows and
+ * near-copies.
+ * Exact definition, per query q of the call:
+ *   1. Candidates.  C = the list svs_index_search(idx, queries, nq, d, fetch_k, ...) returns for query q (this call's
+ *      nq, coalescing off): c = min(fetch_k, live rows) entries in (score desc, row desc) order, s[p] the score bits
+ *      of position p.  Every route of the ordinary search is taken unchanged; tombstoned rows never appear.
+ *   2. Similarity.  G[i][j] = the dot product of the STORED values of candidate rows i and j (what
+ *      svs_index_debug_dequant shows: f32 as is; f16 widened; fp8 as e4m3 x row scale), f32 products accumulated in
+ *      f32 over the columns in ascending order as ONE fmaf chain per element; fp8 sums the e4m3 values and multiplies
+ *      by (scale_i * scale_j) once, after the sum.  G[i][j] depends only on the two rows' stored values and on d --
+ *      not on positions, c, nq or tiles -- and G[i][j] == G[j][i] bit for bit.
+ *   3. Greedy pick.  Pick 0 is position 0.  For t >= 1: red[p] = max over earlier picks j of G[p][j],
+ *      obj[p] = lambda_mult * s[p] - (1 - lambda_mult) * red[p] in f32 (the compiler may fuse it), and the pick is the
+ *      unpicked p with the largest obj; an exact tie goes to the LOWER position (the better score, at equal score
+ *      the higher row).
+ *   4. Outputs.  *out_count = min(max(k, 0), c), the same for every query, written by every successful call.  At
+ *      out_*[q*k + t], t < count, in PICK order: the row (row_offset + local), s of the pick (the search's bits) and
+ *      red of the pick when it was chosen (-inf for pick 0, the max over nothing); out_redundancy may be NULL.
+ *      Entries past the count are not touched.
+ * It follows that lambda_mult == 1 returns the first count entries of C (rows, order and bits, for finite data), that
+ * k == 1 or c == 1 returns C[0] and launches nothing beyond the search, and that no row appears twice.
+ * Non-finite scores or stored values neither fault nor hang: the call still returns count distinct candidates; which
+ * ones is unspecified.
+ * Errors: everything is validated before anything is launched, and a failing call writes no output.  d != index d or
+ * an empty index -> SVS_ERR_SHAPE.  SVS_ERR_INVALID: nq < 0; null queries with nq > 0; lambda_mult NaN or outside
+ * [0, 1]; 0 < fetch_k < k; fetch_k <= 0 with k > 0; null out_scores, out_rows or out_count with work to do (nq > 0 and
+ * k > 0).  fetch_k > SVS_DIVERSE_MAX_FETCH -> SVS_ERR_UNSUPPORTED.  k <= 0 or nq == 0 -> SVS_OK, count 0, nothing
+ * launched.
+ * Cost: the search at fetch_k, then per block of queries (as many as keep the c x c f32 matrices within 64 MiB) one
+ * tiled f32-MFMA kernel (2 c^2 d FLOP per query over rows that sit in HBM) and one workgroup per query for the picks.
+ * Blocking; re-entrant on one handle; holds a reference and the geometry lock shared; waits for pending staging
+ * copies; never goes through the coalescer: all as svs_index_search_rows.
+ * Out of scope: svs_multi / row-sharded corpora, a device-pointer variant, fetch_k above SVS_DIVERSE_MAX_FETCH, and
+ * diversity ACROSS the queries of one call (every query is re-ranked on its own). */
+#define SVS_DIVERSE_MAX_FETCH 1024
+int32_t svs_index_search_diverse(svs_index* idx, const float* queries, int32_t nq, int32_t d,
+                                 int32_t k, int32_t fetch_k, float lambda_mult,
+                                 float* out_scores, int64_t* out_rows /* stride k */,
+                                 float* out_redundancy /* stride k, or NULL */, int32_t* out_count);
+
 /* ---- neighbours of STORED rows ("more like this", near-duplicates of one document, the kNN graph):
  *      replaces a loop of np.dot(M, M[i]) + get_top_k per row (src/svs/kb.py:1623, src/svs/util.py:190-203;
  *      0.24 s per row at 1M x 1536 by the reference's published figure).  The rows are already in HBM in the

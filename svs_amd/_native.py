@@ -86,6 +86,8 @@ SIGNATURES = {
     "svs_index_search_rows": (C.c_int32, [_P, _P, C.c_int32, C.c_int32, C.c_int32, _P, C.c_int64, _P, _P, C.POINTER(C.c_int32)]),
     "svs_index_search_segments": (C.c_int32, [_P, _P, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P, C.c_int32, _P, _P, _P]),
     "svs_index_search_above": (C.c_int32, [_P, _P, C.c_int32, C.c_int32, _P, C.c_int32, _P, _P, _P, _P]),
+    "svs_index_search_diverse": (C.c_int32, [_P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_float, _P, _P, _P,
+                                             C.POINTER(C.c_int32)]),
     "svs_index_neighbors": (C.c_int32, [_P, _P, C.c_int64, C.c_int32, _P, _P, C.POINTER(C.c_int32)]),
     "svs_index_top_pairs": (C.c_int32, [_P, C.c_int32, _P, _P, _P, C.POINTER(C.c_int32)]),
     "svs_index_debug_dequant": (C.c_int32, [_P, C.c_int64, C.c_int64, _P]),

@@ -17,6 +17,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <limits>
 #include <mutex>
 #include <shared_mutex>
 #include <new>
@@ -39,6 +40,7 @@
 #include "neighbors.h"
 #include "segments.h"
 #include "above.h"
+#include "diverse.h"
 
 namespace {
 
@@ -240,6 +242,10 @@ struct Ctx {
   DevBuf<int64_t> seg_res_dev;  PinBuf<int64_t> seg_res_pin;
   // svs_index_search_above (above.h): per query, the entries the device wrote (-1: re-run on the host) and the total
   PinBuf<int32_t> above_cnt_pin; PinBuf<int64_t> above_tot_pin;
+  // svs_index_search_diverse (diverse.h): a block of queries' c x c similarity matrices (at most DIVERSE_G_BUDGET bytes)
+  // and the call's picks; the candidates are read where the search left them, in out_s_pin / out_r_pin
+  DevBuf<float> dv_G;
+  PinBuf<float> dv_s_pin;       PinBuf<int64_t> dv_r_pin;     PinBuf<float> dv_red_pin;
   // Scratch is reused in stream order.  A context stays with the stream that
   // last used it; handing it to ANOTHER stream first drains the old one.
   hipStream_t last_stream = nullptr;
@@ -2715,18 +2721,13 @@ int32_t svs_index_info(const svs_index* idx, svs_index_info_t* out) {
   return SVS_OK;
 }
 
-static int32_t search_host(svs_index* idx, const float* queries, int32_t nq, int32_t d, int32_t k,
-                           float* out_scores, int64_t* out_rows, int32_t* out_count) {
-  RefGuard guard(idx);
-  std::shared_lock<std::shared_mutex> geo(idx->rw);
-  int rc = check_query_args(idx, queries, nq, d);
-  if (rc != SVS_OK) return rc;
-  const int count = (int)std::min<int64_t>(std::max(k, 0), idx->n - (int64_t)idx->dead_list.size());
-  if (out_count) *out_count = count;
-  if (nq == 0 || count == 0) return SVS_OK;
-  if (!out_scores || !out_rows) return fail(SVS_ERR_INVALID, "null output");
-  HostCall fr(idx);
-  if ((rc = fr.open()) != SVS_OK) return rc;
+// The host search inside an open frame, under the caller's reference and geometry lock: nq >= 1 checked queries, count
+// (1 .. live rows) results each.  They end up in the context's pinned block c->out_s_pin / c->out_r_pin at stride count
+// (device-visible), and from there in out_scores / out_rows at stride k -- unless out_scores is null: the caller
+// (svs_index_search_diverse) goes on from the pinned block.
+static int32_t search_host_framed(svs_index* idx, HostCall& fr, const float* queries, int32_t nq, int32_t d, int32_t k, int count,
+                                  float* out_scores, int64_t* out_rows) {
+  int rc;
   Ctx* const c = fr.c;
   const size_t qn = (size_t)nq * (size_t)d, on = (size_t)nq * (size_t)count;
   if ((rc = c->q_dev.grow(qn)) != SVS_OK) return rc;
@@ -2798,9 +2799,24 @@ static int32_t search_host(svs_index* idx, const float* queries, int32_t nq, int
   int n_redo = 0;
   if ((rc = rerun_overflowed(idx, fr, 0, nq, count, count, c->q_dev, nullptr, nullptr, stage, [](int) {}, &n_redo)) != SVS_OK) return rc;
   g_host_phase[5] = (double)n_redo;   // (svs_internal_host_phases: queries of this call that were re-run)
-  deliver_results(c, nq, count, k, out_scores, out_rows);
+  if (out_scores) deliver_results(c, nq, count, k, out_scores, out_rows);
   stamp(4);
   return SVS_OK;
+}
+
+static int32_t search_host(svs_index* idx, const float* queries, int32_t nq, int32_t d, int32_t k,
+                           float* out_scores, int64_t* out_rows, int32_t* out_count) {
+  RefGuard guard(idx);
+  std::shared_lock<std::shared_mutex> geo(idx->rw);
+  int rc = check_query_args(idx, queries, nq, d);
+  if (rc != SVS_OK) return rc;
+  const int count = (int)std::min<int64_t>(std::max(k, 0), idx->n - (int64_t)idx->dead_list.size());
+  if (out_count) *out_count = count;
+  if (nq == 0 || count == 0) return SVS_OK;
+  if (!out_scores || !out_rows) return fail(SVS_ERR_INVALID, "null output");
+  HostCall fr(idx);
+  if ((rc = fr.open()) != SVS_OK) return rc;
+  return search_host_framed(idx, fr, queries, nq, d, k, count, out_scores, out_rows);
 }
 
 int32_t svs_index_search(svs_index* idx, const float* queries, int32_t nq, int32_t d, int32_t k,
@@ -3251,6 +3267,91 @@ int32_t svs_index_search_above(svs_index* idx, const float* queries, int32_t nq,
     }
     out_counts[q] = count;
     if (out_totals) out_totals[q] = total;
+  }
+  return SVS_OK;
+}
+
+// The similarity matrices of one block of queries: 64 MiB, i.e. 16 queries at fetch_k = SVS_DIVERSE_MAX_FETCH (4 MiB each)
+// and every query of most calls at the usual 32-256 candidates; a block costs two launches and no host wait.
+constexpr size_t DIVERSE_G_BUDGET = (size_t)64 << 20;
+static_assert(SVS_DIVERSE_MAX_FETCH == DV_MAX_FETCH, "the pick kernel's LDS arrays hold SVS_DIVERSE_MAX_FETCH candidates");
+
+int32_t svs_index_search_diverse(svs_index* idx, const float* queries, int32_t nq, int32_t d, int32_t k, int32_t fetch_k,
+                                 float lambda_mult, float* out_scores, int64_t* out_rows, float* out_redundancy, int32_t* out_count) {
+  launch_reset();
+  if (!idx) return fail(SVS_ERR_INVALID, "null index");
+  RefGuard guard(idx);
+  std::shared_lock<std::shared_mutex> geo(idx->rw);
+  // ---- everything is validated before anything is written or launched
+  int rc = check_query_args(idx, queries, nq, d);
+  if (rc != SVS_OK) return rc;
+  if (!(lambda_mult >= 0.f && lambda_mult <= 1.f))
+    return fail(SVS_ERR_INVALID, "svs_index_search_diverse: lambda_mult must lie in [0, 1], got %g", (double)lambda_mult);
+  if (k > 0 && fetch_k <= 0) return fail(SVS_ERR_INVALID, "svs_index_search_diverse: fetch_k must be >= 1, got %d", (int)fetch_k);
+  if (fetch_k > 0 && fetch_k < k)
+    return fail(SVS_ERR_INVALID, "svs_index_search_diverse: fetch_k (%d) is smaller than k (%d)", (int)fetch_k, (int)k);
+  if (fetch_k > SVS_DIVERSE_MAX_FETCH)
+    return fail(SVS_ERR_UNSUPPORTED, "svs_index_search_diverse: fetch_k %d; at most %d candidates are re-ranked", (int)fetch_k,
+                SVS_DIVERSE_MAX_FETCH);
+  const bool work = nq > 0 && k > 0;
+  if (work && (!out_scores || !out_rows || !out_count)) return fail(SVS_ERR_INVALID, "null output");
+  const int64_t live = idx->n - (int64_t)idx->dead_list.size();
+  const int c = (int)std::min<int64_t>(std::max(fetch_k, 0), live);   // candidates per query
+  const int count = std::min(std::max(k, 0), c);
+  if (out_count) *out_count = count;
+  if (!work || count == 0) return SVS_OK;
+  HostCall fr(idx);
+  if ((rc = fr.open()) != SVS_OK) return rc;
+  Ctx* const cx = fr.c;
+  // ---- candidates: the ordinary host search at fetch_k, left in the context's pinned block (stride c)
+  if ((rc = search_host_framed(idx, fr, queries, nq, d, c, c, nullptr, nullptr)) != SVS_OK) return rc;
+  if (count == 1) {   // (k == 1 or c == 1) the best candidate: nothing behind the search
+    for (int32_t q = 0; q < nq; ++q) {
+      out_scores[(size_t)q * k] = cx->out_s_pin[(size_t)q * c];
+      out_rows[(size_t)q * k] = cx->out_r_pin[(size_t)q * c];
+      if (out_redundancy) out_redundancy[(size_t)q * k] = -std::numeric_limits<float>::infinity();
+    }
+    return SVS_OK;
+  }
+  const size_t cc = (size_t)c * (size_t)c;
+  // (and at most 32,768 queries: a block's queries are the grid's y dimension)
+  const int qb = (int)std::max<size_t>(1, std::min<size_t>(std::min<size_t>((size_t)nq, 32768), DIVERSE_G_BUDGET / (cc * sizeof(float))));
+  const size_t on = (size_t)nq * (size_t)count;
+  if ((rc = cx->dv_G.grow((size_t)qb * cc)) != SVS_OK) return rc;
+  if ((rc = cx->dv_s_pin.grow(on)) != SVS_OK || (rc = cx->dv_r_pin.grow(on)) != SVS_OK || (rc = cx->dv_red_pin.grow(on)) != SVS_OK) return rc;
+  const hipStream_t st = fr.stream();
+  const int ld16 = (int)((size_t)idx->ld * elem_bytes(idx) / 16);
+  const int nt = (c + DV_TILE - 1) / DV_TILE;
+  const u32x4* M = (const u32x4*)idx->rows;
+  const float oml = 1.0f - lambda_mult;
+  // Block by block on the context's stream (the scratch is reused in stream order); one wait for the whole call
+  for (int q0 = 0; q0 < nq; q0 += qb) {
+    const int nb = std::min(qb, nq - q0);
+    // (the candidates stay in the pinned, device-visible block the search wrote them to: a workgroup of the Gram kernel
+    //  reads 128 row numbers over the bus, the pick kernel c scores and rows; copying them into HBM first measured the same)
+    const int64_t* cand_r = cx->out_r_pin + (size_t)q0 * c;
+    const float* cand_s = cx->out_s_pin + (size_t)q0 * c;
+    const dim3 grid((unsigned)(nt * (nt + 1) / 2), (unsigned)nb);
+    launch_record("diverse_gram_kernel", c, nb);
+    if (idx->dtype == SVS_DTYPE_F32)
+      hipLaunchKernelGGL(diverse_gram_kernel<0>, grid, dim3(DV_THREADS), 0, st, M, ld16, (const float*)nullptr, cand_r,
+                         c, idx->row_offset, idx->n, nt, cx->dv_G.p);
+    else if (idx->dtype == SVS_DTYPE_F16)
+      hipLaunchKernelGGL(diverse_gram_kernel<1>, grid, dim3(DV_THREADS), 0, st, M, ld16, (const float*)nullptr, cand_r,
+                         c, idx->row_offset, idx->n, nt, cx->dv_G.p);
+    else
+      hipLaunchKernelGGL(diverse_gram_kernel<2>, grid, dim3(DV_THREADS), 0, st, M, ld16, (const float*)idx->row_scales,
+                         cand_r, c, idx->row_offset, idx->n, nt, cx->dv_G.p);
+    launch_record("diverse_pick_kernel", c, nb);
+    hipLaunchKernelGGL(diverse_pick_kernel, dim3((unsigned)nb), dim3(DV_PICK_THREADS), 0, st, cand_s, cand_r,
+                       (const float*)cx->dv_G.p, c, count, lambda_mult, oml,
+                       cx->dv_s_pin + (size_t)q0 * count, cx->dv_r_pin + (size_t)q0 * count, cx->dv_red_pin + (size_t)q0 * count);
+  }
+  if ((rc = fr.close("search_diverse")) != SVS_OK) return rc;
+  for (int32_t q = 0; q < nq; ++q) {
+    memcpy(out_scores + (size_t)q * k, cx->dv_s_pin + (size_t)q * count, (size_t)count * sizeof(float));
+    memcpy(out_rows + (size_t)q * k, cx->dv_r_pin + (size_t)q * count, (size_t)count * sizeof(int64_t));
+    if (out_redundancy) memcpy(out_redundancy + (size_t)q * k, cx->dv_red_pin + (size_t)q * count, (size_t)count * sizeof(float));
   }
   return SVS_OK;
 }

@@ -22,6 +22,8 @@ from . import _native
 # "fp8" stores OCP e4m3 with one f32 scale per row -- configs[4].
 _DTYPES = {"f32": _native.DTYPE_F32, "f16": _native.DTYPE_F16, "fp8": _native.DTYPE_FP8}
 
+DIVERSE_MAX_FETCH = 1024   # SVS_DIVERSE_MAX_FETCH: the most candidates (and so results) of a diverse search
+
 
 class DeviceIndex:
     """One shard of a corpus, resident in the HBM of one MI355X.
@@ -371,6 +373,65 @@ class DeviceIndex:
             raise ValueError(f"query must be 1-D, got shape {q.shape}")
         s, r, total = self.search_batch_above(q[None, :], [min_score], limit)[0]
         return list(zip(s.astype(np.float64).tolist(), r.tolist())), total
+
+    @staticmethod
+    def diverse_fetch(n: int, fetch_k: Optional[int] = None) -> int:
+        """How many candidates a diverse search of ``n`` results re-ranks: ``fetch_k``, or by default
+        min(max(4 n, 32), DIVERSE_MAX_FETCH), raised to ``n`` where ``n`` is larger.  More than DIVERSE_MAX_FETCH
+        (results or candidates) is a ValueError."""
+        n = max(n, 0)
+        if n > DIVERSE_MAX_FETCH:
+            raise ValueError(f"a diverse search returns at most {DIVERSE_MAX_FETCH} rows, {n} were asked for")
+        if fetch_k is None:
+            return max(min(max(4 * n, 32), DIVERSE_MAX_FETCH), n)
+        assert isinstance(fetch_k, int)
+        if fetch_k > DIVERSE_MAX_FETCH:
+            raise ValueError(f"a diverse search re-ranks at most {DIVERSE_MAX_FETCH} candidates, fetch_k is {fetch_k}")
+        if n > 0 and fetch_k < n:
+            raise ValueError(f"fetch_k ({fetch_k}) is smaller than n ({n})")
+        return fetch_k
+
+    def search_batch_diverse(self, queries: np.ndarray, n: int, fetch_k: Optional[int] = None,
+                             lam: float = 0.5) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+        """Maximal-marginal-relevance re-ranking on the device (svs_index_search_diverse): for each row of ``queries``
+        (nq, D) the ``fetch_k`` best rows are the candidates (``diverse_fetch``: by default min(max(4 n, 32), 1024)), and
+        ``n`` of them are picked greedily by ``lam * score - (1 - lam) * (largest stored-row similarity to a row already
+        picked)``, starting from the best; an exact tie goes to the better-ranked candidate.  Returns
+        (scores f32 (nq, count), rows i64 (nq, count), redundancy f32 (nq, count)) in PICK order, count = min(max(n, 0),
+        fetch_k, live rows); redundancy is that largest similarity when the row was picked (-inf for the first).
+        ``lam=1`` is ``search_batch``; ``lam`` outside [0, 1] or NaN, and ``n`` or ``fetch_k`` above 1024, are
+        ValueErrors."""
+        assert isinstance(n, int)
+        q = self._queries_2d(queries)
+        nq, d = q.shape
+        lam = float(lam)
+        if not 0.0 <= lam <= 1.0:
+            raise ValueError(f"lam must lie in [0, 1], got {lam}")
+        fk = self.diverse_fetch(n, fetch_k)
+        h = self._pinned_handle()
+        try:
+            k = min(max(n, 0), max(fk, 0), self._live_rows(h))
+            scores = np.empty((nq, k), dtype=np.float32)
+            rows = np.empty((nq, k), dtype=np.int64)
+            red = np.empty((nq, k), dtype=np.float32)
+            count = C.c_int32(0)
+            # (the one call that releases the GIL)
+            _native.check(self._lib.svs_index_search_diverse(h, q.ctypes.data, nq, d, k, fk, lam, scores.ctypes.data,
+                                                             rows.ctypes.data, red.ctypes.data, C.byref(count)))
+        finally:
+            self._unpin(h)
+        c = count.value
+        return (scores, rows, red) if c == k else (scores[:, :c], rows[:, :c], red[:, :c])
+
+    def search_diverse(self, query_vec: np.ndarray, n: int, fetch_k: Optional[int] = None,
+                       lam: float = 0.5) -> List[Tuple[float, int, float]]:
+        """``search`` re-ranked for diversity (see ``search_batch_diverse``): [(score, row, redundancy)] in pick order."""
+        assert isinstance(n, int)
+        q = np.asarray(query_vec, dtype=np.float32)
+        if q.ndim != 1:
+            raise ValueError(f"query must be 1-D, got shape {q.shape}")
+        s, r, red = self.search_batch_diverse(q[None, :], n, fetch_k, lam)
+        return list(zip(s[0].astype(np.float64).tolist(), r[0].tolist(), red[0].astype(np.float64).tolist()))
 
     def neighbors(self, rows, n: int) -> Tuple[np.ndarray, np.ndarray]:
         """The ``n`` nearest stored rows of each listed stored row (GLOBAL indices, any order, repeats allowed), the

@@ -30,7 +30,7 @@ from typing import Any, Awaitable, Callable, Dict, Iterator, List, Optional, Tup
 import numpy as np
 
 from .index import DeviceIndex
-from .matrix import DeviceEmbeddingsMatrix, above_op, batch_op, neighbors_op, pairs_op, segments_op, single_op, within_op
+from .matrix import DeviceEmbeddingsMatrix, above_op, batch_op, diverse_op, neighbors_op, pairs_op, segments_op, single_op, within_op
 
 _LOG = logging.getLogger(__name__)
 
@@ -346,6 +346,22 @@ def _fetch_lists(db: _Store, per_list: List[List[Tuple[float, int]]]) -> List[Li
     return [_fetch_list(db, emb_ids) for emb_ids in per_list]
 
 
+def _fetch_diverse(db: _Store, picks: List[Tuple[float, int, float]]) -> List[Dict[str, Any]]:
+    """[(score, emb id, redundancy)] in pick order -> ``Retrieval`` list with a 'redundancy' key, the docs fetched with
+    one SQL statement; call it in a transaction."""
+    docs = db.fetch_docs_for_embeddings([e for _, e, _ in picks])
+    return [{"score": s, "doc": docs[e], "redundancy": r} for s, e, r in picks]
+
+
+def _diverse_args(n: int, fetch_n: Optional[int], diversity: float) -> Tuple[int, float]:
+    """(candidates to fetch, lambda_mult = 1 - diversity) of a diverse retrieval; ValueError for a diversity outside
+    [0, 1] or NaN, more than 1024 results or candidates, or fewer candidates than results."""
+    diversity = float(diversity)
+    if not 0.0 <= diversity <= 1.0:
+        raise ValueError(f"diversity must lie in [0, 1], got {diversity}")
+    return DeviceIndex.diverse_fetch(n, fetch_n), 1.0 - diversity
+
+
 class KB:
     """Sync knowledge base, retrieve() path only.  Mirrors reference
     src/svs/kb.py:1407-1640."""
@@ -504,6 +520,26 @@ class KB:
             res = _fetch_list(self.db, emb_ids)
         _LOG.info(f"retrieved top {n} documents")
         return res, total
+
+    def retrieve_diverse(self, query: str, n: int, fetch_n: Optional[int] = None, diversity: float = 0.5) -> List[Dict[str, Any]]:
+        """``retrieve`` without the near-copies: the ``fetch_n`` best documents (default min(max(4 n, 32), 1024)) are
+        re-ranked on the device by maximal marginal relevance (svs_index_search_diverse) -- greedily, by
+        ``(1 - diversity) * score - diversity * (largest similarity to a document already picked)`` -- and ``n`` of
+        them come back in PICK order, shaped like ``retrieve`` with a 'redundancy' key (that largest similarity when the
+        document was picked; -inf for the first).  ``diversity=0`` is ``retrieve``.  ValueError for a diversity outside
+        [0, 1], for ``n`` or ``fetch_n`` above 1024, and for ``fetch_n < n``."""
+        fetch_k, lam = _diverse_args(n, fetch_n, diversity)
+        _LOG.info(f"retrieving {n} documents with query string: {query}")
+        assert self.db is not None
+        self.embeddings_matrix.get_sync(self.db)
+        query_vec = np.array(self._embed([query])[0], dtype=np.float32)
+        _LOG.info("got embedding for query!")
+        picks = self.embeddings_matrix.search_diverse(query_vec, n, fetch_k, lam)   # HIP
+        _LOG.info(f"computed {self.embeddings_matrix.index.shape[0]} cosine similarities")
+        with self.db.transaction():
+            res = _fetch_diverse(self.db, picks)
+        _LOG.info(f"retrieved top {n} documents")
+        return res
 
     def retrieve_similar(self, doc_id: int, n: int) -> List[Dict[str, Any]]:
         """"More like this": the n documents nearest to the STORED document ``doc_id``, itself excluded, shaped like
@@ -808,6 +844,21 @@ class AsyncKB:
         res = await self._fetch(lambda db: _fetch_list(db, emb_ids))
         _LOG.info(f"retrieved top {n} documents")
         return res, total
+
+    async def retrieve_diverse(self, query: str, n: int, fetch_n: Optional[int] = None,
+                               diversity: float = 0.5) -> List[Dict[str, Any]]:
+        """Async twin of ``KB.retrieve_diverse``, structured as ``retrieve``: the reference to the matrix under the
+        lock, the diverse search on an executor thread outside it, the docs under the lock."""
+        fetch_k, lam = _diverse_args(n, fetch_n, diversity)
+        _LOG.info(f"retrieving {n} documents with query string: {query}")
+        async with self._held() as (held, _):
+            query_vec = np.array((await self._embed([query]))[0], dtype=np.float32)
+            _LOG.info("got embedding for query!")
+            picks = await self._search(held, diverse_op(query_vec, n, fetch_k, lam))
+            _LOG.info(f"computed {held[0].shape[0]} cosine similarities")
+        res = await self._fetch(lambda db: _fetch_diverse(db, picks))
+        _LOG.info(f"retrieved top {n} documents")
+        return res
 
     async def retrieve_many(self, queries: List[str], n: int) -> List[List[Dict[str, Any]]]:
         """Async twin of ``KB.retrieve_many``.  Same structure as

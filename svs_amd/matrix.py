@@ -185,6 +185,20 @@ def above_op(query_vec: np.ndarray, min_score: float, n: int):
     return native, finish
 
 
+def diverse_op(query_vec: np.ndarray, n: int, fetch_k: Optional[int] = None, lam: float = 0.5):
+    """Diverse (MMR) search: ``idx.search_diverse`` (svs_index_search_diverse), rows -> ids:
+    [(score, emb_id, redundancy)] in pick order."""
+    def native(idx, lookup, *_):
+        return idx, idx.search_diverse(query_vec, n, fetch_k, lam)
+
+    def finish(res, arr):
+        used, rows = res
+        off = int(getattr(used, "row_offset", 0))
+        return [(score, int(arr[row - off]), red) for score, row, red in rows]
+
+    return native, finish
+
+
 def ids_of_rows(res, arr: np.ndarray) -> List[Tuple[float, int]]:
     return [(score, int(arr[row])) for score, row in res]
 
@@ -444,6 +458,12 @@ class DeviceEmbeddingsMatrix:
         """Every stored embedding scoring at or above ``min_score``, best first, at most ``n``:
         ([(score, emb_id)], total qualifying) (``KB.retrieve_above``)."""
         return self.run_mapped(above_op(query_vec, min_score, n))
+
+    def search_diverse(self, query_vec: np.ndarray, n: int, fetch_k: Optional[int] = None,
+                       lam: float = 0.5) -> List[Tuple[float, int, float]]:
+        """``search`` re-ranked for diversity (MMR over the ``fetch_k`` best, on the device):
+        [(score, emb_id, redundancy)] in pick order (``KB.retrieve_diverse``)."""
+        return self.run_mapped(diverse_op(query_vec, n, fetch_k, lam))
 
     def search_within_many(self, query_vecs: np.ndarray, n: int, emb_id_lists, seg_query=None) -> List[List[Tuple[float, int]]]:
         """``search_within`` for many id lists in one call: list s against query ``seg_query[s]`` of ``query_vecs``

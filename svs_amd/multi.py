@@ -209,6 +209,11 @@ class MultiDeviceIndex:
     def search_above(self, query_vec: np.ndarray, min_score: float, limit: int):
         raise NotImplementedError("threshold search is per device: call search_above on a DeviceIndex (a shard's totals and lists are its own)")
 
+    def search_diverse(self, query_vec: np.ndarray, n: int, fetch_k: Optional[int] = None, lam: float = 0.5):
+        raise NotImplementedError("diverse search is per device: the candidates' rows must sit in one HBM; call search_diverse on a DeviceIndex")
+
+    search_batch_diverse = search_diverse
+
     def top_pairs(self, n: int):
         raise NotImplementedError("pairwise scores need the whole corpus on one device; build a DeviceIndex for it")
 
