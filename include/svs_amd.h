@@ -304,6 +304,56 @@ int32_t svs_index_search_segments(svs_index* idx, const float* queries, int32_t 
                                   const int32_t* seg_query /* nseg, or NULL */, int32_t nseg,
                                   float* out_scores, int64_t* out_rows, int32_t* out_counts /* nseg */);
 
+/* ---- labels: one uint32_t per row, kept next to the vectors in HBM, and the search that names them -- "one level of
+ *      the document tree", "one tenant", "one source" -- for which a row list (svs_index_search_rows) is the wrong
+ *      tool: at 1M rows the list's SQL, validation and upload cost more than the search.
+ * The column.  HBM only (no host mirror), one label per row of the index's row CAPACITY, counted in hbm_bytes.  A row
+ * that was never labelled carries label 0, and an index on which svs_index_set_labels was never called behaves as if
+ * every label were 0 and owns no column.  The first svs_index_set_labels (with nrows > 0) allocates it, zero-filled;
+ * svs_index_reserve, svs_index_append* and svs_index_staging_commit carry it along when the buffers grow, and new
+ * rows get label 0; svs_index_mask_rows does not touch it; svs_index_compact moves it with the rows (new row p carries
+ * the label of the row it was) -- the compacted column is built in a fresh buffer BEFORE the first row moves, so no
+ * memory for it is SVS_ERR_NOMEM with the handle untouched, like the bounce buffer.
+ *   set: labels[0 .. nrows) become the labels of GLOBAL rows [row0, row0 + nrows); tombstoned rows may be labelled.
+ *        Holds a reference and the geometry lock exclusively, like svs_index_mask_rows: it waits for what it would
+ *        disturb, and a search never sees half of one call's range.
+ *   get: reads the DEVICE copy of those rows' labels back (zeros when the index has no column); tombstoned rows too.
+ * Both: nrows < 0, or a range that is not inside [row_offset, row_offset + n) -> SVS_ERR_INVALID; null labels / out
+ * with nrows > 0 -> SVS_ERR_INVALID; nrows == 0 -> SVS_OK, nothing allocated, nothing read.
+ *
+ * Labelled search.  Exact definition: let S = { live local rows r : label[r] in set(labels) }, ascending.  The call
+ * writes what
+ *   svs_index_search_rows(idx, queries, nq, d, k, S + row_offset, |S|, ...)
+ * writes: the same rows, the same order (score desc, row desc), the same score bits, the same *out_count =
+ * min(max(k, 0), |S|); entries past the count are not touched.  *out_matched (may be NULL) = |S|; *out_count (may be
+ * NULL) and *out_matched are written by every successful call.  A query's result does not depend on nq.
+ *   labels    any order, repeats allowed: sorted and deduplicated on the host.  nlabels == 0 is the empty set: SVS_OK,
+ *             count 0, matched 0, nothing launched.
+ *   COUNT-ONLY call: with out_matched != NULL and (k <= 0 or nq == 0) only the counting launch runs; out_scores /
+ *             out_rows may be NULL.  With out_matched == NULL and (k <= 0 or nq == 0): SVS_OK, nothing launched.
+ * Errors: everything is validated before anything is launched, and a failing call writes no output.  d != index d or
+ * an empty index -> SVS_ERR_SHAPE, as svs_index_search_rows.  SVS_ERR_INVALID: nq < 0, nlabels < 0, null labels with
+ * nlabels > 0, null queries with nq > 0, null out_scores / out_rows with work to do (nq > 0, k > 0 and a set that is
+ * not empty).  More than SVS_LABELS_MAX_SET DISTINCT labels -> SVS_ERR_UNSUPPORTED (repeats do not count).  Rows of
+ * more than 16 KiB with work to do -> SVS_ERR_UNSUPPORTED, the gather kernels' limit.
+ * Cost: the filter runs on the device -- a counting pass over the column (4 bytes per row; the set in LDS, a set of
+ * one label a plain compare), ONE host wait for |S|, then a one-workgroup scan and a writing pass that emit S in
+ * ascending order; then svs_index_search_rows' own score and top-k kernels over that device list (always the list
+ * route, whatever the share of rows that match), and the result positions are mapped to rows on the device.  No
+ * list is built, checked, sorted or uploaded on the host.
+ * Blocking; re-entrant on one handle; holds a reference and the geometry lock shared; waits for pending staging
+ * copies; never goes through the coalescer, the run-ahead pipelines or shared passes: all as svs_index_search_rows.
+ * Out of scope: svs_multi / row-sharded corpora, a device-pointer variant, per-query label sets in one call,
+ * predicates richer than set membership (ranges, bit masks), and routing very broad sets through a full-corpus pass
+ * instead of the list route. */
+#define SVS_LABELS_MAX_SET 1024
+int32_t svs_index_set_labels(svs_index* idx, int64_t row0 /* GLOBAL */, int64_t nrows, const uint32_t* labels);
+int32_t svs_index_get_labels(svs_index* idx, int64_t row0 /* GLOBAL */, int64_t nrows, uint32_t* out);
+int32_t svs_index_search_labeled(svs_index* idx, const float* queries, int32_t nq, int32_t d, int32_t k,
+                                 const uint32_t* labels, int32_t nlabels,
+                                 float* out_scores, int64_t* out_rows /* stride k */,
+                                 int32_t* out_count, int64_t* out_matched /* or NULL */);
+
 /* Threshold search: every live row that scores at or above a cut-off, best first, and how many there are -- "all
  * documents with cosine >= 0.8", "how many would qualify", "drop the weak tail by score, not by rank" -- without
  * guessing a k and without pulling the score vector to the host.

@@ -85,6 +85,10 @@ SIGNATURES = {
     "svs_index_scores_n": (C.c_int32, [_P, _P, C.c_int32, _P, C.c_int64, C.POINTER(C.c_int64)]),
     "svs_index_search_rows": (C.c_int32, [_P, _P, C.c_int32, C.c_int32, C.c_int32, _P, C.c_int64, _P, _P, C.POINTER(C.c_int32)]),
     "svs_index_search_segments": (C.c_int32, [_P, _P, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P, C.c_int32, _P, _P, _P]),
+    "svs_index_set_labels": (C.c_int32, [_P, C.c_int64, C.c_int64, _P]),
+    "svs_index_get_labels": (C.c_int32, [_P, C.c_int64, C.c_int64, _P]),
+    "svs_index_search_labeled": (C.c_int32, [_P, _P, C.c_int32, C.c_int32, C.c_int32, _P, C.c_int32, _P, _P, C.POINTER(C.c_int32),
+                                             C.POINTER(C.c_int64)]),
     "svs_index_search_above": (C.c_int32, [_P, _P, C.c_int32, C.c_int32, _P, C.c_int32, _P, _P, _P, _P]),
     "svs_index_search_diverse": (C.c_int32, [_P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_float, _P, _P, _P,
                                              C.POINTER(C.c_int32)]),
@@ -118,6 +122,7 @@ INTERNAL = {
     "svs_internal_compact_plan": (C.c_int64, [_P, C.c_int64, C.c_int64, C.c_int64, _P, C.c_int64]),
     "svs_internal_segments_plan": (C.c_int64, [_P, _P, C.c_int64, C.c_int32, _P, C.c_int64, _P, C.POINTER(C.c_int64)]),
     "svs_internal_live_rows": (C.c_int64, [_P, C.c_int64, C.c_int64, C.c_int64, _P, _P, C.c_int64]),
+    "svs_internal_labels_strip": (C.c_int32, []),
     "svs_internal_compact": (C.c_int32, [_P, C.c_int64, _P, C.c_int64, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
 }
 

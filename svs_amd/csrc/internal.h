@@ -125,6 +125,9 @@ int64_t svs_internal_segments_plan(const int64_t* sizes, const int32_t* seg_quer
  * ascending; cap = the room in out, at least nrows.  Returns m, or SVS_ERR_INVALID with out untouched. */
 int64_t svs_internal_live_rows(const int64_t* rows, int64_t nrows, int64_t row_offset, int64_t n, const uint8_t* dead_flags, uint32_t* out,
                                int64_t cap);
+/* Rows per workgroup strip of the label filter (labels.h, LB_STRIP): the sizes at which svs_index_search_labeled's
+ * kernels change what they do (tests). */
+int32_t svs_internal_labels_strip(void);
 /* multi.hip -> svs_amd.hip: carries a worker thread's error message over to the caller's thread */
 int32_t svs_internal_set_error(int32_t code, const char* msg);
 #ifdef __cplusplus

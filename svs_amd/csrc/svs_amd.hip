@@ -41,6 +41,7 @@
 #include "segments.h"
 #include "above.h"
 #include "diverse.h"
+#include "labels.h"
 
 namespace {
 
@@ -246,6 +247,12 @@ struct Ctx {
   // and the call's picks; the candidates are read where the search left them, in out_s_pin / out_r_pin
   DevBuf<float> dv_G;
   PinBuf<float> dv_s_pin;       PinBuf<int64_t> dv_r_pin;     PinBuf<float> dv_red_pin;
+  // svs_index_search_labeled (labels.h): the sorted set (pinned copy, device copy); the call's total (one u64) followed
+  // by the per-strip counts, which the scan turns into the strips' bases; the total's pinned copy; and the list
+  // positions the top-k stage writes, mapped to rows on the device.  The list itself is list_dev.
+  PinBuf<uint32_t> lab_set_pin; DevBuf<uint32_t> lab_set_dev;
+  DevBuf<uint32_t> lab_cnt;     PinBuf<unsigned long long> lab_tot_pin;
+  DevBuf<int64_t> lab_pos;
   // Scratch is reused in stream order.  A context stays with the stream that
   // last used it; handing it to ANOTHER stream first drains the old one.
   hipStream_t last_stream = nullptr;
@@ -320,6 +327,11 @@ struct svs_index {
   void* rows = nullptr;
   float* row_scales = nullptr;   // fp8 only: one f32 per row
   size_t bytes = 0;
+  // svs_index_set_labels: one u32 per row of the CAPACITY (rounded up to 4: the kernels load 16 bytes), HBM only; null
+  // until the first call -- every label is then 0.  Invariant: the labels of the rows from n on are 0, so that rows
+  // appended later carry label 0 without a write.  Written under the exclusive geometry lock, read under the shared one.
+  uint32_t* labels = nullptr;
+  size_t labels_bytes = 0;
   // Corpus geometry lock: searches hold it shared while they enqueue (and, for the
   // host API, until their results are back); append / mask_rows take it exclusive.
   std::shared_mutex rw;
@@ -464,6 +476,7 @@ void index_destroy(svs_index* idx) {
   for (auto& t : idx->evs) ev_destroy(t);
   (void)hipFree(idx->rows);
   (void)hipFree(idx->row_scales);
+  (void)hipFree(idx->labels);
   (void)hipFree(idx->pfx_rows);
   (void)hipFree(idx->pfx_scales);
   (void)hipFree(idx->shadow);
@@ -2097,6 +2110,30 @@ int sync_dead_bits(svs_index* idx) {
   return SVS_OK;
 }
 
+// ---- the label column and its ordered filter (labels.h) ------------------------------------------------------------
+static_assert(SVS_LABELS_MAX_SET == LB_MAX_SET, "the filter kernels' LDS image of the set holds SVS_LABELS_MAX_SET labels");
+constexpr size_t label_column_bytes(int64_t rows_cap) { return (size_t)((rows_cap + 3) & ~(int64_t)3) * sizeof(uint32_t); }
+inline int64_t label_strips(int64_t n) { return (n + LB_STRIP - 1) / LB_STRIP; }
+
+// The filter over the rows [0, n) the index holds: set[0 .. nset) sorted and distinct on the HOST, set_dev its device
+// copy (read when nset >= 2 only); nset == 0: every live row
+LabelFilter label_filter(const svs_index* idx, const uint32_t* set, int nset, const uint32_t* set_dev) {
+  return LabelFilter{idx->labels, idx->n, idx->dead_list.empty() ? nullptr : idx->dead_bits_dev.p, set_dev, nset, nset == 1 ? set[0] : 0u};
+}
+
+// cnt: one u64 (the total, zeroed here) followed by one u32 per strip of f.n rows
+void launch_label_count(const LabelFilter& f, uint32_t* cnt, hipStream_t st) {
+  (void)hipMemsetAsync(cnt, 0, sizeof(unsigned long long), st);
+  hipLaunchKernelGGL(label_count_kernel, dim3((unsigned)label_strips(f.n)), dim3(LB_THREADS), 0, st, f, cnt + 2, (unsigned long long*)cnt);
+}
+
+// ... and behind it: the counts scanned into the strips' bases, then the m matches written to out in ascending row order
+template <int PAYLOAD>
+void launch_label_write(const LabelFilter& f, uint32_t* cnt, uint32_t* out, int64_t m, hipStream_t st) {
+  hipLaunchKernelGGL(label_scan_kernel, dim3(1), dim3(LB_THREADS), 0, st, cnt + 2, label_strips(f.n));
+  hipLaunchKernelGGL((label_write_kernel<PAYLOAD>), dim3((unsigned)label_strips(f.n)), dim3(LB_THREADS), 0, st, f, (const uint32_t*)(cnt + 2), out, m);
+}
+
 // Makes room for `rows` rows (caller holds the geometry lock exclusively).  exact == false grows
 // by 1.5x (amortised appends); exact == true (svs_index_reserve) allocates just `rows`.
 int ensure_capacity(svs_index* idx, int64_t rows, bool exact) {
@@ -2114,21 +2151,35 @@ int ensure_capacity(svs_index* idx, int64_t rows, bool exact) {
       return fail(SVS_ERR_NOMEM, "hipMalloc(row scales): %s", hipGetErrorString(e));
     }
   }
+  uint32_t* nlabels = nullptr;   // the label column grows with the rows: the old labels, then zeros
+  if (idx->labels) {
+    hipError_t e = hipMalloc((void**)&nlabels, label_column_bytes(new_cap));
+    if (e != hipSuccess) {
+      (void)hipFree(nrows);
+      (void)hipFree(nscales);
+      return fail(SVS_ERR_NOMEM, "hipMalloc(labels): %s", hipGetErrorString(e));
+    }
+  }
   // (the new buffers are the caller's problem only once they are installed: every failure until then frees them)
   struct Fresh {
-    void* rows; float* scales; bool keep = false;
-    ~Fresh() { if (!keep) { (void)hipFree(rows); (void)hipFree(scales); } }
-  } fresh{nrows, nscales};
+    void* rows; float* scales; uint32_t* labels; bool keep = false;
+    ~Fresh() { if (!keep) { (void)hipFree(rows); (void)hipFree(scales); (void)hipFree(labels); } }
+  } fresh{nrows, nscales, nlabels};
   // work already enqueued by the device API may still read the old buffers
   HIP_TRY(hipDeviceSynchronize());
   const int64_t n_old = idx->n;
   if (n_old) HIP_TRY(hipMemcpy(nrows, idx->rows, (size_t)n_old * row_b, hipMemcpyDeviceToDevice));
   if (n_old && nscales) HIP_TRY(hipMemcpy(nscales, idx->row_scales, (size_t)n_old * sizeof(float), hipMemcpyDeviceToDevice));
+  if (nlabels) HIP_TRY(hipMemset(nlabels, 0, label_column_bytes(new_cap)));
+  if (n_old && nlabels) HIP_TRY(hipMemcpy(nlabels, idx->labels, (size_t)n_old * sizeof(uint32_t), hipMemcpyDeviceToDevice));
   fresh.keep = true;
   (void)hipFree(idx->rows);
   (void)hipFree(idx->row_scales);
+  (void)hipFree(idx->labels);
   idx->rows = nrows;
   idx->row_scales = nscales;
+  idx->labels = nlabels;
+  idx->labels_bytes = nlabels ? label_column_bytes(new_cap) : 0;
   if (idx->shadow) {   // grows with the rows; if there is no room for it the index carries on without
     void* nsh = nullptr;
     bool ok = shadow_alloc(idx, new_cap, &nsh);
@@ -2316,11 +2367,26 @@ int compact_index(svs_index* idx, int64_t bounce_rows, int64_t* out_old_rows, in
     HIP_TRY(tmp.alloc(&dead_sorted, (size_t)ndead * sizeof(uint32_t)));
     HIP_TRY(hipMemcpy(dead_sorted, dead.data(), (size_t)ndead * sizeof(uint32_t), hipMemcpyHostToDevice));
   }
+  // The label column moves with the rows, OUT OF PLACE: the fresh column (and the filter's counts) are allocated here,
+  // before the first row moves -- SVS_ERR_NOMEM leaves the handle untouched -- and swapped in after the rows' move
+  uint32_t *lab_new = nullptr, *lab_cnt = nullptr;
+  if (idx->labels) {
+    HIP_TRY(tmp.alloc(&lab_new, label_column_bytes(idx->cap)));
+    HIP_TRY(tmp.alloc(&lab_cnt, (size_t)(label_strips(n) + 2) * sizeof(uint32_t)));
+  }
   // work enqueued by the device entries may still read the rows; the pipelines start their rings over
   HIP_TRY(hipDeviceSynchronize());
   for (AheadPipe* p : idx->pipes) {
     std::lock_guard<std::mutex> lk(p->mu);
     HIP_TRY(pipe_drain(p));
+  }
+  if (lab_new) {
+    // the ordered stream compaction of the label VALUES under "row is live" (the empty set): new row p gets the label
+    // of the p-th live row; the tail stays zero
+    HIP_TRY(hipMemsetAsync(lab_new, 0, label_column_bytes(idx->cap), nullptr));
+    const LabelFilter f = label_filter(idx, nullptr, 0, nullptr);
+    launch_label_count(f, lab_cnt, nullptr);
+    launch_label_write<LB_VALUES>(f, lab_cnt, lab_new, n_live, nullptr);
   }
   const CompactBufs corpus{(uint4*)idx->rows, idx->row_scales, (uint4*)idx->shadow};
   CompactBufs bnc{};   // rows, then shadow rows, then scales: every part starts on a 16-byte boundary
@@ -2347,6 +2413,11 @@ int compact_index(svs_index* idx, int64_t bounce_rows, int64_t* out_old_rows, in
   if (e != hipSuccess)
     return fail(SVS_ERR_DEVICE, "svs_index_compact: %s while rows were moving; the handle is only good for svs_index_release",
                 hipGetErrorString(e));
+  if (lab_new) {   // (the rows have moved: the compacted column takes the old one's place)
+    tmp.p.erase(std::find(tmp.p.begin(), tmp.p.end(), (void*)lab_new));
+    (void)hipFree(idx->labels);
+    idx->labels = lab_new;
+  }
   if (out_old_rows) {   // (branch-free: the slot is overwritten until a live row keeps it; the last live row is the last write inside the map)
     int64_t p = 0;
     for (int64_t r = 0; r < n && p < n_live; ++r) {
@@ -2716,7 +2787,7 @@ int32_t svs_index_info(const svs_index* idx, svs_index_info_t* out) {
   out->dtype = idx->dtype;
   out->device = idx->device;
   out->row_offset = idx->row_offset;
-  out->hbm_bytes = (int64_t)(idx->bytes + idx->shadow_bytes);
+  out->hbm_bytes = (int64_t)(idx->bytes + idx->shadow_bytes + idx->labels_bytes);
   out->n_masked = (int64_t)idx->dead_list.size();
   return SVS_OK;
 }
@@ -3191,6 +3262,158 @@ int32_t svs_index_search_rows(svs_index* idx, const float* queries, int32_t nq, 
   if ((rc = fr.close("search_rows")) != SVS_OK) return rc;
   if ((rc = list_positions_to_rows(c->out_r_pin, on, S, m, lo, -1)) != SVS_OK) return rc;
   deliver_results(c, nq, count, k, out_scores, out_rows);
+  return SVS_OK;
+}
+
+// The local range of a caller's [row0, row0 + nrows) of GLOBAL rows (svs_index_set_labels / _get_labels); nrows > 0
+static int label_range(const svs_index* idx, const char* entry, int64_t row0, int64_t nrows, int64_t* r0) {
+  *r0 = row0 - idx->row_offset;
+  if (*r0 < 0 || *r0 > idx->n || nrows > idx->n - *r0)
+    return fail(SVS_ERR_INVALID, "%s: rows [%lld, %lld) outside [%lld, %lld)", entry, (long long)row0, (long long)(row0 + nrows),
+                (long long)idx->row_offset, (long long)(idx->row_offset + idx->n));
+  return SVS_OK;
+}
+
+int32_t svs_index_set_labels(svs_index* idx, int64_t row0, int64_t nrows, const uint32_t* labels) {
+  if (!idx) return fail(SVS_ERR_INVALID, "null index");
+  RefGuard guard(idx);
+  std::unique_lock<std::shared_mutex> geo(idx->rw);   // no labelled search is between its count and its write
+  if (nrows < 0) return fail(SVS_ERR_INVALID, "nrows must be >= 0");
+  if (nrows == 0) return SVS_OK;
+  int64_t r0;
+  int rc = label_range(idx, "svs_index_set_labels", row0, nrows, &r0);
+  if (rc != SVS_OK) return rc;
+  if (!labels) return fail(SVS_ERR_INVALID, "null labels");
+  HIP_TRY(hipSetDevice(idx->device));
+  if (!idx->labels) {   // the first call: a zero column for the row CAPACITY
+    const size_t bytes = label_column_bytes(std::max(idx->cap, idx->n));
+    uint32_t* col = nullptr;
+    HIP_TRY(hipMalloc((void**)&col, bytes));
+    const hipError_t e = hipMemset(col, 0, bytes);
+    if (e != hipSuccess) {
+      (void)hipFree(col);
+      return fail(SVS_ERR_DEVICE, "svs_index_set_labels: %s", hipGetErrorString(e));
+    }
+    idx->labels = col;
+    idx->labels_bytes = bytes;
+  }
+  // (only svs_index_search_labeled and svs_index_get_labels read the column, blocking and under the shared lock: nothing
+  //  enqueued can be reading it now)
+  HIP_TRY(hipMemcpy(idx->labels + r0, labels, (size_t)nrows * sizeof(uint32_t), hipMemcpyHostToDevice));
+  return SVS_OK;
+}
+
+int32_t svs_index_get_labels(svs_index* idx, int64_t row0, int64_t nrows, uint32_t* out) {
+  if (!idx) return fail(SVS_ERR_INVALID, "null index");
+  RefGuard guard(idx);
+  std::shared_lock<std::shared_mutex> geo(idx->rw);
+  if (nrows < 0) return fail(SVS_ERR_INVALID, "nrows must be >= 0");
+  if (nrows == 0) return SVS_OK;
+  int64_t r0;
+  int rc = label_range(idx, "svs_index_get_labels", row0, nrows, &r0);
+  if (rc != SVS_OK) return rc;
+  if (!out) return fail(SVS_ERR_INVALID, "null output");
+  if (!idx->labels) {
+    memset(out, 0, (size_t)nrows * sizeof(uint32_t));
+    return SVS_OK;
+  }
+  HIP_TRY(hipSetDevice(idx->device));
+  HIP_TRY(hipMemcpy(out, idx->labels + r0, (size_t)nrows * sizeof(uint32_t), hipMemcpyDeviceToHost));
+  return SVS_OK;
+}
+
+int32_t svs_internal_labels_strip(void) { return LB_STRIP; }
+
+int32_t svs_index_search_labeled(svs_index* idx, const float* queries, int32_t nq, int32_t d, int32_t k, const uint32_t* labels,
+                                 int32_t nlabels, float* out_scores, int64_t* out_rows, int32_t* out_count, int64_t* out_matched) {
+  launch_reset();
+  if (!idx) return fail(SVS_ERR_INVALID, "null index");
+  RefGuard guard(idx);
+  std::shared_lock<std::shared_mutex> geo(idx->rw);   // (set_labels, mask_rows, compact take it exclusively: the count and the write see one column)
+  int rc = check_query_args(idx, queries, nq, d);
+  if (rc != SVS_OK) return rc;
+  if (nlabels < 0) return fail(SVS_ERR_INVALID, "nlabels must be >= 0");
+  if (nlabels > 0 && !labels) return fail(SVS_ERR_INVALID, "null labels");
+  // the set: sorted, without repeats
+  std::vector<uint32_t> set;
+  try {
+    set.assign(labels, labels + nlabels);
+  } catch (const std::bad_alloc&) {
+    return fail(SVS_ERR_NOMEM, "out of host memory for %d labels", (int)nlabels);
+  }
+  std::sort(set.begin(), set.end());
+  set.erase(std::unique(set.begin(), set.end()), set.end());
+  if (set.size() > (size_t)SVS_LABELS_MAX_SET)
+    return fail(SVS_ERR_UNSUPPORTED, "svs_index_search_labeled: %zu distinct labels; a set holds at most %d", set.size(), SVS_LABELS_MAX_SET);
+  const int nset = (int)set.size();
+  const bool ranks = nq > 0 && k > 0 && nset > 0;   // results are wanted, if a row matches
+  if (ranks && (!out_scores || !out_rows)) return fail(SVS_ERR_INVALID, "null output");
+  if (ranks && gather_rows_per_wave(idx) == 0)
+    return fail(SVS_ERR_UNSUPPORTED, "svs_index_search_labeled: rows of %zu bytes; the gather kernels take rows of up to 16 KiB",
+                (size_t)idx->ld * elem_bytes(idx));
+  if (nset == 0 || (!ranks && !out_matched)) {   // the empty set, or nothing to rank and nobody to tell the count
+    if (out_count) *out_count = 0;
+    if (out_matched) *out_matched = 0;
+    return SVS_OK;
+  }
+  HostCall fr(idx);
+  if ((rc = fr.open()) != SVS_OK) return rc;
+  Ctx* const c = fr.c;
+  const int64_t n = idx->n, lo = idx->row_offset;
+  if ((rc = c->lab_cnt.grow((size_t)label_strips(n) + 2)) != SVS_OK || (rc = c->lab_tot_pin.grow(1)) != SVS_OK) return rc;
+  if (nset > 1 && ((rc = c->lab_set_pin.grow((size_t)nset)) != SVS_OK || (rc = c->lab_set_dev.grow((size_t)nset)) != SVS_OK)) return rc;
+  // 1. the set goes up, the count runs; the host needs m = |S| to size the list, the score matrix and the select route
+  hipStream_t st = fr.stream();
+  if (nset > 1) {
+    memcpy(c->lab_set_pin, set.data(), (size_t)nset * sizeof(uint32_t));
+    HIP_TRY(hipMemcpyAsync(c->lab_set_dev, c->lab_set_pin, (size_t)nset * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+  }
+  const LabelFilter f = label_filter(idx, set.data(), nset, c->lab_set_dev);
+  launch_record("label_count_kernel", n, nset);
+  launch_label_count(f, c->lab_cnt, st);
+  HIP_TRY(hipMemcpyAsync(c->lab_tot_pin, c->lab_cnt, sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
+  if ((rc = fr.close("search_labeled")) != SVS_OK) return rc;
+  const int64_t m = (int64_t)c->lab_tot_pin[0];
+  if (m < 0 || m > n) return fail(SVS_ERR_DEVICE, "search_labeled: the filter counted %lld of %lld rows", (long long)m, (long long)n);
+  const int count = ranks ? (int)std::min<int64_t>(k, m) : 0;
+  if (count == 0) {
+    if (out_count) *out_count = 0;
+    if (out_matched) *out_matched = m;
+    return SVS_OK;
+  }
+  // 2. the list is written on the device; from here on the call is svs_index_search_rows over it
+  const size_t qn = (size_t)nq * (size_t)d, on = (size_t)nq * (size_t)count;
+  if ((rc = c->list_dev.grow((size_t)m)) != SVS_OK || (rc = c->lab_pos.grow(on)) != SVS_OK) return rc;
+  if ((rc = c->out_s_pin.grow(on)) != SVS_OK || (rc = c->out_r_pin.grow(on)) != SVS_OK) return rc;
+  st = fr.stream();
+  if ((rc = upload_queries(c, queries, qn, st)) != SVS_OK) return rc;
+  launch_record("label_write_kernel", n, nset);
+  launch_label_write<LB_ROWS>(f, c->lab_cnt, c->list_dev, m, st);
+  // Query chunks whose score matrix (and, for k > SEL_KMAX over more than SORT_CAP rows, sort keys) stays <= 2 GiB
+  const int64_t sstride = (m + 3) & ~(int64_t)3;
+  int64_t per_q = 4 * sstride;
+  const SelectPath sel = select_path(m, count);
+  if (sel == SelectPath::SORT) per_q += 8 * next_pow2_i64(m);
+  const int qc = (int)std::max<int64_t>(1, std::min<int64_t>(nq, ((int64_t)2 << 30) / per_q));
+  if ((rc = c->scores.grow((size_t)qc * (size_t)sstride)) != SVS_OK) return rc;
+  if (sel == SelectPath::WINDOW && (rc = grow_select_scratch(c, qc, st)) != SVS_OK) return rc;
+  for (int q0 = 0; q0 < nq; q0 += qc) {
+    const int nc = std::min(qc, nq - q0);
+    if ((rc = enqueue_list_search(idx, c, c->q_dev + (size_t)q0 * d, nc, c->list_dev, m, count, c->out_s_pin + (size_t)q0 * count,
+                                  c->lab_pos + (size_t)q0 * count, st)) != SVS_OK)
+      return rc;
+  }
+  // the positions -> global rows, on the device: the list never exists on the host
+  hipLaunchKernelGGL(label_map_rows_kernel, dim3((unsigned)std::min<size_t>((on + 255) / 256, 1024)), dim3(256), 0, st,
+                     (const int64_t*)c->lab_pos.p, (int64_t)on, (const uint32_t*)c->list_dev.p, m, lo, c->out_r_pin.p);
+  if ((rc = fr.close("search_labeled")) != SVS_OK) return rc;
+  for (size_t i = 0; i < on; ++i)
+    if (c->out_r_pin[i] < 0)
+      return fail(SVS_ERR_DEVICE, "search_labeled: result %zu of query %zu is a position outside the %lld matching rows", i % (size_t)count,
+                  i / (size_t)count, (long long)m);
+  deliver_results(c, nq, count, k, out_scores, out_rows);
+  if (out_count) *out_count = count;
+  if (out_matched) *out_matched = m;
   return SVS_OK;
 }
 

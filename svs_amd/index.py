@@ -23,6 +23,20 @@ from . import _native
 _DTYPES = {"f32": _native.DTYPE_F32, "f16": _native.DTYPE_F16, "fp8": _native.DTYPE_FP8}
 
 DIVERSE_MAX_FETCH = 1024   # SVS_DIVERSE_MAX_FETCH: the most candidates (and so results) of a diverse search
+LABELS_MAX_SET = 1024      # SVS_LABELS_MAX_SET: the most distinct labels one labelled search names
+
+
+def labels_u32(labels) -> np.ndarray:
+    """Row labels, or the label set of a search, as a C-contiguous u32 vector; ValueError for a value outside
+    [0, 2**32) or one that is no integer (a cast would silently name another label)."""
+    a = np.asarray(labels if isinstance(labels, np.ndarray) else list(labels))
+    if a.dtype != np.uint32:
+        if a.size and a.dtype.kind not in "iu":
+            raise ValueError(f"labels must be integers, got dtype {a.dtype}")
+        if a.size and (int(a.min()) < 0 or int(a.max()) > 0xFFFFFFFF):
+            raise ValueError("labels must lie in [0, 2**32)")
+        a = a.astype(np.uint32)
+    return np.ascontiguousarray(a).reshape(-1)
 
 
 class DeviceIndex:
@@ -373,6 +387,65 @@ class DeviceIndex:
             raise ValueError(f"query must be 1-D, got shape {q.shape}")
         s, r, total = self.search_batch_above(q[None, :], [min_score], limit)[0]
         return list(zip(s.astype(np.float64).tolist(), r.tolist())), total
+
+    # -- labels: one u32 per row in HBM, and the search that names them (svs_index_search_labeled) ----------------
+    def set_labels(self, labels, row0: Optional[int] = None) -> None:
+        """``labels`` (integers in [0, 2**32)) become the labels of the GLOBAL rows ``row0 .. row0 + len(labels)``
+        (``row0=None``: from the index's first row).  The column lives in HBM only; a row never labelled carries 0, and
+        rows appended later get 0 (svs_index_set_labels)."""
+        lab = labels_u32(labels)
+        r0 = self.row_offset if row0 is None else int(row0)
+        _native.check(self._lib.svs_index_set_labels(self._handle(), r0, len(lab), lab.ctypes.data))
+        self._refresh()      # (the first call allocates the column: hbm_bytes)
+
+    def labels(self, row0: Optional[int] = None, nrows: Optional[int] = None) -> np.ndarray:
+        """The labels of the GLOBAL rows ``row0 .. row0 + nrows`` as the DEVICE holds them, u32 (``row0=None``: from the
+        first row; ``nrows=None``: to the last).  Zeros when no label was ever set (svs_index_get_labels)."""
+        h = self._pinned_handle()
+        try:
+            info = _native.IndexInfo()
+            _native.check(self._quick.svs_index_info(h, C.byref(info)))
+            r0 = int(info.row_offset) if row0 is None else int(row0)
+            cnt = int(info.row_offset) + int(info.n) - r0 if nrows is None else int(nrows)
+            out = np.empty(max(cnt, 0), dtype=np.uint32)
+            _native.check(self._lib.svs_index_get_labels(h, r0, cnt, out.ctypes.data))
+        finally:
+            self._unpin(h)
+        return out
+
+    def search_batch_labeled(self, queries: np.ndarray, n: int, labels) -> Tuple[np.ndarray, np.ndarray, int]:
+        """``search_batch`` over the live rows whose label is in ``labels`` (any order, repeats allowed, at most
+        LABELS_MAX_SET distinct ones; none: the empty set): (scores f32 (nq, count), rows i64 (nq, count), matched),
+        matched = how many rows carry such a label, count = min(max(n, 0), matched), each row ordered (score desc,
+        row desc) -- the rows and score bits ``search_batch_within`` gives for exactly those rows, with the filter run on
+        the device (svs_index_search_labeled).  ``n=0`` only counts."""
+        assert isinstance(n, int)
+        q = self._queries_2d(queries)
+        nq, d = q.shape
+        lab = labels_u32(labels)
+        h = self._pinned_handle()
+        try:
+            # (clamped before allocating and before the int32 argument, as in search_batch)
+            k = min(max(n, 0), self._live_rows(h))
+            scores = np.empty((nq, k), dtype=np.float32)
+            rows = np.empty((nq, k), dtype=np.int64)
+            count, matched = C.c_int32(0), C.c_int64(0)
+            # (the one call that releases the GIL)
+            _native.check(self._lib.svs_index_search_labeled(h, q.ctypes.data, nq, d, k, lab.ctypes.data, len(lab),
+                                                             scores.ctypes.data, rows.ctypes.data, C.byref(count), C.byref(matched)))
+        finally:
+            self._unpin(h)
+        return self._trimmed(scores, rows, count.value) + (matched.value,)
+
+    def search_labeled(self, query_vec: np.ndarray, n: int, labels) -> Tuple[List[Tuple[float, int]], int]:
+        """``search`` restricted to the rows whose label is in ``labels`` (see ``search_batch_labeled``):
+        ([(score, row)], matched)."""
+        assert isinstance(n, int)
+        q = np.asarray(query_vec, dtype=np.float32)
+        if q.ndim != 1:
+            raise ValueError(f"query must be 1-D, got shape {q.shape}")
+        s, r, matched = self.search_batch_labeled(q[None, :], n, labels)
+        return list(zip(s[0].astype(np.float64).tolist(), r[0].tolist())), matched
 
     @staticmethod
     def diverse_fetch(n: int, fetch_k: Optional[int] = None) -> int:

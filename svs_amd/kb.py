@@ -29,8 +29,9 @@ from typing import Any, Awaitable, Callable, Dict, Iterator, List, Optional, Tup
 
 import numpy as np
 
-from .index import DeviceIndex
-from .matrix import DeviceEmbeddingsMatrix, above_op, batch_op, diverse_op, neighbors_op, pairs_op, segments_op, single_op, within_op
+from .index import LABELS_MAX_SET, DeviceIndex
+from .matrix import (DeviceEmbeddingsMatrix, above_op, batch_op, diverse_op, labeled_op, neighbors_op, pairs_op, segments_op, single_op,
+                     within_op)
 
 _LOG = logging.getLogger(__name__)
 
@@ -120,6 +121,10 @@ class _Store:
 
     # -- docs ---------------------------------------------------------------
     def add_doc(self, text: str, parent_id: Optional[int], meta: Optional[Dict[str, Any]]) -> int:
+        return self.add_doc_at(text, parent_id, meta)[0]
+
+    def add_doc_at(self, text: str, parent_id: Optional[int], meta: Optional[Dict[str, Any]]) -> Tuple[int, int]:
+        """``add_doc`` that also tells the level the doc landed on: (doc id, level)."""
         level = 0
         if parent_id is not None:
             row = self.conn.execute("SELECT level FROM docs WHERE id = ?", (parent_id,)).fetchone()
@@ -129,7 +134,7 @@ class _Store:
         cur = self.conn.execute(
             "INSERT INTO docs (parent_id, level, text, embedding, meta) VALUES (?, ?, ?, NULL, ?)",
             (parent_id, level, text, json.dumps(meta) if meta is not None else None))
-        return int(cur.lastrowid)
+        return int(cur.lastrowid), int(level)
 
     def set_doc_embedding(self, doc_id: int, blob: bytes) -> int:
         cur = self.conn.execute("INSERT INTO embeddings (embedding) VALUES (?)", (blob,))
@@ -191,6 +196,13 @@ class _Store:
             if doc_id not in found:
                 raise KeyError(doc_id)
         return sorted({e for e in found.values() if e is not None})
+
+    def embedding_levels(self) -> Tuple[np.ndarray, np.ndarray]:
+        """(embedding ids i64, labels u32) of every doc that has an embedding, in one scan (``retrieve_at_level``: the
+        label column of the HBM copy).  The label of a doc is ``level + 1``: 0 is left for "not labelled yet"."""
+        rows = self.conn.execute("SELECT embedding, level FROM docs WHERE embedding IS NOT NULL").fetchall()
+        pairs = np.array(rows, dtype=np.int64).reshape(-1, 2)
+        return pairs[:, 0].copy(), (pairs[:, 1] + 1).astype(np.uint32)
 
     def embedding_of_doc(self, doc_id: int) -> int:
         """The embedding id of one doc (``retrieve_similar``): KeyError(doc_id) for an unknown doc, like the
@@ -353,6 +365,29 @@ def _fetch_diverse(db: _Store, picks: List[Tuple[float, int, float]]) -> List[Di
     return [{"score": s, "doc": docs[e], "redundancy": r} for s, e, r in picks]
 
 
+def _level_labels(levels) -> List[int]:
+    """The label set of ``retrieve_at_level``: ``levels`` (an int or an iterable of ints) as the distinct stored labels
+    ``level + 1``, ascending.  ValueError for a level that is negative or no integer, and for more than
+    ``LABELS_MAX_SET`` distinct levels."""
+    if isinstance(levels, (int, np.integer)):
+        given = [levels]
+    elif isinstance(levels, (str, bytes)) or not hasattr(levels, "__iter__"):
+        raise ValueError(f"levels must be an integer or an iterable of integers, got {levels!r}")
+    else:
+        given = list(levels)
+    for lv in given:
+        if isinstance(lv, bool) or not isinstance(lv, (int, np.integer)):
+            raise ValueError(f"a level must be an integer, got {lv!r}")
+        if lv < 0:
+            raise ValueError(f"a level cannot be negative, got {lv}")
+        if lv + 1 > 0xFFFFFFFF:
+            raise ValueError(f"level {lv} is too large")
+    labels = sorted({int(lv) + 1 for lv in given})
+    if len(labels) > LABELS_MAX_SET:
+        raise ValueError(f"{len(labels)} distinct levels; one retrieval names at most {LABELS_MAX_SET}")
+    return labels
+
+
 def _diverse_args(n: int, fetch_n: Optional[int], diversity: float) -> Tuple[int, float]:
     """(candidates to fetch, lambda_mult = 1 - diversity) of a diverse retrieval; ValueError for a diversity outside
     [0, 1] or NaN, more than 1024 results or candidates, or fewer candidates than results."""
@@ -413,17 +448,18 @@ class KB:
         assert self.db is not None
         new_ids: List[int] = []
         new_vecs: List[List[float]] = []
+        new_labels: List[int] = []     # level + 1 of every new embedding's doc (retrieve_at_level)
         try:
             with self.db.transaction():
                 live = True
-                pending: List[Tuple[int, str]] = []
+                pending: List[Tuple[int, str, int]] = []
 
                 def add_doc(text: str, parent_id: Optional[int] = None, meta: Optional[Dict[str, Any]] = None,
                             no_embedding: bool = False) -> int:
                     assert live, "You may not call this function outside of the context manager!"
-                    doc_id = self.db.add_doc(text, parent_id, meta)
+                    doc_id, level = self.db.add_doc_at(text, parent_id, meta)
                     if not no_embedding:
-                        pending.append((doc_id, text))
+                        pending.append((doc_id, text, level))
                     return doc_id
 
                 try:
@@ -432,17 +468,18 @@ class KB:
                     live = False
                 for c0 in range(0, len(pending), BULK_EMBEDDING_CHUNK_SIZE):
                     chunk = pending[c0:c0 + BULK_EMBEDDING_CHUNK_SIZE]
-                    vectors = self._embed([t for _, t in chunk])
-                    for (doc_id, _), vec in zip(chunk, vectors):
+                    vectors = self._embed([t for _, t, _ in chunk])
+                    for (doc_id, _, level), vec in zip(chunk, vectors):
                         new_ids.append(self.db.set_doc_embedding(doc_id, embedding_to_bytes(vec)))
                         new_vecs.append(vec)
+                        new_labels.append(level + 1)
         except BaseException:
             self.embeddings_matrix.invalidate()
             raise
         # committed: the reference drops the whole cached matrix here (kb.py:1523); the
         # HBM copy is instead extended in place (falls back to invalidate when not loaded)
         if new_ids:
-            self.embeddings_matrix.append(np.array(new_vecs, dtype=np.float32), new_ids)
+            self.embeddings_matrix.append(np.array(new_vecs, dtype=np.float32), new_ids, labels=new_labels)
 
     @contextmanager
     def bulk_del_docs(self) -> Iterator[Callable[[int], None]]:
@@ -520,6 +557,34 @@ class KB:
             res = _fetch_list(self.db, emb_ids)
         _LOG.info(f"retrieved top {n} documents")
         return res, total
+
+    def retrieve_at_level(self, query: str, n: int, levels) -> List[Dict[str, Any]]:
+        """``retrieve`` restricted to the documents of one level of the tree (``levels``: an int) or of several (an
+        iterable of ints): the top n of those docs, same log lines and result shape.  The level sits next to each
+        vector in HBM as a label (``level + 1``; 0 = not labelled yet, which matches no level) and the filter runs on
+        the device (svs_index_search_labeled): no doc-id list, no SQL per query.  The column is installed at the first
+        such retrieval of an index generation, by one scan of the docs table; afterwards ``bulk_add_docs`` labels the
+        rows it appends and deletions move the labels with the rows.  A level no doc has gives ``[]``; a negative
+        level, or more than 1,024 distinct ones, raises ValueError.  A doc added concurrently becomes visible here when
+        its label is set, a moment after ``retrieve`` sees it."""
+        labels = _level_labels(levels)
+        _LOG.info(f"retrieving {n} documents with query string: {query}")
+        assert self.db is not None
+        self.embeddings_matrix.get_sync(self.db)
+
+        def levels_from_store():
+            with self.db.transaction():
+                return self.db.embedding_levels()
+
+        self.embeddings_matrix.ensure_labels(levels_from_store)
+        query_vec = np.array(self._embed([query])[0], dtype=np.float32)
+        _LOG.info("got embedding for query!")
+        emb_ids, matched = self.embeddings_matrix.search_labeled(query_vec, n, labels)   # filter + superheavy(): HIP
+        _LOG.info(f"computed {matched} cosine similarities")
+        with self.db.transaction():
+            res = _fetch_list(self.db, emb_ids)
+        _LOG.info(f"retrieved top {n} documents")
+        return res
 
     def retrieve_diverse(self, query: str, n: int, fetch_n: Optional[int] = None, diversity: float = 0.5) -> List[Dict[str, Any]]:
         """``retrieve`` without the near-copies: the ``fetch_n`` best documents (default min(max(4 n, 32), 1024)) are
@@ -743,16 +808,16 @@ class AsyncKB:
     async def bulk_add_docs(self):
         async with self._get_lock():
             db = await self._ensure_db()
-            pending: List[Tuple[int, str]] = []
+            pending: List[Tuple[int, str, int]] = []
             live = True
             db.conn.execute("BEGIN")
             try:
                 async def add_doc(text: str, parent_id: Optional[int] = None,
                                   meta: Optional[Dict[str, Any]] = None, no_embedding: bool = False) -> int:
                     assert live, "You may not call this function outside of the context manager!"
-                    doc_id = db.add_doc(text, parent_id, meta)
+                    doc_id, level = db.add_doc_at(text, parent_id, meta)
                     if not no_embedding:
-                        pending.append((doc_id, text))
+                        pending.append((doc_id, text, level))
                     return doc_id
                 try:
                     yield add_doc
@@ -760,12 +825,14 @@ class AsyncKB:
                     live = False
                 new_ids: List[int] = []
                 new_vecs: List[List[float]] = []
+                new_labels: List[int] = []     # level + 1 of every new embedding's doc (retrieve_at_level)
                 for c0 in range(0, len(pending), BULK_EMBEDDING_CHUNK_SIZE):
                     chunk = pending[c0:c0 + BULK_EMBEDDING_CHUNK_SIZE]
-                    vectors = await self._embed([t for _, t in chunk])
-                    for (doc_id, _), vec in zip(chunk, vectors):
+                    vectors = await self._embed([t for _, t, _ in chunk])
+                    for (doc_id, _, level), vec in zip(chunk, vectors):
                         new_ids.append(db.set_doc_embedding(doc_id, embedding_to_bytes(vec)))
                         new_vecs.append(vec)
+                        new_labels.append(level + 1)
             except BaseException:
                 db.conn.execute("ROLLBACK")
                 self.embeddings_matrix.invalidate()
@@ -775,7 +842,7 @@ class AsyncKB:
             if new_ids:   # extend the HBM copy in place (reference: invalidate(), kb.py:1062)
                 loop = asyncio.get_running_loop()
                 await loop.run_in_executor(None, lambda: self.embeddings_matrix.append(
-                    np.array(new_vecs, dtype=np.float32), new_ids))
+                    np.array(new_vecs, dtype=np.float32), new_ids, labels=new_labels))
 
     @asynccontextmanager
     async def bulk_del_docs(self):
@@ -844,6 +911,21 @@ class AsyncKB:
         res = await self._fetch(lambda db: _fetch_list(db, emb_ids))
         _LOG.info(f"retrieved top {n} documents")
         return res, total
+
+    async def retrieve_at_level(self, query: str, n: int, levels) -> List[Dict[str, Any]]:
+        """Async twin of ``KB.retrieve_at_level``, structured as ``retrieve``: the label column is installed (when this
+        index generation has none yet) and the reference to the matrix is taken under the lock, the labelled search
+        runs on an executor thread outside it, the docs are fetched under the lock."""
+        labels = _level_labels(levels)
+        _LOG.info(f"retrieving {n} documents with query string: {query}")
+        async with self._held(lambda db: self.embeddings_matrix.ensure_labels(db.embedding_levels)) as (held, _):
+            query_vec = np.array((await self._embed([query]))[0], dtype=np.float32)
+            _LOG.info("got embedding for query!")
+            emb_ids, matched = await self._search(held, labeled_op(query_vec, n, labels))
+            _LOG.info(f"computed {matched} cosine similarities")
+        res = await self._fetch(lambda db: _fetch_list(db, emb_ids))
+        _LOG.info(f"retrieved top {n} documents")
+        return res
 
     async def retrieve_diverse(self, query: str, n: int, fetch_n: Optional[int] = None,
                                diversity: float = 0.5) -> List[Dict[str, Any]]:

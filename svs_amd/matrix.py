@@ -185,6 +185,21 @@ def above_op(query_vec: np.ndarray, min_score: float, n: int):
     return native, finish
 
 
+def labeled_op(query_vec: np.ndarray, n: int, labels):
+    """Labelled search: ``idx.search_labeled`` (svs_index_search_labeled) over the rows whose stored label is in
+    ``labels``, rows -> ids: ([(score, emb_id)], rows that carry such a label).  The column is whatever the index holds
+    (``DeviceEmbeddingsMatrix.ensure_labels``)."""
+    def native(idx, lookup, *_):
+        return idx, idx.search_labeled(query_vec, n, labels)
+
+    def finish(res, arr):
+        used, (rows, matched) = res
+        off = int(getattr(used, "row_offset", 0))
+        return [(score, int(arr[row - off])) for score, row in rows], int(matched)
+
+    return native, finish
+
+
 def diverse_op(query_vec: np.ndarray, n: int, fetch_k: Optional[int] = None, lam: float = 0.5):
     """Diverse (MMR) search: ``idx.search_diverse`` (svs_index_search_diverse), rows -> ids:
     [(score, emb_id, redundancy)] in pick order."""
@@ -238,6 +253,8 @@ class DeviceEmbeddingsMatrix:
         self.embeddings_matrix: Optional[np.ndarray] = None   # host copy (pairwise path), optional
         self._lookup: Optional[_Lookup] = None
         self._n_dead = 0
+        # the index generation whose label column is installed and complete (ensure_labels); None: none is
+        self._labels_for: Optional[Any] = None
         # concurrent single-query searches of one index generation share corpus passes (coalesce.py)
         self.coalesce = True
         self._coalescer: Optional[SearchCoalescer] = None
@@ -257,6 +274,7 @@ class DeviceEmbeddingsMatrix:
             self.embeddings_matrix = None
             self._lookup = None
             self._n_dead = 0
+            self._labels_for = None
             self._coalescer = None
         if idx is not None:
             idx.release()
@@ -337,11 +355,13 @@ class DeviceEmbeddingsMatrix:
         return idx
 
     # -- incremental update ---------------------------------
-    def append(self, new_rows: np.ndarray, new_ids) -> bool:
+    def append(self, new_rows: np.ndarray, new_ids, labels=None) -> bool:
         """Rows a ``bulk_add_docs`` just committed, in embedding-id order (the order
         ``SELECT id, embedding FROM embeddings`` would return them, src/svs/kb.py:603).
         Edits the HBM copy in place; False if nothing is loaded (the next ``get``
-        builds from storage anyway)."""
+        builds from storage anyway).  ``labels``: one per new row, set behind the append while this generation's
+        label column is installed (``ensure_labels``); an append WITHOUT labels marks the column not installed -- the
+        new rows carry label 0 until the next ``ensure_labels`` installs the whole column again."""
         new_rows = np.ascontiguousarray(new_rows, dtype=np.float32)
         ids = np.asarray(new_ids, dtype=np.int64)
         with self._mu:
@@ -354,8 +374,16 @@ class DeviceEmbeddingsMatrix:
                     or np.any(np.diff(ids) <= 0) or new_rows.shape[1] != idx.shape[1]:
                 idx = None   # not a pure append (or dimension change): rebuild
             else:
+                installed = self._labels_for is idx
+                self._labels_for = None      # (until the new rows' labels are in: a failure below leaves it so)
+                row0 = int(getattr(idx, "row_offset", 0)) + len(lk.arr)
                 idx.append(new_rows)
                 lk.arr = np.concatenate([lk.arr, ids])
+                if installed and labels is not None:
+                    if len(labels) != len(ids):
+                        raise ValueError(f"{len(labels)} labels for {len(ids)} new rows")
+                    idx.set_labels(labels, row0)
+                    self._labels_for = idx
                 if self.embeddings_matrix is not None:
                     self.embeddings_matrix = np.vstack([self.embeddings_matrix, new_rows])
         if idx is None:
@@ -458,6 +486,36 @@ class DeviceEmbeddingsMatrix:
         """Every stored embedding scoring at or above ``min_score``, best first, at most ``n``:
         ([(score, emb_id)], total qualifying) (``KB.retrieve_above``)."""
         return self.run_mapped(above_op(query_vec, min_score, n))
+
+    def ensure_labels(self, fetch: Callable[[], Tuple[Any, Any]]) -> bool:
+        """The label column of the loaded index generation, installed at most once per generation: a no-op (False) while
+        it is installed; otherwise ``fetch()`` -> (embedding ids, labels), any order, is mapped to rows with one
+        ``searchsorted`` on the lookup, rows nobody names get 0, and ONE ``set_labels`` writes the whole range (True).
+        Ids the loaded matrix does not hold (committed, not yet appended) are skipped: their ``append`` brings their
+        labels.  ``append`` and this method exclude each other, so a row is never left with a stale label: it is
+        labelled by whichever of the two saw it last."""
+        with self._mu:
+            idx, lk = self._loaded()
+            if self._labels_for is idx:
+                return False
+            ids, labels = fetch()
+            ids = np.asarray(ids, dtype=np.int64).reshape(-1)
+            labels = np.asarray(labels, dtype=np.uint32).reshape(-1)
+            arr = lk.arr
+            column = np.zeros(len(arr), dtype=np.uint32)
+            if len(arr) and len(ids):
+                pos = np.minimum(np.searchsorted(arr, ids), len(arr) - 1)
+                known = arr[pos] == ids
+                column[pos[known]] = labels[known]
+            if len(column):
+                idx.set_labels(column)
+            self._labels_for = idx
+            return True
+
+    def search_labeled(self, query_vec: np.ndarray, n: int, labels) -> Tuple[List[Tuple[float, int]], int]:
+        """``search`` over the stored embeddings whose label is in ``labels``: ([(score, emb_id)], how many carry
+        such a label) (``KB.retrieve_at_level``).  Call ``ensure_labels`` first."""
+        return self.run_mapped(labeled_op(query_vec, n, labels))
 
     def search_diverse(self, query_vec: np.ndarray, n: int, fetch_k: Optional[int] = None,
                        lam: float = 0.5) -> List[Tuple[float, int, float]]:

@@ -209,6 +209,14 @@ class MultiDeviceIndex:
     def search_above(self, query_vec: np.ndarray, min_score: float, limit: int):
         raise NotImplementedError("threshold search is per device: call search_above on a DeviceIndex (a shard's totals and lists are its own)")
 
+    def search_labeled(self, query_vec: np.ndarray, n: int, labels):
+        raise NotImplementedError("labelled search is per device: the label column sits beside one shard's rows; call set_labels / search_labeled on a DeviceIndex")
+
+    search_batch_labeled = search_labeled
+
+    def set_labels(self, labels, row0: Optional[int] = None):
+        raise NotImplementedError("labels are per device: call set_labels on a DeviceIndex")
+
     def search_diverse(self, query_vec: np.ndarray, n: int, fetch_k: Optional[int] = None, lam: float = 0.5):
         raise NotImplementedError("diverse search is per device: the candidates' rows must sit in one HBM; call search_diverse on a DeviceIndex")
 

@@ -205,6 +205,11 @@ class ShardedIndex:
             return None
         return [(float(a), int(b)) for a, b in zip(res[0][0], res[1][0])]
 
+    def search_labeled(self, query_vec: np.ndarray, n: int, labels):
+        raise NotImplementedError("labelled search is per device: a rank labels and searches its own shard (DeviceIndex.search_labeled); nothing is merged across ranks")
+
+    search_batch_labeled = search_labeled
+
     # ---- pipelined single-query searches (device path; what bench.py times) ----------------
     def open(self, capacity: int, k: int) -> None:
         """Buffers for up to ``capacity`` enqueued single-query searches of top-``k``."""
