@@ -6,7 +6,8 @@
 //                            Grid: the upper-triangle 64 x 64 tiles (tile_i <= tile_j) x the block's queries; a tile off the
 //                            diagonal also stores its mirror image.  A workgroup gathers its two panels of 64 rows through
 //                            the query's candidate list (global rows, 64-bit addressing row * ld16 as gather.h), decodes
-//                            32 columns of each into LDS as f32 (f32 as is, f16 widened, fp8 e4m3 -> f32: all exact) and
+//                            32 columns of each into LDS as f32 (decode_chunk, chunk.h: f32 as is, f16 widened, fp8 e4m3
+//                            -> f32, all exact) and
 //                            walks them with v_mfma_f32_32x32x2_f32, one 32 x 32 accumulator per wave.  That MFMA is bit for
 //                            bit a k-ordered fmaf chain, so G[i][j] is ONE chain over columns 0 .. ld-1 in order: it depends
 //                            on the two rows' stored values and d only -- not on the tile, the position, c or nq -- and
@@ -27,8 +28,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include "fp8.h"
-#include "gemv_f16.h"
+#include "chunk.h"
 
 namespace svs {
 
@@ -59,8 +59,8 @@ template <int DT>
 __global__ __launch_bounds__(DV_THREADS) void diverse_gram_kernel(
     const u32x4* __restrict__ M, int ld16, const float* __restrict__ row_scales, const int64_t* __restrict__ cand, int c,
     int64_t row_offset, int64_t n, int nt, float* __restrict__ G) {
-  constexpr int EB = DT == 0 ? 4 : (DT == 1 ? 2 : 1);   // bytes per element = 16-byte chunks per 16 elements
-  constexpr int EPC = 16 / EB;                          // elements per chunk
+  constexpr int EPC = elems_per_chunk(DT);
+  constexpr int EB = 16 / EPC;                          // bytes per element = 16-byte chunks per 16 elements
   __shared__ float P[2][DV_TILE][DV_LDK];               // the two panels, [row][column of the step]
   __shared__ float S[2][DV_TILE];                       // fp8: the rows' scales
   int ti, tj;
@@ -86,21 +86,10 @@ __global__ __launch_bounds__(DV_THREADS) void diverse_gram_kernel(
     float* o = &P[pn][rr][h * 16];
 #pragma unroll
     for (int e = 0; e < EB; ++e) {
-      const uint32_t w[4] = {buf[e].x, buf[e].y, buf[e].z, buf[e].w};
+      float v[EPC];
+      decode_chunk<DT>(buf[e], v);
 #pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        if constexpr (DT == 0) {
-          o[e * 4 + j] = __uint_as_float(w[j]);
-        } else if constexpr (DT == 1) {
-          const h2 p = __builtin_bit_cast(h2, w[j]);
-          o[e * 8 + j * 2] = (float)p.x;
-          o[e * 8 + j * 2 + 1] = (float)p.y;
-        } else {
-          float v[4];
-          unpack_fp8x4(w[j], v);
-          o[j * 4] = v[0]; o[j * 4 + 1] = v[1]; o[j * 4 + 2] = v[2]; o[j * 4 + 3] = v[3];
-        }
-      }
+      for (int j = 0; j < EPC; ++j) o[e * EPC + j] = v[j];
     }
   };
   // ---- MFMA: wave w owns the 32 x 32 block (wi, wj) of the tile; lane l feeds A[i = l & 31][k = l >> 5], B[k][j = l & 31]

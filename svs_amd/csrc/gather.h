@@ -23,6 +23,9 @@
 // Batches: G queries per workgroup (staged in LDS), each row read once per group.  A lane sums its chunks
 // in chunk order, then seg_sum<T> -- the same for every G, so a query's scores are bit-identical whatever
 // batch or group it was scored in.
+//
+// gather_wave is that lane-level body, one wave's rows against one query or a staged group; gather_scores_kernel here
+// and gather_segments_kernel (segments.h) are prologues that decide which rows and which queries a wave takes.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -65,32 +68,21 @@ template <> struct GatherDot<0> { typedef DotF32 type; };
 template <> struct GatherDot<1> { typedef DotF16 type; };
 template <> struct GatherDot<2> { typedef DotFp8Packed type; };
 
-// M: rows of ld16 16-byte chunks; list: m local rows; q: nq staged queries of ld16 chunks each (zero padded
-// like the rows); row_scales / q_scales: fp8 only.  Grid: (row blocks, query groups).
-template <int DT, int T, int NC, int U, int G>
-__global__ __launch_bounds__(gather_wpb(NC) * 64) void gather_scores_kernel(
-    const u32x4* __restrict__ M, int ld16, const uint32_t* __restrict__ list, int64_t m,
-    const u32x4* __restrict__ q, int nq, const float* __restrict__ row_scales, const float* __restrict__ q_scales,
-    float* __restrict__ scores, int64_t sstride) {
+// One wave of either gather kernel: rows list[0 .. nrows), 1 <= nrows <= (64 / T) * U, against the queries
+// qsrc[g * ld16 ..] for g < (MANY ? gq : 1); scores[g * sstride + p] = <row list[p], query g>, q_scales[g] the
+// query's scale (fp8).  Lanes past the rows re-read entry nrows - 1 and store nothing.  Everything a score's bits
+// depend on -- the Dot type, the chunk order, seg_sum<T>, the fp8 scale order -- is here and nowhere else.
+template <int DT, int T, int NC, int U, bool MANY>
+__device__ __forceinline__ void gather_wave(const u32x4* __restrict__ M, int ld16, const uint32_t* __restrict__ list, int nrows,
+                                            const u32x4* qsrc, int gq, const float* __restrict__ row_scales,
+                                            const float* __restrict__ q_scales, float* __restrict__ scores, int64_t sstride) {
   typedef typename GatherDot<DT>::type Dot;
   constexpr bool SCALED = DT == 2;
-  constexpr int RPW = 64 / T, WPB = gather_wpb(NC);
+  constexpr int RPW = 64 / T;
   const Dot dot{};
   const int lane = threadIdx.x & 63;
   const int sub = lane & (T - 1);
   const int rsub = lane / T;
-  const int q0 = blockIdx.y * G;
-  const int gq = nq - q0 < G ? nq - q0 : G;   // queries of this group (block-uniform)
-  q += (size_t)q0 * ld16;
-  const u32x4* qsrc = q;
-  if constexpr (G > 1) {
-    extern __shared__ u32x4 q_lds[];   // [gq][ld16]
-    for (int i = threadIdx.x; i < gq * ld16; i += WPB * 64) q_lds[i] = q[i];
-    __syncthreads();
-    qsrc = q_lds;
-  }
-  const int64_t base = ((int64_t)blockIdx.x * WPB + (threadIdx.x >> 6)) * (RPW * U);
-  if (base >= m) return;
   int col[NC];
 #pragma unroll
   for (int c = 0; c < NC; ++c) {
@@ -100,8 +92,8 @@ __global__ __launch_bounds__(gather_wpb(NC) * 64) void gather_scores_kernel(
   uint32_t row[U];
 #pragma unroll
   for (int u = 0; u < U; ++u) {
-    const int64_t p = base + u * RPW + rsub;
-    row[u] = list[p < m ? p : m - 1];
+    const int p = u * RPW + rsub;
+    row[u] = list[p < nrows ? p : nrows - 1];
   }
   u32x4 a[U][NC];
 #pragma unroll
@@ -115,7 +107,7 @@ __global__ __launch_bounds__(gather_wpb(NC) * 64) void gather_scores_kernel(
   for (int u = 0; u < U; ++u) rs[u] = SCALED ? row_scales[row[u]] : 1.f;
   // (one query at a time: unrolled, the compiler would hold every query's chunks at once)
 #pragma unroll 1
-  for (int g = 0; g < (G == 1 ? 1 : gq); ++g) {
+  for (int g = 0; g < (MANY ? gq : 1); ++g) {
     float acc[U];
 #pragma unroll
     for (int u = 0; u < U; ++u) acc[u] = 0.f;
@@ -136,16 +128,41 @@ __global__ __launch_bounds__(gather_wpb(NC) * 64) void gather_scores_kernel(
         if constexpr (SCALED) asm volatile("" : "+v"(acc[u]));
       }
     }
-    float* out = scores + (size_t)(q0 + g) * sstride;
-    const float sq = SCALED ? q_scales[q0 + g] : 1.f;
+    float* out = scores + (size_t)g * sstride;
+    const float sq = SCALED ? q_scales[g] : 1.f;
 #pragma unroll
     for (int u = 0; u < U; ++u) {
       float v = seg_sum<T>(acc[u]);
       if constexpr (SCALED) v = v * rs[u] * sq;
-      const int64_t p = base + u * RPW + rsub;
-      if (sub == 0 && p < m) out[p] = v;
+      const int p = u * RPW + rsub;
+      if (sub == 0 && p < nrows) out[p] = v;
     }
   }
+}
+
+// M: rows of ld16 16-byte chunks; list: m local rows; q: nq staged queries of ld16 chunks each (zero padded
+// like the rows); row_scales / q_scales: fp8 only.  Grid: (row blocks, query groups); a wave takes (64 / T) U rows.
+template <int DT, int T, int NC, int U, int G>
+__global__ __launch_bounds__(gather_wpb(NC) * 64) void gather_scores_kernel(
+    const u32x4* __restrict__ M, int ld16, const uint32_t* __restrict__ list, int64_t m,
+    const u32x4* __restrict__ q, int nq, const float* __restrict__ row_scales, const float* __restrict__ q_scales,
+    float* __restrict__ scores, int64_t sstride) {
+  constexpr int W = 64 / T * U, WPB = gather_wpb(NC);
+  const int q0 = blockIdx.y * G;
+  const int gq = nq - q0 < G ? nq - q0 : G;   // queries of this group (block-uniform)
+  q += (size_t)q0 * ld16;
+  const u32x4* qsrc = q;
+  if constexpr (G > 1) {
+    extern __shared__ u32x4 q_lds[];   // [gq][ld16]
+    for (int i = threadIdx.x; i < gq * ld16; i += WPB * 64) q_lds[i] = q[i];
+    __syncthreads();
+    qsrc = q_lds;
+  }
+  const int64_t base = ((int64_t)blockIdx.x * WPB + (threadIdx.x >> 6)) * W;
+  if (base >= m) return;
+  const int nrows = m - base < W ? (int)(m - base) : W;
+  gather_wave<DT, T, NC, U, (G > 1)>(M, ld16, list + base, nrows, qsrc, gq, row_scales, q_scales + q0,
+                                     scores + (size_t)q0 * sstride + base, sstride);
 }
 
 }  // namespace svs

@@ -4,7 +4,8 @@
 //                           converts and quantises like any host batch.  Values are those of dequant_rows_*_kernel
 //                           (f32: the row; f16: widened; fp8: e4m3 x row scale), so the panel holds bit for bit what
 //                           svs_index_debug_dequant returns for those rows.  Reads whole 16-byte chunks of a row per
-//                           lane, as gather.h does; the padding columns (>= d) are not copied.
+//                           lane, as gather.h does, decoded by decode_chunk (chunk.h); the padding columns (>= d) are
+//                           not copied.
 //   drop_self_kernel        the search ran at count + 1; one wave per query removes the entry whose row is the source
 //                           row (at most one: a search returns a row once), or the last entry when the source row is
 //                           not among the count + 1 best, and writes `count` entries at stride `count`.
@@ -14,8 +15,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include "fp8.h"
-#include "gemv_f16.h"
+#include "chunk.h"
 
 namespace svs {
 
@@ -27,7 +27,7 @@ template <int DT>
 __global__ __launch_bounds__(NEIGHBORS_THREADS) void rows_as_queries_kernel(
     const u32x4* __restrict__ M, int ld16, const float* __restrict__ row_scales, const uint32_t* __restrict__ list,
     int nq, int d, float* __restrict__ out) {
-  constexpr int EPC = DT == 0 ? 4 : (DT == 1 ? 8 : 16);   // elements per chunk
+  constexpr int EPC = elems_per_chunk(DT);
   const int used = (d + EPC - 1) / EPC;                    // chunks of a row that hold columns < d (<= ld16)
   const int64_t total = (int64_t)nq * used;
   const int64_t stride = (int64_t)gridDim.x * NEIGHBORS_THREADS;
@@ -35,28 +35,12 @@ __global__ __launch_bounds__(NEIGHBORS_THREADS) void rows_as_queries_kernel(
     const int q = (int)(i / used);
     const int ch = (int)(i - (int64_t)q * used);
     const uint32_t row = list[q];
-    const u32x4 a = M[(int64_t)row * ld16 + ch];
-    const uint32_t w[4] = {a.x, a.y, a.z, a.w};
     float v[EPC];
-    if constexpr (DT == 0) {
-#pragma unroll
-      for (int e = 0; e < 4; ++e) v[e] = __uint_as_float(w[e]);
-    } else if constexpr (DT == 1) {
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        const h2 p = __builtin_bit_cast(h2, w[e]);
-        v[2 * e] = (float)p.x;
-        v[2 * e + 1] = (float)p.y;
-      }
-    } else {
+    decode_chunk<DT>(M[(int64_t)row * ld16 + ch], v);
+    if constexpr (DT == 2) {
       const float s = row_scales[row];
 #pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        float b[4];
-        unpack_fp8x4(w[e], b);
-#pragma unroll
-        for (int j = 0; j < 4; ++j) v[4 * e + j] = b[j] * s;
-      }
+      for (int e = 0; e < EPC; ++e) v[e] = v[e] * s;
     }
     const int c0 = ch * EPC;
     float* o = out + (int64_t)q * d + c0;

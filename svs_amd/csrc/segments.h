@@ -13,10 +13,10 @@
 // rows; at one tile per wave only the last wave of each segment is ragged.  Segments of more than SORT_CAP live rows
 // take svs_index_search_rows' own kernels.
 //
-// gather_segments_kernel: the G = 1 body of gather_scores_kernel driven by the tile table -- the same Dot types, chunk
-// order, seg_sum<T>, fp8 scale order and non-temporal loads, so a row's score has the same bits as there.  Lanes past
-// the tile's rows re-read the tile's own last list entry and store nothing (the next score belongs to another
-// segment).  No LDS, no barrier; HBM-bound like gather_scores_kernel: bytes = listed rows x row bytes.
+// gather_segments_kernel: gather_wave (gather.h), the one-query body of gather_scores_kernel, driven by the tile table:
+// the same function, so a row's score has the same bits as there.  Lanes past the tile's rows re-read the tile's own
+// last list entry and store nothing (the next score belongs to another segment).  No LDS, no barrier; HBM-bound like
+// gather_scores_kernel: bytes = listed rows x row bytes.
 //
 // select_segments_kernel: one workgroup per segment sorts make_key(score, position) of its <= SORT_CAP scores in LDS
 // (select_final_kernel's mode 1: rank emission up to FINAL_THREADS keys, the bitonic network beyond) and writes
@@ -72,13 +72,7 @@ __global__ __launch_bounds__(gather_wpb(NC) * 64) void gather_segments_kernel(
     const u32x4* __restrict__ M, int ld16, const uint32_t* __restrict__ list, const SegTile* __restrict__ tiles, int64_t ntiles,
     const u32x4* __restrict__ q, const float* __restrict__ row_scales, const float* __restrict__ q_scales,
     float* __restrict__ scores) {
-  typedef typename GatherDot<DT>::type Dot;
-  constexpr bool SCALED = DT == 2;
-  constexpr int RPW = 64 / T, WPB = gather_wpb(NC);
-  const Dot dot{};
-  const int lane = threadIdx.x & 63;
-  const int sub = lane & (T - 1);
-  const int rsub = lane / T;
+  constexpr int WPB = gather_wpb(NC);
   const int64_t w = (int64_t)blockIdx.x * WPB + (threadIdx.x >> 6);
   if (w >= ntiles) return;
   const SegTile tile = tiles[w];
@@ -86,57 +80,7 @@ __global__ __launch_bounds__(gather_wpb(NC) * 64) void gather_segments_kernel(
   const uint32_t off = (uint32_t)__builtin_amdgcn_readfirstlane((int)tile.off);
   const int nrows = __builtin_amdgcn_readfirstlane((int)tile.rows);
   const uint32_t qi = (uint32_t)__builtin_amdgcn_readfirstlane((int)tile.query);
-  const u32x4* qsrc = q + (size_t)qi * ld16;
-  list += off;
-  scores += off;
-  int col[NC];
-#pragma unroll
-  for (int c = 0; c < NC; ++c) {
-    const int i = sub + c * T;
-    col[c] = i < ld16 ? i : ld16 - 1;
-  }
-  uint32_t row[U];
-#pragma unroll
-  for (int u = 0; u < U; ++u) {
-    const int p = u * RPW + rsub;
-    row[u] = list[p < nrows ? p : nrows - 1];
-  }
-  u32x4 a[U][NC];
-#pragma unroll
-  for (int u = 0; u < U; ++u) {
-    const u32x4* pr = M + (int64_t)row[u] * ld16;
-#pragma unroll
-    for (int c = 0; c < NC; ++c) a[u][c] = __builtin_nontemporal_load(pr + col[c]);
-  }
-  float rs[U];
-#pragma unroll
-  for (int u = 0; u < U; ++u) rs[u] = SCALED ? row_scales[row[u]] : 1.f;
-  float acc[U];
-#pragma unroll
-  for (int u = 0; u < U; ++u) acc[u] = 0.f;
-#pragma unroll
-  for (int c = 0; c < NC; ++c) {
-    const int i = sub + c * T;
-    const typename Dot::Q qc = dot.prep(i < ld16 ? qsrc[i] : (u32x4){0u, 0u, 0u, 0u});
-#pragma unroll
-    for (int u = 0; u < U; ++u) {
-      u32x4 av = a[u][c];
-      // (fp8: each chunk's decode pinned between its own load and its FMAs, as in gather_scores_kernel)
-      if constexpr (SCALED) asm volatile("" : "+v"(av));
-      // (lanes past the row keep their sum: the chunk they re-read may hold inf or NaN, and 0 * inf is NaN)
-      const float with_chunk = dot.dot(av, qc, acc[u]);
-      acc[u] = i < ld16 ? with_chunk : acc[u];
-      if constexpr (SCALED) asm volatile("" : "+v"(acc[u]));
-    }
-  }
-  const float sq = SCALED ? q_scales[qi] : 1.f;
-#pragma unroll
-  for (int u = 0; u < U; ++u) {
-    float v = seg_sum<T>(acc[u]);
-    if constexpr (SCALED) v = v * rs[u] * sq;
-    const int p = u * RPW + rsub;
-    if (sub == 0 && p < nrows) scores[p] = v;
-  }
+  gather_wave<DT, T, NC, U, false>(M, ld16, list + off, nrows, q + (size_t)qi * ld16, 1, row_scales, q_scales + qi, scores + off, 0);
 }
 
 // grid = the call's small segments; out_scores / out_rows: [segments][kk], entries past a segment's count untouched

@@ -1202,6 +1202,21 @@ constexpr SelectPath select_path(int64_t n_eff, int count) {
   return n_eff > SORT_CAP && count <= SEL_KMAX ? SelectPath::WINDOW : (n_eff > SORT_CAP ? SelectPath::SORT : SelectPath::FINAL);
 }
 
+// Histogram / candidate scratch of run_select's window path (SelectPath::WINDOW) for nq queries.
+int grow_select_scratch(Ctx* c, int nq, hipStream_t st) {
+  if ((size_t)nq <= c->hist_cap) return SVS_OK;
+  c->hist_cap = 0;
+  HIP_TRY(c->hist.release());
+  HIP_TRY(c->cand.release());
+  int rc;
+  if ((rc = c->hist.grow((size_t)nq * SCR_WORDS)) != SVS_OK) return rc;
+  if ((rc = c->cand.grow((size_t)nq * CAND_CAP)) != SVS_OK) return rc;
+  // zeroed once; select_final_kernel leaves it zeroed after every search
+  HIP_TRY(hipMemsetAsync(c->hist, 0, (size_t)nq * SCR_WORDS * sizeof(uint32_t), st));
+  c->hist_cap = nq;
+  return SVS_OK;
+}
+
 // Top-k stage over a materialised score matrix scores[nq][sstride] with n_eff rows.
 int run_select(svs_index* idx, Ctx* c, const float* scores, int64_t n_eff, int64_t sstride, int nq, int k,
                int count, float* out_s, int64_t* out_r, hipStream_t st, int64_t row_offset) {
@@ -1368,9 +1383,9 @@ int stage_gather_queries(const svs_index* idx, Ctx* c, const float* q_dev, int n
   return SVS_OK;
 }
 
-// f(Int<DT>): the corpus dtype as the gather kernels' template argument
+// f(Int<DT>): the corpus dtype as the template argument of the kernels that read stored rows (0 f32, 1 f16, 2 fp8)
 template <class F>
-auto for_gather_dtype(const svs_index* idx, F&& f) {
+auto for_store_dtype(const svs_index* idx, F&& f) {
   return idx->dtype == SVS_DTYPE_F32 ? f(Int<0>{}) : (idx->dtype == SVS_DTYPE_F16 ? f(Int<1>{}) : f(Int<2>{}));
 }
 
@@ -1381,7 +1396,7 @@ int launch_gather(const svs_index* idx, Ctx* c, const float* q_dev, int nq, cons
   const float* qs = nullptr;
   const int rc = stage_gather_queries(idx, c, q_dev, nq, &q, &qs, st);
   if (rc != SVS_OK) return rc;
-  return for_gather_dtype(idx, [&](auto dt) { return launch_gather_dt<dt()>(idx, q, qs, nq, list, m, scores, sstride, st); });
+  return for_store_dtype(idx, [&](auto dt) { return launch_gather_dt<dt()>(idx, q, qs, nq, list, m, scores, sstride, st); });
 }
 
 // Top `count` of nq queries (f32 on the device) over a device row list: m local rows, ascending.  The context's score
@@ -1391,6 +1406,27 @@ int enqueue_list_search(svs_index* idx, Ctx* c, const float* q_dev, int nq, cons
   const int64_t sstride = (m + 3) & ~(int64_t)3;
   const int rc = launch_gather(idx, c, q_dev, nq, list, m, c->scores, sstride, st);
   return rc != SVS_OK ? rc : run_select(idx, c, c->scores, m, sstride, nq, count, count, out_s, out_r, st, 0);
+}
+
+// The call's nq queries (f32 in c->q_dev, d columns) over one device list, sized here: query chunks whose score matrix
+// (and, for k > SEL_KMAX over more than SORT_CAP rows, sort keys) stays <= 2 GiB.  out_s / out_r: [nq][count].
+int search_list_chunked(svs_index* idx, Ctx* c, int nq, int d, const uint32_t* list_dev, int64_t m, int count, float* out_s,
+                        int64_t* out_r, hipStream_t st) {
+  const int64_t sstride = (m + 3) & ~(int64_t)3;
+  int64_t per_q = 4 * sstride;
+  const SelectPath sel = select_path(m, count);
+  if (sel == SelectPath::SORT) per_q += 8 * next_pow2_i64(m);
+  const int qc = (int)std::max<int64_t>(1, std::min<int64_t>(nq, ((int64_t)2 << 30) / per_q));
+  int rc;
+  if ((rc = c->scores.grow((size_t)qc * (size_t)sstride)) != SVS_OK) return rc;
+  if (sel == SelectPath::WINDOW && (rc = grow_select_scratch(c, qc, st)) != SVS_OK) return rc;
+  for (int q0 = 0; q0 < nq; q0 += qc) {
+    const int nc = std::min(qc, nq - q0);
+    if ((rc = enqueue_list_search(idx, c, c->q_dev + (size_t)q0 * d, nc, list_dev, m, count, out_s + (size_t)q0 * count,
+                                  out_r + (size_t)q0 * count, st)) != SVS_OK)
+      return rc;
+  }
+  return SVS_OK;
 }
 
 // ... and, once they have arrived in pinned memory, the positions -> global rows, in place.  S: the list on the host;
@@ -1439,7 +1475,7 @@ int launch_gather_segments(const svs_index* idx, Ctx* c, const float* q_dev, int
   const float* qs = nullptr;
   const int rc = stage_gather_queries(idx, c, q_dev, nq, &q, &qs, st);
   if (rc != SVS_OK) return rc;
-  for_gather_dtype(idx, [&](auto dt) { launch_gather_segments_dt<dt()>(idx, q, qs, list, tiles, ntiles, total_rows, nseg, scores, st); });
+  for_store_dtype(idx, [&](auto dt) { launch_gather_segments_dt<dt()>(idx, q, qs, list, tiles, ntiles, total_rows, nseg, scores, st); });
   return SVS_OK;
 }
 
@@ -1523,21 +1559,6 @@ struct SearchPlan {
   uint64_t share_num = 0, share_reach = 0, share_epoch = 0;
   bool share_thin = false;           // ... and the pass on a thin grid
 };
-
-// Histogram / candidate scratch of run_select's window path (SelectPath::WINDOW) for nq queries.
-int grow_select_scratch(Ctx* c, int nq, hipStream_t st) {
-  if ((size_t)nq <= c->hist_cap) return SVS_OK;
-  c->hist_cap = 0;
-  HIP_TRY(c->hist.release());
-  HIP_TRY(c->cand.release());
-  int rc;
-  if ((rc = c->hist.grow((size_t)nq * SCR_WORDS)) != SVS_OK) return rc;
-  if ((rc = c->cand.grow((size_t)nq * CAND_CAP)) != SVS_OK) return rc;
-  // zeroed once; select_final_kernel leaves it zeroed after every search
-  HIP_TRY(hipMemsetAsync(c->hist, 0, (size_t)nq * SCR_WORDS * sizeof(uint32_t), st));
-  c->hist_cap = nq;
-  return SVS_OK;
-}
 
 int plan_search(svs_index* idx, Ctx* c, int nq, int k, int count, hipStream_t st, bool allow_fused, int variant, SearchPlan* p) {
   const int64_t n = idx->n;
@@ -2493,17 +2514,20 @@ int rerun_overflowed(svs_index* idx, HostCall& fr, int64_t q0, int64_t q1, int c
   return SVS_OK;
 }
 
-// The pinned result block (stride `count`) into the caller's (stride k)
-void deliver_results(const Ctx* c, int64_t nq, int count, int k, float* out_scores, int64_t* out_rows) {
-  if (count == k) {   // (one piece each)
-    memcpy(out_scores, c->out_s_pin, (size_t)nq * count * sizeof(float));
-    memcpy(out_rows, c->out_r_pin, (size_t)nq * count * sizeof(int64_t));
+// nq results of `count` entries each (stride `count`) into the caller's block (stride k >= count)
+template <class T>
+void deliver_strided(T* dst, int k, const T* src, int count, int64_t nq) {
+  if (count == k) {   // (one piece)
+    memcpy(dst, src, (size_t)nq * count * sizeof(T));
     return;
   }
-  for (int64_t qi = 0; qi < nq; ++qi) {
-    memcpy(out_scores + (size_t)qi * k, c->out_s_pin + (size_t)qi * count, (size_t)count * sizeof(float));
-    memcpy(out_rows + (size_t)qi * k, c->out_r_pin + (size_t)qi * count, (size_t)count * sizeof(int64_t));
-  }
+  for (int64_t qi = 0; qi < nq; ++qi) memcpy(dst + (size_t)qi * k, src + (size_t)qi * count, (size_t)count * sizeof(T));
+}
+
+// The pinned result block into the caller's
+void deliver_results(const Ctx* c, int64_t nq, int count, int k, float* out_scores, int64_t* out_rows) {
+  deliver_strided(out_scores, k, c->out_s_pin.p, count, nq);
+  deliver_strided(out_rows, k, c->out_r_pin.p, count, nq);
 }
 
 // A caller's list of global rows: every one a row of an index of n rows from row `lo`.  *ascending (may be null):
@@ -3244,21 +3268,7 @@ int32_t svs_index_search_rows(svs_index* idx, const float* queries, int32_t nq, 
   const hipStream_t st = fr.stream();
   if ((rc = upload_queries(c, queries, qn, st)) != SVS_OK) return rc;
   HIP_TRY(hipMemcpyAsync(c->list_dev, S, (size_t)m * sizeof(uint32_t), hipMemcpyHostToDevice, st));
-  // Query chunks whose score matrix (and, for k > SEL_KMAX over more than SORT_CAP rows, sort keys) stays <= 2 GiB
-  const int64_t sstride = (m + 3) & ~(int64_t)3;
-  int64_t per_q = 4 * sstride;
-  const SelectPath sel = select_path(m, count);
-  const bool window = sel == SelectPath::WINDOW;
-  if (sel == SelectPath::SORT) per_q += 8 * next_pow2_i64(m);
-  const int qc = (int)std::max<int64_t>(1, std::min<int64_t>(nq, ((int64_t)2 << 30) / per_q));
-  if ((rc = c->scores.grow((size_t)qc * (size_t)sstride)) != SVS_OK) return rc;
-  if (window && (rc = grow_select_scratch(c, qc, st)) != SVS_OK) return rc;
-  for (int q0 = 0; q0 < nq; q0 += qc) {
-    const int nc = std::min(qc, nq - q0);
-    if ((rc = enqueue_list_search(idx, c, c->q_dev + (size_t)q0 * d, nc, c->list_dev, m, count, c->out_s_pin + (size_t)q0 * count,
-                                  c->out_r_pin + (size_t)q0 * count, st)) != SVS_OK)
-      return rc;
-  }
+  if ((rc = search_list_chunked(idx, c, nq, d, c->list_dev, m, count, c->out_s_pin, c->out_r_pin, st)) != SVS_OK) return rc;
   if ((rc = fr.close("search_rows")) != SVS_OK) return rc;
   if ((rc = list_positions_to_rows(c->out_r_pin, on, S, m, lo, -1)) != SVS_OK) return rc;
   deliver_results(c, nq, count, k, out_scores, out_rows);
@@ -3389,20 +3399,7 @@ int32_t svs_index_search_labeled(svs_index* idx, const float* queries, int32_t n
   if ((rc = upload_queries(c, queries, qn, st)) != SVS_OK) return rc;
   launch_record("label_write_kernel", n, nset);
   launch_label_write<LB_ROWS>(f, c->lab_cnt, c->list_dev, m, st);
-  // Query chunks whose score matrix (and, for k > SEL_KMAX over more than SORT_CAP rows, sort keys) stays <= 2 GiB
-  const int64_t sstride = (m + 3) & ~(int64_t)3;
-  int64_t per_q = 4 * sstride;
-  const SelectPath sel = select_path(m, count);
-  if (sel == SelectPath::SORT) per_q += 8 * next_pow2_i64(m);
-  const int qc = (int)std::max<int64_t>(1, std::min<int64_t>(nq, ((int64_t)2 << 30) / per_q));
-  if ((rc = c->scores.grow((size_t)qc * (size_t)sstride)) != SVS_OK) return rc;
-  if (sel == SelectPath::WINDOW && (rc = grow_select_scratch(c, qc, st)) != SVS_OK) return rc;
-  for (int q0 = 0; q0 < nq; q0 += qc) {
-    const int nc = std::min(qc, nq - q0);
-    if ((rc = enqueue_list_search(idx, c, c->q_dev + (size_t)q0 * d, nc, c->list_dev, m, count, c->out_s_pin + (size_t)q0 * count,
-                                  c->lab_pos + (size_t)q0 * count, st)) != SVS_OK)
-      return rc;
-  }
+  if ((rc = search_list_chunked(idx, c, nq, d, c->list_dev, m, count, c->out_s_pin, c->lab_pos, st)) != SVS_OK) return rc;
   // the positions -> global rows, on the device: the list never exists on the host
   hipLaunchKernelGGL(label_map_rows_kernel, dim3((unsigned)std::min<size_t>((on + 255) / 256, 1024)), dim3(256), 0, st,
                      (const int64_t*)c->lab_pos.p, (int64_t)on, (const uint32_t*)c->list_dev.p, m, lo, c->out_r_pin.p);
@@ -3556,26 +3553,19 @@ int32_t svs_index_search_diverse(svs_index* idx, const float* queries, int32_t n
     const float* cand_s = cx->out_s_pin + (size_t)q0 * c;
     const dim3 grid((unsigned)(nt * (nt + 1) / 2), (unsigned)nb);
     launch_record("diverse_gram_kernel", c, nb);
-    if (idx->dtype == SVS_DTYPE_F32)
-      hipLaunchKernelGGL(diverse_gram_kernel<0>, grid, dim3(DV_THREADS), 0, st, M, ld16, (const float*)nullptr, cand_r,
-                         c, idx->row_offset, idx->n, nt, cx->dv_G.p);
-    else if (idx->dtype == SVS_DTYPE_F16)
-      hipLaunchKernelGGL(diverse_gram_kernel<1>, grid, dim3(DV_THREADS), 0, st, M, ld16, (const float*)nullptr, cand_r,
-                         c, idx->row_offset, idx->n, nt, cx->dv_G.p);
-    else
-      hipLaunchKernelGGL(diverse_gram_kernel<2>, grid, dim3(DV_THREADS), 0, st, M, ld16, (const float*)idx->row_scales,
-                         cand_r, c, idx->row_offset, idx->n, nt, cx->dv_G.p);
+    for_store_dtype(idx, [&](auto dt) {
+      hipLaunchKernelGGL(diverse_gram_kernel<dt()>, grid, dim3(DV_THREADS), 0, st, M, ld16, (const float*)idx->row_scales, cand_r,
+                         c, idx->row_offset, idx->n, nt, cx->dv_G.p);   // (row_scales: null unless fp8)
+    });
     launch_record("diverse_pick_kernel", c, nb);
     hipLaunchKernelGGL(diverse_pick_kernel, dim3((unsigned)nb), dim3(DV_PICK_THREADS), 0, st, cand_s, cand_r,
                        (const float*)cx->dv_G.p, c, count, lambda_mult, oml,
                        cx->dv_s_pin + (size_t)q0 * count, cx->dv_r_pin + (size_t)q0 * count, cx->dv_red_pin + (size_t)q0 * count);
   }
   if ((rc = fr.close("search_diverse")) != SVS_OK) return rc;
-  for (int32_t q = 0; q < nq; ++q) {
-    memcpy(out_scores + (size_t)q * k, cx->dv_s_pin + (size_t)q * count, (size_t)count * sizeof(float));
-    memcpy(out_rows + (size_t)q * k, cx->dv_r_pin + (size_t)q * count, (size_t)count * sizeof(int64_t));
-    if (out_redundancy) memcpy(out_redundancy + (size_t)q * k, cx->dv_red_pin + (size_t)q * count, (size_t)count * sizeof(float));
-  }
+  deliver_strided(out_scores, k, cx->dv_s_pin.p, count, nq);
+  deliver_strided(out_rows, k, cx->dv_r_pin.p, count, nq);
+  if (out_redundancy) deliver_strided(out_redundancy, k, cx->dv_red_pin.p, count, nq);
   return SVS_OK;
 }
 
@@ -3764,12 +3754,10 @@ static void launch_rows_as_queries(const svs_index* idx, const uint32_t* list_de
   const unsigned blocks = (unsigned)std::min<int64_t>(4096, (items + NEIGHBORS_THREADS - 1) / NEIGHBORS_THREADS);
   launch_record("rows_as_queries_kernel", nq, nq);
   const u32x4* M = (const u32x4*)idx->rows;
-  if (idx->dtype == SVS_DTYPE_F32)
-    hipLaunchKernelGGL(rows_as_queries_kernel<0>, dim3(blocks), dim3(NEIGHBORS_THREADS), 0, st, M, ld16, (const float*)nullptr, list_dev, nq, idx->d, panel);
-  else if (idx->dtype == SVS_DTYPE_F16)
-    hipLaunchKernelGGL(rows_as_queries_kernel<1>, dim3(blocks), dim3(NEIGHBORS_THREADS), 0, st, M, ld16, (const float*)nullptr, list_dev, nq, idx->d, panel);
-  else
-    hipLaunchKernelGGL(rows_as_queries_kernel<2>, dim3(blocks), dim3(NEIGHBORS_THREADS), 0, st, M, ld16, (const float*)idx->row_scales, list_dev, nq, idx->d, panel);
+  for_store_dtype(idx, [&](auto dt) {
+    hipLaunchKernelGGL(rows_as_queries_kernel<dt()>, dim3(blocks), dim3(NEIGHBORS_THREADS), 0, st, M, ld16, (const float*)idx->row_scales,
+                       list_dev, nq, idx->d, panel);
+  });
 }
 
 // drop_self_kernel: nq results at stride count + 1 -> count entries each at stride count
@@ -3895,11 +3883,7 @@ int32_t svs_index_debug_dequant(svs_index* idx, int64_t row0, int64_t nrows, flo
   }
   float* tmp = nullptr;
   HIP_TRY(hipMalloc((void**)&tmp, cnt * sizeof(float)));
-  if (idx->dtype == SVS_DTYPE_F16)
-    hipLaunchKernelGGL(dequant_rows_f16_kernel, dim3(2048), dim3(256), 0, 0, (const _Float16*)idx->rows, row0, nrows, idx->d, idx->ld, tmp);
-  else
-    hipLaunchKernelGGL(dequant_rows_fp8_kernel, dim3(2048), dim3(256), 0, 0, (const uint8_t*)idx->rows, idx->row_scales, row0, nrows,
-                       idx->d, idx->ld, tmp);
+  (void)dequant_rows_to(idx, row0, nrows, tmp, 0);   // (f16 / fp8: a kernel launch, which reports nothing here)
   hipError_t e = hipMemcpy(out, tmp, cnt * sizeof(float), hipMemcpyDeviceToHost);
   (void)hipFree(tmp);
   if (e != hipSuccess) return fail(SVS_ERR_DEVICE, "dequant read-back: %s", hipGetErrorString(e));

@@ -11,7 +11,8 @@ For every table row:
   a. f64 closeness on what the index really stores (stored_rows, stored_query), at the bounds of
      test_search_within_gpu.py, at m = 2 B + W + 1 (several workgroups, a partial last wave and a partial group of rows),
      m = 1 and m = W - 1 (every clamped lane re-reads list entry m - 1), for one query and for five (a full group of four
-     and a group of one); then rows whose norms span 1e-2 .. 1e2, relative to |row| |q|;
+     and a group of one); then rows whose norms span 1e-2 .. 1e2, relative to |row| |q|; for one geometry per dtype
+     also m = 2 B and 2 B + 1 (the last wave exactly full, and holding one row), bit-equal to a longer list's scores;
   b. one non-zero per listed row: the row at list position p holds one value, at column p mod d; its score is that
      value times the query's, to the bit (f32, f16);
   c. one row copied n times scores with one bit pattern wherever it is listed;
@@ -150,6 +151,48 @@ def test_edges_vs_f64(gpu, case):
     m *= (10.0 ** rng.uniform(-2, 2, n)).astype(np.float32)[:, None]
     qs *= (10.0 ** rng.uniform(-1, 1, BATCH)).astype(np.float32)[:, None]
     _check_f64(rng, m, qs, sizes[:1], case, relative=True)
+
+
+# ---- a'. the last wave of the grid exactly full, and holding exactly one row ---------------------------------------------
+# (rows of 8 chunks, one zero column at the end: the T = 8 kernels of the table's 6-chunk and 8-chunk rows)
+FULL_WAVE_CASES = [(dt, d, "ragged") + next(c[3:5] for c in CASES if c[0] == dt and geometry(c[3]) == (8, 1))
+                   for dt, d in (("f32", 31), ("f16", 63), ("fp8", 127))]
+
+
+@pytest.mark.parametrize("case", FULL_WAVE_CASES, ids=case_id)
+def test_last_wave_full_and_one_row(gpu, case):
+    """A wave's row count is min(m - base, W) (gather.h).  At m = 2 B the last wave of the grid holds exactly W rows and
+    nothing is clamped; at m = 2 B + 1 one more wave holds one row and every other lane of it re-reads that row.  Both
+    against f64, and each listed row's score bit-equal to its score inside a longer list, where it sits at another
+    position of another wave."""
+    dtype, d, _, kernel, _ = case
+    w, b = rows_per_wave(kernel), rows_per_block(kernel)
+    assert geometry(kernel) == (8, 1) and w == 64 and b == 1024       # U = 8: several rows per lane group
+    rng = np.random.default_rng(_seed("fullwave", case_id(case)))
+    sizes = [2 * b + 1, 2 * b]
+    mat, qs = _unit(rng, 3 * sizes[0], d), _unit(rng, BATCH, d)
+    idx = _open(mat, dtype)
+    try:
+        md, qd = _stored(idx, mat, qs)
+        truth = md.astype(np.float64) @ qd.astype(np.float64).T
+        for size in sizes:
+            rows = _scattered(rng, idx.n, size)
+            extra = rng.choice(np.setdiff1d(np.arange(idx.n), rows), w + 3, replace=False)
+            longer = np.sort(np.concatenate([rows, extra])).astype(np.int64)
+            at = np.searchsorted(longer, rows)
+            assert np.count_nonzero(at != np.arange(size)) > size // 2
+            for batch in (qs[:1], qs):
+                nq = len(batch)
+                got = _within(idx, batch, rows, case)
+                err = np.abs(got.astype(np.float64) - truth[rows, :nq].T)
+                print(f"{case_id(case)} m={size} nq={nq}: max |score - f64| = {float(err.max()):.3g}")
+                assert np.all(err <= TOL[dtype]), f"{case_id(case)} m={size} nq={nq}: max |score - f64| = {float(err.max()):.3g}"
+                inside = _within(idx, batch, longer, case)[:, at]
+                odd = np.argwhere(got.view(np.uint32) != inside.view(np.uint32))
+                assert odd.size == 0, (f"{case_id(case)} m={size} nq={nq}: {len(odd)} scores differ in bits from the same rows inside a list "
+                                       f"of {len(longer)}, the first query {odd[0][0]}, list position {odd[0][1]}")
+    finally:
+        idx.release()
 
 
 # ---- b. one non-zero per listed row ------------------------------------------------------------------------------------

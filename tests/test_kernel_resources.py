@@ -297,3 +297,15 @@ def test_gather_kernel_table_rows_have_the_row_length_their_kernels_take():
     # the ragged rows leave lanes past the row for every geometry but T = 1 and 2
     assert sorted(t * nc - choose_ld(d, dtype) // PER16[dtype] for (dtype, t, nc, shape), (_, d, *_) in seen.items()
                   if shape == "ragged" and dtype == "f32") == [0, 0, 1, 2, 4, 8, 24, 24, 32, 32, 104, 120, 192, 192]
+
+
+def test_no_gather_kernel_uses_scratch(build_reports):
+    """Every gather_scores_kernel and gather_segments_kernel instantiation (3 dtypes x 14 row geometries x a lone query /
+    a batch / the tile table: 126) holds its U x NC row chunks in registers: a spill would put scratch reloads between
+    the row loads that keep the HBM busy and the dot loop (gather.h; fp8 pins each chunk's decode for this reason)."""
+    table = _resources(build_reports[0])
+    names = _demangle([n for n in table if "gather_scores_kernel" in n or "gather_segments_kernel" in n])
+    assert len(names) >= 126, len(names)
+    for mangled, pretty in names.items():
+        r = table[mangled]
+        assert r["scratch"] == 0 and r["vgpr_spill"] == 0 and r["sgpr_spill"] == 0, f"{pretty}: {r}"
