@@ -392,6 +392,51 @@ int32_t svs_index_search_above(svs_index* idx, const float* queries, int32_t nq,
                                float* out_scores, int64_t* out_rows /* stride limit */,
                                int32_t* out_counts /* nq */, int64_t* out_totals /* nq, or NULL */);
 
+/* Per-label breakdown: for every label of a set, how many live rows of that label score at or above a cut-off and
+ * which of them is the best, the labels ordered by their best row -- facet counts plus one best hit per facet ("120
+ * hits in manuals, 30 in FAQ, 2 in release notes; here is the best one of each, best source first") in one corpus
+ * pass per query, whatever the number of labels.
+ * Exact definition.  For query q of the call let s be the vector svs_index_scores_n(idx, query q) returns at that
+ * moment (the unscreened single-query score kernel of the index's dtype, the one svs_index_search_above uses), L the
+ * live (not tombstoned) local rows, T = score_key(min_scores[q]) (svs_amd/csrc/keys.h; min_scores == NULL: -inf for
+ * every query), and for each DISTINCT label l of `labels`
+ *   A_l     = { r in L : label[r] == l and score_key(s[r]) >= T }      (an index without a column: label[r] == 0)
+ *   G       = { l : A_l is not empty }
+ *   best(l) = max over r in A_l of make_key(s[r], r)
+ * The comparison is made in KEY space, as in svs_index_search_above: -0.0 and +0.0 are one cut-off; a NaN SCORE
+ * qualifies for every cut-off and sorts first; -inf admits every live row.  Tombstoned rows are excluded by the
+ * dead-row bitmap, never by their score.
+ *   out_groups[q]   = |G|; may be NULL
+ *   out_counts[q]   = min(max(k, 0), |G|)
+ *   out_*[q*k + t], t < out_counts[q]   the labels of G in descending best(l) -- keys are unique because rows are, so
+ *                     the order is total: the top-k order (score desc, row desc) applied to each label's best row.
+ *                     out_labels = l, out_scores = the score bits of the best row (a NaN comes back as the quiet NaN
+ *                     0x7fc00000), out_rows = row_offset + the best row, out_totals = |A_l|, always exact.  Entries
+ *                     past the count are not touched.
+ * A query's result does not depend on nq, on the other queries of the call, or on the order and repeats of `labels`
+ * (sorted and deduplicated on the host, as svs_index_search_labeled does).  Counts are integers and the best row is the
+ * maximum of unique integer keys: the answer is bit-reproducible however the device schedules the work.
+ * Errors: everything is validated before anything is launched, and a failing call writes no output.  d != index d or
+ * an empty index -> SVS_ERR_SHAPE.  SVS_ERR_INVALID: nq < 0, nlabels < 0, null labels with nlabels > 0, null queries
+ * with nq > 0, a NaN in min_scores (the message names the query), null out_counts, null out_labels / out_scores /
+ * out_rows / out_totals with k > 0, nq > 0 and nlabels > 0.  More than SVS_LABELS_MAX_SET DISTINCT labels ->
+ * SVS_ERR_UNSUPPORTED.  k <= 0 is a COUNT-ONLY call: out_groups is computed, every count is 0, the four result pointers
+ * may be NULL.  nq == 0 or nlabels == 0 -> SVS_OK, counts and groups 0, nothing launched.
+ * Each query costs one single-query corpus pass plus two small launches: a reduction over the score vector, the label
+ * column and the bitmap (8 bytes per row) into one count and one best key per label, and one workgroup that ranks
+ * the at most SVS_LABELS_MAX_SET groups.  The host waits once per call.
+ * Blocking; re-entrant on one handle; holds a reference and the geometry lock shared; waits for pending staging
+ * copies; never goes through the coalescer, the run-ahead pipelines or shared passes: all as svs_index_search_above.
+ * Out of scope: svs_multi / row-sharded corpora, a device-pointer variant, more than one row per label, groups that
+ * are not a caller-given set (one group per parent document needs a second column), the batched GEMM and the
+ * screened score routes. */
+int32_t svs_index_search_by_label(svs_index* idx, const float* queries, int32_t nq, int32_t d,
+                                  const uint32_t* labels, int32_t nlabels,
+                                  const float* min_scores /* nq, or NULL: -inf for every query */, int32_t k,
+                                  uint32_t* out_labels, float* out_scores, int64_t* out_rows,
+                                  int64_t* out_totals /* all four: stride k */,
+                                  int32_t* out_counts /* nq */, int32_t* out_groups /* nq, or NULL */);
+
 /* Diverse retrieval: maximal-marginal-relevance (MMR) re-ranking of the fetch_k best rows, on the device -- the answer
  * to "the top 10 are ten versions of one paragraph" in a corpus of chunked documents, overlapping windows and
  * near-copies.

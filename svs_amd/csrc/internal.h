@@ -22,7 +22,9 @@ int32_t svs_internal_coalesce_hold(svs_index* idx, int32_t n);
  *      front of every pass
  *   5  run-ahead pipelines MADE FROM NOW ON: queries one score pass may serve (1 .. SHARE_MAX; 1 = no shared passes)
  *   6  run-ahead pipelines, the grid of a shareable search's own pass: 0 = thin (one resident set of workgroups) where the
- *      host predicts that an earlier pass serves the search (default); 1 = always the one-shot grid; 2 = always thin */
+ *      host predicts that an earlier pass serves the search (default); 1 = always the one-shot grid; 2 = always thin
+ *   7  svs_index_search_by_label, what crosses workgroups (by_label.h): 0 = integer atomics on the query's table in HBM
+ *      (default); 1 = one partial table per workgroup, reduced by the final kernel.  The same bits either way. */
 int32_t svs_internal_tune(int32_t what, int64_t value);
 /* Seconds since the start of the calling thread's last svs_index_search(host batch) at which: [0] scratch was planned,
  * [1] the queries were in pinned memory (and their DMA enqueued), [2] every kernel was enqueued, [3] the stream had
@@ -128,6 +130,10 @@ int64_t svs_internal_live_rows(const int64_t* rows, int64_t nrows, int64_t row_o
 /* Rows per workgroup strip of the label filter (labels.h, LB_STRIP): the sizes at which svs_index_search_labeled's
  * kernels change what they do (tests). */
 int32_t svs_internal_labels_strip(void);
+/* svs_index_search_by_label's reduce kernel (by_label.h): out[0] = rows per strip (BL_STRIP), out[1] = the most
+ * workgroups of a launch (BL_GRID_MAX); an index of more than out[0] * out[1] rows gives a workgroup several strips
+ * (tests). */
+int32_t svs_internal_by_label_geometry(int32_t* out);
 /* multi.hip -> svs_amd.hip: carries a worker thread's error message over to the caller's thread */
 int32_t svs_internal_set_error(int32_t code, const char* msg);
 #ifdef __cplusplus

@@ -42,6 +42,7 @@
 #include "above.h"
 #include "diverse.h"
 #include "labels.h"
+#include "by_label.h"
 
 namespace {
 
@@ -109,7 +110,9 @@ std::atomic<int64_t> g_tune_handover{0};      // run-ahead pipelines made from n
 std::atomic<int64_t> g_tune_share{SHARE_DEFAULT};  // run-ahead pipelines made from now on: queries one score pass may serve (1: its own search only)
 std::atomic<int64_t> g_tune_thin{0};          // run-ahead pipelines, grid of a shareable search's pass: 0 = thin where the host predicts that an earlier pass
                                               // serves the search, 1 = always the one-shot grid, 2 = always thin (tests)
-thread_local double g_host_phase[6];          // svs_internal_host_phases: seconds since the call began (last svs_index_search on this thread)
+std::atomic<int64_t> g_tune_by_label_cross{BL_ATOMIC};  // svs_index_search_by_label, what crosses workgroups: BL_ATOMIC = integer atomics on the query's
+                                              // table in HBM, BL_PARTIALS = a partial table per workgroup, reduced by the final kernel (the same bits)
+thread_local double g_host_phase[6];         // svs_internal_host_phases: seconds since the call began (last svs_index_search on this thread)
 
 // svs_internal_last_launches: the score kernels the calling thread's last search / scores call enqueued, in order: every
 // batched launch (launch_batched), and for the single-query kernels a "gemv" entry per loop (launch_batch,
@@ -253,6 +256,13 @@ struct Ctx {
   PinBuf<uint32_t> lab_set_pin; DevBuf<uint32_t> lab_set_dev;
   DevBuf<uint32_t> lab_cnt;     PinBuf<unsigned long long> lab_tot_pin;
   DevBuf<int64_t> lab_pos;
+  // svs_index_search_by_label (by_label.h): the query's table of BL_TAB_WORDS words, zeroed when allocated and left
+  // zeroed by the final kernel; the workgroups' partial tables (svs_internal_tune(7, 1) only); per query the labels and
+  // totals the device wrote (scores and rows: out_s_pin / out_r_pin), then nq counts followed by nq group counts.  The
+  // set is lab_set_pin / lab_set_dev.
+  DevBuf<unsigned long long> bl_tab;
+  DevBuf<unsigned long long> bl_part_best; DevBuf<uint32_t> bl_part_cnt;
+  PinBuf<uint32_t> bl_lab_pin;  PinBuf<int64_t> bl_tot_pin;   PinBuf<int32_t> bl_cnt_pin;
   // Scratch is reused in stream order.  A context stays with the stream that
   // last used it; handing it to ANOTHER stream first drains the old one.
   hipStream_t last_stream = nullptr;
@@ -3491,6 +3501,113 @@ int32_t svs_index_search_above(svs_index* idx, const float* queries, int32_t nq,
   return SVS_OK;
 }
 
+int32_t svs_internal_by_label_geometry(int32_t* out) {
+  if (!out) return fail(SVS_ERR_INVALID, "null output");
+  out[0] = BL_STRIP;
+  out[1] = BL_GRID_MAX;
+  return SVS_OK;
+}
+
+int32_t svs_index_search_by_label(svs_index* idx, const float* queries, int32_t nq, int32_t d, const uint32_t* labels, int32_t nlabels,
+                                  const float* min_scores, int32_t k, uint32_t* out_labels, float* out_scores, int64_t* out_rows,
+                                  int64_t* out_totals, int32_t* out_counts, int32_t* out_groups) {
+  launch_reset();
+  if (!idx) return fail(SVS_ERR_INVALID, "null index");
+  RefGuard guard(idx);
+  std::shared_lock<std::shared_mutex> geo(idx->rw);   // (set_labels, mask_rows, compact take it exclusively: every query sees one column)
+  int rc = check_query_args(idx, queries, nq, d);
+  if (rc != SVS_OK) return rc;
+  if (nlabels < 0) return fail(SVS_ERR_INVALID, "nlabels must be >= 0");
+  if (nlabels > 0 && !labels) return fail(SVS_ERR_INVALID, "null labels");
+  if (min_scores)
+    for (int32_t q = 0; q < nq; ++q)
+      if (min_scores[q] != min_scores[q]) return fail(SVS_ERR_INVALID, "svs_index_search_by_label: the cut-off of query %d is NaN", (int)q);
+  if (!out_counts) return fail(SVS_ERR_INVALID, "null out_counts");
+  // the set: sorted, without repeats; a label's slot in every table is its index here
+  std::vector<uint32_t> set;
+  try {
+    set.assign(labels, labels + nlabels);
+  } catch (const std::bad_alloc&) {
+    return fail(SVS_ERR_NOMEM, "out of host memory for %d labels", (int)nlabels);
+  }
+  std::sort(set.begin(), set.end());
+  set.erase(std::unique(set.begin(), set.end()), set.end());
+  if (set.size() > (size_t)SVS_LABELS_MAX_SET)
+    return fail(SVS_ERR_UNSUPPORTED, "svs_index_search_by_label: %zu distinct labels; a set holds at most %d", set.size(), SVS_LABELS_MAX_SET);
+  const int nset = (int)set.size();
+  if (k > 0 && nq > 0 && nset > 0 && (!out_labels || !out_scores || !out_rows || !out_totals)) return fail(SVS_ERR_INVALID, "null output");
+  if (nq == 0 || nset == 0) {
+    for (int32_t q = 0; q < nq; ++q) {
+      out_counts[q] = 0;
+      if (out_groups) out_groups[q] = 0;
+    }
+    return SVS_OK;
+  }
+  const int64_t n = idx->n;
+  const int ks = std::min(std::max(k, 0), nset);   // entries a query can have
+  const int cross = (int)g_tune_by_label_cross.load();
+  const unsigned blocks = (unsigned)std::min<int64_t>((n + BL_STRIP - 1) / BL_STRIP, BL_GRID_MAX);
+  HostCall fr(idx);
+  if ((rc = fr.open()) != SVS_OK) return rc;
+  Ctx* const c = fr.c;
+  hipStream_t st = fr.stream();
+  const size_t qn = (size_t)nq * (size_t)d, on = std::max<size_t>((size_t)nq * (size_t)ks, 1);
+  if ((rc = c->out_s_pin.grow(on)) != SVS_OK || (rc = c->out_r_pin.grow(on)) != SVS_OK) return rc;
+  if ((rc = c->bl_lab_pin.grow(on)) != SVS_OK || (rc = c->bl_tot_pin.grow(on)) != SVS_OK || (rc = c->bl_cnt_pin.grow((size_t)nq * 2)) != SVS_OK) return rc;
+  if ((rc = c->scores.grow((size_t)((n + 3) & ~(int64_t)3))) != SVS_OK) return rc;
+  if (nset > 1 && ((rc = c->lab_set_pin.grow((size_t)nset)) != SVS_OK || (rc = c->lab_set_dev.grow((size_t)nset)) != SVS_OK)) return rc;
+  if (cross == BL_PARTIALS) {
+    if ((rc = c->bl_part_best.grow((size_t)blocks * nset)) != SVS_OK || (rc = c->bl_part_cnt.grow((size_t)blocks * nset)) != SVS_OK) return rc;
+  } else if (!c->bl_tab.p) {
+    if ((rc = c->bl_tab.grow(BL_TAB_WORDS)) != SVS_OK) return rc;
+    // zeroed once; by_label_final_kernel leaves it zeroed after every query
+    HIP_TRY(hipMemsetAsync(c->bl_tab, 0, (size_t)BL_TAB_WORDS * sizeof(unsigned long long), st));
+  }
+  const SingleRoute route = single_route(idx, idx->variant.load(), false);   // the kernel svs_index_scores_n runs
+  if ((rc = upload_queries(c, queries, qn, st)) != SVS_OK) return rc;
+  if (nset > 1) {
+    memcpy(c->lab_set_pin, set.data(), (size_t)nset * sizeof(uint32_t));
+    HIP_TRY(hipMemcpyAsync(c->lab_set_dev, c->lab_set_pin, (size_t)nset * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+  }
+  const LabelFilter f = label_filter(idx, set.data(), nset, c->lab_set_dev);
+  // every query back to back: score pass, reduce, final -- the context's one score vector and one table are reused in
+  // stream order; no host wait in between
+  for (int32_t q = 0; q < nq; ++q) {
+    const uint32_t tkey = score_key(min_scores ? min_scores[q] : -std::numeric_limits<float>::infinity());
+    launch_record("gemv", n, 1);
+    if ((rc = launch_scores(idx, c, route, c->q_dev + (size_t)q * d, c->scores, st)) != SVS_OK) return rc;
+    launch_record("by_label_reduce_kernel", n, 1);
+    if (cross == BL_PARTIALS)
+      hipLaunchKernelGGL(by_label_reduce_kernel<BL_PARTIALS>, dim3(blocks), dim3(BL_THREADS), 0, st, f, (const float*)c->scores.p, tkey,
+                         (unsigned long long*)nullptr, c->bl_part_best.p, c->bl_part_cnt.p);
+    else
+      hipLaunchKernelGGL(by_label_reduce_kernel<BL_ATOMIC>, dim3(blocks), dim3(BL_THREADS), 0, st, f, (const float*)c->scores.p, tkey,
+                         c->bl_tab.p, (unsigned long long*)nullptr, (uint32_t*)nullptr);
+    hipLaunchKernelGGL(by_label_final_kernel, dim3(1), dim3(BL_FINAL_THREADS), 0, st, c->bl_tab.p, (const unsigned long long*)c->bl_part_best.p,
+                       (const uint32_t*)c->bl_part_cnt.p, cross == BL_PARTIALS ? (int)blocks : 0, (const uint32_t*)c->lab_set_dev.p, f.single, nset,
+                       k, idx->row_offset, c->bl_lab_pin + (size_t)q * ks, c->out_s_pin + (size_t)q * ks, c->out_r_pin + (size_t)q * ks,
+                       c->bl_tot_pin + (size_t)q * ks, c->bl_cnt_pin + q, c->bl_cnt_pin + nq + q);
+  }
+  if ((rc = fr.close("search_by_label")) != SVS_OK) return rc;
+  for (int32_t q = 0; q < nq; ++q) {
+    const int count = c->bl_cnt_pin[q], groups = c->bl_cnt_pin[nq + q];
+    if (count < 0 || count > ks || groups < count || groups > nset)
+      return fail(SVS_ERR_DEVICE, "search_by_label: query %d came back with %d entries of %d groups (%d labels)", (int)q, count, groups, nset);
+  }
+  for (int32_t q = 0; q < nq; ++q) {
+    const size_t count = (size_t)c->bl_cnt_pin[q], from = (size_t)q * ks, to = (size_t)q * k;
+    if (count) {
+      memcpy(out_labels + to, c->bl_lab_pin + from, count * sizeof(uint32_t));
+      memcpy(out_scores + to, c->out_s_pin + from, count * sizeof(float));
+      memcpy(out_rows + to, c->out_r_pin + from, count * sizeof(int64_t));
+      memcpy(out_totals + to, c->bl_tot_pin + from, count * sizeof(int64_t));
+    }
+    out_counts[q] = (int32_t)count;
+    if (out_groups) out_groups[q] = c->bl_cnt_pin[nq + q];
+  }
+  return SVS_OK;
+}
+
 // The similarity matrices of one block of queries: 64 MiB, i.e. 16 queries at fetch_k = SVS_DIVERSE_MAX_FETCH (4 MiB each)
 // and every query of most calls at the usual 32-256 candidates; a block costs two launches and no host wait.
 constexpr size_t DIVERSE_G_BUDGET = (size_t)64 << 20;
@@ -3956,6 +4073,7 @@ int32_t svs_internal_tune(int32_t what, int64_t value) {
     case 4: if (value < 0 || value > 1) break; g_tune_handover.store(value); return SVS_OK;
     case 5: if (value < 1 || value > SHARE_MAX) break; g_tune_share.store(value); return SVS_OK;
     case 6: if (value < 0 || value > 2) break; g_tune_thin.store(value); return SVS_OK;
+    case 7: if (value != BL_ATOMIC && value != BL_PARTIALS) break; g_tune_by_label_cross.store(value); return SVS_OK;
     default: break;
   }
   return fail(SVS_ERR_INVALID, "svs_internal_tune(%d, %lld): unknown knob or value", what, (long long)value);

@@ -447,6 +447,56 @@ class DeviceIndex:
         s, r, matched = self.search_batch_labeled(q[None, :], n, labels)
         return list(zip(s[0].astype(np.float64).tolist(), r[0].tolist())), matched
 
+    def search_batch_by_label(self, queries: np.ndarray, labels, min_scores=None,
+                              n: Optional[int] = None) -> List[Tuple[np.ndarray, np.ndarray, np.ndarray, np.ndarray, int]]:
+        """Per-label breakdown (svs_index_search_by_label): for each row of ``queries`` (nq, D) and every label of
+        ``labels`` (any order, repeats allowed, at most LABELS_MAX_SET distinct ones) the number of live rows of that
+        label scoring at or above ``min_scores[q]`` (None: every live row; compared in key space as in
+        ``search_batch_above``) and the best of them.  Returns one ``(labels u32, scores f32, rows i64, totals i64,
+        groups)`` per query: the labels that have a qualifying row ordered by their best row (score desc, row desc), at
+        most ``n`` of them (None: every label of the set; 0: only ``groups``); groups = how many labels have one.
+        A NaN cut-off is a ValueError."""
+        assert n is None or isinstance(n, int)
+        q = self._queries_2d(queries)
+        nq, d = q.shape
+        lab = labels_u32(labels)
+        cut = None
+        if min_scores is not None:
+            cut = np.ascontiguousarray(min_scores, dtype=np.float32).reshape(-1)
+            if len(cut) != nq:
+                raise ValueError(f"min_scores has {len(cut)} entries for {nq} queries")
+            if np.isnan(cut).any():
+                raise ValueError(f"the cut-off of query {int(np.argmax(np.isnan(cut)))} is NaN")
+        # (clamped before allocating and before the int32 argument: a query has at most one entry per label given)
+        k = len(lab) if n is None else min(max(n, 0), len(lab))
+        out_l = np.empty((nq, k), dtype=np.uint32)
+        out_s = np.empty((nq, k), dtype=np.float32)
+        out_r = np.empty((nq, k), dtype=np.int64)
+        out_t = np.empty((nq, k), dtype=np.int64)
+        counts = np.zeros(nq, dtype=np.int32)
+        groups = np.zeros(nq, dtype=np.int32)
+        h = self._pinned_handle()
+        try:
+            # (the one call that releases the GIL; a count-only call passes no result buffers)
+            _native.check(self._lib.svs_index_search_by_label(h, q.ctypes.data, nq, d, lab.ctypes.data, len(lab),
+                                                              None if cut is None else cut.ctypes.data, k,
+                                                              out_l.ctypes.data if k else None, out_s.ctypes.data if k else None,
+                                                              out_r.ctypes.data if k else None, out_t.ctypes.data if k else None,
+                                                              counts.ctypes.data, groups.ctypes.data))
+        finally:
+            self._unpin(h)
+        return [(out_l[i, :c], out_s[i, :c], out_r[i, :c], out_t[i, :c], g) for i, (c, g) in enumerate(zip(counts.tolist(), groups.tolist()))]
+
+    def search_by_label(self, query_vec: np.ndarray, labels, min_score: Optional[float] = None,
+                        n: Optional[int] = None) -> List[Tuple[int, float, int, int]]:
+        """The breakdown of one query over ``labels``: [(label, score of its best row, that row, rows of the label at or
+        above ``min_score``)], best label first; labels without such a row are absent.  See ``search_batch_by_label``."""
+        q = np.asarray(query_vec, dtype=np.float32)
+        if q.ndim != 1:
+            raise ValueError(f"query must be 1-D, got shape {q.shape}")
+        l, s, r, t, _ = self.search_batch_by_label(q[None, :], labels, None if min_score is None else [min_score], n)[0]
+        return list(zip(l.tolist(), s.astype(np.float64).tolist(), r.tolist(), t.tolist()))
+
     @staticmethod
     def diverse_fetch(n: int, fetch_k: Optional[int] = None) -> int:
         """How many candidates a diverse search of ``n`` results re-ranks: ``fetch_k``, or by default

@@ -30,7 +30,7 @@ from typing import Any, Awaitable, Callable, Dict, Iterator, List, Optional, Tup
 import numpy as np
 
 from .index import LABELS_MAX_SET, DeviceIndex
-from .matrix import (DeviceEmbeddingsMatrix, above_op, batch_op, diverse_op, labeled_op, neighbors_op, pairs_op, segments_op, single_op,
+from .matrix import (DeviceEmbeddingsMatrix, above_op, batch_op, by_label_op, diverse_op, labeled_op, neighbors_op, pairs_op, segments_op, single_op,
                      within_op)
 
 _LOG = logging.getLogger(__name__)
@@ -204,6 +204,11 @@ class _Store:
         pairs = np.array(rows, dtype=np.int64).reshape(-1, 2)
         return pairs[:, 0].copy(), (pairs[:, 1] + 1).astype(np.uint32)
 
+    def embedded_levels(self) -> List[int]:
+        """The distinct levels of the docs that have an embedding, ascending, in one statement
+        (``retrieve_by_level`` with ``levels=None``)."""
+        return [int(r[0]) for r in self.conn.execute("SELECT DISTINCT level FROM docs WHERE embedding IS NOT NULL ORDER BY level")]
+
     def embedding_of_doc(self, doc_id: int) -> int:
         """The embedding id of one doc (``retrieve_similar``): KeyError(doc_id) for an unknown doc, like the
         reference's fetch_doc; ValueError for a doc that was added without an embedding."""
@@ -363,6 +368,22 @@ def _fetch_diverse(db: _Store, picks: List[Tuple[float, int, float]]) -> List[Di
     one SQL statement; call it in a transaction."""
     docs = db.fetch_docs_for_embeddings([e for _, e, _ in picks])
     return [{"score": s, "doc": docs[e], "redundancy": r} for s, e, r in picks]
+
+
+def _fetch_by_level(db: _Store, groups: List[Tuple[int, float, int, int]]) -> List[Dict[str, Any]]:
+    """[(label, score, emb id, count)], best label first -> [{'level', 'count', 'score', 'doc'}] (the label of a level
+    is ``level + 1``), the docs fetched with one SQL statement; call it in a transaction."""
+    docs = db.fetch_docs_for_embeddings([e for _, _, e, _ in groups])
+    return [{"level": label - 1, "count": count, "score": s, "doc": docs[e]} for label, s, e, count in groups]
+
+
+def _by_level_cut(min_score: Optional[float]) -> Optional[float]:
+    """The cut-off of ``retrieve_by_level`` as a float (None: every document); ValueError for a NaN."""
+    if min_score is None:
+        return None
+    if min_score != min_score:
+        raise ValueError("min_score is NaN")
+    return float(min_score)
 
 
 def _level_labels(levels) -> List[int]:
@@ -584,6 +605,37 @@ class KB:
         with self.db.transaction():
             res = _fetch_list(self.db, emb_ids)
         _LOG.info(f"retrieved top {n} documents")
+        return res
+
+    def retrieve_by_level(self, query: str, min_score: Optional[float] = None, levels=None) -> List[Dict[str, Any]]:
+        """The breakdown of one query over the levels of the tree: for every level that has a document scoring at or
+        above ``min_score`` (None: any document) the best such document and how many there are --
+        [{'level': int, 'count': int, 'score': float, 'doc': DocumentRecord}], best level first.  ``levels``: an int or
+        an iterable of ints as in ``retrieve_at_level``; None: every level present in the store.  One corpus pass on
+        the device whatever the number of levels (svs_index_search_by_label) over the label column
+        ``retrieve_at_level`` uses; a level nobody has, or none of whose documents reaches the cut-off, is absent.  A
+        NaN cut-off, a negative level, or more than 1,024 distinct levels raises ValueError."""
+        cut = _by_level_cut(min_score)
+        labels = None if levels is None else _level_labels(levels)
+        _LOG.info(f"retrieving the best document of {'every level' if labels is None else f'{len(labels)} levels'} with query string: {query}")
+        assert self.db is not None
+        self.embeddings_matrix.get_sync(self.db)
+
+        def levels_from_store():
+            with self.db.transaction():
+                return self.db.embedding_levels()
+
+        self.embeddings_matrix.ensure_labels(levels_from_store)
+        if labels is None:
+            with self.db.transaction():
+                labels = _level_labels(self.db.embedded_levels())
+        query_vec = np.array(self._embed([query])[0], dtype=np.float32)
+        _LOG.info("got embedding for query!")
+        groups = self.embeddings_matrix.search_by_label(query_vec, labels, cut) if labels else []   # one pass + reduction: HIP
+        _LOG.info(f"computed {self.embeddings_matrix.index.shape[0]} cosine similarities")
+        with self.db.transaction():
+            res = _fetch_by_level(self.db, groups)
+        _LOG.info(f"retrieved the best documents of {len(res)} levels")
         return res
 
     def retrieve_diverse(self, query: str, n: int, fetch_n: Optional[int] = None, diversity: float = 0.5) -> List[Dict[str, Any]]:
@@ -925,6 +977,28 @@ class AsyncKB:
             _LOG.info(f"computed {matched} cosine similarities")
         res = await self._fetch(lambda db: _fetch_list(db, emb_ids))
         _LOG.info(f"retrieved top {n} documents")
+        return res
+
+    async def retrieve_by_level(self, query: str, min_score: Optional[float] = None, levels=None) -> List[Dict[str, Any]]:
+        """Async twin of ``KB.retrieve_by_level``, structured as ``retrieve``: the label column is installed (when this
+        index generation has none yet), the levels of the store are read (``levels=None``) and the reference to the
+        matrix is taken under the lock, the breakdown runs on an executor thread outside it, the docs are fetched
+        under the lock."""
+        cut = _by_level_cut(min_score)
+        given = None if levels is None else _level_labels(levels)
+        _LOG.info(f"retrieving the best document of {'every level' if given is None else f'{len(given)} levels'} with query string: {query}")
+
+        def prepare(db):
+            self.embeddings_matrix.ensure_labels(db.embedding_levels)
+            return given if given is not None else _level_labels(db.embedded_levels())
+
+        async with self._held(prepare) as (held, labels):
+            query_vec = np.array((await self._embed([query]))[0], dtype=np.float32)
+            _LOG.info("got embedding for query!")
+            groups = await self._search(held, by_label_op(query_vec, labels, cut)) if labels else []
+            _LOG.info(f"computed {held[0].shape[0]} cosine similarities")
+        res = await self._fetch(lambda db: _fetch_by_level(db, groups))
+        _LOG.info(f"retrieved the best documents of {len(res)} levels")
         return res
 
     async def retrieve_diverse(self, query: str, n: int, fetch_n: Optional[int] = None,

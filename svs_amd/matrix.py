@@ -200,6 +200,21 @@ def labeled_op(query_vec: np.ndarray, n: int, labels):
     return native, finish
 
 
+def by_label_op(query_vec: np.ndarray, labels, min_score: Optional[float] = None, n: Optional[int] = None):
+    """Per-label breakdown: ``idx.search_by_label`` (svs_index_search_by_label) over ``labels``, rows -> ids:
+    [(label, score, emb_id of the label's best row, rows of the label at or above ``min_score``)], best label first.
+    The column is whatever the index holds (``DeviceEmbeddingsMatrix.ensure_labels``)."""
+    def native(idx, lookup, *_):
+        return idx, idx.search_by_label(query_vec, labels, min_score, n)
+
+    def finish(res, arr):
+        used, groups = res
+        off = int(getattr(used, "row_offset", 0))
+        return [(int(label), score, int(arr[row - off]), int(total)) for label, score, row, total in groups]
+
+    return native, finish
+
+
 def diverse_op(query_vec: np.ndarray, n: int, fetch_k: Optional[int] = None, lam: float = 0.5):
     """Diverse (MMR) search: ``idx.search_diverse`` (svs_index_search_diverse), rows -> ids:
     [(score, emb_id, redundancy)] in pick order."""
@@ -516,6 +531,13 @@ class DeviceEmbeddingsMatrix:
         """``search`` over the stored embeddings whose label is in ``labels``: ([(score, emb_id)], how many carry
         such a label) (``KB.retrieve_at_level``).  Call ``ensure_labels`` first."""
         return self.run_mapped(labeled_op(query_vec, n, labels))
+
+    def search_by_label(self, query_vec: np.ndarray, labels, min_score: Optional[float] = None,
+                        n: Optional[int] = None) -> List[Tuple[int, float, int, int]]:
+        """The breakdown of one query over ``labels``: [(label, score, emb_id of the label's best embedding, how many
+        of the label score at or above ``min_score``)], best label first (``KB.retrieve_by_level``).  Call
+        ``ensure_labels`` first."""
+        return self.run_mapped(by_label_op(query_vec, labels, min_score, n))
 
     def search_diverse(self, query_vec: np.ndarray, n: int, fetch_k: Optional[int] = None,
                        lam: float = 0.5) -> List[Tuple[float, int, float]]:

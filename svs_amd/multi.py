@@ -214,6 +214,11 @@ class MultiDeviceIndex:
 
     search_batch_labeled = search_labeled
 
+    def search_by_label(self, query_vec: np.ndarray, labels, min_score: Optional[float] = None, n: Optional[int] = None):
+        raise NotImplementedError("the per-label breakdown is per device: the label column sits beside one shard's rows; call set_labels / search_by_label on a DeviceIndex")
+
+    search_batch_by_label = search_by_label
+
     def set_labels(self, labels, row0: Optional[int] = None):
         raise NotImplementedError("labels are per device: call set_labels on a DeviceIndex")
 

@@ -210,6 +210,11 @@ class ShardedIndex:
 
     search_batch_labeled = search_labeled
 
+    def search_by_label(self, query_vec: np.ndarray, labels, min_score=None, n=None):
+        raise NotImplementedError("the per-label breakdown is per device: a rank labels and searches its own shard (DeviceIndex.search_by_label); nothing is merged across ranks")
+
+    search_batch_by_label = search_by_label
+
     # ---- pipelined single-query searches (device path; what bench.py times) ----------------
     def open(self, capacity: int, k: int) -> None:
         """Buffers for up to ``capacity`` enqueued single-query searches of top-``k``."""
