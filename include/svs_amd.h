@@ -437,6 +437,54 @@ int32_t svs_index_search_by_label(svs_index* idx, const float* queries, int32_t 
                                   int64_t* out_totals /* all four: stride k */,
                                   int32_t* out_counts /* nq */, int32_t* out_groups /* nq, or NULL */);
 
+/* Nearest-vector assignment: for every stored row of a range, which of c given vectors it scores best against -- the
+ * transposed question of a search ("which topic is each document about", the assignment step of a clustering, coarse
+ * centroids for probing), answered where the corpus lies; optionally the answer is written into the label column, so
+ * that svs_index_search_labeled and svs_index_search_by_label then work per topic or cluster.
+ * Exact definition.
+ *   Vectors as stored.  V[j] is vector j as a stored row of an index of this handle's dtype -- what
+ *     svs_index_debug_query returns for it: f32 unchanged, f16 rounded to half, fp8 e4m3 with its own scale.  The
+ *     vectors go through the rows' ingest and quantisation kernels.  Nothing requires unit norm.
+ *   Score of a pair.  For local row r and position j, A[r][j] = the dot product of the STORED values of row r and of
+ *     V[j], f32 products accumulated in f32 over the columns in ascending order as ONE fmaf chain per element; fp8 sums
+ *     the e4m3 values and multiplies by (scale_r * scale_j) once, after the sum (svs_index_search_diverse's rule for G).
+ *     A[r][j] depends only on the row's stored values, the vector's stored values and d -- not on c, j, the range,
+ *     tiles or scheduling.
+ *   Best position.  best[r] = the j that maximises score_key(A[r][j]) (svs_amd/csrc/keys.h); an exact tie in key space
+ *     goes to the LOWER j; -0.0 and +0.0 are one value; a NaN score has the largest key, as in every search.
+ *   Per-row outputs, for every row of [row0, row0 + nrows) (GLOBAL rows), live or tombstoned, at i = row - row0:
+ *     out_best[i] = best, out_scores[i] = key_score(score_key(A[r][best])): the score's bits, -0.0 reported as +0.0, a
+ *     NaN as the quiet NaN 0x7fc00000.  Either may be NULL.
+ *   Counts.  out_counts[j] = the number of LIVE rows of the range with best == j; the dead-row bitmap decides, never the
+ *     score; the counts sum to the live rows of the range.  May be NULL.
+ *   Label column.  With vector_labels != NULL, label[r] = vector_labels[best[r]] for every row of the range, tombstoned
+ *     rows included (as svs_index_set_labels may label them); labels outside the range are untouched.  The first such
+ *     call allocates the zero-filled column exactly as svs_index_set_labels does (counted in hbm_bytes; no memory ->
+ *     SVS_ERR_NOMEM, handle untouched).  With vector_labels == NULL the column is neither read, written nor allocated.
+ * Scores are single chains, the arg-max is over unique integer keys and the counts are integers: the answer is
+ * bit-reproducible however the device schedules the work.
+ * Errors: everything is validated before anything is launched; a failing call writes no output and allocates no
+ * column.  d != index d or an empty index -> SVS_ERR_SHAPE.  SVS_ERR_INVALID: c <= 0, nrows < 0, null vectors, a range
+ * not inside [row_offset, row_offset + n).  c > SVS_ASSIGN_MAX_VECTORS -> SVS_ERR_UNSUPPORTED.  nrows == 0 -> SVS_OK,
+ * out_counts zeroed if given, nothing launched, no column.  All three outputs NULL and vector_labels == NULL -> SVS_OK,
+ * nothing launched.
+ * Cost: the c vectors are ingested into a device image of at most 1024 rows (it stays in cache), then ONE kernel
+ * streams the range's rows past it (exact f32 MFMA, svs_amd/csrc/assign.h): the rows are read once per 256 vectors (once
+ * in all for c <= 256), 2 nrows ld max(c, 64) FLOP; 8 bytes per row come back.
+ * Blocking; re-entrant on one handle; holds a reference; waits for pending staging copies; never goes through the
+ * coalescer, the run-ahead pipelines or shared passes.  With vector_labels == NULL it holds the geometry lock shared,
+ * like a search.  With vector_labels != NULL it holds the geometry lock EXCLUSIVELY for the whole call, as
+ * svs_index_set_labels does: searches, appends and other writers on the handle wait that long.
+ * Out of scope: svs_multi / row-sharded corpora, a device-pointer variant, more than one position per row (soft
+ * assignment), more than SVS_ASSIGN_MAX_VECTORS vectors, per-label sums or means on the device (the update step of
+ * k-means: the natural follow-up), a second label column. */
+#define SVS_ASSIGN_MAX_VECTORS 1024   /* = SVS_LABELS_MAX_SET: every label an assignment writes can be named in one labelled call */
+int32_t svs_index_assign(svs_index* idx, const float* vectors /* host, f32, C-contiguous (c, d) */, int32_t c, int32_t d,
+                         int64_t row0 /* GLOBAL */, int64_t nrows,
+                         const uint32_t* vector_labels /* c, or NULL: the label column is not touched */,
+                         int32_t* out_best /* nrows, or NULL */, float* out_scores /* nrows, or NULL */,
+                         int64_t* out_counts /* c, or NULL */);
+
 /* Diverse retrieval: maximal-marginal-relevance (MMR) re-ranking of the fetch_k best rows, on the device -- the answer
  * to "the top 10 are ten versions of one paragraph" in a corpus of chunked documents, overlapping windows and
  * near-copies.

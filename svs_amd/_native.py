@@ -91,6 +91,7 @@ SIGNATURES = {
                                              C.POINTER(C.c_int64)]),
     "svs_index_search_above": (C.c_int32, [_P, _P, C.c_int32, C.c_int32, _P, C.c_int32, _P, _P, _P, _P]),
     "svs_index_search_by_label": (C.c_int32, [_P, _P, C.c_int32, C.c_int32, _P, C.c_int32, _P, C.c_int32, _P, _P, _P, _P, _P, _P]),
+    "svs_index_assign": (C.c_int32, [_P, _P, C.c_int32, C.c_int32, C.c_int64, C.c_int64, _P, _P, _P, _P]),
     "svs_index_search_diverse": (C.c_int32, [_P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_float, _P, _P, _P,
                                              C.POINTER(C.c_int32)]),
     "svs_index_neighbors": (C.c_int32, [_P, _P, C.c_int64, C.c_int32, _P, _P, C.POINTER(C.c_int32)]),
@@ -125,6 +126,7 @@ INTERNAL = {
     "svs_internal_live_rows": (C.c_int64, [_P, C.c_int64, C.c_int64, C.c_int64, _P, _P, C.c_int64]),
     "svs_internal_labels_strip": (C.c_int32, []),
     "svs_internal_by_label_geometry": (C.c_int32, [C.POINTER(C.c_int32)]),
+    "svs_internal_assign_kernel_ms": (C.c_int32, [C.POINTER(C.c_double)]),
     "svs_internal_compact": (C.c_int32, [_P, C.c_int64, _P, C.c_int64, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
 }
 

@@ -43,6 +43,7 @@
 #include "diverse.h"
 #include "labels.h"
 #include "by_label.h"
+#include "assign.h"
 
 namespace {
 
@@ -263,6 +264,13 @@ struct Ctx {
   DevBuf<unsigned long long> bl_tab;
   DevBuf<unsigned long long> bl_part_best; DevBuf<uint32_t> bl_part_cnt;
   PinBuf<uint32_t> bl_lab_pin;  PinBuf<int64_t> bl_tot_pin;   PinBuf<int32_t> bl_cnt_pin;
+  // svs_index_assign (assign.h): the call's vectors in the index's storage format (rows of ld elements; fp8: their
+  // scales), the per-row results, the counts and the vectors' labels.  The f32 vectors go up through q_pin / q_dev, the
+  // labels through lab_set_pin.
+  DevBuf<uint8_t> as_vec;       DevBuf<float> as_vec_scales;
+  DevBuf<int32_t> as_best;      DevBuf<float> as_score;
+  DevBuf<unsigned long long> as_cnt;
+  DevBuf<uint32_t> as_lab;
   // Scratch is reused in stream order.  A context stays with the stream that
   // last used it; handing it to ANOTHER stream first drains the old one.
   hipStream_t last_stream = nullptr;
@@ -1943,24 +1951,30 @@ int check_query_args(const svs_index* idx, const void* q, int nq, int d) {
 // f32 corpus: a copy of `kind` (the source is device or pinned memory) that writes the d floats of every row; the
 // columns of padded rows beyond d are the caller's to zero.  f16 / fp8 corpus: the source is on the device and a kernel
 // of `blocks` workgroups converts it.
-hipError_t ingest_rows(svs_index* idx, const float* src, int64_t nrows, int64_t src_ld, int64_t row0, hipMemcpyKind kind,
-                       unsigned blocks, hipStream_t st) {
+// ... into rows [row0, row0 + nrows) of ANY image of the index's layout: `rows` (stride idx->ld elements) and, fp8, `scales`
+// (the corpus itself; svs_index_assign's image of its vectors)
+hipError_t ingest_rows_into(const svs_index* idx, void* rows, float* scales, const float* src, int64_t nrows, int64_t src_ld, int64_t row0,
+                            hipMemcpyKind kind, unsigned blocks, hipStream_t st) {
   const int d = idx->d;
   if (idx->dtype == SVS_DTYPE_F16) {
     hipLaunchKernelGGL(convert_rows_f16_kernel, dim3(blocks), dim3(256), 0, st, src, nrows, d, src_ld,
-                       (_Float16*)idx->rows + (size_t)row0 * idx->ld, idx->ld);
+                       (_Float16*)rows + (size_t)row0 * idx->ld, idx->ld);
     return hipGetLastError();
   }
   if (idx->dtype == SVS_DTYPE_FP8) {
     hipLaunchKernelGGL(quantize_rows_fp8_kernel, dim3(blocks), dim3(256), 0, st, src, nrows, d, src_ld,
-                       (uint8_t*)idx->rows + (size_t)row0 * idx->ld, idx->ld, idx->row_scales + row0, (float*)nullptr);
+                       (uint8_t*)rows + (size_t)row0 * idx->ld, idx->ld, scales + row0, (float*)nullptr);
     return hipGetLastError();
   }
-  float* dst = (float*)idx->rows + (size_t)row0 * idx->ld;
+  float* dst = (float*)rows + (size_t)row0 * idx->ld;
   if (kind == hipMemcpyHostToDevice && idx->ld == d && src_ld == d)
     return hipMemcpyAsync(dst, src, (size_t)nrows * d * sizeof(float), kind, st);
   return hipMemcpy2DAsync(dst, (size_t)idx->ld * sizeof(float), src, (size_t)src_ld * sizeof(float), (size_t)d * sizeof(float),
                           (size_t)nrows, kind, st);
+}
+hipError_t ingest_rows(svs_index* idx, const float* src, int64_t nrows, int64_t src_ld, int64_t row0, hipMemcpyKind kind,
+                       unsigned blocks, hipStream_t st) {
+  return ingest_rows_into(idx, idx->rows, idx->row_scales, src, nrows, src_ld, row0, kind, blocks, st);
 }
 
 // Host rows [0, nrows) (f32, C-contiguous, d floats each) -> HBM rows [row0, row0+nrows).
@@ -2584,6 +2598,20 @@ int upload_queries(Ctx* c, const float* queries, size_t qn, hipStream_t st) {
   memcpy(c->q_pin, queries, qn * sizeof(float));
   HIP_TRY(hipMemcpyAsync(c->q_dev, c->q_pin, qn * sizeof(float), hipMemcpyHostToDevice, st));
   return SVS_OK;
+}
+
+// ---- svs_index_assign (assign.h)
+thread_local double g_assign_kernel_ms = -1.0;   // svs_internal_assign_kernel_ms
+
+// accumulators per wave: one sweep of 64 vectors covers a small c, 256 per sweep beyond
+template <int DT, int NA>
+void launch_assign_na(const svs_index* idx, const Ctx* cx, int c, int64_t r0, int64_t nrows, const uint32_t* vec_labels, int32_t* best,
+                             float* scores, uint32_t* labels, unsigned long long* counts, hipStream_t st) {
+  const int ld16 = (int)((size_t)idx->ld * elem_bytes(idx) / 16);
+  const unsigned blocks = (unsigned)std::min<int64_t>((nrows + AS_ROWS - 1) / AS_ROWS, AS_GRID_MAX);
+  hipLaunchKernelGGL((assign_rows_kernel<DT, NA>), dim3(blocks), dim3(AS_THREADS), 0, st, (const u32x4*)idx->rows, ld16,
+                     (const float*)idx->row_scales, idx->n, (const u32x4*)cx->as_vec.p, (const float*)cx->as_vec_scales.p, c, r0, nrows,
+                     (const uint32_t*)(idx->dead_list.empty() ? nullptr : idx->dead_bits_dev.p), vec_labels, best, scores, labels, counts);
 }
 
 }  // namespace
@@ -3294,6 +3322,22 @@ static int label_range(const svs_index* idx, const char* entry, int64_t row0, in
   return SVS_OK;
 }
 
+// The first write of the label column (under the exclusive geometry lock): a zero column for the row CAPACITY
+static int label_column_ensure(svs_index* idx, const char* entry) {
+  if (idx->labels) return SVS_OK;
+  const size_t bytes = label_column_bytes(std::max(idx->cap, idx->n));
+  uint32_t* col = nullptr;
+  HIP_TRY(hipMalloc((void**)&col, bytes));
+  const hipError_t e = hipMemset(col, 0, bytes);
+  if (e != hipSuccess) {
+    (void)hipFree(col);
+    return fail(SVS_ERR_DEVICE, "%s: %s", entry, hipGetErrorString(e));
+  }
+  idx->labels = col;
+  idx->labels_bytes = bytes;
+  return SVS_OK;
+}
+
 int32_t svs_index_set_labels(svs_index* idx, int64_t row0, int64_t nrows, const uint32_t* labels) {
   if (!idx) return fail(SVS_ERR_INVALID, "null index");
   RefGuard guard(idx);
@@ -3305,20 +3349,11 @@ int32_t svs_index_set_labels(svs_index* idx, int64_t row0, int64_t nrows, const 
   if (rc != SVS_OK) return rc;
   if (!labels) return fail(SVS_ERR_INVALID, "null labels");
   HIP_TRY(hipSetDevice(idx->device));
-  if (!idx->labels) {   // the first call: a zero column for the row CAPACITY
-    const size_t bytes = label_column_bytes(std::max(idx->cap, idx->n));
-    uint32_t* col = nullptr;
-    HIP_TRY(hipMalloc((void**)&col, bytes));
-    const hipError_t e = hipMemset(col, 0, bytes);
-    if (e != hipSuccess) {
-      (void)hipFree(col);
-      return fail(SVS_ERR_DEVICE, "svs_index_set_labels: %s", hipGetErrorString(e));
-    }
-    idx->labels = col;
-    idx->labels_bytes = bytes;
-  }
-  // (only svs_index_search_labeled and svs_index_get_labels read the column, blocking and under the shared lock: nothing
-  //  enqueued can be reading it now)
+  if ((rc = label_column_ensure(idx, "svs_index_set_labels")) != SVS_OK) return rc;
+  // (svs_index_search_labeled, svs_index_search_by_label and svs_index_get_labels read the column, blocking and under the
+  //  shared lock; svs_index_assign with vector_labels is the one other writer, blocking and under the exclusive lock like
+  //  this call; reserve, append and compact carry the column along under the exclusive lock too: nothing enqueued can be
+  //  reading or writing it now)
   HIP_TRY(hipMemcpy(idx->labels + r0, labels, (size_t)nrows * sizeof(uint32_t), hipMemcpyHostToDevice));
   return SVS_OK;
 }
@@ -3605,6 +3640,101 @@ int32_t svs_index_search_by_label(svs_index* idx, const float* queries, int32_t 
     out_counts[q] = (int32_t)count;
     if (out_groups) out_groups[q] = c->bl_cnt_pin[nq + q];
   }
+  return SVS_OK;
+}
+
+static_assert(SVS_ASSIGN_MAX_VECTORS == AS_MAX_VECTORS, "the assign kernel's LDS count table holds SVS_ASSIGN_MAX_VECTORS slots");
+static_assert(SVS_ASSIGN_MAX_VECTORS == SVS_LABELS_MAX_SET, "every label an assignment writes can be named in one labelled call");
+
+int32_t svs_index_assign(svs_index* idx, const float* vectors, int32_t c, int32_t d, int64_t row0, int64_t nrows,
+                         const uint32_t* vector_labels, int32_t* out_best, float* out_scores, int64_t* out_counts) {
+  launch_reset();
+  if (!idx) return fail(SVS_ERR_INVALID, "null index");
+  RefGuard guard(idx);
+  // with labels to write: exclusive for the whole call, as svs_index_set_labels (no labelled search is between its count
+  // and its write); without: a reader like every search
+  std::shared_lock<std::shared_mutex> geo_shared(idx->rw, std::defer_lock);
+  std::unique_lock<std::shared_mutex> geo_excl(idx->rw, std::defer_lock);
+  if (vector_labels) geo_excl.lock();
+  else geo_shared.lock();
+  // ---- everything is validated before anything is written, allocated or launched
+  if (d != idx->d || idx->n == 0 || idx->d == 0)
+    return fail(SVS_ERR_SHAPE, "shapes (%lld,%d) and (%d,) not aligned: %d (dim 1) != %d (dim 0)", (long long)idx->n, idx->d, d, idx->d, d);
+  if (c <= 0) return fail(SVS_ERR_INVALID, "svs_index_assign: c must be >= 1, got %d", (int)c);
+  if (nrows < 0) return fail(SVS_ERR_INVALID, "nrows must be >= 0");
+  if (!vectors) return fail(SVS_ERR_INVALID, "null vectors");
+  if (c > SVS_ASSIGN_MAX_VECTORS)
+    return fail(SVS_ERR_UNSUPPORTED, "svs_index_assign: %d vectors; a call takes at most %d", (int)c, SVS_ASSIGN_MAX_VECTORS);
+  if (nrows == 0) {
+    if (out_counts) memset(out_counts, 0, (size_t)c * sizeof(int64_t));
+    return SVS_OK;
+  }
+  int64_t r0;
+  int rc = label_range(idx, "svs_index_assign", row0, nrows, &r0);
+  if (rc != SVS_OK) return rc;
+  if (!out_best && !out_scores && !out_counts && !vector_labels) return SVS_OK;
+  HostCall fr(idx);
+  if ((rc = fr.open()) != SVS_OK) return rc;
+  Ctx* const cx = fr.c;
+  const size_t vec_bytes = (size_t)c * idx->ld * elem_bytes(idx);
+  if ((rc = cx->as_vec.grow(vec_bytes)) != SVS_OK) return rc;
+  if (idx->dtype == SVS_DTYPE_FP8 && (rc = cx->as_vec_scales.grow((size_t)c)) != SVS_OK) return rc;
+  if (out_best && (rc = cx->as_best.grow((size_t)nrows)) != SVS_OK) return rc;
+  if (out_scores && (rc = cx->as_score.grow((size_t)nrows)) != SVS_OK) return rc;
+  if (out_counts && (rc = cx->as_cnt.grow((size_t)c)) != SVS_OK) return rc;
+  if (vector_labels && ((rc = cx->as_lab.grow((size_t)c)) != SVS_OK || (rc = cx->lab_set_pin.grow((size_t)c)) != SVS_OK)) return rc;
+  if ((rc = cx->q_dev.grow((size_t)c * d)) != SVS_OK || (rc = cx->q_pin.grow((size_t)c * d)) != SVS_OK) return rc;
+  // the column last: a call that fails above has allocated none
+  if (vector_labels && (rc = label_column_ensure(idx, "svs_index_assign")) != SVS_OK) return rc;
+  hipStream_t st = fr.stream();
+  // ---- the vectors as stored rows: the rows' own ingest path into the context's image
+  if ((rc = upload_queries(cx, vectors, (size_t)c * d, st)) != SVS_OK) return rc;
+  if (idx->dtype == SVS_DTYPE_F32 && idx->ld != d) HIP_TRY(hipMemsetAsync(cx->as_vec, 0, vec_bytes, st));
+  const unsigned iblocks = idx->dtype == SVS_DTYPE_FP8 ? (unsigned)((c + 3) / 4)
+                                                       : (unsigned)std::min<size_t>(((size_t)c * idx->ld + 255) / 256, 2048);
+  HIP_TRY(ingest_rows_into(idx, cx->as_vec.p, cx->as_vec_scales.p, cx->q_dev, c, d, 0, hipMemcpyDeviceToDevice, iblocks, st));
+  if (vector_labels) {
+    memcpy(cx->lab_set_pin, vector_labels, (size_t)c * sizeof(uint32_t));
+    HIP_TRY(hipMemcpyAsync(cx->as_lab, cx->lab_set_pin, (size_t)c * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+  }
+  if (out_counts) HIP_TRY(hipMemsetAsync(cx->as_cnt, 0, (size_t)c * sizeof(unsigned long long), st));
+  // ---- one launch over the range (svs_index_set_timing: events around it, read by svs_internal_assign_kernel_ms)
+  hipEvent_t ev0 = nullptr, ev1 = nullptr;
+  const bool timed = idx->timing.load() > 0 && hipEventCreate(&ev0) == hipSuccess && hipEventCreate(&ev1) == hipSuccess;
+  if (timed) (void)hipEventRecord(ev0, st);
+  launch_record("assign_rows_kernel", nrows, c);
+  const uint32_t* const k_lab = vector_labels ? cx->as_lab.p : nullptr;
+  int32_t* const k_best = out_best ? cx->as_best.p : nullptr;
+  float* const k_score = out_scores ? cx->as_score.p : nullptr;
+  uint32_t* const k_col = vector_labels ? idx->labels : nullptr;
+  unsigned long long* const k_cnt = out_counts ? cx->as_cnt.p : nullptr;
+  for_store_dtype(idx, [&](auto dt) {
+    constexpr int DT = decltype(dt)::value;
+    if (c <= assign_sweep(1)) launch_assign_na<DT, 1>(idx, cx, c, r0, nrows, k_lab, k_best, k_score, k_col, k_cnt, st);
+    else launch_assign_na<DT, 4>(idx, cx, c, r0, nrows, k_lab, k_best, k_score, k_col, k_cnt, st);
+  });
+  if (timed) (void)hipEventRecord(ev1, st);
+  rc = fr.launched("assign");
+  auto hip_status = [](hipError_t e) {
+    return e == hipSuccess ? (int)SVS_OK : fail(e == hipErrorOutOfMemory ? SVS_ERR_NOMEM : SVS_ERR_DEVICE, "assign read-back: %s", hipGetErrorString(e));
+  };
+  if (rc == SVS_OK && out_best) rc = hip_status(hipMemcpyAsync(out_best, cx->as_best, (size_t)nrows * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+  if (rc == SVS_OK && out_scores) rc = hip_status(hipMemcpyAsync(out_scores, cx->as_score, (size_t)nrows * sizeof(float), hipMemcpyDeviceToHost, st));
+  if (rc == SVS_OK && out_counts) rc = hip_status(hipMemcpyAsync(out_counts, cx->as_cnt, (size_t)c * sizeof(int64_t), hipMemcpyDeviceToHost, st));
+  if (rc == SVS_OK) rc = fr.wait();
+  g_assign_kernel_ms = -1.0;
+  if (timed && rc == SVS_OK) {
+    float ms = 0.f;
+    if (hipEventElapsedTime(&ms, ev0, ev1) == hipSuccess) g_assign_kernel_ms = ms;
+  }
+  if (ev0) (void)hipEventDestroy(ev0);
+  if (ev1) (void)hipEventDestroy(ev1);
+  return rc;
+}
+
+int32_t svs_internal_assign_kernel_ms(double* out) {
+  if (!out) return fail(SVS_ERR_INVALID, "null output");
+  *out = g_assign_kernel_ms;
   return SVS_OK;
 }
 

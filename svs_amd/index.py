@@ -24,6 +24,7 @@ _DTYPES = {"f32": _native.DTYPE_F32, "f16": _native.DTYPE_F16, "fp8": _native.DT
 
 DIVERSE_MAX_FETCH = 1024   # SVS_DIVERSE_MAX_FETCH: the most candidates (and so results) of a diverse search
 LABELS_MAX_SET = 1024      # SVS_LABELS_MAX_SET: the most distinct labels one labelled search names
+ASSIGN_MAX_VECTORS = 1024  # SVS_ASSIGN_MAX_VECTORS: the most vectors one assignment takes
 
 
 def labels_u32(labels) -> np.ndarray:
@@ -496,6 +497,43 @@ class DeviceIndex:
             raise ValueError(f"query must be 1-D, got shape {q.shape}")
         l, s, r, t, _ = self.search_batch_by_label(q[None, :], labels, None if min_score is None else [min_score], n)[0]
         return list(zip(l.tolist(), s.astype(np.float64).tolist(), r.tolist(), t.tolist()))
+
+    def assign(self, vectors, labels=None, row0: Optional[int] = None, nrows: Optional[int] = None,
+               scores: bool = True) -> Tuple[np.ndarray, Optional[np.ndarray], np.ndarray]:
+        """Nearest-vector assignment (svs_index_assign): for each of the GLOBAL rows ``row0 .. row0 + nrows`` (default:
+        the whole index), live or tombstoned, the position of the row of ``vectors`` (c, D; at most ASSIGN_MAX_VECTORS)
+        it scores best against -- both as stored, an exact tie to the lower position.  Returns ``(best i32 (nrows,),
+        scores f32 (nrows,) or None with scores=False, counts i64 (c,))``; counts[j] = the LIVE rows of the range
+        assigned to j.  ``labels`` (c integers in [0, 2**32)): label[row] = labels[best[row]] is also written into the
+        label column for every row of the range; None: the column is not touched.  ValueError for shape and argument
+        errors, NotImplementedError for more than ASSIGN_MAX_VECTORS vectors."""
+        v = np.ascontiguousarray(vectors, dtype=np.float32)
+        if v.ndim != 2:
+            raise ValueError(f"vectors must be 2-D (c, D), got shape {v.shape}")
+        c, d = v.shape
+        lab = None
+        if labels is not None:
+            lab = labels_u32(labels)
+            if len(lab) != c:
+                raise ValueError(f"{len(lab)} labels for {c} vectors")
+        h = self._pinned_handle()
+        try:
+            info = _native.IndexInfo()
+            _native.check(self._quick.svs_index_info(h, C.byref(info)))
+            r0 = int(info.row_offset) if row0 is None else int(row0)
+            cnt = int(info.row_offset) + int(info.n) - r0 if nrows is None else int(nrows)
+            best = np.empty(max(cnt, 0), dtype=np.int32)
+            sc = np.empty(max(cnt, 0), dtype=np.float32) if scores else None
+            counts = np.zeros(max(c, 0), dtype=np.int64)
+            # (the one call that releases the GIL)
+            _native.check(self._lib.svs_index_assign(h, v.ctypes.data if v.size else None, c, d, r0, cnt,
+                                                     None if lab is None else lab.ctypes.data, best.ctypes.data,
+                                                     None if sc is None else sc.ctypes.data, counts.ctypes.data))
+        finally:
+            self._unpin(h)
+        if lab is not None:
+            self._refresh()      # (the first labelled call allocates the column: hbm_bytes)
+        return best, sc, counts
 
     @staticmethod
     def diverse_fetch(n: int, fetch_k: Optional[int] = None) -> int:

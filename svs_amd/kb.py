@@ -29,8 +29,8 @@ from typing import Any, Awaitable, Callable, Dict, Iterator, List, Optional, Tup
 
 import numpy as np
 
-from .index import LABELS_MAX_SET, DeviceIndex
-from .matrix import (DeviceEmbeddingsMatrix, above_op, batch_op, by_label_op, diverse_op, labeled_op, neighbors_op, pairs_op, segments_op, single_op,
+from .index import ASSIGN_MAX_VECTORS, LABELS_MAX_SET, DeviceIndex
+from .matrix import (DeviceEmbeddingsMatrix, above_op, assign_op, batch_op, by_label_op, diverse_op, labeled_op, neighbors_op, pairs_op, segments_op, single_op,
                      within_op)
 
 _LOG = logging.getLogger(__name__)
@@ -409,6 +409,29 @@ def _level_labels(levels) -> List[int]:
     return labels
 
 
+def _classify_topics(topics: List[str]) -> List[str]:
+    """The topics of ``classify_documents`` as a list; ValueError for none or more than ``ASSIGN_MAX_VECTORS``."""
+    topics = list(topics)
+    if not topics:
+        raise ValueError("classify_documents needs at least one topic")
+    if len(topics) > ASSIGN_MAX_VECTORS:
+        raise ValueError(f"{len(topics)} topics; one classification takes at most {ASSIGN_MAX_VECTORS}")
+    return topics
+
+
+def _classified(assigned, doc_of: Dict[int, int], n_topics: int) -> Dict[str, np.ndarray]:
+    """(emb ids, best, scores, counts) of ``DeviceEmbeddingsMatrix.assign`` -> {'doc_ids', 'topic', 'score', 'counts'};
+    an embedding whose doc left the store since is dropped, and the counts are those of the docs returned."""
+    emb_ids, best, scores, counts = assigned
+    known = np.fromiter((int(e) in doc_of for e in emb_ids), dtype=bool, count=len(emb_ids))
+    if not known.all():
+        emb_ids, best, scores = emb_ids[known], best[known], scores[known]
+        counts = np.bincount(best, minlength=n_topics).astype(np.int64)
+    doc_ids = np.fromiter((doc_of[int(e)] for e in emb_ids), dtype=np.int64, count=len(emb_ids))
+    return {"doc_ids": doc_ids, "topic": best.astype(np.int32), "score": scores.astype(np.float32),
+            "counts": np.asarray(counts, dtype=np.int64)}
+
+
 def _diverse_args(n: int, fetch_n: Optional[int], diversity: float) -> Tuple[int, float]:
     """(candidates to fetch, lambda_mult = 1 - diversity) of a diverse retrieval; ValueError for a diversity outside
     [0, 1] or NaN, more than 1024 results or candidates, or fewer candidates than results."""
@@ -636,6 +659,28 @@ class KB:
         with self.db.transaction():
             res = _fetch_by_level(self.db, groups)
         _LOG.info(f"retrieved the best documents of {len(res)} levels")
+        return res
+
+    def classify_documents(self, topics: List[str]) -> Dict[str, np.ndarray]:
+        """Zero-shot tagging: every document that has an embedding gets the topic its embedding scores best against.
+        The topic strings are embedded like queries and the whole corpus is assigned in ONE native call on the device
+        (svs_index_assign) -- nothing is pulled out of HBM but 8 bytes per document.  Returns {'doc_ids': int64 (m,),
+        'topic': int32 (m,), 'score': float32 (m,), 'counts': int64 (len(topics),)}: ``topic[i]`` is the position in
+        ``topics`` of document ``doc_ids[i]``'s best topic (an exact tie goes to the earlier topic), ``counts[t]`` the
+        number of documents of topic t; documents in embedding-id order, documents without an embedding absent.  The
+        label column is not touched (it belongs to the levels).  No topic, or more than 1,024, raises ValueError."""
+        topics = _classify_topics(topics)
+        _LOG.info(f"classifying every document by {len(topics)} topics")
+        assert self.db is not None
+        self.embeddings_matrix.get_sync(self.db)
+        vecs = np.array(self._embed_chunked(topics), dtype=np.float32)
+        _LOG.info("got embeddings for the topics!")
+        assigned = self.embeddings_matrix.assign(vecs)   # one pass over the corpus: HIP
+        _LOG.info(f"computed {self.embeddings_matrix.index.shape[0]} x {len(topics)} cosine similarities")
+        with self.db.transaction():
+            doc_of = self.db.doc_ids_for_embeddings(None)
+        res = _classified(assigned, doc_of, len(topics))
+        _LOG.info(f"classified {len(res['doc_ids'])} documents")
         return res
 
     def retrieve_diverse(self, query: str, n: int, fetch_n: Optional[int] = None, diversity: float = 0.5) -> List[Dict[str, Any]]:
@@ -999,6 +1044,22 @@ class AsyncKB:
             _LOG.info(f"computed {held[0].shape[0]} cosine similarities")
         res = await self._fetch(lambda db: _fetch_by_level(db, groups))
         _LOG.info(f"retrieved the best documents of {len(res)} levels")
+        return res
+
+    async def classify_documents(self, topics: List[str]) -> Dict[str, np.ndarray]:
+        """Async twin of ``KB.classify_documents``, structured as ``retrieve_many``: the reference to the matrix under
+        the lock, the embedding and the one assignment call on an executor thread outside it, the doc ids under the
+        lock."""
+        topics = _classify_topics(topics)
+        _LOG.info(f"classifying every document by {len(topics)} topics")
+        async with self._held() as (held, _):
+            vecs = np.array(await self._embed_chunked(topics), dtype=np.float32)
+            _LOG.info("got embeddings for the topics!")
+            assigned = await self._search(held, assign_op(vecs))
+            _LOG.info(f"computed {held[0].shape[0]} x {len(topics)} cosine similarities")
+        doc_of = await self._fetch(lambda db: db.doc_ids_for_embeddings(None))
+        res = _classified(assigned, doc_of, len(topics))
+        _LOG.info(f"classified {len(res['doc_ids'])} documents")
         return res
 
     async def retrieve_diverse(self, query: str, n: int, fetch_n: Optional[int] = None,

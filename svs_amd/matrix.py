@@ -56,6 +56,9 @@ class _Lookup:
     def __init__(self, arr: np.ndarray):
         self.arr = arr
         self.stale = False
+        # positions of ``arr`` tombstoned in this numbering (``DeviceEmbeddingsMatrix.remove``), ascending; replaced, never
+        # edited in place.  Only ``assign_op`` needs it: every search leaves masked rows out on the device.
+        self.dead = np.zeros(0, dtype=np.int64)
 
 
 def search_mapped(hold: Callable[[], tuple], held: tuple, native: Callable[..., Any], finish: Callable[[Any, np.ndarray], Any]):
@@ -225,6 +228,27 @@ def diverse_op(query_vec: np.ndarray, n: int, fetch_k: Optional[int] = None, lam
         used, rows = res
         off = int(getattr(used, "row_offset", 0))
         return [(score, int(arr[row - off]), red) for score, row, red in rows]
+
+    return native, finish
+
+
+def assign_op(vectors: np.ndarray):
+    """Nearest-vector assignment of every LIVE stored embedding: ``idx.assign`` (svs_index_assign) over the whole index
+    without touching the label column, rows -> ids: (emb_ids i64 (m,), best i32 (m,), scores f32 (m,), counts i64 (c,))
+    in row order.  The tombstoned rows are dropped here (the device answers for them too)."""
+    def native(idx, lookup, *_):
+        dead = lookup.dead          # (before the call: a removal that lands during it may or may not be in the counts)
+        return dead, idx.assign(vectors)
+
+    def finish(res, arr):
+        dead, (best, scores, counts) = res
+        live = np.ones(len(best), dtype=bool)
+        live[dead[dead < len(best)]] = False
+        ids = np.asarray(arr[:len(best)], dtype=np.int64)[live]
+        best = best[live]
+        if int(counts.sum()) != len(best):   # a removal landed between the read of ``dead`` and the device's bitmap
+            counts = np.bincount(best, minlength=len(counts)).astype(np.int64)
+        return ids, best, scores[live], counts
 
     return native, finish
 
@@ -430,6 +454,7 @@ class DeviceEmbeddingsMatrix:
                     rebuild = True      # a host copy would go stale: rebuild from storage
                 elif self._n_dead <= self.COMPACT_AT * len(lk.arr):
                     idx.mask_rows(pos + off)
+                    lk.dead = np.union1d(lk.dead, pos)
                 elif self._view or not hasattr(idx, "compact"):
                     rebuild = True      # compaction by a rebuild from storage
                 else:
@@ -544,6 +569,12 @@ class DeviceEmbeddingsMatrix:
         """``search`` re-ranked for diversity (MMR over the ``fetch_k`` best, on the device):
         [(score, emb_id, redundancy)] in pick order (``KB.retrieve_diverse``)."""
         return self.run_mapped(diverse_op(query_vec, n, fetch_k, lam))
+
+    def assign(self, vectors: np.ndarray) -> Tuple[np.ndarray, np.ndarray, np.ndarray, np.ndarray]:
+        """For every LIVE stored embedding, in row order, the row of ``vectors`` (c, D) it scores best against:
+        (emb_ids i64 (m,), best i32 (m,), scores f32 (m,), counts i64 (c,)) (``KB.classify_documents``).  The label
+        column is never written: on a KB it belongs to the levels (``ensure_labels``)."""
+        return self.run_mapped(assign_op(vectors))
 
     def search_within_many(self, query_vecs: np.ndarray, n: int, emb_id_lists, seg_query=None) -> List[List[Tuple[float, int]]]:
         """``search_within`` for many id lists in one call: list s against query ``seg_query[s]`` of ``query_vecs``

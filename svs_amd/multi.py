@@ -222,6 +222,9 @@ class MultiDeviceIndex:
     def set_labels(self, labels, row0: Optional[int] = None):
         raise NotImplementedError("labels are per device: call set_labels on a DeviceIndex")
 
+    def assign(self, vectors, labels=None, row0: Optional[int] = None, nrows: Optional[int] = None, scores: bool = True):
+        raise NotImplementedError("assignment is per device: the rows and their label column sit in one shard's HBM; call assign on a DeviceIndex")
+
     def search_diverse(self, query_vec: np.ndarray, n: int, fetch_k: Optional[int] = None, lam: float = 0.5):
         raise NotImplementedError("diverse search is per device: the candidates' rows must sit in one HBM; call search_diverse on a DeviceIndex")
 

@@ -215,6 +215,9 @@ class ShardedIndex:
 
     search_batch_by_label = search_by_label
 
+    def assign(self, vectors, labels=None, row0=None, nrows=None, scores=True):
+        raise NotImplementedError("assignment is per device: a rank assigns the rows of its own shard (DeviceIndex.assign); nothing is merged across ranks")
+
     # ---- pipelined single-query searches (device path; what bench.py times) ----------------
     def open(self, capacity: int, k: int) -> None:
         """Buffers for up to ``capacity`` enqueued single-query searches of top-``k``."""
