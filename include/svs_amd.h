@@ -476,14 +476,59 @@ int32_t svs_index_search_by_label(svs_index* idx, const float* queries, int32_t 
  * like a search.  With vector_labels != NULL it holds the geometry lock EXCLUSIVELY for the whole call, as
  * svs_index_set_labels does: searches, appends and other writers on the handle wait that long.
  * Out of scope: svs_multi / row-sharded corpora, a device-pointer variant, more than one position per row (soft
- * assignment), more than SVS_ASSIGN_MAX_VECTORS vectors, per-label sums or means on the device (the update step of
- * k-means: the natural follow-up), a second label column. */
+ * assignment), more than SVS_ASSIGN_MAX_VECTORS vectors, a second label column.  (Per-label sums, the update step of
+ * k-means, are svs_index_label_sums below.) */
 #define SVS_ASSIGN_MAX_VECTORS 1024   /* = SVS_LABELS_MAX_SET: every label an assignment writes can be named in one labelled call */
 int32_t svs_index_assign(svs_index* idx, const float* vectors /* host, f32, C-contiguous (c, d) */, int32_t c, int32_t d,
                          int64_t row0 /* GLOBAL */, int64_t nrows,
                          const uint32_t* vector_labels /* c, or NULL: the label column is not touched */,
                          int32_t* out_best /* nrows, or NULL */, float* out_scores /* nrows, or NULL */,
                          int64_t* out_counts /* c, or NULL */);
+
+/* Per-label row sums: for every label of a set, the f64 sum of the stored values of the live rows of a range that
+ * carry it, and how many there are -- topic centroids, a refined centroid after a classification, and the update step
+ * of k-means beside svs_index_assign, computed where the corpus lies: nlabels x d numbers come back instead of every
+ * row.
+ * Exact definition.
+ *   Labels.  The label of local row r is lab[r]: with row_labels != NULL, row_labels[r - r0] (r0 = the range's first
+ *     local row; e.g. the out_best of an assignment); otherwise the label column's value, and 0 everywhere for an index
+ *     without a column, as everywhere else.
+ *   Rows of a label.  For each position j of `labels`, R_j = the LIVE rows of the range with lab[r] == labels[j], in
+ *     ascending order r_0 < ... < r_(m-1).  The dead-row bitmap decides which rows are live, never a value.
+ *   Values.  x(r)[col] = the stored value as svs_index_debug_dequant returns it, widened to f64 (exact): f32 as is,
+ *     f16 the half widened, fp8 the e4m3 value times the row's scale as ONE f32 product.
+ *   The sum is a fixed tree of plain IEEE f64 additions; nothing is fused, nothing is reassociated:
+ *     chunk t of R_j is the rows r_(256 t) .. r_(min(256 t + 255, m - 1))     (SVS_LABEL_SUMS_CHUNK = 256)
+ *     P_t[col] = (((+0.0 + x(r_a)[col]) + x(r_(a+1))[col]) + ...)             one chain over the chunk's rows
+ *     S_j[col] = (((+0.0 + P_0[col]) + P_1[col]) + ...)                       one chain over the label's chunks
+ *   out_sums[j * d + col] = S_j[col] for col < d (padding columns never appear); out_counts[j] = m.  An empty R_j gives
+ *     +0.0 everywhere and count 0; no element is ever -0.0.  Repeated labels are allowed and every position gets its
+ *     label's answer: the device works on the sorted distinct set, as svs_index_search_by_label does, and the host
+ *     copies each label's answer to the caller's positions.
+ * The answer depends only on the stored values, the labels, the bitmap and the range -- not on nlabels, on the other
+ * labels of the set, on grids or on scheduling: it is bit-reproducible.  Whenever every partial sum is representable in
+ * f64 the result is the exact sum; that holds for all f16 data of realistic size and for unit-norm f32 data.
+ * Errors: everything is validated before anything is launched, and a failing call writes nothing.  An empty index ->
+ * SVS_ERR_SHAPE.  SVS_ERR_INVALID: nlabels < 0, nrows < 0, null labels with nlabels > 0, a range not inside
+ * [row_offset, row_offset + n).  More than SVS_LABELS_MAX_SET DISTINCT labels -> SVS_ERR_UNSUPPORTED.  Rows of more
+ * than 16 KiB (the gather kernels' limit) when sums are asked for over a non-empty range and set -> SVS_ERR_UNSUPPORTED.
+ * nlabels == 0, or both outputs NULL -> SVS_OK, nothing launched.  nrows == 0 -> SVS_OK, the given outputs zeroed,
+ * nothing launched.  out_sums == NULL with out_counts given is a COUNT-ONLY call: only the histogram runs, and no row
+ * is read.
+ * Cost: two passes over 4 bytes of label and one bit per row of the range (a histogram per strip of rows, then a
+ * stable scatter into a label-major row list), then every matching row is read ONCE (svs_amd/csrc/label_sums.h); the
+ * chunks' partial sums, (ceil(nrows / 256) + nlabels) x d f64 at most, are written and folded on the device.  The host
+ * waits once per call; row_labels (4 bytes per row) goes up, nlabels x d f64 and the counts come back.
+ * Blocking; re-entrant on one handle; holds a reference and the geometry lock shared, like a search and like
+ * svs_index_assign without labels; waits for pending staging copies; never goes through the coalescer, the run-ahead
+ * pipelines or shared passes; never allocates a label column.
+ * Out of scope: svs_multi / row-sharded corpora, a device-pointer variant, weighted sums, sums of squares. */
+#define SVS_LABEL_SUMS_CHUNK 256   /* part of the definition above */
+int32_t svs_index_label_sums(svs_index* idx, const uint32_t* labels, int32_t nlabels,
+                             int64_t row0 /* GLOBAL */, int64_t nrows,
+                             const uint32_t* row_labels /* host, nrows, or NULL: the index's label column */,
+                             double* out_sums /* (nlabels, d) C-contiguous, or NULL */,
+                             int64_t* out_counts /* nlabels, or NULL */);
 
 /* Diverse retrieval: maximal-marginal-relevance (MMR) re-ranking of the fetch_k best rows, on the device -- the answer
  * to "the top 10 are ten versions of one paragraph" in a corpus of chunked documents, overlapping windows and

@@ -92,6 +92,7 @@ SIGNATURES = {
     "svs_index_search_above": (C.c_int32, [_P, _P, C.c_int32, C.c_int32, _P, C.c_int32, _P, _P, _P, _P]),
     "svs_index_search_by_label": (C.c_int32, [_P, _P, C.c_int32, C.c_int32, _P, C.c_int32, _P, C.c_int32, _P, _P, _P, _P, _P, _P]),
     "svs_index_assign": (C.c_int32, [_P, _P, C.c_int32, C.c_int32, C.c_int64, C.c_int64, _P, _P, _P, _P]),
+    "svs_index_label_sums": (C.c_int32, [_P, _P, C.c_int32, C.c_int64, C.c_int64, _P, _P, _P]),
     "svs_index_search_diverse": (C.c_int32, [_P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_float, _P, _P, _P,
                                              C.POINTER(C.c_int32)]),
     "svs_index_neighbors": (C.c_int32, [_P, _P, C.c_int64, C.c_int32, _P, _P, C.POINTER(C.c_int32)]),
@@ -127,6 +128,7 @@ INTERNAL = {
     "svs_internal_labels_strip": (C.c_int32, []),
     "svs_internal_by_label_geometry": (C.c_int32, [C.POINTER(C.c_int32)]),
     "svs_internal_assign_kernel_ms": (C.c_int32, [C.POINTER(C.c_double)]),
+    "svs_internal_label_sums_kernel_ms": (C.c_int32, [C.POINTER(C.c_double)]),
     "svs_internal_compact": (C.c_int32, [_P, C.c_int64, _P, C.c_int64, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
 }
 

@@ -137,6 +137,10 @@ int32_t svs_internal_by_label_geometry(int32_t* out);
 /* Milliseconds between the HIP events around assign_rows_kernel in the calling thread's last svs_index_assign, recorded
  * while svs_index_set_timing is on for the handle; -1 when that call recorded none (tools/assign_time.py). */
 int32_t svs_internal_assign_kernel_ms(double* out);
+/* Milliseconds between the HIP events around label_sums_chunk_kernel and label_sums_fold_kernel in the calling thread's
+ * last svs_index_label_sums, recorded while svs_index_set_timing is on for the handle; -1 when that call recorded none
+ * (a count-only call, tools/label_sums_time.py). */
+int32_t svs_internal_label_sums_kernel_ms(double* out);
 /* multi.hip -> svs_amd.hip: carries a worker thread's error message over to the caller's thread */
 int32_t svs_internal_set_error(int32_t code, const char* msg);
 #ifdef __cplusplus

@@ -44,6 +44,7 @@
 #include "labels.h"
 #include "by_label.h"
 #include "assign.h"
+#include "label_sums.h"
 
 namespace {
 
@@ -271,6 +272,15 @@ struct Ctx {
   DevBuf<int32_t> as_best;      DevBuf<float> as_score;
   DevBuf<unsigned long long> as_cnt;
   DevBuf<uint32_t> as_lab;
+  // svs_index_label_sums (label_sums.h): the call's row_labels on the device; the strips' histogram; per slot the
+  // label's rows, its first list position and its first chunk (3 LB_MAX_SET + 1 words); the label-major row list; the
+  // chunk table; the chunks' partial sums; the (nset, d) image of the sums and its pinned copy; the counts' pinned copy.
+  // The set is lab_set_pin / lab_set_dev.
+  DevBuf<uint32_t> ls_lab;      DevBuf<uint32_t> ls_hist;
+  DevBuf<unsigned long long> ls_tot;
+  DevBuf<uint32_t> ls_list;     DevBuf<LsChunk> ls_table;
+  DevBuf<double> ls_part;       DevBuf<double> ls_out;
+  PinBuf<double> ls_out_pin;    PinBuf<unsigned long long> ls_cnt_pin;
   // Scratch is reused in stream order.  A context stays with the stream that
   // last used it; handing it to ANOTHER stream first drains the old one.
   hipStream_t last_stream = nullptr;
@@ -3735,6 +3745,140 @@ int32_t svs_index_assign(svs_index* idx, const float* vectors, int32_t c, int32_
 int32_t svs_internal_assign_kernel_ms(double* out) {
   if (!out) return fail(SVS_ERR_INVALID, "null output");
   *out = g_assign_kernel_ms;
+  return SVS_OK;
+}
+
+// ---- svs_index_label_sums (label_sums.h)
+thread_local double g_label_sums_kernel_ms = -1.0;   // svs_internal_label_sums_kernel_ms
+static_assert(SVS_LABEL_SUMS_CHUNK == LS_CHUNK, "the chunk length is part of the sum's definition");
+
+int32_t svs_index_label_sums(svs_index* idx, const uint32_t* labels, int32_t nlabels, int64_t row0, int64_t nrows,
+                             const uint32_t* row_labels, double* out_sums, int64_t* out_counts) {
+  launch_reset();
+  g_label_sums_kernel_ms = -1.0;   // (a call that fails or records nothing leaves no earlier call's time behind)
+  if (!idx) return fail(SVS_ERR_INVALID, "null index");
+  RefGuard guard(idx);
+  std::shared_lock<std::shared_mutex> geo(idx->rw);   // a reader like every search: one column, one bitmap for the whole call
+  // ---- everything is validated before anything is written, allocated or launched
+  if (idx->n == 0 || idx->d == 0) return fail(SVS_ERR_SHAPE, "svs_index_label_sums: the index is empty");
+  // (the list holds local rows as u32 and a strip prefix is a u32: ensure_capacity admits at most 2^32 - 1 rows per handle)
+  if (idx->n > 0xffffffffll) return fail(SVS_ERR_UNSUPPORTED, "svs_index_label_sums: %lld rows; a handle holds fewer than 2^32", (long long)idx->n);
+  if (nlabels < 0) return fail(SVS_ERR_INVALID, "nlabels must be >= 0");
+  if (nrows < 0) return fail(SVS_ERR_INVALID, "nrows must be >= 0");
+  if (nlabels > 0 && !labels) return fail(SVS_ERR_INVALID, "null labels");
+  int64_t r0;
+  int rc = label_range(idx, "svs_index_label_sums", row0, nrows, &r0);
+  if (rc != SVS_OK) return rc;
+  // the set: sorted, without repeats; a label's slot in every table is its index here
+  std::vector<uint32_t> set;
+  try {
+    set.assign(labels, labels + nlabels);
+  } catch (const std::bad_alloc&) {
+    return fail(SVS_ERR_NOMEM, "out of host memory for %d labels", (int)nlabels);
+  }
+  std::sort(set.begin(), set.end());
+  set.erase(std::unique(set.begin(), set.end()), set.end());
+  if (set.size() > (size_t)SVS_LABELS_MAX_SET)
+    return fail(SVS_ERR_UNSUPPORTED, "svs_index_label_sums: %zu distinct labels; a set holds at most %d", set.size(), SVS_LABELS_MAX_SET);
+  const int nset = (int)set.size(), d = idx->d;
+  if (nset == 0 || (!out_sums && !out_counts)) return SVS_OK;
+  if (nrows == 0) {
+    if (out_sums) std::fill(out_sums, out_sums + (size_t)nlabels * d, 0.0);
+    if (out_counts) memset(out_counts, 0, (size_t)nlabels * sizeof(int64_t));
+    return SVS_OK;
+  }
+  if (out_sums && gather_rows_per_wave(idx) == 0)
+    return fail(SVS_ERR_UNSUPPORTED, "svs_index_label_sums: rows of %zu bytes; the gather kernels take rows of up to 16 KiB",
+                (size_t)idx->ld * elem_bytes(idx));
+  const int64_t nstrips = (nrows + LS_STRIP - 1) / LS_STRIP;
+  const int64_t bound = (nrows + LS_CHUNK - 1) / LS_CHUNK + nset;   // chunks never cross a label: at most one ragged chunk each
+  const int ld16 = (int)((size_t)idx->ld * elem_bytes(idx) / 16);
+  HostCall fr(idx);
+  if ((rc = fr.open()) != SVS_OK) return rc;
+  Ctx* const c = fr.c;
+  if ((rc = c->ls_hist.grow((size_t)nstrips * nset)) != SVS_OK || (rc = c->ls_tot.grow(3 * (size_t)LB_MAX_SET + 1)) != SVS_OK ||
+      (rc = c->ls_cnt_pin.grow((size_t)nset)) != SVS_OK)
+    return rc;
+  if (row_labels && (rc = c->ls_lab.grow((size_t)nrows)) != SVS_OK) return rc;
+  if (nset > 1 && ((rc = c->lab_set_pin.grow((size_t)nset)) != SVS_OK || (rc = c->lab_set_dev.grow((size_t)nset)) != SVS_OK)) return rc;
+  if (out_sums && ((rc = c->ls_list.grow((size_t)nrows)) != SVS_OK || (rc = c->ls_table.grow((size_t)bound)) != SVS_OK ||
+                   (rc = c->ls_part.grow((size_t)bound * d)) != SVS_OK || (rc = c->ls_out.grow((size_t)nset * d)) != SVS_OK ||
+                   (rc = c->ls_out_pin.grow((size_t)nset * d)) != SVS_OK))
+    return rc;
+  hipStream_t st = fr.stream();
+  if (nset > 1) {
+    memcpy(c->lab_set_pin, set.data(), (size_t)nset * sizeof(uint32_t));
+    HIP_TRY(hipMemcpyAsync(c->lab_set_dev, c->lab_set_pin, (size_t)nset * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+  }
+  if (row_labels) HIP_TRY(hipMemcpyAsync(c->ls_lab, row_labels, (size_t)nrows * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+  const LabelFilter f = label_filter(idx, set.data(), nset, c->lab_set_dev);
+  const LsRange g{r0, nrows, row_labels ? c->ls_lab.p : nullptr};
+  unsigned long long* const tot = c->ls_tot.p;
+  unsigned long long* const lbase = tot + LB_MAX_SET;
+  unsigned long long* const cbase = tot + 2 * LB_MAX_SET;
+  // ---- 1, 2: the strips' histogram and its scan; a count-only call ends here
+  launch_record("label_sums_hist_kernel", nrows, nset);
+  hipLaunchKernelGGL(label_sums_hist_kernel, dim3((unsigned)nstrips), dim3(LS_THREADS), 0, st, f, g, c->ls_hist.p);
+  launch_record("label_sums_scan_kernel", nrows, nset);
+  hipLaunchKernelGGL(label_sums_scan_kernel, dim3((unsigned)nset), dim3(LS_THREADS), 0, st, c->ls_hist.p, nstrips, nset, tot);
+  hipEvent_t ev0 = nullptr, ev1 = nullptr;
+  bool timed = false;
+  if (out_sums) {
+    // ---- 3, 4: the plan and the label-major list, on the device: no host wait before the sums
+    launch_record("label_sums_plan_kernel", nrows, nset);
+    hipLaunchKernelGGL(label_sums_plan_kernel, dim3(1), dim3(LS_PLAN_THREADS), 0, st, (const unsigned long long*)tot, nset, lbase, cbase,
+                       c->ls_table.p, bound);
+    launch_record("label_sums_scatter_kernel", nrows, nset);
+    hipLaunchKernelGGL(label_sums_scatter_kernel, dim3((unsigned)nstrips), dim3(LS_THREADS), 0, st, f, g, (const uint32_t*)c->ls_hist.p,
+                       (const unsigned long long*)lbase, (const unsigned long long*)tot, c->ls_list.p, nrows);
+    // ---- 5, 6: chunk sums and fold (svs_index_set_timing: events around them, read by svs_internal_label_sums_kernel_ms)
+    timed = idx->timing.load() > 0 && hipEventCreate(&ev0) == hipSuccess && hipEventCreate(&ev1) == hipSuccess;
+    if (timed) (void)hipEventRecord(ev0, st);
+    launch_record("label_sums_chunk_kernel", nrows, nset);
+    for_store_dtype(idx, [&](auto dt) {
+      constexpr int DT = decltype(dt)::value;
+      hipLaunchKernelGGL((label_sums_chunk_kernel<DT>), dim3((unsigned)bound, (unsigned)((ld16 + LS_THREADS - 1) / LS_THREADS)), dim3(LS_THREADS),
+                         0, st, (const u32x4*)idx->rows, ld16, (const float*)idx->row_scales, idx->n, d, (const LsChunk*)c->ls_table.p,
+                         (const uint32_t*)c->ls_list.p, nrows, c->ls_part.p);
+    });
+    launch_record("label_sums_fold_kernel", nrows, nset);
+    hipLaunchKernelGGL(label_sums_fold_kernel, dim3((unsigned)((d + LS_FOLD_THREADS - 1) / LS_FOLD_THREADS), (unsigned)nset),
+                       dim3(LS_FOLD_THREADS), 0, st, (const double*)c->ls_part.p, (const unsigned long long*)tot,
+                       (const unsigned long long*)cbase, d, bound, c->ls_out.p);
+    if (timed) (void)hipEventRecord(ev1, st);
+  }
+  rc = fr.launched("label_sums");
+  auto hip_status = [](hipError_t e) {
+    return e == hipSuccess ? (int)SVS_OK : fail(e == hipErrorOutOfMemory ? SVS_ERR_NOMEM : SVS_ERR_DEVICE, "label_sums read-back: %s", hipGetErrorString(e));
+  };
+  if (rc == SVS_OK) rc = hip_status(hipMemcpyAsync(c->ls_cnt_pin, tot, (size_t)nset * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
+  if (rc == SVS_OK && out_sums) rc = hip_status(hipMemcpyAsync(c->ls_out_pin, c->ls_out, (size_t)nset * d * sizeof(double), hipMemcpyDeviceToHost, st));
+  if (rc == SVS_OK) rc = fr.wait();
+  if (timed && rc == SVS_OK) {
+    float ms = 0.f;
+    if (hipEventElapsedTime(&ms, ev0, ev1) == hipSuccess) g_label_sums_kernel_ms = ms;
+  }
+  if (ev0) (void)hipEventDestroy(ev0);
+  if (ev1) (void)hipEventDestroy(ev1);
+  if (rc != SVS_OK) return rc;
+  unsigned long long seen = 0;
+  for (int s = 0; s < nset; ++s) {
+    if (c->ls_cnt_pin[s] > (unsigned long long)nrows - seen)
+      return fail(SVS_ERR_DEVICE, "label_sums: the histogram counted more than the range's %lld rows", (long long)nrows);
+    seen += c->ls_cnt_pin[s];
+  }
+  // ---- the device worked on the sorted distinct set: every position of the caller's gets its label's answer
+  for (int32_t j = 0; j < nlabels; ++j) {
+    const size_t s = (size_t)(std::lower_bound(set.begin(), set.end(), labels[j]) - set.begin());
+    if (out_sums) memcpy(out_sums + (size_t)j * d, c->ls_out_pin + s * d, (size_t)d * sizeof(double));
+    if (out_counts) out_counts[j] = (int64_t)c->ls_cnt_pin[s];
+  }
+  return SVS_OK;
+}
+
+int32_t svs_internal_label_sums_kernel_ms(double* out) {
+  if (!out) return fail(SVS_ERR_INVALID, "null output");
+  *out = g_label_sums_kernel_ms;
   return SVS_OK;
 }
 

@@ -9,6 +9,7 @@ the HIP kernels; this module only marshals numpy buffers.
 from __future__ import annotations
 
 import ctypes as C
+import operator
 import threading
 from typing import List, Optional, Tuple
 
@@ -38,6 +39,27 @@ def labels_u32(labels) -> np.ndarray:
             raise ValueError("labels must lie in [0, 2**32)")
         a = a.astype(np.uint32)
     return np.ascontiguousarray(a).reshape(-1)
+
+
+def _means(sums: np.ndarray, counts: np.ndarray) -> np.ndarray:
+    """Per-label sums (L, D) f64 and counts (L,) -> the means in f64; a label with count 0 gets zeros."""
+    means = np.zeros(sums.shape, dtype=np.float64)
+    has = counts > 0
+    means[has] = sums[has] / counts[has, None].astype(np.float64)
+    return means
+
+
+def _centroids(sums: np.ndarray, counts: np.ndarray, previous: np.ndarray, spherical: bool) -> np.ndarray:
+    """The update step of ``DeviceIndex.kmeans``: the means (``spherical``: normalised to unit length) in f64, cast
+    to f32; a label with count 0, or with a zero-norm sum, keeps its row of ``previous``."""
+    cent = _means(sums, counts)
+    norm = np.sqrt((cent * cent).sum(axis=1))
+    keep = (counts == 0) | ~(norm > 0.0)
+    if spherical:
+        cent[~keep] = cent[~keep] / norm[~keep, None]
+    out = cent.astype(np.float32)
+    out[keep] = previous[keep]
+    return out
 
 
 class DeviceIndex:
@@ -534,6 +556,114 @@ class DeviceIndex:
         if lab is not None:
             self._refresh()      # (the first labelled call allocates the column: hbm_bytes)
         return best, sc, counts
+
+    def label_sums(self, labels, row_labels=None, row0: Optional[int] = None, nrows: Optional[int] = None,
+                   sums: bool = True) -> Tuple[Optional[np.ndarray], np.ndarray]:
+        """Per-label row sums (svs_index_label_sums): for every entry of ``labels`` (L integers in [0, 2**32), any order,
+        repeats allowed, at most LABELS_MAX_SET distinct ones) the f64 sum of the stored values of the LIVE rows among
+        the GLOBAL rows ``row0 .. row0 + nrows`` (default: the whole index) that carry the label, and their number.  A
+        row's label is ``row_labels[row - row0]`` when ``row_labels`` (one integer per row of the range, e.g. the
+        ``best`` of ``assign``) is given, else the label column's.  Returns ``(sums f64 (L, D) or None with sums=False,
+        counts i64 (L,))``; ``sums=False`` runs the histogram only.  The sum is a fixed tree of f64 additions (chunks of
+        256 rows in ascending row order): bit-reproducible, and exact whenever its partial sums are representable.
+        ValueError for argument errors, NotImplementedError for too many labels or rows of more than 16 KiB."""
+        lab = labels_u32(labels)
+        rl = None if row_labels is None else labels_u32(row_labels)
+        h = self._pinned_handle()
+        try:
+            info = _native.IndexInfo()
+            _native.check(self._quick.svs_index_info(h, C.byref(info)))
+            r0 = int(info.row_offset) if row0 is None else int(row0)
+            cnt = int(info.row_offset) + int(info.n) - r0 if nrows is None else int(nrows)
+            if rl is not None and len(rl) != cnt:
+                raise ValueError(f"{len(rl)} row labels for {cnt} rows")
+            out = np.zeros((len(lab), int(info.d)), dtype=np.float64) if sums else None
+            counts = np.zeros(len(lab), dtype=np.int64)
+            # (the one call that releases the GIL)
+            _native.check(self._lib.svs_index_label_sums(h, lab.ctypes.data if len(lab) else None, len(lab), r0, cnt,
+                                                         None if rl is None or not len(rl) else rl.ctypes.data,
+                                                         None if out is None else out.ctypes.data, counts.ctypes.data))
+        finally:
+            self._unpin(h)
+        return out, counts
+
+    def label_means(self, labels, row_labels=None, row0: Optional[int] = None,
+                    nrows: Optional[int] = None) -> Tuple[np.ndarray, np.ndarray]:
+        """``label_sums`` divided by the counts in f64, then cast: ``(means f32 (L, D), counts i64 (L,))``; a label
+        without a live row gets an all-zero mean."""
+        s, counts = self.label_sums(labels, row_labels, row0, nrows)
+        return _means(s, counts).astype(np.float32), counts
+
+    def kmeans(self, c: int, iterations: int = 10, seed: int = 0, init=None, spherical: bool = True,
+               write_labels: bool = False) -> Tuple[np.ndarray, np.ndarray, np.ndarray, np.ndarray, int]:
+        """k-means over the stored rows, every step on the device: per iteration one ``assign`` (the nearest centroid of
+        every row by dot product) and one ``label_sums(arange(c), row_labels=best)`` (the update) -- c x D numbers and 4
+        bytes per row cross PCIe, no row leaves HBM.  ``init`` (c, D): the first centroids; None: the stored values of
+        ``c`` distinct rows drawn with ``np.random.default_rng(seed)`` (a tombstoned row's values are still in HBM).  A
+        centroid is its cluster's mean over the LIVE rows, with ``spherical`` normalised to unit length in f64, then
+        cast to f32; a cluster without a live row, or whose sum has zero norm, keeps its previous centroid.  The loop
+        stops after ``iterations`` updates or as soon as ``best`` no longer changes.  Returns ``(centroids f32 (c, D),
+        best i32 (n,), scores f32 (n,), counts i64 (c,), iterations run)``: best and scores are the last assignment's
+        (against the centroids before it), counts its live rows per cluster, the centroids that assignment's means;
+        iterations run = the updates made.  ``write_labels``: one final ``assign(centroids, labels=arange(c))`` writes
+        the label column, and best, scores and counts are then its answer.  The rows are those the index holds when the
+        call begins: rows appended while it runs take no part and get no label.  More than ASSIGN_MAX_VECTORS clusters,
+        or fewer than one, is a ValueError."""
+        try:
+            c, iterations = operator.index(c), operator.index(iterations)
+        except TypeError:
+            raise ValueError(f"c and iterations must be integers, got {c!r} and {iterations!r}") from None
+        if c < 1 or c > ASSIGN_MAX_VECTORS:
+            raise ValueError(f"k-means takes 1 to {ASSIGN_MAX_VECTORS} clusters, got {c}")
+        if iterations < 1:
+            raise ValueError(f"iterations must be >= 1, got {iterations}")
+        # ONE row range for the whole loop: rows appended while it runs (another thread, another owner of the handle)
+        # are not part of this clustering, and no call of the loop sees another range than the one before it
+        row0, n, d = self._extent()
+        if init is None:
+            if c > n:
+                raise ValueError(f"{c} clusters for {n} rows")
+            cent = self._stored_rows_at(np.random.default_rng(seed).choice(n, size=c, replace=False))
+        else:
+            cent = np.array(init, dtype=np.float32)
+            if cent.shape != (c, d):
+                raise ValueError(f"init must have shape ({c}, {d}), got {cent.shape}")
+        ids = np.arange(c, dtype=np.uint32)
+        prev, ran = None, 0
+        while ran < iterations:
+            best, scores, counts = self.assign(cent, row0=row0, nrows=n)
+            if prev is not None and np.array_equal(best, prev):
+                break                # (cent already holds this assignment's means)
+            s, counts = self.label_sums(ids, row_labels=best, row0=row0, nrows=n)
+            cent = _centroids(s, counts, cent, spherical)
+            prev = best
+            ran += 1
+        if write_labels:
+            best, scores, counts = self.assign(cent, labels=ids, row0=row0, nrows=n)
+        return cent, best, scores, counts, ran
+
+    def _extent(self) -> Tuple[int, int, int]:
+        """(row_offset, n, d) as the HANDLE holds them now."""
+        info = _native.IndexInfo()
+        _native.check(self._quick.svs_index_info(self._handle(), C.byref(info)))
+        return int(info.row_offset), int(info.n), int(info.d)
+
+    def _stored_rows_at(self, rows, gap: int = 64) -> np.ndarray:
+        """``stored_rows`` of the listed LOCAL rows, in the order given: the rows are read in ascending order, and rows
+        no more than ``gap`` apart share one read (a few thousand rows are cheaper than a second blocking call)."""
+        rows = np.asarray(rows, dtype=np.int64).reshape(-1)
+        out = np.empty((len(rows), self.shape[1]), dtype=np.float32)
+        order = np.argsort(rows, kind="stable")
+        at = 0
+        while at < len(order):
+            end = at + 1
+            while end < len(order) and rows[order[end]] - rows[order[end - 1]] <= gap:
+                end += 1
+            first = int(rows[order[at]])
+            block = self.stored_rows(first, int(rows[order[end - 1]]) - first + 1)
+            out[order[at:end]] = block[rows[order[at:end]] - first]
+            at = end
+        return out
 
     @staticmethod
     def diverse_fetch(n: int, fetch_k: Optional[int] = None) -> int:

@@ -30,7 +30,7 @@ from typing import Any, Awaitable, Callable, Dict, Iterator, List, Optional, Tup
 import numpy as np
 
 from .index import ASSIGN_MAX_VECTORS, LABELS_MAX_SET, DeviceIndex
-from .matrix import (DeviceEmbeddingsMatrix, above_op, assign_op, batch_op, by_label_op, diverse_op, labeled_op, neighbors_op, pairs_op, segments_op, single_op,
+from .matrix import (DeviceEmbeddingsMatrix, above_op, assign_op, batch_op, by_label_op, cluster_op, diverse_op, labeled_op, neighbors_op, pairs_op, segments_op, single_op,
                      within_op)
 
 _LOG = logging.getLogger(__name__)
@@ -432,6 +432,22 @@ def _classified(assigned, doc_of: Dict[int, int], n_topics: int) -> Dict[str, np
             "counts": np.asarray(counts, dtype=np.int64)}
 
 
+def _cluster_args(n_clusters: int, iterations: int) -> None:
+    """ValueError for fewer than one or more than ``ASSIGN_MAX_VECTORS`` clusters, or fewer than one iteration."""
+    if not 1 <= int(n_clusters) <= ASSIGN_MAX_VECTORS:
+        raise ValueError(f"{n_clusters} clusters; one clustering takes 1 to {ASSIGN_MAX_VECTORS}")
+    if int(iterations) < 1:
+        raise ValueError(f"iterations must be >= 1, got {iterations}")
+
+
+def _clustered(clustered, doc_of: Dict[int, int], n_clusters: int) -> Dict[str, Any]:
+    """(emb ids, cluster, scores, counts, centroids, iterations) of ``DeviceEmbeddingsMatrix.cluster`` -> {'doc_ids',
+    'cluster', 'score', 'counts', 'centroids', 'iterations'}; dropped docs and counts as in ``_classified``."""
+    res = _classified(clustered[:4], doc_of, n_clusters)
+    return {"doc_ids": res["doc_ids"], "cluster": res["topic"], "score": res["score"], "counts": res["counts"],
+            "centroids": np.asarray(clustered[4], dtype=np.float32), "iterations": int(clustered[5])}
+
+
 def _diverse_args(n: int, fetch_n: Optional[int], diversity: float) -> Tuple[int, float]:
     """(candidates to fetch, lambda_mult = 1 - diversity) of a diverse retrieval; ValueError for a diversity outside
     [0, 1] or NaN, more than 1024 results or candidates, or fewer candidates than results."""
@@ -681,6 +697,27 @@ class KB:
             doc_of = self.db.doc_ids_for_embeddings(None)
         res = _classified(assigned, doc_of, len(topics))
         _LOG.info(f"classified {len(res['doc_ids'])} documents")
+        return res
+
+    def cluster_documents(self, n_clusters: int, iterations: int = 10, seed: int = 0) -> Dict[str, Any]:
+        """Unsupervised grouping: spherical k-means of the document embeddings into ``n_clusters`` clusters, every
+        iteration on the device (svs_index_assign, then svs_index_label_sums) -- no embedding leaves HBM.  Returns
+        {'doc_ids': int64 (m,), 'cluster': int32 (m,), 'score': float32 (m,), 'counts': int64 (n_clusters,),
+        'centroids': float32 (n_clusters, D), 'iterations': int}: ``cluster[i]`` is the cluster of document
+        ``doc_ids[i]`` and ``score[i]`` its similarity to the centroid it was assigned to; documents in embedding-id
+        order, documents without an embedding absent.  The first centroids are ``n_clusters`` stored embeddings drawn
+        with ``seed``; one seed gives one answer.  The label column is not touched (it belongs to the levels).  Fewer
+        than one or more than 1,024 clusters, or more clusters than embeddings, raises ValueError."""
+        _cluster_args(n_clusters, iterations)
+        _LOG.info(f"clustering every document into {n_clusters} clusters")
+        assert self.db is not None
+        self.embeddings_matrix.get_sync(self.db)
+        clustered = self.embeddings_matrix.cluster(int(n_clusters), int(iterations), int(seed))   # the whole loop: HIP
+        _LOG.info(f"ran {clustered[5]} k-means iterations over {self.embeddings_matrix.index.shape[0]} embeddings")
+        with self.db.transaction():
+            doc_of = self.db.doc_ids_for_embeddings(None)
+        res = _clustered(clustered, doc_of, int(n_clusters))
+        _LOG.info(f"clustered {len(res['doc_ids'])} documents")
         return res
 
     def retrieve_diverse(self, query: str, n: int, fetch_n: Optional[int] = None, diversity: float = 0.5) -> List[Dict[str, Any]]:
@@ -1060,6 +1097,20 @@ class AsyncKB:
         doc_of = await self._fetch(lambda db: db.doc_ids_for_embeddings(None))
         res = _classified(assigned, doc_of, len(topics))
         _LOG.info(f"classified {len(res['doc_ids'])} documents")
+        return res
+
+    async def cluster_documents(self, n_clusters: int, iterations: int = 10, seed: int = 0) -> Dict[str, Any]:
+        """Async twin of ``KB.cluster_documents``, structured as ``classify_documents``: the reference to the matrix
+        under the lock, the whole k-means loop as ONE mapped call on an executor thread outside it, the doc ids under
+        the lock."""
+        _cluster_args(n_clusters, iterations)
+        _LOG.info(f"clustering every document into {n_clusters} clusters")
+        async with self._held() as (held, _):
+            clustered = await self._search(held, cluster_op(int(n_clusters), int(iterations), int(seed)))
+            _LOG.info(f"ran {clustered[5]} k-means iterations over {held[0].shape[0]} embeddings")
+        doc_of = await self._fetch(lambda db: db.doc_ids_for_embeddings(None))
+        res = _clustered(clustered, doc_of, int(n_clusters))
+        _LOG.info(f"clustered {len(res['doc_ids'])} documents")
         return res
 
     async def retrieve_diverse(self, query: str, n: int, fetch_n: Optional[int] = None,

@@ -253,6 +253,29 @@ def assign_op(vectors: np.ndarray):
     return native, finish
 
 
+def cluster_op(c: int, iterations: int = 10, seed: int = 0):
+    """k-means over every stored embedding: ``idx.kmeans`` (svs_index_assign + svs_index_label_sums per iteration)
+    without touching the label column, rows -> ids: (emb_ids i64 (m,), cluster i32 (m,), scores f32 (m,), counts i64
+    (c,), centroids f32 (c, D), iterations run) in row order, tombstoned rows dropped as in ``assign_op``.  The WHOLE loop
+    is one mapped op: a compaction that lands inside it fails or stales the op as a whole, and ``search_mapped`` runs
+    it again -- never two iterations in two numberings."""
+    def native(idx, lookup, *_):
+        dead = lookup.dead
+        return dead, idx.kmeans(c, iterations, seed)
+
+    def finish(res, arr):
+        dead, (centroids, best, scores, counts, ran) = res
+        live = np.ones(len(best), dtype=bool)
+        live[dead[dead < len(best)]] = False
+        ids = np.asarray(arr[:len(best)], dtype=np.int64)[live]
+        best = best[live]
+        if int(counts.sum()) != len(best):   # a removal landed between the read of ``dead`` and the device's bitmap
+            counts = np.bincount(best, minlength=len(counts)).astype(np.int64)
+        return ids, best, scores[live], counts, centroids, ran
+
+    return native, finish
+
+
 def ids_of_rows(res, arr: np.ndarray) -> List[Tuple[float, int]]:
     return [(score, int(arr[row])) for score, row in res]
 
@@ -575,6 +598,12 @@ class DeviceEmbeddingsMatrix:
         (emb_ids i64 (m,), best i32 (m,), scores f32 (m,), counts i64 (c,)) (``KB.classify_documents``).  The label
         column is never written: on a KB it belongs to the levels (``ensure_labels``)."""
         return self.run_mapped(assign_op(vectors))
+
+    def cluster(self, c: int, iterations: int = 10, seed: int = 0):
+        """k-means of the stored embeddings into ``c`` clusters, on the device: (emb_ids i64 (m,), cluster i32 (m,),
+        scores f32 (m,), counts i64 (c,), centroids f32 (c, D), iterations run) for the LIVE embeddings in row order
+        (``KB.cluster_documents``).  The label column is never written."""
+        return self.run_mapped(cluster_op(c, iterations, seed))
 
     def search_within_many(self, query_vecs: np.ndarray, n: int, emb_id_lists, seg_query=None) -> List[List[Tuple[float, int]]]:
         """``search_within`` for many id lists in one call: list s against query ``seg_query[s]`` of ``query_vecs``

@@ -225,6 +225,14 @@ class MultiDeviceIndex:
     def assign(self, vectors, labels=None, row0: Optional[int] = None, nrows: Optional[int] = None, scores: bool = True):
         raise NotImplementedError("assignment is per device: the rows and their label column sit in one shard's HBM; call assign on a DeviceIndex")
 
+    def label_sums(self, labels, row_labels=None, row0: Optional[int] = None, nrows: Optional[int] = None, sums: bool = True):
+        raise NotImplementedError("per-label sums are per device: a label's rows are summed in one shard's HBM; call label_sums on a DeviceIndex")
+
+    label_means = label_sums
+
+    def kmeans(self, c: int, iterations: int = 10, seed: int = 0, init=None, spherical: bool = True, write_labels: bool = False):
+        raise NotImplementedError("k-means is per device: assignment and update run over one shard's HBM; call kmeans on a DeviceIndex")
+
     def search_diverse(self, query_vec: np.ndarray, n: int, fetch_k: Optional[int] = None, lam: float = 0.5):
         raise NotImplementedError("diverse search is per device: the candidates' rows must sit in one HBM; call search_diverse on a DeviceIndex")
 

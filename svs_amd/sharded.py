@@ -218,6 +218,14 @@ class ShardedIndex:
     def assign(self, vectors, labels=None, row0=None, nrows=None, scores=True):
         raise NotImplementedError("assignment is per device: a rank assigns the rows of its own shard (DeviceIndex.assign); nothing is merged across ranks")
 
+    def label_sums(self, labels, row_labels=None, row0=None, nrows=None, sums=True):
+        raise NotImplementedError("per-label sums are per device: a rank sums the rows of its own shard (DeviceIndex.label_sums); nothing is merged across ranks")
+
+    label_means = label_sums
+
+    def kmeans(self, c, iterations=10, seed=0, init=None, spherical=True, write_labels=False):
+        raise NotImplementedError("k-means is per device: a rank clusters the rows of its own shard (DeviceIndex.kmeans); nothing is merged across ranks")
+
     # ---- pipelined single-query searches (device path; what bench.py times) ----------------
     def open(self, capacity: int, k: int) -> None:
         """Buffers for up to ``capacity`` enqueued single-query searches of top-``k``."""
