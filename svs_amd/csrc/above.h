@@ -19,13 +19,14 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "dead_bits.h"
 #include "keys.h"
 #include "select.h"
 
 namespace svs {
 
 // grid = blocks of FA_THREADS * SEL_VPT float4 groups over scores[0 .. n); tkey = score_key(cut-off);
-// dead_bits: one bit per row (bit r & 31 of word r >> 5), null when no row is masked; hdr / cand: one query's
+// dead_bits: the dead-row bitmap (dead_bits.h), null when no row is masked; hdr / cand: one query's
 // SelHeader (zero on entry) and candidate list of CAND_CAP entries.
 __global__ __launch_bounds__(FA_THREADS) void above_filter_kernel(
     const float* __restrict__ scores, int64_t n, uint32_t tkey, const uint32_t* __restrict__ dead_bits,
@@ -41,8 +42,7 @@ __global__ __launch_bounds__(FA_THREADS) void above_filter_kernel(
   for (int j = 0; j < SEL_VPT; ++j) {   // all requested before the first is used
     const int64_t i4 = base + (int64_t)j * FA_THREADS;
     v[j] = i4 < n4 ? s4[i4] : (sel_v4f){0.f, 0.f, 0.f, 0.f};
-    // the four rows of a group share one bitmap word (the group starts at a multiple of 4)
-    dead[j] = (dead_bits && i4 < n4) ? dead_bits[i4 >> 3] >> ((uint32_t)(i4 & 7) * 4u) : 0u;
+    dead[j] = dead_nibble(i4 < n4 ? dead_bits : nullptr, i4);
   }
 #pragma unroll
   for (int j = 0; j < SEL_VPT; ++j) {

@@ -36,6 +36,7 @@
 #include <stdint.h>
 
 #include "chunk.h"
+#include "dead_bits.h"
 #include "keys.h"
 
 namespace svs {
@@ -185,8 +186,7 @@ __global__ __launch_bounds__(AS_THREADS) void assign_rows_kernel(
       if (out_scores) out_scores[i] = key_score((uint32_t)(key >> 32));
       if (labels) labels[row] = vec_labels[j];
       if (counts) {
-        const bool dead = dead_bits && ((dead_bits[row >> 5] >> (uint32_t)(row & 31)) & 1u);
-        if (!dead) atomicAdd(&s_cnt[j], 1u);
+        if (!row_dead(dead_bits, row)) atomicAdd(&s_cnt[j], 1u);
       }
     }
     __syncthreads();   // s_best before the next tile zeroes it; s_cnt before the merge

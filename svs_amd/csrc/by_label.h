@@ -11,8 +11,7 @@
 //   1. by_label_reduce_kernel<CROSS>: workgroups stride over strips of BL_STRIP rows.  A thread takes BL_VPT groups of
 //      four consecutive rows per strip: a 16-byte load of the four scores, one of their four labels, and one nibble of
 //      a bitmap word, every load requested before the first is used.  A qualifying row's label is searched in the
-//      set's LDS image (label_stage_set; bisection as label_in_set, a set of one label a plain compare): its SLOT is
-//      its index in the sorted set.  Each workgroup keeps a private table in LDS -- a u32 count and a u64 best key per
+//      set's LDS image (label_stage_set, label_slot): its SLOT is its index in the sorted set.  Each workgroup keeps a private table in LDS -- a u32 count and a u64 best key per
 //      slot, 12 KiB at 1,024 labels -- updated with LDS atomics (add, max).  Before that the wave aggregates the slot
 //      of its first hit: the lanes that share it become ONE add and ONE max (one label holding every row: 2 LDS
 //      atomics per wave and element instead of 128 on one address); the other lanes update on their own.
@@ -44,18 +43,6 @@ constexpr int BL_ATOMIC = 0, BL_PARTIALS = 1;           // by_label_reduce_kerne
 constexpr int BL_TAB_WORDS = 2 * LB_MAX_SET;            // the query's table in HBM: best[LB_MAX_SET], then count[LB_MAX_SET], u64 each
 static_assert(BL_THREADS == LB_THREADS, "label_stage_set strides by LB_THREADS");
 static_assert(BL_STRIP % 32 == 0, "strips begin at whole bitmap words");
-
-// The index of v in the sorted set (label_in_set's bisection, which keeps the index), or -1
-__device__ __forceinline__ int by_label_slot(uint32_t v, const LabelFilter& f, const uint32_t* s_set) {
-  if (f.nset == 1) return v == f.single ? 0 : -1;
-  int lo = 0, len = f.nset;   // the last entry <= v, if there is one, is in [lo, lo + len)
-  while (len > 1) {
-    const int half = len >> 1;
-    lo = s_set[lo + half] <= v ? lo + half : lo;
-    len -= half;
-  }
-  return s_set[lo] == v ? lo : -1;
-}
 
 // Every lane of the wave calls this (converged): slot < 0 = no hit; key32 = the hit's score key, row = its row.  Rows
 // ascend with the lane, so among the lanes that share the largest key32 the HIGHEST lane holds the largest 64-bit key.
@@ -118,8 +105,7 @@ __global__ __launch_bounds__(BL_THREADS) void by_label_reduce_kernel(LabelFilter
       const bool in = i4 < n4;
       v[j] = in ? s4[i4] : make_float4(0.f, 0.f, 0.f, 0.f);
       lab[j] = (l4 && in) ? l4[i4] : make_uint4(0u, 0u, 0u, 0u);
-      // the four rows of a group share one bitmap word (the group starts at a multiple of 4)
-      dead[j] = (f.dead_bits && in) ? f.dead_bits[i4 >> 3] >> ((uint32_t)(i4 & 7) * 4u) : 0u;
+      dead[j] = dead_nibble(in ? f.dead_bits : nullptr, i4);
     }
 #pragma unroll
     for (int j = 0; j < BL_VPT; ++j) {
@@ -130,7 +116,7 @@ __global__ __launch_bounds__(BL_THREADS) void by_label_reduce_kernel(LabelFilter
       for (int e = 0; e < 4; ++e) {
         int slot = -1;
         const uint32_t kk = score_key(sc[e]);
-        if (i + e < f.n && !((dead[j] >> e) & 1u) && kk >= tkey) slot = by_label_slot(lb[e], f, s_set);
+        if (i + e < f.n && !((dead[j] >> e) & 1u) && kk >= tkey) slot = label_slot(lb[e], f, s_set);
         by_label_update(slot, kk, (uint32_t)(i + e), s_best, s_cnt);
       }
     }

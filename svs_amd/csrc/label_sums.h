@@ -10,10 +10,10 @@
 //
 //   1. label_sums_hist_kernel     One workgroup per strip of LS_STRIP consecutive rows of the range.  A row's label (the
 //                                 column, the call's row_labels, or 0) is searched in the set's LDS image
-//                                 (label_stage_set, by_label_slot); live rows by the bitmap.  An LDS table of u32 counts
+//                                 (label_stage_set, label_slot); live rows by the bitmap.  An LDS table of u32 counts
 //                                 (integer LDS atomics: order-free) goes out whole as hist[strip][slot].
 //   2. label_sums_scan_kernel     One workgroup per slot: the strips' counts of the slot become their exclusive prefix
-//                                 sums in place (label_scan_kernel's scheme); tot[slot] = the label's rows.  A
+//                                 sums in place (block_run_scan, as label_scan_kernel); tot[slot] = the label's rows.  A
 //                                 count-only call ends here.
 //   3. label_sums_plan_kernel     One workgroup: scans over the slots give each label's first list position and first
 //                                 chunk; then the chunk table, one entry (slot, first list position, length <= 256) per
@@ -45,7 +45,6 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include "by_label.h"
 #include "chunk.h"
 #include "labels.h"
 
@@ -82,9 +81,9 @@ __device__ __forceinline__ int label_sums_slot(const LabelFilter& f, const LsRan
   if (i >= g.nrows) return -1;
   int64_t row = g.r0 + i;
   row = row < 0 ? 0 : (row < f.n ? row : f.n - 1);
-  if (f.dead_bits && ((f.dead_bits[row >> 5] >> (uint32_t)(row & 31)) & 1u)) return -1;
+  if (row_dead(f.dead_bits, row)) return -1;
   const uint32_t v = g.row_labels ? g.row_labels[i] : (f.labels ? f.labels[row] : 0u);
-  return by_label_slot(v, f, s_set);
+  return label_slot(v, f, s_set);
 }
 
 // grid = ceil(nrows / LS_STRIP).  hist[blockIdx.x * f.nset + slot] = the strip's live rows of the slot's label.
@@ -107,30 +106,12 @@ __global__ __launch_bounds__(LS_THREADS) void label_sums_hist_kernel(LabelFilter
 }
 
 // grid = nset, one workgroup per slot.  hist[strip * nset + slot], strip < nstrips -> its exclusive prefix sum over the
-// strips, in place; tot[slot] = the sum.  Thread t takes a run of consecutive strips.
+// strips, in place (block_run_scan at stride nset; a prefix is below the range's rows, at most 2^32); tot[slot] = the sum.
 __global__ __launch_bounds__(LS_THREADS) void label_sums_scan_kernel(uint32_t* __restrict__ hist, int64_t nstrips, int nset,
                                                                      unsigned long long* __restrict__ tot) {
   __shared__ unsigned long long s_sum[LS_THREADS];
-  const int slot = blockIdx.x;
-  const int64_t per = (nstrips + LS_THREADS - 1) / LS_THREADS;
-  const int64_t i0 = (int64_t)threadIdx.x * per, i1 = i0 + per < nstrips ? i0 + per : nstrips;
-  unsigned long long sum = 0;
-  for (int64_t i = i0; i < i1; ++i) sum += hist[i * nset + slot];
-  s_sum[threadIdx.x] = sum;
-  __syncthreads();
-  for (int off = 1; off < LS_THREADS; off <<= 1) {   // inclusive scan of the runs' sums
-    const unsigned long long t = threadIdx.x >= off ? s_sum[threadIdx.x - off] : 0ull;
-    __syncthreads();
-    s_sum[threadIdx.x] += t;
-    __syncthreads();
-  }
-  unsigned long long run = s_sum[threadIdx.x] - sum;
-  for (int64_t i = i0; i < i1; ++i) {
-    const uint32_t c = hist[i * nset + slot];
-    hist[i * nset + slot] = (uint32_t)run;   // (a prefix is below the range's rows, at most 2^32)
-    run += c;
-  }
-  if (threadIdx.x == LS_THREADS - 1) tot[slot] = s_sum[threadIdx.x];
+  const unsigned long long total = block_run_scan<LS_THREADS>(hist + blockIdx.x, nstrips, nset, s_sum);
+  if (threadIdx.x == LS_THREADS - 1) tot[blockIdx.x] = total;
 }
 
 // One workgroup.  tot[0 .. nset) -> lbase[slot] = the list position of the label's first row, cbase[slot] = its first
@@ -148,14 +129,8 @@ __global__ __launch_bounds__(LS_PLAN_THREADS) void label_sums_plan_kernel(const 
   s_l[t] = cnt;
   s_c[t] = nch;
   s_n[t] = cnt;
-  __syncthreads();
-  for (int off = 1; off < LS_PLAN_THREADS; off <<= 1) {
-    const unsigned long long a = t >= off ? s_l[t - off] : 0ull, b = t >= off ? s_c[t - off] : 0ull;
-    __syncthreads();
-    s_l[t] += a;
-    s_c[t] += b;
-    __syncthreads();
-  }
+  unsigned long long* const both[2] = {s_l, s_c};
+  block_scan<LS_PLAN_THREADS>(both);
   if (t < nset) {
     lbase[t] = s_l[t] - cnt;
     cbase[t] = s_c[t] - nch;

@@ -25,6 +25,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "dead_bits.h"
+
 namespace svs {
 
 constexpr int LB_THREADS = 256;
@@ -36,7 +38,7 @@ constexpr int LB_MAX_SET = 1024;                      // SVS_LABELS_MAX_SET: the
 constexpr int LB_ROWS = 0, LB_VALUES = 1;             // label_write_kernel's payload
 
 // What a kernel of the filter is given: the column (null: every label is 0), the rows it covers, the dead-row bitmap
-// (bit r & 31 of word r >> 5; null when no row is masked), and the set -- nset == 0: every label matches; nset == 1:
+// (dead_bits.h; null when no row is masked), and the set -- nset == 0: every label matches; nset == 1:
 // `single`; nset >= 2: set[0 .. nset) on the device, strictly ascending.
 struct LabelFilter {
   const uint32_t* labels;
@@ -54,16 +56,61 @@ __device__ __forceinline__ void label_stage_set(const LabelFilter& f, uint32_t* 
   __syncthreads();
 }
 
-__device__ __forceinline__ bool label_in_set(uint32_t v, const LabelFilter& f, const uint32_t* s_set) {
-  if (f.nset == 0) return true;
-  if (f.nset == 1) return v == f.single;
+// The SLOT of v, its index in the sorted set (nset >= 1), or -1: one label a compare, more a bisection of the LDS image
+__device__ __forceinline__ int label_slot(uint32_t v, const LabelFilter& f, const uint32_t* s_set) {
   int lo = 0, len = f.nset;   // the last entry <= v, if there is one, is in [lo, lo + len)
-  while (len > 1) {
-    const int half = len >> 1;
-    lo = s_set[lo + half] <= v ? lo + half : lo;
-    len -= half;
+  bool hit;
+  if (f.nset == 1) hit = v == f.single;
+  else {
+    while (len > 1) {
+      const int half = len >> 1;
+      lo = s_set[lo + half] <= v ? lo + half : lo;
+      len -= half;
+    }
+    hit = s_set[lo] == v;
   }
-  return s_set[lo] == v;
+  return hit ? lo : -1;
+}
+
+__device__ __forceinline__ bool label_in_set(uint32_t v, const LabelFilter& f, const uint32_t* s_set) {
+  return f.nset == 0 || label_slot(v, f, s_set) >= 0;
+}
+
+// Every thread of a workgroup of THREADS calls this with s[a][threadIdx.x] written: the NA arrays (LDS) become their
+// inclusive prefix sums (Hillis-Steele, the arrays side by side between one pair of barriers per step).
+template <int THREADS, int NA, class S>
+__device__ __forceinline__ void block_scan(S* const (&s)[NA]) {
+  const int t = threadIdx.x;
+  __syncthreads();
+  for (int off = 1; off < THREADS; off <<= 1) {
+    S add[NA];
+#pragma unroll
+    for (int a = 0; a < NA; ++a) add[a] = t >= off ? s[a][t - off] : (S)0;
+    __syncthreads();
+#pragma unroll
+    for (int a = 0; a < NA; ++a) s[a][t] += add[a];
+    __syncthreads();
+  }
+}
+
+// One workgroup of THREADS: items[i * stride], i < n, become their exclusive prefix sums in place; returns their sum.
+// Thread t takes a run of consecutive items; the runs' sums (type S) are scanned in s_sum[THREADS].
+template <int THREADS, class S>
+__device__ __forceinline__ S block_run_scan(uint32_t* items, int64_t n, int64_t stride, S* s_sum) {
+  const int64_t per = (n + THREADS - 1) / THREADS;
+  const int64_t i0 = (int64_t)threadIdx.x * per, i1 = i0 + per < n ? i0 + per : n;
+  S sum = 0;
+  for (int64_t i = i0; i < i1; ++i) sum += items[i * stride];
+  s_sum[threadIdx.x] = sum;
+  S* const runs[1] = {s_sum};
+  block_scan<THREADS>(runs);
+  S run = s_sum[threadIdx.x] - sum;
+  for (int64_t i = i0; i < i1; ++i) {
+    const uint32_t c = items[i * stride];
+    items[i * stride] = (uint32_t)run;   // (the callers' prefixes are below 2^32)
+    run += c;
+  }
+  return s_sum[THREADS - 1];
 }
 
 // The calling wave's part of strip `blockIdx.x`: b[j][e] = the ballot of "row row0 + 256 j + 4 lane + e matches",
@@ -79,7 +126,7 @@ __device__ __forceinline__ int label_strip_ballots(const LabelFilter& f, const u
     const int64_t i = w0 + j * 256 + lane * 4;   // a multiple of 4: one 16-byte load, one nibble of a bitmap word
     const bool in = i < f.n;
     v[j] = (f.labels && in) ? ((const uint4*)f.labels)[i >> 2] : make_uint4(0u, 0u, 0u, 0u);
-    dead[j] = (f.dead_bits && in) ? f.dead_bits[i >> 5] >> (uint32_t)(i & 31) : 0u;
+    dead[j] = dead_nibble(in ? f.dead_bits : nullptr, i >> 2);
   }
   int cnt = 0;
 #pragma unroll
@@ -117,27 +164,10 @@ __global__ __launch_bounds__(LB_THREADS) void label_count_kernel(LabelFilter f, 
   }
 }
 
-// One workgroup: counts[0 .. nb) -> their exclusive prefix sums, in place.  Thread t takes a run of consecutive counts.
+// One workgroup: counts[0 .. nb) -> their exclusive prefix sums, in place (block_run_scan).
 __global__ __launch_bounds__(LB_THREADS) void label_scan_kernel(uint32_t* __restrict__ counts, int64_t nb) {
   __shared__ uint32_t s_sum[LB_THREADS];
-  const int64_t per = (nb + LB_THREADS - 1) / LB_THREADS;
-  const int64_t i0 = (int64_t)threadIdx.x * per, i1 = i0 + per < nb ? i0 + per : nb;
-  uint32_t sum = 0;
-  for (int64_t i = i0; i < i1; ++i) sum += counts[i];
-  s_sum[threadIdx.x] = sum;
-  __syncthreads();
-  for (int off = 1; off < LB_THREADS; off <<= 1) {   // inclusive scan of the runs' sums
-    const uint32_t t = threadIdx.x >= off ? s_sum[threadIdx.x - off] : 0u;
-    __syncthreads();
-    s_sum[threadIdx.x] += t;
-    __syncthreads();
-  }
-  uint32_t run = s_sum[threadIdx.x] - sum;
-  for (int64_t i = i0; i < i1; ++i) {
-    const uint32_t c = counts[i];
-    counts[i] = run;
-    run += c;
-  }
+  (void)block_run_scan<LB_THREADS>(counts, nb, 1, s_sum);
 }
 
 // grid as label_count_kernel, same filter.  bases = the scanned counts; out[0 .. m) receives, in ascending row order,

@@ -15,6 +15,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "dead_bits.h"
 #include "gemv_f16.h"
 #include "gemv_f32.h"
 #include "keys.h"
@@ -225,7 +226,7 @@ __global__ __launch_bounds__(256) void rescore_f32_kernel(
         float s = row_dot_f32<NSTEP>(buf[u], qv);
         const int64_t row = r + u;
         if (lane == 0 && row < n) {
-          if (dead_bits && ((dead_bits[row >> 5] >> (row & 31)) & 1u)) s = -__builtin_inff();
+          if (row_dead(dead_bits, row)) s = -__builtin_inff();
           scores[row] = s;
         }
       }

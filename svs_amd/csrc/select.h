@@ -30,6 +30,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "dead_bits.h"
 #include "keys.h"
 
 namespace svs {
@@ -466,7 +467,7 @@ __global__ __launch_bounds__(FINAL_THREADS) void select_final_kernel(
       uint32_t dropped = 0;
       for (uint32_t i = threadIdx.x; i < n_cand; i += blockDim.x) {
         const uint32_t row = (uint32_t)cq[i];
-        if ((dead_bits[row >> 5] >> (row & 31)) & 1u) {
+        if (row_dead(dead_bits, row)) {
           cq[i] = 0ull;
           ++dropped;
         }
@@ -829,12 +830,12 @@ __global__ __launch_bounds__(256) void collect_pairs_kernel(
     if (threadIdx.x == 0) atomicExch(&gstate[1], 1u);
     return;
   }
-  if (dead_bits && ((dead_bits[i >> 5] >> (i & 31)) & 1u)) return;
+  if (row_dead(dead_bits, i)) return;
   const uint64_t* cq = cand + (int64_t)q * CAND_CAP;
   for (uint32_t c = threadIdx.x; c < n_cand; c += blockDim.x) {
     const uint64_t key = cq[c];
     const uint32_t j = (uint32_t)key;
-    if (dead_bits && ((dead_bits[j >> 5] >> (j & 31)) & 1u)) continue;
+    if (row_dead(dead_bits, j)) continue;
     const uint32_t slot = atomicAdd(&gstate[0], 1u);
     if (slot < cap) {
       out_key[slot] = (uint32_t)(key >> 32);

@@ -17,6 +17,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <initializer_list>
 #include <limits>
 #include <mutex>
 #include <shared_mutex>
@@ -252,30 +253,27 @@ struct Ctx {
   // and the call's picks; the candidates are read where the search left them, in out_s_pin / out_r_pin
   DevBuf<float> dv_G;
   PinBuf<float> dv_s_pin;       PinBuf<int64_t> dv_r_pin;     PinBuf<float> dv_red_pin;
-  // svs_index_search_labeled (labels.h): the sorted set (pinned copy, device copy); the call's total (one u64) followed
-  // by the per-strip counts, which the scan turns into the strips' bases; the total's pinned copy; and the list
-  // positions the top-k stage writes, mapped to rows on the device.  The list itself is list_dev.
+  // The call's labels, pinned and device copy: a sorted set (LabelSet::stage) or svs_index_assign's vector labels
   PinBuf<uint32_t> lab_set_pin; DevBuf<uint32_t> lab_set_dev;
+  // svs_index_search_labeled (labels.h): the call's total (one u64) followed by the per-strip counts, which the scan
+  // turns into the strips' bases; the total's pinned copy; and the list positions the top-k stage writes, mapped to
+  // rows on the device.  The list itself is list_dev.
   DevBuf<uint32_t> lab_cnt;     PinBuf<unsigned long long> lab_tot_pin;
   DevBuf<int64_t> lab_pos;
   // svs_index_search_by_label (by_label.h): the query's table of BL_TAB_WORDS words, zeroed when allocated and left
   // zeroed by the final kernel; the workgroups' partial tables (svs_internal_tune(7, 1) only); per query the labels and
-  // totals the device wrote (scores and rows: out_s_pin / out_r_pin), then nq counts followed by nq group counts.  The
-  // set is lab_set_pin / lab_set_dev.
+  // totals the device wrote (scores and rows: out_s_pin / out_r_pin), then nq counts followed by nq group counts.
   DevBuf<unsigned long long> bl_tab;
   DevBuf<unsigned long long> bl_part_best; DevBuf<uint32_t> bl_part_cnt;
   PinBuf<uint32_t> bl_lab_pin;  PinBuf<int64_t> bl_tot_pin;   PinBuf<int32_t> bl_cnt_pin;
   // svs_index_assign (assign.h): the call's vectors in the index's storage format (rows of ld elements; fp8: their
-  // scales), the per-row results, the counts and the vectors' labels.  The f32 vectors go up through q_pin / q_dev, the
-  // labels through lab_set_pin.
+  // scales), the per-row results and the counts.  The f32 vectors go up through q_pin / q_dev.
   DevBuf<uint8_t> as_vec;       DevBuf<float> as_vec_scales;
   DevBuf<int32_t> as_best;      DevBuf<float> as_score;
   DevBuf<unsigned long long> as_cnt;
-  DevBuf<uint32_t> as_lab;
   // svs_index_label_sums (label_sums.h): the call's row_labels on the device; the strips' histogram; per slot the
   // label's rows, its first list position and its first chunk (3 LB_MAX_SET + 1 words); the label-major row list; the
   // chunk table; the chunks' partial sums; the (nset, d) image of the sums and its pinned copy; the counts' pinned copy.
-  // The set is lab_set_pin / lab_set_dev.
   DevBuf<uint32_t> ls_lab;      DevBuf<uint32_t> ls_hist;
   DevBuf<unsigned long long> ls_tot;
   DevBuf<uint32_t> ls_list;     DevBuf<LsChunk> ls_table;
@@ -2189,6 +2187,95 @@ void launch_label_write(const LabelFilter& f, uint32_t* cnt, uint32_t* out, int6
   hipLaunchKernelGGL((label_write_kernel<PAYLOAD>), dim3((unsigned)label_strips(f.n)), dim3(LB_THREADS), 0, st, f, (const uint32_t*)(cnt + 2), out, m);
 }
 
+// A caller's label set, sorted and without repeats: a label's SLOT in every table of the device is its index here
+struct LabelSet {
+  std::vector<uint32_t> set;
+  int nset = 0;
+  // The caller's arguments, checked where the entry checked them; build (entry: the ABI name, for the message) follows
+  static int check(const uint32_t* labels, int32_t nlabels) {
+    if (nlabels < 0) return fail(SVS_ERR_INVALID, "nlabels must be >= 0");
+    return nlabels > 0 && !labels ? fail(SVS_ERR_INVALID, "null labels") : (int)SVS_OK;
+  }
+  int build(const char* entry, const uint32_t* labels, int32_t nlabels) {
+    try {
+      set.assign(labels, labels + nlabels);
+    } catch (const std::bad_alloc&) {
+      return fail(SVS_ERR_NOMEM, "out of host memory for %d labels", (int)nlabels);
+    }
+    std::sort(set.begin(), set.end());
+    set.erase(std::unique(set.begin(), set.end()), set.end());
+    if (set.size() > (size_t)SVS_LABELS_MAX_SET)
+      return fail(SVS_ERR_UNSUPPORTED, "%s: %zu distinct labels; a set holds at most %d", entry, set.size(), SVS_LABELS_MAX_SET);
+    nset = (int)set.size();
+    return SVS_OK;
+  }
+  size_t slot_of(uint32_t label) const { return (size_t)(std::lower_bound(set.begin(), set.end(), label) - set.begin()); }
+  // Two labels or more go up on st through the context's pinned copy (one is a kernel argument); *f = the index's filter
+  int stage(const svs_index* idx, Ctx* c, hipStream_t st, LabelFilter* f) const {
+    if (nset >= 2) {
+      int rc;
+      if ((rc = c->lab_set_pin.grow((size_t)nset)) != SVS_OK || (rc = c->lab_set_dev.grow((size_t)nset)) != SVS_OK) return rc;
+      memcpy(c->lab_set_pin, set.data(), (size_t)nset * sizeof(uint32_t));
+      HIP_TRY(hipMemcpyAsync(c->lab_set_dev, c->lab_set_pin, (size_t)nset * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+    }
+    *f = label_filter(idx, set.data(), nset, c->lab_set_dev);
+    return SVS_OK;
+  }
+};
+
+// The local range of a caller's [row0, row0 + nrows) of GLOBAL rows: nrows < 0 is refused, and so is a range, empty or
+// not, that is not inside the index
+int label_range(const svs_index* idx, const char* entry, int64_t row0, int64_t nrows, int64_t* r0) {
+  if (nrows < 0) return fail(SVS_ERR_INVALID, "nrows must be >= 0");
+  *r0 = row0 - idx->row_offset;
+  if (*r0 < 0 || *r0 > idx->n || nrows > idx->n - *r0)
+    return fail(SVS_ERR_INVALID, "%s: rows [%lld, %lld) outside [%lld, %lld)", entry, (long long)row0, (long long)(row0 + nrows),
+                (long long)idx->row_offset, (long long)(idx->row_offset + idx->n));
+  return SVS_OK;
+}
+
+// The entries that gather rows (gather.h) refuse rows no gather kernel takes
+int check_gather_rows(const svs_index* idx, const char* entry) {
+  return gather_rows_per_wave(idx) != 0 ? (int)SVS_OK
+      : fail(SVS_ERR_UNSUPPORTED, "%s: rows of %zu bytes; the gather kernels take rows of up to 16 KiB", entry, (size_t)idx->ld * elem_bytes(idx));
+}
+
+// Per-query cut-offs (svs_index_search_above, svs_index_search_by_label): none may be NaN; null: no cut-offs
+int check_cutoffs(const char* entry, const float* min_scores, int32_t nq) {
+  for (int32_t q = 0; min_scores && q < nq; ++q)
+    if (min_scores[q] != min_scores[q]) return fail(SVS_ERR_INVALID, "%s: the cut-off of query %d is NaN", entry, (int)q);
+  return SVS_OK;
+}
+
+// Uploaded query q (c->q_dev) scored into the context's one score vector
+int launch_query_scores(const svs_index* idx, Ctx* c, const SingleRoute& route, int32_t q, hipStream_t st) {
+  launch_record("gemv", idx->n, 1);
+  return launch_scores(idx, c, route, c->q_dev + (size_t)q * idx->d, c->scores, st);
+}
+
+// svs_index_set_timing: the two events around a call's kernels, made only when wanted (the index is timed and the call
+// runs what is timed) and destroyed on every exit.  ms(), once the stream has drained: begin to end, or -1.
+struct TimedSpan {
+  hipEvent_t ev[2] = {nullptr, nullptr};
+  const bool on;
+  explicit TimedSpan(bool wanted) : on(wanted && hipEventCreate(&ev[0]) == hipSuccess && hipEventCreate(&ev[1]) == hipSuccess) {}
+  ~TimedSpan() { for (hipEvent_t e : ev) if (e) (void)hipEventDestroy(e); }
+  void begin(hipStream_t st) const { if (on) (void)hipEventRecord(ev[0], st); }
+  void end(hipStream_t st) const { if (on) (void)hipEventRecord(ev[1], st); }
+  double ms() const { float t = 0.f; return on && hipEventElapsedTime(&t, ev[0], ev[1]) == hipSuccess ? (double)t : -1.0; }
+};
+
+// Behind a call's launches: they were accepted, the copies are enqueued (a null dst: nobody asked), the stream drains
+struct ReadBack { void* dst; const void* src; size_t bytes; };
+int read_back(HostCall& fr, const char* entry, std::initializer_list<ReadBack> copies) {
+  int rc = fr.launched(entry);
+  for (const ReadBack& r : copies) {
+    const hipError_t e = rc == SVS_OK && r.dst ? hipMemcpyAsync(r.dst, r.src, r.bytes, hipMemcpyDeviceToHost, fr.stream()) : hipSuccess;
+    if (e != hipSuccess) rc = fail(e == hipErrorOutOfMemory ? SVS_ERR_NOMEM : SVS_ERR_DEVICE, "%s read-back: %s", entry, hipGetErrorString(e));
+  }
+  return rc == SVS_OK ? fr.wait() : rc;
+}
+
 // Makes room for `rows` rows (caller holds the geometry lock exclusively).  exact == false grows
 // by 1.5x (amortised appends); exact == true (svs_index_reserve) allocates just `rows`.
 int ensure_capacity(svs_index* idx, int64_t rows, bool exact) {
@@ -2548,14 +2635,18 @@ int rerun_overflowed(svs_index* idx, HostCall& fr, int64_t q0, int64_t q1, int c
   return SVS_OK;
 }
 
-// nq results of `count` entries each (stride `count`) into the caller's block (stride k >= count)
+// nq results of `count` entries each (stride `count`) into the caller's block (stride k >= count).  counts (may be null):
+// the results are ragged, query qi has counts[qi] <= count entries (below 1: none)
 template <class T>
-void deliver_strided(T* dst, int k, const T* src, int count, int64_t nq) {
-  if (count == k) {   // (one piece)
+void deliver_strided(T* dst, int k, const T* src, int count, int64_t nq, const int32_t* counts = nullptr) {
+  if (count == k && !counts) {   // (one piece)
     memcpy(dst, src, (size_t)nq * count * sizeof(T));
     return;
   }
-  for (int64_t qi = 0; qi < nq; ++qi) memcpy(dst + (size_t)qi * k, src + (size_t)qi * count, (size_t)count * sizeof(T));
+  for (int64_t qi = 0; qi < nq; ++qi) {
+    const int c = counts ? counts[qi] : count;
+    if (c > 0) memcpy(dst + (size_t)qi * k, src + (size_t)qi * count, (size_t)c * sizeof(T));
+  }
 }
 
 // The pinned result block into the caller's
@@ -2610,8 +2701,15 @@ int upload_queries(Ctx* c, const float* queries, size_t qn, hipStream_t st) {
   return SVS_OK;
 }
 
-// ---- svs_index_assign (assign.h)
-thread_local double g_assign_kernel_ms = -1.0;   // svs_internal_assign_kernel_ms
+// ---- svs_index_assign, svs_index_label_sums: the timing hooks' readings, -1 from the moment a call of the entry begins
+// until that call has timed its kernels (TimedSpan); a call of the other entry never touches it
+thread_local double g_assign_kernel_ms = -1.0;       // svs_internal_assign_kernel_ms
+thread_local double g_label_sums_kernel_ms = -1.0;   // svs_internal_label_sums_kernel_ms
+int report_ms(double* out, double ms) {
+  if (!out) return fail(SVS_ERR_INVALID, "null output");
+  *out = ms;
+  return SVS_OK;
+}
 
 // accumulators per wave: one sweep of 64 vectors covers a small c, 256 per sweep beyond
 template <int DT, int NA>
@@ -3272,8 +3370,7 @@ int32_t svs_index_scores_n(svs_index* idx, const float* query, int32_t d, float*
   if ((rc = c->scores.grow((size_t)((idx->n + 3) & ~(int64_t)3))) != SVS_OK) return rc;
   const hipStream_t st = fr.stream();
   HIP_TRY(hipMemcpyAsync(c->q_dev, query, (size_t)d * sizeof(float), hipMemcpyHostToDevice, st));
-  launch_record("gemv", idx->n, 1);
-  if ((rc = launch_scores(idx, c, single_route(idx, idx->variant.load(), false), c->q_dev, c->scores, st)) != SVS_OK) return rc;
+  if ((rc = launch_query_scores(idx, c, single_route(idx, idx->variant.load(), false), 0, st)) != SVS_OK) return rc;
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipMemcpyAsync(out_scores, c->scores, (size_t)idx->n * sizeof(float), hipMemcpyDeviceToHost, st));
   return fr.wait();
@@ -3323,15 +3420,6 @@ int32_t svs_index_search_rows(svs_index* idx, const float* queries, int32_t nq, 
   return SVS_OK;
 }
 
-// The local range of a caller's [row0, row0 + nrows) of GLOBAL rows (svs_index_set_labels / _get_labels); nrows > 0
-static int label_range(const svs_index* idx, const char* entry, int64_t row0, int64_t nrows, int64_t* r0) {
-  *r0 = row0 - idx->row_offset;
-  if (*r0 < 0 || *r0 > idx->n || nrows > idx->n - *r0)
-    return fail(SVS_ERR_INVALID, "%s: rows [%lld, %lld) outside [%lld, %lld)", entry, (long long)row0, (long long)(row0 + nrows),
-                (long long)idx->row_offset, (long long)(idx->row_offset + idx->n));
-  return SVS_OK;
-}
-
 // The first write of the label column (under the exclusive geometry lock): a zero column for the row CAPACITY
 static int label_column_ensure(svs_index* idx, const char* entry) {
   if (idx->labels) return SVS_OK;
@@ -3352,7 +3440,6 @@ int32_t svs_index_set_labels(svs_index* idx, int64_t row0, int64_t nrows, const 
   if (!idx) return fail(SVS_ERR_INVALID, "null index");
   RefGuard guard(idx);
   std::unique_lock<std::shared_mutex> geo(idx->rw);   // no labelled search is between its count and its write
-  if (nrows < 0) return fail(SVS_ERR_INVALID, "nrows must be >= 0");
   if (nrows == 0) return SVS_OK;
   int64_t r0;
   int rc = label_range(idx, "svs_index_set_labels", row0, nrows, &r0);
@@ -3372,10 +3459,9 @@ int32_t svs_index_get_labels(svs_index* idx, int64_t row0, int64_t nrows, uint32
   if (!idx) return fail(SVS_ERR_INVALID, "null index");
   RefGuard guard(idx);
   std::shared_lock<std::shared_mutex> geo(idx->rw);
-  if (nrows < 0) return fail(SVS_ERR_INVALID, "nrows must be >= 0");
   if (nrows == 0) return SVS_OK;
   int64_t r0;
-  int rc = label_range(idx, "svs_index_get_labels", row0, nrows, &r0);
+  const int rc = label_range(idx, "svs_index_get_labels", row0, nrows, &r0);
   if (rc != SVS_OK) return rc;
   if (!out) return fail(SVS_ERR_INVALID, "null output");
   if (!idx->labels) {
@@ -3397,43 +3483,27 @@ int32_t svs_index_search_labeled(svs_index* idx, const float* queries, int32_t n
   std::shared_lock<std::shared_mutex> geo(idx->rw);   // (set_labels, mask_rows, compact take it exclusively: the count and the write see one column)
   int rc = check_query_args(idx, queries, nq, d);
   if (rc != SVS_OK) return rc;
-  if (nlabels < 0) return fail(SVS_ERR_INVALID, "nlabels must be >= 0");
-  if (nlabels > 0 && !labels) return fail(SVS_ERR_INVALID, "null labels");
-  // the set: sorted, without repeats
-  std::vector<uint32_t> set;
-  try {
-    set.assign(labels, labels + nlabels);
-  } catch (const std::bad_alloc&) {
-    return fail(SVS_ERR_NOMEM, "out of host memory for %d labels", (int)nlabels);
-  }
-  std::sort(set.begin(), set.end());
-  set.erase(std::unique(set.begin(), set.end()), set.end());
-  if (set.size() > (size_t)SVS_LABELS_MAX_SET)
-    return fail(SVS_ERR_UNSUPPORTED, "svs_index_search_labeled: %zu distinct labels; a set holds at most %d", set.size(), SVS_LABELS_MAX_SET);
-  const int nset = (int)set.size();
+  LabelSet ls;
+  if ((rc = LabelSet::check(labels, nlabels)) != SVS_OK || (rc = ls.build("svs_index_search_labeled", labels, nlabels)) != SVS_OK) return rc;
+  const int nset = ls.nset;
   const bool ranks = nq > 0 && k > 0 && nset > 0;   // results are wanted, if a row matches
   if (ranks && (!out_scores || !out_rows)) return fail(SVS_ERR_INVALID, "null output");
-  if (ranks && gather_rows_per_wave(idx) == 0)
-    return fail(SVS_ERR_UNSUPPORTED, "svs_index_search_labeled: rows of %zu bytes; the gather kernels take rows of up to 16 KiB",
-                (size_t)idx->ld * elem_bytes(idx));
-  if (nset == 0 || (!ranks && !out_matched)) {   // the empty set, or nothing to rank and nobody to tell the count
-    if (out_count) *out_count = 0;
-    if (out_matched) *out_matched = 0;
-    return SVS_OK;
-  }
+  if (ranks && (rc = check_gather_rows(idx, "svs_index_search_labeled")) != SVS_OK) return rc;
+  const auto done = [&](int count, int64_t m) {   // every successful exit: the entries written, the rows that matched
+    if (out_count) *out_count = count;
+    if (out_matched) *out_matched = m;
+    return (int32_t)SVS_OK;
+  };
+  if (nset == 0 || (!ranks && !out_matched)) return done(0, 0);   // the empty set, or nothing to rank and nobody to tell the count
   HostCall fr(idx);
   if ((rc = fr.open()) != SVS_OK) return rc;
   Ctx* const c = fr.c;
   const int64_t n = idx->n, lo = idx->row_offset;
   if ((rc = c->lab_cnt.grow((size_t)label_strips(n) + 2)) != SVS_OK || (rc = c->lab_tot_pin.grow(1)) != SVS_OK) return rc;
-  if (nset > 1 && ((rc = c->lab_set_pin.grow((size_t)nset)) != SVS_OK || (rc = c->lab_set_dev.grow((size_t)nset)) != SVS_OK)) return rc;
   // 1. the set goes up, the count runs; the host needs m = |S| to size the list, the score matrix and the select route
   hipStream_t st = fr.stream();
-  if (nset > 1) {
-    memcpy(c->lab_set_pin, set.data(), (size_t)nset * sizeof(uint32_t));
-    HIP_TRY(hipMemcpyAsync(c->lab_set_dev, c->lab_set_pin, (size_t)nset * sizeof(uint32_t), hipMemcpyHostToDevice, st));
-  }
-  const LabelFilter f = label_filter(idx, set.data(), nset, c->lab_set_dev);
+  LabelFilter f;
+  if ((rc = ls.stage(idx, c, st, &f)) != SVS_OK) return rc;
   launch_record("label_count_kernel", n, nset);
   launch_label_count(f, c->lab_cnt, st);
   HIP_TRY(hipMemcpyAsync(c->lab_tot_pin, c->lab_cnt, sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
@@ -3441,11 +3511,7 @@ int32_t svs_index_search_labeled(svs_index* idx, const float* queries, int32_t n
   const int64_t m = (int64_t)c->lab_tot_pin[0];
   if (m < 0 || m > n) return fail(SVS_ERR_DEVICE, "search_labeled: the filter counted %lld of %lld rows", (long long)m, (long long)n);
   const int count = ranks ? (int)std::min<int64_t>(k, m) : 0;
-  if (count == 0) {
-    if (out_count) *out_count = 0;
-    if (out_matched) *out_matched = m;
-    return SVS_OK;
-  }
+  if (count == 0) return done(0, m);
   // 2. the list is written on the device; from here on the call is svs_index_search_rows over it
   const size_t qn = (size_t)nq * (size_t)d, on = (size_t)nq * (size_t)count;
   if ((rc = c->list_dev.grow((size_t)m)) != SVS_OK || (rc = c->lab_pos.grow(on)) != SVS_OK) return rc;
@@ -3464,9 +3530,7 @@ int32_t svs_index_search_labeled(svs_index* idx, const float* queries, int32_t n
       return fail(SVS_ERR_DEVICE, "search_labeled: result %zu of query %zu is a position outside the %lld matching rows", i % (size_t)count,
                   i / (size_t)count, (long long)m);
   deliver_results(c, nq, count, k, out_scores, out_rows);
-  if (out_count) *out_count = count;
-  if (out_matched) *out_matched = m;
-  return SVS_OK;
+  return done(count, m);
 }
 
 int32_t svs_index_search_above(svs_index* idx, const float* queries, int32_t nq, int32_t d, const float* min_scores, int32_t limit,
@@ -3478,8 +3542,7 @@ int32_t svs_index_search_above(svs_index* idx, const float* queries, int32_t nq,
   int rc = check_query_args(idx, queries, nq, d);
   if (rc != SVS_OK) return rc;
   if (nq > 0 && !min_scores) return fail(SVS_ERR_INVALID, "null min_scores");
-  for (int32_t q = 0; q < nq; ++q)
-    if (min_scores[q] != min_scores[q]) return fail(SVS_ERR_INVALID, "svs_index_search_above: the cut-off of query %d is NaN", (int)q);
+  if ((rc = check_cutoffs("svs_index_search_above", min_scores, nq)) != SVS_OK) return rc;
   if (!out_counts) return fail(SVS_ERR_INVALID, "null out_counts");
   if (limit > 0 && nq > 0 && (!out_scores || !out_rows)) return fail(SVS_ERR_INVALID, "null output");
   if (nq == 0) return SVS_OK;
@@ -3506,8 +3569,7 @@ int32_t svs_index_search_above(svs_index* idx, const float* queries, int32_t nq,
   // every query back to back: score pass, filter, final -- the context's one score vector, header and candidate list
   // are reused in stream order; no host wait in between
   for (int32_t q = 0; q < nq; ++q) {
-    launch_record("gemv", n, 1);
-    if ((rc = launch_scores(idx, c, route, c->q_dev + (size_t)q * d, c->scores, st)) != SVS_OK) return rc;
+    if ((rc = launch_query_scores(idx, c, route, q, st)) != SVS_OK) return rc;
     launch_record("above_filter_kernel", n, 1);
     hipLaunchKernelGGL(above_filter_kernel, dim3(blocks), dim3(FA_THREADS), 0, st, (const float*)c->scores.p, n, score_key(min_scores[q]),
                        dead_bits, c->hist.p, c->cand.p);
@@ -3515,6 +3577,8 @@ int32_t svs_index_search_above(svs_index* idx, const float* queries, int32_t nq,
                        c->out_s_pin + (size_t)q * ls, c->out_r_pin + (size_t)q * ls, c->above_cnt_pin + q, c->above_tot_pin + q);
   }
   if ((rc = fr.close("search_above")) != SVS_OK) return rc;
+  deliver_strided(out_scores, limit, c->out_s_pin.p, ls, nq, c->above_cnt_pin.p);   // (the device-complete queries)
+  deliver_strided(out_rows, limit, c->out_r_pin.p, ls, nq, c->above_cnt_pin.p);
   for (int32_t q = 0; q < nq; ++q) {
     const int64_t total = c->above_tot_pin[q];
     int count = c->above_cnt_pin[q];
@@ -3525,8 +3589,7 @@ int32_t svs_index_search_above(svs_index* idx, const float* queries, int32_t nq,
       count = (int)std::min<int64_t>(lim, total);
       if ((rc = c->redo_s_pin.grow((size_t)count)) != SVS_OK || (rc = c->redo_r_pin.grow((size_t)count)) != SVS_OK) return rc;
       st = fr.stream();
-      launch_record("gemv", n, 1);
-      if ((rc = launch_scores(idx, c, route, c->q_dev + (size_t)q * d, c->scores, st)) != SVS_OK) return rc;
+      if ((rc = launch_query_scores(idx, c, route, q, st)) != SVS_OK) return rc;
       if (masked)
         hipLaunchKernelGGL(mask_dead_rows_kernel, dim3(64), dim3(256), 0, st, c->scores.p, sstride, 1, (const uint32_t*)idx->dead_dev.p,
                            (int64_t)idx->dead_list.size(), n, (int64_t)0);
@@ -3536,9 +3599,6 @@ int32_t svs_index_search_above(svs_index* idx, const float* queries, int32_t nq,
       if ((rc = fr.close("search_above", true)) != SVS_OK) return rc;
       memcpy(out_scores + (size_t)q * limit, c->redo_s_pin, (size_t)count * sizeof(float));
       memcpy(out_rows + (size_t)q * limit, c->redo_r_pin, (size_t)count * sizeof(int64_t));
-    } else if (count > 0) {
-      memcpy(out_scores + (size_t)q * limit, c->out_s_pin + (size_t)q * ls, (size_t)count * sizeof(float));
-      memcpy(out_rows + (size_t)q * limit, c->out_r_pin + (size_t)q * ls, (size_t)count * sizeof(int64_t));
     }
     out_counts[q] = count;
     if (out_totals) out_totals[q] = total;
@@ -3562,24 +3622,12 @@ int32_t svs_index_search_by_label(svs_index* idx, const float* queries, int32_t 
   std::shared_lock<std::shared_mutex> geo(idx->rw);   // (set_labels, mask_rows, compact take it exclusively: every query sees one column)
   int rc = check_query_args(idx, queries, nq, d);
   if (rc != SVS_OK) return rc;
-  if (nlabels < 0) return fail(SVS_ERR_INVALID, "nlabels must be >= 0");
-  if (nlabels > 0 && !labels) return fail(SVS_ERR_INVALID, "null labels");
-  if (min_scores)
-    for (int32_t q = 0; q < nq; ++q)
-      if (min_scores[q] != min_scores[q]) return fail(SVS_ERR_INVALID, "svs_index_search_by_label: the cut-off of query %d is NaN", (int)q);
+  if ((rc = LabelSet::check(labels, nlabels)) != SVS_OK) return rc;
+  if ((rc = check_cutoffs("svs_index_search_by_label", min_scores, nq)) != SVS_OK) return rc;
   if (!out_counts) return fail(SVS_ERR_INVALID, "null out_counts");
-  // the set: sorted, without repeats; a label's slot in every table is its index here
-  std::vector<uint32_t> set;
-  try {
-    set.assign(labels, labels + nlabels);
-  } catch (const std::bad_alloc&) {
-    return fail(SVS_ERR_NOMEM, "out of host memory for %d labels", (int)nlabels);
-  }
-  std::sort(set.begin(), set.end());
-  set.erase(std::unique(set.begin(), set.end()), set.end());
-  if (set.size() > (size_t)SVS_LABELS_MAX_SET)
-    return fail(SVS_ERR_UNSUPPORTED, "svs_index_search_by_label: %zu distinct labels; a set holds at most %d", set.size(), SVS_LABELS_MAX_SET);
-  const int nset = (int)set.size();
+  LabelSet ls;
+  if ((rc = ls.build("svs_index_search_by_label", labels, nlabels)) != SVS_OK) return rc;
+  const int nset = ls.nset;
   if (k > 0 && nq > 0 && nset > 0 && (!out_labels || !out_scores || !out_rows || !out_totals)) return fail(SVS_ERR_INVALID, "null output");
   if (nq == 0 || nset == 0) {
     for (int32_t q = 0; q < nq; ++q) {
@@ -3600,7 +3648,6 @@ int32_t svs_index_search_by_label(svs_index* idx, const float* queries, int32_t 
   if ((rc = c->out_s_pin.grow(on)) != SVS_OK || (rc = c->out_r_pin.grow(on)) != SVS_OK) return rc;
   if ((rc = c->bl_lab_pin.grow(on)) != SVS_OK || (rc = c->bl_tot_pin.grow(on)) != SVS_OK || (rc = c->bl_cnt_pin.grow((size_t)nq * 2)) != SVS_OK) return rc;
   if ((rc = c->scores.grow((size_t)((n + 3) & ~(int64_t)3))) != SVS_OK) return rc;
-  if (nset > 1 && ((rc = c->lab_set_pin.grow((size_t)nset)) != SVS_OK || (rc = c->lab_set_dev.grow((size_t)nset)) != SVS_OK)) return rc;
   if (cross == BL_PARTIALS) {
     if ((rc = c->bl_part_best.grow((size_t)blocks * nset)) != SVS_OK || (rc = c->bl_part_cnt.grow((size_t)blocks * nset)) != SVS_OK) return rc;
   } else if (!c->bl_tab.p) {
@@ -3610,17 +3657,13 @@ int32_t svs_index_search_by_label(svs_index* idx, const float* queries, int32_t 
   }
   const SingleRoute route = single_route(idx, idx->variant.load(), false);   // the kernel svs_index_scores_n runs
   if ((rc = upload_queries(c, queries, qn, st)) != SVS_OK) return rc;
-  if (nset > 1) {
-    memcpy(c->lab_set_pin, set.data(), (size_t)nset * sizeof(uint32_t));
-    HIP_TRY(hipMemcpyAsync(c->lab_set_dev, c->lab_set_pin, (size_t)nset * sizeof(uint32_t), hipMemcpyHostToDevice, st));
-  }
-  const LabelFilter f = label_filter(idx, set.data(), nset, c->lab_set_dev);
+  LabelFilter f;
+  if ((rc = ls.stage(idx, c, st, &f)) != SVS_OK) return rc;
   // every query back to back: score pass, reduce, final -- the context's one score vector and one table are reused in
   // stream order; no host wait in between
   for (int32_t q = 0; q < nq; ++q) {
     const uint32_t tkey = score_key(min_scores ? min_scores[q] : -std::numeric_limits<float>::infinity());
-    launch_record("gemv", n, 1);
-    if ((rc = launch_scores(idx, c, route, c->q_dev + (size_t)q * d, c->scores, st)) != SVS_OK) return rc;
+    if ((rc = launch_query_scores(idx, c, route, q, st)) != SVS_OK) return rc;
     launch_record("by_label_reduce_kernel", n, 1);
     if (cross == BL_PARTIALS)
       hipLaunchKernelGGL(by_label_reduce_kernel<BL_PARTIALS>, dim3(blocks), dim3(BL_THREADS), 0, st, f, (const float*)c->scores.p, tkey,
@@ -3639,17 +3682,12 @@ int32_t svs_index_search_by_label(svs_index* idx, const float* queries, int32_t 
     if (count < 0 || count > ks || groups < count || groups > nset)
       return fail(SVS_ERR_DEVICE, "search_by_label: query %d came back with %d entries of %d groups (%d labels)", (int)q, count, groups, nset);
   }
-  for (int32_t q = 0; q < nq; ++q) {
-    const size_t count = (size_t)c->bl_cnt_pin[q], from = (size_t)q * ks, to = (size_t)q * k;
-    if (count) {
-      memcpy(out_labels + to, c->bl_lab_pin + from, count * sizeof(uint32_t));
-      memcpy(out_scores + to, c->out_s_pin + from, count * sizeof(float));
-      memcpy(out_rows + to, c->out_r_pin + from, count * sizeof(int64_t));
-      memcpy(out_totals + to, c->bl_tot_pin + from, count * sizeof(int64_t));
-    }
-    out_counts[q] = (int32_t)count;
-    if (out_groups) out_groups[q] = c->bl_cnt_pin[nq + q];
-  }
+  deliver_strided(out_labels, k, c->bl_lab_pin.p, ks, nq, c->bl_cnt_pin.p);
+  deliver_strided(out_scores, k, c->out_s_pin.p, ks, nq, c->bl_cnt_pin.p);
+  deliver_strided(out_rows, k, c->out_r_pin.p, ks, nq, c->bl_cnt_pin.p);
+  deliver_strided(out_totals, k, c->bl_tot_pin.p, ks, nq, c->bl_cnt_pin.p);
+  memcpy(out_counts, c->bl_cnt_pin, (size_t)nq * sizeof(int32_t));
+  if (out_groups) memcpy(out_groups, c->bl_cnt_pin + nq, (size_t)nq * sizeof(int32_t));
   return SVS_OK;
 }
 
@@ -3659,6 +3697,7 @@ static_assert(SVS_ASSIGN_MAX_VECTORS == SVS_LABELS_MAX_SET, "every label an assi
 int32_t svs_index_assign(svs_index* idx, const float* vectors, int32_t c, int32_t d, int64_t row0, int64_t nrows,
                          const uint32_t* vector_labels, int32_t* out_best, float* out_scores, int64_t* out_counts) {
   launch_reset();
+  g_assign_kernel_ms = -1.0;   // (a call that fails or records nothing leaves no earlier call's time behind)
   if (!idx) return fail(SVS_ERR_INVALID, "null index");
   RefGuard guard(idx);
   // with labels to write: exclusive for the whole call, as svs_index_set_labels (no labelled search is between its count
@@ -3671,7 +3710,7 @@ int32_t svs_index_assign(svs_index* idx, const float* vectors, int32_t c, int32_
   if (d != idx->d || idx->n == 0 || idx->d == 0)
     return fail(SVS_ERR_SHAPE, "shapes (%lld,%d) and (%d,) not aligned: %d (dim 1) != %d (dim 0)", (long long)idx->n, idx->d, d, idx->d, d);
   if (c <= 0) return fail(SVS_ERR_INVALID, "svs_index_assign: c must be >= 1, got %d", (int)c);
-  if (nrows < 0) return fail(SVS_ERR_INVALID, "nrows must be >= 0");
+  if (nrows < 0) return fail(SVS_ERR_INVALID, "nrows must be >= 0");   // (reported ahead of the vectors' faults, as ever)
   if (!vectors) return fail(SVS_ERR_INVALID, "null vectors");
   if (c > SVS_ASSIGN_MAX_VECTORS)
     return fail(SVS_ERR_UNSUPPORTED, "svs_index_assign: %d vectors; a call takes at most %d", (int)c, SVS_ASSIGN_MAX_VECTORS);
@@ -3692,7 +3731,7 @@ int32_t svs_index_assign(svs_index* idx, const float* vectors, int32_t c, int32_
   if (out_best && (rc = cx->as_best.grow((size_t)nrows)) != SVS_OK) return rc;
   if (out_scores && (rc = cx->as_score.grow((size_t)nrows)) != SVS_OK) return rc;
   if (out_counts && (rc = cx->as_cnt.grow((size_t)c)) != SVS_OK) return rc;
-  if (vector_labels && ((rc = cx->as_lab.grow((size_t)c)) != SVS_OK || (rc = cx->lab_set_pin.grow((size_t)c)) != SVS_OK)) return rc;
+  if (vector_labels && ((rc = cx->lab_set_dev.grow((size_t)c)) != SVS_OK || (rc = cx->lab_set_pin.grow((size_t)c)) != SVS_OK)) return rc;
   if ((rc = cx->q_dev.grow((size_t)c * d)) != SVS_OK || (rc = cx->q_pin.grow((size_t)c * d)) != SVS_OK) return rc;
   // the column last: a call that fails above has allocated none
   if (vector_labels && (rc = label_column_ensure(idx, "svs_index_assign")) != SVS_OK) return rc;
@@ -3705,15 +3744,14 @@ int32_t svs_index_assign(svs_index* idx, const float* vectors, int32_t c, int32_
   HIP_TRY(ingest_rows_into(idx, cx->as_vec.p, cx->as_vec_scales.p, cx->q_dev, c, d, 0, hipMemcpyDeviceToDevice, iblocks, st));
   if (vector_labels) {
     memcpy(cx->lab_set_pin, vector_labels, (size_t)c * sizeof(uint32_t));
-    HIP_TRY(hipMemcpyAsync(cx->as_lab, cx->lab_set_pin, (size_t)c * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(cx->lab_set_dev, cx->lab_set_pin, (size_t)c * sizeof(uint32_t), hipMemcpyHostToDevice, st));
   }
   if (out_counts) HIP_TRY(hipMemsetAsync(cx->as_cnt, 0, (size_t)c * sizeof(unsigned long long), st));
-  // ---- one launch over the range (svs_index_set_timing: events around it, read by svs_internal_assign_kernel_ms)
-  hipEvent_t ev0 = nullptr, ev1 = nullptr;
-  const bool timed = idx->timing.load() > 0 && hipEventCreate(&ev0) == hipSuccess && hipEventCreate(&ev1) == hipSuccess;
-  if (timed) (void)hipEventRecord(ev0, st);
+  // ---- one launch over the range (svs_index_set_timing: a span around it, read by svs_internal_assign_kernel_ms)
+  const TimedSpan span(idx->timing.load() > 0);
+  span.begin(st);
   launch_record("assign_rows_kernel", nrows, c);
-  const uint32_t* const k_lab = vector_labels ? cx->as_lab.p : nullptr;
+  const uint32_t* const k_lab = vector_labels ? cx->lab_set_dev.p : nullptr;
   int32_t* const k_best = out_best ? cx->as_best.p : nullptr;
   float* const k_score = out_scores ? cx->as_score.p : nullptr;
   uint32_t* const k_col = vector_labels ? idx->labels : nullptr;
@@ -3723,33 +3761,17 @@ int32_t svs_index_assign(svs_index* idx, const float* vectors, int32_t c, int32_
     if (c <= assign_sweep(1)) launch_assign_na<DT, 1>(idx, cx, c, r0, nrows, k_lab, k_best, k_score, k_col, k_cnt, st);
     else launch_assign_na<DT, 4>(idx, cx, c, r0, nrows, k_lab, k_best, k_score, k_col, k_cnt, st);
   });
-  if (timed) (void)hipEventRecord(ev1, st);
-  rc = fr.launched("assign");
-  auto hip_status = [](hipError_t e) {
-    return e == hipSuccess ? (int)SVS_OK : fail(e == hipErrorOutOfMemory ? SVS_ERR_NOMEM : SVS_ERR_DEVICE, "assign read-back: %s", hipGetErrorString(e));
-  };
-  if (rc == SVS_OK && out_best) rc = hip_status(hipMemcpyAsync(out_best, cx->as_best, (size_t)nrows * sizeof(int32_t), hipMemcpyDeviceToHost, st));
-  if (rc == SVS_OK && out_scores) rc = hip_status(hipMemcpyAsync(out_scores, cx->as_score, (size_t)nrows * sizeof(float), hipMemcpyDeviceToHost, st));
-  if (rc == SVS_OK && out_counts) rc = hip_status(hipMemcpyAsync(out_counts, cx->as_cnt, (size_t)c * sizeof(int64_t), hipMemcpyDeviceToHost, st));
-  if (rc == SVS_OK) rc = fr.wait();
-  g_assign_kernel_ms = -1.0;
-  if (timed && rc == SVS_OK) {
-    float ms = 0.f;
-    if (hipEventElapsedTime(&ms, ev0, ev1) == hipSuccess) g_assign_kernel_ms = ms;
-  }
-  if (ev0) (void)hipEventDestroy(ev0);
-  if (ev1) (void)hipEventDestroy(ev1);
+  span.end(st);
+  rc = read_back(fr, "assign", {{out_best, cx->as_best.p, (size_t)nrows * sizeof(int32_t)},
+                                {out_scores, cx->as_score.p, (size_t)nrows * sizeof(float)},
+                                {out_counts, cx->as_cnt.p, (size_t)c * sizeof(int64_t)}});
+  if (rc == SVS_OK) g_assign_kernel_ms = span.ms();
   return rc;
 }
 
-int32_t svs_internal_assign_kernel_ms(double* out) {
-  if (!out) return fail(SVS_ERR_INVALID, "null output");
-  *out = g_assign_kernel_ms;
-  return SVS_OK;
-}
+int32_t svs_internal_assign_kernel_ms(double* out) { return report_ms(out, g_assign_kernel_ms); }
 
 // ---- svs_index_label_sums (label_sums.h)
-thread_local double g_label_sums_kernel_ms = -1.0;   // svs_internal_label_sums_kernel_ms
 static_assert(SVS_LABEL_SUMS_CHUNK == LS_CHUNK, "the chunk length is part of the sum's definition");
 
 int32_t svs_index_label_sums(svs_index* idx, const uint32_t* labels, int32_t nlabels, int64_t row0, int64_t nrows,
@@ -3763,33 +3785,19 @@ int32_t svs_index_label_sums(svs_index* idx, const uint32_t* labels, int32_t nla
   if (idx->n == 0 || idx->d == 0) return fail(SVS_ERR_SHAPE, "svs_index_label_sums: the index is empty");
   // (the list holds local rows as u32 and a strip prefix is a u32: ensure_capacity admits at most 2^32 - 1 rows per handle)
   if (idx->n > 0xffffffffll) return fail(SVS_ERR_UNSUPPORTED, "svs_index_label_sums: %lld rows; a handle holds fewer than 2^32", (long long)idx->n);
-  if (nlabels < 0) return fail(SVS_ERR_INVALID, "nlabels must be >= 0");
-  if (nrows < 0) return fail(SVS_ERR_INVALID, "nrows must be >= 0");
-  if (nlabels > 0 && !labels) return fail(SVS_ERR_INVALID, "null labels");
   int64_t r0;
-  int rc = label_range(idx, "svs_index_label_sums", row0, nrows, &r0);
-  if (rc != SVS_OK) return rc;
-  // the set: sorted, without repeats; a label's slot in every table is its index here
-  std::vector<uint32_t> set;
-  try {
-    set.assign(labels, labels + nlabels);
-  } catch (const std::bad_alloc&) {
-    return fail(SVS_ERR_NOMEM, "out of host memory for %d labels", (int)nlabels);
-  }
-  std::sort(set.begin(), set.end());
-  set.erase(std::unique(set.begin(), set.end()), set.end());
-  if (set.size() > (size_t)SVS_LABELS_MAX_SET)
-    return fail(SVS_ERR_UNSUPPORTED, "svs_index_label_sums: %zu distinct labels; a set holds at most %d", set.size(), SVS_LABELS_MAX_SET);
-  const int nset = (int)set.size(), d = idx->d;
+  int rc = LabelSet::check(labels, nlabels);
+  if (rc != SVS_OK || (rc = label_range(idx, "svs_index_label_sums", row0, nrows, &r0)) != SVS_OK) return rc;
+  LabelSet ls;
+  if ((rc = ls.build("svs_index_label_sums", labels, nlabels)) != SVS_OK) return rc;
+  const int nset = ls.nset, d = idx->d;
   if (nset == 0 || (!out_sums && !out_counts)) return SVS_OK;
   if (nrows == 0) {
     if (out_sums) std::fill(out_sums, out_sums + (size_t)nlabels * d, 0.0);
     if (out_counts) memset(out_counts, 0, (size_t)nlabels * sizeof(int64_t));
     return SVS_OK;
   }
-  if (out_sums && gather_rows_per_wave(idx) == 0)
-    return fail(SVS_ERR_UNSUPPORTED, "svs_index_label_sums: rows of %zu bytes; the gather kernels take rows of up to 16 KiB",
-                (size_t)idx->ld * elem_bytes(idx));
+  if (out_sums && (rc = check_gather_rows(idx, "svs_index_label_sums")) != SVS_OK) return rc;
   const int64_t nstrips = (nrows + LS_STRIP - 1) / LS_STRIP;
   const int64_t bound = (nrows + LS_CHUNK - 1) / LS_CHUNK + nset;   // chunks never cross a label: at most one ragged chunk each
   const int ld16 = (int)((size_t)idx->ld * elem_bytes(idx) / 16);
@@ -3800,18 +3808,14 @@ int32_t svs_index_label_sums(svs_index* idx, const uint32_t* labels, int32_t nla
       (rc = c->ls_cnt_pin.grow((size_t)nset)) != SVS_OK)
     return rc;
   if (row_labels && (rc = c->ls_lab.grow((size_t)nrows)) != SVS_OK) return rc;
-  if (nset > 1 && ((rc = c->lab_set_pin.grow((size_t)nset)) != SVS_OK || (rc = c->lab_set_dev.grow((size_t)nset)) != SVS_OK)) return rc;
   if (out_sums && ((rc = c->ls_list.grow((size_t)nrows)) != SVS_OK || (rc = c->ls_table.grow((size_t)bound)) != SVS_OK ||
                    (rc = c->ls_part.grow((size_t)bound * d)) != SVS_OK || (rc = c->ls_out.grow((size_t)nset * d)) != SVS_OK ||
                    (rc = c->ls_out_pin.grow((size_t)nset * d)) != SVS_OK))
     return rc;
   hipStream_t st = fr.stream();
-  if (nset > 1) {
-    memcpy(c->lab_set_pin, set.data(), (size_t)nset * sizeof(uint32_t));
-    HIP_TRY(hipMemcpyAsync(c->lab_set_dev, c->lab_set_pin, (size_t)nset * sizeof(uint32_t), hipMemcpyHostToDevice, st));
-  }
+  LabelFilter f;
+  if ((rc = ls.stage(idx, c, st, &f)) != SVS_OK) return rc;
   if (row_labels) HIP_TRY(hipMemcpyAsync(c->ls_lab, row_labels, (size_t)nrows * sizeof(uint32_t), hipMemcpyHostToDevice, st));
-  const LabelFilter f = label_filter(idx, set.data(), nset, c->lab_set_dev);
   const LsRange g{r0, nrows, row_labels ? c->ls_lab.p : nullptr};
   unsigned long long* const tot = c->ls_tot.p;
   unsigned long long* const lbase = tot + LB_MAX_SET;
@@ -3821,8 +3825,7 @@ int32_t svs_index_label_sums(svs_index* idx, const uint32_t* labels, int32_t nla
   hipLaunchKernelGGL(label_sums_hist_kernel, dim3((unsigned)nstrips), dim3(LS_THREADS), 0, st, f, g, c->ls_hist.p);
   launch_record("label_sums_scan_kernel", nrows, nset);
   hipLaunchKernelGGL(label_sums_scan_kernel, dim3((unsigned)nset), dim3(LS_THREADS), 0, st, c->ls_hist.p, nstrips, nset, tot);
-  hipEvent_t ev0 = nullptr, ev1 = nullptr;
-  bool timed = false;
+  const TimedSpan span(out_sums && idx->timing.load() > 0);
   if (out_sums) {
     // ---- 3, 4: the plan and the label-major list, on the device: no host wait before the sums
     launch_record("label_sums_plan_kernel", nrows, nset);
@@ -3831,9 +3834,8 @@ int32_t svs_index_label_sums(svs_index* idx, const uint32_t* labels, int32_t nla
     launch_record("label_sums_scatter_kernel", nrows, nset);
     hipLaunchKernelGGL(label_sums_scatter_kernel, dim3((unsigned)nstrips), dim3(LS_THREADS), 0, st, f, g, (const uint32_t*)c->ls_hist.p,
                        (const unsigned long long*)lbase, (const unsigned long long*)tot, c->ls_list.p, nrows);
-    // ---- 5, 6: chunk sums and fold (svs_index_set_timing: events around them, read by svs_internal_label_sums_kernel_ms)
-    timed = idx->timing.load() > 0 && hipEventCreate(&ev0) == hipSuccess && hipEventCreate(&ev1) == hipSuccess;
-    if (timed) (void)hipEventRecord(ev0, st);
+    // ---- 5, 6: chunk sums and fold (svs_index_set_timing: a span around them, read by svs_internal_label_sums_kernel_ms)
+    span.begin(st);
     launch_record("label_sums_chunk_kernel", nrows, nset);
     for_store_dtype(idx, [&](auto dt) {
       constexpr int DT = decltype(dt)::value;
@@ -3845,22 +3847,12 @@ int32_t svs_index_label_sums(svs_index* idx, const uint32_t* labels, int32_t nla
     hipLaunchKernelGGL(label_sums_fold_kernel, dim3((unsigned)((d + LS_FOLD_THREADS - 1) / LS_FOLD_THREADS), (unsigned)nset),
                        dim3(LS_FOLD_THREADS), 0, st, (const double*)c->ls_part.p, (const unsigned long long*)tot,
                        (const unsigned long long*)cbase, d, bound, c->ls_out.p);
-    if (timed) (void)hipEventRecord(ev1, st);
+    span.end(st);
   }
-  rc = fr.launched("label_sums");
-  auto hip_status = [](hipError_t e) {
-    return e == hipSuccess ? (int)SVS_OK : fail(e == hipErrorOutOfMemory ? SVS_ERR_NOMEM : SVS_ERR_DEVICE, "label_sums read-back: %s", hipGetErrorString(e));
-  };
-  if (rc == SVS_OK) rc = hip_status(hipMemcpyAsync(c->ls_cnt_pin, tot, (size_t)nset * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
-  if (rc == SVS_OK && out_sums) rc = hip_status(hipMemcpyAsync(c->ls_out_pin, c->ls_out, (size_t)nset * d * sizeof(double), hipMemcpyDeviceToHost, st));
-  if (rc == SVS_OK) rc = fr.wait();
-  if (timed && rc == SVS_OK) {
-    float ms = 0.f;
-    if (hipEventElapsedTime(&ms, ev0, ev1) == hipSuccess) g_label_sums_kernel_ms = ms;
-  }
-  if (ev0) (void)hipEventDestroy(ev0);
-  if (ev1) (void)hipEventDestroy(ev1);
+  rc = read_back(fr, "label_sums", {{c->ls_cnt_pin.p, tot, (size_t)nset * sizeof(unsigned long long)},
+                                    {out_sums ? c->ls_out_pin.p : nullptr, c->ls_out.p, (size_t)nset * d * sizeof(double)}});
   if (rc != SVS_OK) return rc;
+  g_label_sums_kernel_ms = span.ms();
   unsigned long long seen = 0;
   for (int s = 0; s < nset; ++s) {
     if (c->ls_cnt_pin[s] > (unsigned long long)nrows - seen)
@@ -3869,18 +3861,14 @@ int32_t svs_index_label_sums(svs_index* idx, const uint32_t* labels, int32_t nla
   }
   // ---- the device worked on the sorted distinct set: every position of the caller's gets its label's answer
   for (int32_t j = 0; j < nlabels; ++j) {
-    const size_t s = (size_t)(std::lower_bound(set.begin(), set.end(), labels[j]) - set.begin());
+    const size_t s = ls.slot_of(labels[j]);
     if (out_sums) memcpy(out_sums + (size_t)j * d, c->ls_out_pin + s * d, (size_t)d * sizeof(double));
     if (out_counts) out_counts[j] = (int64_t)c->ls_cnt_pin[s];
   }
   return SVS_OK;
 }
 
-int32_t svs_internal_label_sums_kernel_ms(double* out) {
-  if (!out) return fail(SVS_ERR_INVALID, "null output");
-  *out = g_label_sums_kernel_ms;
-  return SVS_OK;
-}
+int32_t svs_internal_label_sums_kernel_ms(double* out) { return report_ms(out, g_label_sums_kernel_ms); }
 
 // The similarity matrices of one block of queries: 64 MiB, i.e. 16 queries at fetch_k = SVS_DIVERSE_MAX_FETCH (4 MiB each)
 // and every query of most calls at the usual 32-256 candidates; a block costs two launches and no host wait.
