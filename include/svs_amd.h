@@ -354,6 +354,73 @@ int32_t svs_index_search_labeled(svs_index* idx, const float* queries, int32_t n
                                  float* out_scores, int64_t* out_rows /* stride k */,
                                  int32_t* out_count, int64_t* out_matched /* or NULL */);
 
+/* ---- columns and predicate search: up to SVS_COLUMNS_MAX uint32_t columns per row and a top-k under a conjunction of
+ *      predicates over them -- "this tenant AND this date range", "this level AND a child of these parents", "visible
+ *      to any of my groups AND not already seen" -- without a host row list.
+ * Columns.  Column 0 IS the label column above: svs_index_set_column(idx, 0, ...) and svs_index_set_labels write the
+ * same memory, and every label entry reads column 0.  Columns 1 .. SVS_COLUMNS_MAX - 1 follow the label column's
+ * rules word for word, each on its own: HBM only, one u32 per row of the row CAPACITY (rounded up to 4 rows), counted
+ * in hbm_bytes; null until first set -- a row never set reads 0, and the rows from n on are 0; allocated zero-filled by
+ * the first svs_index_set_column with nrows > 0 (no memory -> SVS_ERR_NOMEM, handle untouched); svs_index_reserve,
+ * svs_index_append* and svs_index_staging_commit carry it along when the buffers grow and new rows get 0;
+ * svs_index_mask_rows does not touch it; svs_index_compact moves it with the rows, every compacted column built in a
+ * fresh buffer BEFORE the first row moves (no memory for any of them -> SVS_ERR_NOMEM, handle untouched); tombstoned
+ * rows may be written and read.  set holds a reference and the geometry lock exclusively, get holds it shared.
+ * column outside [0, SVS_COLUMNS_MAX) -> SVS_ERR_INVALID; range and null-pointer rules: svs_index_set_labels /
+ * svs_index_get_labels.  A column never set costs nothing and stays unallocated through growth and compaction.
+ *
+ * Predicate search.  A term is true on a row when its op holds on v = column[term.column][row], inverted when
+ * negate == 1:
+ *   SVS_WHERE_IN        v is a member of set[0 .. nset) (host; any order, repeats allowed; an empty set is never true)
+ *   SVS_WHERE_RANGE     a <= v && v <= b                (a > b: never true)
+ *   SVS_WHERE_ANY_BITS  (v & a) != 0
+ *   SVS_WHERE_ALL_BITS  (v & a) == a
+ * Exact definition: let S = { live local rows r : every term is true on r }, ascending; nterms == 0: every live row.
+ * The call writes what
+ *   svs_index_search_rows(idx, queries, nq, d, k, S + row_offset, |S|, ...)
+ * writes: the same rows, the same order (score desc, row desc), the same score bits, the same *out_count =
+ * min(max(k, 0), |S|); entries past the count are not touched.  *out_matched (may be NULL) = |S|; *out_count (may be
+ * NULL) and *out_matched are written by every successful call.  A query's result does not depend on nq, on the order
+ * of the terms, or on the order and repeats inside a set.  One term {column 0, IN, set} is svs_index_search_labeled
+ * with that set, bit for bit, matched included.
+ *   COUNT-ONLY call: with out_matched != NULL and (k <= 0 or nq == 0) only the counting launch runs; out_scores /
+ *             out_rows may be NULL.  With out_matched == NULL and (k <= 0 or nq == 0): SVS_OK, nothing launched.
+ *             The host takes no other short-cut: a predicate nothing satisfies is found by the counting launch, and the
+ *             call ends after it.
+ * Errors: everything is validated before anything is launched, and a failing call writes no output.  d != index d or
+ * an empty index -> SVS_ERR_SHAPE.  SVS_ERR_INVALID: nq < 0, nterms < 0, null terms with nterms > 0, a column outside
+ * [0, SVS_COLUMNS_MAX), an unknown op, negate not 0 or 1, IN with nset < 0 or a null set with nset > 0, null queries
+ * with nq > 0, null out_scores / out_rows with work to do (nq > 0 and k > 0).  SVS_ERR_UNSUPPORTED: nterms >
+ * SVS_WHERE_MAX_TERMS; more than SVS_LABELS_MAX_SET distinct set members summed over the call's IN terms (each term's
+ * repeats do not count; one 4 KiB LDS image holds all sets); rows of more than 16 KiB with work to do.
+ * Cost: a counting pass that reads 4 bytes per row of every DISTINCT column the terms name plus one bit per row (a
+ * column the index does not own is not read), ONE host wait for |S|, a one-workgroup scan and a writing pass that
+ * reads the same again and emits S in ascending order (svs_amd/csrc/where.h); then svs_index_search_rows' own score
+ * and top-k kernels over that device list and the mapping of positions to rows on the device -- the path of
+ * svs_index_search_labeled from there on.
+ * Blocking; re-entrant on one handle; holds a reference and the geometry lock shared; waits for pending staging
+ * copies; never goes through the coalescer, the run-ahead pipelines or shared passes.
+ * Out of scope: svs_multi / row-sharded corpora, a device-pointer variant, OR across terms, per-query predicates in
+ * one call, 64-bit or float columns, more than four columns or terms, routing broad predicates through a full-corpus
+ * pass, columns on the attach path, grouping by a column. */
+#define SVS_COLUMNS_MAX 4          /* column 0 IS the label column of svs_index_set_labels */
+#define SVS_WHERE_MAX_TERMS 4
+typedef enum svs_where_op { SVS_WHERE_IN = 0, SVS_WHERE_RANGE = 1, SVS_WHERE_ANY_BITS = 2, SVS_WHERE_ALL_BITS = 3 } svs_where_op;
+typedef struct svs_where_term_t {
+  int32_t column;        /* 0 .. SVS_COLUMNS_MAX-1; a column never set reads 0 everywhere */
+  int32_t op;            /* svs_where_op */
+  int32_t negate;        /* 0 / 1: the term is the op's truth value, inverted when 1 */
+  uint32_t a, b;         /* RANGE: a <= v && v <= b (a > b: never true); ANY_BITS: (v & a) != 0; ALL_BITS: (v & a) == a; IN: unused */
+  const uint32_t* set;   /* IN: host, any order, repeats allowed; others: ignored */
+  int32_t nset;          /* IN: >= 0; an empty set is never true */
+} svs_where_term_t;
+int32_t svs_index_set_column(svs_index* idx, int32_t column, int64_t row0 /* GLOBAL */, int64_t nrows, const uint32_t* values);
+int32_t svs_index_get_column(svs_index* idx, int32_t column, int64_t row0 /* GLOBAL */, int64_t nrows, uint32_t* out);
+int32_t svs_index_search_where(svs_index* idx, const float* queries, int32_t nq, int32_t d, int32_t k,
+                               const svs_where_term_t* terms, int32_t nterms,
+                               float* out_scores, int64_t* out_rows /* stride k */,
+                               int32_t* out_count, int64_t* out_matched /* or NULL */);
+
 /* Threshold search: every live row that scores at or above a cut-off, best first, and how many there are -- "all
  * documents with cosine >= 0.8", "how many would qualify", "drop the weak tail by score, not by rank" -- without
  * guessing a k and without pulling the score vector to the host.

@@ -39,6 +39,24 @@ class IndexInfo(C.Structure):
     ]
 
 
+COLUMNS_MAX = 4          # SVS_COLUMNS_MAX
+WHERE_MAX_TERMS = 4      # SVS_WHERE_MAX_TERMS
+WHERE_IN, WHERE_RANGE, WHERE_ANY_BITS, WHERE_ALL_BITS = 0, 1, 2, 3   # svs_where_op
+
+
+class WhereTerm(C.Structure):
+    """svs_where_term_t"""
+    _fields_ = [
+        ("column", C.c_int32),
+        ("op", C.c_int32),
+        ("negate", C.c_int32),
+        ("a", C.c_uint32),
+        ("b", C.c_uint32),
+        ("set", C.c_void_p),
+        ("nset", C.c_int32),
+    ]
+
+
 class Timing(C.Structure):
     _fields_ = [
         ("score_ms_sum", C.c_double),
@@ -89,6 +107,10 @@ SIGNATURES = {
     "svs_index_get_labels": (C.c_int32, [_P, C.c_int64, C.c_int64, _P]),
     "svs_index_search_labeled": (C.c_int32, [_P, _P, C.c_int32, C.c_int32, C.c_int32, _P, C.c_int32, _P, _P, C.POINTER(C.c_int32),
                                              C.POINTER(C.c_int64)]),
+    "svs_index_set_column": (C.c_int32, [_P, C.c_int32, C.c_int64, C.c_int64, _P]),
+    "svs_index_get_column": (C.c_int32, [_P, C.c_int32, C.c_int64, C.c_int64, _P]),
+    "svs_index_search_where": (C.c_int32, [_P, _P, C.c_int32, C.c_int32, C.c_int32, _P, C.c_int32, _P, _P, C.POINTER(C.c_int32),
+                                           C.POINTER(C.c_int64)]),
     "svs_index_search_above": (C.c_int32, [_P, _P, C.c_int32, C.c_int32, _P, C.c_int32, _P, _P, _P, _P]),
     "svs_index_search_by_label": (C.c_int32, [_P, _P, C.c_int32, C.c_int32, _P, C.c_int32, _P, C.c_int32, _P, _P, _P, _P, _P, _P]),
     "svs_index_assign": (C.c_int32, [_P, _P, C.c_int32, C.c_int32, C.c_int64, C.c_int64, _P, _P, _P, _P]),

@@ -43,6 +43,7 @@
 #include "above.h"
 #include "diverse.h"
 #include "labels.h"
+#include "where.h"
 #include "by_label.h"
 #include "assign.h"
 #include "label_sums.h"
@@ -356,8 +357,11 @@ struct svs_index {
   // svs_index_set_labels: one u32 per row of the CAPACITY (rounded up to 4: the kernels load 16 bytes), HBM only; null
   // until the first call -- every label is then 0.  Invariant: the labels of the rows from n on are 0, so that rows
   // appended later carry label 0 without a write.  Written under the exclusive geometry lock, read under the shared one.
-  uint32_t* labels = nullptr;
-  size_t labels_bytes = 0;
+  // svs_index_set_column: cols[0] IS that label column; columns 1 .. SVS_COLUMNS_MAX - 1 follow the same rules, each
+  // null until its own first write.  An allocated column has label_column_bytes(cap) bytes.
+  uint32_t* cols[SVS_COLUMNS_MAX] = {};
+  size_t col_bytes[SVS_COLUMNS_MAX] = {};
+  size_t cols_bytes() const { size_t b = 0; for (size_t cb : col_bytes) b += cb; return b; }
   // Corpus geometry lock: searches hold it shared while they enqueue (and, for the
   // host API, until their results are back); append / mask_rows take it exclusive.
   std::shared_mutex rw;
@@ -502,7 +506,7 @@ void index_destroy(svs_index* idx) {
   for (auto& t : idx->evs) ev_destroy(t);
   (void)hipFree(idx->rows);
   (void)hipFree(idx->row_scales);
-  (void)hipFree(idx->labels);
+  for (uint32_t* col : idx->cols) (void)hipFree(col);
   (void)hipFree(idx->pfx_rows);
   (void)hipFree(idx->pfx_scales);
   (void)hipFree(idx->shadow);
@@ -2170,8 +2174,8 @@ inline int64_t label_strips(int64_t n) { return (n + LB_STRIP - 1) / LB_STRIP; }
 
 // The filter over the rows [0, n) the index holds: set[0 .. nset) sorted and distinct on the HOST, set_dev its device
 // copy (read when nset >= 2 only); nset == 0: every live row
-LabelFilter label_filter(const svs_index* idx, const uint32_t* set, int nset, const uint32_t* set_dev) {
-  return LabelFilter{idx->labels, idx->n, idx->dead_list.empty() ? nullptr : idx->dead_bits_dev.p, set_dev, nset, nset == 1 ? set[0] : 0u};
+LabelFilter label_filter(const svs_index* idx, int column, const uint32_t* set, int nset, const uint32_t* set_dev) {
+  return LabelFilter{idx->cols[column], idx->n, idx->dead_list.empty() ? nullptr : idx->dead_bits_dev.p, set_dev, nset, nset == 1 ? set[0] : 0u};
 }
 
 // cnt: one u64 (the total, zeroed here) followed by one u32 per strip of f.n rows
@@ -2218,7 +2222,7 @@ struct LabelSet {
       memcpy(c->lab_set_pin, set.data(), (size_t)nset * sizeof(uint32_t));
       HIP_TRY(hipMemcpyAsync(c->lab_set_dev, c->lab_set_pin, (size_t)nset * sizeof(uint32_t), hipMemcpyHostToDevice, st));
     }
-    *f = label_filter(idx, set.data(), nset, c->lab_set_dev);
+    *f = label_filter(idx, 0, set.data(), nset, c->lab_set_dev);
     return SVS_OK;
   }
 };
@@ -2293,35 +2297,36 @@ int ensure_capacity(svs_index* idx, int64_t rows, bool exact) {
       return fail(SVS_ERR_NOMEM, "hipMalloc(row scales): %s", hipGetErrorString(e));
     }
   }
-  uint32_t* nlabels = nullptr;   // the label column grows with the rows: the old labels, then zeros
-  if (idx->labels) {
-    hipError_t e = hipMalloc((void**)&nlabels, label_column_bytes(new_cap));
-    if (e != hipSuccess) {
-      (void)hipFree(nrows);
-      (void)hipFree(nscales);
-      return fail(SVS_ERR_NOMEM, "hipMalloc(labels): %s", hipGetErrorString(e));
-    }
-  }
   // (the new buffers are the caller's problem only once they are installed: every failure until then frees them)
   struct Fresh {
-    void* rows; float* scales; uint32_t* labels; bool keep = false;
-    ~Fresh() { if (!keep) { (void)hipFree(rows); (void)hipFree(scales); (void)hipFree(labels); } }
-  } fresh{nrows, nscales, nlabels};
+    void* rows; float* scales; uint32_t* cols[SVS_COLUMNS_MAX] = {}; bool keep = false;
+    ~Fresh() { if (!keep) { (void)hipFree(rows); (void)hipFree(scales); for (uint32_t* col : cols) (void)hipFree(col); } }
+  } fresh{nrows, nscales};
+  for (int c = 0; c < SVS_COLUMNS_MAX; ++c) {   // every column the index owns grows with the rows: the old values, then zeros
+    if (!idx->cols[c]) continue;
+    const hipError_t e = hipMalloc((void**)&fresh.cols[c], label_column_bytes(new_cap));
+    if (e != hipSuccess) return fail(SVS_ERR_NOMEM, "hipMalloc(column %d): %s", c, hipGetErrorString(e));
+  }
   // work already enqueued by the device API may still read the old buffers
   HIP_TRY(hipDeviceSynchronize());
   const int64_t n_old = idx->n;
   if (n_old) HIP_TRY(hipMemcpy(nrows, idx->rows, (size_t)n_old * row_b, hipMemcpyDeviceToDevice));
   if (n_old && nscales) HIP_TRY(hipMemcpy(nscales, idx->row_scales, (size_t)n_old * sizeof(float), hipMemcpyDeviceToDevice));
-  if (nlabels) HIP_TRY(hipMemset(nlabels, 0, label_column_bytes(new_cap)));
-  if (n_old && nlabels) HIP_TRY(hipMemcpy(nlabels, idx->labels, (size_t)n_old * sizeof(uint32_t), hipMemcpyDeviceToDevice));
+  for (int c = 0; c < SVS_COLUMNS_MAX; ++c) {
+    if (!fresh.cols[c]) continue;
+    HIP_TRY(hipMemset(fresh.cols[c], 0, label_column_bytes(new_cap)));
+    if (n_old) HIP_TRY(hipMemcpy(fresh.cols[c], idx->cols[c], (size_t)n_old * sizeof(uint32_t), hipMemcpyDeviceToDevice));
+  }
   fresh.keep = true;
   (void)hipFree(idx->rows);
   (void)hipFree(idx->row_scales);
-  (void)hipFree(idx->labels);
   idx->rows = nrows;
   idx->row_scales = nscales;
-  idx->labels = nlabels;
-  idx->labels_bytes = nlabels ? label_column_bytes(new_cap) : 0;
+  for (int c = 0; c < SVS_COLUMNS_MAX; ++c) {
+    (void)hipFree(idx->cols[c]);
+    idx->cols[c] = fresh.cols[c];
+    idx->col_bytes[c] = fresh.cols[c] ? label_column_bytes(new_cap) : 0;
+  }
   if (idx->shadow) {   // grows with the rows; if there is no room for it the index carries on without
     void* nsh = nullptr;
     bool ok = shadow_alloc(idx, new_cap, &nsh);
@@ -2511,10 +2516,12 @@ int compact_index(svs_index* idx, int64_t bounce_rows, int64_t* out_old_rows, in
   }
   // The label column moves with the rows, OUT OF PLACE: the fresh column (and the filter's counts) are allocated here,
   // before the first row moves -- SVS_ERR_NOMEM leaves the handle untouched -- and swapped in after the rows' move
-  uint32_t *lab_new = nullptr, *lab_cnt = nullptr;
-  if (idx->labels) {
-    HIP_TRY(tmp.alloc(&lab_new, label_column_bytes(idx->cap)));
-    HIP_TRY(tmp.alloc(&lab_cnt, (size_t)(label_strips(n) + 2) * sizeof(uint32_t)));
+  // Every column the index owns (svs_index_set_column) moves the same way, each into its own fresh buffer.
+  uint32_t *col_new[SVS_COLUMNS_MAX] = {}, *lab_cnt = nullptr;
+  for (int c = 0; c < SVS_COLUMNS_MAX; ++c) {
+    if (!idx->cols[c]) continue;
+    HIP_TRY(tmp.alloc(&col_new[c], label_column_bytes(idx->cap)));
+    if (!lab_cnt) HIP_TRY(tmp.alloc(&lab_cnt, (size_t)(label_strips(n) + 2) * sizeof(uint32_t)));
   }
   // work enqueued by the device entries may still read the rows; the pipelines start their rings over
   HIP_TRY(hipDeviceSynchronize());
@@ -2522,13 +2529,16 @@ int compact_index(svs_index* idx, int64_t bounce_rows, int64_t* out_old_rows, in
     std::lock_guard<std::mutex> lk(p->mu);
     HIP_TRY(pipe_drain(p));
   }
-  if (lab_new) {
-    // the ordered stream compaction of the label VALUES under "row is live" (the empty set): new row p gets the label
-    // of the p-th live row; the tail stays zero
-    HIP_TRY(hipMemsetAsync(lab_new, 0, label_column_bytes(idx->cap), nullptr));
-    const LabelFilter f = label_filter(idx, nullptr, 0, nullptr);
+  for (int c = 0; c < SVS_COLUMNS_MAX; ++c) {
+    if (!col_new[c]) continue;
+    // the ordered stream compaction of the column's VALUES under "row is live" (the empty set): new row p gets the value
+    // of the p-th live row; the tail stays zero.  (The predicate does not read the column, so every column would count
+    // the same; the scan turns the counts into bases in place, so each column counts again: launch-bound, 4 KiB of
+    // counts per million rows.)
+    HIP_TRY(hipMemsetAsync(col_new[c], 0, label_column_bytes(idx->cap), nullptr));
+    const LabelFilter f = label_filter(idx, c, nullptr, 0, nullptr);
     launch_label_count(f, lab_cnt, nullptr);
-    launch_label_write<LB_VALUES>(f, lab_cnt, lab_new, n_live, nullptr);
+    launch_label_write<LB_VALUES>(f, lab_cnt, col_new[c], n_live, nullptr);
   }
   const CompactBufs corpus{(uint4*)idx->rows, idx->row_scales, (uint4*)idx->shadow};
   CompactBufs bnc{};   // rows, then shadow rows, then scales: every part starts on a 16-byte boundary
@@ -2555,10 +2565,11 @@ int compact_index(svs_index* idx, int64_t bounce_rows, int64_t* out_old_rows, in
   if (e != hipSuccess)
     return fail(SVS_ERR_DEVICE, "svs_index_compact: %s while rows were moving; the handle is only good for svs_index_release",
                 hipGetErrorString(e));
-  if (lab_new) {   // (the rows have moved: the compacted column takes the old one's place)
-    tmp.p.erase(std::find(tmp.p.begin(), tmp.p.end(), (void*)lab_new));
-    (void)hipFree(idx->labels);
-    idx->labels = lab_new;
+  for (int c = 0; c < SVS_COLUMNS_MAX; ++c) {   // (the rows have moved: the compacted columns take the old ones' places)
+    if (!col_new[c]) continue;
+    tmp.p.erase(std::find(tmp.p.begin(), tmp.p.end(), (void*)col_new[c]));
+    (void)hipFree(idx->cols[c]);
+    idx->cols[c] = col_new[c];
   }
   if (out_old_rows) {   // (branch-free: the slot is overwritten until a live row keeps it; the last live row is the last write inside the map)
     int64_t p = 0;
@@ -2957,7 +2968,7 @@ int32_t svs_index_info(const svs_index* idx, svs_index_info_t* out) {
   out->dtype = idx->dtype;
   out->device = idx->device;
   out->row_offset = idx->row_offset;
-  out->hbm_bytes = (int64_t)(idx->bytes + idx->shadow_bytes + idx->labels_bytes);
+  out->hbm_bytes = (int64_t)(idx->bytes + idx->shadow_bytes + idx->cols_bytes());
   out->n_masked = (int64_t)idx->dead_list.size();
   return SVS_OK;
 }
@@ -3420,9 +3431,9 @@ int32_t svs_index_search_rows(svs_index* idx, const float* queries, int32_t nq, 
   return SVS_OK;
 }
 
-// The first write of the label column (under the exclusive geometry lock): a zero column for the row CAPACITY
-static int label_column_ensure(svs_index* idx, const char* entry) {
-  if (idx->labels) return SVS_OK;
+// The first write of a column (under the exclusive geometry lock): a zero column for the row CAPACITY
+static int column_ensure(svs_index* idx, int column, const char* entry) {
+  if (idx->cols[column]) return SVS_OK;
   const size_t bytes = label_column_bytes(std::max(idx->cap, idx->n));
   uint32_t* col = nullptr;
   HIP_TRY(hipMalloc((void**)&col, bytes));
@@ -3431,46 +3442,73 @@ static int label_column_ensure(svs_index* idx, const char* entry) {
     (void)hipFree(col);
     return fail(SVS_ERR_DEVICE, "%s: %s", entry, hipGetErrorString(e));
   }
-  idx->labels = col;
-  idx->labels_bytes = bytes;
+  idx->cols[column] = col;
+  idx->col_bytes[column] = bytes;
+  return SVS_OK;
+}
+
+static int check_column(const char* entry, int32_t column) {
+  return column >= 0 && column < SVS_COLUMNS_MAX ? (int)SVS_OK
+      : fail(SVS_ERR_INVALID, "%s: column %d; an index has columns 0 .. %d", entry, (int)column, SVS_COLUMNS_MAX - 1);
+}
+
+// svs_index_set_labels (column 0) and svs_index_set_column
+static int32_t column_set(svs_index* idx, const char* entry, int column, int64_t row0, int64_t nrows, const uint32_t* labels) {
+  RefGuard guard(idx);
+  std::unique_lock<std::shared_mutex> geo(idx->rw);   // no filtered search is between its count and its write
+  if (nrows == 0) return SVS_OK;
+  int64_t r0;
+  int rc = label_range(idx, entry, row0, nrows, &r0);
+  if (rc != SVS_OK) return rc;
+  if (!labels) return fail(SVS_ERR_INVALID, column ? "null values" : "null labels");
+  HIP_TRY(hipSetDevice(idx->device));
+  if ((rc = column_ensure(idx, column, entry)) != SVS_OK) return rc;
+  // (svs_index_search_labeled, svs_index_search_by_label and svs_index_get_labels read the column, blocking and under the
+  //  shared lock; svs_index_assign with vector_labels is the one other writer, blocking and under the exclusive lock like
+  //  this call; reserve, append and compact carry the column along under the exclusive lock too: nothing enqueued can be
+  //  reading or writing it now)
+  HIP_TRY(hipMemcpy(idx->cols[column] + r0, labels, (size_t)nrows * sizeof(uint32_t), hipMemcpyHostToDevice));
+  return SVS_OK;
+}
+
+// svs_index_get_labels (column 0) and svs_index_get_column
+static int32_t column_get(svs_index* idx, const char* entry, int column, int64_t row0, int64_t nrows, uint32_t* out) {
+  RefGuard guard(idx);
+  std::shared_lock<std::shared_mutex> geo(idx->rw);
+  if (nrows == 0) return SVS_OK;
+  int64_t r0;
+  const int rc = label_range(idx, entry, row0, nrows, &r0);
+  if (rc != SVS_OK) return rc;
+  if (!out) return fail(SVS_ERR_INVALID, "null output");
+  if (!idx->cols[column]) {
+    memset(out, 0, (size_t)nrows * sizeof(uint32_t));
+    return SVS_OK;
+  }
+  HIP_TRY(hipSetDevice(idx->device));
+  HIP_TRY(hipMemcpy(out, idx->cols[column] + r0, (size_t)nrows * sizeof(uint32_t), hipMemcpyDeviceToHost));
   return SVS_OK;
 }
 
 int32_t svs_index_set_labels(svs_index* idx, int64_t row0, int64_t nrows, const uint32_t* labels) {
   if (!idx) return fail(SVS_ERR_INVALID, "null index");
-  RefGuard guard(idx);
-  std::unique_lock<std::shared_mutex> geo(idx->rw);   // no labelled search is between its count and its write
-  if (nrows == 0) return SVS_OK;
-  int64_t r0;
-  int rc = label_range(idx, "svs_index_set_labels", row0, nrows, &r0);
-  if (rc != SVS_OK) return rc;
-  if (!labels) return fail(SVS_ERR_INVALID, "null labels");
-  HIP_TRY(hipSetDevice(idx->device));
-  if ((rc = label_column_ensure(idx, "svs_index_set_labels")) != SVS_OK) return rc;
-  // (svs_index_search_labeled, svs_index_search_by_label and svs_index_get_labels read the column, blocking and under the
-  //  shared lock; svs_index_assign with vector_labels is the one other writer, blocking and under the exclusive lock like
-  //  this call; reserve, append and compact carry the column along under the exclusive lock too: nothing enqueued can be
-  //  reading or writing it now)
-  HIP_TRY(hipMemcpy(idx->labels + r0, labels, (size_t)nrows * sizeof(uint32_t), hipMemcpyHostToDevice));
-  return SVS_OK;
+  return column_set(idx, "svs_index_set_labels", 0, row0, nrows, labels);
 }
 
 int32_t svs_index_get_labels(svs_index* idx, int64_t row0, int64_t nrows, uint32_t* out) {
   if (!idx) return fail(SVS_ERR_INVALID, "null index");
-  RefGuard guard(idx);
-  std::shared_lock<std::shared_mutex> geo(idx->rw);
-  if (nrows == 0) return SVS_OK;
-  int64_t r0;
-  const int rc = label_range(idx, "svs_index_get_labels", row0, nrows, &r0);
-  if (rc != SVS_OK) return rc;
-  if (!out) return fail(SVS_ERR_INVALID, "null output");
-  if (!idx->labels) {
-    memset(out, 0, (size_t)nrows * sizeof(uint32_t));
-    return SVS_OK;
-  }
-  HIP_TRY(hipSetDevice(idx->device));
-  HIP_TRY(hipMemcpy(out, idx->labels + r0, (size_t)nrows * sizeof(uint32_t), hipMemcpyDeviceToHost));
-  return SVS_OK;
+  return column_get(idx, "svs_index_get_labels", 0, row0, nrows, out);
+}
+
+int32_t svs_index_set_column(svs_index* idx, int32_t column, int64_t row0, int64_t nrows, const uint32_t* values) {
+  if (!idx) return fail(SVS_ERR_INVALID, "null index");
+  const int rc = check_column("svs_index_set_column", column);
+  return rc != SVS_OK ? rc : column_set(idx, "svs_index_set_column", column, row0, nrows, values);
+}
+
+int32_t svs_index_get_column(svs_index* idx, int32_t column, int64_t row0, int64_t nrows, uint32_t* out) {
+  if (!idx) return fail(SVS_ERR_INVALID, "null index");
+  const int rc = check_column("svs_index_get_column", column);
+  return rc != SVS_OK ? rc : column_get(idx, "svs_index_get_column", column, row0, nrows, out);
 }
 
 int32_t svs_internal_labels_strip(void) { return LB_STRIP; }
@@ -3528,6 +3566,142 @@ int32_t svs_index_search_labeled(svs_index* idx, const float* queries, int32_t n
   for (size_t i = 0; i < on; ++i)
     if (c->out_r_pin[i] < 0)
       return fail(SVS_ERR_DEVICE, "search_labeled: result %zu of query %zu is a position outside the %lld matching rows", i % (size_t)count,
+                  i / (size_t)count, (long long)m);
+  deliver_results(c, nq, count, k, out_scores, out_rows);
+  return done(count, m);
+}
+
+// ---- svs_index_search_where (where.h)
+static_assert(SVS_COLUMNS_MAX == WH_COLS && SVS_WHERE_MAX_TERMS == WH_MAX_TERMS, "where.h's kernels are built for the header's limits");
+static_assert(SVS_WHERE_IN == WH_IN && SVS_WHERE_RANGE == WH_RANGE && SVS_WHERE_ANY_BITS == WH_ANY_BITS && SVS_WHERE_ALL_BITS == WH_ALL_BITS,
+              "where.h's kernels take the header's op codes");
+
+// A caller's terms, checked, and their kernel form: every IN term's set sorted and without repeats; the sets of two
+// members or more one after another in `image` (at most SVS_LABELS_MAX_SET words: the kernels' LDS image)
+struct WherePlan {
+  WhereTerm t[WH_MAX_TERMS] = {};
+  int nterms = 0;
+  uint32_t col_mask = 0;
+  std::vector<uint32_t> image;
+  int build(const svs_where_term_t* terms, int32_t nterms_in) {
+    if (nterms_in < 0) return fail(SVS_ERR_INVALID, "nterms must be >= 0");
+    if (nterms_in > SVS_WHERE_MAX_TERMS)
+      return fail(SVS_ERR_UNSUPPORTED, "svs_index_search_where: %d terms; a predicate holds at most %d", (int)nterms_in, SVS_WHERE_MAX_TERMS);
+    if (nterms_in > 0 && !terms) return fail(SVS_ERR_INVALID, "null terms");
+    for (int i = 0; i < nterms_in; ++i) {
+      const svs_where_term_t& u = terms[i];
+      int rc = check_column("svs_index_search_where", u.column);
+      if (rc != SVS_OK) return rc;
+      if (u.op < SVS_WHERE_IN || u.op > SVS_WHERE_ALL_BITS) return fail(SVS_ERR_INVALID, "svs_index_search_where: term %d has the unknown op %d", i, (int)u.op);
+      if (u.negate != 0 && u.negate != 1) return fail(SVS_ERR_INVALID, "svs_index_search_where: term %d: negate must be 0 or 1", i);
+      if (u.op == SVS_WHERE_IN && (rc = LabelSet::check(u.set, u.nset)) != SVS_OK) return rc;
+    }
+    size_t members = 0;
+    for (int i = 0; i < nterms_in; ++i) {
+      const svs_where_term_t& u = terms[i];
+      WhereTerm& w = t[i];
+      w = WhereTerm{u.a, u.b, 0, 0, WhereTerm::pack(u.column, u.op, u.negate)};
+      col_mask |= 1u << u.column;
+      if (u.op != SVS_WHERE_IN) continue;
+      w.a = w.b = 0;
+      std::vector<uint32_t> set;
+      try {
+        set.assign(u.set, u.set + u.nset);
+        std::sort(set.begin(), set.end());
+        set.erase(std::unique(set.begin(), set.end()), set.end());
+        members += set.size();
+        if (set.size() >= 2 && members <= (size_t)SVS_LABELS_MAX_SET) {
+          w.set0 = (int32_t)image.size();
+          image.insert(image.end(), set.begin(), set.end());
+        }
+      } catch (const std::bad_alloc&) {
+        return fail(SVS_ERR_NOMEM, "out of host memory for a set of %d", (int)u.nset);
+      }
+      w.nset = (int32_t)set.size();
+      if (set.size() == 1) w.a = set[0];
+    }
+    if (members > (size_t)SVS_LABELS_MAX_SET)
+      return fail(SVS_ERR_UNSUPPORTED, "svs_index_search_where: %zu distinct set members over the IN terms; a call holds at most %d", members,
+                  SVS_LABELS_MAX_SET);
+    nterms = nterms_in;
+    return SVS_OK;
+  }
+  // The image goes up on st through the context's pinned copy; *f = the index's filter
+  int stage(const svs_index* idx, Ctx* c, hipStream_t st, WhereFilter* f) const {
+    const size_t words = image.size();
+    if (words) {
+      int rc;
+      if ((rc = c->lab_set_pin.grow(words)) != SVS_OK || (rc = c->lab_set_dev.grow(words)) != SVS_OK) return rc;
+      memcpy(c->lab_set_pin, image.data(), words * sizeof(uint32_t));
+      HIP_TRY(hipMemcpyAsync(c->lab_set_dev, c->lab_set_pin, words * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+    }
+    *f = WhereFilter{};
+    f->col0 = idx->cols[0], f->col1 = idx->cols[1], f->col2 = idx->cols[2], f->col3 = idx->cols[3];
+    f->n = idx->n;
+    f->dead_bits = idx->dead_list.empty() ? nullptr : idx->dead_bits_dev.p;
+    f->set = words ? c->lab_set_dev.p : nullptr;
+    f->set_words = (int32_t)words;
+    f->nterms = nterms;
+    f->col_mask = col_mask;
+    f->t0 = t[0], f->t1 = t[1], f->t2 = t[2], f->t3 = t[3];
+    return SVS_OK;
+  }
+};
+
+int32_t svs_index_search_where(svs_index* idx, const float* queries, int32_t nq, int32_t d, int32_t k, const svs_where_term_t* terms,
+                               int32_t nterms, float* out_scores, int64_t* out_rows, int32_t* out_count, int64_t* out_matched) {
+  launch_reset();
+  if (!idx) return fail(SVS_ERR_INVALID, "null index");
+  RefGuard guard(idx);
+  std::shared_lock<std::shared_mutex> geo(idx->rw);   // (set_column, mask_rows, compact take it exclusively: the count and the write see the same columns)
+  int rc = check_query_args(idx, queries, nq, d);
+  if (rc != SVS_OK) return rc;
+  WherePlan plan;
+  if ((rc = plan.build(terms, nterms)) != SVS_OK) return rc;
+  const bool ranks = nq > 0 && k > 0;   // results are wanted, if a row matches
+  if (ranks && (!out_scores || !out_rows)) return fail(SVS_ERR_INVALID, "null output");
+  if (ranks && (rc = check_gather_rows(idx, "svs_index_search_where")) != SVS_OK) return rc;
+  const auto done = [&](int count, int64_t m) {   // every successful exit: the entries written, the rows that matched
+    if (out_count) *out_count = count;
+    if (out_matched) *out_matched = m;
+    return (int32_t)SVS_OK;
+  };
+  if (!ranks && !out_matched) return done(0, 0);   // nothing to rank and nobody to tell the count
+  HostCall fr(idx);
+  if ((rc = fr.open()) != SVS_OK) return rc;
+  Ctx* const c = fr.c;
+  const int64_t n = idx->n, lo = idx->row_offset;
+  if ((rc = c->lab_cnt.grow((size_t)label_strips(n) + 2)) != SVS_OK || (rc = c->lab_tot_pin.grow(1)) != SVS_OK) return rc;
+  // 1. the sets go up, the count runs; the host needs m = |S| to size the list, the score matrix and the select route
+  hipStream_t st = fr.stream();
+  WhereFilter f;
+  if ((rc = plan.stage(idx, c, st, &f)) != SVS_OK) return rc;
+  const unsigned strips = (unsigned)label_strips(n);
+  launch_record("where_count_kernel", n, plan.nterms);
+  (void)hipMemsetAsync(c->lab_cnt, 0, sizeof(unsigned long long), st);
+  hipLaunchKernelGGL(where_count_kernel, dim3(strips), dim3(LB_THREADS), 0, st, f, c->lab_cnt.p + 2, (unsigned long long*)c->lab_cnt.p);
+  HIP_TRY(hipMemcpyAsync(c->lab_tot_pin, c->lab_cnt, sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
+  if ((rc = fr.close("search_where")) != SVS_OK) return rc;
+  const int64_t m = (int64_t)c->lab_tot_pin[0];
+  if (m < 0 || m > n) return fail(SVS_ERR_DEVICE, "search_where: the filter counted %lld of %lld rows", (long long)m, (long long)n);
+  const int count = ranks ? (int)std::min<int64_t>(k, m) : 0;
+  if (count == 0) return done(0, m);
+  // 2. the list is written on the device; from here on the call is svs_index_search_rows over it, as svs_index_search_labeled
+  const size_t qn = (size_t)nq * (size_t)d, on = (size_t)nq * (size_t)count;
+  if ((rc = c->list_dev.grow((size_t)m)) != SVS_OK || (rc = c->lab_pos.grow(on)) != SVS_OK) return rc;
+  if ((rc = c->out_s_pin.grow(on)) != SVS_OK || (rc = c->out_r_pin.grow(on)) != SVS_OK) return rc;
+  st = fr.stream();
+  if ((rc = upload_queries(c, queries, qn, st)) != SVS_OK) return rc;
+  launch_record("where_write_kernel", n, plan.nterms);
+  hipLaunchKernelGGL(label_scan_kernel, dim3(1), dim3(LB_THREADS), 0, st, c->lab_cnt.p + 2, label_strips(n));
+  hipLaunchKernelGGL(where_write_kernel, dim3(strips), dim3(LB_THREADS), 0, st, f, (const uint32_t*)(c->lab_cnt.p + 2), c->list_dev.p, m);
+  if ((rc = search_list_chunked(idx, c, nq, d, c->list_dev, m, count, c->out_s_pin, c->lab_pos, st)) != SVS_OK) return rc;
+  hipLaunchKernelGGL(label_map_rows_kernel, dim3((unsigned)std::min<size_t>((on + 255) / 256, 1024)), dim3(256), 0, st,
+                     (const int64_t*)c->lab_pos.p, (int64_t)on, (const uint32_t*)c->list_dev.p, m, lo, c->out_r_pin.p);
+  if ((rc = fr.close("search_where")) != SVS_OK) return rc;
+  for (size_t i = 0; i < on; ++i)
+    if (c->out_r_pin[i] < 0)
+      return fail(SVS_ERR_DEVICE, "search_where: result %zu of query %zu is a position outside the %lld matching rows", i % (size_t)count,
                   i / (size_t)count, (long long)m);
   deliver_results(c, nq, count, k, out_scores, out_rows);
   return done(count, m);
@@ -3734,7 +3908,7 @@ int32_t svs_index_assign(svs_index* idx, const float* vectors, int32_t c, int32_
   if (vector_labels && ((rc = cx->lab_set_dev.grow((size_t)c)) != SVS_OK || (rc = cx->lab_set_pin.grow((size_t)c)) != SVS_OK)) return rc;
   if ((rc = cx->q_dev.grow((size_t)c * d)) != SVS_OK || (rc = cx->q_pin.grow((size_t)c * d)) != SVS_OK) return rc;
   // the column last: a call that fails above has allocated none
-  if (vector_labels && (rc = label_column_ensure(idx, "svs_index_assign")) != SVS_OK) return rc;
+  if (vector_labels && (rc = column_ensure(idx, 0, "svs_index_assign")) != SVS_OK) return rc;
   hipStream_t st = fr.stream();
   // ---- the vectors as stored rows: the rows' own ingest path into the context's image
   if ((rc = upload_queries(cx, vectors, (size_t)c * d, st)) != SVS_OK) return rc;
@@ -3754,7 +3928,7 @@ int32_t svs_index_assign(svs_index* idx, const float* vectors, int32_t c, int32_
   const uint32_t* const k_lab = vector_labels ? cx->lab_set_dev.p : nullptr;
   int32_t* const k_best = out_best ? cx->as_best.p : nullptr;
   float* const k_score = out_scores ? cx->as_score.p : nullptr;
-  uint32_t* const k_col = vector_labels ? idx->labels : nullptr;
+  uint32_t* const k_col = vector_labels ? idx->cols[0] : nullptr;
   unsigned long long* const k_cnt = out_counts ? cx->as_cnt.p : nullptr;
   for_store_dtype(idx, [&](auto dt) {
     constexpr int DT = decltype(dt)::value;

@@ -41,6 +41,99 @@ def labels_u32(labels) -> np.ndarray:
     return np.ascontiguousarray(a).reshape(-1)
 
 
+COLUMNS_MAX = _native.COLUMNS_MAX          # SVS_COLUMNS_MAX: column 0 is the label column
+WHERE_MAX_TERMS = _native.WHERE_MAX_TERMS  # SVS_WHERE_MAX_TERMS: the most terms of one predicate
+
+# op name of a ``where`` term -> (svs_where_op, negate)
+WHERE_OPS = {
+    "in": (_native.WHERE_IN, 0), "not in": (_native.WHERE_IN, 1),
+    "range": (_native.WHERE_RANGE, 0), "not range": (_native.WHERE_RANGE, 1),
+    "any_bits": (_native.WHERE_ANY_BITS, 0), "no_bits": (_native.WHERE_ANY_BITS, 1),
+    "all_bits": (_native.WHERE_ALL_BITS, 0), "not all_bits": (_native.WHERE_ALL_BITS, 1),
+}
+
+
+def _u32_scalar(x, what: str) -> int:
+    """An integer in [0, 2**32) as an int; ValueError for a bool, a non-integer or a value outside."""
+    if isinstance(x, (bool, np.bool_)) or not isinstance(x, (int, np.integer)):
+        raise ValueError(f"{what} must be an integer, got {x!r}")
+    if not 0 <= int(x) <= 0xFFFFFFFF:
+        raise ValueError(f"{what} must lie in [0, 2**32), got {x!r}")
+    return int(x)
+
+
+def column_index(c) -> int:
+    """A column number as an int; ValueError outside [0, COLUMNS_MAX)."""
+    if isinstance(c, (bool, np.bool_)) or not isinstance(c, (int, np.integer)) or not 0 <= int(c) < COLUMNS_MAX:
+        raise ValueError(f"column must be an integer in [0, {COLUMNS_MAX}), got {c!r}")
+    return int(c)
+
+
+def where_terms(where) -> list:
+    """A ``where`` list -- terms ``(column, op, arg)``, all of which must hold -- checked and normalised to
+    ``[(column, svs_where_op, negate, a, b, members)]``: ``members`` is the u32 vector of an in / not in term as given
+    (the library sorts and deduplicates it) and None otherwise.  ``op`` is a key of WHERE_OPS; ``arg`` is an iterable of integers for in / not in,
+    ``(lo, hi)`` for the range ops and an int mask for the bit ops.  ValueError for an unknown op, a bad column, a
+    value that is negative, >= 2**32, a bool or no integer, more than WHERE_MAX_TERMS terms, or more than LABELS_MAX_SET
+    distinct members over the call's sets."""
+    terms = list(where)
+    if len(terms) > WHERE_MAX_TERMS:
+        raise ValueError(f"{len(terms)} terms; a predicate holds at most {WHERE_MAX_TERMS}")
+    out, sets = [], []
+    for term in terms:
+        try:
+            column, op, arg = term
+        except (TypeError, ValueError):
+            raise ValueError(f"a term is (column, op, arg), got {term!r}") from None
+        column = column_index(column)
+        if not isinstance(op, str) or op not in WHERE_OPS:
+            raise ValueError(f"unknown op {op!r}; one of {sorted(WHERE_OPS)}")
+        code, negate = WHERE_OPS[op]
+        a = b = 0
+        mem = None
+        if code == _native.WHERE_IN:
+            if isinstance(arg, (str, bytes)) or not hasattr(arg, "__iter__"):
+                raise ValueError(f"{op!r} takes an iterable of integers, got {arg!r}")
+            arg = arg if isinstance(arg, np.ndarray) else list(arg)
+            if not isinstance(arg, np.ndarray) and any(isinstance(x, (bool, np.bool_)) for x in arg):
+                raise ValueError("set members must be integers, got a bool")
+            mem = labels_u32(arg)
+            sets.append(mem)
+        elif code == _native.WHERE_RANGE:
+            try:
+                lo, hi = arg
+            except (TypeError, ValueError):
+                raise ValueError(f"{op!r} takes (lo, hi), got {arg!r}") from None
+            a, b = _u32_scalar(lo, "a range bound"), _u32_scalar(hi, "a range bound")
+        else:
+            a = _u32_scalar(arg, "a bit mask")
+        out.append((column, code, negate, a, b, mem))
+    # (distinct members are counted only when the members as given could exceed the limit)
+    members = sum(len(m) for m in sets)
+    if members > LABELS_MAX_SET:
+        members = sum(len(np.unique(m)) for m in sets)
+    if members > LABELS_MAX_SET:
+        raise ValueError(f"{members} distinct set members over the in / not in terms; a call holds at most {LABELS_MAX_SET}")
+    return out
+
+
+def pack_where(where):
+    """``where`` -> (the C array of svs_where_term_t or None, its length, what must stay alive during the call)."""
+    terms = where_terms(where)
+    if not terms:
+        return None, 0, []
+    arr = (_native.WhereTerm * len(terms))()
+    keep = []
+    for t, (column, code, negate, a, b, mem) in zip(arr, terms):
+        t.column, t.op, t.negate, t.a, t.b = column, code, negate, a, b
+        if mem is not None and len(mem):
+            keep.append(mem)
+            t.set, t.nset = mem.ctypes.data, len(mem)
+        else:
+            t.set, t.nset = None, 0
+    return arr, len(terms), keep
+
+
 def _means(sums: np.ndarray, counts: np.ndarray) -> np.ndarray:
     """Per-label sums (L, D) f64 and counts (L,) -> the means in f64; a label with count 0 gets zeros."""
     means = np.zeros(sums.shape, dtype=np.float64)
@@ -469,6 +562,80 @@ class DeviceIndex:
             raise ValueError(f"query must be 1-D, got shape {q.shape}")
         s, r, matched = self.search_batch_labeled(q[None, :], n, labels)
         return list(zip(s[0].astype(np.float64).tolist(), r[0].tolist())), matched
+
+    # -- columns and predicate search (svs_index_set_column, svs_index_search_where) -------------------------------
+    def set_column(self, c: int, values, row0: Optional[int] = None) -> None:
+        """``values`` (integers in [0, 2**32)) become column ``c``'s values of the GLOBAL rows ``row0 .. row0 +
+        len(values)`` (``row0=None``: from the index's first row).  Column 0 is the label column (``set_labels``);
+        every column lives in HBM only, a row never set reads 0 and rows appended later get 0 (svs_index_set_column)."""
+        c = column_index(c)
+        val = labels_u32(values)
+        r0 = self.row_offset if row0 is None else int(row0)
+        _native.check(self._lib.svs_index_set_column(self._handle(), c, r0, len(val), val.ctypes.data))
+        self._refresh()      # (the first call allocates the column: hbm_bytes)
+
+    def column(self, c: int, row0: Optional[int] = None, nrows: Optional[int] = None) -> np.ndarray:
+        """Column ``c`` of the GLOBAL rows ``row0 .. row0 + nrows`` as the DEVICE holds it, u32 (``row0=None``: from the
+        first row; ``nrows=None``: to the last).  Zeros for a column never set (svs_index_get_column)."""
+        c = column_index(c)
+        h = self._pinned_handle()
+        try:
+            info = _native.IndexInfo()
+            _native.check(self._quick.svs_index_info(h, C.byref(info)))
+            r0 = int(info.row_offset) if row0 is None else int(row0)
+            cnt = int(info.row_offset) + int(info.n) - r0 if nrows is None else int(nrows)
+            out = np.empty(max(cnt, 0), dtype=np.uint32)
+            _native.check(self._lib.svs_index_get_column(h, c, r0, cnt, out.ctypes.data))
+        finally:
+            self._unpin(h)
+        return out
+
+    def search_batch_where(self, queries: np.ndarray, n: int, where) -> Tuple[np.ndarray, np.ndarray, int]:
+        """``search_batch`` over the live rows on which every term of ``where`` holds (``where_terms``; no term: every
+        live row): (scores f32 (nq, count), rows i64 (nq, count), matched), matched = how many rows satisfy the
+        predicate, count = min(max(n, 0), matched), each row ordered (score desc, row desc) -- the rows and score bits
+        ``search_batch_within`` gives for exactly those rows, with the filter run on the device
+        (svs_index_search_where).  ``n=0`` only counts."""
+        assert isinstance(n, int)
+        q = self._queries_2d(queries)
+        nq, d = q.shape
+        terms, nterms, keep = pack_where(where)
+        h = self._pinned_handle()
+        try:
+            # (clamped before allocating and before the int32 argument, as in search_batch)
+            k = min(max(n, 0), self._live_rows(h))
+            scores = np.empty((nq, k), dtype=np.float32)
+            rows = np.empty((nq, k), dtype=np.int64)
+            count, matched = C.c_int32(0), C.c_int64(0)
+            # (the one call that releases the GIL)
+            _native.check(self._lib.svs_index_search_where(h, q.ctypes.data, nq, d, k, terms, nterms,
+                                                           scores.ctypes.data, rows.ctypes.data, C.byref(count), C.byref(matched)))
+        finally:
+            self._unpin(h)
+        del keep
+        return self._trimmed(scores, rows, count.value) + (matched.value,)
+
+    def search_where(self, query_vec: np.ndarray, n: int, where) -> Tuple[List[Tuple[float, int]], int]:
+        """``search`` restricted to the rows on which every term of ``where`` holds (see ``search_batch_where``):
+        ([(score, row)], matched)."""
+        assert isinstance(n, int)
+        q = np.asarray(query_vec, dtype=np.float32)
+        if q.ndim != 1:
+            raise ValueError(f"query must be 1-D, got shape {q.shape}")
+        s, r, matched = self.search_batch_where(q[None, :], n, where)
+        return list(zip(s[0].astype(np.float64).tolist(), r[0].tolist())), matched
+
+    def count_where(self, where) -> int:
+        """How many live rows satisfy ``where``: the counting launch alone (svs_index_search_where with k = 0)."""
+        terms, nterms, keep = pack_where(where)
+        h = self._pinned_handle()
+        try:
+            matched = C.c_int64(0)
+            _native.check(self._lib.svs_index_search_where(h, None, 0, self.d, 0, terms, nterms, None, None, None, C.byref(matched)))
+        finally:
+            self._unpin(h)
+        del keep
+        return int(matched.value)
 
     def search_batch_by_label(self, queries: np.ndarray, labels, min_scores=None,
                               n: Optional[int] = None) -> List[Tuple[np.ndarray, np.ndarray, np.ndarray, np.ndarray, int]]:

@@ -30,7 +30,7 @@ from typing import Any, Awaitable, Callable, Dict, Iterator, List, Optional, Tup
 import numpy as np
 
 from .index import ASSIGN_MAX_VECTORS, LABELS_MAX_SET, DeviceIndex
-from .matrix import (DeviceEmbeddingsMatrix, above_op, assign_op, batch_op, by_label_op, cluster_op, diverse_op, labeled_op, neighbors_op, pairs_op, segments_op, single_op,
+from .matrix import (DeviceEmbeddingsMatrix, above_op, assign_op, batch_op, by_label_op, cluster_op, diverse_op, labeled_op, neighbors_op, pairs_op, segments_op, single_op, where_op,
                      within_op)
 
 _LOG = logging.getLogger(__name__)
@@ -203,6 +203,14 @@ class _Store:
         rows = self.conn.execute("SELECT embedding, level FROM docs WHERE embedding IS NOT NULL").fetchall()
         pairs = np.array(rows, dtype=np.int64).reshape(-1, 2)
         return pairs[:, 0].copy(), (pairs[:, 1] + 1).astype(np.uint32)
+
+    def embedding_parents(self) -> Tuple[np.ndarray, np.ndarray]:
+        """(embedding ids i64, values u32) of every doc that has an embedding, in one scan (``retrieve_under``: column
+        ``PARENT_COLUMN`` of the HBM copy).  The value of a doc is ``parent_id + 1``; 0 means no parent.  ValueError for
+        a stored parent id that does not fit (``_parent_value``)."""
+        rows = self.conn.execute("SELECT embedding, parent_id FROM docs WHERE embedding IS NOT NULL").fetchall()
+        ids = np.array([r[0] for r in rows], dtype=np.int64)
+        return ids, np.array([_parent_value(r[1]) for r in rows], dtype=np.uint32)
 
     def embedded_levels(self) -> List[int]:
         """The distinct levels of the docs that have an embedding, ascending, in one statement
@@ -386,6 +394,59 @@ def _by_level_cut(min_score: Optional[float]) -> Optional[float]:
     return float(min_score)
 
 
+PARENT_COLUMN = 1   # the column of the HBM copy that holds parent_id + 1 (column 0: level + 1)
+
+
+def _parent_value(parent_id) -> int:
+    """What column ``PARENT_COLUMN`` holds for a doc: ``parent_id + 1``, and 0 for a doc without a parent.  ValueError
+    for a parent id that is negative or no integer, or >= 2**32 - 1 (its value would not fit in a u32)."""
+    if parent_id is None:
+        return 0
+    if isinstance(parent_id, (bool, np.bool_)) or not isinstance(parent_id, (int, np.integer)):
+        raise ValueError(f"a parent id must be an integer, got {parent_id!r}")
+    if parent_id < 0:
+        raise ValueError(f"a parent id cannot be negative, got {parent_id}")
+    if parent_id >= 0xFFFFFFFF:
+        raise ValueError(f"parent id {parent_id} is too large: the column holds parent_id + 1 as a u32")
+    return int(parent_id) + 1
+
+
+def _parent_values(parent_ids) -> List[int]:
+    """The set of ``retrieve_under``: ``parent_ids`` (an int or an iterable of ints) as the distinct stored values
+    ``parent_id + 1``, ascending.  ValueError as ``_parent_value`` (None is no parent id here), and for more than
+    ``LABELS_MAX_SET`` distinct parents."""
+    if isinstance(parent_ids, (int, np.integer)) and not isinstance(parent_ids, bool):
+        given = [parent_ids]
+    elif isinstance(parent_ids, (str, bytes)) or not hasattr(parent_ids, "__iter__"):
+        raise ValueError(f"parent_ids must be an integer or an iterable of integers, got {parent_ids!r}")
+    else:
+        given = list(parent_ids)
+    if any(p is None for p in given):
+        raise ValueError("a parent id must be an integer, got None")
+    values = sorted({_parent_value(p) for p in given})
+    if len(values) > LABELS_MAX_SET:
+        raise ValueError(f"{len(values)} distinct parents; one retrieval names at most {LABELS_MAX_SET}")
+    return values
+
+
+def _parent_column(parent_ids) -> Optional[List[int]]:
+    """Column ``PARENT_COLUMN``'s values of the rows a ``bulk_add_docs`` appends, or None when one of the parent ids
+    does not fit: the append then leaves the column not installed, and the next ``retrieve_under`` meets the id in its
+    scan of the store and raises there."""
+    try:
+        return [_parent_value(p) for p in parent_ids]
+    except ValueError:
+        return None
+
+
+def _under_where(parent_ids, levels) -> list:
+    """The predicate of ``retrieve_under``: a child of one of ``parent_ids``, and on one of ``levels`` unless None."""
+    where = [(PARENT_COLUMN, "in", _parent_values(parent_ids))]
+    if levels is not None:
+        where.append((0, "in", _level_labels(levels)))
+    return where
+
+
 def _level_labels(levels) -> List[int]:
     """The label set of ``retrieve_at_level``: ``levels`` (an int or an iterable of ints) as the distinct stored labels
     ``level + 1``, ascending.  ValueError for a level that is negative or no integer, and for more than
@@ -509,17 +570,18 @@ class KB:
         new_ids: List[int] = []
         new_vecs: List[List[float]] = []
         new_labels: List[int] = []     # level + 1 of every new embedding's doc (retrieve_at_level)
+        new_parents: List[Optional[int]] = []   # its parent id (retrieve_under)
         try:
             with self.db.transaction():
                 live = True
-                pending: List[Tuple[int, str, int]] = []
+                pending: List[Tuple[int, str, int, Optional[int]]] = []
 
                 def add_doc(text: str, parent_id: Optional[int] = None, meta: Optional[Dict[str, Any]] = None,
                             no_embedding: bool = False) -> int:
                     assert live, "You may not call this function outside of the context manager!"
                     doc_id, level = self.db.add_doc_at(text, parent_id, meta)
                     if not no_embedding:
-                        pending.append((doc_id, text, level))
+                        pending.append((doc_id, text, level, parent_id))
                     return doc_id
 
                 try:
@@ -528,18 +590,20 @@ class KB:
                     live = False
                 for c0 in range(0, len(pending), BULK_EMBEDDING_CHUNK_SIZE):
                     chunk = pending[c0:c0 + BULK_EMBEDDING_CHUNK_SIZE]
-                    vectors = self._embed([t for _, t, _ in chunk])
-                    for (doc_id, _, level), vec in zip(chunk, vectors):
+                    vectors = self._embed([c[1] for c in chunk])
+                    for (doc_id, _, level, parent_id), vec in zip(chunk, vectors):
                         new_ids.append(self.db.set_doc_embedding(doc_id, embedding_to_bytes(vec)))
                         new_vecs.append(vec)
                         new_labels.append(level + 1)
+                        new_parents.append(parent_id)
         except BaseException:
             self.embeddings_matrix.invalidate()
             raise
         # committed: the reference drops the whole cached matrix here (kb.py:1523); the
         # HBM copy is instead extended in place (falls back to invalidate when not loaded)
         if new_ids:
-            self.embeddings_matrix.append(np.array(new_vecs, dtype=np.float32), new_ids, labels=new_labels)
+            self.embeddings_matrix.append(np.array(new_vecs, dtype=np.float32), new_ids, labels=new_labels,
+                                          columns={PARENT_COLUMN: _parent_column(new_parents)})
 
     @contextmanager
     def bulk_del_docs(self) -> Iterator[Callable[[int], None]]:
@@ -640,6 +704,39 @@ class KB:
         query_vec = np.array(self._embed([query])[0], dtype=np.float32)
         _LOG.info("got embedding for query!")
         emb_ids, matched = self.embeddings_matrix.search_labeled(query_vec, n, labels)   # filter + superheavy(): HIP
+        _LOG.info(f"computed {matched} cosine similarities")
+        with self.db.transaction():
+            res = _fetch_list(self.db, emb_ids)
+        _LOG.info(f"retrieved top {n} documents")
+        return res
+
+    def retrieve_under(self, query: str, n: int, parent_ids, levels=None) -> List[Dict[str, Any]]:
+        """``retrieve`` restricted to the children of ``parent_ids`` (an int or an iterable of ints, at most 1,024
+        distinct), and with ``levels`` also to those levels as in ``retrieve_at_level``: the top n of those docs, same
+        log lines and result shape -- the answer of ``retrieve_within`` over those children's ids.  ``parent_id + 1``
+        sits next to each vector in HBM in column ``PARENT_COLUMN`` (0 = no parent) beside the level in column 0, and
+        the conjunction runs on the device (svs_index_search_where): no doc-id list, no SQL per query.  The column is
+        installed and maintained exactly like the level column: at the first such retrieval of an index generation,
+        by one scan of the docs table; afterwards ``bulk_add_docs`` passes the values of the rows it appends and
+        deletions move them with the rows.  No parent, or a parent without children, gives ``[]``; a parent id that is
+        negative, no integer or >= 2**32 - 1, in the call or in the store, raises ValueError."""
+        where = _under_where(parent_ids, levels)
+        _LOG.info(f"retrieving {n} documents with query string: {query}")
+        assert self.db is not None
+        self.embeddings_matrix.get_sync(self.db)
+
+        def from_store(read):
+            def fetch():
+                with self.db.transaction():
+                    return read()
+            return fetch
+
+        self.embeddings_matrix.ensure_column(PARENT_COLUMN, from_store(self.db.embedding_parents))
+        if levels is not None:
+            self.embeddings_matrix.ensure_labels(from_store(self.db.embedding_levels))
+        query_vec = np.array(self._embed([query])[0], dtype=np.float32)
+        _LOG.info("got embedding for query!")
+        emb_ids, matched = self.embeddings_matrix.search_where(query_vec, n, where)   # filter + superheavy(): HIP
         _LOG.info(f"computed {matched} cosine similarities")
         with self.db.transaction():
             res = _fetch_list(self.db, emb_ids)
@@ -942,7 +1039,7 @@ class AsyncKB:
     async def bulk_add_docs(self):
         async with self._get_lock():
             db = await self._ensure_db()
-            pending: List[Tuple[int, str, int]] = []
+            pending: List[Tuple[int, str, int, Optional[int]]] = []
             live = True
             db.conn.execute("BEGIN")
             try:
@@ -951,7 +1048,7 @@ class AsyncKB:
                     assert live, "You may not call this function outside of the context manager!"
                     doc_id, level = db.add_doc_at(text, parent_id, meta)
                     if not no_embedding:
-                        pending.append((doc_id, text, level))
+                        pending.append((doc_id, text, level, parent_id))
                     return doc_id
                 try:
                     yield add_doc
@@ -960,13 +1057,15 @@ class AsyncKB:
                 new_ids: List[int] = []
                 new_vecs: List[List[float]] = []
                 new_labels: List[int] = []     # level + 1 of every new embedding's doc (retrieve_at_level)
+                new_parents: List[Optional[int]] = []   # its parent id (retrieve_under)
                 for c0 in range(0, len(pending), BULK_EMBEDDING_CHUNK_SIZE):
                     chunk = pending[c0:c0 + BULK_EMBEDDING_CHUNK_SIZE]
-                    vectors = await self._embed([t for _, t, _ in chunk])
-                    for (doc_id, _, level), vec in zip(chunk, vectors):
+                    vectors = await self._embed([c[1] for c in chunk])
+                    for (doc_id, _, level, parent_id), vec in zip(chunk, vectors):
                         new_ids.append(db.set_doc_embedding(doc_id, embedding_to_bytes(vec)))
                         new_vecs.append(vec)
                         new_labels.append(level + 1)
+                        new_parents.append(parent_id)
             except BaseException:
                 db.conn.execute("ROLLBACK")
                 self.embeddings_matrix.invalidate()
@@ -976,7 +1075,8 @@ class AsyncKB:
             if new_ids:   # extend the HBM copy in place (reference: invalidate(), kb.py:1062)
                 loop = asyncio.get_running_loop()
                 await loop.run_in_executor(None, lambda: self.embeddings_matrix.append(
-                    np.array(new_vecs, dtype=np.float32), new_ids, labels=new_labels))
+                    np.array(new_vecs, dtype=np.float32), new_ids, labels=new_labels,
+                    columns={PARENT_COLUMN: _parent_column(new_parents)}))
 
     @asynccontextmanager
     async def bulk_del_docs(self):
@@ -1056,6 +1156,27 @@ class AsyncKB:
             query_vec = np.array((await self._embed([query]))[0], dtype=np.float32)
             _LOG.info("got embedding for query!")
             emb_ids, matched = await self._search(held, labeled_op(query_vec, n, labels))
+            _LOG.info(f"computed {matched} cosine similarities")
+        res = await self._fetch(lambda db: _fetch_list(db, emb_ids))
+        _LOG.info(f"retrieved top {n} documents")
+        return res
+
+    async def retrieve_under(self, query: str, n: int, parent_ids, levels=None) -> List[Dict[str, Any]]:
+        """Async twin of ``KB.retrieve_under``, structured as ``retrieve_at_level``: the columns are installed (when
+        this index generation lacks them) and the reference to the matrix is taken under the lock, the predicate search
+        runs on an executor thread outside it, the docs are fetched under the lock."""
+        where = _under_where(parent_ids, levels)
+        _LOG.info(f"retrieving {n} documents with query string: {query}")
+
+        def install(db):
+            self.embeddings_matrix.ensure_column(PARENT_COLUMN, db.embedding_parents)
+            if levels is not None:
+                self.embeddings_matrix.ensure_labels(db.embedding_levels)
+
+        async with self._held(install) as (held, _):
+            query_vec = np.array((await self._embed([query]))[0], dtype=np.float32)
+            _LOG.info("got embedding for query!")
+            emb_ids, matched = await self._search(held, where_op(query_vec, n, where))
             _LOG.info(f"computed {matched} cosine similarities")
         res = await self._fetch(lambda db: _fetch_list(db, emb_ids))
         _LOG.info(f"retrieved top {n} documents")

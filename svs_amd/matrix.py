@@ -22,7 +22,7 @@ from __future__ import annotations
 import asyncio
 import logging
 import threading
-from typing import Any, Callable, List, Optional, Tuple
+from typing import Any, Callable, Dict, List, Optional, Tuple
 
 import numpy as np
 
@@ -203,6 +203,21 @@ def labeled_op(query_vec: np.ndarray, n: int, labels):
     return native, finish
 
 
+def where_op(query_vec: np.ndarray, n: int, where):
+    """Predicate search: ``idx.search_where`` (svs_index_search_where) over the rows on which every term of ``where``
+    holds, rows -> ids: ([(score, emb_id)], rows that satisfy the predicate).  The columns are whatever the index holds
+    (``DeviceEmbeddingsMatrix.ensure_column``)."""
+    def native(idx, lookup, *_):
+        return idx, idx.search_where(query_vec, n, where)
+
+    def finish(res, arr):
+        used, (rows, matched) = res
+        off = int(getattr(used, "row_offset", 0))
+        return [(score, int(arr[row - off])) for score, row in rows], int(matched)
+
+    return native, finish
+
+
 def by_label_op(query_vec: np.ndarray, labels, min_score: Optional[float] = None, n: Optional[int] = None):
     """Per-label breakdown: ``idx.search_by_label`` (svs_index_search_by_label) over ``labels``, rows -> ids:
     [(label, score, emb_id of the label's best row, rows of the label at or above ``min_score``)], best label first.
@@ -315,8 +330,9 @@ class DeviceEmbeddingsMatrix:
         self.embeddings_matrix: Optional[np.ndarray] = None   # host copy (pairwise path), optional
         self._lookup: Optional[_Lookup] = None
         self._n_dead = 0
-        # the index generation whose label column is installed and complete (ensure_labels); None: none is
-        self._labels_for: Optional[Any] = None
+        # column -> the index generation for which it is installed and complete (ensure_column); absent: none is.
+        # Column 0 is the label column (ensure_labels).
+        self._columns_for: Dict[int, Any] = {}
         # concurrent single-query searches of one index generation share corpus passes (coalesce.py)
         self.coalesce = True
         self._coalescer: Optional[SearchCoalescer] = None
@@ -336,7 +352,7 @@ class DeviceEmbeddingsMatrix:
             self.embeddings_matrix = None
             self._lookup = None
             self._n_dead = 0
-            self._labels_for = None
+            self._columns_for = {}
             self._coalescer = None
         if idx is not None:
             idx.release()
@@ -417,13 +433,17 @@ class DeviceEmbeddingsMatrix:
         return idx
 
     # -- incremental update ---------------------------------
-    def append(self, new_rows: np.ndarray, new_ids, labels=None) -> bool:
+    def append(self, new_rows: np.ndarray, new_ids, labels=None, columns: Optional[Dict[int, Any]] = None) -> bool:
         """Rows a ``bulk_add_docs`` just committed, in embedding-id order (the order
         ``SELECT id, embedding FROM embeddings`` would return them, src/svs/kb.py:603).
         Edits the HBM copy in place; False if nothing is loaded (the next ``get``
-        builds from storage anyway).  ``labels``: one per new row, set behind the append while this generation's
-        label column is installed (``ensure_labels``); an append WITHOUT labels marks the column not installed -- the
-        new rows carry label 0 until the next ``ensure_labels`` installs the whole column again."""
+        builds from storage anyway).  ``columns``: {column: one value per new row}, each set behind the append while
+        this generation's column is installed (``ensure_column``); an append WITHOUT values for an installed column
+        marks it not installed -- the new rows carry 0 there until the next ``ensure_column`` installs the whole column
+        again.  ``labels`` is ``columns[0]``."""
+        given = dict(columns or {})
+        if labels is not None:
+            given[0] = labels
         new_rows = np.ascontiguousarray(new_rows, dtype=np.float32)
         ids = np.asarray(new_ids, dtype=np.int64)
         with self._mu:
@@ -436,16 +456,19 @@ class DeviceEmbeddingsMatrix:
                     or np.any(np.diff(ids) <= 0) or new_rows.shape[1] != idx.shape[1]:
                 idx = None   # not a pure append (or dimension change): rebuild
             else:
-                installed = self._labels_for is idx
-                self._labels_for = None      # (until the new rows' labels are in: a failure below leaves it so)
+                installed = [c for c, gen in self._columns_for.items() if gen is idx]
+                self._columns_for = {}       # (until the new rows' values are in: a failure below leaves it so)
                 row0 = int(getattr(idx, "row_offset", 0)) + len(lk.arr)
                 idx.append(new_rows)
                 lk.arr = np.concatenate([lk.arr, ids])
-                if installed and labels is not None:
-                    if len(labels) != len(ids):
-                        raise ValueError(f"{len(labels)} labels for {len(ids)} new rows")
-                    idx.set_labels(labels, row0)
-                    self._labels_for = idx
+                for c in installed:
+                    values = given.get(c)
+                    if values is None:
+                        continue
+                    if len(values) != len(ids):
+                        raise ValueError(f"{len(values)} {'labels' if c == 0 else f'values of column {c}'} for {len(ids)} new rows")
+                    self._set_column(idx, c, values, row0)
+                    self._columns_for[c] = idx
                 if self.embeddings_matrix is not None:
                     self.embeddings_matrix = np.vstack([self.embeddings_matrix, new_rows])
         if idx is None:
@@ -550,16 +573,28 @@ class DeviceEmbeddingsMatrix:
         ([(score, emb_id)], total qualifying) (``KB.retrieve_above``)."""
         return self.run_mapped(above_op(query_vec, min_score, n))
 
+    @staticmethod
+    def _set_column(idx, c: int, values, row0=None) -> None:
+        """Column 0 goes through ``set_labels``: it is the label column, and every index double has that entry."""
+        if c == 0:
+            idx.set_labels(values, row0)
+        else:
+            idx.set_column(c, values, row0)
+
     def ensure_labels(self, fetch: Callable[[], Tuple[Any, Any]]) -> bool:
-        """The label column of the loaded index generation, installed at most once per generation: a no-op (False) while
-        it is installed; otherwise ``fetch()`` -> (embedding ids, labels), any order, is mapped to rows with one
-        ``searchsorted`` on the lookup, rows nobody names get 0, and ONE ``set_labels`` writes the whole range (True).
+        """``ensure_column(0, fetch)``: the label column."""
+        return self.ensure_column(0, fetch)
+
+    def ensure_column(self, c: int, fetch: Callable[[], Tuple[Any, Any]]) -> bool:
+        """Column ``c`` of the loaded index generation, installed at most once per generation: a no-op (False) while
+        it is installed; otherwise ``fetch()`` -> (embedding ids, values), any order, is mapped to rows with one
+        ``searchsorted`` on the lookup, rows nobody names get 0, and ONE write sets the whole range (True).
         Ids the loaded matrix does not hold (committed, not yet appended) are skipped: their ``append`` brings their
-        labels.  ``append`` and this method exclude each other, so a row is never left with a stale label: it is
-        labelled by whichever of the two saw it last."""
+        values.  ``append`` and this method exclude each other, so a row is never left with a stale value: it is
+        written by whichever of the two saw it last."""
         with self._mu:
             idx, lk = self._loaded()
-            if self._labels_for is idx:
+            if self._columns_for.get(c) is idx:
                 return False
             ids, labels = fetch()
             ids = np.asarray(ids, dtype=np.int64).reshape(-1)
@@ -571,14 +606,19 @@ class DeviceEmbeddingsMatrix:
                 known = arr[pos] == ids
                 column[pos[known]] = labels[known]
             if len(column):
-                idx.set_labels(column)
-            self._labels_for = idx
+                self._set_column(idx, c, column)
+            self._columns_for[c] = idx
             return True
 
     def search_labeled(self, query_vec: np.ndarray, n: int, labels) -> Tuple[List[Tuple[float, int]], int]:
         """``search`` over the stored embeddings whose label is in ``labels``: ([(score, emb_id)], how many carry
         such a label) (``KB.retrieve_at_level``).  Call ``ensure_labels`` first."""
         return self.run_mapped(labeled_op(query_vec, n, labels))
+
+    def search_where(self, query_vec: np.ndarray, n: int, where) -> Tuple[List[Tuple[float, int]], int]:
+        """``search`` over the stored embeddings on which every term of ``where`` holds: ([(score, emb_id)], how many
+        satisfy it) (``KB.retrieve_under``).  Call ``ensure_column`` for the columns it names first."""
+        return self.run_mapped(where_op(query_vec, n, where))
 
     def search_by_label(self, query_vec: np.ndarray, labels, min_score: Optional[float] = None,
                         n: Optional[int] = None) -> List[Tuple[int, float, int, int]]:

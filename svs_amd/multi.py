@@ -222,6 +222,20 @@ class MultiDeviceIndex:
     def set_labels(self, labels, row0: Optional[int] = None):
         raise NotImplementedError("labels are per device: call set_labels on a DeviceIndex")
 
+    def search_where(self, query_vec: np.ndarray, n: int, where):
+        raise NotImplementedError("predicate search is per device: the columns sit beside one shard's rows; call set_column / search_where on a DeviceIndex")
+
+    search_batch_where = search_where
+
+    def count_where(self, where):
+        raise NotImplementedError("predicate counts are per device: the columns sit beside one shard's rows; call count_where on a DeviceIndex")
+
+    def set_column(self, c: int, values, row0: Optional[int] = None):
+        raise NotImplementedError("columns are per device: call set_column on a DeviceIndex")
+
+    def column(self, c: int, row0: Optional[int] = None, nrows: Optional[int] = None):
+        raise NotImplementedError("columns are per device: call column on a DeviceIndex")
+
     def assign(self, vectors, labels=None, row0: Optional[int] = None, nrows: Optional[int] = None, scores: bool = True):
         raise NotImplementedError("assignment is per device: the rows and their label column sit in one shard's HBM; call assign on a DeviceIndex")
 

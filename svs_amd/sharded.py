@@ -215,6 +215,20 @@ class ShardedIndex:
 
     search_batch_by_label = search_by_label
 
+    def search_where(self, query_vec: np.ndarray, n: int, where):
+        raise NotImplementedError("predicate search is per device: a rank fills and searches the columns of its own shard (DeviceIndex.search_where); nothing is merged across ranks")
+
+    search_batch_where = search_where
+
+    def count_where(self, where):
+        raise NotImplementedError("predicate counts are per device: a rank counts over its own shard (DeviceIndex.count_where); nothing is merged across ranks")
+
+    def set_column(self, c, values, row0=None):
+        raise NotImplementedError("columns are per device: a rank fills the columns of its own shard (DeviceIndex.set_column)")
+
+    def column(self, c, row0=None, nrows=None):
+        raise NotImplementedError("columns are per device: a rank reads the columns of its own shard (DeviceIndex.column)")
+
     def assign(self, vectors, labels=None, row0=None, nrows=None, scores=True):
         raise NotImplementedError("assignment is per device: a rank assigns the rows of its own shard (DeviceIndex.assign); nothing is merged across ranks")
 
