@@ -459,6 +459,42 @@ int32_t svs_index_search_above(svs_index* idx, const float* queries, int32_t nq,
                                float* out_scores, int64_t* out_rows /* stride limit */,
                                int32_t* out_counts /* nq */, int64_t* out_totals /* nq, or NULL */);
 
+/* Combined search: the top k rows ranked by how they score against SEVERAL vectors at once -- the best score against
+ * any of a question's rewordings (MAX), "relevant to all of these" (MIN), "like these, less like those" (a weighted SUM
+ * with negative weights) -- in one pass over the corpus and one selection, with nothing but the answer leaving the device.
+ * Exact definition.  A combined query is m vectors v_0 .. v_{m-1} (1 <= m <= SVS_COMBINE_MAX_VECTORS), weights w_j
+ * (weights == NULL: every w_j is 1.0f) and an op.  Let s_j be the vector svs_index_scores_n(idx, v_j) returns at that
+ * moment (the unscreened single-query score kernel of the index's dtype: each vector is quantised the way the index
+ * quantises a query; an f32 index reads its f32 rows, never the half shadow), and t_j[i] = w_j * s_j[i], ONE f32
+ * multiplication rounded to nearest (with w_j == 1.0f that is s_j[i]).  The combined score c[i] of local row i is
+ *   SVS_COMBINE_MAX   key_score(max_j score_key(t_j[i]))    the order's own key (svs_amd/csrc/keys.h): -0.0 folds onto
+ *   SVS_COMBINE_MIN   key_score(min_j score_key(t_j[i]))    +0.0 and any NaN is the largest value
+ *   SVS_COMBINE_SUM   ((t_0[i] + t_1[i]) + t_2[i]) + ...    f32 additions in vector order, each rounded to nearest; no
+ *                                                           fused multiply-add joins a multiplication and an addition
+ * and the result is what the top-k stage returns over c with the tombstoned rows masked: count = min(max(k, 0), live
+ * rows), out_*[q*k .. q*k + count) in (score desc, row desc) order, rows as row_offset + local row, a NaN as the quiet
+ * NaN 0x7fc00000; entries past the count are not touched.  *out_count (may be NULL) is the same for every query.  With
+ * m == 1, weights == NULL and SVS_COMBINE_MAX the result equals svs_index_search's on an unscreened index: rows and
+ * score bits.  A query's result does not depend on nq or on the other queries of the call.
+ * vectors: host, (nq, m, d) C-contiguous; weights: host, (nq, m), or NULL.  The nq combined queries run back to back
+ * on one stream with no host wait between them.
+ * Errors: everything is validated before anything is launched, and a failing call writes no output.  All of them are
+ * SVS_ERR_INVALID and name the argument: nq < 0, m outside 1 .. SVS_COMBINE_MAX_VECTORS, d != index d, an unknown op,
+ * k < 0, null vectors with nq > 0, a NaN or infinite weight (the message names the query and the vector), null
+ * out_scores / out_rows with work to do (nq > 0 and count > 0).  nq == 0 or k == 0 -> SVS_OK, nothing launched.
+ * Cost.  Row lengths with a one-shot single-query kernel (f32: multiples of 256 floats up to 4096; f16: multiples of
+ * 512 halves up to 4096; fp8: 512, 1024, 1536, 2048, 3072, 4096 bytes) take ONE fused pass: every wave loads its rows
+ * once and streams the m vectors through them.  Every other row length takes m single-query passes and one elementwise
+ * kernel over the m score vectors.  Both give the bits of the definition.
+ * Blocking; re-entrant on one handle; holds a reference and the geometry lock shared; waits for pending staging
+ * copies; never goes through the coalescer, the run-ahead pipelines or shared passes: all as svs_index_search_above.
+ * Out of scope: svs_multi / row-sharded corpora and a device-pointer variant. */
+#define SVS_COMBINE_MAX_VECTORS 8
+enum { SVS_COMBINE_MAX = 0, SVS_COMBINE_MIN = 1, SVS_COMBINE_SUM = 2 };
+int32_t svs_index_search_combined(svs_index* idx, const float* vectors /* host, [nq][m][d] */, int32_t nq, int32_t m, int32_t d,
+                                  const float* weights /* [nq][m] or NULL */, int32_t op, int32_t k,
+                                  float* out_scores, int64_t* out_rows /* [nq][k] */, int32_t* out_count);
+
 /* Per-label breakdown: for every label of a set, how many live rows of that label score at or above a cut-off and
  * which of them is the best, the labels ordered by their best row -- facet counts plus one best hit per facet ("120
  * hits in manuals, 30 in FAQ, 2 in release notes; here is the best one of each, best source first") in one corpus

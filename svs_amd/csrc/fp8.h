@@ -110,6 +110,38 @@ template <int LB> struct Fp8Chunk;
 template <> struct Fp8Chunk<16> { typedef u32x4_t type; };
 template <> struct Fp8Chunk<8> { typedef u32x2_t type; };
 
+// One row against one packed query: THE summation order of the one-shot row lengths.  Lane l holds chunk j * 64 + l of
+// the row and of the query; the 32-bit words of a chunk alternate between s0 (even) and s1 (odd); then wave_sum(s0 + s1),
+// still unscaled.  gemv_fp8_oneshot_kernel and the combined search's fused kernel (combine.h) both call this.
+template <int NSTEP, int LB>
+__device__ __forceinline__ float row_dot_fp8(const typename Fp8Chunk<LB>::type (&row)[NSTEP], const typename Fp8Chunk<LB>::type (&qv)[NSTEP]) {
+  constexpr int NW = LB / 4;               // 32-bit words per lane per load
+  float s0 = 0.f, s1 = 0.f;
+#pragma unroll
+  for (int j = 0; j < NSTEP; ++j) {
+    uint32_t aw[NW], qw[NW];
+    if constexpr (NW == 4) {
+      aw[0] = row[j].x; aw[1] = row[j].y; aw[2] = row[j].z; aw[3] = row[j].w;
+      qw[0] = qv[j].x; qw[1] = qv[j].y; qw[2] = qv[j].z; qw[3] = qv[j].w;
+    } else {
+      aw[0] = row[j].x; aw[1] = row[j].y;
+      qw[0] = qv[j].x; qw[1] = qv[j].y;
+    }
+#pragma unroll
+    for (int w = 0; w < NW; ++w) {
+      float v[4], u[4];
+      unpack_fp8x4(aw[w], v);
+      unpack_fp8x4(qw[w], u);
+      float& acc = (w & 1) ? s1 : s0;
+      acc = fmaf(v[0], u[0], acc);
+      acc = fmaf(v[1], u[1], acc);
+      acc = fmaf(v[2], u[2], acc);
+      acc = fmaf(v[3], u[3], acc);
+    }
+  }
+  return wave_sum(s0 + s1);
+}
+
 // The query stays PACKED (e4m3, LB bytes per lane per step) and is converted next
 // to the row bytes: 4x fewer registers than holding it as f32, which is what lets
 // two 16-wave workgroups share a CU (the kernel is HBM-bound; the extra
@@ -119,7 +151,6 @@ __global__ __launch_bounds__(WPB * 64) void gemv_fp8_oneshot_kernel(
     const uint8_t* __restrict__ M, const float* __restrict__ row_scales, const uint8_t* __restrict__ q8,
     const float* __restrict__ q_scale, float* __restrict__ scores, int64_t n) {
   typedef typename Fp8Chunk<LB>::type chunk_t;
-  constexpr int NW = LB / 4;               // 32-bit words per lane per load
   constexpr int64_t LDB = (int64_t)NSTEP * 64 * LB;
   const int lane = threadIdx.x & 63;
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -141,32 +172,9 @@ __global__ __launch_bounds__(WPB * 64) void gemv_fp8_oneshot_kernel(
   float out = 0.f;
 #pragma unroll
   for (int r = 0; r < R; ++r) {
-    float s0 = 0.f, s1 = 0.f;
-#pragma unroll
-    for (int j = 0; j < NSTEP; ++j) {
-      uint32_t aw[NW], qw[NW];
-      if constexpr (NW == 4) {
-        aw[0] = buf[r][j].x; aw[1] = buf[r][j].y; aw[2] = buf[r][j].z; aw[3] = buf[r][j].w;
-        qw[0] = qv[j].x; qw[1] = qv[j].y; qw[2] = qv[j].z; qw[3] = qv[j].w;
-      } else {
-        aw[0] = buf[r][j].x; aw[1] = buf[r][j].y;
-        qw[0] = qv[j].x; qw[1] = qv[j].y;
-      }
-#pragma unroll
-      for (int w = 0; w < NW; ++w) {
-        float v[4], u[4];
-        unpack_fp8x4(aw[w], v);
-        unpack_fp8x4(qw[w], u);
-        float& acc = (w & 1) ? s1 : s0;
-        acc = fmaf(v[0], u[0], acc);
-        acc = fmaf(v[1], u[1], acc);
-        acc = fmaf(v[2], u[2], acc);
-        acc = fmaf(v[3], u[3], acc);
-      }
-    }
     int64_t row = row0 + r;
     row = row < n ? row : n - 1;
-    const float v = wave_sum(s0 + s1) * row_scales[row] * sq;
+    const float v = row_dot_fp8<NSTEP, LB>(buf[r], qv) * row_scales[row] * sq;
     out = lane == r ? v : out;
   }
   const int64_t row = row0 + lane;

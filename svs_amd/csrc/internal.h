@@ -24,7 +24,9 @@ int32_t svs_internal_coalesce_hold(svs_index* idx, int32_t n);
  *   6  run-ahead pipelines, the grid of a shareable search's own pass: 0 = thin (one resident set of workgroups) where the
  *      host predicts that an earlier pass serves the search (default); 1 = always the one-shot grid; 2 = always thin
  *   7  svs_index_search_by_label, what crosses workgroups (by_label.h): 0 = integer atomics on the query's table in HBM
- *      (default); 1 = one partial table per workgroup, reduced by the final kernel.  The same bits either way. */
+ *      (default); 1 = one partial table per workgroup, reduced by the final kernel.  The same bits either way.
+ *   8  svs_index_search_combined, the route (combine.h): 0 = the route's own choice (default); 1 = the fused kernel
+ *      wherever the row length has one; 2 = always m single-query passes and combine_scores_kernel.  The same bits. */
 int32_t svs_internal_tune(int32_t what, int64_t value);
 /* Seconds since the start of the calling thread's last svs_index_search(host batch) at which: [0] scratch was planned,
  * [1] the queries were in pinned memory (and their DMA enqueued), [2] every kernel was enqueued, [3] the stream had
@@ -141,6 +143,11 @@ int32_t svs_internal_assign_kernel_ms(double* out);
  * last svs_index_label_sums, recorded while svs_index_set_timing is on for the handle; -1 when that call recorded none
  * (a count-only call, tools/label_sums_time.py). */
 int32_t svs_internal_label_sums_kernel_ms(double* out);
+/* The unmasked combined score vector of ONE combined query (svs_index_search_combined: m vectors [m][d], weights [m] or
+ * NULL, op) over all n local rows, into out[0 .. n) (capacity >= n floats).  route: 0 = the route's choice, 1 = the
+ * fused kernel (SVS_ERR_UNSUPPORTED where the row length has none), 2 = m passes and combine_scores_kernel (tests). */
+int32_t svs_internal_combined_scores(svs_index* idx, const float* vectors, int32_t m, int32_t d, const float* weights, int32_t op,
+                                     int32_t route, float* out, int64_t capacity);
 /* multi.hip -> svs_amd.hip: carries a worker thread's error message over to the caller's thread */
 int32_t svs_internal_set_error(int32_t code, const char* msg);
 #ifdef __cplusplus

@@ -12,6 +12,7 @@
 #include <algorithm>
 #include <atomic>
 #include <chrono>
+#include <cmath>
 #include <condition_variable>
 #include <cstdarg>
 #include <cstdio>
@@ -41,6 +42,7 @@
 #include "neighbors.h"
 #include "segments.h"
 #include "above.h"
+#include "combine.h"
 #include "diverse.h"
 #include "labels.h"
 #include "where.h"
@@ -116,6 +118,8 @@ std::atomic<int64_t> g_tune_thin{0};          // run-ahead pipelines, grid of a 
                                               // serves the search, 1 = always the one-shot grid, 2 = always thin (tests)
 std::atomic<int64_t> g_tune_by_label_cross{BL_ATOMIC};  // svs_index_search_by_label, what crosses workgroups: BL_ATOMIC = integer atomics on the query's
                                               // table in HBM, BL_PARTIALS = a partial table per workgroup, reduced by the final kernel (the same bits)
+std::atomic<int64_t> g_tune_combine_route{0};  // svs_index_search_combined: 0 = the route's choice (combine_route), 1 = fused wherever a fused kernel
+                                              // exists, 2 = always m passes (tools/combined_time.py)
 thread_local double g_host_phase[6];         // svs_internal_host_phases: seconds since the call began (last svs_index_search on this thread)
 
 // svs_internal_last_launches: the score kernels the calling thread's last search / scores call enqueued, in order: every
@@ -2257,6 +2261,129 @@ int launch_query_scores(const svs_index* idx, Ctx* c, const SingleRoute& route, 
   return launch_scores(idx, c, route, c->q_dev + (size_t)q * idx->d, c->scores, st);
 }
 
+// ---- svs_index_search_combined (combine.h) -------------------------------------------------------------------------
+static_assert(SVS_COMBINE_MAX == CB_MAX && SVS_COMBINE_MIN == CB_MIN && SVS_COMBINE_SUM == CB_SUM && SVS_COMBINE_MAX_VECTORS == CB_MAX_VECTORS,
+              "combine.h's kernels take the header's op codes and limit");
+static_assert(CB_MAX_VECTORS <= GQ, "the padded vectors of a combined query are staged in Ctx::q16");
+
+// The route of a combined query, decided once per call: the fused kernel of the index's one-shot family, or m passes of
+// `single` -- the kernel svs_index_scores_n runs -- and combine_scores_kernel.
+struct CombineRoute {
+  bool fused;           // what the call runs
+  bool has_fused;       // the row length has a fused kernel
+  SingleRoute single;
+};
+// The default geometry of launch_rows (variant 0), which the fused f32 kernel shares
+constexpr int f32_rows_r(int nstep) { return nstep <= 2 ? 4 : (nstep <= 4 ? 2 : 1); }
+constexpr int f32_rows_wpb(int nstep) { return nstep <= 6 ? 16 : 8; }
+template <int NSTEP>
+constexpr KernelName kCombineF32Name = kernel_name("combine_f32_kernel", NSTEP, f32_rows_r(NSTEP), f32_rows_wpb(NSTEP));
+template <int NSTEP>
+constexpr KernelName kCombineF16Name = kernel_name("combine_f16_kernel", NSTEP, f16_rows_r(NSTEP), f16_rows_wpb(NSTEP));
+template <int NSTEP, int LB, int R>
+constexpr KernelName kCombineFp8Name = kernel_name("combine_fp8_kernel", NSTEP, LB, R, 16);
+
+// Where the fused route is the default, per dtype and m: where it was measured FASTER than the passes (1M x 1536,
+// profiles/combined_time.txt) -- from two vectors on, in all three dtypes.  One vector: a tie within the
+// spread for f32 and f16, and the passes ahead for fp8; it takes the passes.
+inline bool combine_fused_default(int /*dtype*/, int m) { return m >= 2; }
+
+// force: 0 the route's choice, 1 fused where a fused kernel exists, 2 passes
+CombineRoute combine_route(const svs_index* idx, int variant, int m, int force) {
+  const SingleRoute s = single_route(idx, variant, false);
+  // (a geometry A/B variant of the single-query kernels, 1 .. 5, keeps to the passes: its kernels are what is being compared)
+  const bool geometry_ab = variant >= VARIANT_GEMV_PERSISTENT_R1 && variant <= VARIANT_GEMV_1X8;
+  const bool has = (s.family == SingleRoute::F32_ROWS && s.geo >= 1 && s.geo <= 16) || (s.family == SingleRoute::F16_ONESHOT && s.geo >= 1 && s.geo <= 8) ||
+                   s.family == SingleRoute::FP8_ONESHOT;
+  const bool fused = has && force != 2 && (force == 1 || (!geometry_ab && combine_fused_default(idx->dtype, m)));
+  return CombineRoute{fused, has, s};
+}
+
+// One combined query into c->scores[0 .. n), unmasked.  v: its m vectors on the device, [m][d]; w: its m weights on the
+// device.  c->scores holds m * sstride floats (the passes route's m score vectors; the combined one ends up in the first).
+int enqueue_combined_scores(const svs_index* idx, Ctx* c, const CombineRoute& r, const float* v, const float* w, int m, int op, int64_t sstride,
+                            hipStream_t st) {
+  const int64_t n = idx->n;
+  int rc;
+  if (!r.fused) {
+    for (int j = 0; j < m; ++j) {
+      launch_record("gemv", n, 1);
+      if ((rc = launch_scores(idx, c, r.single, v + (size_t)j * idx->d, c->scores + (size_t)j * sstride, st)) != SVS_OK) return rc;
+    }
+    launch_record("combine_scores_kernel", n, m);
+    const int64_t n4 = sstride >> 2;
+    hipLaunchKernelGGL(combine_scores_kernel, dim3((unsigned)std::min<int64_t>((n4 + 255) / 256, 4096)), dim3(256), 0, st, c->scores.p, sstride, n4, m, w, op);
+    return SVS_OK;
+  }
+  if (r.single.family == SingleRoute::FP8_ONESHOT) {
+    if ((rc = stage_queries_fp8(idx, c, v, m, m, false, st)) != SVS_OK) return rc;
+    for_fp8_oneshot(idx->ld, [&](auto ns, auto lb, auto rr) {
+      constexpr int NSTEP = ns(), LB = lb(), R = rr();
+      launch_record(kCombineFp8Name<NSTEP, LB, R>.s, n, m);
+      hipLaunchKernelGGL((combine_fp8_kernel<NSTEP, LB, R, 16>), dim3((unsigned)((n + R * 16 - 1) / (R * 16))), dim3(16 * 64), 0, st, (const uint8_t*)idx->rows,
+                         (const float*)idx->row_scales, (const uint8_t*)c->q8.p, (const float*)c->q8s.p, w, m, op, c->scores.p, n);
+    });
+    return SVS_OK;
+  }
+  // f32 / f16: the vectors as ld floats each, 16-byte aligned -- the caller's where the rows are not padded
+  const float* q = v;
+  if (idx->ld != idx->d || (((uintptr_t)v) & 15) != 0) {
+    if ((rc = c->q16.grow((size_t)GQ * idx->ld)) != SVS_OK) return rc;
+    HIP_TRY(hipMemsetAsync(c->q16, 0, (size_t)m * idx->ld * sizeof(float), st));
+    HIP_TRY(hipMemcpy2DAsync(c->q16, (size_t)idx->ld * sizeof(float), v, (size_t)idx->d * sizeof(float), (size_t)idx->d * sizeof(float), (size_t)m,
+                             hipMemcpyDeviceToDevice, st));
+    q = c->q16;
+  }
+  if (r.single.family == SingleRoute::F16_ONESHOT) {
+    for_f16_oneshot(r.single.geo, [&](auto ns) {
+      constexpr int NSTEP = ns(), R = f16_rows_r(NSTEP), WPB = f16_rows_wpb(NSTEP);
+      launch_record(kCombineF16Name<NSTEP>.s, n, m);
+      hipLaunchKernelGGL((combine_f16_kernel<NSTEP, R, WPB>), dim3((unsigned)((n + R * WPB - 1) / (R * WPB))), dim3(WPB * 64), 0, st, (const u32x4*)idx->rows,
+                         (const v4f*)q, w, m, op, c->scores.p, n);
+    });
+    return SVS_OK;
+  }
+  switch (r.single.geo) {
+#define SVS_ROWS_CASE(N)                                                                                                                        \
+  case N: {                                                                                                                                     \
+    constexpr int R = f32_rows_r(N), WPB = f32_rows_wpb(N);                                                                                     \
+    launch_record(kCombineF32Name<N>.s, n, m);                                                                                                  \
+    hipLaunchKernelGGL((combine_f32_kernel<N, R, WPB>), dim3((unsigned)((n + R * WPB - 1) / (R * WPB))), dim3(WPB * 64), 0, st,                 \
+                       (const v4f*)idx->rows, (const v4f*)q, w, m, op, c->scores.p, n);                                                         \
+    break;                                                                                                                                      \
+  }
+    SVS_ROWS_CASE(1) SVS_ROWS_CASE(2) SVS_ROWS_CASE(3) SVS_ROWS_CASE(4) SVS_ROWS_CASE(5) SVS_ROWS_CASE(6) SVS_ROWS_CASE(7) SVS_ROWS_CASE(8)
+    SVS_ROWS_CASE(9) SVS_ROWS_CASE(10) SVS_ROWS_CASE(11) SVS_ROWS_CASE(12) SVS_ROWS_CASE(13) SVS_ROWS_CASE(14) SVS_ROWS_CASE(15) SVS_ROWS_CASE(16)
+#undef SVS_ROWS_CASE
+    default: return fail(SVS_ERR_INVALID, "internal: no fused combine kernel for ld %d", idx->ld);
+  }
+  return SVS_OK;
+}
+
+// The arguments every combined entry takes, checked in the header's order; `entry` names the caller
+int check_combined_args(const char* entry, const svs_index* idx, const float* vectors, int64_t nq, int32_t m, int32_t d, const float* weights, int32_t op) {
+  if (nq < 0) return fail(SVS_ERR_INVALID, "%s: nq must be >= 0", entry);
+  if (m < 1 || m > SVS_COMBINE_MAX_VECTORS) return fail(SVS_ERR_INVALID, "%s: m is %d, a combined query has 1 .. %d vectors", entry, (int)m, SVS_COMBINE_MAX_VECTORS);
+  if (d != idx->d) return fail(SVS_ERR_INVALID, "%s: d is %d, the index holds rows of %d", entry, (int)d, idx->d);
+  if (op != SVS_COMBINE_MAX && op != SVS_COMBINE_MIN && op != SVS_COMBINE_SUM) return fail(SVS_ERR_INVALID, "%s: unknown op %d", entry, (int)op);
+  if (nq > 0 && !vectors) return fail(SVS_ERR_INVALID, "%s: null vectors", entry);
+  for (int64_t i = 0; weights && i < nq * m; ++i)
+    if (!std::isfinite(weights[i]))
+      return fail(SVS_ERR_INVALID, "%s: weights: the weight of vector %d of query %lld is not finite", entry, (int)(i % m), (long long)(i / m));
+  return SVS_OK;
+}
+
+// The call's vectors and weights (null: 1.0f each) to the device in one copy: c->q_dev = [nq * m * d vectors | nq * m weights]
+int upload_combined(Ctx* c, const float* vectors, const float* weights, size_t vn, size_t wn, hipStream_t st) {
+  int rc;
+  if ((rc = c->q_dev.grow(vn + wn)) != SVS_OK || (rc = c->q_pin.grow(vn + wn)) != SVS_OK) return rc;
+  memcpy(c->q_pin, vectors, vn * sizeof(float));
+  if (weights) memcpy(c->q_pin + vn, weights, wn * sizeof(float));
+  else std::fill(c->q_pin + vn, c->q_pin + vn + wn, 1.0f);
+  HIP_TRY(hipMemcpyAsync(c->q_dev, c->q_pin, (vn + wn) * sizeof(float), hipMemcpyHostToDevice, st));
+  return SVS_OK;
+}
+
 // svs_index_set_timing: the two events around a call's kernels, made only when wanted (the index is timed and the call
 // runs what is timed) and destroyed on every exit.  ms(), once the stream has drained: begin to end, or -1.
 struct TimedSpan {
@@ -3780,6 +3907,76 @@ int32_t svs_index_search_above(svs_index* idx, const float* queries, int32_t nq,
   return SVS_OK;
 }
 
+int32_t svs_index_search_combined(svs_index* idx, const float* vectors, int32_t nq, int32_t m, int32_t d, const float* weights, int32_t op,
+                                  int32_t k, float* out_scores, int64_t* out_rows, int32_t* out_count) {
+  launch_reset();
+  if (!idx) return fail(SVS_ERR_INVALID, "svs_index_search_combined: null index");
+  RefGuard guard(idx);
+  std::shared_lock<std::shared_mutex> geo(idx->rw);
+  int rc = check_combined_args("svs_index_search_combined", idx, vectors, nq, m, d, weights, op);
+  if (rc != SVS_OK) return rc;
+  if (k < 0) return fail(SVS_ERR_INVALID, "svs_index_search_combined: k must be >= 0");
+  const int64_t n = idx->n;
+  const int count = (int)std::min<int64_t>(k, n - (int64_t)idx->dead_list.size());
+  if (nq > 0 && count > 0 && (!out_scores || !out_rows)) return fail(SVS_ERR_INVALID, "svs_index_search_combined: null output");
+  if (out_count) *out_count = count;
+  if (nq == 0 || count == 0) return SVS_OK;
+  HostCall fr(idx);
+  if ((rc = fr.open()) != SVS_OK) return rc;
+  Ctx* const c = fr.c;
+  const hipStream_t st = fr.stream();
+  const CombineRoute route = combine_route(idx, idx->variant.load(), m, (int)g_tune_combine_route.load());
+  const int64_t sstride = (n + 3) & ~(int64_t)3;
+  const size_t vn = (size_t)nq * m * d, wn = (size_t)nq * m, on = (size_t)nq * (size_t)count;
+  if ((rc = c->out_s_pin.grow(on)) != SVS_OK || (rc = c->out_r_pin.grow(on)) != SVS_OK) return rc;
+  if ((rc = c->scores.grow((size_t)(route.fused ? 1 : m) * sstride)) != SVS_OK) return rc;
+  if (select_path(n, count) == SelectPath::WINDOW && (rc = grow_select_scratch(c, 1, st)) != SVS_OK) return rc;
+  if ((rc = upload_combined(c, vectors, weights, vn, wn, st)) != SVS_OK) return rc;
+  const bool masked = !idx->dead_list.empty();
+  // every combined query back to back: score pass(es), tombstone mask, selection -- the context's score vectors and
+  // selection scratch are reused in stream order; no host wait in between
+  for (int32_t q = 0; q < nq; ++q) {
+    if ((rc = enqueue_combined_scores(idx, c, route, c->q_dev + (size_t)q * m * d, c->q_dev + vn + (size_t)q * m, m, op, sstride, st)) != SVS_OK) return rc;
+    if (masked)
+      hipLaunchKernelGGL(mask_dead_rows_kernel, dim3(64), dim3(256), 0, st, c->scores.p, sstride, 1, (const uint32_t*)idx->dead_dev.p,
+                         (int64_t)idx->dead_list.size(), n, (int64_t)0);
+    if ((rc = run_select(idx, c, c->scores, n, sstride, 1, count, count, c->out_s_pin + (size_t)q * count, c->out_r_pin + (size_t)q * count, st,
+                         idx->row_offset)) != SVS_OK)
+      return rc;
+  }
+  if ((rc = fr.close("search_combined")) != SVS_OK) return rc;
+  deliver_results(c, nq, count, k, out_scores, out_rows);
+  return SVS_OK;
+}
+
+int32_t svs_internal_combined_scores(svs_index* idx, const float* vectors, int32_t m, int32_t d, const float* weights, int32_t op, int32_t route,
+                                     float* out, int64_t capacity) {
+  launch_reset();
+  if (!idx) return fail(SVS_ERR_INVALID, "svs_internal_combined_scores: null index");
+  RefGuard guard(idx);
+  std::shared_lock<std::shared_mutex> geo(idx->rw);
+  int rc = check_combined_args("svs_internal_combined_scores", idx, vectors, 1, m, d, weights, op);
+  if (rc != SVS_OK) return rc;
+  if (route < 0 || route > 2) return fail(SVS_ERR_INVALID, "svs_internal_combined_scores: route %d", (int)route);
+  const int64_t n = idx->n;
+  if (!out || capacity < n) return fail(SVS_ERR_INVALID, "svs_internal_combined_scores: the index holds %lld rows, the output %lld floats", (long long)n, (long long)capacity);
+  if (n == 0) return SVS_OK;
+  const CombineRoute r = combine_route(idx, idx->variant.load(), m, route);
+  if (route == 1 && !r.has_fused) return fail(SVS_ERR_UNSUPPORTED, "svs_internal_combined_scores: rows of %d elements have no fused kernel", idx->ld);
+  HostCall fr(idx);
+  if ((rc = fr.open()) != SVS_OK) return rc;
+  Ctx* const c = fr.c;
+  const hipStream_t st = fr.stream();
+  const int64_t sstride = (n + 3) & ~(int64_t)3;
+  const size_t vn = (size_t)m * d;
+  if ((rc = c->scores.grow((size_t)(r.fused ? 1 : m) * sstride)) != SVS_OK) return rc;
+  if ((rc = upload_combined(c, vectors, weights, vn, (size_t)m, st)) != SVS_OK) return rc;
+  if ((rc = enqueue_combined_scores(idx, c, r, c->q_dev, c->q_dev + vn, m, op, sstride, st)) != SVS_OK) return rc;
+  if ((rc = fr.launched("combined_scores")) != SVS_OK) return rc;
+  HIP_TRY(hipMemcpyAsync(out, c->scores, (size_t)n * sizeof(float), hipMemcpyDeviceToHost, st));
+  return fr.wait();
+}
+
 int32_t svs_internal_by_label_geometry(int32_t* out) {
   if (!out) return fail(SVS_ERR_INVALID, "null output");
   out[0] = BL_STRIP;
@@ -4510,6 +4707,7 @@ int32_t svs_internal_tune(int32_t what, int64_t value) {
     case 5: if (value < 1 || value > SHARE_MAX) break; g_tune_share.store(value); return SVS_OK;
     case 6: if (value < 0 || value > 2) break; g_tune_thin.store(value); return SVS_OK;
     case 7: if (value != BL_ATOMIC && value != BL_PARTIALS) break; g_tune_by_label_cross.store(value); return SVS_OK;
+    case 8: if (value < 0 || value > 2) break; g_tune_combine_route.store(value); return SVS_OK;
     default: break;
   }
   return fail(SVS_ERR_INVALID, "svs_internal_tune(%d, %lld): unknown knob or value", what, (long long)value);

@@ -26,6 +26,8 @@ _DTYPES = {"f32": _native.DTYPE_F32, "f16": _native.DTYPE_F16, "fp8": _native.DT
 DIVERSE_MAX_FETCH = 1024   # SVS_DIVERSE_MAX_FETCH: the most candidates (and so results) of a diverse search
 LABELS_MAX_SET = 1024      # SVS_LABELS_MAX_SET: the most distinct labels one labelled search names
 ASSIGN_MAX_VECTORS = 1024  # SVS_ASSIGN_MAX_VECTORS: the most vectors one assignment takes
+COMBINE_MAX_VECTORS = _native.COMBINE_MAX_VECTORS   # SVS_COMBINE_MAX_VECTORS: the most vectors of one combined query
+COMBINE_OPS = {"max": _native.COMBINE_MAX, "min": _native.COMBINE_MIN, "sum": _native.COMBINE_SUM}
 
 
 def labels_u32(labels) -> np.ndarray:
@@ -890,6 +892,59 @@ class DeviceIndex:
             raise ValueError(f"query must be 1-D, got shape {q.shape}")
         s, r, red = self.search_batch_diverse(q[None, :], n, fetch_k, lam)
         return list(zip(s[0].astype(np.float64).tolist(), r[0].tolist(), red[0].astype(np.float64).tolist()))
+
+    def search_batch_combined(self, vectors: np.ndarray, n: int, op: str = "max",
+                              weights=None) -> Tuple[np.ndarray, np.ndarray, int]:
+        """Top-n of each COMBINED query (svs_index_search_combined): ``vectors`` is (nq, m, D), 1 <= m <= 8, and a row's
+        score is the ``op`` -- "max", "min" or "sum" -- over its m terms ``weights[q, j] * scores(vectors[q, j])[row]``
+        (``weights`` (nq, m), finite; None: every weight 1).  "max" and "min" compare in the order's own key (-0.0 equals
+        +0.0, a NaN is the largest), "sum" adds the f32 terms in vector order.  One pass over the corpus and one
+        selection per combined query, on the device.  Returns (scores f32 (nq, count), rows i64 (nq, count), count),
+        count = min(max(n, 0), live rows), each row ordered (score desc, row desc); with m = 1, "max" and no weights
+        that is ``search_batch`` on an unscreened index.  Shape, op and weight errors are ValueErrors."""
+        assert isinstance(n, int)
+        v = np.ascontiguousarray(vectors, dtype=np.float32)
+        if v.ndim != 3:
+            raise ValueError(f"vectors must be (nq, m, D), got shape {v.shape}")
+        nq, m, d = v.shape
+        if not 1 <= m <= COMBINE_MAX_VECTORS:
+            raise ValueError(f"a combined query has 1 .. {COMBINE_MAX_VECTORS} vectors, got {m}")
+        if op not in COMBINE_OPS:
+            raise ValueError(f"op must be one of {sorted(COMBINE_OPS)}, got {op!r}")
+        w = None
+        if weights is not None:
+            w = np.ascontiguousarray(weights, dtype=np.float32)
+            if w.shape != (nq, m):
+                raise ValueError(f"weights must be (nq, m) = {(nq, m)}, got shape {w.shape}")
+        h = self._pinned_handle()
+        try:
+            k = min(max(n, 0), self._live_rows(h))   # (clamped before allocating and before the int32 argument, as in search_batch)
+            scores = np.empty((nq, k), dtype=np.float32)
+            rows = np.empty((nq, k), dtype=np.int64)
+            count = C.c_int32(0)
+            # (the one call that releases the GIL)
+            _native.check(self._lib.svs_index_search_combined(h, v.ctypes.data, nq, m, d, None if w is None else w.ctypes.data,
+                                                              COMBINE_OPS[op], k, scores.ctypes.data, rows.ctypes.data, C.byref(count)))
+        finally:
+            self._unpin(h)
+        s, r = self._trimmed(scores, rows, count.value)
+        return s, r, count.value
+
+    def search_combined(self, vectors: np.ndarray, n: int, op: str = "max", weights=None) -> List[Tuple[float, int]]:
+        """One combined query (see ``search_batch_combined``): ``vectors`` (m, D), ``weights`` (m,) or None;
+        [(score, row)] as ``search`` returns them."""
+        assert isinstance(n, int)
+        v = np.asarray(vectors, dtype=np.float32)
+        if v.ndim != 2:
+            raise ValueError(f"vectors must be (m, D), got shape {v.shape}")
+        w = None
+        if weights is not None:
+            w = np.asarray(weights, dtype=np.float32)
+            if w.ndim != 1:
+                raise ValueError(f"weights must be (m,), got shape {w.shape}")
+            w = w[None, :]
+        s, r, _ = self.search_batch_combined(v[None, :, :], n, op, w)
+        return list(zip(s[0].astype(np.float64).tolist(), r[0].tolist()))
 
     def neighbors(self, rows, n: int) -> Tuple[np.ndarray, np.ndarray]:
         """The ``n`` nearest stored rows of each listed stored row (GLOBAL indices, any order, repeats allowed), the

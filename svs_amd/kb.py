@@ -29,8 +29,8 @@ from typing import Any, Awaitable, Callable, Dict, Iterator, List, Optional, Tup
 
 import numpy as np
 
-from .index import ASSIGN_MAX_VECTORS, LABELS_MAX_SET, DeviceIndex
-from .matrix import (DeviceEmbeddingsMatrix, above_op, assign_op, batch_op, by_label_op, cluster_op, diverse_op, labeled_op, neighbors_op, pairs_op, segments_op, single_op, where_op,
+from .index import ASSIGN_MAX_VECTORS, COMBINE_MAX_VECTORS, LABELS_MAX_SET, DeviceIndex
+from .matrix import (DeviceEmbeddingsMatrix, above_op, assign_op, batch_op, by_label_op, cluster_op, combined_op, diverse_op, labeled_op, neighbors_op, pairs_op, segments_op, single_op, where_op,
                      within_op)
 
 _LOG = logging.getLogger(__name__)
@@ -509,6 +509,25 @@ def _clustered(clustered, doc_of: Dict[int, int], n_clusters: int) -> Dict[str, 
             "centroids": np.asarray(clustered[4], dtype=np.float32), "iterations": int(clustered[5])}
 
 
+_COMBINED_MODES = {"any": "max", "all": "min", "sum": "sum"}
+
+
+def _combined_args(queries: List[str], mode: str, weights) -> Tuple[List[str], str, Optional[np.ndarray]]:
+    """(query strings, the index's op, weights f32 (m,) or None) of a combined retrieval; ValueError for no query or more
+    than 8, an unknown mode, and weights that are not one finite number per query."""
+    queries = list(queries)
+    if not 1 <= len(queries) <= COMBINE_MAX_VECTORS:
+        raise ValueError(f"a combined retrieval takes 1 .. {COMBINE_MAX_VECTORS} queries, got {len(queries)}")
+    if mode not in _COMBINED_MODES:
+        raise ValueError(f"mode must be one of {sorted(_COMBINED_MODES)}, got {mode!r}")
+    w = None
+    if weights is not None:
+        w = np.asarray(weights, dtype=np.float32)
+        if w.shape != (len(queries),) or not np.isfinite(w).all():
+            raise ValueError(f"weights must be {len(queries)} finite numbers, one per query")
+    return queries, _COMBINED_MODES[mode], w
+
+
 def _diverse_args(n: int, fetch_n: Optional[int], diversity: float) -> Tuple[int, float]:
     """(candidates to fetch, lambda_mult = 1 - diversity) of a diverse retrieval; ValueError for a diversity outside
     [0, 1] or NaN, more than 1024 results or candidates, or fewer candidates than results."""
@@ -834,6 +853,27 @@ class KB:
         _LOG.info(f"computed {self.embeddings_matrix.index.shape[0]} cosine similarities")
         with self.db.transaction():
             res = _fetch_diverse(self.db, picks)
+        _LOG.info(f"retrieved top {n} documents")
+        return res
+
+    def retrieve_combined(self, queries: List[str], n: int, mode: str = "any", weights=None) -> List[Dict[str, Any]]:
+        """``retrieve`` against several query strings at once -- the rewordings of one question, the facets of a request,
+        liked and disliked examples: the 1 .. 8 ``queries`` are embedded in one call and every document is ranked on the
+        device (svs_index_search_combined) by its best score against any of them (``mode="any"``), by its worst (``"all"``:
+        relevant to every one), or by the weighted sum of its scores (``"sum"``; negative ``weights`` push away).
+        ``weights``: one finite number per query, or None for 1.  One pass over the corpus; results shaped like
+        ``retrieve``, and ``retrieve_combined([q], n)`` is ``retrieve(q, n)``.  ValueError for no query or more than 8,
+        an unknown mode, and bad weights."""
+        queries, op, w = _combined_args(queries, mode, weights)
+        _LOG.info(f"retrieving {n} documents with {len(queries)} query strings: {queries}")
+        assert self.db is not None
+        self.embeddings_matrix.get_sync(self.db)
+        query_vecs = np.array(self._embed(queries), dtype=np.float32)
+        _LOG.info("got embeddings for the queries!")
+        emb_ids = self.embeddings_matrix.search_combined(query_vecs, n, op, w)   # one pass + selection: HIP
+        _LOG.info(f"computed {self.embeddings_matrix.index.shape[0]} x {len(queries)} cosine similarities")
+        with self.db.transaction():
+            res = _fetch_list(self.db, emb_ids)
         _LOG.info(f"retrieved top {n} documents")
         return res
 
@@ -1246,6 +1286,20 @@ class AsyncKB:
             picks = await self._search(held, diverse_op(query_vec, n, fetch_k, lam))
             _LOG.info(f"computed {held[0].shape[0]} cosine similarities")
         res = await self._fetch(lambda db: _fetch_diverse(db, picks))
+        _LOG.info(f"retrieved top {n} documents")
+        return res
+
+    async def retrieve_combined(self, queries: List[str], n: int, mode: str = "any", weights=None) -> List[Dict[str, Any]]:
+        """Async twin of ``KB.retrieve_combined``, structured as ``retrieve``: the reference to the matrix under the
+        lock, the one embedding call and the combined search on an executor thread outside it, the docs under the lock."""
+        queries, op, w = _combined_args(queries, mode, weights)
+        _LOG.info(f"retrieving {n} documents with {len(queries)} query strings: {queries}")
+        async with self._held() as (held, _):
+            query_vecs = np.array(await self._embed(queries), dtype=np.float32)
+            _LOG.info("got embeddings for the queries!")
+            emb_ids = await self._search(held, combined_op(query_vecs, n, op, w))
+            _LOG.info(f"computed {held[0].shape[0]} x {len(queries)} cosine similarities")
+        res = await self._fetch(lambda db: _fetch_list(db, emb_ids))
         _LOG.info(f"retrieved top {n} documents")
         return res
 

@@ -247,6 +247,20 @@ def diverse_op(query_vec: np.ndarray, n: int, fetch_k: Optional[int] = None, lam
     return native, finish
 
 
+def combined_op(vectors: np.ndarray, n: int, op: str = "max", weights=None):
+    """Combined search: ``idx.search_combined`` (svs_index_search_combined) of the (m, D) ``vectors``, rows -> ids:
+    [(score, emb_id)]."""
+    def native(idx, lookup, *_):
+        return idx, idx.search_combined(vectors, n, op, weights)
+
+    def finish(res, arr):
+        used, rows = res
+        off = int(getattr(used, "row_offset", 0))
+        return [(score, int(arr[row - off])) for score, row in rows]
+
+    return native, finish
+
+
 def assign_op(vectors: np.ndarray):
     """Nearest-vector assignment of every LIVE stored embedding: ``idx.assign`` (svs_index_assign) over the whole index
     without touching the label column, rows -> ids: (emb_ids i64 (m,), best i32 (m,), scores f32 (m,), counts i64 (c,))
@@ -632,6 +646,11 @@ class DeviceEmbeddingsMatrix:
         """``search`` re-ranked for diversity (MMR over the ``fetch_k`` best, on the device):
         [(score, emb_id, redundancy)] in pick order (``KB.retrieve_diverse``)."""
         return self.run_mapped(diverse_op(query_vec, n, fetch_k, lam))
+
+    def search_combined(self, vectors: np.ndarray, n: int, op: str = "max", weights=None) -> List[Tuple[float, int]]:
+        """``search`` ranked against several vectors at once (``DeviceIndex.search_combined``: the "max", "min" or weighted
+        "sum" of a row's scores against the (m, D) ``vectors``): [(score, emb_id)] (``KB.retrieve_combined``)."""
+        return self.run_mapped(combined_op(vectors, n, op, weights))
 
     def assign(self, vectors: np.ndarray) -> Tuple[np.ndarray, np.ndarray, np.ndarray, np.ndarray]:
         """For every LIVE stored embedding, in row order, the row of ``vectors`` (c, D) it scores best against:

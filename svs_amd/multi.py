@@ -222,6 +222,11 @@ class MultiDeviceIndex:
     def set_labels(self, labels, row0: Optional[int] = None):
         raise NotImplementedError("labels are per device: call set_labels on a DeviceIndex")
 
+    def search_combined(self, vectors: np.ndarray, n: int, op: str = "max", weights=None):
+        raise NotImplementedError("combined search is per device: a shard answers over its own rows (DeviceIndex.search_combined); nothing is merged across shards")
+
+    search_batch_combined = search_combined
+
     def search_where(self, query_vec: np.ndarray, n: int, where):
         raise NotImplementedError("predicate search is per device: the columns sit beside one shard's rows; call set_column / search_where on a DeviceIndex")
 
