@@ -402,7 +402,7 @@ int32_t svs_index_search_labeled(svs_index* idx, const float* queries, int32_t n
  * copies; never goes through the coalescer, the run-ahead pipelines or shared passes.
  * Out of scope: svs_multi / row-sharded corpora, a device-pointer variant, OR across terms, per-query predicates in
  * one call, 64-bit or float columns, more than four columns or terms, routing broad predicates through a full-corpus
- * pass, columns on the attach path, grouping by a column. */
+ * pass, columns on the attach path. */
 #define SVS_COLUMNS_MAX 4          /* column 0 IS the label column of svs_index_set_labels */
 #define SVS_WHERE_MAX_TERMS 4
 typedef enum svs_where_op { SVS_WHERE_IN = 0, SVS_WHERE_RANGE = 1, SVS_WHERE_ANY_BITS = 2, SVS_WHERE_ALL_BITS = 3 } svs_where_op;
@@ -530,15 +530,61 @@ int32_t svs_index_search_combined(svs_index* idx, const float* vectors /* host, 
  * the at most SVS_LABELS_MAX_SET groups.  The host waits once per call.
  * Blocking; re-entrant on one handle; holds a reference and the geometry lock shared; waits for pending staging
  * copies; never goes through the coalescer, the run-ahead pipelines or shared passes: all as svs_index_search_above.
- * Out of scope: svs_multi / row-sharded corpora, a device-pointer variant, more than one row per label, groups that
- * are not a caller-given set (one group per parent document needs a second column), the batched GEMM and the
- * screened score routes. */
+ * Out of scope: svs_multi / row-sharded corpora, a device-pointer variant, more than one row per label, the batched
+ * GEMM and the screened score routes.  (Groups that are not a caller-given set -- one group per parent document --
+ * are svs_index_search_collapsed below.) */
 int32_t svs_index_search_by_label(svs_index* idx, const float* queries, int32_t nq, int32_t d,
                                   const uint32_t* labels, int32_t nlabels,
                                   const float* min_scores /* nq, or NULL: -inf for every query */, int32_t k,
                                   uint32_t* out_labels, float* out_scores, int64_t* out_rows,
                                   int64_t* out_totals /* all four: stride k */,
                                   int32_t* out_counts /* nq */, int32_t* out_groups /* nq, or NULL */);
+
+/* Collapsed search: the top k rows with at most ONE row per value of a column -- "the 10 best parent documents, each
+ * represented by its best chunk" (other vector stores: collapse, group_by) -- in one corpus pass per query, whatever
+ * the number of distinct values: a corpus has as many parents as it has documents, and none of them is named in the call.
+ * Exact definition.  For query q of the call let s be the vector svs_index_scores_n(idx, query q) returns at that
+ * moment (the unscreened single-query score kernel of the index's dtype, the one svs_index_search_above uses), L the
+ * live (not tombstoned) local rows and v[r] = column[column][r] (a column never set reads 0 everywhere).  Row r's group
+ * is v[r]; under SVS_COLLAPSE_ZERO_SINGLE a row with v[r] == 0 is a group of its own ("no parent" never collapses),
+ * under SVS_COLLAPSE_ZERO_IS_GROUP 0 is a value like any other.
+ *   best(G) = max over r in G and L of make_key(s[r], r)     (svs_amd/csrc/keys.h)
+ *   W       = { r : r is the best of its group }             (a group with no live row has none)
+ * The maximum is taken in KEY space, the space the order is defined in: -0.0 folds onto +0.0, a NaN score is the
+ * largest, a score tie goes to the larger row, as everywhere.  Tombstoned rows are excluded by the dead-row bitmap,
+ * never by their score.
+ *   out_groups[q]   = |W|, always exact; may be NULL
+ *   out_counts[q]   = min(max(k, 0), |W|)
+ *   out_*[q*k + t], t < out_counts[q]   the rows of W in descending key, that is (score desc, row desc): out_scores =
+ *                     the score bits of s (a NaN comes back as the quiet NaN 0x7fc00000, as from every search),
+ *                     out_rows = row_offset + r, out_values = v[r].  Entries past the count are not touched.
+ * A query's result does not depend on nq, on the other queries of the call, or on how the device schedules the work:
+ * it is maxima of unique integer keys and an integer count.  Two identities: a column never set gives, under
+ * ZERO_SINGLE, the plain top-k over s with the tombstoned rows masked (rows and score bits), and under ZERO_IS_GROUP
+ * one hit, the best live row.
+ * Errors: everything is validated before anything is launched, and a failing call writes no output.  d != index d or
+ * an empty index -> SVS_ERR_SHAPE.  SVS_ERR_INVALID: nq < 0, a column outside [0, SVS_COLUMNS_MAX), an unknown
+ * zero_mode, null queries with nq > 0, null out_counts, null out_scores / out_rows / out_values with k > 0 and nq > 0.
+ * k <= 0 is a COUNT-ONLY call: the groups are counted, every count is 0, the three result pointers may be NULL.
+ * nq == 0 -> SVS_OK, nothing launched.
+ * Each query costs one single-query corpus pass, two passes over the score vector, the column and the bitmap (8 bytes
+ * per row each: one finds every group's best key in an open-addressing table in HBM with 64-bit integer compare-and-
+ * swap and max -- no float atomics, nothing waits or spins --, one strikes every row that is not its group's best to
+ * -inf and counts the rest), a fill that empties the table, the top-k stage with k' = min(k, live rows) over the
+ * rewritten vector, and one tiny launch for the values; after the call's one wait the host trims each query to
+ * min(k, |W|).  Every row of W sorts above every struck row.  (A LIVE best row whose score is -inf itself ties with
+ * the struck rows; finite rows and queries never produce one.)  The table belongs to the search context: 16 bytes per
+ * slot, a power of two >= 2 x rows slots -- 32 to 64 MB per million rows and per context that ran a collapsed search.
+ * Blocking; re-entrant on one handle; holds a reference and the geometry lock shared; waits for pending staging
+ * copies; never goes through the coalescer, the run-ahead pipelines or shared passes: all as svs_index_search_above.
+ * Out of scope: more than one row per group or a per-group row count, collapsing under a predicate
+ * (svs_index_search_where) or over a row list, grouping by two columns, svs_multi / row-sharded corpora, a
+ * device-pointer variant, the batched GEMM and the screened score routes, routing through shared passes. */
+enum { SVS_COLLAPSE_ZERO_IS_GROUP = 0, SVS_COLLAPSE_ZERO_SINGLE = 1 };
+int32_t svs_index_search_collapsed(svs_index* idx, const float* queries, int32_t nq, int32_t d, int32_t k,
+                                   int32_t column, int32_t zero_mode,
+                                   float* out_scores, int64_t* out_rows, uint32_t* out_values /* all three: stride k */,
+                                   int32_t* out_counts /* nq */, int64_t* out_groups /* nq, or NULL */);
 
 /* Nearest-vector assignment: for every stored row of a range, which of c given vectors it scores best against -- the
  * transposed question of a search ("which topic is each document about", the assignment step of a clustering, coarse

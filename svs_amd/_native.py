@@ -44,6 +44,9 @@ WHERE_MAX_TERMS = 4      # SVS_WHERE_MAX_TERMS
 WHERE_IN, WHERE_RANGE, WHERE_ANY_BITS, WHERE_ALL_BITS = 0, 1, 2, 3   # svs_where_op
 
 
+COLLAPSE_ZERO_IS_GROUP, COLLAPSE_ZERO_SINGLE = 0, 1   # svs_index_search_collapsed's zero modes
+
+
 COMBINE_MAX_VECTORS = 8   # SVS_COMBINE_MAX_VECTORS
 COMBINE_MAX, COMBINE_MIN, COMBINE_SUM = 0, 1, 2   # svs_index_search_combined's ops
 
@@ -118,6 +121,7 @@ SIGNATURES = {
     "svs_index_search_above": (C.c_int32, [_P, _P, C.c_int32, C.c_int32, _P, C.c_int32, _P, _P, _P, _P]),
     "svs_index_search_combined": (C.c_int32, [_P, _P, C.c_int32, C.c_int32, C.c_int32, _P, C.c_int32, C.c_int32, _P, _P, C.POINTER(C.c_int32)]),
     "svs_index_search_by_label": (C.c_int32, [_P, _P, C.c_int32, C.c_int32, _P, C.c_int32, _P, C.c_int32, _P, _P, _P, _P, _P, _P]),
+    "svs_index_search_collapsed": (C.c_int32, [_P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P, _P, _P]),
     "svs_index_assign": (C.c_int32, [_P, _P, C.c_int32, C.c_int32, C.c_int64, C.c_int64, _P, _P, _P, _P]),
     "svs_index_label_sums": (C.c_int32, [_P, _P, C.c_int32, C.c_int64, C.c_int64, _P, _P, _P]),
     "svs_index_search_diverse": (C.c_int32, [_P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_float, _P, _P, _P,
@@ -154,6 +158,8 @@ INTERNAL = {
     "svs_internal_live_rows": (C.c_int64, [_P, C.c_int64, C.c_int64, C.c_int64, _P, _P, C.c_int64]),
     "svs_internal_labels_strip": (C.c_int32, []),
     "svs_internal_by_label_geometry": (C.c_int32, [C.POINTER(C.c_int32)]),
+    "svs_internal_collapse_geometry": (C.c_int32, [C.POINTER(C.c_int32)]),
+    "svs_internal_collapse_kernel_ms": (C.c_int32, [C.POINTER(C.c_double)]),
     "svs_internal_assign_kernel_ms": (C.c_int32, [C.POINTER(C.c_double)]),
     "svs_internal_label_sums_kernel_ms": (C.c_int32, [C.POINTER(C.c_double)]),
     "svs_internal_combined_scores": (C.c_int32, [_P, _P, C.c_int32, C.c_int32, _P, C.c_int32, C.c_int32, _P, C.c_int64]),

@@ -136,6 +136,15 @@ int32_t svs_internal_labels_strip(void);
  * workgroups of a launch (BL_GRID_MAX); an index of more than out[0] * out[1] rows gives a workgroup several strips
  * (tests). */
 int32_t svs_internal_by_label_geometry(int32_t* out);
+/* svs_index_search_collapsed's reduce and mark kernels (collapse.h): out[0] = rows per strip (CL_STRIP), out[1] = the
+ * most workgroups of a launch (CL_GRID_MAX); an index of more than out[0] * out[1] rows gives a workgroup several
+ * strips (tests). */
+int32_t svs_internal_collapse_geometry(int32_t* out);
+/* Milliseconds between the HIP events around the stages of the LAST query of the calling thread's last
+ * svs_index_search_collapsed, recorded while svs_index_set_timing is on for the handle: out[0] collapse_reduce_kernel,
+ * out[1] collapse_mark_kernel, out[2] the table's fill, out[3] the top-k stage; -1 where that call recorded none
+ * (tools/collapse_time.py). */
+int32_t svs_internal_collapse_kernel_ms(double* out);
 /* Milliseconds between the HIP events around assign_rows_kernel in the calling thread's last svs_index_assign, recorded
  * while svs_index_set_timing is on for the handle; -1 when that call recorded none (tools/assign_time.py). */
 int32_t svs_internal_assign_kernel_ms(double* out);

@@ -47,6 +47,7 @@
 #include "labels.h"
 #include "where.h"
 #include "by_label.h"
+#include "collapse.h"
 #include "assign.h"
 #include "label_sums.h"
 
@@ -271,6 +272,14 @@ struct Ctx {
   DevBuf<unsigned long long> bl_tab;
   DevBuf<unsigned long long> bl_part_best; DevBuf<uint32_t> bl_part_cnt;
   PinBuf<uint32_t> bl_lab_pin;  PinBuf<int64_t> bl_tot_pin;   PinBuf<int32_t> bl_cnt_pin;
+  // svs_index_search_collapsed (collapse.h): the open-addressing table (CL_SLOT_WORDS words per slot), grown to the row
+  // count, EMPTY (all zero) between queries and between calls -- cl_clean is false from a query's first insert until
+  // the fill behind its mark kernel is enqueued, so a call that left early is repaired by the next one; the queries'
+  // survivor counters and their pinned copy; the values of the returned rows (scores and rows: out_s_pin / out_r_pin).
+  DevBuf<unsigned long long> cl_tab;
+  bool cl_clean = true;
+  DevBuf<unsigned long long> cl_cnt; PinBuf<unsigned long long> cl_cnt_pin;
+  PinBuf<uint32_t> cl_val_pin;
   // svs_index_assign (assign.h): the call's vectors in the index's storage format (rows of ld elements; fp8: their
   // scales), the per-row results and the counts.  The f32 vectors go up through q_pin / q_dev.
   DevBuf<uint8_t> as_vec;       DevBuf<float> as_vec_scales;
@@ -2843,6 +2852,7 @@ int upload_queries(Ctx* c, const float* queries, size_t qn, hipStream_t st) {
 // until that call has timed its kernels (TimedSpan); a call of the other entry never touches it
 thread_local double g_assign_kernel_ms = -1.0;       // svs_internal_assign_kernel_ms
 thread_local double g_label_sums_kernel_ms = -1.0;   // svs_internal_label_sums_kernel_ms
+thread_local double g_collapse_ms[4] = {-1.0, -1.0, -1.0, -1.0};   // svs_internal_collapse_kernel_ms: reduce, mark, clear, select
 int report_ms(double* out, double ms) {
   if (!out) return fail(SVS_ERR_INVALID, "null output");
   *out = ms;
@@ -4059,6 +4069,116 @@ int32_t svs_index_search_by_label(svs_index* idx, const float* queries, int32_t 
   deliver_strided(out_totals, k, c->bl_tot_pin.p, ks, nq, c->bl_cnt_pin.p);
   memcpy(out_counts, c->bl_cnt_pin, (size_t)nq * sizeof(int32_t));
   if (out_groups) memcpy(out_groups, c->bl_cnt_pin + nq, (size_t)nq * sizeof(int32_t));
+  return SVS_OK;
+}
+
+// ---- svs_index_search_collapsed (collapse.h)
+static_assert(SVS_COLLAPSE_ZERO_IS_GROUP == CL_ZERO_IS_GROUP && SVS_COLLAPSE_ZERO_SINGLE == CL_ZERO_SINGLE, "collapse.h's kernels take the header's zero modes");
+
+int32_t svs_internal_collapse_geometry(int32_t* out) {
+  if (!out) return fail(SVS_ERR_INVALID, "null output");
+  out[0] = CL_STRIP;
+  out[1] = CL_GRID_MAX;
+  return SVS_OK;
+}
+
+int32_t svs_internal_collapse_kernel_ms(double* out) {
+  if (!out) return fail(SVS_ERR_INVALID, "null output");
+  for (int i = 0; i < 4; ++i) out[i] = g_collapse_ms[i];
+  return SVS_OK;
+}
+
+int32_t svs_index_search_collapsed(svs_index* idx, const float* queries, int32_t nq, int32_t d, int32_t k, int32_t column, int32_t zero_mode,
+                                   float* out_scores, int64_t* out_rows, uint32_t* out_values, int32_t* out_counts, int64_t* out_groups) {
+  launch_reset();
+  for (double& ms : g_collapse_ms) ms = -1.0;   // (a call that fails or records nothing leaves no earlier call's times behind)
+  if (!idx) return fail(SVS_ERR_INVALID, "null index");
+  RefGuard guard(idx);
+  std::shared_lock<std::shared_mutex> geo(idx->rw);   // (set_column, mask_rows, compact take it exclusively: every query sees one column)
+  // ---- everything is validated before anything is written, allocated or launched
+  int rc = check_query_args(idx, queries, nq, d);
+  if (rc != SVS_OK || (rc = check_column("svs_index_search_collapsed", column)) != SVS_OK) return rc;
+  if (zero_mode != SVS_COLLAPSE_ZERO_IS_GROUP && zero_mode != SVS_COLLAPSE_ZERO_SINGLE)
+    return fail(SVS_ERR_INVALID, "svs_index_search_collapsed: zero_mode %d", (int)zero_mode);
+  if (!out_counts) return fail(SVS_ERR_INVALID, "null out_counts");
+  if (k > 0 && nq > 0 && (!out_scores || !out_rows || !out_values)) return fail(SVS_ERR_INVALID, "null output");
+  if (nq == 0) return SVS_OK;
+  const int64_t n = idx->n;
+  const int64_t live = n - (int64_t)idx->dead_list.size();
+  const int ks = (int)std::min<int64_t>(std::max(k, 0), live);   // entries a query can have: what the top-k stage is asked for
+  const int bits = collapse_table_bits(n);
+  const size_t tab_words = ((size_t)1 << bits) * CL_SLOT_WORDS;
+  const unsigned blocks = (unsigned)std::min<int64_t>((n + CL_STRIP - 1) / CL_STRIP, CL_GRID_MAX);
+  HostCall fr(idx);
+  if ((rc = fr.open()) != SVS_OK) return rc;
+  Ctx* const c = fr.c;
+  hipStream_t st = fr.stream();
+  const size_t qn = (size_t)nq * (size_t)d, on = std::max<size_t>((size_t)nq * (size_t)ks, 1);
+  const int64_t sstride = (n + 3) & ~(int64_t)3;
+  if ((rc = c->out_s_pin.grow(on)) != SVS_OK || (rc = c->out_r_pin.grow(on)) != SVS_OK || (rc = c->cl_val_pin.grow(on)) != SVS_OK) return rc;
+  if ((rc = c->cl_cnt.grow((size_t)nq)) != SVS_OK || (rc = c->cl_cnt_pin.grow((size_t)nq)) != SVS_OK) return rc;
+  if ((rc = c->scores.grow((size_t)sstride)) != SVS_OK) return rc;
+  if (ks > 0 && select_path(n, ks) == SelectPath::WINDOW && (rc = grow_select_scratch(c, 1, st)) != SVS_OK) return rc;
+  if (c->cl_tab.cap < tab_words || !c->cl_clean) {   // a fresh table, or one an earlier call left early: all of it goes to empty
+    if ((rc = c->cl_tab.grow(tab_words)) != SVS_OK) return rc;
+    HIP_TRY(hipMemsetAsync(c->cl_tab, 0, c->cl_tab.cap * sizeof(unsigned long long), st));
+    c->cl_clean = true;
+  }
+  HIP_TRY(hipMemsetAsync(c->cl_cnt, 0, (size_t)nq * sizeof(unsigned long long), st));
+  const SingleRoute route = single_route(idx, idx->variant.load(), false);   // the kernel svs_index_scores_n runs
+  if ((rc = upload_queries(c, queries, qn, st)) != SVS_OK) return rc;
+  const CollapseArgs a{idx->cols[column], idx->dead_list.empty() ? nullptr : idx->dead_bits_dev.p, c->cl_tab.p, n, bits,
+                       zero_mode == SVS_COLLAPSE_ZERO_SINGLE ? 1 : 0};
+  const bool timed = idx->timing.load() > 0;
+  const TimedSpan t_reduce(timed), t_mark(timed), t_clear(timed), t_select(timed);
+  // every query back to back: score pass, reduce, mark, the table's fill, selection, values -- the context's one score
+  // vector, one table and selection scratch are reused in stream order; no host wait in between
+  for (int32_t q = 0; q < nq; ++q) {
+    const bool last = q == nq - 1;   // (svs_index_set_timing: spans around the last query's stages)
+    if ((rc = launch_query_scores(idx, c, route, q, st)) != SVS_OK) return rc;
+    c->cl_clean = false;
+    if (last) t_reduce.begin(st);
+    launch_record("collapse_reduce_kernel", n, 1);
+    hipLaunchKernelGGL(collapse_reduce_kernel, dim3(blocks), dim3(CL_THREADS), 0, st, a, (const float*)c->scores.p);
+    if (last) { t_reduce.end(st); t_mark.begin(st); }
+    launch_record("collapse_mark_kernel", n, 1);
+    hipLaunchKernelGGL(collapse_mark_kernel, dim3(blocks), dim3(CL_THREADS), 0, st, a, c->scores.p, c->cl_cnt.p + q);
+    if (last) { t_mark.end(st); t_clear.begin(st); }
+    HIP_TRY(hipMemsetAsync(c->cl_tab, 0, tab_words * sizeof(unsigned long long), st));
+    c->cl_clean = true;
+    if (last) t_clear.end(st);
+    if (ks == 0) continue;
+    if (last) t_select.begin(st);
+    if ((rc = run_select(idx, c, c->scores, n, sstride, 1, ks, ks, c->out_s_pin + (size_t)q * ks, c->out_r_pin + (size_t)q * ks, st,
+                         idx->row_offset)) != SVS_OK)
+      return rc;
+    if (last) t_select.end(st);
+    hipLaunchKernelGGL(collapse_values_kernel, dim3((unsigned)std::min((ks + 255) / 256, 64)), dim3(256), 0, st,
+                       (const int64_t*)(c->out_r_pin + (size_t)q * ks), ks, idx->row_offset, n, (const uint32_t*)idx->cols[column],
+                       c->cl_val_pin + (size_t)q * ks);
+  }
+  rc = read_back(fr, "search_collapsed", {{c->cl_cnt_pin.p, c->cl_cnt.p, (size_t)nq * sizeof(unsigned long long)}});
+  if (rc != SVS_OK) return rc;
+  std::vector<int32_t> counts((size_t)nq);
+  for (int32_t q = 0; q < nq; ++q) {
+    const unsigned long long w = c->cl_cnt_pin[q];
+    if (w > (unsigned long long)live)
+      return fail(SVS_ERR_DEVICE, "search_collapsed: query %d came back with %llu groups of %lld live rows", (int)q, w, (long long)live);
+    counts[(size_t)q] = (int32_t)std::min<unsigned long long>((unsigned long long)ks, w);
+  }
+  if (ks > 0) {
+    deliver_strided(out_scores, k, c->out_s_pin.p, ks, nq, counts.data());
+    deliver_strided(out_rows, k, c->out_r_pin.p, ks, nq, counts.data());
+    deliver_strided(out_values, k, c->cl_val_pin.p, ks, nq, counts.data());
+  }
+  for (int32_t q = 0; q < nq; ++q) {
+    out_counts[q] = counts[(size_t)q];
+    if (out_groups) out_groups[q] = (int64_t)c->cl_cnt_pin[q];
+  }
+  g_collapse_ms[0] = t_reduce.ms();
+  g_collapse_ms[1] = t_mark.ms();
+  g_collapse_ms[2] = t_clear.ms();
+  g_collapse_ms[3] = ks > 0 ? t_select.ms() : -1.0;
   return SVS_OK;
 }
 

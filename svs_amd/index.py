@@ -71,6 +71,17 @@ def column_index(c) -> int:
     return int(c)
 
 
+COLLAPSE_ZERO = {"group": _native.COLLAPSE_ZERO_IS_GROUP, "single": _native.COLLAPSE_ZERO_SINGLE}
+
+
+def collapse_zero_mode(zero) -> int:
+    """``zero`` of a collapsed search -- "single": a row whose value is 0 is a group of its own; "group": 0 is a value
+    like any other -- as svs_index_search_collapsed's zero_mode; ValueError for anything else."""
+    if not isinstance(zero, str) or zero not in COLLAPSE_ZERO:
+        raise ValueError(f"zero must be one of {sorted(COLLAPSE_ZERO)}, got {zero!r}")
+    return COLLAPSE_ZERO[zero]
+
+
 def where_terms(where) -> list:
     """A ``where`` list -- terms ``(column, op, arg)``, all of which must hold -- checked and normalised to
     ``[(column, svs_where_op, negate, a, b, members)]``: ``members`` is the u32 vector of an in / not in term as given
@@ -688,6 +699,48 @@ class DeviceIndex:
             raise ValueError(f"query must be 1-D, got shape {q.shape}")
         l, s, r, t, _ = self.search_batch_by_label(q[None, :], labels, None if min_score is None else [min_score], n)[0]
         return list(zip(l.tolist(), s.astype(np.float64).tolist(), r.tolist(), t.tolist()))
+
+    def search_batch_collapsed(self, queries: np.ndarray, n: int, column: int,
+                               zero: str = "single") -> Tuple[np.ndarray, np.ndarray, np.ndarray, np.ndarray, np.ndarray]:
+        """Collapsed search (svs_index_search_collapsed): for each row of ``queries`` (nq, D) the ``n`` best live rows
+        with at most ONE row per value of column ``column`` -- every value is represented by its best row (score
+        desc, row desc in key space).  ``zero="single"``: a row whose value is 0 ("no parent") stands for itself;
+        ``zero="group"``: 0 is a value like any other.  Returns ``(scores f32 (nq, k), rows i64 (nq, k), values u32
+        (nq, k), counts i32 (nq,), groups i64 (nq,))`` with k = min(max(n, 0), live rows): query i has counts[i] =
+        min(k, groups[i]) valid entries, groups[i] = how many rows are the best of their group; the entries past
+        counts[i] are unspecified.  ``n=0`` only counts the groups."""
+        assert isinstance(n, int)
+        q = self._queries_2d(queries)
+        nq, d = q.shape
+        c = column_index(column)
+        mode = collapse_zero_mode(zero)
+        h = self._pinned_handle()
+        try:
+            # (clamped before allocating and before the int32 argument, as in search_batch)
+            k = min(max(n, 0), self._live_rows(h))
+            scores = np.empty((nq, k), dtype=np.float32)
+            rows = np.empty((nq, k), dtype=np.int64)
+            values = np.empty((nq, k), dtype=np.uint32)
+            counts = np.zeros(nq, dtype=np.int32)
+            groups = np.zeros(nq, dtype=np.int64)
+            # (the one call that releases the GIL; a count-only call passes no result buffers)
+            _native.check(self._lib.svs_index_search_collapsed(h, q.ctypes.data, nq, d, k, c, mode,
+                                                               scores.ctypes.data if k else None, rows.ctypes.data if k else None,
+                                                               values.ctypes.data if k else None, counts.ctypes.data, groups.ctypes.data))
+        finally:
+            self._unpin(h)
+        return scores, rows, values, counts, groups
+
+    def search_collapsed(self, query_vec: np.ndarray, n: int, column: int, zero: str = "single") -> Tuple[List[Tuple[float, int, int]], int]:
+        """The ``n`` best rows of one query with at most one row per value of column ``column``: ([(score, row,
+        value)], groups), best first.  See ``search_batch_collapsed``."""
+        assert isinstance(n, int)
+        q = np.asarray(query_vec, dtype=np.float32)
+        if q.ndim != 1:
+            raise ValueError(f"query must be 1-D, got shape {q.shape}")
+        s, r, v, counts, groups = self.search_batch_collapsed(q[None, :], n, column, zero)
+        c = int(counts[0])
+        return list(zip(s[0, :c].astype(np.float64).tolist(), r[0, :c].tolist(), v[0, :c].tolist())), int(groups[0])
 
     def assign(self, vectors, labels=None, row0: Optional[int] = None, nrows: Optional[int] = None,
                scores: bool = True) -> Tuple[np.ndarray, Optional[np.ndarray], np.ndarray]:

@@ -30,7 +30,7 @@ from typing import Any, Awaitable, Callable, Dict, Iterator, List, Optional, Tup
 import numpy as np
 
 from .index import ASSIGN_MAX_VECTORS, COMBINE_MAX_VECTORS, LABELS_MAX_SET, DeviceIndex
-from .matrix import (DeviceEmbeddingsMatrix, above_op, assign_op, batch_op, by_label_op, cluster_op, combined_op, diverse_op, labeled_op, neighbors_op, pairs_op, segments_op, single_op, where_op,
+from .matrix import (DeviceEmbeddingsMatrix, above_op, assign_op, batch_op, by_label_op, cluster_op, collapsed_op, combined_op, diverse_op, labeled_op, neighbors_op, pairs_op, segments_op, single_op, where_op,
                      within_op)
 
 _LOG = logging.getLogger(__name__)
@@ -762,6 +762,31 @@ class KB:
         _LOG.info(f"retrieved top {n} documents")
         return res
 
+    def retrieve_collapsed(self, query: str, n: int) -> List[Dict[str, Any]]:
+        """``retrieve`` with at most ONE document per parent: the n best documents after every parent's children are
+        represented by the best of them -- "the 10 best sections, one per chapter" -- same log lines and result shape.
+        A document without a parent stands for itself.  ``parent_id + 1`` sits next to each vector in HBM in column
+        ``PARENT_COLUMN`` (0 = no parent), the column ``retrieve_under`` installs and maintains, and the grouping runs
+        on the device in the query's one corpus pass (svs_index_search_collapsed): no over-fetching, and a parent that
+        holds the best 500 documents still yields one."""
+        _LOG.info(f"retrieving {n} documents with query string: {query}")
+        assert self.db is not None
+        self.embeddings_matrix.get_sync(self.db)
+
+        def parents_from_store():
+            with self.db.transaction():
+                return self.db.embedding_parents()
+
+        self.embeddings_matrix.ensure_column(PARENT_COLUMN, parents_from_store)
+        query_vec = np.array(self._embed([query])[0], dtype=np.float32)
+        _LOG.info("got embedding for query!")
+        hits, _ = self.embeddings_matrix.search_collapsed(query_vec, n, PARENT_COLUMN, "single")   # one pass + grouping: HIP
+        _LOG.info(f"computed {self.embeddings_matrix.index.shape[0]} cosine similarities")
+        with self.db.transaction():
+            res = _fetch_list(self.db, [(score, emb_id) for score, emb_id, _ in hits])
+        _LOG.info(f"retrieved top {n} documents")
+        return res
+
     def retrieve_by_level(self, query: str, min_score: Optional[float] = None, levels=None) -> List[Dict[str, Any]]:
         """The breakdown of one query over the levels of the tree: for every level that has a document scoring at or
         above ``min_score`` (None: any document) the best such document and how many there are --
@@ -1219,6 +1244,20 @@ class AsyncKB:
             emb_ids, matched = await self._search(held, where_op(query_vec, n, where))
             _LOG.info(f"computed {matched} cosine similarities")
         res = await self._fetch(lambda db: _fetch_list(db, emb_ids))
+        _LOG.info(f"retrieved top {n} documents")
+        return res
+
+    async def retrieve_collapsed(self, query: str, n: int) -> List[Dict[str, Any]]:
+        """Async twin of ``KB.retrieve_collapsed``, structured as ``retrieve_under``: the parent column is installed
+        (when this index generation lacks it) and the reference to the matrix is taken under the lock, the collapsed
+        search runs on an executor thread outside it, the docs are fetched under the lock."""
+        _LOG.info(f"retrieving {n} documents with query string: {query}")
+        async with self._held(lambda db: self.embeddings_matrix.ensure_column(PARENT_COLUMN, db.embedding_parents)) as (held, _):
+            query_vec = np.array((await self._embed([query]))[0], dtype=np.float32)
+            _LOG.info("got embedding for query!")
+            hits, _ = await self._search(held, collapsed_op(query_vec, n, PARENT_COLUMN, "single"))
+            _LOG.info(f"computed {held[0].shape[0]} cosine similarities")
+        res = await self._fetch(lambda db: _fetch_list(db, [(score, emb_id) for score, emb_id, _ in hits]))
         _LOG.info(f"retrieved top {n} documents")
         return res
 

@@ -233,6 +233,21 @@ def by_label_op(query_vec: np.ndarray, labels, min_score: Optional[float] = None
     return native, finish
 
 
+def collapsed_op(query_vec: np.ndarray, n: int, column: int, zero: str = "single"):
+    """Collapsed search: ``idx.search_collapsed`` (svs_index_search_collapsed), at most one row per value of column
+    ``column``, rows -> ids: ([(score, emb_id, value)], groups), best first.  The column is whatever the index holds
+    (``DeviceEmbeddingsMatrix.ensure_column``)."""
+    def native(idx, lookup, *_):
+        return idx, idx.search_collapsed(query_vec, n, column, zero)
+
+    def finish(res, arr):
+        used, (rows, groups) = res
+        off = int(getattr(used, "row_offset", 0))
+        return [(score, int(arr[row - off]), int(value)) for score, row, value in rows], int(groups)
+
+    return native, finish
+
+
 def diverse_op(query_vec: np.ndarray, n: int, fetch_k: Optional[int] = None, lam: float = 0.5):
     """Diverse (MMR) search: ``idx.search_diverse`` (svs_index_search_diverse), rows -> ids:
     [(score, emb_id, redundancy)] in pick order."""
@@ -640,6 +655,13 @@ class DeviceEmbeddingsMatrix:
         of the label score at or above ``min_score``)], best label first (``KB.retrieve_by_level``).  Call
         ``ensure_labels`` first."""
         return self.run_mapped(by_label_op(query_vec, labels, min_score, n))
+
+    def search_collapsed(self, query_vec: np.ndarray, n: int, column: int,
+                         zero: str = "single") -> Tuple[List[Tuple[float, int, int]], int]:
+        """``search`` with at most one stored embedding per value of column ``column``, every value represented by its
+        best one: ([(score, emb_id, value)], how many values -- and, with ``zero="single"``, value-0 embeddings -- have
+        a live embedding) (``KB.retrieve_collapsed``).  Call ``ensure_column`` for the column first."""
+        return self.run_mapped(collapsed_op(query_vec, n, column, zero))
 
     def search_diverse(self, query_vec: np.ndarray, n: int, fetch_k: Optional[int] = None,
                        lam: float = 0.5) -> List[Tuple[float, int, float]]:

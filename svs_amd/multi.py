@@ -219,6 +219,11 @@ class MultiDeviceIndex:
 
     search_batch_by_label = search_by_label
 
+    def search_collapsed(self, query_vec: np.ndarray, n: int, column: int, zero: str = "single"):
+        raise NotImplementedError("collapsed search is per device: the columns sit beside one shard's rows and a value's rows may lie on several; call set_column / search_collapsed on a DeviceIndex")
+
+    search_batch_collapsed = search_collapsed
+
     def set_labels(self, labels, row0: Optional[int] = None):
         raise NotImplementedError("labels are per device: call set_labels on a DeviceIndex")
 

@@ -215,6 +215,11 @@ class ShardedIndex:
 
     search_batch_by_label = search_by_label
 
+    def search_collapsed(self, query_vec: np.ndarray, n: int, column: int, zero: str = "single"):
+        raise NotImplementedError("collapsed search is per device: a rank fills and searches the columns of its own shard (DeviceIndex.search_collapsed); groups are not merged across ranks")
+
+    search_batch_collapsed = search_collapsed
+
     def search_combined(self, vectors: np.ndarray, n: int, op: str = "max", weights=None):
         raise NotImplementedError("combined search is per device: a shard answers over its own rows (DeviceIndex.search_combined); nothing is merged across shards")
 
