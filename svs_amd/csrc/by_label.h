@@ -13,7 +13,7 @@
 //      a bitmap word, every load requested before the first is used.  A qualifying row's label is searched in the
 //      set's LDS image (label_stage_set, label_slot): its SLOT is its index in the sorted set.  Each workgroup keeps a private table in LDS -- a u32 count and a u64 best key per
 //      slot, 12 KiB at 1,024 labels -- updated with LDS atomics (add, max).  Before that the wave aggregates the slot
-//      of its first hit: the lanes that share it become ONE add and ONE max (one label holding every row: 2 LDS
+//      of its first hit (wave_fold_top): the lanes that share it become ONE add and ONE max (one label holding every row: 2 LDS
 //      atomics per wave and element instead of 128 on one address); the other lanes update on their own.
 //      What crosses workgroups:
 //        BL_ATOMIC    the non-empty slots go to the query's table in HBM with integer atomicAdd (u64) / atomicMax (u64);
@@ -31,6 +31,7 @@
 
 #include "keys.h"
 #include "labels.h"
+#include "scored_strip.h"
 
 namespace svs {
 
@@ -44,24 +45,16 @@ constexpr int BL_TAB_WORDS = 2 * LB_MAX_SET;            // the query's table in 
 static_assert(BL_THREADS == LB_THREADS, "label_stage_set strides by LB_THREADS");
 static_assert(BL_STRIP % 32 == 0, "strips begin at whole bitmap words");
 
-// Every lane of the wave calls this (converged): slot < 0 = no hit; key32 = the hit's score key, row = its row.  Rows
-// ascend with the lane, so among the lanes that share the largest key32 the HIGHEST lane holds the largest 64-bit key.
+// Every lane of the wave calls this (converged): slot < 0 = no hit; key32 = the hit's score key, row = its row.
 __device__ __forceinline__ void by_label_update(int slot, uint32_t key32, uint32_t row, unsigned long long* s_best, uint32_t* s_cnt) {
   const unsigned long long hit = __ballot(slot >= 0);
   if (!hit) return;   // (wave-uniform)
-  const int lane = threadIdx.x & 63;
   const int lead = __shfl(slot, __ffsll((long long)hit) - 1, 64);
   const bool peer = slot == lead;
-  const unsigned long long peers = __ballot(peer);
+  bool top;
+  const unsigned long long peers = wave_fold_top(peer, key32, &top);
   if (peers & (peers - 1)) {   // two lanes or more on the leader's slot: one add, one max
-    uint32_t mx = peer ? key32 : 0u;   // (a real key is never 0)
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-      const uint32_t t = (uint32_t)__shfl_xor((int)mx, off, 64);
-      mx = t > mx ? t : mx;
-    }
-    const unsigned long long top = __ballot(peer && key32 == mx);
-    if (lane == 63 - __clzll((long long)top)) {
+    if (top) {
       atomicAdd(&s_cnt[lead], (uint32_t)__popcll(peers));
       atomicMax(&s_best[lead], ((unsigned long long)key32 << 32) | row);
     }
@@ -90,6 +83,8 @@ __global__ __launch_bounds__(BL_THREADS) void by_label_reduce_kernel(LabelFilter
   }
   label_stage_set(f, s_set);
   __syncthreads();
+  // (The strip's loads are spelled out here, not taken from scored_strip.h's ScoredStrip as collapse.h's are: with it
+  //  the kernel came out one VGPR larger and, with every row qualifying on f16, 0.5 % slower per call over six runs.)
   const float4* s4 = (const float4*)scores;
   const uint4* l4 = (const uint4*)f.labels;
   const int64_t n4 = (f.n + 3) >> 2;   // both allocations are padded to a multiple of 4

@@ -9,15 +9,15 @@
 // lands in the table.  Tombstoned rows leave through the dead-row BITMAP.
 //
 // Behind the unchanged single-query score pass, on the context's stream:
-//   1. collapse_reduce_kernel: workgroups stride over strips of CL_STRIP rows.  A thread takes CL_VPT groups of four
-//      consecutive rows per strip: a 16-byte load of the four scores, one of their four values and one nibble of a
-//      bitmap word, every load requested before the first is used.  Every live row (but a value-0 row under
+//   1. collapse_reduce_kernel: workgroups stride over strips of CL_STRIP rows; a thread's part of a strip is a
+//      ScoredStrip<CL_THREADS, CL_VPT> (scored_strip.h: scores, values and tombstone bits of CL_VPT groups of four
+//      consecutive rows, every load requested before the first is used).  Every live row (but a value-0 row under
 //      ZERO_SINGLE) finds or claims its value's slot -- tag word 1 << 32 | v, 0 = empty, claimed with a 64-bit
 //      atomicCAS, linear probing from a multiplicative hash -- and does a 64-bit atomicMax on the slot's best key.
 //      Every probe either finishes or moves one slot on: no lane waits for another, nothing spins, no float atomics.
 //      The capacity is a power of two >= 2 x rows, so at least half the slots stay empty and every probe sequence ends.
 //      Rows of one parent usually lie next to each other: a thread first folds the equal values among its four rows,
-//      then the wave folds the lanes that share its first candidate's value (by_label_update's pattern) into ONE insert;
+//      then the wave folds the lanes that share its first candidate's value (wave_fold_top, shared with by_label.h) into ONE insert;
 //      and an insert reads the slot's best key first and leaves the atomic out when it cannot raise it.
 //   2. collapse_mark_kernel: the same stride.  A row keeps its score iff it is live and either exempt (value 0 under
 //      ZERO_SINGLE) or its own key IS its group's best; every other row, the dead ones included, becomes -inf.  The
@@ -31,6 +31,7 @@
 
 #include "dead_bits.h"
 #include "keys.h"
+#include "scored_strip.h"
 
 namespace svs {
 
@@ -104,60 +105,35 @@ __device__ __forceinline__ unsigned long long collapse_lookup(const unsigned lon
   return 0ull;
 }
 
-// Every lane of the wave calls this (converged): has = the lane holds a candidate (value v, key).  Rows ascend with the
-// lane, so among the lanes that share the largest score key the HIGHEST lane holds the largest 64-bit key.  The lanes
+// Every lane of the wave calls this (converged): has = the lane holds a candidate (value v, key).  The lanes
 // that share the first candidate's value become one insert; the other candidates go in on their own.
 __device__ __forceinline__ void collapse_update(unsigned long long* tab, int bits, bool has, uint32_t v, unsigned long long key) {
   const unsigned long long hit = __ballot(has);
   if (!hit) return;   // (wave-uniform)
-  const int lane = threadIdx.x & 63;
   const uint32_t lead = (uint32_t)__shfl((int)v, __ffsll((long long)hit) - 1, 64);
   const bool peer = has && v == lead;
-  const unsigned long long peers = __ballot(peer);
-  if (peers & (peers - 1)) {   // two lanes or more on the leader's value
-    const uint32_t key32 = (uint32_t)(key >> 32);
-    uint32_t mx = peer ? key32 : 0u;   // (a real key is never 0)
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-      const uint32_t t = (uint32_t)__shfl_xor((int)mx, off, 64);
-      mx = t > mx ? t : mx;
-    }
-    const unsigned long long top = __ballot(peer && key32 == mx);
-    if (peer && lane != 63 - __clzll((long long)top)) has = false;
-  }
+  bool top;
+  (void)wave_fold_top(peer, (uint32_t)(key >> 32), &top);
+  if (peer && !top) has = false;
   if (has) collapse_insert(tab, bits, v, key);
 }
 
 // grid = min(strips, CL_GRID_MAX) workgroups; the table is empty on entry
 __global__ __launch_bounds__(CL_THREADS) void collapse_reduce_kernel(CollapseArgs a, const float* __restrict__ scores) {
-  const float4* s4 = (const float4*)scores;
-  const uint4* v4 = (const uint4*)a.values;
-  const int64_t n4 = (a.n + 3) >> 2;   // both allocations are padded to a multiple of 4
-  const int64_t strips = (a.n + CL_STRIP - 1) / CL_STRIP;
+  using Strip = ScoredStrip<CL_THREADS, CL_VPT>;
+  const int64_t strips = Strip::strips(a.n);
   for (int64_t strip = blockIdx.x; strip < strips; strip += gridDim.x) {   // (the trip count is the workgroup's: waves stay converged)
-    const int64_t base = strip * (CL_STRIP / 4) + threadIdx.x;
-    float4 sc4[CL_VPT];
-    uint4 val4[CL_VPT];
-    uint32_t dead[CL_VPT];
-#pragma unroll
-    for (int j = 0; j < CL_VPT; ++j) {   // all requested before the first is used
-      const int64_t i4 = base + (int64_t)j * CL_THREADS;
-      const bool in = i4 < n4;
-      sc4[j] = in ? s4[i4] : make_float4(0.f, 0.f, 0.f, 0.f);
-      val4[j] = (v4 && in) ? v4[i4] : make_uint4(0u, 0u, 0u, 0u);
-      dead[j] = dead_nibble(in ? a.dead_bits : nullptr, i4);
-    }
+    const Strip s(scores, a.values, a.dead_bits, a.n, strip);
 #pragma unroll
     for (int j = 0; j < CL_VPT; ++j) {
-      const int64_t i = (base + (int64_t)j * CL_THREADS) * 4;
-      const float sc[4] = {sc4[j].x, sc4[j].y, sc4[j].z, sc4[j].w};
-      const uint32_t vv[4] = {val4[j].x, val4[j].y, val4[j].z, val4[j].w};
+      uint32_t vv[4];
       bool has[4];
       unsigned long long key[4];
 #pragma unroll
       for (int e = 0; e < 4; ++e) {
-        has[e] = i + e < a.n && !((dead[j] >> e) & 1u) && !(a.zero_single && vv[e] == 0u);
-        key[e] = make_key(sc[e], (uint32_t)(i + e));
+        vv[e] = s.value(j, e);
+        has[e] = s.live(j, e) && !(a.zero_single && vv[e] == 0u);
+        key[e] = make_key(s.score(j, e), (uint32_t)s.row(j, e));
       }
       // equal values among the thread's own four rows: the latest such element carries the largest of their keys on
 #pragma unroll
@@ -180,39 +156,25 @@ __global__ __launch_bounds__(CL_THREADS) void collapse_reduce_kernel(CollapseArg
 // *survivors (zero on entry) += the rows that stay.
 __global__ __launch_bounds__(CL_THREADS) void collapse_mark_kernel(CollapseArgs a, float* __restrict__ scores,
                                                                    unsigned long long* __restrict__ survivors) {
-  float4* s4 = (float4*)scores;
-  const uint4* v4 = (const uint4*)a.values;
+  using Strip = ScoredStrip<CL_THREADS, CL_VPT>;
   const int64_t n4 = (a.n + 3) >> 2;
-  const int64_t strips = (a.n + CL_STRIP - 1) / CL_STRIP;
+  const int64_t strips = Strip::strips(a.n);
   uint32_t kept = 0;   // the wave's count, the same in every lane
   for (int64_t strip = blockIdx.x; strip < strips; strip += gridDim.x) {
-    const int64_t base = strip * (CL_STRIP / 4) + threadIdx.x;
-    float4 sc4[CL_VPT];
-    uint4 val4[CL_VPT];
-    uint32_t dead[CL_VPT];
-#pragma unroll
-    for (int j = 0; j < CL_VPT; ++j) {   // all requested before the first is used
-      const int64_t i4 = base + (int64_t)j * CL_THREADS;
-      const bool in = i4 < n4;
-      sc4[j] = in ? s4[i4] : make_float4(0.f, 0.f, 0.f, 0.f);
-      val4[j] = (v4 && in) ? v4[i4] : make_uint4(0u, 0u, 0u, 0u);
-      dead[j] = dead_nibble(in ? a.dead_bits : nullptr, i4);
-    }
+    const Strip s(scores, a.values, a.dead_bits, a.n, strip);
 #pragma unroll
     for (int j = 0; j < CL_VPT; ++j) {
-      const int64_t i4 = base + (int64_t)j * CL_THREADS;
-      const int64_t i = i4 * 4;
-      float sc[4] = {sc4[j].x, sc4[j].y, sc4[j].z, sc4[j].w};
-      const uint32_t vv[4] = {val4[j].x, val4[j].y, val4[j].z, val4[j].w};
+      float sc[4];
 #pragma unroll
       for (int e = 0; e < 4; ++e) {
-        bool keep = i + e < a.n && !((dead[j] >> e) & 1u);
-        if (keep && !(a.zero_single && vv[e] == 0u))
-          keep = collapse_lookup(a.tab, a.bits, vv[e]) == make_key(sc[e], (uint32_t)(i + e));
+        sc[e] = s.score(j, e);
+        bool keep = s.live(j, e);
+        if (keep && !(a.zero_single && s.value(j, e) == 0u))
+          keep = collapse_lookup(a.tab, a.bits, s.value(j, e)) == make_key(sc[e], (uint32_t)s.row(j, e));
         if (!keep) sc[e] = -__builtin_inff();
         kept += (uint32_t)__popcll(__ballot(keep));
       }
-      if (i4 < n4) s4[i4] = make_float4(sc[0], sc[1], sc[2], sc[3]);   // (the padding past n belongs to the vector: -inf there too)
+      if (s.group(j) < n4) ((float4*)scores)[s.group(j)] = make_float4(sc[0], sc[1], sc[2], sc[3]);   // (the padding past n belongs to the vector: -inf there too)
     }
   }
   if ((threadIdx.x & 63) == 0 && kept) atomicAdd(survivors, (unsigned long long)kept);

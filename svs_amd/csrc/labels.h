@@ -9,6 +9,9 @@
 //      the earlier waves of the strip + the matches before it in its own wave (mbcnt of the wave's ballots).  Slots
 //      ascend with the rows, so the output is the matches in strictly ascending row order: the device row list
 //      enqueue_list_search takes (PAYLOAD 0, the row index) or the compacted label column (PAYLOAD 1, the label value).
+// The two passes are written once, as strip_count and strip_write<PAYLOAD>, for every filter type over strips
+// (LabelFilter here, WhereFilter in where.h): the type's overloads of strip_stage and strip_ballots stage its LDS image
+// and give the calling wave's ballots for the strip.  The __global__ kernels own the LDS arrays and call one of the two.
 // No workgroup ever waits for another: the only thing that crosses workgroups is the per-strip count, and it crosses
 // through a kernel boundary.  Every label is read twice per call (once per pass): a 1M-row column is 4 MB, the kernels
 // are launch-bound.
@@ -49,27 +52,34 @@ struct LabelFilter {
   uint32_t single;
 };
 
-// nset >= 2: the workgroup's copy of the set (call it from every thread, before label_strip_ballots)
+// nset >= 2: the workgroup's copy of the set (call it from every thread, before strip_ballots)
 __device__ __forceinline__ void label_stage_set(const LabelFilter& f, uint32_t* s_set) {
   if (f.nset < 2) return;
   for (int i = threadIdx.x; i < f.nset; i += LB_THREADS) s_set[i] = f.set[i];
   __syncthreads();
 }
 
+// Bisection of the sorted slice s_set[lo .. lo + len), len >= 1, of an LDS image: where the last entry <= v is, if there
+// is one (the caller compares).  The trip count depends on len alone.
+__device__ __forceinline__ int set_floor(const uint32_t* s_set, int lo, int len, uint32_t v) {
+  while (len > 1) {   // the last entry <= v, if there is one, is in [lo, lo + len)
+    const int half = len >> 1;
+    lo = s_set[lo + half] <= v ? lo + half : lo;
+    len -= half;
+  }
+  return lo;
+}
+
 // The SLOT of v, its index in the sorted set (nset >= 1), or -1: one label a compare, more a bisection of the LDS image
 __device__ __forceinline__ int label_slot(uint32_t v, const LabelFilter& f, const uint32_t* s_set) {
-  int lo = 0, len = f.nset;   // the last entry <= v, if there is one, is in [lo, lo + len)
+  int at = 0;
   bool hit;
   if (f.nset == 1) hit = v == f.single;
   else {
-    while (len > 1) {
-      const int half = len >> 1;
-      lo = s_set[lo + half] <= v ? lo + half : lo;
-      len -= half;
-    }
-    hit = s_set[lo] == v;
+    at = set_floor(s_set, 0, f.nset, v);
+    hit = s_set[at] == v;
   }
-  return hit ? lo : -1;
+  return hit ? at : -1;
 }
 
 __device__ __forceinline__ bool label_in_set(uint32_t v, const LabelFilter& f, const uint32_t* s_set) {
@@ -115,8 +125,8 @@ __device__ __forceinline__ S block_run_scan(uint32_t* items, int64_t n, int64_t 
 
 // The calling wave's part of strip `blockIdx.x`: b[j][e] = the ballot of "row row0 + 256 j + 4 lane + e matches",
 // v[j] = the lane's four labels of step j; returns the wave's matches.  row0 (out) = the wave's first row.
-__device__ __forceinline__ int label_strip_ballots(const LabelFilter& f, const uint32_t* s_set, unsigned long long (&b)[LB_ITERS][4],
-                                                   uint4 (&v)[LB_ITERS], int64_t* row0) {
+__device__ __forceinline__ int strip_ballots(const LabelFilter& f, const uint32_t* s_set, unsigned long long (&b)[LB_ITERS][4],
+                                             uint4 (&v)[LB_ITERS], int64_t* row0) {
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int64_t w0 = (int64_t)blockIdx.x * LB_STRIP + (int64_t)wave * LB_WAVE_ROWS;
   *row0 = w0;
@@ -143,16 +153,18 @@ __device__ __forceinline__ int label_strip_ballots(const LabelFilter& f, const u
   return cnt;
 }
 
-// grid = ceil(n / LB_STRIP) workgroups.  counts[blockIdx.x] = the strip's matches; *total += them (zero on entry).
-__global__ __launch_bounds__(LB_THREADS) void label_count_kernel(LabelFilter f, uint32_t* __restrict__ counts,
-                                                                 unsigned long long* __restrict__ total) {
-  __shared__ uint32_t s_set[LB_MAX_SET];
-  __shared__ int s_wave[LB_WAVES];
-  label_stage_set(f, s_set);
+__device__ __forceinline__ void strip_stage(const LabelFilter& f, uint32_t* s_set) { label_stage_set(f, s_set); }
+
+// The count pass of a workgroup over its strip, for a FILTER with strip_stage and strip_ballots: counts[blockIdx.x] =
+// the strip's matches; *total += them.
+template <class FILTER>
+__device__ __forceinline__ void strip_count(const FILTER& f, uint32_t* s_set, int* s_wave, uint32_t* __restrict__ counts,
+                                            unsigned long long* __restrict__ total) {
+  strip_stage(f, s_set);
   unsigned long long b[LB_ITERS][4];
   uint4 v[LB_ITERS];
   int64_t row0;
-  const int cnt = label_strip_ballots(f, s_set, b, v, &row0);
+  const int cnt = strip_ballots(f, s_set, b, v, &row0);
   if ((threadIdx.x & 63) == 0) s_wave[threadIdx.x >> 6] = cnt;
   __syncthreads();
   if (threadIdx.x == 0) {
@@ -164,25 +176,17 @@ __global__ __launch_bounds__(LB_THREADS) void label_count_kernel(LabelFilter f, 
   }
 }
 
-// One workgroup: counts[0 .. nb) -> their exclusive prefix sums, in place (block_run_scan).
-__global__ __launch_bounds__(LB_THREADS) void label_scan_kernel(uint32_t* __restrict__ counts, int64_t nb) {
-  __shared__ uint32_t s_sum[LB_THREADS];
-  (void)block_run_scan<LB_THREADS>(counts, nb, 1, s_sum);
-}
-
-// grid as label_count_kernel, same filter.  bases = the scanned counts; out[0 .. m) receives, in ascending row order,
-// the matching rows (PAYLOAD == LB_ROWS: local row indices) or their labels (LB_VALUES).  m = the total the count pass
-// found: a slot at or past it is never written.
-template <int PAYLOAD>
-__global__ __launch_bounds__(LB_THREADS) void label_write_kernel(LabelFilter f, const uint32_t* __restrict__ bases,
-                                                                 uint32_t* __restrict__ out, int64_t m) {
-  __shared__ uint32_t s_set[LB_MAX_SET];
-  __shared__ int s_wave[LB_WAVES];
-  label_stage_set(f, s_set);
+// The write pass: the predicate again; a match's slot is the strip's base + the matches in the earlier waves of the
+// strip + the matches before it in its own wave.  A slot at or past m is never written.  The payload of a match is its
+// row (LB_ROWS) or the value strip_ballots left in v (LB_VALUES: the label filter's).
+template <int PAYLOAD, class FILTER>
+__device__ __forceinline__ void strip_write(const FILTER& f, uint32_t* s_set, int* s_wave, const uint32_t* __restrict__ bases,
+                                            uint32_t* __restrict__ out, int64_t m) {
+  strip_stage(f, s_set);
   unsigned long long b[LB_ITERS][4];
   uint4 v[LB_ITERS];
   int64_t row0;
-  const int cnt = label_strip_ballots(f, s_set, b, v, &row0);
+  const int cnt = strip_ballots(f, s_set, b, v, &row0);
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   if (lane == 0) s_wave[wave] = cnt;
   __syncthreads();
@@ -209,6 +213,31 @@ __global__ __launch_bounds__(LB_THREADS) void label_write_kernel(LabelFilter f, 
     }
     slot += step;
   }
+}
+
+// grid = ceil(n / LB_STRIP) workgroups.  counts[blockIdx.x] = the strip's matches; *total += them (zero on entry).
+__global__ __launch_bounds__(LB_THREADS) void label_count_kernel(LabelFilter f, uint32_t* __restrict__ counts,
+                                                                 unsigned long long* __restrict__ total) {
+  __shared__ uint32_t s_set[LB_MAX_SET];
+  __shared__ int s_wave[LB_WAVES];
+  strip_count(f, s_set, s_wave, counts, total);
+}
+
+// One workgroup: counts[0 .. nb) -> their exclusive prefix sums, in place (block_run_scan).
+__global__ __launch_bounds__(LB_THREADS) void label_scan_kernel(uint32_t* __restrict__ counts, int64_t nb) {
+  __shared__ uint32_t s_sum[LB_THREADS];
+  (void)block_run_scan<LB_THREADS>(counts, nb, 1, s_sum);
+}
+
+// grid as label_count_kernel, same filter.  bases = the scanned counts; out[0 .. m) receives, in ascending row order,
+// the matching rows (PAYLOAD == LB_ROWS: local row indices) or their labels (LB_VALUES).  m = the total the count pass
+// found: a slot at or past it is never written.
+template <int PAYLOAD>
+__global__ __launch_bounds__(LB_THREADS) void label_write_kernel(LabelFilter f, const uint32_t* __restrict__ bases,
+                                                                 uint32_t* __restrict__ out, int64_t m) {
+  __shared__ uint32_t s_set[LB_MAX_SET];
+  __shared__ int s_wave[LB_WAVES];
+  strip_write<PAYLOAD>(f, s_set, s_wave, bases, out, m);
 }
 
 // pos[0 .. cnt): list positions as run_select wrote them -> out_rows[i] = list[pos[i]] + row_offset; a position

@@ -454,6 +454,12 @@ struct svs_index {
 
 namespace {
 
+// Floats from one score vector of n rows to the next: float4-aligned, as the select and strip kernels load them
+constexpr int64_t score_stride(int64_t n) { return (n + 3) & ~(int64_t)3; }
+
+// The device's dead-row bitmap (dead_bits.h), null while no row is masked
+inline const uint32_t* dead_bits_of(const svs_index* idx) { return idx->dead_list.empty() ? nullptr : idx->dead_bits_dev.p; }
+
 void ctx_destroy(Ctx* c) {
   if (!c) return;
   if (c->async_pending) (void)hipStreamSynchronize(c->last_stream);
@@ -1340,7 +1346,7 @@ thread_local int g_screen_slot;
 // steps 2-5 (step 1, approximate scores from the half shadow, is the route single_route(idx, variant, true)): histogram, filter with margin, exact re-score of the candidates, final top-k
 int run_select_screened(svs_index* idx, Ctx* c, const float* q_padded, int k, int count, float* out_s, int64_t* out_r,
                         hipStream_t st) {
-  const int64_t n = idx->n, sstride = (n + 3) & ~(int64_t)3;
+  const int64_t n = idx->n, sstride = score_stride(n);
   const int64_t per_block = (int64_t)FA_THREADS * SEL_VPT * 4;
   const unsigned blocks = (unsigned)((n + per_block - 1) / per_block);
   uint32_t* cnt_dev = idx->scr_dev + sizeof(ScreenStats) / 4 + (size_t)c->slot * SCREEN_SLOT_WORDS;
@@ -1350,7 +1356,7 @@ int run_select_screened(svs_index* idx, Ctx* c, const float* q_padded, int k, in
   hipLaunchKernelGGL(select_window_hist_kernel, dim3(blocks, 1), dim3(FA_THREADS), 0, st, (const float*)c->scores, n, sstride, c->hist);
   hipLaunchKernelGGL(screen_filter_kernel, dim3(blocks), dim3(FA_THREADS), 0, st, (const float*)c->scores, n, (uint32_t)count,
                      c->hist, c->cand, q_padded, idx->ld, (const ScreenStats*)idx->scr_dev, slot_host);
-  const uint32_t* dead_bits = idx->dead_list.empty() ? nullptr : idx->dead_bits_dev.p;
+  const uint32_t* dead_bits = dead_bits_of(idx);
   const int rblocks = idx->cu_count * 4;
   switch (idx->ld / 256) {
 #define SVS_RESCORE_CASE(N)                                                                                          \
@@ -1446,7 +1452,7 @@ int launch_gather(const svs_index* idx, Ctx* c, const float* q_dev, int nq, cons
 // matrix and select scratch are the caller's to size.  out_r receives POSITIONS in the list: list_positions_to_rows.
 int enqueue_list_search(svs_index* idx, Ctx* c, const float* q_dev, int nq, const uint32_t* list, int64_t m, int count, float* out_s,
                         int64_t* out_r, hipStream_t st) {
-  const int64_t sstride = (m + 3) & ~(int64_t)3;
+  const int64_t sstride = score_stride(m);
   const int rc = launch_gather(idx, c, q_dev, nq, list, m, c->scores, sstride, st);
   return rc != SVS_OK ? rc : run_select(idx, c, c->scores, m, sstride, nq, count, count, out_s, out_r, st, 0);
 }
@@ -1455,7 +1461,7 @@ int enqueue_list_search(svs_index* idx, Ctx* c, const float* q_dev, int nq, cons
 // (and, for k > SEL_KMAX over more than SORT_CAP rows, sort keys) stays <= 2 GiB.  out_s / out_r: [nq][count].
 int search_list_chunked(svs_index* idx, Ctx* c, int nq, int d, const uint32_t* list_dev, int64_t m, int count, float* out_s,
                         int64_t* out_r, hipStream_t st) {
-  const int64_t sstride = (m + 3) & ~(int64_t)3;
+  const int64_t sstride = score_stride(m);
   int64_t per_q = 4 * sstride;
   const SelectPath sel = select_path(m, count);
   if (sel == SelectPath::SORT) per_q += 8 * next_pow2_i64(m);
@@ -1625,7 +1631,7 @@ int plan_search(svs_index* idx, Ctx* c, int nq, int k, int count, hipStream_t st
   }
   if (nq == 1) p->route = single_route(idx, variant, p->screen);
   p->n_mat = p->fused ? fuse_prefix_rows(n) : n;       // rows of the materialised score matrix
-  p->sstride = (p->n_mat + 3) & ~(int64_t)3;           // float4-aligned score vectors
+  p->sstride = score_stride(p->n_mat);           // float4-aligned score vectors
   // thresholds: many queries over a short prefix -> one k-th-value kernel (47 vs 62 us at 1024 x 16,384);
   // otherwise the ordinary three-launch top-k, whose kernels spread one query over many workgroups
   // (16 queries: 20 vs 33 us; 256 x 156,250 rows: 119 vs 284 us).
@@ -1726,7 +1732,7 @@ int enqueue_select_half(svs_index* idx, Ctx* c, SearchPlan& p, float* out_s, int
   if (p.fused) {
     hipLaunchKernelGGL(select_final_kernel, dim3(nq), dim3(FINAL_THREADS), 0, st, (const float*)nullptr, n, (int64_t)0, k, count, 3,
                        c->hist, c->cand, idx->row_offset, out_s, out_r,
-                       (const uint32_t*)(idx->dead_list.empty() ? nullptr : idx->dead_bits_dev.p));
+                       dead_bits_of(idx));
   } else if (p.screen) {   // (stage_ms.score is the screen pass; the exact re-score of the candidates counts as select)
     if ((rc = run_select_screened(idx, c, p.q_padded, k, count, out_s, out_r, st)) != SVS_OK) return rc;
   } else if (k > 0 && (rc = run_select(idx, c, c->scores, n, p.sstride, nq, k, count, out_s, out_r, st, idx->row_offset)) != SVS_OK) {
@@ -1830,7 +1836,7 @@ int dequant_rows_to(svs_index* idx, int64_t r0, int64_t nrows, float* out, hipSt
 // triangle, the ordinary top-k stage over the flattened matrix (flat index i * np + j reproduces the
 // reference's tie order).  Results (scores, flat indices) stay on the device.
 int pairs_block_device(svs_index* idx, Ctx* c, int variant, int64_t ns, int count, float* S, float* qbuf, float* d_s, int64_t* d_r, hipStream_t st) {
-  const int64_t np = (ns + 3) & ~(int64_t)3;
+  const int64_t np = score_stride(ns);
   int rc;
   const int chunk = 1024;
   for (int64_t q0 = 0; q0 < ns; q0 += chunk) {
@@ -1859,7 +1865,7 @@ struct DevTmp {   // frees on scope exit
 };
 
 int top_pairs_materialised(svs_index* idx, HostCall& fr, int variant, int64_t n, int count, float* out_scores, int64_t* out_i, int64_t* out_j) {
-  const int64_t np = (n + 3) & ~(int64_t)3;
+  const int64_t np = score_stride(n);
   Ctx* const c = fr.c;
   const hipStream_t st = fr.stream();
   DevTmp tmp;
@@ -1902,7 +1908,7 @@ int top_pairs_tiled(svs_index* idx, HostCall& fr, int variant, int count, float*
   // prefix block: at least `count` live pairs inside it
   int64_t P = std::min<int64_t>(n, count > SEL_KMAX ? 8192 : 16384);
   while (P < n && (P - (int64_t)idx->dead_list.size()) * (P - (int64_t)idx->dead_list.size() - 1) / 2 < count) P = std::min<int64_t>(n, P * 2);
-  const int64_t Pp = (P + 3) & ~(int64_t)3;
+  const int64_t Pp = score_stride(P);
   if (P * Pp > 0xffffffffll) return fail(SVS_ERR_UNSUPPORTED, "top_pairs: k = %d needs a prefix block past 2^32 scores", count);
   constexpr uint32_t LIST_CAP = 8u << 20;  // global pair list (96 MB)
   DevTmp tmp;
@@ -1931,7 +1937,7 @@ int top_pairs_tiled(svs_index* idx, HostCall& fr, int variant, int count, float*
     FuseLaunch fl{c->hist, c->cand, thr, 0, TgPairs{(long long)qs, (long long)row_base, (long long)q0, 1}};
     if ((rc = score_batch(idx, c, variant, qbuf, nq, n - row_base, nullptr, 0, fl, st)) != SVS_OK) return rc;
     hipLaunchKernelGGL(collect_pairs_kernel, dim3(nq), dim3(256), 0, st, c->hist, (const uint64_t*)c->cand, (long long)qs, (long long)q0,
-                       (const uint32_t*)(idx->dead_list.empty() ? nullptr : idx->dead_bits_dev.p), gstate, LIST_CAP, l_key, l_i, l_j);
+                       dead_bits_of(idx), gstate, LIST_CAP, l_key, l_i, l_j);
   }
   HIP_TRY(hipGetLastError());
   uint32_t hs[4] = {0, 0, 0, 0};
@@ -2188,24 +2194,35 @@ inline int64_t label_strips(int64_t n) { return (n + LB_STRIP - 1) / LB_STRIP; }
 // The filter over the rows [0, n) the index holds: set[0 .. nset) sorted and distinct on the HOST, set_dev its device
 // copy (read when nset >= 2 only); nset == 0: every live row
 LabelFilter label_filter(const svs_index* idx, int column, const uint32_t* set, int nset, const uint32_t* set_dev) {
-  return LabelFilter{idx->cols[column], idx->n, idx->dead_list.empty() ? nullptr : idx->dead_bits_dev.p, set_dev, nset, nset == 1 ? set[0] : 0u};
+  return LabelFilter{idx->cols[column], idx->n, dead_bits_of(idx), set_dev, nset, nset == 1 ? set[0] : 0u};
+}
+
+// The two kernels of a filter type (labels.h's strip compaction; where.h's writes rows only)
+inline auto strip_count_kernel(const LabelFilter&) { return &label_count_kernel; }
+inline auto strip_count_kernel(const WhereFilter&) { return &where_count_kernel; }
+template <int PAYLOAD> auto strip_write_kernel(const LabelFilter&) { return &label_write_kernel<PAYLOAD>; }
+template <int PAYLOAD> auto strip_write_kernel(const WhereFilter&) {
+  static_assert(PAYLOAD == LB_ROWS, "where_write_kernel writes row indices");
+  return &where_write_kernel;
 }
 
 // cnt: one u64 (the total, zeroed here) followed by one u32 per strip of f.n rows
-void launch_label_count(const LabelFilter& f, uint32_t* cnt, hipStream_t st) {
+template <class FILTER>
+void launch_label_count(const FILTER& f, uint32_t* cnt, hipStream_t st) {
   (void)hipMemsetAsync(cnt, 0, sizeof(unsigned long long), st);
-  hipLaunchKernelGGL(label_count_kernel, dim3((unsigned)label_strips(f.n)), dim3(LB_THREADS), 0, st, f, cnt + 2, (unsigned long long*)cnt);
+  hipLaunchKernelGGL(strip_count_kernel(f), dim3((unsigned)label_strips(f.n)), dim3(LB_THREADS), 0, st, f, cnt + 2, (unsigned long long*)cnt);
 }
 
 // ... and behind it: the counts scanned into the strips' bases, then the m matches written to out in ascending row order
-template <int PAYLOAD>
-void launch_label_write(const LabelFilter& f, uint32_t* cnt, uint32_t* out, int64_t m, hipStream_t st) {
+template <int PAYLOAD, class FILTER>
+void launch_label_write(const FILTER& f, uint32_t* cnt, uint32_t* out, int64_t m, hipStream_t st) {
   hipLaunchKernelGGL(label_scan_kernel, dim3(1), dim3(LB_THREADS), 0, st, cnt + 2, label_strips(f.n));
-  hipLaunchKernelGGL((label_write_kernel<PAYLOAD>), dim3((unsigned)label_strips(f.n)), dim3(LB_THREADS), 0, st, f, (const uint32_t*)(cnt + 2), out, m);
+  hipLaunchKernelGGL(strip_write_kernel<PAYLOAD>(f), dim3((unsigned)label_strips(f.n)), dim3(LB_THREADS), 0, st, f, (const uint32_t*)(cnt + 2), out, m);
 }
 
 // A caller's label set, sorted and without repeats: a label's SLOT in every table of the device is its index here
 struct LabelSet {
+  using Filter = LabelFilter;
   std::vector<uint32_t> set;
   int nset = 0;
   // The caller's arguments, checked where the entry checked them; build (entry: the ABI name, for the message) follows
@@ -2213,14 +2230,18 @@ struct LabelSet {
     if (nlabels < 0) return fail(SVS_ERR_INVALID, "nlabels must be >= 0");
     return nlabels > 0 && !labels ? fail(SVS_ERR_INVALID, "null labels") : (int)SVS_OK;
   }
+  // set = the distinct members of labels[0 .. nlabels), ascending (std::bad_alloc is the caller's to report)
+  static void sort_distinct(std::vector<uint32_t>& set, const uint32_t* labels, int32_t nlabels) {
+    set.assign(labels, labels + nlabels);
+    std::sort(set.begin(), set.end());
+    set.erase(std::unique(set.begin(), set.end()), set.end());
+  }
   int build(const char* entry, const uint32_t* labels, int32_t nlabels) {
     try {
-      set.assign(labels, labels + nlabels);
+      sort_distinct(set, labels, nlabels);
     } catch (const std::bad_alloc&) {
       return fail(SVS_ERR_NOMEM, "out of host memory for %d labels", (int)nlabels);
     }
-    std::sort(set.begin(), set.end());
-    set.erase(std::unique(set.begin(), set.end()), set.end());
     if (set.size() > (size_t)SVS_LABELS_MAX_SET)
       return fail(SVS_ERR_UNSUPPORTED, "%s: %zu distinct labels; a set holds at most %d", entry, set.size(), SVS_LABELS_MAX_SET);
     nset = (int)set.size();
@@ -2867,7 +2888,75 @@ void launch_assign_na(const svs_index* idx, const Ctx* cx, int c, int64_t r0, in
   const unsigned blocks = (unsigned)std::min<int64_t>((nrows + AS_ROWS - 1) / AS_ROWS, AS_GRID_MAX);
   hipLaunchKernelGGL((assign_rows_kernel<DT, NA>), dim3(blocks), dim3(AS_THREADS), 0, st, (const u32x4*)idx->rows, ld16,
                      (const float*)idx->row_scales, idx->n, (const u32x4*)cx->as_vec.p, (const float*)cx->as_vec_scales.p, c, r0, nrows,
-                     (const uint32_t*)(idx->dead_list.empty() ? nullptr : idx->dead_bits_dev.p), vec_labels, best, scores, labels, counts);
+                     dead_bits_of(idx), vec_labels, best, scores, labels, counts);
+}
+
+// The context's one score vector over all n rows: the tombstoned rows' scores go to -inf, then the exact top-k stage
+// writes the best `count` rows (global) to out_s / out_r
+int select_live(svs_index* idx, Ctx* c, int count, float* out_s, int64_t* out_r, hipStream_t st) {
+  const int64_t n = idx->n, sstride = score_stride(n);
+  if (!idx->dead_list.empty())
+    hipLaunchKernelGGL(mask_dead_rows_kernel, dim3(64), dim3(256), 0, st, c->scores.p, sstride, 1, (const uint32_t*)idx->dead_dev.p,
+                       (int64_t)idx->dead_list.size(), n, (int64_t)0);
+  return run_select(idx, c, c->scores, n, sstride, 1, count, count, out_s, out_r, st, idx->row_offset);
+}
+
+// ---- the filtered searches: svs_index_search_labeled (labels.h) and svs_index_search_where (where.h)
+// Every successful exit of the two: the entries written, the rows that matched
+int32_t filtered_done(int32_t* out_count, int64_t* out_matched, int count, int64_t m) {
+  if (out_count) *out_count = count;
+  if (out_matched) *out_matched = m;
+  return SVS_OK;
+}
+
+struct FilteredNames {
+  const char *entry, *count_kernel, *write_kernel;   // the entry's short name for the messages, the two recorded launches
+};
+
+// What the two do once their arguments are checked (the caller holds the index's shared lock): plan (a LabelSet or a
+// WherePlan) stages its filter, the strips are counted, and the matching rows' list is written and searched on the
+// device.  record_arg: the recorded launches' second figure; ranks: results are wanted, if a row matches.
+template <class PLAN>
+int32_t filtered_search(svs_index* idx, const PLAN& plan, const FilteredNames& names, int record_arg, bool ranks, const float* queries,
+                               int32_t nq, int32_t d, int32_t k, float* out_scores, int64_t* out_rows, int32_t* out_count, int64_t* out_matched) {
+  if (!ranks && !out_matched) return filtered_done(out_count, out_matched, 0, 0);   // nothing to rank and nobody to tell the count
+  int rc;
+  HostCall fr(idx);
+  if ((rc = fr.open()) != SVS_OK) return rc;
+  Ctx* const c = fr.c;
+  const int64_t n = idx->n, lo = idx->row_offset;
+  if ((rc = c->lab_cnt.grow((size_t)label_strips(n) + 2)) != SVS_OK || (rc = c->lab_tot_pin.grow(1)) != SVS_OK) return rc;
+  // 1. the filter goes up, the count runs; the host needs m = |S| to size the list, the score matrix and the select route
+  hipStream_t st = fr.stream();
+  typename PLAN::Filter f;
+  if ((rc = plan.stage(idx, c, st, &f)) != SVS_OK) return rc;
+  launch_record(names.count_kernel, n, record_arg);
+  launch_label_count(f, c->lab_cnt, st);
+  HIP_TRY(hipMemcpyAsync(c->lab_tot_pin, c->lab_cnt, sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
+  if ((rc = fr.close(names.entry)) != SVS_OK) return rc;
+  const int64_t m = (int64_t)c->lab_tot_pin[0];
+  if (m < 0 || m > n) return fail(SVS_ERR_DEVICE, "%s: the filter counted %lld of %lld rows", names.entry, (long long)m, (long long)n);
+  const int count = ranks ? (int)std::min<int64_t>(k, m) : 0;
+  if (count == 0) return filtered_done(out_count, out_matched, 0, m);
+  // 2. the list is written on the device; from here on the call is svs_index_search_rows over it
+  const size_t qn = (size_t)nq * (size_t)d, on = (size_t)nq * (size_t)count;
+  if ((rc = c->list_dev.grow((size_t)m)) != SVS_OK || (rc = c->lab_pos.grow(on)) != SVS_OK) return rc;
+  if ((rc = c->out_s_pin.grow(on)) != SVS_OK || (rc = c->out_r_pin.grow(on)) != SVS_OK) return rc;
+  st = fr.stream();
+  if ((rc = upload_queries(c, queries, qn, st)) != SVS_OK) return rc;
+  launch_record(names.write_kernel, n, record_arg);
+  launch_label_write<LB_ROWS>(f, c->lab_cnt, c->list_dev, m, st);
+  if ((rc = search_list_chunked(idx, c, nq, d, c->list_dev, m, count, c->out_s_pin, c->lab_pos, st)) != SVS_OK) return rc;
+  // the positions -> global rows, on the device: the list never exists on the host
+  hipLaunchKernelGGL(label_map_rows_kernel, dim3((unsigned)std::min<size_t>((on + 255) / 256, 1024)), dim3(256), 0, st,
+                     (const int64_t*)c->lab_pos.p, (int64_t)on, (const uint32_t*)c->list_dev.p, m, lo, c->out_r_pin.p);
+  if ((rc = fr.close(names.entry)) != SVS_OK) return rc;
+  for (size_t i = 0; i < on; ++i)
+    if (c->out_r_pin[i] < 0)
+      return fail(SVS_ERR_DEVICE, "%s: result %zu of query %zu is a position outside the %lld matching rows", names.entry, i % (size_t)count,
+                  i / (size_t)count, (long long)m);
+  deliver_results(c, nq, count, k, out_scores, out_rows);
+  return filtered_done(out_count, out_matched, count, m);
 }
 
 }  // namespace
@@ -3330,7 +3419,7 @@ static int pipe_get(svs_index* idx, hipStream_t caller, AheadPipe** out) {
 struct SingleScratch { size_t scores, hist, keys, q16, qh, q8, q8s, q8f; };
 static SingleScratch single_scratch(const svs_index* idx, const SingleRoute& r, SelectPath sel) {
   const size_t ld = (size_t)idx->ld, half = r.query == SingleRoute::HALF, fp8 = r.query == SingleRoute::FP8;
-  return {(size_t)((idx->n + 3) & ~(int64_t)3), sel == SelectPath::WINDOW, sel == SelectPath::SORT ? (size_t)next_pow2_i64(idx->n) : 0,
+  return {(size_t)score_stride(idx->n), sel == SelectPath::WINDOW, sel == SelectPath::SORT ? (size_t)next_pow2_i64(idx->n) : 0,
           r.query == SingleRoute::PADDED ? (size_t)GQ * ld : 0, half * ld, fp8 * ld, fp8, fp8 * ld};
 }
 static bool ahead_scratch_ok(const Ctx* c, const SingleScratch& s) {
@@ -3478,7 +3567,7 @@ static int32_t search_device(svs_index* idx, const float* dev_queries, int32_t n
   if ((rc = ctx_acquire(idx, st, false, &c)) != SVS_OK) return rc;
   CtxGuard cg{idx, c};
   // growing scratch frees buffers that earlier work on this stream may still read
-  const size_t need_scores = (size_t)nq * (size_t)((idx->n + 3) & ~(int64_t)3);
+  const size_t need_scores = (size_t)nq * (size_t)score_stride(idx->n);
   if (c->async_pending && (need_scores > c->scores.cap || (size_t)nq > c->hist_cap)) HIP_TRY(hipStreamSynchronize(st));
   rc = enqueue_search(idx, c, dev_queries, nq, k, count, dev_out_scores, dev_out_rows, st);
   c->last_stream = st;
@@ -3515,7 +3604,7 @@ int32_t svs_index_scores_n(svs_index* idx, const float* query, int32_t d, float*
   if ((rc = fr.open()) != SVS_OK) return rc;
   Ctx* const c = fr.c;
   if ((rc = c->q_dev.grow((size_t)d)) != SVS_OK) return rc;
-  if ((rc = c->scores.grow((size_t)((idx->n + 3) & ~(int64_t)3))) != SVS_OK) return rc;
+  if ((rc = c->scores.grow((size_t)score_stride(idx->n))) != SVS_OK) return rc;
   const hipStream_t st = fr.stream();
   HIP_TRY(hipMemcpyAsync(c->q_dev, query, (size_t)d * sizeof(float), hipMemcpyHostToDevice, st));
   if ((rc = launch_query_scores(idx, c, single_route(idx, idx->variant.load(), false), 0, st)) != SVS_OK) return rc;
@@ -3664,48 +3753,9 @@ int32_t svs_index_search_labeled(svs_index* idx, const float* queries, int32_t n
   const bool ranks = nq > 0 && k > 0 && nset > 0;   // results are wanted, if a row matches
   if (ranks && (!out_scores || !out_rows)) return fail(SVS_ERR_INVALID, "null output");
   if (ranks && (rc = check_gather_rows(idx, "svs_index_search_labeled")) != SVS_OK) return rc;
-  const auto done = [&](int count, int64_t m) {   // every successful exit: the entries written, the rows that matched
-    if (out_count) *out_count = count;
-    if (out_matched) *out_matched = m;
-    return (int32_t)SVS_OK;
-  };
-  if (nset == 0 || (!ranks && !out_matched)) return done(0, 0);   // the empty set, or nothing to rank and nobody to tell the count
-  HostCall fr(idx);
-  if ((rc = fr.open()) != SVS_OK) return rc;
-  Ctx* const c = fr.c;
-  const int64_t n = idx->n, lo = idx->row_offset;
-  if ((rc = c->lab_cnt.grow((size_t)label_strips(n) + 2)) != SVS_OK || (rc = c->lab_tot_pin.grow(1)) != SVS_OK) return rc;
-  // 1. the set goes up, the count runs; the host needs m = |S| to size the list, the score matrix and the select route
-  hipStream_t st = fr.stream();
-  LabelFilter f;
-  if ((rc = ls.stage(idx, c, st, &f)) != SVS_OK) return rc;
-  launch_record("label_count_kernel", n, nset);
-  launch_label_count(f, c->lab_cnt, st);
-  HIP_TRY(hipMemcpyAsync(c->lab_tot_pin, c->lab_cnt, sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
-  if ((rc = fr.close("search_labeled")) != SVS_OK) return rc;
-  const int64_t m = (int64_t)c->lab_tot_pin[0];
-  if (m < 0 || m > n) return fail(SVS_ERR_DEVICE, "search_labeled: the filter counted %lld of %lld rows", (long long)m, (long long)n);
-  const int count = ranks ? (int)std::min<int64_t>(k, m) : 0;
-  if (count == 0) return done(0, m);
-  // 2. the list is written on the device; from here on the call is svs_index_search_rows over it
-  const size_t qn = (size_t)nq * (size_t)d, on = (size_t)nq * (size_t)count;
-  if ((rc = c->list_dev.grow((size_t)m)) != SVS_OK || (rc = c->lab_pos.grow(on)) != SVS_OK) return rc;
-  if ((rc = c->out_s_pin.grow(on)) != SVS_OK || (rc = c->out_r_pin.grow(on)) != SVS_OK) return rc;
-  st = fr.stream();
-  if ((rc = upload_queries(c, queries, qn, st)) != SVS_OK) return rc;
-  launch_record("label_write_kernel", n, nset);
-  launch_label_write<LB_ROWS>(f, c->lab_cnt, c->list_dev, m, st);
-  if ((rc = search_list_chunked(idx, c, nq, d, c->list_dev, m, count, c->out_s_pin, c->lab_pos, st)) != SVS_OK) return rc;
-  // the positions -> global rows, on the device: the list never exists on the host
-  hipLaunchKernelGGL(label_map_rows_kernel, dim3((unsigned)std::min<size_t>((on + 255) / 256, 1024)), dim3(256), 0, st,
-                     (const int64_t*)c->lab_pos.p, (int64_t)on, (const uint32_t*)c->list_dev.p, m, lo, c->out_r_pin.p);
-  if ((rc = fr.close("search_labeled")) != SVS_OK) return rc;
-  for (size_t i = 0; i < on; ++i)
-    if (c->out_r_pin[i] < 0)
-      return fail(SVS_ERR_DEVICE, "search_labeled: result %zu of query %zu is a position outside the %lld matching rows", i % (size_t)count,
-                  i / (size_t)count, (long long)m);
-  deliver_results(c, nq, count, k, out_scores, out_rows);
-  return done(count, m);
+  if (nset == 0) return filtered_done(out_count, out_matched, 0, 0);   // the empty set: no row
+  return filtered_search(idx, ls, FilteredNames{"search_labeled", "label_count_kernel", "label_write_kernel"}, nset, ranks, queries, nq, d, k,
+                         out_scores, out_rows, out_count, out_matched);
 }
 
 // ---- svs_index_search_where (where.h)
@@ -3716,6 +3766,7 @@ static_assert(SVS_WHERE_IN == WH_IN && SVS_WHERE_RANGE == WH_RANGE && SVS_WHERE_
 // A caller's terms, checked, and their kernel form: every IN term's set sorted and without repeats; the sets of two
 // members or more one after another in `image` (at most SVS_LABELS_MAX_SET words: the kernels' LDS image)
 struct WherePlan {
+  using Filter = WhereFilter;
   WhereTerm t[WH_MAX_TERMS] = {};
   int nterms = 0;
   uint32_t col_mask = 0;
@@ -3743,9 +3794,7 @@ struct WherePlan {
       w.a = w.b = 0;
       std::vector<uint32_t> set;
       try {
-        set.assign(u.set, u.set + u.nset);
-        std::sort(set.begin(), set.end());
-        set.erase(std::unique(set.begin(), set.end()), set.end());
+        LabelSet::sort_distinct(set, u.set, u.nset);
         members += set.size();
         if (set.size() >= 2 && members <= (size_t)SVS_LABELS_MAX_SET) {
           w.set0 = (int32_t)image.size();
@@ -3775,7 +3824,7 @@ struct WherePlan {
     *f = WhereFilter{};
     f->col0 = idx->cols[0], f->col1 = idx->cols[1], f->col2 = idx->cols[2], f->col3 = idx->cols[3];
     f->n = idx->n;
-    f->dead_bits = idx->dead_list.empty() ? nullptr : idx->dead_bits_dev.p;
+    f->dead_bits = dead_bits_of(idx);
     f->set = words ? c->lab_set_dev.p : nullptr;
     f->set_words = (int32_t)words;
     f->nterms = nterms;
@@ -3798,50 +3847,8 @@ int32_t svs_index_search_where(svs_index* idx, const float* queries, int32_t nq,
   const bool ranks = nq > 0 && k > 0;   // results are wanted, if a row matches
   if (ranks && (!out_scores || !out_rows)) return fail(SVS_ERR_INVALID, "null output");
   if (ranks && (rc = check_gather_rows(idx, "svs_index_search_where")) != SVS_OK) return rc;
-  const auto done = [&](int count, int64_t m) {   // every successful exit: the entries written, the rows that matched
-    if (out_count) *out_count = count;
-    if (out_matched) *out_matched = m;
-    return (int32_t)SVS_OK;
-  };
-  if (!ranks && !out_matched) return done(0, 0);   // nothing to rank and nobody to tell the count
-  HostCall fr(idx);
-  if ((rc = fr.open()) != SVS_OK) return rc;
-  Ctx* const c = fr.c;
-  const int64_t n = idx->n, lo = idx->row_offset;
-  if ((rc = c->lab_cnt.grow((size_t)label_strips(n) + 2)) != SVS_OK || (rc = c->lab_tot_pin.grow(1)) != SVS_OK) return rc;
-  // 1. the sets go up, the count runs; the host needs m = |S| to size the list, the score matrix and the select route
-  hipStream_t st = fr.stream();
-  WhereFilter f;
-  if ((rc = plan.stage(idx, c, st, &f)) != SVS_OK) return rc;
-  const unsigned strips = (unsigned)label_strips(n);
-  launch_record("where_count_kernel", n, plan.nterms);
-  (void)hipMemsetAsync(c->lab_cnt, 0, sizeof(unsigned long long), st);
-  hipLaunchKernelGGL(where_count_kernel, dim3(strips), dim3(LB_THREADS), 0, st, f, c->lab_cnt.p + 2, (unsigned long long*)c->lab_cnt.p);
-  HIP_TRY(hipMemcpyAsync(c->lab_tot_pin, c->lab_cnt, sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
-  if ((rc = fr.close("search_where")) != SVS_OK) return rc;
-  const int64_t m = (int64_t)c->lab_tot_pin[0];
-  if (m < 0 || m > n) return fail(SVS_ERR_DEVICE, "search_where: the filter counted %lld of %lld rows", (long long)m, (long long)n);
-  const int count = ranks ? (int)std::min<int64_t>(k, m) : 0;
-  if (count == 0) return done(0, m);
-  // 2. the list is written on the device; from here on the call is svs_index_search_rows over it, as svs_index_search_labeled
-  const size_t qn = (size_t)nq * (size_t)d, on = (size_t)nq * (size_t)count;
-  if ((rc = c->list_dev.grow((size_t)m)) != SVS_OK || (rc = c->lab_pos.grow(on)) != SVS_OK) return rc;
-  if ((rc = c->out_s_pin.grow(on)) != SVS_OK || (rc = c->out_r_pin.grow(on)) != SVS_OK) return rc;
-  st = fr.stream();
-  if ((rc = upload_queries(c, queries, qn, st)) != SVS_OK) return rc;
-  launch_record("where_write_kernel", n, plan.nterms);
-  hipLaunchKernelGGL(label_scan_kernel, dim3(1), dim3(LB_THREADS), 0, st, c->lab_cnt.p + 2, label_strips(n));
-  hipLaunchKernelGGL(where_write_kernel, dim3(strips), dim3(LB_THREADS), 0, st, f, (const uint32_t*)(c->lab_cnt.p + 2), c->list_dev.p, m);
-  if ((rc = search_list_chunked(idx, c, nq, d, c->list_dev, m, count, c->out_s_pin, c->lab_pos, st)) != SVS_OK) return rc;
-  hipLaunchKernelGGL(label_map_rows_kernel, dim3((unsigned)std::min<size_t>((on + 255) / 256, 1024)), dim3(256), 0, st,
-                     (const int64_t*)c->lab_pos.p, (int64_t)on, (const uint32_t*)c->list_dev.p, m, lo, c->out_r_pin.p);
-  if ((rc = fr.close("search_where")) != SVS_OK) return rc;
-  for (size_t i = 0; i < on; ++i)
-    if (c->out_r_pin[i] < 0)
-      return fail(SVS_ERR_DEVICE, "search_where: result %zu of query %zu is a position outside the %lld matching rows", i % (size_t)count,
-                  i / (size_t)count, (long long)m);
-  deliver_results(c, nq, count, k, out_scores, out_rows);
-  return done(count, m);
+  return filtered_search(idx, plan, FilteredNames{"search_where", "where_count_kernel", "where_write_kernel"}, plan.nterms, ranks, queries, nq, d,
+                         k, out_scores, out_rows, out_count, out_matched);
 }
 
 int32_t svs_index_search_above(svs_index* idx, const float* queries, int32_t nq, int32_t d, const float* min_scores, int32_t limit,
@@ -3866,14 +3873,12 @@ int32_t svs_index_search_above(svs_index* idx, const float* queries, int32_t nq,
   Ctx* const c = fr.c;
   hipStream_t st = fr.stream();
   const size_t qn = (size_t)nq * (size_t)d, on = std::max<size_t>((size_t)nq * (size_t)ls, 1);
-  const int64_t sstride = (n + 3) & ~(int64_t)3;
   if ((rc = c->out_s_pin.grow(on)) != SVS_OK || (rc = c->out_r_pin.grow(on)) != SVS_OK) return rc;
   if ((rc = c->above_cnt_pin.grow((size_t)nq)) != SVS_OK || (rc = c->above_tot_pin.grow((size_t)nq)) != SVS_OK) return rc;
-  if ((rc = c->scores.grow((size_t)sstride)) != SVS_OK) return rc;
+  if ((rc = c->scores.grow((size_t)score_stride(n))) != SVS_OK) return rc;
   if ((rc = grow_select_scratch(c, 1, st)) != SVS_OK) return rc;
   const SingleRoute route = single_route(idx, idx->variant.load(), false);   // the kernel svs_index_scores_n runs
-  const bool masked = !idx->dead_list.empty();
-  const uint32_t* dead_bits = masked ? idx->dead_bits_dev.p : nullptr;
+  const uint32_t* dead_bits = dead_bits_of(idx);
   const int64_t per_block = (int64_t)FA_THREADS * SEL_VPT * 4;
   const unsigned blocks = (unsigned)((n + per_block - 1) / per_block);
   if ((rc = upload_queries(c, queries, qn, st)) != SVS_OK) return rc;
@@ -3901,12 +3906,9 @@ int32_t svs_index_search_above(svs_index* idx, const float* queries, int32_t nq,
       if ((rc = c->redo_s_pin.grow((size_t)count)) != SVS_OK || (rc = c->redo_r_pin.grow((size_t)count)) != SVS_OK) return rc;
       st = fr.stream();
       if ((rc = launch_query_scores(idx, c, route, q, st)) != SVS_OK) return rc;
-      if (masked)
-        hipLaunchKernelGGL(mask_dead_rows_kernel, dim3(64), dim3(256), 0, st, c->scores.p, sstride, 1, (const uint32_t*)idx->dead_dev.p,
-                           (int64_t)idx->dead_list.size(), n, (int64_t)0);
       const SelectPath path = select_path(n, count);   // (recorded: which stage the re-run took)
       launch_record(path == SelectPath::WINDOW ? "select_window_hist_kernel" : (path == SelectPath::SORT ? "keys_build_kernel" : "select_final_kernel"), n, 1);
-      if ((rc = run_select(idx, c, c->scores, n, sstride, 1, count, count, c->redo_s_pin, c->redo_r_pin, st, idx->row_offset)) != SVS_OK) return rc;
+      if ((rc = select_live(idx, c, count, c->redo_s_pin, c->redo_r_pin, st)) != SVS_OK) return rc;
       if ((rc = fr.close("search_above", true)) != SVS_OK) return rc;
       memcpy(out_scores + (size_t)q * limit, c->redo_s_pin, (size_t)count * sizeof(float));
       memcpy(out_rows + (size_t)q * limit, c->redo_r_pin, (size_t)count * sizeof(int64_t));
@@ -3936,23 +3938,17 @@ int32_t svs_index_search_combined(svs_index* idx, const float* vectors, int32_t 
   Ctx* const c = fr.c;
   const hipStream_t st = fr.stream();
   const CombineRoute route = combine_route(idx, idx->variant.load(), m, (int)g_tune_combine_route.load());
-  const int64_t sstride = (n + 3) & ~(int64_t)3;
+  const int64_t sstride = score_stride(n);
   const size_t vn = (size_t)nq * m * d, wn = (size_t)nq * m, on = (size_t)nq * (size_t)count;
   if ((rc = c->out_s_pin.grow(on)) != SVS_OK || (rc = c->out_r_pin.grow(on)) != SVS_OK) return rc;
   if ((rc = c->scores.grow((size_t)(route.fused ? 1 : m) * sstride)) != SVS_OK) return rc;
   if (select_path(n, count) == SelectPath::WINDOW && (rc = grow_select_scratch(c, 1, st)) != SVS_OK) return rc;
   if ((rc = upload_combined(c, vectors, weights, vn, wn, st)) != SVS_OK) return rc;
-  const bool masked = !idx->dead_list.empty();
   // every combined query back to back: score pass(es), tombstone mask, selection -- the context's score vectors and
   // selection scratch are reused in stream order; no host wait in between
   for (int32_t q = 0; q < nq; ++q) {
     if ((rc = enqueue_combined_scores(idx, c, route, c->q_dev + (size_t)q * m * d, c->q_dev + vn + (size_t)q * m, m, op, sstride, st)) != SVS_OK) return rc;
-    if (masked)
-      hipLaunchKernelGGL(mask_dead_rows_kernel, dim3(64), dim3(256), 0, st, c->scores.p, sstride, 1, (const uint32_t*)idx->dead_dev.p,
-                         (int64_t)idx->dead_list.size(), n, (int64_t)0);
-    if ((rc = run_select(idx, c, c->scores, n, sstride, 1, count, count, c->out_s_pin + (size_t)q * count, c->out_r_pin + (size_t)q * count, st,
-                         idx->row_offset)) != SVS_OK)
-      return rc;
+    if ((rc = select_live(idx, c, count, c->out_s_pin + (size_t)q * count, c->out_r_pin + (size_t)q * count, st)) != SVS_OK) return rc;
   }
   if ((rc = fr.close("search_combined")) != SVS_OK) return rc;
   deliver_results(c, nq, count, k, out_scores, out_rows);
@@ -3977,7 +3973,7 @@ int32_t svs_internal_combined_scores(svs_index* idx, const float* vectors, int32
   if ((rc = fr.open()) != SVS_OK) return rc;
   Ctx* const c = fr.c;
   const hipStream_t st = fr.stream();
-  const int64_t sstride = (n + 3) & ~(int64_t)3;
+  const int64_t sstride = score_stride(n);
   const size_t vn = (size_t)m * d;
   if ((rc = c->scores.grow((size_t)(r.fused ? 1 : m) * sstride)) != SVS_OK) return rc;
   if ((rc = upload_combined(c, vectors, weights, vn, (size_t)m, st)) != SVS_OK) return rc;
@@ -4028,7 +4024,7 @@ int32_t svs_index_search_by_label(svs_index* idx, const float* queries, int32_t 
   const size_t qn = (size_t)nq * (size_t)d, on = std::max<size_t>((size_t)nq * (size_t)ks, 1);
   if ((rc = c->out_s_pin.grow(on)) != SVS_OK || (rc = c->out_r_pin.grow(on)) != SVS_OK) return rc;
   if ((rc = c->bl_lab_pin.grow(on)) != SVS_OK || (rc = c->bl_tot_pin.grow(on)) != SVS_OK || (rc = c->bl_cnt_pin.grow((size_t)nq * 2)) != SVS_OK) return rc;
-  if ((rc = c->scores.grow((size_t)((n + 3) & ~(int64_t)3))) != SVS_OK) return rc;
+  if ((rc = c->scores.grow((size_t)score_stride(n))) != SVS_OK) return rc;
   if (cross == BL_PARTIALS) {
     if ((rc = c->bl_part_best.grow((size_t)blocks * nset)) != SVS_OK || (rc = c->bl_part_cnt.grow((size_t)blocks * nset)) != SVS_OK) return rc;
   } else if (!c->bl_tab.p) {
@@ -4114,7 +4110,7 @@ int32_t svs_index_search_collapsed(svs_index* idx, const float* queries, int32_t
   Ctx* const c = fr.c;
   hipStream_t st = fr.stream();
   const size_t qn = (size_t)nq * (size_t)d, on = std::max<size_t>((size_t)nq * (size_t)ks, 1);
-  const int64_t sstride = (n + 3) & ~(int64_t)3;
+  const int64_t sstride = score_stride(n);
   if ((rc = c->out_s_pin.grow(on)) != SVS_OK || (rc = c->out_r_pin.grow(on)) != SVS_OK || (rc = c->cl_val_pin.grow(on)) != SVS_OK) return rc;
   if ((rc = c->cl_cnt.grow((size_t)nq)) != SVS_OK || (rc = c->cl_cnt_pin.grow((size_t)nq)) != SVS_OK) return rc;
   if ((rc = c->scores.grow((size_t)sstride)) != SVS_OK) return rc;
@@ -4127,7 +4123,7 @@ int32_t svs_index_search_collapsed(svs_index* idx, const float* queries, int32_t
   HIP_TRY(hipMemsetAsync(c->cl_cnt, 0, (size_t)nq * sizeof(unsigned long long), st));
   const SingleRoute route = single_route(idx, idx->variant.load(), false);   // the kernel svs_index_scores_n runs
   if ((rc = upload_queries(c, queries, qn, st)) != SVS_OK) return rc;
-  const CollapseArgs a{idx->cols[column], idx->dead_list.empty() ? nullptr : idx->dead_bits_dev.p, c->cl_tab.p, n, bits,
+  const CollapseArgs a{idx->cols[column], dead_bits_of(idx), c->cl_tab.p, n, bits,
                        zero_mode == SVS_COLLAPSE_ZERO_SINGLE ? 1 : 0};
   const bool timed = idx->timing.load() > 0;
   const TimedSpan t_reduce(timed), t_mark(timed), t_clear(timed), t_select(timed);
@@ -4565,7 +4561,7 @@ int32_t svs_index_search_segments(svs_index* idx, const float* queries, int32_t 
   const size_t res_words = res_n + (res_n + 1) / 2;
   if ((rc = c->list_dev.grow((size_t)listed)) != SVS_OK) return rc;
   if ((rc = c->seg_res_dev.grow(res_words)) != SVS_OK || (rc = c->seg_res_pin.grow(res_words)) != SVS_OK) return rc;
-  const int64_t small_stride = (small_rows + 3) & ~(int64_t)3, large_stride = (max_large + 3) & ~(int64_t)3;
+  const int64_t small_stride = score_stride(small_rows), large_stride = score_stride(max_large);
   if ((rc = c->scores.grow((size_t)std::max(small_stride, large_stride))) != SVS_OK) return rc;
   bool window = false;
   for (int32_t s = 0; s < nseg && !window; ++s)
@@ -4719,7 +4715,7 @@ int32_t svs_index_top_pairs(svs_index* idx, int32_t k, float* out_scores, int64_
   RefGuard guard(idx);
   std::shared_lock<std::shared_mutex> geo(idx->rw);
   const int64_t n = idx->n;
-  const int64_t np = (n + 3) & ~(int64_t)3;
+  const int64_t np = score_stride(n);
   const int64_t n_live = n - (int64_t)idx->dead_list.size();
   const int64_t pairs = n_live * (n_live - 1) / 2;
   const int count = (int)std::min<int64_t>(std::max(k, 0), pairs);
@@ -4988,7 +4984,7 @@ int32_t svs_internal_select_scores(svs_index* idx, const float* scores, int32_t 
   std::shared_lock<std::shared_mutex> geo(idx->rw);
   const int count = (int)std::min<int64_t>(k, n);
   *out_count = count;
-  const int64_t sstride = (n + 3) & ~(int64_t)3;   // float4-aligned score vectors, as plan_search lays them out
+  const int64_t sstride = score_stride(n);   // float4-aligned score vectors, as plan_search lays them out
   const bool path_a = select_path(n, count) == SelectPath::WINDOW;
   HostCall fr(idx);
   int rc;
@@ -5018,7 +5014,7 @@ int32_t svs_internal_kth_value(svs_index* idx, const float* scores, int32_t nq, 
     return fail(SVS_ERR_INVALID, "svs_internal_kth_value: nq %d, n %lld, k %d out of range (1 <= k <= n)", nq, (long long)n, k);
   RefGuard guard(idx);
   std::shared_lock<std::shared_mutex> geo(idx->rw);
-  const int64_t sstride = (n + 3) & ~(int64_t)3;
+  const int64_t sstride = score_stride(n);
   HostCall fr(idx);
   int rc;
   if ((rc = fr.open()) != SVS_OK) return rc;

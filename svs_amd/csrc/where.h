@@ -1,15 +1,9 @@
 // Predicate search (svs_index_search_where): the ORDERED filter of labels.h over up to WH_COLS u32 columns and a
 // conjunction of up to WH_MAX_TERMS terms, on the device.
 //
-// The shape is labels.h's, and its strip geometry, label_scan_kernel, label_map_rows_kernel and block_run_scan are
-// used as they are: a two-pass stream compaction over strips of LB_STRIP consecutive rows, one workgroup per strip.
-//   1. where_count_kernel: evaluates "row is live and every term holds" for the strip, counts the matches per wave
-//      (__ballot + __popcll), writes ONE count per workgroup and adds it to the call's total.
-//   2. label_scan_kernel: the counts become the strips' bases.
-//   3. where_write_kernel: evaluates the predicate again; a match's slot is the strip's base + the matches in the
-//      earlier waves of the strip + the matches before it in its own wave (mbcnt of the wave's ballots): the output is
-//      the matching local rows in strictly ascending order, the device row list enqueue_list_search takes.
-// No workgroup ever waits for another.
+// The compaction IS labels.h's: where_count_kernel and where_write_kernel are its strip_count and strip_write over a
+// WhereFilter, with label_scan_kernel between them and label_map_rows_kernel behind the search.  This file holds what
+// the predicate adds: its filter, its loader, its terms, and the wave's ballots of "row is live and every term holds".
 //
 // Per step of 256 rows a lane issues ONE 16-byte load per DISTINCT column the predicate names (WhereFilter::col_mask;
 // a column no term names is never read, a column the index does not own reads as 0 without a load) plus its nibble of
@@ -19,7 +13,7 @@
 //
 // The terms travel as a by-value kernel argument.  The sets of the IN terms with two members or more lie one after
 // another in ONE LDS image of at most LB_MAX_SET words, each sorted and without repeats (the host's work): a term
-// bisects its own slice [set0, set0 + nset).  A set of one member is a plain compare against WhereTerm::a (no LDS); an
+// bisects its own slice [set0, set0 + nset) (set_floor).  A set of one member is a plain compare against WhereTerm::a (no LDS); an
 // empty set is never true.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -60,7 +54,7 @@ struct WhereFilter {
 };
 static_assert(WH_COLS == 4 && WH_MAX_TERMS == 4, "WhereFilter names four columns and four terms");
 
-__device__ __forceinline__ void where_stage_sets(const WhereFilter& f, uint32_t* s_set) {
+__device__ __forceinline__ void strip_stage(const WhereFilter& f, uint32_t* s_set) {
   if (f.set_words == 0) return;
   for (int i = threadIdx.x; i < f.set_words; i += LB_THREADS) s_set[i] = f.set[i];
   __syncthreads();
@@ -74,15 +68,7 @@ __device__ __forceinline__ bool where_term(uint32_t v, const WhereTerm& t, const
   else if (op == WH_ANY_BITS) hit = (v & t.a) != 0u;
   else if (op == WH_ALL_BITS) hit = (v & t.a) == t.a;
   else if (t.nset < 2) hit = t.nset == 1 && v == t.a;
-  else {
-    int lo = t.set0, len = t.nset;   // the last entry <= v of the slice, if there is one, is in [lo, lo + len)
-    while (len > 1) {
-      const int half = len >> 1;
-      lo = s_set[lo + half] <= v ? lo + half : lo;
-      len -= half;
-    }
-    hit = s_set[lo] == v;
-  }
+  else hit = s_set[set_floor(s_set, t.set0, t.nset, v)] == v;
   return hit != t.negate();
 }
 
@@ -106,9 +92,9 @@ __device__ __forceinline__ void where_apply(const WhereTerm& t, const uint4 (&v)
 }
 
 // The calling wave's part of strip `blockIdx.x`: b[j][e] = the ballot of "row row0 + 256 j + 4 lane + e matches";
-// returns the wave's matches.  row0 (out) = the wave's first row.
-__device__ __forceinline__ int where_strip_ballots(const WhereFilter& f, const uint32_t* s_set, unsigned long long (&b)[LB_ITERS][4],
-                                                   int64_t* row0) {
+// returns the wave's matches.  row0 (out) = the wave's first row.  (The payload is the row: nothing is left in the uint4s.)
+__device__ __forceinline__ int strip_ballots(const WhereFilter& f, const uint32_t* s_set, unsigned long long (&b)[LB_ITERS][4],
+                                             uint4 (&)[LB_ITERS], int64_t* row0) {
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int64_t w0 = (int64_t)blockIdx.x * LB_STRIP + (int64_t)wave * LB_WAVE_ROWS;
   *row0 = w0;
@@ -149,19 +135,7 @@ __global__ __launch_bounds__(LB_THREADS) void where_count_kernel(WhereFilter f, 
                                                                  unsigned long long* __restrict__ total) {
   __shared__ uint32_t s_set[LB_MAX_SET];
   __shared__ int s_wave[LB_WAVES];
-  where_stage_sets(f, s_set);
-  unsigned long long b[LB_ITERS][4];
-  int64_t row0;
-  const int cnt = where_strip_ballots(f, s_set, b, &row0);
-  if ((threadIdx.x & 63) == 0) s_wave[threadIdx.x >> 6] = cnt;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    int sum = 0;
-#pragma unroll
-    for (int w = 0; w < LB_WAVES; ++w) sum += s_wave[w];
-    counts[blockIdx.x] = (uint32_t)sum;
-    if (sum) atomicAdd(total, (unsigned long long)sum);
-  }
+  strip_count(f, s_set, s_wave, counts, total);
 }
 
 // grid as where_count_kernel, same filter.  bases = the scanned counts; out[0 .. m) receives the matching local rows in
@@ -170,34 +144,7 @@ __global__ __launch_bounds__(LB_THREADS) void where_write_kernel(WhereFilter f, 
                                                                  uint32_t* __restrict__ out, int64_t m) {
   __shared__ uint32_t s_set[LB_MAX_SET];
   __shared__ int s_wave[LB_WAVES];
-  where_stage_sets(f, s_set);
-  unsigned long long b[LB_ITERS][4];
-  int64_t row0;
-  const int cnt = where_strip_ballots(f, s_set, b, &row0);
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  if (lane == 0) s_wave[wave] = cnt;
-  __syncthreads();
-  int64_t slot = bases[blockIdx.x];
-  for (int w = 0; w < wave; ++w) slot += s_wave[w];   // the matches in the earlier waves of the strip
-#pragma unroll
-  for (int j = 0; j < LB_ITERS; ++j) {
-    // within a step the rows ascend lane by lane, then element by element (label_write_kernel's order)
-    int below = 0, step = 0;
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-      below += (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(b[j][e] >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)b[j][e], 0u));
-      step += __popcll(b[j][e]);
-    }
-    int64_t s = slot + below;
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-      if ((b[j][e] >> lane) & 1ull) {
-        if (s < m) out[s] = (uint32_t)(row0 + j * 256 + lane * 4 + e);
-        ++s;
-      }
-    }
-    slot += step;
-  }
+  strip_write<LB_ROWS>(f, s_set, s_wave, bases, out, m);
 }
 
 }  // namespace svs

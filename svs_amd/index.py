@@ -147,6 +147,14 @@ def pack_where(where):
     return arr, len(terms), keep
 
 
+def _query_1d(query_vec) -> np.ndarray:
+    """The query of a single-query search as an f32 (D,) array."""
+    q = np.asarray(query_vec, dtype=np.float32)
+    if q.ndim != 1:
+        raise ValueError(f"query must be 1-D, got shape {q.shape}")
+    return q
+
+
 def _means(sums: np.ndarray, counts: np.ndarray) -> np.ndarray:
     """Per-label sums (L, D) f64 and counts (L,) -> the means in f64; a label with count 0 gets zeros."""
     means = np.zeros(sums.shape, dtype=np.float64)
@@ -404,9 +412,7 @@ class DeviceIndex:
         """``get_top_k(np.dot(M, query_vec), n)``: list of (score, row index),
         python float / python int, as the reference returns them."""
         assert isinstance(n, int)
-        q = np.asarray(query_vec, dtype=np.float32)
-        if q.ndim != 1:
-            raise ValueError(f"query must be 1-D, got shape {q.shape}")
+        q = _query_1d(query_vec)
         s, r = self.search_batch(q[None, :], n)
         # (tolist(): python floats -- the exact widening float(np.float32) does, src/svs/util.py:203 -- and ints in C)
         return list(zip(s[0].astype(np.float64).tolist(), r[0].tolist()))
@@ -435,9 +441,7 @@ class DeviceIndex:
     def search_within(self, query_vec: np.ndarray, n: int, rows) -> List[Tuple[float, int]]:
         """``search`` restricted to the listed rows (see ``search_batch_within``): [(score, row)]."""
         assert isinstance(n, int)
-        q = np.asarray(query_vec, dtype=np.float32)
-        if q.ndim != 1:
-            raise ValueError(f"query must be 1-D, got shape {q.shape}")
+        q = _query_1d(query_vec)
         s, r = self.search_batch_within(q[None, :], n, rows)
         return list(zip(s[0].astype(np.float64).tolist(), r[0].tolist()))
 
@@ -511,9 +515,7 @@ class DeviceIndex:
         """Every live row scoring at or above ``min_score``, best first, at most ``limit``: ([(score, row)], total),
         total = how many rows qualify (``limit=0``: only that).  See ``search_batch_above``."""
         assert isinstance(limit, int)
-        q = np.asarray(query_vec, dtype=np.float32)
-        if q.ndim != 1:
-            raise ValueError(f"query must be 1-D, got shape {q.shape}")
+        q = _query_1d(query_vec)
         s, r, total = self.search_batch_above(q[None, :], [min_score], limit)[0]
         return list(zip(s.astype(np.float64).tolist(), r.tolist())), total
 
@@ -542,16 +544,11 @@ class DeviceIndex:
             self._unpin(h)
         return out
 
-    def search_batch_labeled(self, queries: np.ndarray, n: int, labels) -> Tuple[np.ndarray, np.ndarray, int]:
-        """``search_batch`` over the live rows whose label is in ``labels`` (any order, repeats allowed, at most
-        LABELS_MAX_SET distinct ones; none: the empty set): (scores f32 (nq, count), rows i64 (nq, count), matched),
-        matched = how many rows carry such a label, count = min(max(n, 0), matched), each row ordered (score desc,
-        row desc) -- the rows and score bits ``search_batch_within`` gives for exactly those rows, with the filter run on
-        the device (svs_index_search_labeled).  ``n=0`` only counts."""
-        assert isinstance(n, int)
+    def _search_batch_filtered(self, native_search, queries, n: int, filter_arg, filter_len: int) -> Tuple[np.ndarray, np.ndarray, int]:
+        """``search_batch_labeled`` / ``search_batch_where``: ``native_search`` is the bound entry, ``filter_arg`` and
+        ``filter_len`` its two filter arguments (the caller keeps what they point to alive)."""
         q = self._queries_2d(queries)
         nq, d = q.shape
-        lab = labels_u32(labels)
         h = self._pinned_handle()
         try:
             # (clamped before allocating and before the int32 argument, as in search_batch)
@@ -560,19 +557,27 @@ class DeviceIndex:
             rows = np.empty((nq, k), dtype=np.int64)
             count, matched = C.c_int32(0), C.c_int64(0)
             # (the one call that releases the GIL)
-            _native.check(self._lib.svs_index_search_labeled(h, q.ctypes.data, nq, d, k, lab.ctypes.data, len(lab),
-                                                             scores.ctypes.data, rows.ctypes.data, C.byref(count), C.byref(matched)))
+            _native.check(native_search(h, q.ctypes.data, nq, d, k, filter_arg, filter_len,
+                                        scores.ctypes.data, rows.ctypes.data, C.byref(count), C.byref(matched)))
         finally:
             self._unpin(h)
         return self._trimmed(scores, rows, count.value) + (matched.value,)
+
+    def search_batch_labeled(self, queries: np.ndarray, n: int, labels) -> Tuple[np.ndarray, np.ndarray, int]:
+        """``search_batch`` over the live rows whose label is in ``labels`` (any order, repeats allowed, at most
+        LABELS_MAX_SET distinct ones; none: the empty set): (scores f32 (nq, count), rows i64 (nq, count), matched),
+        matched = how many rows carry such a label, count = min(max(n, 0), matched), each row ordered (score desc,
+        row desc) -- the rows and score bits ``search_batch_within`` gives for exactly those rows, with the filter run on
+        the device (svs_index_search_labeled).  ``n=0`` only counts."""
+        assert isinstance(n, int)
+        lab = labels_u32(labels)
+        return self._search_batch_filtered(self._lib.svs_index_search_labeled, queries, n, lab.ctypes.data, len(lab))
 
     def search_labeled(self, query_vec: np.ndarray, n: int, labels) -> Tuple[List[Tuple[float, int]], int]:
         """``search`` restricted to the rows whose label is in ``labels`` (see ``search_batch_labeled``):
         ([(score, row)], matched)."""
         assert isinstance(n, int)
-        q = np.asarray(query_vec, dtype=np.float32)
-        if q.ndim != 1:
-            raise ValueError(f"query must be 1-D, got shape {q.shape}")
+        q = _query_1d(query_vec)
         s, r, matched = self.search_batch_labeled(q[None, :], n, labels)
         return list(zip(s[0].astype(np.float64).tolist(), r[0].tolist())), matched
 
@@ -610,31 +615,16 @@ class DeviceIndex:
         ``search_batch_within`` gives for exactly those rows, with the filter run on the device
         (svs_index_search_where).  ``n=0`` only counts."""
         assert isinstance(n, int)
-        q = self._queries_2d(queries)
-        nq, d = q.shape
         terms, nterms, keep = pack_where(where)
-        h = self._pinned_handle()
-        try:
-            # (clamped before allocating and before the int32 argument, as in search_batch)
-            k = min(max(n, 0), self._live_rows(h))
-            scores = np.empty((nq, k), dtype=np.float32)
-            rows = np.empty((nq, k), dtype=np.int64)
-            count, matched = C.c_int32(0), C.c_int64(0)
-            # (the one call that releases the GIL)
-            _native.check(self._lib.svs_index_search_where(h, q.ctypes.data, nq, d, k, terms, nterms,
-                                                           scores.ctypes.data, rows.ctypes.data, C.byref(count), C.byref(matched)))
-        finally:
-            self._unpin(h)
+        out = self._search_batch_filtered(self._lib.svs_index_search_where, queries, n, terms, nterms)
         del keep
-        return self._trimmed(scores, rows, count.value) + (matched.value,)
+        return out
 
     def search_where(self, query_vec: np.ndarray, n: int, where) -> Tuple[List[Tuple[float, int]], int]:
         """``search`` restricted to the rows on which every term of ``where`` holds (see ``search_batch_where``):
         ([(score, row)], matched)."""
         assert isinstance(n, int)
-        q = np.asarray(query_vec, dtype=np.float32)
-        if q.ndim != 1:
-            raise ValueError(f"query must be 1-D, got shape {q.shape}")
+        q = _query_1d(query_vec)
         s, r, matched = self.search_batch_where(q[None, :], n, where)
         return list(zip(s[0].astype(np.float64).tolist(), r[0].tolist())), matched
 
@@ -694,9 +684,7 @@ class DeviceIndex:
                         n: Optional[int] = None) -> List[Tuple[int, float, int, int]]:
         """The breakdown of one query over ``labels``: [(label, score of its best row, that row, rows of the label at or
         above ``min_score``)], best label first; labels without such a row are absent.  See ``search_batch_by_label``."""
-        q = np.asarray(query_vec, dtype=np.float32)
-        if q.ndim != 1:
-            raise ValueError(f"query must be 1-D, got shape {q.shape}")
+        q = _query_1d(query_vec)
         l, s, r, t, _ = self.search_batch_by_label(q[None, :], labels, None if min_score is None else [min_score], n)[0]
         return list(zip(l.tolist(), s.astype(np.float64).tolist(), r.tolist(), t.tolist()))
 
@@ -735,9 +723,7 @@ class DeviceIndex:
         """The ``n`` best rows of one query with at most one row per value of column ``column``: ([(score, row,
         value)], groups), best first.  See ``search_batch_collapsed``."""
         assert isinstance(n, int)
-        q = np.asarray(query_vec, dtype=np.float32)
-        if q.ndim != 1:
-            raise ValueError(f"query must be 1-D, got shape {q.shape}")
+        q = _query_1d(query_vec)
         s, r, v, counts, groups = self.search_batch_collapsed(q[None, :], n, column, zero)
         c = int(counts[0])
         return list(zip(s[0, :c].astype(np.float64).tolist(), r[0, :c].tolist(), v[0, :c].tolist())), int(groups[0])
@@ -940,9 +926,7 @@ class DeviceIndex:
                        lam: float = 0.5) -> List[Tuple[float, int, float]]:
         """``search`` re-ranked for diversity (see ``search_batch_diverse``): [(score, row, redundancy)] in pick order."""
         assert isinstance(n, int)
-        q = np.asarray(query_vec, dtype=np.float32)
-        if q.ndim != 1:
-            raise ValueError(f"query must be 1-D, got shape {q.shape}")
+        q = _query_1d(query_vec)
         s, r, red = self.search_batch_diverse(q[None, :], n, fetch_k, lam)
         return list(zip(s[0].astype(np.float64).tolist(), r[0].tolist(), red[0].astype(np.float64).tolist()))
 
@@ -1022,9 +1006,7 @@ class DeviceIndex:
 
     def scores(self, query_vec: np.ndarray) -> np.ndarray:
         """The raw ``np.dot(M, q)`` vector, f32 (N,)."""
-        q = np.ascontiguousarray(query_vec, dtype=np.float32)
-        if q.ndim != 1:
-            raise ValueError(f"query must be 1-D, got shape {q.shape}")
+        q = _query_1d(np.ascontiguousarray(query_vec, dtype=np.float32))
         h = self._pinned_handle()
         try:
             # The library writes one f32 per row the HANDLE holds when the call runs, never more than the capacity

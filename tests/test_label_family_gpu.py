@@ -15,6 +15,9 @@ from types import SimpleNamespace
 import numpy as np
 import pytest
 
+import by_label_model
+import collapse_model
+
 D = 32
 SIZES = [1023, 1025, 2049, 4099]
 LS_STRIP = 1024                                       # label_sums.h (not exported; the other two are read below)
@@ -179,3 +182,73 @@ def test_timing_hooks_follow_one_rule(case):
         assert readings() == (-1.0, -1.0)
     finally:
         k.idx.set_timing(0)
+
+
+# -- the wave fold that by_label_reduce_kernel and collapse_reduce_kernel share ---------------------------------------
+FOLD_D = 64
+FOLD_WAVE_ROWS = 256      # one call of the fold: the rows r of one 256-row block with one r % 4; lane = r % 256 // 4
+
+
+def _fold_corpus(n):
+    """(m, q, values, ties): blocks of 256 rows take three layouts in turn.  Block b % 3 == 0: every lane of a wave
+    holds value 1000 + b.  == 1: lane l holds 100 + l, so no two lanes of a wave share a value (and every such block
+    shares them with the others).  == 2: the even lanes hold 2000 + b, the leader's, every odd lane l holds
+    3000 + 64 b + l.  In every block of the first and the third layout two rows on even lanes that are not lane 0, with
+    one r % 4, are ONE vector close to the query: their group's largest score twice in one call of the fold, away from
+    the leader.  ties: [(smaller row, larger row)]."""
+    rng = np.random.default_rng(8229)
+    unit = lambda v: (v / np.linalg.norm(v, axis=-1, keepdims=True)).astype(np.float32)
+    m = unit(rng.standard_normal((n, FOLD_D)))
+    q = unit(rng.standard_normal(FOLD_D))
+    r = np.arange(n)
+    b, lane = r // FOLD_WAVE_ROWS, r % FOLD_WAVE_ROWS // 4
+    values = np.where(b % 3 == 0, 1000 + b, np.where(b % 3 == 1, 100 + lane, np.where(lane % 2 == 0, 2000 + b, 3000 + 64 * b + lane)))
+    ties = []
+    for blk in range((n + FOLD_WAVE_ROWS - 1) // FOLD_WAVE_ROWS):
+        if blk % 3 == 1:
+            continue
+        lanes = min(64, (n - blk * FOLD_WAVE_ROWS + 3) // 4)
+        e = blk % 4 if lanes == 64 else 0
+        la, lb = (2 + 2 * (blk % 5), lanes - 2 - 2 * (blk % 7)) if lanes == 64 else (2, (lanes - 1) // 2 * 2)
+        r1, r2 = (blk * FOLD_WAVE_ROWS + 4 * l + e for l in (la, lb))
+        assert 0 < la < lb and r2 < n and values[r1] == values[r2] == values[blk * FOLD_WAVE_ROWS + e]
+        m[r1] = m[r2] = unit(q + 0.05 * (1 + blk) / 40 * unit(rng.standard_normal(FOLD_D)))
+        ties.append((r1, r2))
+    return m, q, values.astype(np.uint32), ties
+
+
+@pytest.mark.gpu
+def test_both_callers_of_the_wave_fold_agree_with_their_models(strips):
+    """search_by_label and search_collapsed over one corpus of 2 * BL_STRIP + 37 f32 rows whose column puts a wave's
+    lanes all on one value, all on different values, and half on the leader's value with the group's largest score on two
+    later lanes (_fold_corpus): labels, values, rows, totals, groups and score bits equal the numpy models' over the
+    library's own scores, and every planted tie goes to the larger row."""
+    import svs_amd
+    n = 2 * strips[2] + 37
+    m, q, values, ties = _fold_corpus(n)
+    assert len(ties) >= 2 * (n // FOLD_WAVE_ROWS) // 3 and {r1 // FOLD_WAVE_ROWS % 3 for r1, _ in ties} == {0, 2}
+    idx = svs_amd.DeviceIndex(m, dtype="f32")
+    try:
+        idx.set_labels(values)
+        s = idx.scores(q)
+        for r1, r2 in ties:     # the pair is the best of its group, with one score
+            group = np.nonzero(values == values[r1])[0]
+            assert s[r1].view(np.uint32) == s[r2].view(np.uint32) and s[r1] > np.delete(s[group], np.searchsorted(group, [r1, r2])).max()
+        label_set = np.unique(values)
+        assert len(label_set) <= 1024
+        bits = lambda a: np.ascontiguousarray(a, dtype=np.float32).view(np.uint32).tolist()
+        # by label: every group, best first
+        l, sc, rows, totals, groups = idx.search_batch_by_label(q[None, :], label_set, None, len(label_set))[0]
+        el, es, er, et, eg = by_label_model.by_label(s, values, None, label_set, None, len(label_set))
+        assert groups == eg == len(label_set)
+        assert (l.tolist(), rows.tolist(), totals.tolist(), bits(sc)) == (el.tolist(), er.tolist(), et.tolist(), bits(es))
+        assert {r2 for _, r2 in ties} <= set(rows.tolist()) and not {r1 for r1, _ in ties} & set(rows.tolist())
+        # collapsed on the same column: one row per value
+        for zero in ("single", "group"):
+            cs, cr, cv, counts, cgroups = idx.search_batch_collapsed(q[None, :], len(label_set), 0, zero)
+            es, er, ev, eg = collapse_model.collapsed(s, values, None, zero == "single", len(label_set))
+            assert int(cgroups[0]) == eg == len(label_set) and int(counts[0]) == eg
+            assert (cr[0].tolist(), cv[0].tolist(), bits(cs[0])) == (er.tolist(), ev.tolist(), bits(es))
+            assert {r2 for _, r2 in ties} <= set(cr[0].tolist()) and not {r1 for r1, _ in ties} & set(cr[0].tolist())
+    finally:
+        idx.release()
