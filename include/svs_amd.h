@@ -586,6 +586,62 @@ int32_t svs_index_search_collapsed(svs_index* idx, const float* queries, int32_t
                                    float* out_scores, int64_t* out_rows, uint32_t* out_values /* all three: stride k */,
                                    int32_t* out_counts /* nq */, int64_t* out_groups /* nq, or NULL */);
 
+/* Group-combined search: the top k GROUPS (parent documents) ranked against several vectors at once, where a group's
+ * score against each vector is its best row's -- "the documents that cover both facets, wherever in the document":
+ * chunk 3 may answer the first facet and chunk 9 the second.  svs_index_search_combined combines per ROW (one chunk
+ * must cover everything); svs_index_search_collapsed takes one vector.  This is their product, per group.
+ * Exact definition.  For combined query q (m vectors, weights, op: svs_index_search_combined's) let s_j be the vector
+ * svs_index_scores_n(idx, v_j) returns at that moment (the unscreened single-query kernel of the index's dtype), L
+ * the live local rows and v[r] = column[column][r].  Groups and the two zero modes are svs_index_search_collapsed's:
+ * row r's group is v[r]; under SVS_COLLAPSE_ZERO_SINGLE a row with v[r] == 0 is a group of its own.
+ *   M_j(G) = max over r in G and L of score_key(s_j[r])       a 32-bit key (svs_amd/csrc/keys.h), of the UNWEIGHTED
+ *                                                              score: the chunk of G that matches vector j best
+ *   c(G)   = combine_finish(fold over j = 0 .. m-1 of combine_step(acc, key_score(M_j(G)), w_j, op), op), from
+ *            combine_init(op): svs_amd/csrc/combine.h's one implementation of MAX, MIN and SUM over the m per-vector
+ *            maxima; t_j = w_j * key_score(M_j) is ONE f32 multiplication, the additions run in vector order and are
+ *            never contracted into a fused multiply-add; weights == NULL: every weight is 1.0f
+ *   rep(G) = the row of G and L with the largest make_key(c_row[r], r), c_row = svs_index_search_combined's per-row
+ *            combined score for the same vectors, weights and op: the row the row-level search would rank first
+ *   W      = the groups that have a live row
+ *   out_groups[q]   = |W|, always exact; may be NULL
+ *   out_counts[q]   = min(max(k, 0), |W|)
+ *   out_*[q*k + t], t < out_counts[q]   the groups in descending make_key(c(G), rep(G)): out_scores = c(G) (a NaN comes
+ *                     back as the quiet NaN 0x7fc00000, -0.0 as +0.0, as from every search), out_rows = row_offset +
+ *                     rep(G), out_values = v[rep(G)].  Entries past the count are not touched.
+ * Every reduction is a maximum of integer keys or a fixed-order f32 chain over m numbers: the answer is bit-reproducible
+ * and does not depend on nq, on the other queries of the call or on how the device schedules the work.
+ * Three identities.  (1) m == 1, weights == NULL, SVS_COMBINE_MAX: svs_index_search_collapsed's result -- rows, values,
+ * groups and score bits.  (2) Every group a single row (a column never set under ZERO_SINGLE): svs_index_search_combined's
+ * result for every op and weight (a score of -0.0 arrives canonicalised as +0.0 at every stage).  (3) SVS_COMBINE_MAX with
+ * all weights >= 0: collapsing the row-level combined vector -- the multiplication is monotone, so the maximum over rows
+ * and the maximum over vectors commute.
+ * Errors: everything is validated before anything is launched, and a failing call writes no output.  All are
+ * SVS_ERR_INVALID and name this function: nq < 0, m outside 1 .. SVS_COMBINE_MAX_VECTORS, d != index d, an unknown op,
+ * null vectors with nq > 0, a NaN or infinite weight, a column outside [0, SVS_COLUMNS_MAX), an unknown zero_mode, null
+ * out_counts, null out_scores / out_rows / out_values with k > 0 and nq > 0.  k <= 0 is a COUNT-ONLY call: the groups
+ * are counted, every count is 0, the three result pointers may be NULL.  nq == 0 -> SVS_OK, nothing launched; an empty
+ * index -> SVS_OK, counts and groups 0, nothing launched.
+ * Cost per combined query.  The score pass: row lengths with a one-shot single-query kernel (see
+ * svs_index_search_combined) take ONE fused multi-score pass -- every wave loads its rows once, streams the m vectors
+ * through them and stores m scores per row --, every other row length m single-query passes.  Then two passes over the m
+ * score vectors, the column and the bitmap (4 m + 4 bytes per row each): one finds every group's slot in
+ * svs_index_search_collapsed's open-addressing table and raises its representative key (64-bit integer max) and its m
+ * per-vector keys (32-bit integer max; no float atomics, nothing waits or spins), one writes c(G) at every representative
+ * row and -inf everywhere else and counts; two fills; the top-k stage with k' = min(k, live rows); one tiny launch for
+ * the values.  The host waits once per call.  (A group whose c(G) is -inf itself ties with the struck rows, as in
+ * svs_index_search_collapsed.)  Memory per search context: the collapsed search's table (16 bytes per slot) plus 4 bytes
+ * per slot and vector, a power of two >= 2 x rows slots -- per million rows 2^21 slots, 32 MB + 8 MB per vector: 40 MB
+ * at m = 1, 96 MB at m = 8 (up to twice that just above a power of two); m score vectors of 4 bytes per row.
+ * Blocking; re-entrant on one handle; holds a reference and the geometry lock shared; waits for pending staging
+ * copies; never goes through the coalescer, the run-ahead pipelines or shared passes: all as svs_index_search_above.
+ * Out of scope: svs_multi / row-sharded corpora, a device-pointer variant, more than SVS_COMBINE_MAX_VECTORS vectors,
+ * mean or count aggregates over a group, predicates and row lists, the screened and the batched GEMM score routes. */
+int32_t svs_index_search_collapsed_combined(svs_index* idx, const float* vectors /* host, [nq][m][d] */, int32_t nq, int32_t m, int32_t d,
+                                            const float* weights /* [nq][m] or NULL */, int32_t op /* SVS_COMBINE_* */, int32_t k,
+                                            int32_t column, int32_t zero_mode /* SVS_COLLAPSE_ZERO_* */,
+                                            float* out_scores, int64_t* out_rows, uint32_t* out_values /* all three: stride k */,
+                                            int32_t* out_counts /* nq */, int64_t* out_groups /* nq, or NULL */);
+
 /* Nearest-vector assignment: for every stored row of a range, which of c given vectors it scores best against -- the
  * transposed question of a search ("which topic is each document about", the assignment step of a clustering, coarse
  * centroids for probing), answered where the corpus lies; optionally the answer is written into the label column, so

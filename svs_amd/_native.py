@@ -122,6 +122,8 @@ SIGNATURES = {
     "svs_index_search_combined": (C.c_int32, [_P, _P, C.c_int32, C.c_int32, C.c_int32, _P, C.c_int32, C.c_int32, _P, _P, C.POINTER(C.c_int32)]),
     "svs_index_search_by_label": (C.c_int32, [_P, _P, C.c_int32, C.c_int32, _P, C.c_int32, _P, C.c_int32, _P, _P, _P, _P, _P, _P]),
     "svs_index_search_collapsed": (C.c_int32, [_P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P, _P, _P]),
+    "svs_index_search_collapsed_combined": (C.c_int32, [_P, _P, C.c_int32, C.c_int32, C.c_int32, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
+                                                        _P, _P, _P, _P, _P]),
     "svs_index_assign": (C.c_int32, [_P, _P, C.c_int32, C.c_int32, C.c_int64, C.c_int64, _P, _P, _P, _P]),
     "svs_index_label_sums": (C.c_int32, [_P, _P, C.c_int32, C.c_int64, C.c_int64, _P, _P, _P]),
     "svs_index_search_diverse": (C.c_int32, [_P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_float, _P, _P, _P,
@@ -163,6 +165,9 @@ INTERNAL = {
     "svs_internal_assign_kernel_ms": (C.c_int32, [C.POINTER(C.c_double)]),
     "svs_internal_label_sums_kernel_ms": (C.c_int32, [C.POINTER(C.c_double)]),
     "svs_internal_combined_scores": (C.c_int32, [_P, _P, C.c_int32, C.c_int32, _P, C.c_int32, C.c_int32, _P, C.c_int64]),
+    "svs_internal_multi_scores": (C.c_int32, [_P, _P, C.c_int32, C.c_int32, C.c_int32, _P, C.c_int64]),
+    "svs_internal_collapsed_combined_kernel_ms": (C.c_int32, [C.POINTER(C.c_double)]),
+    "svs_internal_score_pass_ms": (C.c_int32, [C.POINTER(C.c_double)]),
     "svs_internal_compact": (C.c_int32, [_P, C.c_int64, _P, C.c_int64, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
 }
 

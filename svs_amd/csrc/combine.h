@@ -211,4 +211,112 @@ __global__ __launch_bounds__(WPB * 64) void combine_fp8_kernel(const uint8_t* __
   if (lane < R && row < n) out[row] = res;
 }
 
+// ---- multi-score pass (svs_index_search_collapsed_combined, collapse_combine.h) ------------------------------------------
+// The three fused kernels again, with one difference: vector t's score of row row0 + r is not folded, it is STORED, to
+// out[t * sstride + row] -- m score vectors, each with the bits of a single-query pass of its own.  The geometry, the
+// loads and the arithmetic are the combine kernels'; no weights, no op.  Kernels of their own, not a template flag on
+// the ones above: those keep their names and their register allocation.  No LDS, no scratch: the rows plus one
+// vector's slice, as above; lane r < R stores one float per vector (m * R dwords per wave against R rows loaded).
+template <int NSTEP, int R, int WPB>
+__global__ __launch_bounds__(WPB * 64) void multi_score_f32_kernel(const v4f* __restrict__ M, const v4f* __restrict__ q, int m,
+                                                                   float* __restrict__ out, int64_t sstride, int64_t n) {
+  constexpr int LD4 = NSTEP * 64;
+  const int lane = threadIdx.x & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int64_t row0 = ((int64_t)blockIdx.x * WPB + wave) * R;
+  if (row0 >= n) return;
+  v4f buf[R][NSTEP];
+#pragma unroll
+  for (int r = 0; r < R; ++r) {
+    int64_t row = row0 + r;
+    row = row < n ? row : n - 1;
+    const v4f* p = M + row * LD4 + lane;
+#pragma unroll
+    for (int j = 0; j < NSTEP; ++j) buf[r][j] = ldg4<true>(p + j * 64);
+  }
+  const int64_t row = row0 + lane;
+  const bool writer = lane < R && row < n;
+#pragma unroll 1
+  for (int t = 0; t < m; ++t) {
+    v4f qv[NSTEP];
+#pragma unroll
+    for (int j = 0; j < NSTEP; ++j) qv[j] = q[t * LD4 + j * 64 + lane];
+    float res = 0.f;
+#pragma unroll
+    for (int r = 0; r < R; ++r) {
+      const float s = row_dot_f32<NSTEP>(buf[r], qv);
+      res = lane == r ? s : res;
+    }
+    if (writer) out[(int64_t)t * sstride + row] = res;
+  }
+}
+
+template <int NSTEP, int R, int WPB>
+__global__ __launch_bounds__(WPB * 64) void multi_score_f16_kernel(const u32x4* __restrict__ M, const v4f* __restrict__ q, int m,
+                                                                   float* __restrict__ out, int64_t sstride, int64_t n) {
+  constexpr int LD8 = NSTEP * 64;
+  const int lane = threadIdx.x & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int64_t row0 = ((int64_t)blockIdx.x * WPB + wave) * R;
+  if (row0 >= n) return;
+  u32x4 buf[R][NSTEP];
+  load_rows_f16<NSTEP, R>(buf, M, row0, n, lane);
+  const int64_t row = row0 + lane;
+  const bool writer = lane < R && row < n;
+#pragma unroll 1
+  for (int t = 0; t < m; ++t) {
+    const v4f* qt = q + (int64_t)t * (2 * LD8);
+    u32x4 qv[NSTEP];
+#pragma unroll
+    for (int j = 0; j < NSTEP; ++j) qv[j] = round_query8(qt[(j * 64 + lane) * 2], qt[(j * 64 + lane) * 2 + 1]);
+    float res = 0.f;
+#pragma unroll
+    for (int r = 0; r < R; ++r) {
+      const float s = row_dot_f16<NSTEP>(buf[r], qv);
+      res = lane == r ? s : res;
+    }
+    if (writer) out[(int64_t)t * sstride + row] = res;
+  }
+}
+
+template <int NSTEP, int LB, int R, int WPB>
+__global__ __launch_bounds__(WPB * 64) void multi_score_fp8_kernel(const uint8_t* __restrict__ M, const float* __restrict__ row_scales,
+                                                                   const uint8_t* __restrict__ q8, const float* __restrict__ q_scales, int m,
+                                                                   float* __restrict__ out, int64_t sstride, int64_t n) {
+  typedef typename Fp8Chunk<LB>::type chunk_t;
+  constexpr int64_t LDB = (int64_t)NSTEP * 64 * LB;
+  const int lane = threadIdx.x & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int64_t row0 = ((int64_t)blockIdx.x * WPB + wave) * R;
+  if (row0 >= n) return;
+  chunk_t buf[R][NSTEP];
+  float rs[R];
+#pragma unroll
+  for (int r = 0; r < R; ++r) {
+    int64_t row = row0 + r;
+    row = row < n ? row : n - 1;
+    const chunk_t* p = (const chunk_t*)(M + row * LDB) + lane;
+#pragma unroll
+    for (int j = 0; j < NSTEP; ++j) buf[r][j] = __builtin_nontemporal_load(p + j * 64);
+    rs[r] = row_scales[row];
+  }
+  const int64_t row = row0 + lane;
+  const bool writer = lane < R && row < n;
+#pragma unroll 1
+  for (int t = 0; t < m; ++t) {
+    const chunk_t* qt = (const chunk_t*)(q8 + (int64_t)t * LDB);
+    chunk_t qv[NSTEP];
+#pragma unroll
+    for (int j = 0; j < NSTEP; ++j) qv[j] = qt[j * 64 + lane];
+    const float sq = q_scales[t];
+    float res = 0.f;
+#pragma unroll
+    for (int r = 0; r < R; ++r) {
+      const float s = row_dot_fp8<NSTEP, LB>(buf[r], qv) * rs[r] * sq;
+      res = lane == r ? s : res;
+    }
+    if (writer) out[(int64_t)t * sstride + row] = res;
+  }
+}
+
 }  // namespace svs

@@ -157,6 +157,22 @@ int32_t svs_internal_label_sums_kernel_ms(double* out);
  * fused kernel (SVS_ERR_UNSUPPORTED where the row length has none), 2 = m passes and combine_scores_kernel (tests). */
 int32_t svs_internal_combined_scores(svs_index* idx, const float* vectors, int32_t m, int32_t d, const float* weights, int32_t op,
                                      int32_t route, float* out, int64_t capacity);
+/* The m unmasked score vectors of ONE combined query (m vectors [m][d]) over all n local rows, vector j into
+ * out[j * n .. (j + 1) * n) (capacity >= m * n floats): what svs_index_search_collapsed_combined's group stage reads.
+ * route: 0 = the route's choice, 1 = the fused multi-score kernel (SVS_ERR_UNSUPPORTED where the row length has none),
+ * 2 = m single-query passes (tests).  Every route gives the bits of svs_index_scores_n per vector. */
+int32_t svs_internal_multi_scores(svs_index* idx, const float* vectors, int32_t m, int32_t d, int32_t route, float* out, int64_t capacity);
+/* Milliseconds between the HIP events around the score pass (the fused kernel, or the m passes and what follows them) in
+ * the calling thread's last svs_internal_combined_scores or svs_internal_multi_scores, recorded while
+ * svs_index_set_timing is on for the handle; -1 when that call recorded none (tools/collapsed_combined_time.py: the
+ * multi-score kernel against the combine kernel of the same shape and m). */
+int32_t svs_internal_score_pass_ms(double* out);
+/* Milliseconds between the HIP events around the stages of the LAST query of the calling thread's last
+ * svs_index_search_collapsed_combined, recorded while svs_index_set_timing is on for the handle: out[0] the score
+ * pass(es), out[1] cc_reduce_kernel, out[2] cc_mark_kernel, out[3] the fills of the table and the keys, out[4] the top-k
+ * stage; -1 where that call recorded none (tools/collapsed_combined_time.py).  The kernels share the geometry
+ * svs_internal_collapse_geometry reports. */
+int32_t svs_internal_collapsed_combined_kernel_ms(double* out);
 /* multi.hip -> svs_amd.hip: carries a worker thread's error message over to the caller's thread */
 int32_t svs_internal_set_error(int32_t code, const char* msg);
 #ifdef __cplusplus

@@ -48,6 +48,7 @@
 #include "where.h"
 #include "by_label.h"
 #include "collapse.h"
+#include "collapse_combine.h"
 #include "assign.h"
 #include "label_sums.h"
 
@@ -280,6 +281,10 @@ struct Ctx {
   bool cl_clean = true;
   DevBuf<unsigned long long> cl_cnt; PinBuf<unsigned long long> cl_cnt_pin;
   PinBuf<uint32_t> cl_val_pin;
+  // svs_index_search_collapsed_combined (collapse_combine.h): beside cl_tab, m per-vector keys for every slot, EMPTY
+  // (all zero) between queries and between calls under a flag of its own -- svs_index_search_collapsed repairs only cl_tab
+  DevBuf<uint32_t> cc_keys;
+  bool cc_clean = true;
   // svs_index_assign (assign.h): the call's vectors in the index's storage format (rows of ld elements; fp8: their
   // scales), the per-row results and the counts.  The f32 vectors go up through q_pin / q_dev.
   DevBuf<uint8_t> as_vec;       DevBuf<float> as_vec_scales;
@@ -2390,6 +2395,70 @@ int enqueue_combined_scores(const svs_index* idx, Ctx* c, const CombineRoute& r,
   return SVS_OK;
 }
 
+template <int NSTEP>
+constexpr KernelName kMultiScoreF32Name = kernel_name("multi_score_f32_kernel", NSTEP, f32_rows_r(NSTEP), f32_rows_wpb(NSTEP));
+template <int NSTEP>
+constexpr KernelName kMultiScoreF16Name = kernel_name("multi_score_f16_kernel", NSTEP, f16_rows_r(NSTEP), f16_rows_wpb(NSTEP));
+template <int NSTEP, int LB, int R>
+constexpr KernelName kMultiScoreFp8Name = kernel_name("multi_score_fp8_kernel", NSTEP, LB, R, 16);
+
+// The m vectors' scores of one combined query into c->scores[j * sstride .. j * sstride + n), j < m, unmasked: the fused
+// multi-score kernel of the route (combine.h), or m passes of `single`.  v: the m vectors on the device, [m][d].
+// c->scores holds m * sstride floats.  (The staging is enqueue_combined_scores': one decision, two families of kernels.)
+int enqueue_multi_scores(const svs_index* idx, Ctx* c, const CombineRoute& r, const float* v, int m, int64_t sstride, hipStream_t st) {
+  const int64_t n = idx->n;
+  int rc;
+  if (!r.fused) {
+    for (int j = 0; j < m; ++j) {
+      launch_record("gemv", n, 1);
+      if ((rc = launch_scores(idx, c, r.single, v + (size_t)j * idx->d, c->scores + (size_t)j * sstride, st)) != SVS_OK) return rc;
+    }
+    return SVS_OK;
+  }
+  if (r.single.family == SingleRoute::FP8_ONESHOT) {
+    if ((rc = stage_queries_fp8(idx, c, v, m, m, false, st)) != SVS_OK) return rc;
+    for_fp8_oneshot(idx->ld, [&](auto ns, auto lb, auto rr) {
+      constexpr int NSTEP = ns(), LB = lb(), R = rr();
+      launch_record(kMultiScoreFp8Name<NSTEP, LB, R>.s, n, m);
+      hipLaunchKernelGGL((multi_score_fp8_kernel<NSTEP, LB, R, 16>), dim3((unsigned)((n + R * 16 - 1) / (R * 16))), dim3(16 * 64), 0, st, (const uint8_t*)idx->rows,
+                         (const float*)idx->row_scales, (const uint8_t*)c->q8.p, (const float*)c->q8s.p, m, c->scores.p, sstride, n);
+    });
+    return SVS_OK;
+  }
+  const float* q = v;
+  if (idx->ld != idx->d || (((uintptr_t)v) & 15) != 0) {
+    if ((rc = c->q16.grow((size_t)GQ * idx->ld)) != SVS_OK) return rc;
+    HIP_TRY(hipMemsetAsync(c->q16, 0, (size_t)m * idx->ld * sizeof(float), st));
+    HIP_TRY(hipMemcpy2DAsync(c->q16, (size_t)idx->ld * sizeof(float), v, (size_t)idx->d * sizeof(float), (size_t)idx->d * sizeof(float), (size_t)m,
+                             hipMemcpyDeviceToDevice, st));
+    q = c->q16;
+  }
+  if (r.single.family == SingleRoute::F16_ONESHOT) {
+    for_f16_oneshot(r.single.geo, [&](auto ns) {
+      constexpr int NSTEP = ns(), R = f16_rows_r(NSTEP), WPB = f16_rows_wpb(NSTEP);
+      launch_record(kMultiScoreF16Name<NSTEP>.s, n, m);
+      hipLaunchKernelGGL((multi_score_f16_kernel<NSTEP, R, WPB>), dim3((unsigned)((n + R * WPB - 1) / (R * WPB))), dim3(WPB * 64), 0, st, (const u32x4*)idx->rows,
+                         (const v4f*)q, m, c->scores.p, sstride, n);
+    });
+    return SVS_OK;
+  }
+  switch (r.single.geo) {
+#define SVS_ROWS_CASE(N)                                                                                                                        \
+  case N: {                                                                                                                                     \
+    constexpr int R = f32_rows_r(N), WPB = f32_rows_wpb(N);                                                                                     \
+    launch_record(kMultiScoreF32Name<N>.s, n, m);                                                                                               \
+    hipLaunchKernelGGL((multi_score_f32_kernel<N, R, WPB>), dim3((unsigned)((n + R * WPB - 1) / (R * WPB))), dim3(WPB * 64), 0, st,             \
+                       (const v4f*)idx->rows, (const v4f*)q, m, c->scores.p, sstride, n);                                                       \
+    break;                                                                                                                                      \
+  }
+    SVS_ROWS_CASE(1) SVS_ROWS_CASE(2) SVS_ROWS_CASE(3) SVS_ROWS_CASE(4) SVS_ROWS_CASE(5) SVS_ROWS_CASE(6) SVS_ROWS_CASE(7) SVS_ROWS_CASE(8)
+    SVS_ROWS_CASE(9) SVS_ROWS_CASE(10) SVS_ROWS_CASE(11) SVS_ROWS_CASE(12) SVS_ROWS_CASE(13) SVS_ROWS_CASE(14) SVS_ROWS_CASE(15) SVS_ROWS_CASE(16)
+#undef SVS_ROWS_CASE
+    default: return fail(SVS_ERR_INVALID, "internal: no fused multi-score kernel for ld %d", idx->ld);
+  }
+  return SVS_OK;
+}
+
 // The arguments every combined entry takes, checked in the header's order; `entry` names the caller
 int check_combined_args(const char* entry, const svs_index* idx, const float* vectors, int64_t nq, int32_t m, int32_t d, const float* weights, int32_t op) {
   if (nq < 0) return fail(SVS_ERR_INVALID, "%s: nq must be >= 0", entry);
@@ -2874,6 +2943,8 @@ int upload_queries(Ctx* c, const float* queries, size_t qn, hipStream_t st) {
 thread_local double g_assign_kernel_ms = -1.0;       // svs_internal_assign_kernel_ms
 thread_local double g_label_sums_kernel_ms = -1.0;   // svs_internal_label_sums_kernel_ms
 thread_local double g_collapse_ms[4] = {-1.0, -1.0, -1.0, -1.0};   // svs_internal_collapse_kernel_ms: reduce, mark, clear, select
+thread_local double g_collapsed_combined_ms[5] = {-1.0, -1.0, -1.0, -1.0, -1.0};   // svs_internal_collapsed_combined_kernel_ms: scores, reduce, mark, clear, select
+thread_local double g_score_pass_ms = -1.0;          // svs_internal_score_pass_ms: the score pass of the last combined_scores / multi_scores hook call
 int report_ms(double* out, double ms) {
   if (!out) return fail(SVS_ERR_INVALID, "null output");
   *out = ms;
@@ -3958,6 +4029,7 @@ int32_t svs_index_search_combined(svs_index* idx, const float* vectors, int32_t 
 int32_t svs_internal_combined_scores(svs_index* idx, const float* vectors, int32_t m, int32_t d, const float* weights, int32_t op, int32_t route,
                                      float* out, int64_t capacity) {
   launch_reset();
+  g_score_pass_ms = -1.0;
   if (!idx) return fail(SVS_ERR_INVALID, "svs_internal_combined_scores: null index");
   RefGuard guard(idx);
   std::shared_lock<std::shared_mutex> geo(idx->rw);
@@ -3977,10 +4049,15 @@ int32_t svs_internal_combined_scores(svs_index* idx, const float* vectors, int32
   const size_t vn = (size_t)m * d;
   if ((rc = c->scores.grow((size_t)(r.fused ? 1 : m) * sstride)) != SVS_OK) return rc;
   if ((rc = upload_combined(c, vectors, weights, vn, (size_t)m, st)) != SVS_OK) return rc;
+  const TimedSpan t_pass(idx->timing.load() > 0);
+  t_pass.begin(st);
   if ((rc = enqueue_combined_scores(idx, c, r, c->q_dev, c->q_dev + vn, m, op, sstride, st)) != SVS_OK) return rc;
+  t_pass.end(st);
   if ((rc = fr.launched("combined_scores")) != SVS_OK) return rc;
   HIP_TRY(hipMemcpyAsync(out, c->scores, (size_t)n * sizeof(float), hipMemcpyDeviceToHost, st));
-  return fr.wait();
+  if ((rc = fr.wait()) != SVS_OK) return rc;
+  g_score_pass_ms = t_pass.ms();
+  return SVS_OK;
 }
 
 int32_t svs_internal_by_label_geometry(int32_t* out) {
@@ -4175,6 +4252,163 @@ int32_t svs_index_search_collapsed(svs_index* idx, const float* queries, int32_t
   g_collapse_ms[1] = t_mark.ms();
   g_collapse_ms[2] = t_clear.ms();
   g_collapse_ms[3] = ks > 0 ? t_select.ms() : -1.0;
+  return SVS_OK;
+}
+
+// ---- svs_index_search_collapsed_combined (collapse_combine.h)
+int32_t svs_internal_collapsed_combined_kernel_ms(double* out) {
+  if (!out) return fail(SVS_ERR_INVALID, "null output");
+  for (int i = 0; i < 5; ++i) out[i] = g_collapsed_combined_ms[i];
+  return SVS_OK;
+}
+
+int32_t svs_internal_score_pass_ms(double* out) { return report_ms(out, g_score_pass_ms); }
+
+int32_t svs_internal_multi_scores(svs_index* idx, const float* vectors, int32_t m, int32_t d, int32_t route, float* out, int64_t capacity) {
+  launch_reset();
+  g_score_pass_ms = -1.0;
+  if (!idx) return fail(SVS_ERR_INVALID, "svs_internal_multi_scores: null index");
+  RefGuard guard(idx);
+  std::shared_lock<std::shared_mutex> geo(idx->rw);
+  int rc = check_combined_args("svs_internal_multi_scores", idx, vectors, 1, m, d, nullptr, SVS_COMBINE_MAX);
+  if (rc != SVS_OK) return rc;
+  if (route < 0 || route > 2) return fail(SVS_ERR_INVALID, "svs_internal_multi_scores: route %d", (int)route);
+  const int64_t n = idx->n;
+  if (!out || capacity < (int64_t)m * n)
+    return fail(SVS_ERR_INVALID, "svs_internal_multi_scores: %d vectors over %lld rows, the output holds %lld floats", (int)m, (long long)n, (long long)capacity);
+  if (n == 0) return SVS_OK;
+  const CombineRoute r = combine_route(idx, idx->variant.load(), m, route);
+  if (route == 1 && !r.has_fused) return fail(SVS_ERR_UNSUPPORTED, "svs_internal_multi_scores: rows of %d elements have no fused kernel", idx->ld);
+  HostCall fr(idx);
+  if ((rc = fr.open()) != SVS_OK) return rc;
+  Ctx* const c = fr.c;
+  const hipStream_t st = fr.stream();
+  const int64_t sstride = score_stride(n);
+  const size_t vn = (size_t)m * d;
+  if ((rc = c->scores.grow((size_t)m * sstride)) != SVS_OK) return rc;
+  if ((rc = upload_combined(c, vectors, nullptr, vn, (size_t)m, st)) != SVS_OK) return rc;
+  const TimedSpan t_pass(idx->timing.load() > 0);
+  t_pass.begin(st);
+  if ((rc = enqueue_multi_scores(idx, c, r, c->q_dev, m, sstride, st)) != SVS_OK) return rc;
+  t_pass.end(st);
+  if ((rc = fr.launched("multi_scores")) != SVS_OK) return rc;
+  HIP_TRY(hipMemcpy2DAsync(out, (size_t)n * sizeof(float), c->scores, (size_t)sstride * sizeof(float), (size_t)n * sizeof(float), (size_t)m,
+                           hipMemcpyDeviceToHost, st));
+  if ((rc = fr.wait()) != SVS_OK) return rc;
+  g_score_pass_ms = t_pass.ms();
+  return SVS_OK;
+}
+
+int32_t svs_index_search_collapsed_combined(svs_index* idx, const float* vectors, int32_t nq, int32_t m, int32_t d, const float* weights, int32_t op,
+                                            int32_t k, int32_t column, int32_t zero_mode, float* out_scores, int64_t* out_rows,
+                                            uint32_t* out_values, int32_t* out_counts, int64_t* out_groups) {
+  static const char* const kEntry = "svs_index_search_collapsed_combined";
+  launch_reset();
+  for (double& ms : g_collapsed_combined_ms) ms = -1.0;   // (a call that fails or records nothing leaves no earlier call's times behind)
+  if (!idx) return fail(SVS_ERR_INVALID, "%s: null index", kEntry);
+  RefGuard guard(idx);
+  std::shared_lock<std::shared_mutex> geo(idx->rw);   // (set_column, mask_rows, compact take it exclusively: every query sees one column)
+  // ---- everything is validated before anything is written, allocated or launched
+  int rc = check_combined_args(kEntry, idx, vectors, nq, m, d, weights, op);
+  if (rc != SVS_OK || (rc = check_column(kEntry, column)) != SVS_OK) return rc;
+  if (zero_mode != SVS_COLLAPSE_ZERO_IS_GROUP && zero_mode != SVS_COLLAPSE_ZERO_SINGLE) return fail(SVS_ERR_INVALID, "%s: zero_mode %d", kEntry, (int)zero_mode);
+  if (!out_counts) return fail(SVS_ERR_INVALID, "%s: null out_counts", kEntry);
+  if (k > 0 && nq > 0 && (!out_scores || !out_rows || !out_values)) return fail(SVS_ERR_INVALID, "%s: null output", kEntry);
+  if (nq == 0) return SVS_OK;
+  const int64_t n = idx->n;
+  if (n == 0) {   // no row, no group
+    for (int32_t q = 0; q < nq; ++q) {
+      out_counts[q] = 0;
+      if (out_groups) out_groups[q] = 0;
+    }
+    return SVS_OK;
+  }
+  const int64_t live = n - (int64_t)idx->dead_list.size();
+  const int ks = (int)std::min<int64_t>(std::max(k, 0), live);   // entries a query can have: what the top-k stage is asked for
+  const int bits = collapse_table_bits(n);
+  const size_t slots = (size_t)1 << bits, tab_words = slots * CL_SLOT_WORDS, key_words = slots * (size_t)m;
+  const unsigned blocks = (unsigned)std::min<int64_t>((n + CL_STRIP - 1) / CL_STRIP, CL_GRID_MAX);
+  HostCall fr(idx);
+  if ((rc = fr.open()) != SVS_OK) return rc;
+  Ctx* const c = fr.c;
+  hipStream_t st = fr.stream();
+  const size_t vn = (size_t)nq * m * d, wn = (size_t)nq * m, on = std::max<size_t>((size_t)nq * (size_t)ks, 1);
+  const int64_t sstride = score_stride(n);
+  if ((rc = c->out_s_pin.grow(on)) != SVS_OK || (rc = c->out_r_pin.grow(on)) != SVS_OK || (rc = c->cl_val_pin.grow(on)) != SVS_OK) return rc;
+  if ((rc = c->cl_cnt.grow((size_t)nq)) != SVS_OK || (rc = c->cl_cnt_pin.grow((size_t)nq)) != SVS_OK) return rc;
+  if ((rc = c->scores.grow((size_t)m * sstride)) != SVS_OK) return rc;
+  if (ks > 0 && select_path(n, ks) == SelectPath::WINDOW && (rc = grow_select_scratch(c, 1, st)) != SVS_OK) return rc;
+  if (c->cl_tab.cap < tab_words || !c->cl_clean) {   // a fresh table, or one an earlier call left early: all of it goes to empty
+    if ((rc = c->cl_tab.grow(tab_words)) != SVS_OK) return rc;
+    HIP_TRY(hipMemsetAsync(c->cl_tab, 0, c->cl_tab.cap * sizeof(unsigned long long), st));
+    c->cl_clean = true;
+  }
+  if (c->cc_keys.cap < key_words || !c->cc_clean) {   // (the keys' layout depends on m: only an all-zero array fits every m)
+    if ((rc = c->cc_keys.grow(key_words)) != SVS_OK) return rc;
+    HIP_TRY(hipMemsetAsync(c->cc_keys, 0, c->cc_keys.cap * sizeof(uint32_t), st));
+    c->cc_clean = true;
+  }
+  HIP_TRY(hipMemsetAsync(c->cl_cnt, 0, (size_t)nq * sizeof(unsigned long long), st));
+  const CombineRoute route = combine_route(idx, idx->variant.load(), m, (int)g_tune_combine_route.load());
+  if ((rc = upload_combined(c, vectors, weights, vn, wn, st)) != SVS_OK) return rc;
+  const CollapseArgs a{idx->cols[column], dead_bits_of(idx), c->cl_tab.p, n, bits, zero_mode == SVS_COLLAPSE_ZERO_SINGLE ? 1 : 0};
+  const bool timed = idx->timing.load() > 0;
+  const TimedSpan t_scores(timed), t_reduce(timed), t_mark(timed), t_clear(timed), t_select(timed);
+  // every query back to back: score pass(es), reduce, mark, the fills, selection, values -- the context's score vectors,
+  // table, keys and selection scratch are reused in stream order; no host wait in between
+  for (int32_t q = 0; q < nq; ++q) {
+    const bool last = q == nq - 1;   // (svs_index_set_timing: spans around the last query's stages)
+    const GroupCombineArgs g{c->scores.p, sstride, c->q_dev + vn + (size_t)q * m, c->cc_keys.p, m, op};
+    if (last) t_scores.begin(st);
+    if ((rc = enqueue_multi_scores(idx, c, route, c->q_dev + (size_t)q * m * d, m, sstride, st)) != SVS_OK) return rc;
+    if (last) t_scores.end(st);
+    c->cl_clean = false;
+    c->cc_clean = false;
+    if (last) t_reduce.begin(st);
+    launch_record("cc_reduce_kernel", n, m);
+    hipLaunchKernelGGL(cc_reduce_kernel, dim3(blocks), dim3(CL_THREADS), 0, st, a, g);
+    if (last) { t_reduce.end(st); t_mark.begin(st); }
+    launch_record("cc_mark_kernel", n, m);
+    hipLaunchKernelGGL(cc_mark_kernel, dim3(blocks), dim3(CL_THREADS), 0, st, a, g, c->cl_cnt.p + q);
+    if (last) { t_mark.end(st); t_clear.begin(st); }
+    HIP_TRY(hipMemsetAsync(c->cl_tab, 0, tab_words * sizeof(unsigned long long), st));
+    c->cl_clean = true;
+    HIP_TRY(hipMemsetAsync(c->cc_keys, 0, key_words * sizeof(uint32_t), st));
+    c->cc_clean = true;
+    if (last) t_clear.end(st);
+    if (ks == 0) continue;
+    if (last) t_select.begin(st);
+    if ((rc = run_select(idx, c, c->scores, n, sstride, 1, ks, ks, c->out_s_pin + (size_t)q * ks, c->out_r_pin + (size_t)q * ks, st,
+                         idx->row_offset)) != SVS_OK)
+      return rc;
+    if (last) t_select.end(st);
+    hipLaunchKernelGGL(collapse_values_kernel, dim3((unsigned)std::min((ks + 255) / 256, 64)), dim3(256), 0, st,
+                       (const int64_t*)(c->out_r_pin + (size_t)q * ks), ks, idx->row_offset, n, (const uint32_t*)idx->cols[column],
+                       c->cl_val_pin + (size_t)q * ks);
+  }
+  rc = read_back(fr, "search_collapsed_combined", {{c->cl_cnt_pin.p, c->cl_cnt.p, (size_t)nq * sizeof(unsigned long long)}});
+  if (rc != SVS_OK) return rc;
+  std::vector<int32_t> counts((size_t)nq);
+  for (int32_t q = 0; q < nq; ++q) {
+    const unsigned long long w = c->cl_cnt_pin[q];
+    if (w > (unsigned long long)live)
+      return fail(SVS_ERR_DEVICE, "search_collapsed_combined: query %d came back with %llu groups of %lld live rows", (int)q, w, (long long)live);
+    counts[(size_t)q] = (int32_t)std::min<unsigned long long>((unsigned long long)ks, w);
+  }
+  if (ks > 0) {
+    deliver_strided(out_scores, k, c->out_s_pin.p, ks, nq, counts.data());
+    deliver_strided(out_rows, k, c->out_r_pin.p, ks, nq, counts.data());
+    deliver_strided(out_values, k, c->cl_val_pin.p, ks, nq, counts.data());
+  }
+  for (int32_t q = 0; q < nq; ++q) {
+    out_counts[q] = counts[(size_t)q];
+    if (out_groups) out_groups[q] = (int64_t)c->cl_cnt_pin[q];
+  }
+  g_collapsed_combined_ms[0] = t_scores.ms();
+  g_collapsed_combined_ms[1] = t_reduce.ms();
+  g_collapsed_combined_ms[2] = t_mark.ms();
+  g_collapsed_combined_ms[3] = t_clear.ms();
+  g_collapsed_combined_ms[4] = ks > 0 ? t_select.ms() : -1.0;
   return SVS_OK;
 }
 

@@ -82,6 +82,39 @@ def collapse_zero_mode(zero) -> int:
     return COLLAPSE_ZERO[zero]
 
 
+def _combined_batch(vectors, op, weights) -> Tuple[np.ndarray, Optional[np.ndarray]]:
+    """(vectors f32 (nq, m, D) contiguous, weights f32 (nq, m) or None) of a batch of combined queries; the shape, op
+    and weight-shape errors of every combined entry are ValueErrors."""
+    v = np.ascontiguousarray(vectors, dtype=np.float32)
+    if v.ndim != 3:
+        raise ValueError(f"vectors must be (nq, m, D), got shape {v.shape}")
+    nq, m, _ = v.shape
+    if not 1 <= m <= COMBINE_MAX_VECTORS:
+        raise ValueError(f"a combined query has 1 .. {COMBINE_MAX_VECTORS} vectors, got {m}")
+    if op not in COMBINE_OPS:
+        raise ValueError(f"op must be one of {sorted(COMBINE_OPS)}, got {op!r}")
+    w = None
+    if weights is not None:
+        w = np.ascontiguousarray(weights, dtype=np.float32)
+        if w.shape != (nq, m):
+            raise ValueError(f"weights must be (nq, m) = {(nq, m)}, got shape {w.shape}")
+    return v, w
+
+
+def _combined_one(vectors, weights) -> Tuple[np.ndarray, Optional[np.ndarray]]:
+    """One combined query, (m, D) and (m,) or None, as a batch of one."""
+    v = np.asarray(vectors, dtype=np.float32)
+    if v.ndim != 2:
+        raise ValueError(f"vectors must be (m, D), got shape {v.shape}")
+    w = None
+    if weights is not None:
+        w = np.asarray(weights, dtype=np.float32)
+        if w.ndim != 1:
+            raise ValueError(f"weights must be (m,), got shape {w.shape}")
+        w = w[None, :]
+    return v[None, :, :], w
+
+
 def where_terms(where) -> list:
     """A ``where`` list -- terms ``(column, op, arg)``, all of which must hold -- checked and normalised to
     ``[(column, svs_where_op, negate, a, b, members)]``: ``members`` is the u32 vector of an in / not in term as given
@@ -940,19 +973,8 @@ class DeviceIndex:
         count = min(max(n, 0), live rows), each row ordered (score desc, row desc); with m = 1, "max" and no weights
         that is ``search_batch`` on an unscreened index.  Shape, op and weight errors are ValueErrors."""
         assert isinstance(n, int)
-        v = np.ascontiguousarray(vectors, dtype=np.float32)
-        if v.ndim != 3:
-            raise ValueError(f"vectors must be (nq, m, D), got shape {v.shape}")
+        v, w = _combined_batch(vectors, op, weights)
         nq, m, d = v.shape
-        if not 1 <= m <= COMBINE_MAX_VECTORS:
-            raise ValueError(f"a combined query has 1 .. {COMBINE_MAX_VECTORS} vectors, got {m}")
-        if op not in COMBINE_OPS:
-            raise ValueError(f"op must be one of {sorted(COMBINE_OPS)}, got {op!r}")
-        w = None
-        if weights is not None:
-            w = np.ascontiguousarray(weights, dtype=np.float32)
-            if w.shape != (nq, m):
-                raise ValueError(f"weights must be (nq, m) = {(nq, m)}, got shape {w.shape}")
         h = self._pinned_handle()
         try:
             k = min(max(n, 0), self._live_rows(h))   # (clamped before allocating and before the int32 argument, as in search_batch)
@@ -971,17 +993,50 @@ class DeviceIndex:
         """One combined query (see ``search_batch_combined``): ``vectors`` (m, D), ``weights`` (m,) or None;
         [(score, row)] as ``search`` returns them."""
         assert isinstance(n, int)
-        v = np.asarray(vectors, dtype=np.float32)
-        if v.ndim != 2:
-            raise ValueError(f"vectors must be (m, D), got shape {v.shape}")
-        w = None
-        if weights is not None:
-            w = np.asarray(weights, dtype=np.float32)
-            if w.ndim != 1:
-                raise ValueError(f"weights must be (m,), got shape {w.shape}")
-            w = w[None, :]
-        s, r, _ = self.search_batch_combined(v[None, :, :], n, op, w)
+        v, w = _combined_one(vectors, weights)
+        s, r, _ = self.search_batch_combined(v, n, op, w)
         return list(zip(s[0].astype(np.float64).tolist(), r[0].tolist()))
+
+    def search_batch_collapsed_combined(self, vectors: np.ndarray, n: int, column: int, op: str = "max", weights=None,
+                                        zero: str = "single") -> Tuple[np.ndarray, np.ndarray, np.ndarray, np.ndarray, np.ndarray]:
+        """Group-combined search (svs_index_search_collapsed_combined): for each COMBINED query of ``vectors`` (nq, m,
+        D) the ``n`` best groups of column ``column``, where a group's score against vector j is its BEST live row's
+        and the m per-vector scores are combined as ``search_batch_combined`` combines a row's (``op``, ``weights``).
+        A group is represented by the row ``search_batch_combined`` would rank first among its rows; ``zero`` as in
+        ``search_batch_collapsed``.  Returns ``(scores f32 (nq, k), rows i64 (nq, k), values u32 (nq, k), counts i32
+        (nq,), groups i64 (nq,))`` with k = min(max(n, 0), live rows): query i has counts[i] = min(k, groups[i]) valid
+        entries; the entries past counts[i] are unspecified.  ``n=0`` only counts the groups."""
+        assert isinstance(n, int)
+        v, w = _combined_batch(vectors, op, weights)
+        nq, m, d = v.shape
+        c = column_index(column)
+        mode = collapse_zero_mode(zero)
+        h = self._pinned_handle()
+        try:
+            k = min(max(n, 0), self._live_rows(h))   # (clamped before allocating and before the int32 argument, as in search_batch)
+            scores = np.empty((nq, k), dtype=np.float32)
+            rows = np.empty((nq, k), dtype=np.int64)
+            values = np.empty((nq, k), dtype=np.uint32)
+            counts = np.zeros(nq, dtype=np.int32)
+            groups = np.zeros(nq, dtype=np.int64)
+            # (the one call that releases the GIL; a count-only call passes no result buffers)
+            _native.check(self._lib.svs_index_search_collapsed_combined(
+                h, v.ctypes.data, nq, m, d, None if w is None else w.ctypes.data, COMBINE_OPS[op], k, c, mode,
+                scores.ctypes.data if k else None, rows.ctypes.data if k else None, values.ctypes.data if k else None,
+                counts.ctypes.data, groups.ctypes.data))
+        finally:
+            self._unpin(h)
+        return scores, rows, values, counts, groups
+
+    def search_collapsed_combined(self, vectors: np.ndarray, n: int, column: int, op: str = "max", weights=None,
+                                  zero: str = "single") -> Tuple[List[Tuple[float, int, int]], int]:
+        """One group-combined query (see ``search_batch_collapsed_combined``): ``vectors`` (m, D), ``weights`` (m,) or
+        None; ([(score, representative row, value)], groups), best group first."""
+        assert isinstance(n, int)
+        v, w = _combined_one(vectors, weights)
+        s, r, val, counts, groups = self.search_batch_collapsed_combined(v, n, column, op, w, zero)
+        c = int(counts[0])
+        return list(zip(s[0, :c].astype(np.float64).tolist(), r[0, :c].tolist(), val[0, :c].tolist())), int(groups[0])
 
     def neighbors(self, rows, n: int) -> Tuple[np.ndarray, np.ndarray]:
         """The ``n`` nearest stored rows of each listed stored row (GLOBAL indices, any order, repeats allowed), the

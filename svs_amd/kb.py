@@ -30,7 +30,7 @@ from typing import Any, Awaitable, Callable, Dict, Iterator, List, Optional, Tup
 import numpy as np
 
 from .index import ASSIGN_MAX_VECTORS, COMBINE_MAX_VECTORS, LABELS_MAX_SET, DeviceIndex
-from .matrix import (DeviceEmbeddingsMatrix, above_op, assign_op, batch_op, by_label_op, cluster_op, collapsed_op, combined_op, diverse_op, labeled_op, neighbors_op, pairs_op, segments_op, single_op, where_op,
+from .matrix import (DeviceEmbeddingsMatrix, above_op, assign_op, batch_op, by_label_op, cluster_op, collapsed_combined_op, collapsed_op, combined_op, diverse_op, labeled_op, neighbors_op, pairs_op, segments_op, single_op, where_op,
                      within_op)
 
 _LOG = logging.getLogger(__name__)
@@ -902,6 +902,33 @@ class KB:
         _LOG.info(f"retrieved top {n} documents")
         return res
 
+    def retrieve_collapsed_combined(self, queries: List[str], n: int, mode: str = "any", weights=None) -> List[Dict[str, Any]]:
+        """``retrieve_collapsed`` against several query strings at once: the n best PARENTS, where a parent's score
+        against each query is its best child's and the per-query scores are combined as ``retrieve_combined`` combines a
+        document's (``mode``, ``weights``: the same arguments and checks).  With ``mode="all"`` over two facets a parent
+        whose one section answers the first facet and another section the second ranks high, which no single section
+        does.  Each parent is represented by the child ``retrieve_combined`` would rank first; a document without a
+        parent stands for itself.  Grouping and combination run on the device (svs_index_search_collapsed_combined)
+        over the column ``retrieve_collapsed`` uses; results shaped like ``retrieve``, 'score' being the parent's."""
+        queries, op, w = _combined_args(queries, mode, weights)
+        _LOG.info(f"retrieving {n} documents with {len(queries)} query strings: {queries}")
+        assert self.db is not None
+        self.embeddings_matrix.get_sync(self.db)
+
+        def parents_from_store():
+            with self.db.transaction():
+                return self.db.embedding_parents()
+
+        self.embeddings_matrix.ensure_column(PARENT_COLUMN, parents_from_store)
+        query_vecs = np.array(self._embed(queries), dtype=np.float32)
+        _LOG.info("got embeddings for the queries!")
+        hits, _ = self.embeddings_matrix.search_collapsed_combined(query_vecs, n, PARENT_COLUMN, op, w, "single")   # one pass + grouping: HIP
+        _LOG.info(f"computed {self.embeddings_matrix.index.shape[0]} x {len(queries)} cosine similarities")
+        with self.db.transaction():
+            res = _fetch_list(self.db, [(score, emb_id) for score, emb_id, _ in hits])
+        _LOG.info(f"retrieved top {n} documents")
+        return res
+
     def retrieve_similar(self, doc_id: int, n: int) -> List[Dict[str, Any]]:
         """"More like this": the n documents nearest to the STORED document ``doc_id``, itself excluded, shaped like
         ``retrieve`` ([{'score', 'doc'}]).  The reference can only loop ``np.dot(M, M[i])`` + ``get_top_k``
@@ -1339,6 +1366,21 @@ class AsyncKB:
             emb_ids = await self._search(held, combined_op(query_vecs, n, op, w))
             _LOG.info(f"computed {held[0].shape[0]} x {len(queries)} cosine similarities")
         res = await self._fetch(lambda db: _fetch_list(db, emb_ids))
+        _LOG.info(f"retrieved top {n} documents")
+        return res
+
+    async def retrieve_collapsed_combined(self, queries: List[str], n: int, mode: str = "any", weights=None) -> List[Dict[str, Any]]:
+        """Async twin of ``KB.retrieve_collapsed_combined``, structured as ``retrieve_collapsed``: the parent column is
+        installed and the reference to the matrix is taken under the lock, the one embedding call and the search run
+        outside it, the docs are fetched under the lock."""
+        queries, op, w = _combined_args(queries, mode, weights)
+        _LOG.info(f"retrieving {n} documents with {len(queries)} query strings: {queries}")
+        async with self._held(lambda db: self.embeddings_matrix.ensure_column(PARENT_COLUMN, db.embedding_parents)) as (held, _):
+            query_vecs = np.array(await self._embed(queries), dtype=np.float32)
+            _LOG.info("got embeddings for the queries!")
+            hits, _ = await self._search(held, collapsed_combined_op(query_vecs, n, PARENT_COLUMN, op, w, "single"))
+            _LOG.info(f"computed {held[0].shape[0]} x {len(queries)} cosine similarities")
+        res = await self._fetch(lambda db: _fetch_list(db, [(score, emb_id) for score, emb_id, _ in hits]))
         _LOG.info(f"retrieved top {n} documents")
         return res
 

@@ -248,6 +248,20 @@ def collapsed_op(query_vec: np.ndarray, n: int, column: int, zero: str = "single
     return native, finish
 
 
+def collapsed_combined_op(vectors: np.ndarray, n: int, column: int, op: str = "max", weights=None, zero: str = "single"):
+    """Group-combined search: ``idx.search_collapsed_combined`` (svs_index_search_collapsed_combined) of the (m, D)
+    ``vectors`` over the groups of column ``column``, representative rows -> ids: ([(score, emb_id, value)], groups)."""
+    def native(idx, lookup, *_):
+        return idx, idx.search_collapsed_combined(vectors, n, column, op, weights, zero)
+
+    def finish(res, arr):
+        used, (rows, groups) = res
+        off = int(getattr(used, "row_offset", 0))
+        return [(score, int(arr[row - off]), int(value)) for score, row, value in rows], int(groups)
+
+    return native, finish
+
+
 def diverse_op(query_vec: np.ndarray, n: int, fetch_k: Optional[int] = None, lam: float = 0.5):
     """Diverse (MMR) search: ``idx.search_diverse`` (svs_index_search_diverse), rows -> ids:
     [(score, emb_id, redundancy)] in pick order."""
@@ -668,6 +682,13 @@ class DeviceEmbeddingsMatrix:
         """``search`` re-ranked for diversity (MMR over the ``fetch_k`` best, on the device):
         [(score, emb_id, redundancy)] in pick order (``KB.retrieve_diverse``)."""
         return self.run_mapped(diverse_op(query_vec, n, fetch_k, lam))
+
+    def search_collapsed_combined(self, vectors: np.ndarray, n: int, column: int, op: str = "max", weights=None,
+                                  zero: str = "single") -> Tuple[List[Tuple[float, int, int]], int]:
+        """``search_collapsed`` against several vectors at once (``DeviceIndex.search_collapsed_combined``: a group's
+        score against each vector is its best row's, the m of them combined by ``op``): ([(score, emb_id of the
+        group's representative, value)], groups) (``KB.retrieve_collapsed_combined``).  Call ``ensure_column`` first."""
+        return self.run_mapped(collapsed_combined_op(vectors, n, column, op, weights, zero))
 
     def search_combined(self, vectors: np.ndarray, n: int, op: str = "max", weights=None) -> List[Tuple[float, int]]:
         """``search`` ranked against several vectors at once (``DeviceIndex.search_combined``: the "max", "min" or weighted

@@ -232,6 +232,11 @@ class MultiDeviceIndex:
 
     search_batch_combined = search_combined
 
+    def search_collapsed_combined(self, vectors: np.ndarray, n: int, column: int, op: str = "max", weights=None, zero: str = "single"):
+        raise NotImplementedError("group-combined search is per device: a group's rows may lie on several shards and its per-vector maxima are not merged across them; call set_column / search_collapsed_combined on a DeviceIndex")
+
+    search_batch_collapsed_combined = search_collapsed_combined
+
     def search_where(self, query_vec: np.ndarray, n: int, where):
         raise NotImplementedError("predicate search is per device: the columns sit beside one shard's rows; call set_column / search_where on a DeviceIndex")
 

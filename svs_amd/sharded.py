@@ -225,6 +225,11 @@ class ShardedIndex:
 
     search_batch_combined = search_combined
 
+    def search_collapsed_combined(self, vectors: np.ndarray, n: int, column: int, op: str = "max", weights=None, zero: str = "single"):
+        raise NotImplementedError("group-combined search is per device: a rank fills and searches the columns of its own shard (DeviceIndex.search_collapsed_combined); per-vector group maxima are not merged across ranks")
+
+    search_batch_collapsed_combined = search_collapsed_combined
+
     def search_where(self, query_vec: np.ndarray, n: int, where):
         raise NotImplementedError("predicate search is per device: a rank fills and searches the columns of its own shard (DeviceIndex.search_where); nothing is merged across ranks")
 
