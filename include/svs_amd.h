@@ -577,14 +577,77 @@ int32_t svs_index_search_by_label(svs_index* idx, const float* queries, int32_t 
  * slot, a power of two >= 2 x rows slots -- 32 to 64 MB per million rows and per context that ran a collapsed search.
  * Blocking; re-entrant on one handle; holds a reference and the geometry lock shared; waits for pending staging
  * copies; never goes through the coalescer, the run-ahead pipelines or shared passes: all as svs_index_search_above.
- * Out of scope: more than one row per group or a per-group row count, collapsing under a predicate
- * (svs_index_search_where) or over a row list, grouping by two columns, svs_multi / row-sharded corpora, a
- * device-pointer variant, the batched GEMM and the screened score routes, routing through shared passes. */
+ * Out of scope: more than one row per group or a per-group row count, grouping by two columns, svs_multi /
+ * row-sharded corpora, a device-pointer variant, the batched GEMM and the screened score routes, routing through shared passes. */
 enum { SVS_COLLAPSE_ZERO_IS_GROUP = 0, SVS_COLLAPSE_ZERO_SINGLE = 1 };
 int32_t svs_index_search_collapsed(svs_index* idx, const float* queries, int32_t nq, int32_t d, int32_t k,
                                    int32_t column, int32_t zero_mode,
                                    float* out_scores, int64_t* out_rows, uint32_t* out_values /* all three: stride k */,
                                    int32_t* out_counts /* nq */, int64_t* out_groups /* nq, or NULL */);
+
+/* Collapsed search inside a scope: svs_index_search_collapsed's groups over the rows of a predicate or of a row list
+ * -- "the 10 best documents of tenant 7, one hit per document", "the 10 best chapters, judged by their best level-2
+ * section" -- with nothing but the answer leaving the device.  (Over-fetching from svs_index_search_where and
+ * de-duplicating is wrong whenever one parent holds the best rows.)
+ * Exact definition.  The scope S, ascending:
+ *   _where   S = { live local rows r : every term is true on r }: svs_index_search_where's S, with its term semantics
+ *            and limits; nterms == 0: every live row
+ *   _rows    S = the live rows of `rows` (GLOBAL, any order, repeats allowed), ascending, each once:
+ *            svs_index_search_rows' S
+ * For query q of the call and r in S let t[r] = the score bits svs_index_search_rows reports for row r when called
+ * with that query over S + row_offset and k = |S|: the GATHER kernel's score, not svs_index_scores_n's.  v[r] =
+ * column[column][r] (a column never set reads 0 everywhere); groups, the two zero modes and make_key are
+ * svs_index_search_collapsed's, restricted to S:
+ *   best(G) = max over r in G and S of make_key(t[r], r)     (svs_amd/csrc/keys.h)
+ *   W       = { r : r is the best of its group }             (a group with no row in S has none)
+ *   *out_matched    = |S|; may be NULL
+ *   out_groups[q]   = |W|, always exact; may be NULL
+ *   out_counts[q]   = min(max(k, 0), |W|)
+ *   out_*[q*k + t], t < out_counts[q]   the rows of W in descending key, that is (score desc, row desc): out_scores =
+ *                     the score bits of t (a NaN comes back as the quiet NaN 0x7fc00000, as from every search),
+ *                     out_rows = row_offset + r, out_values = v[r].  Entries past the count are not touched.
+ * A query's result does not depend on nq, on the other queries of the call, or on how the device schedules the work.
+ * Three identities.  (a) A column never set under ZERO_SINGLE gives svs_index_search_where's / svs_index_search_rows'
+ * result -- rows and score bits -- with groups = |S|.  (b) A column never set under ZERO_IS_GROUP gives one hit, the
+ * first row of (a).  (c) The two entries agree bit for bit when `rows` lists exactly the predicate's S.
+ * NOT claimed: any identity with the unscoped svs_index_search_collapsed, not even with nterms == 0 -- that entry
+ * collapses the full-pass kernel's scores, these collapse the gather kernel's, and the two need not round alike.
+ * Errors: everything is validated before anything is launched, and a failing call writes no output.  d != index d or
+ * an empty index -> SVS_ERR_SHAPE.  SVS_ERR_INVALID: svs_index_search_collapsed's argument errors (nq < 0, a column
+ * outside [0, SVS_COLUMNS_MAX), an unknown zero_mode, null queries with nq > 0, null out_counts, null out_scores /
+ * out_rows / out_values with k > 0 and nq > 0); _where: svs_index_search_where's term errors (nterms < 0, null terms
+ * with nterms > 0, a term's column outside [0, SVS_COLUMNS_MAX), an unknown op, negate not 0 or 1, IN with nset < 0 or
+ * a null set with nset > 0); _rows: svs_index_search_rows' list errors (nrows < 0, null rows with nrows > 0, a row
+ * outside the index).  SVS_ERR_UNSUPPORTED: nterms > SVS_WHERE_MAX_TERMS; more than SVS_LABELS_MAX_SET distinct set
+ * members over the call's IN terms; rows of more than 16 KiB with work to do (nq > 0).
+ * nq == 0 -> SVS_OK, nothing launched, nothing written.  |S| == 0 -> SVS_OK, counts and groups 0, matched 0; nothing
+ * runs after the counting launch (_rows: nothing runs).  k <= 0 is a COUNT-ONLY call, as in
+ * svs_index_search_collapsed: groups and matched are computed, every count is 0, the three result pointers may be NULL.
+ * Cost.  _where: svs_index_search_where's counting pass and ONE host wait for |S|, then a one-workgroup scan and ONE
+ * writing pass that evaluates the predicate once and emits both S and the group column compacted beside it (one more
+ * 16-byte load per lane and step; none when a term names the column anyway or the index does not own it).  _rows: the
+ * list is built on the host and uploaded as svs_index_search_rows does, and a tiny launch reads its column values.
+ * Then the gather kernel scores the list for chunks of queries whose score vectors stay <= 2 GiB, and every query's
+ * |S| scores go through svs_index_search_collapsed's own kernels with list positions for rows (positions ascend with
+ * rows, so a tie still goes to the larger row): reduce, mark, the table's fill -- a table sized by |S|, not by the
+ * index --, the top-k stage, the values; positions become rows on the device (svs_amd/csrc/collapse_scope.h).
+ * Blocking; re-entrant on one handle; holds a reference and the geometry lock shared; waits for pending staging
+ * copies; two host waits per call (_rows: one); never goes through the coalescer, the run-ahead pipelines or shared
+ * passes: all as svs_index_search_where.
+ * Out of scope: svs_multi / row-sharded corpora, a device-pointer variant, a scoped
+ * svs_index_search_collapsed_combined, svs_index_search_above and svs_index_search_by_label under a scope, OR across
+ * terms, routing a broad predicate through a full-corpus pass. */
+int32_t svs_index_search_collapsed_where(svs_index* idx, const float* queries, int32_t nq, int32_t d, int32_t k,
+                                         const svs_where_term_t* terms, int32_t nterms,
+                                         int32_t column, int32_t zero_mode,
+                                         float* out_scores, int64_t* out_rows, uint32_t* out_values /* stride k */,
+                                         int32_t* out_counts /* nq */, int64_t* out_groups /* nq, or NULL */,
+                                         int64_t* out_matched /* or NULL */);
+int32_t svs_index_search_collapsed_rows(svs_index* idx, const float* queries, int32_t nq, int32_t d, int32_t k,
+                                        const int64_t* rows, int64_t nrows,
+                                        int32_t column, int32_t zero_mode,
+                                        float* out_scores, int64_t* out_rows, uint32_t* out_values,
+                                        int32_t* out_counts, int64_t* out_groups, int64_t* out_matched);
 
 /* Group-combined search: the top k GROUPS (parent documents) ranked against several vectors at once, where a group's
  * score against each vector is its best row's -- "the documents that cover both facets, wherever in the document":

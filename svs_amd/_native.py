@@ -124,6 +124,10 @@ SIGNATURES = {
     "svs_index_search_collapsed": (C.c_int32, [_P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P, _P, _P]),
     "svs_index_search_collapsed_combined": (C.c_int32, [_P, _P, C.c_int32, C.c_int32, C.c_int32, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
                                                         _P, _P, _P, _P, _P]),
+    "svs_index_search_collapsed_where": (C.c_int32, [_P, _P, C.c_int32, C.c_int32, C.c_int32, _P, C.c_int32, C.c_int32, C.c_int32,
+                                                     _P, _P, _P, _P, _P, C.POINTER(C.c_int64)]),
+    "svs_index_search_collapsed_rows": (C.c_int32, [_P, _P, C.c_int32, C.c_int32, C.c_int32, _P, C.c_int64, C.c_int32, C.c_int32,
+                                                    _P, _P, _P, _P, _P, C.POINTER(C.c_int64)]),
     "svs_index_assign": (C.c_int32, [_P, _P, C.c_int32, C.c_int32, C.c_int64, C.c_int64, _P, _P, _P, _P]),
     "svs_index_label_sums": (C.c_int32, [_P, _P, C.c_int32, C.c_int64, C.c_int64, _P, _P, _P]),
     "svs_index_search_diverse": (C.c_int32, [_P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_float, _P, _P, _P,
@@ -162,6 +166,7 @@ INTERNAL = {
     "svs_internal_by_label_geometry": (C.c_int32, [C.POINTER(C.c_int32)]),
     "svs_internal_collapse_geometry": (C.c_int32, [C.POINTER(C.c_int32)]),
     "svs_internal_collapse_kernel_ms": (C.c_int32, [C.POINTER(C.c_double)]),
+    "svs_internal_collapse_scope_kernel_ms": (C.c_int32, [C.POINTER(C.c_double)]),
     "svs_internal_assign_kernel_ms": (C.c_int32, [C.POINTER(C.c_double)]),
     "svs_internal_label_sums_kernel_ms": (C.c_int32, [C.POINTER(C.c_double)]),
     "svs_internal_combined_scores": (C.c_int32, [_P, _P, C.c_int32, C.c_int32, _P, C.c_int32, C.c_int32, _P, C.c_int64]),

@@ -145,6 +145,13 @@ int32_t svs_internal_collapse_geometry(int32_t* out);
  * out[1] collapse_mark_kernel, out[2] the table's fill, out[3] the top-k stage; -1 where that call recorded none
  * (tools/collapse_time.py). */
 int32_t svs_internal_collapse_kernel_ms(double* out);
+/* Milliseconds between the HIP events around the stages of the calling thread's last svs_index_search_collapsed_where
+ * or svs_index_search_collapsed_rows, recorded while svs_index_set_timing is on for the handle: out[0] the filter (the
+ * counting launch plus the scan and scoped_write_kernel; _rows: the list's upload and scoped_values_kernel), out[1]
+ * the last query chunk's gather launch, and for the LAST query out[2] collapse_reduce_kernel, out[3]
+ * collapse_mark_kernel, out[4] the table's fill, out[5] the top-k stage; -1 where that call recorded none
+ * (tools/collapse_where_time.py). */
+int32_t svs_internal_collapse_scope_kernel_ms(double* out);
 /* Milliseconds between the HIP events around assign_rows_kernel in the calling thread's last svs_index_assign, recorded
  * while svs_index_set_timing is on for the handle; -1 when that call recorded none (tools/assign_time.py). */
 int32_t svs_internal_assign_kernel_ms(double* out);

@@ -176,17 +176,12 @@ __device__ __forceinline__ void strip_count(const FILTER& f, uint32_t* s_set, in
   }
 }
 
-// The write pass: the predicate again; a match's slot is the strip's base + the matches in the earlier waves of the
-// strip + the matches before it in its own wave.  A slot at or past m is never written.  The payload of a match is its
-// row (LB_ROWS) or the value strip_ballots left in v (LB_VALUES: the label filter's).
-template <int PAYLOAD, class FILTER>
-__device__ __forceinline__ void strip_write(const FILTER& f, uint32_t* s_set, int* s_wave, const uint32_t* __restrict__ bases,
-                                            uint32_t* __restrict__ out, int64_t m) {
-  strip_stage(f, s_set);
-  unsigned long long b[LB_ITERS][4];
-  uint4 v[LB_ITERS];
-  int64_t row0;
-  const int cnt = strip_ballots(f, s_set, b, v, &row0);
+// The slots of the write pass, from the calling wave's ballots b and their sum cnt: a match's slot is the strip's base +
+// the matches in the earlier waves of the strip + the matches before it in its own wave.  put(slot, j, e) is called for
+// the lane's own matches -- element e of step j -- whose slot is below m: a slot at or past m is never written.
+template <class PUT>
+__device__ __forceinline__ void strip_slots(const unsigned long long (&b)[LB_ITERS][4], int cnt, int* s_wave,
+                                            const uint32_t* __restrict__ bases, int64_t m, PUT&& put) {
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   if (lane == 0) s_wave[wave] = cnt;
   __syncthreads();
@@ -202,17 +197,35 @@ __device__ __forceinline__ void strip_write(const FILTER& f, uint32_t* s_set, in
       below += (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(b[j][e] >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)b[j][e], 0u));
       step += __popcll(b[j][e]);
     }
-    const uint32_t lab[4] = {v[j].x, v[j].y, v[j].z, v[j].w};
     int64_t s = slot + below;
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
       if ((b[j][e] >> lane) & 1ull) {
-        if (s < m) out[s] = PAYLOAD == LB_ROWS ? (uint32_t)(row0 + j * 256 + lane * 4 + e) : lab[e];
+        if (s < m) put(s, j, e);
         ++s;
       }
     }
     slot += step;
   }
+}
+
+// Element e of a lane's 16-byte load
+__device__ __forceinline__ uint32_t uint4_at(const uint4& v, int e) { return e == 0 ? v.x : e == 1 ? v.y : e == 2 ? v.z : v.w; }
+
+// The write pass: the predicate again, then strip_slots.  The payload of a match is its row (LB_ROWS) or the value
+// strip_ballots left in v (LB_VALUES: the label filter's).
+template <int PAYLOAD, class FILTER>
+__device__ __forceinline__ void strip_write(const FILTER& f, uint32_t* s_set, int* s_wave, const uint32_t* __restrict__ bases,
+                                            uint32_t* __restrict__ out, int64_t m) {
+  strip_stage(f, s_set);
+  unsigned long long b[LB_ITERS][4];
+  uint4 v[LB_ITERS];
+  int64_t row0;
+  const int cnt = strip_ballots(f, s_set, b, v, &row0);
+  const int lane = threadIdx.x & 63;
+  strip_slots(b, cnt, s_wave, bases, m, [&](int64_t s, int j, int e) {
+    out[s] = PAYLOAD == LB_ROWS ? (uint32_t)(row0 + j * 256 + lane * 4 + e) : uint4_at(v[j], e);
+  });
 }
 
 // grid = ceil(n / LB_STRIP) workgroups.  counts[blockIdx.x] = the strip's matches; *total += them (zero on entry).

@@ -49,6 +49,7 @@
 #include "by_label.h"
 #include "collapse.h"
 #include "collapse_combine.h"
+#include "collapse_scope.h"
 #include "assign.h"
 #include "label_sums.h"
 
@@ -285,6 +286,9 @@ struct Ctx {
   // (all zero) between queries and between calls under a flag of its own -- svs_index_search_collapsed repairs only cl_tab
   DevBuf<uint32_t> cc_keys;
   bool cc_clean = true;
+  // svs_index_search_collapsed_where / _rows (collapse_scope.h): the group column compacted beside list_dev, padded to
+  // whole groups of four.  The table, cl_clean, the counters and the values' pinned copy are the unscoped entry's.
+  DevBuf<uint32_t> sc_vals;
   // svs_index_assign (assign.h): the call's vectors in the index's storage format (rows of ld elements; fp8: their
   // scales), the per-row results and the counts.  The f32 vectors go up through q_pin / q_dev.
   DevBuf<uint8_t> as_vec;       DevBuf<float> as_vec_scales;
@@ -2944,7 +2948,8 @@ thread_local double g_assign_kernel_ms = -1.0;       // svs_internal_assign_kern
 thread_local double g_label_sums_kernel_ms = -1.0;   // svs_internal_label_sums_kernel_ms
 thread_local double g_collapse_ms[4] = {-1.0, -1.0, -1.0, -1.0};   // svs_internal_collapse_kernel_ms: reduce, mark, clear, select
 thread_local double g_collapsed_combined_ms[5] = {-1.0, -1.0, -1.0, -1.0, -1.0};   // svs_internal_collapsed_combined_kernel_ms: scores, reduce, mark, clear, select
-thread_local double g_score_pass_ms = -1.0;          // svs_internal_score_pass_ms: the score pass of the last combined_scores / multi_scores hook call
+thread_local double g_collapse_scope_ms[6] = {-1.0, -1.0, -1.0, -1.0, -1.0, -1.0};   // svs_internal_collapse_scope_kernel_ms: filter, gather, reduce, mark, clear, select
+thread_local double g_score_pass_ms = -1.0;         // svs_internal_score_pass_ms: the score pass of the last combined_scores / multi_scores hook call
 int report_ms(double* out, double ms) {
   if (!out) return fail(SVS_ERR_INVALID, "null output");
   *out = ms;
@@ -3835,24 +3840,25 @@ static_assert(SVS_WHERE_IN == WH_IN && SVS_WHERE_RANGE == WH_RANGE && SVS_WHERE_
               "where.h's kernels take the header's op codes");
 
 // A caller's terms, checked, and their kernel form: every IN term's set sorted and without repeats; the sets of two
-// members or more one after another in `image` (at most SVS_LABELS_MAX_SET words: the kernels' LDS image)
+// members or more one after another in `image` (at most SVS_LABELS_MAX_SET words: the kernels' LDS image).  entry: the
+// ABI name the messages begin with.
 struct WherePlan {
   using Filter = WhereFilter;
   WhereTerm t[WH_MAX_TERMS] = {};
   int nterms = 0;
   uint32_t col_mask = 0;
   std::vector<uint32_t> image;
-  int build(const svs_where_term_t* terms, int32_t nterms_in) {
+  int build(const svs_where_term_t* terms, int32_t nterms_in, const char* entry = "svs_index_search_where") {
     if (nterms_in < 0) return fail(SVS_ERR_INVALID, "nterms must be >= 0");
     if (nterms_in > SVS_WHERE_MAX_TERMS)
-      return fail(SVS_ERR_UNSUPPORTED, "svs_index_search_where: %d terms; a predicate holds at most %d", (int)nterms_in, SVS_WHERE_MAX_TERMS);
+      return fail(SVS_ERR_UNSUPPORTED, "%s: %d terms; a predicate holds at most %d", entry, (int)nterms_in, SVS_WHERE_MAX_TERMS);
     if (nterms_in > 0 && !terms) return fail(SVS_ERR_INVALID, "null terms");
     for (int i = 0; i < nterms_in; ++i) {
       const svs_where_term_t& u = terms[i];
-      int rc = check_column("svs_index_search_where", u.column);
+      int rc = check_column(entry, u.column);
       if (rc != SVS_OK) return rc;
-      if (u.op < SVS_WHERE_IN || u.op > SVS_WHERE_ALL_BITS) return fail(SVS_ERR_INVALID, "svs_index_search_where: term %d has the unknown op %d", i, (int)u.op);
-      if (u.negate != 0 && u.negate != 1) return fail(SVS_ERR_INVALID, "svs_index_search_where: term %d: negate must be 0 or 1", i);
+      if (u.op < SVS_WHERE_IN || u.op > SVS_WHERE_ALL_BITS) return fail(SVS_ERR_INVALID, "%s: term %d has the unknown op %d", entry, i, (int)u.op);
+      if (u.negate != 0 && u.negate != 1) return fail(SVS_ERR_INVALID, "%s: term %d: negate must be 0 or 1", entry, i);
       if (u.op == SVS_WHERE_IN && (rc = LabelSet::check(u.set, u.nset)) != SVS_OK) return rc;
     }
     size_t members = 0;
@@ -3878,7 +3884,7 @@ struct WherePlan {
       if (set.size() == 1) w.a = set[0];
     }
     if (members > (size_t)SVS_LABELS_MAX_SET)
-      return fail(SVS_ERR_UNSUPPORTED, "svs_index_search_where: %zu distinct set members over the IN terms; a call holds at most %d", members,
+      return fail(SVS_ERR_UNSUPPORTED, "%s: %zu distinct set members over the IN terms; a call holds at most %d", entry, members,
                   SVS_LABELS_MAX_SET);
     nterms = nterms_in;
     return SVS_OK;
@@ -4253,6 +4259,237 @@ int32_t svs_index_search_collapsed(svs_index* idx, const float* queries, int32_t
   g_collapse_ms[2] = t_clear.ms();
   g_collapse_ms[3] = ks > 0 ? t_select.ms() : -1.0;
   return SVS_OK;
+}
+
+// ---- svs_index_search_collapsed_where, svs_index_search_collapsed_rows (collapse_scope.h)
+int32_t svs_internal_collapse_scope_kernel_ms(double* out) {
+  if (!out) return fail(SVS_ERR_INVALID, "null output");
+  for (int i = 0; i < 6; ++i) out[i] = g_collapse_scope_ms[i];
+  return SVS_OK;
+}
+
+// What the two entries are given to write into, and their one way of writing an empty scope's answer
+struct ScopedOut {
+  float* scores;
+  int64_t* rows;
+  uint32_t* values;
+  int32_t* counts;
+  int64_t* groups;
+  int64_t* matched;
+};
+
+static int32_t scoped_empty(const ScopedOut& o, int32_t nq) {
+  for (int32_t q = 0; q < nq; ++q) {
+    o.counts[q] = 0;
+    if (o.groups) o.groups[q] = 0;
+  }
+  if (o.matched) *o.matched = 0;
+  return SVS_OK;
+}
+
+// The checks the two entries share, in svs_index_search_collapsed's order (the caller has checked the queries)
+static int check_scoped_args(const char* entry, int32_t nq, int32_t k, int32_t column, int32_t zero_mode, const ScopedOut& o) {
+  const int rc = check_column(entry, column);
+  if (rc != SVS_OK) return rc;
+  if (zero_mode != SVS_COLLAPSE_ZERO_IS_GROUP && zero_mode != SVS_COLLAPSE_ZERO_SINGLE)
+    return fail(SVS_ERR_INVALID, "%s: zero_mode %d", entry, (int)zero_mode);
+  if (!o.counts) return fail(SVS_ERR_INVALID, "null out_counts");
+  if (k > 0 && nq > 0 && (!o.scores || !o.rows || !o.values)) return fail(SVS_ERR_INVALID, "null output");
+  return SVS_OK;
+}
+
+// What the two do once c->list_dev holds S (m >= 1 local rows, ascending) and c->sc_vals the group column beside it,
+// both enqueued on the frame's stream, with the queries uploaded: the gather kernel scores chunks of queries over the
+// list (search_list_chunked's 2 GiB rule), and every query's compact vector goes through svs_index_search_collapsed's
+// stages with positions for rows -- reduce, mark, the table's fill, the top-k stage, the values -- then positions ->
+// global rows on the device, the call's last wait, and the trimmed results.  filter_ms: what the caller's filter took.
+static int32_t collapse_over_list(svs_index* idx, HostCall& fr, const char* entry, int32_t nq, int32_t d, int32_t k, int64_t m, int32_t zero_mode,
+                                  const ScopedOut& o, const TimedSpan& t_filter, double filter_ms) {
+  Ctx* const c = fr.c;
+  int rc;
+  const int ks = (int)std::min<int64_t>(std::max(k, 0), m);   // entries a query can have: what the top-k stage is asked for
+  const int64_t sstride = score_stride(m);
+  const int qc = (int)std::max<int64_t>(1, std::min<int64_t>(nq, ((int64_t)2 << 30) / (4 * sstride)));   // queries per gather launch
+  const int bits = collapse_table_bits(m);
+  const size_t tab_words = ((size_t)1 << bits) * CL_SLOT_WORDS;
+  const unsigned blocks = (unsigned)std::min<int64_t>((m + CL_STRIP - 1) / CL_STRIP, CL_GRID_MAX);
+  const size_t on = std::max<size_t>((size_t)nq * (size_t)ks, 1);
+  hipStream_t st = fr.stream();
+  if ((rc = c->out_s_pin.grow(on)) != SVS_OK || (rc = c->out_r_pin.grow(on)) != SVS_OK || (rc = c->cl_val_pin.grow(on)) != SVS_OK) return rc;
+  if ((rc = c->lab_pos.grow(on)) != SVS_OK) return rc;
+  if ((rc = c->cl_cnt.grow((size_t)nq)) != SVS_OK || (rc = c->cl_cnt_pin.grow((size_t)nq)) != SVS_OK) return rc;
+  if ((rc = c->scores.grow((size_t)qc * (size_t)sstride)) != SVS_OK) return rc;
+  if (ks > 0 && select_path(m, ks) == SelectPath::WINDOW && (rc = grow_select_scratch(c, 1, st)) != SVS_OK) return rc;
+  if (c->cl_tab.cap < tab_words || !c->cl_clean) {   // a fresh table, or one an earlier call of either kind left early: all of it goes to empty
+    if ((rc = c->cl_tab.grow(tab_words)) != SVS_OK) return rc;
+    HIP_TRY(hipMemsetAsync(c->cl_tab, 0, c->cl_tab.cap * sizeof(unsigned long long), st));
+    c->cl_clean = true;
+  }
+  HIP_TRY(hipMemsetAsync(c->cl_cnt, 0, (size_t)nq * sizeof(unsigned long long), st));
+  // (no bitmap: S holds live rows only)
+  const CollapseArgs a{c->sc_vals.p, nullptr, c->cl_tab.p, m, bits, zero_mode == SVS_COLLAPSE_ZERO_SINGLE ? 1 : 0};
+  const bool timed = idx->timing.load() > 0;
+  const TimedSpan t_gather(timed), t_reduce(timed), t_mark(timed), t_clear(timed), t_select(timed);
+  for (int32_t q0 = 0; q0 < nq; q0 += qc) {
+    const int32_t nc = std::min<int32_t>(qc, nq - q0);
+    const bool last_chunk = q0 + nc == nq;   // (svs_index_set_timing: spans around the last chunk's gather and the last query's stages)
+    if (last_chunk) t_gather.begin(st);
+    if ((rc = launch_gather(idx, c, c->q_dev + (size_t)q0 * d, nc, c->list_dev, m, c->scores, sstride, st)) != SVS_OK) return rc;
+    if (last_chunk) t_gather.end(st);
+    for (int32_t q = q0; q < q0 + nc; ++q) {
+      const bool last = q == nq - 1;
+      float* const sv = c->scores.p + (size_t)(q - q0) * (size_t)sstride;
+      c->cl_clean = false;
+      if (last) t_reduce.begin(st);
+      launch_record("collapse_reduce_kernel", m, 1);
+      hipLaunchKernelGGL(collapse_reduce_kernel, dim3(blocks), dim3(CL_THREADS), 0, st, a, (const float*)sv);
+      if (last) { t_reduce.end(st); t_mark.begin(st); }
+      launch_record("collapse_mark_kernel", m, 1);
+      hipLaunchKernelGGL(collapse_mark_kernel, dim3(blocks), dim3(CL_THREADS), 0, st, a, sv, c->cl_cnt.p + q);
+      if (last) { t_mark.end(st); t_clear.begin(st); }
+      HIP_TRY(hipMemsetAsync(c->cl_tab, 0, tab_words * sizeof(unsigned long long), st));
+      c->cl_clean = true;
+      if (last) t_clear.end(st);
+      if (ks == 0) continue;
+      if (last) t_select.begin(st);
+      if ((rc = run_select(idx, c, sv, m, sstride, 1, ks, ks, c->out_s_pin + (size_t)q * ks, c->lab_pos + (size_t)q * ks, st, 0)) != SVS_OK)
+        return rc;
+      if (last) t_select.end(st);
+      hipLaunchKernelGGL(collapse_values_kernel, dim3((unsigned)std::min((ks + 255) / 256, 64)), dim3(256), 0, st,
+                         (const int64_t*)(c->lab_pos + (size_t)q * ks), ks, (int64_t)0, m, (const uint32_t*)c->sc_vals.p,
+                         c->cl_val_pin + (size_t)q * ks);
+    }
+  }
+  const size_t nres = (size_t)nq * (size_t)ks;
+  if (nres)   // the positions -> global rows, on the device
+    hipLaunchKernelGGL(label_map_rows_kernel, dim3((unsigned)std::min<size_t>((nres + 255) / 256, 1024)), dim3(256), 0, st,
+                       (const int64_t*)c->lab_pos.p, (int64_t)nres, (const uint32_t*)c->list_dev.p, m, idx->row_offset, c->out_r_pin.p);
+  rc = read_back(fr, entry, {{c->cl_cnt_pin.p, c->cl_cnt.p, (size_t)nq * sizeof(unsigned long long)}});
+  if (rc != SVS_OK) return rc;
+  std::vector<int32_t> counts((size_t)nq);
+  for (int32_t q = 0; q < nq; ++q) {
+    const unsigned long long w = c->cl_cnt_pin[q];
+    if (w > (unsigned long long)m)
+      return fail(SVS_ERR_DEVICE, "%s: query %d came back with %llu groups of %lld rows in scope", entry, (int)q, w, (long long)m);
+    counts[(size_t)q] = (int32_t)std::min<unsigned long long>((unsigned long long)ks, w);
+  }
+  for (size_t i = 0; i < nres; ++i)
+    if (c->out_r_pin[i] < 0)
+      return fail(SVS_ERR_DEVICE, "%s: result %zu of query %zu is a position outside the %lld rows in scope", entry, i % (size_t)ks, i / (size_t)ks,
+                  (long long)m);
+  if (ks > 0) {
+    deliver_strided(o.scores, k, c->out_s_pin.p, ks, nq, counts.data());
+    deliver_strided(o.rows, k, c->out_r_pin.p, ks, nq, counts.data());
+    deliver_strided(o.values, k, c->cl_val_pin.p, ks, nq, counts.data());
+  }
+  for (int32_t q = 0; q < nq; ++q) {
+    o.counts[q] = counts[(size_t)q];
+    if (o.groups) o.groups[q] = (int64_t)c->cl_cnt_pin[q];
+  }
+  if (o.matched) *o.matched = m;
+  const double write_ms = t_filter.ms();
+  g_collapse_scope_ms[0] = filter_ms >= 0.0 && write_ms >= 0.0 ? filter_ms + write_ms : write_ms;
+  g_collapse_scope_ms[1] = t_gather.ms();
+  g_collapse_scope_ms[2] = t_reduce.ms();
+  g_collapse_scope_ms[3] = t_mark.ms();
+  g_collapse_scope_ms[4] = t_clear.ms();
+  g_collapse_scope_ms[5] = ks > 0 ? t_select.ms() : -1.0;
+  return SVS_OK;
+}
+
+int32_t svs_index_search_collapsed_where(svs_index* idx, const float* queries, int32_t nq, int32_t d, int32_t k, const svs_where_term_t* terms,
+                                         int32_t nterms, int32_t column, int32_t zero_mode, float* out_scores, int64_t* out_rows,
+                                         uint32_t* out_values, int32_t* out_counts, int64_t* out_groups, int64_t* out_matched) {
+  static const char* const kEntry = "svs_index_search_collapsed_where";
+  launch_reset();
+  for (double& ms : g_collapse_scope_ms) ms = -1.0;   // (a call that fails or records nothing leaves no earlier call's times behind)
+  if (!idx) return fail(SVS_ERR_INVALID, "null index");
+  RefGuard guard(idx);
+  std::shared_lock<std::shared_mutex> geo(idx->rw);   // (set_column, mask_rows, compact take it exclusively: the count and the write see the same columns)
+  // ---- everything is validated before anything is written, allocated or launched
+  const ScopedOut o{out_scores, out_rows, out_values, out_counts, out_groups, out_matched};
+  int rc = check_query_args(idx, queries, nq, d);
+  if (rc != SVS_OK || (rc = check_scoped_args(kEntry, nq, k, column, zero_mode, o)) != SVS_OK) return rc;
+  WherePlan plan;
+  if ((rc = plan.build(terms, nterms, kEntry)) != SVS_OK) return rc;
+  if (nq == 0) return SVS_OK;
+  if ((rc = check_gather_rows(idx, kEntry)) != SVS_OK) return rc;
+  HostCall fr(idx);
+  if ((rc = fr.open()) != SVS_OK) return rc;
+  Ctx* const c = fr.c;
+  const int64_t n = idx->n;
+  if ((rc = c->lab_cnt.grow((size_t)label_strips(n) + 2)) != SVS_OK || (rc = c->lab_tot_pin.grow(1)) != SVS_OK) return rc;
+  // 1. the filter goes up, the count runs; the host needs m = |S| to size the list, the table and the score vectors
+  const bool timed = idx->timing.load() > 0;
+  const TimedSpan t_count(timed), t_write(timed);
+  hipStream_t st = fr.stream();
+  WhereFilter f;
+  if ((rc = plan.stage(idx, c, st, &f)) != SVS_OK) return rc;
+  t_count.begin(st);
+  launch_record("where_count_kernel", n, plan.nterms);
+  launch_label_count(f, c->lab_cnt, st);
+  t_count.end(st);
+  HIP_TRY(hipMemcpyAsync(c->lab_tot_pin, c->lab_cnt, sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
+  if ((rc = fr.close(kEntry)) != SVS_OK) return rc;
+  const int64_t m = (int64_t)c->lab_tot_pin[0];
+  if (m < 0 || m > n) return fail(SVS_ERR_DEVICE, "%s: the filter counted %lld of %lld rows", kEntry, (long long)m, (long long)n);
+  if (m == 0) return scoped_empty(o, nq);
+  // 2. one write pass emits the list and the group column beside it
+  if ((rc = c->list_dev.grow((size_t)m)) != SVS_OK || (rc = c->sc_vals.grow((size_t)score_stride(m))) != SVS_OK) return rc;
+  st = fr.stream();
+  if ((rc = upload_queries(c, queries, (size_t)nq * (size_t)d, st)) != SVS_OK) return rc;
+  t_write.begin(st);
+  launch_record("scoped_write_kernel", n, plan.nterms);
+  hipLaunchKernelGGL(label_scan_kernel, dim3(1), dim3(LB_THREADS), 0, st, c->lab_cnt.p + 2, label_strips(n));
+  hipLaunchKernelGGL(scoped_write_kernel, dim3((unsigned)label_strips(n)), dim3(LB_THREADS), 0, st, f, (int)column,
+                     (const uint32_t*)(c->lab_cnt.p + 2), c->list_dev.p, c->sc_vals.p, m);
+  t_write.end(st);
+  return collapse_over_list(idx, fr, kEntry, nq, d, k, m, zero_mode, o, t_write, t_count.ms());
+}
+
+int32_t svs_index_search_collapsed_rows(svs_index* idx, const float* queries, int32_t nq, int32_t d, int32_t k, const int64_t* rows, int64_t nrows,
+                                        int32_t column, int32_t zero_mode, float* out_scores, int64_t* out_rows, uint32_t* out_values,
+                                        int32_t* out_counts, int64_t* out_groups, int64_t* out_matched) {
+  static const char* const kEntry = "svs_index_search_collapsed_rows";
+  launch_reset();
+  for (double& ms : g_collapse_scope_ms) ms = -1.0;
+  if (!idx) return fail(SVS_ERR_INVALID, "null index");
+  RefGuard guard(idx);
+  std::shared_lock<std::shared_mutex> geo(idx->rw);   // (set_column, mask_rows, compact take it exclusively: the list and the column are one state's)
+  // ---- everything is validated before anything is written, allocated or launched
+  const ScopedOut o{out_scores, out_rows, out_values, out_counts, out_groups, out_matched};
+  int rc = check_query_args(idx, queries, nq, d);
+  if (rc != SVS_OK || (rc = check_scoped_args(kEntry, nq, k, column, zero_mode, o)) != SVS_OK) return rc;
+  const int64_t lo = idx->row_offset;
+  bool ascending;
+  if ((rc = check_row_list(rows, nrows, lo, idx->n, &ascending)) != SVS_OK) return rc;
+  if (nq == 0) return SVS_OK;
+  if ((rc = check_gather_rows(idx, kEntry)) != SVS_OK) return rc;
+  if (nrows == 0) return scoped_empty(o, nq);
+  HostCall fr(idx);
+  if ((rc = fr.open()) != SVS_OK) return rc;
+  Ctx* const c = fr.c;
+  // S = the live listed rows, ascending, as local u32 rows in pinned memory (the upload's source): svs_index_search_rows'
+  if ((rc = c->list_pin.grow((size_t)nrows)) != SVS_OK) return rc;
+  int64_t m = 0;
+  try {
+    std::vector<uint32_t> tmp;
+    m = live_rows_ascending(rows, nrows, lo, idx->dead_flag.data(), ascending, tmp, c->list_pin);
+  } catch (const std::bad_alloc&) {
+    return fail(SVS_ERR_NOMEM, "out of host memory for a %lld-row list", (long long)nrows);
+  }
+  if (m == 0) return scoped_empty(o, nq);
+  if ((rc = c->list_dev.grow((size_t)m)) != SVS_OK || (rc = c->sc_vals.grow((size_t)score_stride(m))) != SVS_OK) return rc;
+  const TimedSpan t_filter(idx->timing.load() > 0);
+  const hipStream_t st = fr.stream();
+  if ((rc = upload_queries(c, queries, (size_t)nq * (size_t)d, st)) != SVS_OK) return rc;
+  t_filter.begin(st);
+  HIP_TRY(hipMemcpyAsync(c->list_dev, c->list_pin, (size_t)m * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+  launch_record("scoped_values_kernel", m, 1);
+  hipLaunchKernelGGL(scoped_values_kernel, dim3((unsigned)std::min<int64_t>((m + 255) / 256, 1024)), dim3(256), 0, st,
+                     (const uint32_t*)c->list_dev.p, m, (const uint32_t*)idx->cols[column], c->sc_vals.p);
+  t_filter.end(st);
+  return collapse_over_list(idx, fr, kEntry, nq, d, k, m, zero_mode, o, t_filter, -1.0);
 }
 
 // ---- svs_index_search_collapsed_combined (collapse_combine.h)

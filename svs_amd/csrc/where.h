@@ -92,22 +92,22 @@ __device__ __forceinline__ void where_apply(const WhereTerm& t, const uint4 (&v)
 }
 
 // The calling wave's part of strip `blockIdx.x`: b[j][e] = the ballot of "row row0 + 256 j + 4 lane + e matches";
-// returns the wave's matches.  row0 (out) = the wave's first row.  (The payload is the row: nothing is left in the uint4s.)
-__device__ __forceinline__ int strip_ballots(const WhereFilter& f, const uint32_t* s_set, unsigned long long (&b)[LB_ITERS][4],
-                                             uint4 (&)[LB_ITERS], int64_t* row0) {
+// returns the wave's matches.  row0 (out) = the wave's first row.  load_mask (wave-uniform, a superset of f.col_mask):
+// bit c = column c is loaded; v[j][c] (out) = the lane's four values of column c at step j, zeros where it was not.
+__device__ __forceinline__ int where_ballots(const WhereFilter& f, uint32_t load_mask, const uint32_t* s_set,
+                                             unsigned long long (&b)[LB_ITERS][4], uint4 (&v)[LB_ITERS][WH_COLS], int64_t* row0) {
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int64_t w0 = (int64_t)blockIdx.x * LB_STRIP + (int64_t)wave * LB_WAVE_ROWS;
   *row0 = w0;
-  uint4 v[LB_ITERS][WH_COLS];
   uint32_t dead[LB_ITERS];
 #pragma unroll
   for (int j = 0; j < LB_ITERS; ++j) {   // all requested before the first is used
     const int64_t i = w0 + j * 256 + lane * 4;   // a multiple of 4: one 16-byte load per column, one nibble of a bitmap word
     const bool in = i < f.n;
-    v[j][0] = where_load(f.col0, in && (f.col_mask & 1u), i);
-    v[j][1] = where_load(f.col1, in && (f.col_mask & 2u), i);
-    v[j][2] = where_load(f.col2, in && (f.col_mask & 4u), i);
-    v[j][3] = where_load(f.col3, in && (f.col_mask & 8u), i);
+    v[j][0] = where_load(f.col0, in && (load_mask & 1u), i);
+    v[j][1] = where_load(f.col1, in && (load_mask & 2u), i);
+    v[j][2] = where_load(f.col2, in && (load_mask & 4u), i);
+    v[j][3] = where_load(f.col3, in && (load_mask & 8u), i);
     dead[j] = dead_nibble(in ? f.dead_bits : nullptr, i >> 2);
   }
   int cnt = 0;
@@ -128,6 +128,14 @@ __device__ __forceinline__ int strip_ballots(const WhereFilter& f, const uint32_
     }
   }
   return cnt;
+}
+
+// strip_count's and strip_write's view of it: the columns the terms name.  (The payload is the row: nothing is left in
+// the uint4s.)
+__device__ __forceinline__ int strip_ballots(const WhereFilter& f, const uint32_t* s_set, unsigned long long (&b)[LB_ITERS][4],
+                                             uint4 (&)[LB_ITERS], int64_t* row0) {
+  uint4 v[LB_ITERS][WH_COLS];
+  return where_ballots(f, f.col_mask, s_set, b, v, row0);
 }
 
 // grid = ceil(n / LB_STRIP) workgroups.  counts[blockIdx.x] = the strip's matches; *total += them (zero on entry).

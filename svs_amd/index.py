@@ -761,6 +761,80 @@ class DeviceIndex:
         c = int(counts[0])
         return list(zip(s[0, :c].astype(np.float64).tolist(), r[0, :c].tolist(), v[0, :c].tolist())), int(groups[0])
 
+    def _search_batch_collapsed_scoped(self, native_search, q: np.ndarray, n: int, scope_arg, scope_len: int, scope_rows: Optional[int],
+                                       c: int, mode: int) -> Tuple[np.ndarray, np.ndarray, np.ndarray, np.ndarray, np.ndarray, int]:
+        """``search_batch_collapsed_where`` / ``search_batch_collapsed_within`` once their arguments are checked:
+        ``native_search`` is the bound entry, ``scope_arg`` and ``scope_len`` its two scope arguments (the caller keeps
+        what they point to alive), ``scope_rows`` a bound on the rows in scope the caller knows (None: none)."""
+        nq, d = q.shape
+        h = self._pinned_handle()
+        try:
+            # (clamped before allocating and before the int32 argument, as in search_batch)
+            k = min(max(n, 0), self._live_rows(h), 2 ** 31 - 1 if scope_rows is None else scope_rows)
+            scores = np.empty((nq, k), dtype=np.float32)
+            rows = np.empty((nq, k), dtype=np.int64)
+            values = np.empty((nq, k), dtype=np.uint32)
+            counts = np.zeros(nq, dtype=np.int32)
+            groups = np.zeros(nq, dtype=np.int64)
+            matched = C.c_int64(0)
+            # (the one call that releases the GIL; a count-only call passes no result buffers)
+            _native.check(native_search(h, q.ctypes.data, nq, d, k, scope_arg, scope_len, c, mode,
+                                        scores.ctypes.data if k else None, rows.ctypes.data if k else None,
+                                        values.ctypes.data if k else None, counts.ctypes.data, groups.ctypes.data, C.byref(matched)))
+        finally:
+            self._unpin(h)
+        return scores, rows, values, counts, groups, int(matched.value)
+
+    def search_batch_collapsed_where(self, queries: np.ndarray, n: int, where, column: int,
+                                     zero: str = "single") -> Tuple[np.ndarray, np.ndarray, np.ndarray, np.ndarray, np.ndarray, int]:
+        """``search_batch_collapsed`` inside the scope of a predicate (svs_index_search_collapsed_where): only the live
+        rows on which every term of ``where`` holds (``where_terms``; no term: every live row) are scored and grouped,
+        so a value is represented by its best row IN SCOPE and a value with no row in scope is absent.  Returns
+        ``(scores, rows, values, counts, groups, matched)``: ``search_batch_collapsed``'s five, k = min(max(n, 0), live
+        rows), and matched = how many rows satisfy the predicate.  The scores are the bits ``search_batch_where``
+        reports for those rows.  ``n=0`` only counts."""
+        assert isinstance(n, int)
+        q = self._queries_2d(queries)
+        c = column_index(column)
+        mode = collapse_zero_mode(zero)
+        terms, nterms, keep = pack_where(where)
+        out = self._search_batch_collapsed_scoped(self._lib.svs_index_search_collapsed_where, q, n, terms, nterms, None, c, mode)
+        del keep
+        return out
+
+    def search_collapsed_where(self, query_vec: np.ndarray, n: int, where, column: int,
+                               zero: str = "single") -> Tuple[List[Tuple[float, int, int]], int, int]:
+        """The ``n`` best rows of one query among the rows ``where`` admits, at most one per value of column
+        ``column``: ([(score, row, value)], groups, matched), best first.  See ``search_batch_collapsed_where``."""
+        assert isinstance(n, int)
+        q = _query_1d(query_vec)
+        s, r, v, counts, groups, matched = self.search_batch_collapsed_where(q[None, :], n, where, column, zero)
+        c = int(counts[0])
+        return list(zip(s[0, :c].astype(np.float64).tolist(), r[0, :c].tolist(), v[0, :c].tolist())), int(groups[0]), matched
+
+    def search_batch_collapsed_within(self, queries: np.ndarray, n: int, rows, column: int,
+                                      zero: str = "single") -> Tuple[np.ndarray, np.ndarray, np.ndarray, np.ndarray, np.ndarray, int]:
+        """``search_batch_collapsed`` inside the scope of a row list (svs_index_search_collapsed_rows): ``rows`` are
+        GLOBAL indices, any order, duplicates allowed; masked rows drop out.  Returns what
+        ``search_batch_collapsed_where`` returns, k = min(max(n, 0), listed rows), matched = the distinct live listed
+        rows; the scores are the bits ``search_batch_within`` reports for them."""
+        assert isinstance(n, int)
+        q = self._queries_2d(queries)
+        c = column_index(column)
+        mode = collapse_zero_mode(zero)
+        r = np.ascontiguousarray(rows, dtype=np.int64).reshape(-1)
+        return self._search_batch_collapsed_scoped(self._lib.svs_index_search_collapsed_rows, q, n, r.ctypes.data, len(r), len(r), c, mode)
+
+    def search_collapsed_within(self, query_vec: np.ndarray, n: int, rows, column: int,
+                                zero: str = "single") -> Tuple[List[Tuple[float, int, int]], int, int]:
+        """The ``n`` best rows of one query among the listed rows, at most one per value of column ``column``:
+        ([(score, row, value)], groups, matched), best first.  See ``search_batch_collapsed_within``."""
+        assert isinstance(n, int)
+        q = _query_1d(query_vec)
+        s, r, v, counts, groups, matched = self.search_batch_collapsed_within(q[None, :], n, rows, column, zero)
+        c = int(counts[0])
+        return list(zip(s[0, :c].astype(np.float64).tolist(), r[0, :c].tolist(), v[0, :c].tolist())), int(groups[0]), matched
+
     def assign(self, vectors, labels=None, row0: Optional[int] = None, nrows: Optional[int] = None,
                scores: bool = True) -> Tuple[np.ndarray, Optional[np.ndarray], np.ndarray]:
         """Nearest-vector assignment (svs_index_assign): for each of the GLOBAL rows ``row0 .. row0 + nrows`` (default:

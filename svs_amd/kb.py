@@ -30,7 +30,7 @@ from typing import Any, Awaitable, Callable, Dict, Iterator, List, Optional, Tup
 import numpy as np
 
 from .index import ASSIGN_MAX_VECTORS, COMBINE_MAX_VECTORS, LABELS_MAX_SET, DeviceIndex
-from .matrix import (DeviceEmbeddingsMatrix, above_op, assign_op, batch_op, by_label_op, cluster_op, collapsed_combined_op, collapsed_op, combined_op, diverse_op, labeled_op, neighbors_op, pairs_op, segments_op, single_op, where_op,
+from .matrix import (DeviceEmbeddingsMatrix, above_op, assign_op, batch_op, by_label_op, cluster_op, collapsed_combined_op, collapsed_op, collapsed_where_op, combined_op, diverse_op, labeled_op, neighbors_op, pairs_op, segments_op, single_op, where_op,
                      within_op)
 
 _LOG = logging.getLogger(__name__)
@@ -762,26 +762,42 @@ class KB:
         _LOG.info(f"retrieved top {n} documents")
         return res
 
-    def retrieve_collapsed(self, query: str, n: int) -> List[Dict[str, Any]]:
+    def retrieve_collapsed(self, query: str, n: int, levels=None) -> List[Dict[str, Any]]:
         """``retrieve`` with at most ONE document per parent: the n best documents after every parent's children are
         represented by the best of them -- "the 10 best sections, one per chapter" -- same log lines and result shape.
         A document without a parent stands for itself.  ``parent_id + 1`` sits next to each vector in HBM in column
         ``PARENT_COLUMN`` (0 = no parent), the column ``retrieve_under`` installs and maintains, and the grouping runs
         on the device in the query's one corpus pass (svs_index_search_collapsed): no over-fetching, and a parent that
-        holds the best 500 documents still yields one."""
+        holds the best 500 documents still yields one.
+        Without ``levels`` every level of the tree is grouped at once: a root stands for itself, its children are one
+        group and each child's children another, so one subtree can take several places.  ``levels`` (an int or an
+        iterable of ints as in ``retrieve_at_level``) keeps the search inside those levels: only their documents are
+        scored, and a parent is represented by its best child THERE (svs_index_search_collapsed_where over the level
+        column and the parent column); the third log line then counts the documents of those levels.  A level no
+        document has gives ``[]``."""
+        labels = None if levels is None else _level_labels(levels)
         _LOG.info(f"retrieving {n} documents with query string: {query}")
         assert self.db is not None
         self.embeddings_matrix.get_sync(self.db)
 
-        def parents_from_store():
-            with self.db.transaction():
-                return self.db.embedding_parents()
+        def from_store(read):
+            def fetch():
+                with self.db.transaction():
+                    return read()
+            return fetch
 
-        self.embeddings_matrix.ensure_column(PARENT_COLUMN, parents_from_store)
+        self.embeddings_matrix.ensure_column(PARENT_COLUMN, from_store(self.db.embedding_parents))
+        if labels is not None:
+            self.embeddings_matrix.ensure_labels(from_store(self.db.embedding_levels))
         query_vec = np.array(self._embed([query])[0], dtype=np.float32)
         _LOG.info("got embedding for query!")
-        hits, _ = self.embeddings_matrix.search_collapsed(query_vec, n, PARENT_COLUMN, "single")   # one pass + grouping: HIP
-        _LOG.info(f"computed {self.embeddings_matrix.index.shape[0]} cosine similarities")
+        if labels is None:
+            hits, _ = self.embeddings_matrix.search_collapsed(query_vec, n, PARENT_COLUMN, "single")   # one pass + grouping: HIP
+            _LOG.info(f"computed {self.embeddings_matrix.index.shape[0]} cosine similarities")
+        else:
+            hits, _, matched = self.embeddings_matrix.search_collapsed_where(query_vec, n, [(0, "in", labels)], PARENT_COLUMN,
+                                                                             "single")   # filter + gather + grouping: HIP
+            _LOG.info(f"computed {matched} cosine similarities")
         with self.db.transaction():
             res = _fetch_list(self.db, [(score, emb_id) for score, emb_id, _ in hits])
         _LOG.info(f"retrieved top {n} documents")
@@ -1274,16 +1290,27 @@ class AsyncKB:
         _LOG.info(f"retrieved top {n} documents")
         return res
 
-    async def retrieve_collapsed(self, query: str, n: int) -> List[Dict[str, Any]]:
-        """Async twin of ``KB.retrieve_collapsed``, structured as ``retrieve_under``: the parent column is installed
-        (when this index generation lacks it) and the reference to the matrix is taken under the lock, the collapsed
-        search runs on an executor thread outside it, the docs are fetched under the lock."""
+    async def retrieve_collapsed(self, query: str, n: int, levels=None) -> List[Dict[str, Any]]:
+        """Async twin of ``KB.retrieve_collapsed``, structured as ``retrieve_under``: the columns are installed (when
+        this index generation lacks them) and the reference to the matrix is taken under the lock, the collapsed search
+        runs on an executor thread outside it, the docs are fetched under the lock."""
+        labels = None if levels is None else _level_labels(levels)
         _LOG.info(f"retrieving {n} documents with query string: {query}")
-        async with self._held(lambda db: self.embeddings_matrix.ensure_column(PARENT_COLUMN, db.embedding_parents)) as (held, _):
+
+        def install(db):
+            self.embeddings_matrix.ensure_column(PARENT_COLUMN, db.embedding_parents)
+            if labels is not None:
+                self.embeddings_matrix.ensure_labels(db.embedding_levels)
+
+        async with self._held(install) as (held, _):
             query_vec = np.array((await self._embed([query]))[0], dtype=np.float32)
             _LOG.info("got embedding for query!")
-            hits, _ = await self._search(held, collapsed_op(query_vec, n, PARENT_COLUMN, "single"))
-            _LOG.info(f"computed {held[0].shape[0]} cosine similarities")
+            if labels is None:
+                hits, _ = await self._search(held, collapsed_op(query_vec, n, PARENT_COLUMN, "single"))
+                _LOG.info(f"computed {held[0].shape[0]} cosine similarities")
+            else:
+                hits, _, matched = await self._search(held, collapsed_where_op(query_vec, n, [(0, "in", labels)], PARENT_COLUMN, "single"))
+                _LOG.info(f"computed {matched} cosine similarities")
         res = await self._fetch(lambda db: _fetch_list(db, [(score, emb_id) for score, emb_id, _ in hits]))
         _LOG.info(f"retrieved top {n} documents")
         return res

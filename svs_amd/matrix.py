@@ -248,6 +248,34 @@ def collapsed_op(query_vec: np.ndarray, n: int, column: int, zero: str = "single
     return native, finish
 
 
+def _collapsed_scoped_finish(res, arr):
+    """([(score, row, value)], groups, matched) of a scoped collapsed search, rows -> ids."""
+    used, (rows, groups, matched) = res
+    off = int(getattr(used, "row_offset", 0))
+    return [(score, int(arr[row - off]), int(value)) for score, row, value in rows], int(groups), int(matched)
+
+
+def collapsed_where_op(query_vec: np.ndarray, n: int, where, column: int, zero: str = "single"):
+    """Collapsed search under a predicate: ``idx.search_collapsed_where`` (svs_index_search_collapsed_where), at most
+    one row per value of column ``column`` among the rows on which every term of ``where`` holds, rows -> ids:
+    ([(score, emb_id, value)], groups, rows that satisfy the predicate).  The columns are whatever the index holds
+    (``DeviceEmbeddingsMatrix.ensure_column``)."""
+    def native(idx, lookup, *_):
+        return idx, idx.search_collapsed_where(query_vec, n, where, column, zero)
+
+    return native, _collapsed_scoped_finish
+
+
+def collapsed_within_op(query_vec: np.ndarray, n: int, emb_ids, column: int, zero: str = "single"):
+    """Collapsed search over ``emb_ids``: ids -> rows through ``lookup.arr``, ``idx.search_collapsed_within``
+    (svs_index_search_collapsed_rows), rows -> ids: ([(score, emb_id, value)], groups, live listed rows).  KeyError for
+    an id the loaded matrix does not hold."""
+    def native(idx, lookup, *_):
+        return idx, idx.search_collapsed_within(query_vec, n, _within_rows(idx, lookup, emb_ids), column, zero)
+
+    return native, _collapsed_scoped_finish
+
+
 def collapsed_combined_op(vectors: np.ndarray, n: int, column: int, op: str = "max", weights=None, zero: str = "single"):
     """Group-combined search: ``idx.search_collapsed_combined`` (svs_index_search_collapsed_combined) of the (m, D)
     ``vectors`` over the groups of column ``column``, representative rows -> ids: ([(score, emb_id, value)], groups)."""
@@ -676,6 +704,19 @@ class DeviceEmbeddingsMatrix:
         best one: ([(score, emb_id, value)], how many values -- and, with ``zero="single"``, value-0 embeddings -- have
         a live embedding) (``KB.retrieve_collapsed``).  Call ``ensure_column`` for the column first."""
         return self.run_mapped(collapsed_op(query_vec, n, column, zero))
+
+    def search_collapsed_where(self, query_vec: np.ndarray, n: int, where, column: int,
+                               zero: str = "single") -> Tuple[List[Tuple[float, int, int]], int, int]:
+        """``search_collapsed`` among the stored embeddings on which every term of ``where`` holds: ([(score, emb_id,
+        value)], groups, how many satisfy the predicate) (``KB.retrieve_collapsed`` with levels).  Call
+        ``ensure_column`` for every column named first."""
+        return self.run_mapped(collapsed_where_op(query_vec, n, where, column, zero))
+
+    def search_collapsed_within(self, query_vec: np.ndarray, n: int, emb_ids, column: int,
+                                zero: str = "single") -> Tuple[List[Tuple[float, int, int]], int, int]:
+        """``search_collapsed`` among the listed embedding ids: ([(score, emb_id, value)], groups, live listed
+        embeddings).  Call ``ensure_column`` for the column first."""
+        return self.run_mapped(collapsed_within_op(query_vec, n, emb_ids, column, zero))
 
     def search_diverse(self, query_vec: np.ndarray, n: int, fetch_k: Optional[int] = None,
                        lam: float = 0.5) -> List[Tuple[float, int, float]]:

@@ -224,6 +224,16 @@ class MultiDeviceIndex:
 
     search_batch_collapsed = search_collapsed
 
+    def search_collapsed_where(self, query_vec: np.ndarray, n: int, where, column: int, zero: str = "single"):
+        raise NotImplementedError("collapsed search under a predicate is per device: the columns sit beside one shard's rows and a value's rows may lie on several; call set_column / search_collapsed_where on a DeviceIndex")
+
+    search_batch_collapsed_where = search_collapsed_where
+
+    def search_collapsed_within(self, query_vec: np.ndarray, n: int, rows, column: int, zero: str = "single"):
+        raise NotImplementedError("collapsed search over a row list is per device: the columns sit beside one shard's rows and a value's rows may lie on several; call set_column / search_collapsed_within on a DeviceIndex")
+
+    search_batch_collapsed_within = search_collapsed_within
+
     def set_labels(self, labels, row0: Optional[int] = None):
         raise NotImplementedError("labels are per device: call set_labels on a DeviceIndex")
 

@@ -220,6 +220,16 @@ class ShardedIndex:
 
     search_batch_collapsed = search_collapsed
 
+    def search_collapsed_where(self, query_vec: np.ndarray, n: int, where, column: int, zero: str = "single"):
+        raise NotImplementedError("collapsed search under a predicate is per device: a rank fills and searches the columns of its own shard (DeviceIndex.search_collapsed_where); groups are not merged across ranks")
+
+    search_batch_collapsed_where = search_collapsed_where
+
+    def search_collapsed_within(self, query_vec: np.ndarray, n: int, rows, column: int, zero: str = "single"):
+        raise NotImplementedError("collapsed search over a row list is per device: a rank fills and searches the columns of its own shard (DeviceIndex.search_collapsed_within); groups are not merged across ranks")
+
+    search_batch_collapsed_within = search_collapsed_within
+
     def search_combined(self, vectors: np.ndarray, n: int, op: str = "max", weights=None):
         raise NotImplementedError("combined search is per device: a shard answers over its own rows (DeviceIndex.search_combined); nothing is merged across shards")
 
