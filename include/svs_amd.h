@@ -50,7 +50,14 @@ typedef enum svs_dtype {
                         f32 path on the dequantised corpus and query. */
   SVS_DTYPE_FP8 = 2  /* extension for BASELINE.json configs[4]: OCP e4m3fn rows with one f32 scale per
                         row (max|x| -> 448), queries quantised the same way; score = scale_row *
-                        scale_query * sum(q8 * q8) accumulated in f32.  Same oracle rule.  (Batches of more
+                        scale_query * sum(q8 * q8) accumulated in f32.  Same oracle rule.
+                        scale = max(max|x|, 7 * 2^-120) / 448 (NaN elements skipped; 1 for an all-zero
+                        row), q8 = e4m3(x * (1 / scale)), round to nearest even.  The floor keeps the scale at
+                        or above 2^-126 so that every finite row reads back finite and zeros read back as zeros
+                        (|stored - x| <= 17 * max(max|x|, 7 * 2^-120) / 448); elements of a row below the floor
+                        quantise against the floor, possibly to zero.  A NaN element is stored as NaN and does
+                        not touch its row's scale.  A row, or query, with an INFINITE element gets scale inf:
+                        every element of it reads back as NaN, and NaN ranks first.  (Batches of more
                         than 16 queries run on the fp8 matrix instruction, whose internal sum of 128 products
                         keeps ~13 bits below the largest one: scores within 3e-6 of the exact dot product of the
                         quantised values on unit-norm data, up to 1.4e-4 relative when a single product

@@ -174,6 +174,7 @@ INTERNAL = {
     "svs_internal_collapsed_combined_kernel_ms": (C.c_int32, [C.POINTER(C.c_double)]),
     "svs_internal_score_pass_ms": (C.c_int32, [C.POINTER(C.c_double)]),
     "svs_internal_compact": (C.c_int32, [_P, C.c_int64, _P, C.c_int64, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
+    "svs_internal_stored_image": (C.c_int32, [_P, C.c_int32, C.c_int64, C.c_int64, _P, C.c_int64]),
 }
 
 _lib: Optional[C.CDLL] = None

@@ -3,7 +3,12 @@
 // scale per row: unit-norm rows have |x| ~ 1/sqrt(d) ~ 0.02, at the very bottom
 // of e4m3's normal range (2^-6), so each row is scaled to put its largest
 // magnitude on 448 (the e4m3 maximum) before rounding (RNE):
-//     scale_i = max_d |M[i,d]| / 448        q8[i,d] = e4m3(M[i,d] / scale_i)
+//     scale_i = max(max_d |M[i,d]|, 7 * 2^-120) / 448        q8[i,d] = e4m3(M[i,d] * (1 / scale_i))
+// (the maximum skips NaN elements; a row whose maximum is 0 gets scale 1).  The floor under the maximum keeps the
+// scale at or above 2^-126, so that 1 / scale_i is finite for every finite row: without it a row with
+// 0 < max|x| < 448 / FLT_MAX had 1 / scale = inf and was stored as NaN throughout.  Elements of a row below the floor
+// quantise against the floor, the smallest of them to zero; every row at or above it stores what it did without it.
+// A row with an infinite element has scale inf and reads back as NaN.
 // Queries are quantised the same way.  A score is
 //     scale_i * scale_q * sum_d f32(q8[i,d]) * f32(q8q[d])      (f32 accumulate)
 // and the parity oracle for this dtype is numpy's f32 path on the DEQUANTISED
@@ -21,6 +26,7 @@ typedef float f32x2_t __attribute__((ext_vector_type(2)));
 typedef uint32_t u32x4_t __attribute__((ext_vector_type(4)));
 
 constexpr float FP8_MAX = 448.0f;
+constexpr float FP8_MIN_ROW_MAX = 0x1.cp-118f;   // 7 * 2^-120: FP8_MIN_ROW_MAX / FP8_MAX = 2^-126, the smallest scale
 
 // 4 floats -> 4 packed e4m3 bytes (RNE)
 __device__ __forceinline__ uint32_t pack_fp8x4(float a, float b, float c, float d) {
@@ -49,7 +55,7 @@ __global__ __launch_bounds__(256) void quantize_rows_fp8_kernel(
     for (int c = lane; c < d; c += 64) mx = fmaxf(mx, fabsf(s[c]));
 #pragma unroll
     for (int off = 32; off > 0; off >>= 1) mx = fmaxf(mx, __shfl_xor(mx, off, 64));
-    const float scale = mx > 0.f ? mx / FP8_MAX : 1.0f;
+    const float scale = mx > 0.f ? fmaxf(mx, FP8_MIN_ROW_MAX) / FP8_MAX : 1.0f;
     const float inv = 1.0f / scale;
     if (lane == 0) scales[row] = scale;
     uint32_t* o = (uint32_t*)(dst + row * ld8);

@@ -180,6 +180,14 @@ int32_t svs_internal_score_pass_ms(double* out);
  * stage; -1 where that call recorded none (tools/collapsed_combined_time.py).  The kernels share the geometry
  * svs_internal_collapse_geometry reports. */
 int32_t svs_internal_collapsed_combined_kernel_ms(double* out);
+/* What ingest left in HBM, byte for byte (tests/test_ingest_image_gpu.py): plain device-to-host copies behind
+ * staging_wait and under the shared geometry lock, no kernel, nothing left on a stream.  Rows [row0, row0 + nrows) of
+ *   what 0  the corpus rows: nrows * ld * element bytes, the padding columns from d to ld included;
+ *   what 1  the fp8 row scales: nrows floats;
+ *   what 2  the half shadow of an f32 index: nrows * ld * 2 bytes.
+ * SVS_ERR_UNSUPPORTED when the index has no such image (scales of an f32 / f16 index, no shadow); SVS_ERR_INVALID for a
+ * null index or out, an unknown what, a range outside [0, n) or a capacity_bytes smaller than the image. */
+int32_t svs_internal_stored_image(svs_index* idx, int32_t what, int64_t row0, int64_t nrows, void* out, int64_t capacity_bytes);
 /* multi.hip -> svs_amd.hip: carries a worker thread's error message over to the caller's thread */
 int32_t svs_internal_set_error(int32_t code, const char* msg);
 #ifdef __cplusplus

@@ -5244,6 +5244,27 @@ int32_t svs_index_debug_query(svs_index* idx, const float* query, int32_t d, flo
   return rc;
 }
 
+// The bytes of an image as they lie in HBM (internal.h): device-to-host copies only, no kernel, so that the tests read
+// what ingest wrote without going through the library's own decoders.
+int32_t svs_internal_stored_image(svs_index* idx, int32_t what, int64_t row0, int64_t nrows, void* out, int64_t capacity_bytes) {
+  if (!idx || !out) return fail(SVS_ERR_INVALID, "null argument");
+  if (what < 0 || what > 2) return fail(SVS_ERR_INVALID, "unknown image %d", what);
+  HIP_TRY(hipSetDevice(idx->device));
+  { int rc = staging_wait(idx); if (rc != SVS_OK) return rc; }
+  std::shared_lock<std::shared_mutex> geo(idx->rw);   // (appends, commits and compactions take it exclusively: n and the pointers stand still)
+  const void* base = what == 0 ? idx->rows : (what == 1 ? (const void*)idx->row_scales : idx->shadow);
+  if (what == 1 && idx->dtype != SVS_DTYPE_FP8) return fail(SVS_ERR_UNSUPPORTED, "only an fp8 index has row scales");
+  if (what == 2 && !idx->shadow) return fail(SVS_ERR_UNSUPPORTED, "the index has no half shadow");
+  if (row0 < 0 || nrows < 0 || row0 > idx->n || nrows > idx->n - row0) return fail(SVS_ERR_INVALID, "row range out of bounds");
+  const size_t row_b = what == 0 ? (size_t)idx->ld * elem_bytes(idx) : (what == 1 ? sizeof(float) : (size_t)idx->ld * sizeof(_Float16));
+  const size_t bytes = (size_t)nrows * row_b;
+  if (capacity_bytes < 0 || (uint64_t)capacity_bytes < bytes)
+    return fail(SVS_ERR_INVALID, "the image takes %zu bytes, the buffer holds %lld", bytes, (long long)capacity_bytes);
+  if (bytes == 0) return SVS_OK;
+  HIP_TRY(hipMemcpy(out, (const char*)base + (size_t)row0 * row_b, bytes, hipMemcpyDeviceToHost));
+  return SVS_OK;
+}
+
 int32_t svs_index_set_timing(svs_index* idx, int32_t enable) {
   if (!idx) return fail(SVS_ERR_INVALID, "null index");
   idx->timing.store(enable > 0 ? enable : 0);

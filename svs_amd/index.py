@@ -1297,6 +1297,23 @@ class DeviceIndex:
         return {"screened": int(out[0]), "fallback": int(out[1]), "shadow": int(out[2]), "paused": bool(out[3]),
                 "E": f(out[4]), "n_cand": int(out[5]), "A": f(out[6]), "B": f(out[7]), "C": f(out[8])}
 
+    def stored_image(self, what: str = "rows", row0: int = 0, nrows: Optional[int] = None) -> np.ndarray:
+        """Rows [row0, row0 + nrows) of an image byte for byte as it lies in HBM, copied without any kernel
+        (svs_internal_stored_image; tests).  ``"rows"``: u8 (nrows, ld * element bytes), the padding columns included;
+        ``"scales"``: f32 (nrows,), fp8 only; ``"shadow"``: u16 (nrows, ld), the half shadow of an f32 index.
+        NotImplementedError when the index has no such image."""
+        which = {"rows": 0, "scales": 1, "shadow": 2}[what]
+        nrows = self.n - row0 if nrows is None else nrows
+        if which == 0:
+            out = np.empty((max(nrows, 0), self.ld * {"f32": 4, "f16": 2, "fp8": 1}[self.dtype]), dtype=np.uint8)
+        elif which == 1:
+            out = np.empty(max(nrows, 0), dtype=np.float32)
+        else:
+            out = np.empty((max(nrows, 0), self.ld), dtype=np.uint16)
+        _native.check(self._lib.svs_internal_stored_image(self._handle(), which, int(row0), int(nrows),
+                                                          out.ctypes.data_as(C.c_void_p), out.nbytes))
+        return out
+
     # -- the top-k stage alone on caller-given data (svs_amd/csrc/internal.h; tests) ----------------
     def select_scores(self, scores: np.ndarray, k: int, row_offset: int = 0) -> Tuple[np.ndarray, np.ndarray, int, int]:
         """run_select over host ``scores`` (nq, n): (scores f32 (nq, k), rows i64 (nq, k), count, dirty scratch words)
