@@ -78,7 +78,8 @@ __global__ __launch_bounds__(256) void combine_scores_kernel(float* __restrict__
 // ---- fused route ------------------------------------------------------------------------------------------------------
 // Common to the three: workgroup b owns rows [b * WPB * R, (b + 1) * WPB * R), wave w of it R consecutive rows; a wave
 // past the last row leaves at once (no barrier anywhere); rows past n are clamped to the last row and their result is
-// not stored; lane r < R stores row0 + r.
+// not stored; lane r < R stores row0 + r.  The f32 and fp8 row loads are spelled in every kernel: lifted into helpers
+// like load_rows_f16 they changed the scalar address code of 26 f32 and 4 fp8 instantiations (both families).
 
 // f32, ld == NSTEP * 256 floats.  q: the m vectors as the single-query kernel reads one, [m][ld] floats, 16-byte aligned.
 template <int NSTEP, int R, int WPB>

@@ -26,6 +26,7 @@
 #include <string>
 #include <thread>
 #include <type_traits>
+#include <utility>
 #include <vector>
 
 #include "fp8.h"
@@ -278,12 +279,13 @@ struct Ctx {
   // count, EMPTY (all zero) between queries and between calls -- cl_clean is false from a query's first insert until
   // the fill behind its mark kernel is enqueued, so a call that left early is repaired by the next one; the queries'
   // survivor counters and their pinned copy; the values of the returned rows (scores and rows: out_s_pin / out_r_pin).
+  // All four collapse entries use them through CollapseFrame, the only writer of cl_clean and cc_clean.
   DevBuf<unsigned long long> cl_tab;
   bool cl_clean = true;
   DevBuf<unsigned long long> cl_cnt; PinBuf<unsigned long long> cl_cnt_pin;
   PinBuf<uint32_t> cl_val_pin;
   // svs_index_search_collapsed_combined (collapse_combine.h): beside cl_tab, m per-vector keys for every slot, EMPTY
-  // (all zero) between queries and between calls under a flag of its own -- svs_index_search_collapsed repairs only cl_tab
+  // (all zero) between queries and between calls under a flag of its own -- the entries without keys repair only cl_tab
   DevBuf<uint32_t> cc_keys;
   bool cc_clean = true;
   // svs_index_search_collapsed_where / _rows (collapse_scope.h): the group column compacted beside list_dev, padded to
@@ -642,6 +644,12 @@ auto with_bool(bool flag, F&& f) {
   return flag ? f(std::true_type{}) : f(std::false_type{});
 }
 
+// f(Int<n>) for n in 1 .. sizeof...(I): a run-time step count as a template argument; false: n is outside
+template <class F, int... I>
+bool for_steps(int n, F&& f, std::integer_sequence<int, I...>) {
+  return ((n == I + 1 && (f(Int<I + 1>{}), true)) || ...);
+}
+
 // f(Int<T>): the lanes that share a row of `units` 16-byte (generic kernels: their own) units -- the smallest
 // power of two that covers it, 64 (a whole wave, looping) beyond
 template <class F>
@@ -743,6 +751,12 @@ void launch_persistent(const svs_index* idx, const float* q, float* scores, hipS
 // Default geometry per row length (measured at NSTEP = 6: one-shot, 16-wave
 // workgroups, one row per wave, nontemporal loads: 7.2 TB/s on MI355X).
 // Short rows take several rows per wave so a wave still has >= 4 KiB in flight.
+// The fused f32 kernels of combine.h take the same geometry.
+constexpr int f32_rows_r(int nstep) { return nstep <= 2 ? 4 : (nstep <= 4 ? 2 : 1); }
+constexpr int f32_rows_wpb(int nstep) { return nstep <= 6 ? 16 : 8; }
+// f(Int<NSTEP>) for the f32 one-shot kernels of rows of nstep x 256 floats; false: they have none
+template <class F>
+bool for_f32_rows(int nstep, F&& f) { return for_steps(nstep, f, std::make_integer_sequence<int, 16>{}); }
 template <int NSTEP>
 void launch_rows(const svs_index* idx, const float* q, float* scores, hipStream_t st, int variant, const PassOpts& o) {
   switch (variant) {
@@ -753,10 +767,7 @@ void launch_rows(const svs_index* idx, const float* q, float* scores, hipStream_
     case VARIANT_GEMV_1X8: launch_oneshot<NSTEP, 1, 8, true>(idx, q, scores, st, o); return;
     default: break;
   }
-  if constexpr (NSTEP <= 2) launch_oneshot<NSTEP, 4, 16, true>(idx, q, scores, st, o);
-  else if constexpr (NSTEP <= 4) launch_oneshot<NSTEP, 2, 16, true>(idx, q, scores, st, o);
-  else if constexpr (NSTEP <= 6) launch_oneshot<NSTEP, 1, 16, true>(idx, q, scores, st, o);
-  else launch_oneshot<NSTEP, 1, 8, true>(idx, q, scores, st, o);
+  launch_oneshot<NSTEP, f32_rows_r(NSTEP), f32_rows_wpb(NSTEP), true>(idx, q, scores, st, o);
 }
 
 // The grid of the loop kernels: T lanes per row, four waves per workgroup, at most eight workgroups per CU
@@ -797,14 +808,7 @@ int thin_grid_rows_f16(const svs_index* idx) {
 }
 // f(Int<NSTEP>) for the f16 one-shot kernel of rows of nstep x 512 halves; false: it has none
 template <class F>
-bool for_f16_oneshot(int nstep, F&& f) {
-  switch (nstep) {
-#define SVS_ROWS_CASE(N) case N: f(Int<N>{}); return true;
-    SVS_ROWS_CASE(1) SVS_ROWS_CASE(2) SVS_ROWS_CASE(3) SVS_ROWS_CASE(4) SVS_ROWS_CASE(5) SVS_ROWS_CASE(6) SVS_ROWS_CASE(7) SVS_ROWS_CASE(8)
-#undef SVS_ROWS_CASE
-    default: return false;
-  }
-}
+bool for_f16_oneshot(int nstep, F&& f) { return for_steps(nstep, f, std::make_integer_sequence<int, 8>{}); }
 // ... of the index's shareable passes (0: its row length does not share)
 int thin_grid_of(const svs_index* idx) {
   int grid = 0;
@@ -950,16 +954,7 @@ int launch_route(const svs_index* idx, const Ctx* c, const SingleRoute& r, const
     case SingleRoute::F16_ONESHOT: ok = for_f16_oneshot(r.geo, [&](auto ns) { launch_rows_f16<ns()>(idx, half_rows_of(idx, r), (const float*)q, scores, st, o); }); break;
     case SingleRoute::F16_UNROLLED: ok = launch_unrolled(idx, q, r.geo, scores, st, DotF16{}, o); break;
     case SingleRoute::F16_GENERIC: for_width(r.geo, [&](auto t) { launch_generic_f16<t()>(idx, (const _Float16*)q, scores, st, o); }); break;
-    case SingleRoute::F32_ROWS:
-      switch (r.geo) {
-#define SVS_ROWS_CASE(N) case N: launch_rows<N>(idx, (const float*)q, scores, st, r.variant, o); break;
-        SVS_ROWS_CASE(1) SVS_ROWS_CASE(2) SVS_ROWS_CASE(3) SVS_ROWS_CASE(4) SVS_ROWS_CASE(5) SVS_ROWS_CASE(6)
-        SVS_ROWS_CASE(7) SVS_ROWS_CASE(8) SVS_ROWS_CASE(9) SVS_ROWS_CASE(10) SVS_ROWS_CASE(11) SVS_ROWS_CASE(12)
-        SVS_ROWS_CASE(13) SVS_ROWS_CASE(14) SVS_ROWS_CASE(15) SVS_ROWS_CASE(16)
-#undef SVS_ROWS_CASE
-        default: ok = false;
-      }
-      break;
+    case SingleRoute::F32_ROWS: ok = for_f32_rows(r.geo, [&](auto ns) { launch_rows<ns()>(idx, (const float*)q, scores, st, r.variant, o); }); break;
     case SingleRoute::F32_UNROLLED: ok = launch_unrolled(idx, q, r.geo, scores, st, DotF32{}, o); break;
     case SingleRoute::F32_GENERIC: for_width(r.geo, [&](auto t) { launch_generic<t()>(idx, (const float*)q, scores, st, o); }); break;
   }
@@ -2312,15 +2307,19 @@ struct CombineRoute {
   bool has_fused;       // the row length has a fused kernel
   SingleRoute single;
 };
-// The default geometry of launch_rows (variant 0), which the fused f32 kernel shares
-constexpr int f32_rows_r(int nstep) { return nstep <= 2 ? 4 : (nstep <= 4 ? 2 : 1); }
-constexpr int f32_rows_wpb(int nstep) { return nstep <= 6 ? 16 : 8; }
+// The fused kernels' names, as c++filt prints them: the geometry is the single-query one-shot kernels' (f32: launch_rows' default)
 template <int NSTEP>
 constexpr KernelName kCombineF32Name = kernel_name("combine_f32_kernel", NSTEP, f32_rows_r(NSTEP), f32_rows_wpb(NSTEP));
 template <int NSTEP>
 constexpr KernelName kCombineF16Name = kernel_name("combine_f16_kernel", NSTEP, f16_rows_r(NSTEP), f16_rows_wpb(NSTEP));
 template <int NSTEP, int LB, int R>
 constexpr KernelName kCombineFp8Name = kernel_name("combine_fp8_kernel", NSTEP, LB, R, 16);
+template <int NSTEP>
+constexpr KernelName kMultiScoreF32Name = kernel_name("multi_score_f32_kernel", NSTEP, f32_rows_r(NSTEP), f32_rows_wpb(NSTEP));
+template <int NSTEP>
+constexpr KernelName kMultiScoreF16Name = kernel_name("multi_score_f16_kernel", NSTEP, f16_rows_r(NSTEP), f16_rows_wpb(NSTEP));
+template <int NSTEP, int LB, int R>
+constexpr KernelName kMultiScoreFp8Name = kernel_name("multi_score_fp8_kernel", NSTEP, LB, R, 16);
 
 // Where the fused route is the default, per dtype and m: where it was measured FASTER than the passes (1M x 1536,
 // profiles/combined_time.txt) -- from two vectors on, in all three dtypes.  One vector: a tie within the
@@ -2338,10 +2337,19 @@ CombineRoute combine_route(const svs_index* idx, int variant, int m, int force) 
   return CombineRoute{fused, has, s};
 }
 
-// One combined query into c->scores[0 .. n), unmasked.  v: its m vectors on the device, [m][d]; w: its m weights on the
-// device.  c->scores holds m * sstride floats (the passes route's m score vectors; the combined one ends up in the first).
-int enqueue_combined_scores(const svs_index* idx, Ctx* c, const CombineRoute& r, const float* v, const float* w, int m, int op, int64_t sstride,
-                            hipStream_t st) {
+// Where the scores of a combined query's m vectors go
+struct ScoreSink {
+  bool fold;        // folded under (w, op) into c->scores[0 .. n); else vector j's stored apart, at c->scores[j * sstride ..)
+  const float* w;   // fold: the query's m weights on the device
+  int op;
+};
+constexpr ScoreSink kStoreScores{false, nullptr, 0};
+
+// The m vectors of one combined query scored on route r, unmasked, into the sink.  v: the vectors on the device, [m][d].
+// c->scores holds m * sstride floats (a fused fold needs one vector's; the passes' fold ends up in the first of the m).
+// One staging and one geometry per dtype; the sink picks between the two families of fused kernels (combine.h).
+int enqueue_vector_scores(const svs_index* idx, Ctx* c, const CombineRoute& r, const float* v, int m, int64_t sstride, const ScoreSink& sink,
+                          hipStream_t st) {
   const int64_t n = idx->n;
   int rc;
   if (!r.fused) {
@@ -2349,118 +2357,53 @@ int enqueue_combined_scores(const svs_index* idx, Ctx* c, const CombineRoute& r,
       launch_record("gemv", n, 1);
       if ((rc = launch_scores(idx, c, r.single, v + (size_t)j * idx->d, c->scores + (size_t)j * sstride, st)) != SVS_OK) return rc;
     }
+    if (!sink.fold) return SVS_OK;
     launch_record("combine_scores_kernel", n, m);
     const int64_t n4 = sstride >> 2;
-    hipLaunchKernelGGL(combine_scores_kernel, dim3((unsigned)std::min<int64_t>((n4 + 255) / 256, 4096)), dim3(256), 0, st, c->scores.p, sstride, n4, m, w, op);
+    hipLaunchKernelGGL(combine_scores_kernel, dim3((unsigned)std::min<int64_t>((n4 + 255) / 256, 4096)), dim3(256), 0, st, c->scores.p, sstride, n4, m, sink.w,
+                       sink.op);
     return SVS_OK;
   }
+  // The sink's kernel of a family over the one-shot grid: the rows and the staged vectors, then what the sink adds
+  const auto launch = [&](const KernelName& fold_name, auto fold_kernel, const KernelName& store_name, auto store_kernel, int rows_per_block, int threads,
+                          auto... rows_and_vectors) {
+    const dim3 grid((unsigned)((n + rows_per_block - 1) / rows_per_block));
+    launch_record(sink.fold ? fold_name.s : store_name.s, n, m);
+    if (sink.fold) hipLaunchKernelGGL(fold_kernel, grid, dim3(threads), 0, st, rows_and_vectors..., sink.w, m, sink.op, c->scores.p, n);
+    else hipLaunchKernelGGL(store_kernel, grid, dim3(threads), 0, st, rows_and_vectors..., m, c->scores.p, sstride, n);
+  };
+  bool ok;
   if (r.single.family == SingleRoute::FP8_ONESHOT) {
     if ((rc = stage_queries_fp8(idx, c, v, m, m, false, st)) != SVS_OK) return rc;
-    for_fp8_oneshot(idx->ld, [&](auto ns, auto lb, auto rr) {
+    ok = for_fp8_oneshot(idx->ld, [&](auto ns, auto lb, auto rr) {
       constexpr int NSTEP = ns(), LB = lb(), R = rr();
-      launch_record(kCombineFp8Name<NSTEP, LB, R>.s, n, m);
-      hipLaunchKernelGGL((combine_fp8_kernel<NSTEP, LB, R, 16>), dim3((unsigned)((n + R * 16 - 1) / (R * 16))), dim3(16 * 64), 0, st, (const uint8_t*)idx->rows,
-                         (const float*)idx->row_scales, (const uint8_t*)c->q8.p, (const float*)c->q8s.p, w, m, op, c->scores.p, n);
+      launch(kCombineFp8Name<NSTEP, LB, R>, combine_fp8_kernel<NSTEP, LB, R, 16>, kMultiScoreFp8Name<NSTEP, LB, R>, multi_score_fp8_kernel<NSTEP, LB, R, 16>,
+             R * 16, 16 * 64, (const uint8_t*)idx->rows, (const float*)idx->row_scales, (const uint8_t*)c->q8.p, (const float*)c->q8s.p);
     });
-    return SVS_OK;
-  }
-  // f32 / f16: the vectors as ld floats each, 16-byte aligned -- the caller's where the rows are not padded
-  const float* q = v;
-  if (idx->ld != idx->d || (((uintptr_t)v) & 15) != 0) {
-    if ((rc = c->q16.grow((size_t)GQ * idx->ld)) != SVS_OK) return rc;
-    HIP_TRY(hipMemsetAsync(c->q16, 0, (size_t)m * idx->ld * sizeof(float), st));
-    HIP_TRY(hipMemcpy2DAsync(c->q16, (size_t)idx->ld * sizeof(float), v, (size_t)idx->d * sizeof(float), (size_t)idx->d * sizeof(float), (size_t)m,
-                             hipMemcpyDeviceToDevice, st));
-    q = c->q16;
-  }
-  if (r.single.family == SingleRoute::F16_ONESHOT) {
-    for_f16_oneshot(r.single.geo, [&](auto ns) {
-      constexpr int NSTEP = ns(), R = f16_rows_r(NSTEP), WPB = f16_rows_wpb(NSTEP);
-      launch_record(kCombineF16Name<NSTEP>.s, n, m);
-      hipLaunchKernelGGL((combine_f16_kernel<NSTEP, R, WPB>), dim3((unsigned)((n + R * WPB - 1) / (R * WPB))), dim3(WPB * 64), 0, st, (const u32x4*)idx->rows,
-                         (const v4f*)q, w, m, op, c->scores.p, n);
-    });
-    return SVS_OK;
-  }
-  switch (r.single.geo) {
-#define SVS_ROWS_CASE(N)                                                                                                                        \
-  case N: {                                                                                                                                     \
-    constexpr int R = f32_rows_r(N), WPB = f32_rows_wpb(N);                                                                                     \
-    launch_record(kCombineF32Name<N>.s, n, m);                                                                                                  \
-    hipLaunchKernelGGL((combine_f32_kernel<N, R, WPB>), dim3((unsigned)((n + R * WPB - 1) / (R * WPB))), dim3(WPB * 64), 0, st,                 \
-                       (const v4f*)idx->rows, (const v4f*)q, w, m, op, c->scores.p, n);                                                         \
-    break;                                                                                                                                      \
-  }
-    SVS_ROWS_CASE(1) SVS_ROWS_CASE(2) SVS_ROWS_CASE(3) SVS_ROWS_CASE(4) SVS_ROWS_CASE(5) SVS_ROWS_CASE(6) SVS_ROWS_CASE(7) SVS_ROWS_CASE(8)
-    SVS_ROWS_CASE(9) SVS_ROWS_CASE(10) SVS_ROWS_CASE(11) SVS_ROWS_CASE(12) SVS_ROWS_CASE(13) SVS_ROWS_CASE(14) SVS_ROWS_CASE(15) SVS_ROWS_CASE(16)
-#undef SVS_ROWS_CASE
-    default: return fail(SVS_ERR_INVALID, "internal: no fused combine kernel for ld %d", idx->ld);
-  }
-  return SVS_OK;
-}
-
-template <int NSTEP>
-constexpr KernelName kMultiScoreF32Name = kernel_name("multi_score_f32_kernel", NSTEP, f32_rows_r(NSTEP), f32_rows_wpb(NSTEP));
-template <int NSTEP>
-constexpr KernelName kMultiScoreF16Name = kernel_name("multi_score_f16_kernel", NSTEP, f16_rows_r(NSTEP), f16_rows_wpb(NSTEP));
-template <int NSTEP, int LB, int R>
-constexpr KernelName kMultiScoreFp8Name = kernel_name("multi_score_fp8_kernel", NSTEP, LB, R, 16);
-
-// The m vectors' scores of one combined query into c->scores[j * sstride .. j * sstride + n), j < m, unmasked: the fused
-// multi-score kernel of the route (combine.h), or m passes of `single`.  v: the m vectors on the device, [m][d].
-// c->scores holds m * sstride floats.  (The staging is enqueue_combined_scores': one decision, two families of kernels.)
-int enqueue_multi_scores(const svs_index* idx, Ctx* c, const CombineRoute& r, const float* v, int m, int64_t sstride, hipStream_t st) {
-  const int64_t n = idx->n;
-  int rc;
-  if (!r.fused) {
-    for (int j = 0; j < m; ++j) {
-      launch_record("gemv", n, 1);
-      if ((rc = launch_scores(idx, c, r.single, v + (size_t)j * idx->d, c->scores + (size_t)j * sstride, st)) != SVS_OK) return rc;
+  } else {
+    // f32 / f16: the vectors as ld floats each, 16-byte aligned -- the caller's where the rows are not padded
+    const float* q = v;
+    if (query_needs_copy(idx, v)) {
+      if ((rc = c->q16.grow((size_t)GQ * idx->ld)) != SVS_OK) return rc;
+      HIP_TRY(hipMemsetAsync(c->q16, 0, (size_t)m * idx->ld * sizeof(float), st));
+      HIP_TRY(hipMemcpy2DAsync(c->q16, (size_t)idx->ld * sizeof(float), v, (size_t)idx->d * sizeof(float), (size_t)idx->d * sizeof(float), (size_t)m,
+                               hipMemcpyDeviceToDevice, st));
+      q = c->q16;
     }
-    return SVS_OK;
+    if (r.single.family == SingleRoute::F16_ONESHOT)
+      ok = for_f16_oneshot(r.single.geo, [&](auto ns) {
+        constexpr int NSTEP = ns(), R = f16_rows_r(NSTEP), WPB = f16_rows_wpb(NSTEP);
+        launch(kCombineF16Name<NSTEP>, combine_f16_kernel<NSTEP, R, WPB>, kMultiScoreF16Name<NSTEP>, multi_score_f16_kernel<NSTEP, R, WPB>, R * WPB, WPB * 64,
+               (const u32x4*)idx->rows, (const v4f*)q);
+      });
+    else
+      ok = for_f32_rows(r.single.geo, [&](auto ns) {
+        constexpr int NSTEP = ns(), R = f32_rows_r(NSTEP), WPB = f32_rows_wpb(NSTEP);
+        launch(kCombineF32Name<NSTEP>, combine_f32_kernel<NSTEP, R, WPB>, kMultiScoreF32Name<NSTEP>, multi_score_f32_kernel<NSTEP, R, WPB>, R * WPB, WPB * 64,
+               (const v4f*)idx->rows, (const v4f*)q);
+      });
   }
-  if (r.single.family == SingleRoute::FP8_ONESHOT) {
-    if ((rc = stage_queries_fp8(idx, c, v, m, m, false, st)) != SVS_OK) return rc;
-    for_fp8_oneshot(idx->ld, [&](auto ns, auto lb, auto rr) {
-      constexpr int NSTEP = ns(), LB = lb(), R = rr();
-      launch_record(kMultiScoreFp8Name<NSTEP, LB, R>.s, n, m);
-      hipLaunchKernelGGL((multi_score_fp8_kernel<NSTEP, LB, R, 16>), dim3((unsigned)((n + R * 16 - 1) / (R * 16))), dim3(16 * 64), 0, st, (const uint8_t*)idx->rows,
-                         (const float*)idx->row_scales, (const uint8_t*)c->q8.p, (const float*)c->q8s.p, m, c->scores.p, sstride, n);
-    });
-    return SVS_OK;
-  }
-  const float* q = v;
-  if (idx->ld != idx->d || (((uintptr_t)v) & 15) != 0) {
-    if ((rc = c->q16.grow((size_t)GQ * idx->ld)) != SVS_OK) return rc;
-    HIP_TRY(hipMemsetAsync(c->q16, 0, (size_t)m * idx->ld * sizeof(float), st));
-    HIP_TRY(hipMemcpy2DAsync(c->q16, (size_t)idx->ld * sizeof(float), v, (size_t)idx->d * sizeof(float), (size_t)idx->d * sizeof(float), (size_t)m,
-                             hipMemcpyDeviceToDevice, st));
-    q = c->q16;
-  }
-  if (r.single.family == SingleRoute::F16_ONESHOT) {
-    for_f16_oneshot(r.single.geo, [&](auto ns) {
-      constexpr int NSTEP = ns(), R = f16_rows_r(NSTEP), WPB = f16_rows_wpb(NSTEP);
-      launch_record(kMultiScoreF16Name<NSTEP>.s, n, m);
-      hipLaunchKernelGGL((multi_score_f16_kernel<NSTEP, R, WPB>), dim3((unsigned)((n + R * WPB - 1) / (R * WPB))), dim3(WPB * 64), 0, st, (const u32x4*)idx->rows,
-                         (const v4f*)q, m, c->scores.p, sstride, n);
-    });
-    return SVS_OK;
-  }
-  switch (r.single.geo) {
-#define SVS_ROWS_CASE(N)                                                                                                                        \
-  case N: {                                                                                                                                     \
-    constexpr int R = f32_rows_r(N), WPB = f32_rows_wpb(N);                                                                                     \
-    launch_record(kMultiScoreF32Name<N>.s, n, m);                                                                                               \
-    hipLaunchKernelGGL((multi_score_f32_kernel<N, R, WPB>), dim3((unsigned)((n + R * WPB - 1) / (R * WPB))), dim3(WPB * 64), 0, st,             \
-                       (const v4f*)idx->rows, (const v4f*)q, m, c->scores.p, sstride, n);                                                       \
-    break;                                                                                                                                      \
-  }
-    SVS_ROWS_CASE(1) SVS_ROWS_CASE(2) SVS_ROWS_CASE(3) SVS_ROWS_CASE(4) SVS_ROWS_CASE(5) SVS_ROWS_CASE(6) SVS_ROWS_CASE(7) SVS_ROWS_CASE(8)
-    SVS_ROWS_CASE(9) SVS_ROWS_CASE(10) SVS_ROWS_CASE(11) SVS_ROWS_CASE(12) SVS_ROWS_CASE(13) SVS_ROWS_CASE(14) SVS_ROWS_CASE(15) SVS_ROWS_CASE(16)
-#undef SVS_ROWS_CASE
-    default: return fail(SVS_ERR_INVALID, "internal: no fused multi-score kernel for ld %d", idx->ld);
-  }
-  return SVS_OK;
+  return ok ? SVS_OK : fail(SVS_ERR_INVALID, "internal: no fused kernel for ld %d", idx->ld);
 }
 
 // The arguments every combined entry takes, checked in the header's order; `entry` names the caller
@@ -4024,7 +3967,8 @@ int32_t svs_index_search_combined(svs_index* idx, const float* vectors, int32_t 
   // every combined query back to back: score pass(es), tombstone mask, selection -- the context's score vectors and
   // selection scratch are reused in stream order; no host wait in between
   for (int32_t q = 0; q < nq; ++q) {
-    if ((rc = enqueue_combined_scores(idx, c, route, c->q_dev + (size_t)q * m * d, c->q_dev + vn + (size_t)q * m, m, op, sstride, st)) != SVS_OK) return rc;
+    const ScoreSink fold{true, c->q_dev + vn + (size_t)q * m, op};
+    if ((rc = enqueue_vector_scores(idx, c, route, c->q_dev + (size_t)q * m * d, m, sstride, fold, st)) != SVS_OK) return rc;
     if ((rc = select_live(idx, c, count, c->out_s_pin + (size_t)q * count, c->out_r_pin + (size_t)q * count, st)) != SVS_OK) return rc;
   }
   if ((rc = fr.close("search_combined")) != SVS_OK) return rc;
@@ -4032,38 +3976,55 @@ int32_t svs_index_search_combined(svs_index* idx, const float* vectors, int32_t 
   return SVS_OK;
 }
 
-int32_t svs_internal_combined_scores(svs_index* idx, const float* vectors, int32_t m, int32_t d, const float* weights, int32_t op, int32_t route,
-                                     float* out, int64_t capacity) {
+// The two test hooks of the vector pass: one combined query on a forced route, timed (svs_internal_score_pass_ms), its
+// scores copied out -- folded under (weights, op): out[0 .. n); stored: vector j's at out[j * n ..).
+static int32_t internal_vector_scores(const char* entry, bool fold, svs_index* idx, const float* vectors, int32_t m, int32_t d, const float* weights,
+                                      int32_t op, int32_t route, float* out, int64_t capacity) {
   launch_reset();
   g_score_pass_ms = -1.0;
-  if (!idx) return fail(SVS_ERR_INVALID, "svs_internal_combined_scores: null index");
+  if (!idx) return fail(SVS_ERR_INVALID, "%s: null index", entry);
   RefGuard guard(idx);
   std::shared_lock<std::shared_mutex> geo(idx->rw);
-  int rc = check_combined_args("svs_internal_combined_scores", idx, vectors, 1, m, d, weights, op);
+  int rc = check_combined_args(entry, idx, vectors, 1, m, d, weights, op);
   if (rc != SVS_OK) return rc;
-  if (route < 0 || route > 2) return fail(SVS_ERR_INVALID, "svs_internal_combined_scores: route %d", (int)route);
+  if (route < 0 || route > 2) return fail(SVS_ERR_INVALID, "%s: route %d", entry, (int)route);
   const int64_t n = idx->n;
-  if (!out || capacity < n) return fail(SVS_ERR_INVALID, "svs_internal_combined_scores: the index holds %lld rows, the output %lld floats", (long long)n, (long long)capacity);
+  const int vectors_out = fold ? 1 : m;
+  if (!out || capacity < vectors_out * n)
+    return fail(SVS_ERR_INVALID, "%s: %d score vectors over %lld rows, the output holds %lld floats", entry, vectors_out, (long long)n, (long long)capacity);
   if (n == 0) return SVS_OK;
   const CombineRoute r = combine_route(idx, idx->variant.load(), m, route);
-  if (route == 1 && !r.has_fused) return fail(SVS_ERR_UNSUPPORTED, "svs_internal_combined_scores: rows of %d elements have no fused kernel", idx->ld);
+  if (route == 1 && !r.has_fused) return fail(SVS_ERR_UNSUPPORTED, "%s: rows of %d elements have no fused kernel", entry, idx->ld);
   HostCall fr(idx);
   if ((rc = fr.open()) != SVS_OK) return rc;
   Ctx* const c = fr.c;
   const hipStream_t st = fr.stream();
   const int64_t sstride = score_stride(n);
   const size_t vn = (size_t)m * d;
-  if ((rc = c->scores.grow((size_t)(r.fused ? 1 : m) * sstride)) != SVS_OK) return rc;
+  if ((rc = c->scores.grow((size_t)(fold && r.fused ? 1 : m) * sstride)) != SVS_OK) return rc;
   if ((rc = upload_combined(c, vectors, weights, vn, (size_t)m, st)) != SVS_OK) return rc;
   const TimedSpan t_pass(idx->timing.load() > 0);
   t_pass.begin(st);
-  if ((rc = enqueue_combined_scores(idx, c, r, c->q_dev, c->q_dev + vn, m, op, sstride, st)) != SVS_OK) return rc;
+  if ((rc = enqueue_vector_scores(idx, c, r, c->q_dev, m, sstride, fold ? ScoreSink{true, c->q_dev + vn, op} : kStoreScores, st)) != SVS_OK) return rc;
   t_pass.end(st);
-  if ((rc = fr.launched("combined_scores")) != SVS_OK) return rc;
-  HIP_TRY(hipMemcpyAsync(out, c->scores, (size_t)n * sizeof(float), hipMemcpyDeviceToHost, st));
+  if ((rc = fr.launched(entry + sizeof("svs_internal_") - 1)) != SVS_OK) return rc;   // ("combined_scores launch: ...")
+  if (fold)
+    HIP_TRY(hipMemcpyAsync(out, c->scores, (size_t)n * sizeof(float), hipMemcpyDeviceToHost, st));
+  else
+    HIP_TRY(hipMemcpy2DAsync(out, (size_t)n * sizeof(float), c->scores, (size_t)sstride * sizeof(float), (size_t)n * sizeof(float), (size_t)m,
+                             hipMemcpyDeviceToHost, st));
   if ((rc = fr.wait()) != SVS_OK) return rc;
   g_score_pass_ms = t_pass.ms();
   return SVS_OK;
+}
+
+int32_t svs_internal_combined_scores(svs_index* idx, const float* vectors, int32_t m, int32_t d, const float* weights, int32_t op, int32_t route,
+                                     float* out, int64_t capacity) {
+  return internal_vector_scores("svs_internal_combined_scores", true, idx, vectors, m, d, weights, op, route, out, capacity);
+}
+
+int32_t svs_internal_multi_scores(svs_index* idx, const float* vectors, int32_t m, int32_t d, int32_t route, float* out, int64_t capacity) {
+  return internal_vector_scores("svs_internal_multi_scores", false, idx, vectors, m, d, nullptr, SVS_COMBINE_MAX, route, out, capacity);
 }
 
 int32_t svs_internal_by_label_geometry(int32_t* out) {
@@ -4151,9 +4112,171 @@ int32_t svs_index_search_by_label(svs_index* idx, const float* queries, int32_t 
   return SVS_OK;
 }
 
-// ---- svs_index_search_collapsed (collapse.h)
+// ---- the collapse entries (collapse.h, collapse_scope.h, collapse_combine.h): what the four share --------------------
 static_assert(SVS_COLLAPSE_ZERO_IS_GROUP == CL_ZERO_IS_GROUP && SVS_COLLAPSE_ZERO_SINGLE == CL_ZERO_SINGLE, "collapse.h's kernels take the header's zero modes");
 
+// What an entry is given to write into (matched: the scoped entries'), and the one way of writing the answer when
+// nothing is in scope: no row, no group
+struct CollapseOut {
+  float* scores;
+  int64_t* rows;
+  uint32_t* values;
+  int32_t* counts;
+  int64_t* groups;
+  int64_t* matched;
+};
+
+static int32_t collapse_empty(const CollapseOut& o, int32_t nq) {
+  for (int32_t q = 0; q < nq; ++q) {
+    o.counts[q] = 0;
+    if (o.groups) o.groups[q] = 0;
+  }
+  if (o.matched) *o.matched = 0;
+  return SVS_OK;
+}
+
+// The checks the entries share, in one order (the caller has checked its queries or vectors)
+static int check_collapse_args(const char* entry, int32_t nq, int32_t k, int32_t column, int32_t zero_mode, const CollapseOut& o) {
+  const int rc = check_column(entry, column);
+  if (rc != SVS_OK) return rc;
+  if (zero_mode != SVS_COLLAPSE_ZERO_IS_GROUP && zero_mode != SVS_COLLAPSE_ZERO_SINGLE)
+    return fail(SVS_ERR_INVALID, "%s: zero_mode %d", entry, (int)zero_mode);
+  if (!o.counts) return fail(SVS_ERR_INVALID, "%s: null out_counts", entry);
+  if (k > 0 && nq > 0 && (!o.scores || !o.rows || !o.values)) return fail(SVS_ERR_INVALID, "%s: null output", entry);
+  return SVS_OK;
+}
+
+// What differs between the entries behind a query's score vector
+struct CollapseScope {
+  const char* name;            // the call in its messages
+  int64_t rows;                // what a score vector covers: the index's n rows, or the positions of c->list_dev
+  int64_t bound;               // no query has more groups: the live rows, or the rows in scope ...
+  const char* bound_what;      // ... as a message calls them
+  bool listed;                 // rows are positions in c->list_dev: selected into c->lab_pos, global rows from finish()
+  int vectors;                 // 0, or a combined query's m: cc_reduce / cc_mark_kernel, m keys per slot in c->cc_keys
+  const uint32_t* values;      // the group column over the rows (null: never set)
+  const uint32_t* dead_bits;   // the rows' tombstones (null: none among them)
+  int zero_mode;
+};
+
+// The stages behind the score pass, once for every collapse entry.  prepare() sizes the outputs, the counters and the
+// selection scratch and leaves the table EMPTY; query() enqueues one query's reduce, mark, fill, top-k stage and values;
+// finish() reads the counters back, validates and delivers.  The table, and the keys beside it, are EMPTY (all zero)
+// between queries and between calls of ANY entry on the context: cl_clean / cc_clean are false from a query's first insert
+// until the fill behind its mark kernel is enqueued, so a call that left early is repaired by the next one.  The flags
+// are written here (query(), empty()) and nowhere else.
+struct CollapseFrame {
+  svs_index* const idx;
+  Ctx* const c;
+  const int32_t nq, k;
+  const CollapseScope s;
+  const int ks;   // entries a query can have: what the top-k stage is asked for
+  const int bits;
+  const size_t tab_words, key_words;
+  const unsigned blocks;
+  const TimedSpan t_reduce, t_mark, t_clear, t_select;   // (svs_index_set_timing: around the last query's stages)
+  CollapseArgs a{};
+
+  CollapseFrame(svs_index* i, Ctx* ctx, int32_t nq_, int32_t k_, const CollapseScope& scope)
+      : idx(i), c(ctx), nq(nq_), k(k_), s(scope), ks((int)std::min<int64_t>(std::max(k_, 0), scope.bound)), bits(collapse_table_bits(scope.rows)),
+        tab_words(((size_t)1 << bits) * CL_SLOT_WORDS), key_words(((size_t)1 << bits) * (size_t)scope.vectors),
+        blocks((unsigned)std::min<int64_t>((scope.rows + CL_STRIP - 1) / CL_STRIP, CL_GRID_MAX)), t_reduce(i->timing.load() > 0), t_mark(t_reduce.on),
+        t_clear(t_reduce.on), t_select(t_reduce.on) {}
+
+  // `words` of the table and `keys` of the key array go to EMPTY behind what is enqueued
+  int empty(size_t words, size_t keys, hipStream_t st) {
+    if (words) {
+      HIP_TRY(hipMemsetAsync(c->cl_tab, 0, words * sizeof(unsigned long long), st));
+      c->cl_clean = true;
+    }
+    if (keys) {   // (the keys' layout depends on m: only an all-zero array fits every m)
+      HIP_TRY(hipMemsetAsync(c->cc_keys, 0, keys * sizeof(uint32_t), st));
+      c->cc_clean = true;
+    }
+    return SVS_OK;
+  }
+
+  int prepare(hipStream_t st) {
+    int rc;
+    const size_t on = std::max<size_t>((size_t)nq * (size_t)ks, 1);
+    if ((rc = c->out_s_pin.grow(on)) != SVS_OK || (rc = c->out_r_pin.grow(on)) != SVS_OK || (rc = c->cl_val_pin.grow(on)) != SVS_OK) return rc;
+    if (s.listed && (rc = c->lab_pos.grow(on)) != SVS_OK) return rc;
+    if ((rc = c->cl_cnt.grow((size_t)nq)) != SVS_OK || (rc = c->cl_cnt_pin.grow((size_t)nq)) != SVS_OK) return rc;
+    if (ks > 0 && select_path(s.rows, ks) == SelectPath::WINDOW && (rc = grow_select_scratch(c, 1, st)) != SVS_OK) return rc;
+    // a fresh array, or one an earlier call left early: all of it goes to empty
+    const bool fresh_tab = c->cl_tab.cap < tab_words || !c->cl_clean, fresh_keys = c->cc_keys.cap < key_words || (key_words && !c->cc_clean);
+    if (fresh_tab && ((rc = c->cl_tab.grow(tab_words)) != SVS_OK || (rc = empty(c->cl_tab.cap, 0, st)) != SVS_OK)) return rc;
+    if (fresh_keys && ((rc = c->cc_keys.grow(key_words)) != SVS_OK || (rc = empty(0, c->cc_keys.cap, st)) != SVS_OK)) return rc;
+    HIP_TRY(hipMemsetAsync(c->cl_cnt, 0, (size_t)nq * sizeof(unsigned long long), st));
+    a = CollapseArgs{s.values, s.dead_bits, c->cl_tab.p, s.rows, bits, s.zero_mode == SVS_COLLAPSE_ZERO_SINGLE ? 1 : 0};
+    return SVS_OK;
+  }
+
+  // Query q's stages over its score vector sv, in stream order behind its score pass.  g: a combined query's m score
+  // vectors (sv is the first; the mark kernel leaves the combined scores there); null: sv holds one query's scores.
+  int query(int32_t q, float* sv, int64_t sstride, const GroupCombineArgs* g, hipStream_t st) {
+    const bool last = q == nq - 1;
+    const dim3 grid(blocks), wg(CL_THREADS);
+    int rc;
+    c->cl_clean = false;
+    if (g) c->cc_clean = false;
+    if (last) t_reduce.begin(st);
+    launch_record(g ? "cc_reduce_kernel" : "collapse_reduce_kernel", s.rows, g ? g->m : 1);
+    if (g) hipLaunchKernelGGL(cc_reduce_kernel, grid, wg, 0, st, a, *g);
+    else hipLaunchKernelGGL(collapse_reduce_kernel, grid, wg, 0, st, a, (const float*)sv);
+    if (last) { t_reduce.end(st); t_mark.begin(st); }
+    launch_record(g ? "cc_mark_kernel" : "collapse_mark_kernel", s.rows, g ? g->m : 1);
+    if (g) hipLaunchKernelGGL(cc_mark_kernel, grid, wg, 0, st, a, *g, c->cl_cnt.p + q);
+    else hipLaunchKernelGGL(collapse_mark_kernel, grid, wg, 0, st, a, sv, c->cl_cnt.p + q);
+    if (last) { t_mark.end(st); t_clear.begin(st); }
+    if ((rc = empty(tab_words, g ? key_words : 0, st)) != SVS_OK) return rc;
+    if (last) t_clear.end(st);
+    if (ks == 0) return SVS_OK;
+    // the best ks survivors: rows of the index, or positions in the list
+    int64_t* const sel = (s.listed ? c->lab_pos.p : c->out_r_pin.p) + (size_t)q * ks;
+    const int64_t base = s.listed ? 0 : idx->row_offset;
+    if (last) t_select.begin(st);
+    if ((rc = run_select(idx, c, sv, s.rows, sstride, 1, ks, ks, c->out_s_pin + (size_t)q * ks, sel, st, base)) != SVS_OK) return rc;
+    if (last) t_select.end(st);
+    hipLaunchKernelGGL(collapse_values_kernel, dim3((unsigned)std::min((ks + 255) / 256, 64)), dim3(256), 0, st, (const int64_t*)sel, ks, base, s.rows,
+                       s.values, c->cl_val_pin + (size_t)q * ks);
+    return SVS_OK;
+  }
+  double select_ms() const { return ks > 0 ? t_select.ms() : -1.0; }
+
+  // The call's last wait and its trimmed results (a list's positions -> global rows on the device first)
+  int finish(HostCall& fr, const CollapseOut& o) {
+    const size_t nres = (size_t)nq * (size_t)ks;
+    if (s.listed && nres)
+      hipLaunchKernelGGL(label_map_rows_kernel, dim3((unsigned)std::min<size_t>((nres + 255) / 256, 1024)), dim3(256), 0, fr.stream(),
+                         (const int64_t*)c->lab_pos.p, (int64_t)nres, (const uint32_t*)c->list_dev.p, s.rows, idx->row_offset, c->out_r_pin.p);
+    int rc = read_back(fr, s.name, {{c->cl_cnt_pin.p, c->cl_cnt.p, (size_t)nq * sizeof(unsigned long long)}});
+    if (rc != SVS_OK) return rc;
+    std::vector<int32_t> counts((size_t)nq);
+    for (int32_t q = 0; q < nq; ++q) {
+      const unsigned long long w = c->cl_cnt_pin[q];
+      if (w > (unsigned long long)s.bound)
+        return fail(SVS_ERR_DEVICE, "%s: query %d came back with %llu groups of %lld %s", s.name, (int)q, w, (long long)s.bound, s.bound_what);
+      counts[(size_t)q] = (int32_t)std::min<unsigned long long>((unsigned long long)ks, w);
+    }
+    for (size_t i = 0; s.listed && i < nres; ++i)
+      if (c->out_r_pin[i] < 0)
+        return fail(SVS_ERR_DEVICE, "%s: result %zu of query %zu is a position outside the %lld %s", s.name, i % (size_t)ks, i / (size_t)ks,
+                    (long long)s.rows, s.bound_what);
+    if (ks > 0) {
+      deliver_strided(o.scores, k, c->out_s_pin.p, ks, nq, counts.data());
+      deliver_strided(o.rows, k, c->out_r_pin.p, ks, nq, counts.data());
+      deliver_strided(o.values, k, c->cl_val_pin.p, ks, nq, counts.data());
+    }
+    for (int32_t q = 0; q < nq; ++q) {
+      o.counts[q] = counts[(size_t)q];
+      if (o.groups) o.groups[q] = (int64_t)c->cl_cnt_pin[q];
+    }
+    return SVS_OK;
+  }
+};
+
+// ---- svs_index_search_collapsed (collapse.h)
 int32_t svs_internal_collapse_geometry(int32_t* out) {
   if (!out) return fail(SVS_ERR_INVALID, "null output");
   out[0] = CL_STRIP;
@@ -4175,89 +4298,29 @@ int32_t svs_index_search_collapsed(svs_index* idx, const float* queries, int32_t
   RefGuard guard(idx);
   std::shared_lock<std::shared_mutex> geo(idx->rw);   // (set_column, mask_rows, compact take it exclusively: every query sees one column)
   // ---- everything is validated before anything is written, allocated or launched
+  const CollapseOut o{out_scores, out_rows, out_values, out_counts, out_groups, nullptr};
   int rc = check_query_args(idx, queries, nq, d);
-  if (rc != SVS_OK || (rc = check_column("svs_index_search_collapsed", column)) != SVS_OK) return rc;
-  if (zero_mode != SVS_COLLAPSE_ZERO_IS_GROUP && zero_mode != SVS_COLLAPSE_ZERO_SINGLE)
-    return fail(SVS_ERR_INVALID, "svs_index_search_collapsed: zero_mode %d", (int)zero_mode);
-  if (!out_counts) return fail(SVS_ERR_INVALID, "null out_counts");
-  if (k > 0 && nq > 0 && (!out_scores || !out_rows || !out_values)) return fail(SVS_ERR_INVALID, "null output");
+  if (rc != SVS_OK || (rc = check_collapse_args("svs_index_search_collapsed", nq, k, column, zero_mode, o)) != SVS_OK) return rc;
   if (nq == 0) return SVS_OK;
   const int64_t n = idx->n;
-  const int64_t live = n - (int64_t)idx->dead_list.size();
-  const int ks = (int)std::min<int64_t>(std::max(k, 0), live);   // entries a query can have: what the top-k stage is asked for
-  const int bits = collapse_table_bits(n);
-  const size_t tab_words = ((size_t)1 << bits) * CL_SLOT_WORDS;
-  const unsigned blocks = (unsigned)std::min<int64_t>((n + CL_STRIP - 1) / CL_STRIP, CL_GRID_MAX);
   HostCall fr(idx);
   if ((rc = fr.open()) != SVS_OK) return rc;
   Ctx* const c = fr.c;
-  hipStream_t st = fr.stream();
-  const size_t qn = (size_t)nq * (size_t)d, on = std::max<size_t>((size_t)nq * (size_t)ks, 1);
+  const hipStream_t st = fr.stream();
   const int64_t sstride = score_stride(n);
-  if ((rc = c->out_s_pin.grow(on)) != SVS_OK || (rc = c->out_r_pin.grow(on)) != SVS_OK || (rc = c->cl_val_pin.grow(on)) != SVS_OK) return rc;
-  if ((rc = c->cl_cnt.grow((size_t)nq)) != SVS_OK || (rc = c->cl_cnt_pin.grow((size_t)nq)) != SVS_OK) return rc;
-  if ((rc = c->scores.grow((size_t)sstride)) != SVS_OK) return rc;
-  if (ks > 0 && select_path(n, ks) == SelectPath::WINDOW && (rc = grow_select_scratch(c, 1, st)) != SVS_OK) return rc;
-  if (c->cl_tab.cap < tab_words || !c->cl_clean) {   // a fresh table, or one an earlier call left early: all of it goes to empty
-    if ((rc = c->cl_tab.grow(tab_words)) != SVS_OK) return rc;
-    HIP_TRY(hipMemsetAsync(c->cl_tab, 0, c->cl_tab.cap * sizeof(unsigned long long), st));
-    c->cl_clean = true;
-  }
-  HIP_TRY(hipMemsetAsync(c->cl_cnt, 0, (size_t)nq * sizeof(unsigned long long), st));
+  CollapseFrame cf(idx, c, nq, k, {"search_collapsed", n, n - (int64_t)idx->dead_list.size(), "live rows", false, 0, idx->cols[column], dead_bits_of(idx), zero_mode});
+  if ((rc = c->scores.grow((size_t)sstride)) != SVS_OK || (rc = cf.prepare(st)) != SVS_OK) return rc;
   const SingleRoute route = single_route(idx, idx->variant.load(), false);   // the kernel svs_index_scores_n runs
-  if ((rc = upload_queries(c, queries, qn, st)) != SVS_OK) return rc;
-  const CollapseArgs a{idx->cols[column], dead_bits_of(idx), c->cl_tab.p, n, bits,
-                       zero_mode == SVS_COLLAPSE_ZERO_SINGLE ? 1 : 0};
-  const bool timed = idx->timing.load() > 0;
-  const TimedSpan t_reduce(timed), t_mark(timed), t_clear(timed), t_select(timed);
-  // every query back to back: score pass, reduce, mark, the table's fill, selection, values -- the context's one score
-  // vector, one table and selection scratch are reused in stream order; no host wait in between
-  for (int32_t q = 0; q < nq; ++q) {
-    const bool last = q == nq - 1;   // (svs_index_set_timing: spans around the last query's stages)
-    if ((rc = launch_query_scores(idx, c, route, q, st)) != SVS_OK) return rc;
-    c->cl_clean = false;
-    if (last) t_reduce.begin(st);
-    launch_record("collapse_reduce_kernel", n, 1);
-    hipLaunchKernelGGL(collapse_reduce_kernel, dim3(blocks), dim3(CL_THREADS), 0, st, a, (const float*)c->scores.p);
-    if (last) { t_reduce.end(st); t_mark.begin(st); }
-    launch_record("collapse_mark_kernel", n, 1);
-    hipLaunchKernelGGL(collapse_mark_kernel, dim3(blocks), dim3(CL_THREADS), 0, st, a, c->scores.p, c->cl_cnt.p + q);
-    if (last) { t_mark.end(st); t_clear.begin(st); }
-    HIP_TRY(hipMemsetAsync(c->cl_tab, 0, tab_words * sizeof(unsigned long long), st));
-    c->cl_clean = true;
-    if (last) t_clear.end(st);
-    if (ks == 0) continue;
-    if (last) t_select.begin(st);
-    if ((rc = run_select(idx, c, c->scores, n, sstride, 1, ks, ks, c->out_s_pin + (size_t)q * ks, c->out_r_pin + (size_t)q * ks, st,
-                         idx->row_offset)) != SVS_OK)
-      return rc;
-    if (last) t_select.end(st);
-    hipLaunchKernelGGL(collapse_values_kernel, dim3((unsigned)std::min((ks + 255) / 256, 64)), dim3(256), 0, st,
-                       (const int64_t*)(c->out_r_pin + (size_t)q * ks), ks, idx->row_offset, n, (const uint32_t*)idx->cols[column],
-                       c->cl_val_pin + (size_t)q * ks);
-  }
-  rc = read_back(fr, "search_collapsed", {{c->cl_cnt_pin.p, c->cl_cnt.p, (size_t)nq * sizeof(unsigned long long)}});
-  if (rc != SVS_OK) return rc;
-  std::vector<int32_t> counts((size_t)nq);
-  for (int32_t q = 0; q < nq; ++q) {
-    const unsigned long long w = c->cl_cnt_pin[q];
-    if (w > (unsigned long long)live)
-      return fail(SVS_ERR_DEVICE, "search_collapsed: query %d came back with %llu groups of %lld live rows", (int)q, w, (long long)live);
-    counts[(size_t)q] = (int32_t)std::min<unsigned long long>((unsigned long long)ks, w);
-  }
-  if (ks > 0) {
-    deliver_strided(out_scores, k, c->out_s_pin.p, ks, nq, counts.data());
-    deliver_strided(out_rows, k, c->out_r_pin.p, ks, nq, counts.data());
-    deliver_strided(out_values, k, c->cl_val_pin.p, ks, nq, counts.data());
-  }
-  for (int32_t q = 0; q < nq; ++q) {
-    out_counts[q] = counts[(size_t)q];
-    if (out_groups) out_groups[q] = (int64_t)c->cl_cnt_pin[q];
-  }
-  g_collapse_ms[0] = t_reduce.ms();
-  g_collapse_ms[1] = t_mark.ms();
-  g_collapse_ms[2] = t_clear.ms();
-  g_collapse_ms[3] = ks > 0 ? t_select.ms() : -1.0;
+  if ((rc = upload_queries(c, queries, (size_t)nq * (size_t)d, st)) != SVS_OK) return rc;
+  // every query back to back: score pass, then the frame's stages -- the context's one score vector, one table and
+  // selection scratch are reused in stream order; no host wait in between
+  for (int32_t q = 0; q < nq; ++q)
+    if ((rc = launch_query_scores(idx, c, route, q, st)) != SVS_OK || (rc = cf.query(q, c->scores.p, sstride, nullptr, st)) != SVS_OK) return rc;
+  if ((rc = cf.finish(fr, o)) != SVS_OK) return rc;
+  g_collapse_ms[0] = cf.t_reduce.ms();
+  g_collapse_ms[1] = cf.t_mark.ms();
+  g_collapse_ms[2] = cf.t_clear.ms();
+  g_collapse_ms[3] = cf.select_ms();
   return SVS_OK;
 }
 
@@ -4268,132 +4331,39 @@ int32_t svs_internal_collapse_scope_kernel_ms(double* out) {
   return SVS_OK;
 }
 
-// What the two entries are given to write into, and their one way of writing an empty scope's answer
-struct ScopedOut {
-  float* scores;
-  int64_t* rows;
-  uint32_t* values;
-  int32_t* counts;
-  int64_t* groups;
-  int64_t* matched;
-};
-
-static int32_t scoped_empty(const ScopedOut& o, int32_t nq) {
-  for (int32_t q = 0; q < nq; ++q) {
-    o.counts[q] = 0;
-    if (o.groups) o.groups[q] = 0;
-  }
-  if (o.matched) *o.matched = 0;
-  return SVS_OK;
-}
-
-// The checks the two entries share, in svs_index_search_collapsed's order (the caller has checked the queries)
-static int check_scoped_args(const char* entry, int32_t nq, int32_t k, int32_t column, int32_t zero_mode, const ScopedOut& o) {
-  const int rc = check_column(entry, column);
-  if (rc != SVS_OK) return rc;
-  if (zero_mode != SVS_COLLAPSE_ZERO_IS_GROUP && zero_mode != SVS_COLLAPSE_ZERO_SINGLE)
-    return fail(SVS_ERR_INVALID, "%s: zero_mode %d", entry, (int)zero_mode);
-  if (!o.counts) return fail(SVS_ERR_INVALID, "null out_counts");
-  if (k > 0 && nq > 0 && (!o.scores || !o.rows || !o.values)) return fail(SVS_ERR_INVALID, "null output");
-  return SVS_OK;
-}
-
 // What the two do once c->list_dev holds S (m >= 1 local rows, ascending) and c->sc_vals the group column beside it,
 // both enqueued on the frame's stream, with the queries uploaded: the gather kernel scores chunks of queries over the
-// list (search_list_chunked's 2 GiB rule), and every query's compact vector goes through svs_index_search_collapsed's
-// stages with positions for rows -- reduce, mark, the table's fill, the top-k stage, the values -- then positions ->
-// global rows on the device, the call's last wait, and the trimmed results.  filter_ms: what the caller's filter took.
+// list (search_list_chunked's 2 GiB rule), and every query's compact vector goes through the frame's stages with
+// positions for rows.  filter_ms: what the caller's filter took.
 static int32_t collapse_over_list(svs_index* idx, HostCall& fr, const char* entry, int32_t nq, int32_t d, int32_t k, int64_t m, int32_t zero_mode,
-                                  const ScopedOut& o, const TimedSpan& t_filter, double filter_ms) {
+                                  const CollapseOut& o, const TimedSpan& t_filter, double filter_ms) {
   Ctx* const c = fr.c;
   int rc;
-  const int ks = (int)std::min<int64_t>(std::max(k, 0), m);   // entries a query can have: what the top-k stage is asked for
   const int64_t sstride = score_stride(m);
   const int qc = (int)std::max<int64_t>(1, std::min<int64_t>(nq, ((int64_t)2 << 30) / (4 * sstride)));   // queries per gather launch
-  const int bits = collapse_table_bits(m);
-  const size_t tab_words = ((size_t)1 << bits) * CL_SLOT_WORDS;
-  const unsigned blocks = (unsigned)std::min<int64_t>((m + CL_STRIP - 1) / CL_STRIP, CL_GRID_MAX);
-  const size_t on = std::max<size_t>((size_t)nq * (size_t)ks, 1);
-  hipStream_t st = fr.stream();
-  if ((rc = c->out_s_pin.grow(on)) != SVS_OK || (rc = c->out_r_pin.grow(on)) != SVS_OK || (rc = c->cl_val_pin.grow(on)) != SVS_OK) return rc;
-  if ((rc = c->lab_pos.grow(on)) != SVS_OK) return rc;
-  if ((rc = c->cl_cnt.grow((size_t)nq)) != SVS_OK || (rc = c->cl_cnt_pin.grow((size_t)nq)) != SVS_OK) return rc;
-  if ((rc = c->scores.grow((size_t)qc * (size_t)sstride)) != SVS_OK) return rc;
-  if (ks > 0 && select_path(m, ks) == SelectPath::WINDOW && (rc = grow_select_scratch(c, 1, st)) != SVS_OK) return rc;
-  if (c->cl_tab.cap < tab_words || !c->cl_clean) {   // a fresh table, or one an earlier call of either kind left early: all of it goes to empty
-    if ((rc = c->cl_tab.grow(tab_words)) != SVS_OK) return rc;
-    HIP_TRY(hipMemsetAsync(c->cl_tab, 0, c->cl_tab.cap * sizeof(unsigned long long), st));
-    c->cl_clean = true;
-  }
-  HIP_TRY(hipMemsetAsync(c->cl_cnt, 0, (size_t)nq * sizeof(unsigned long long), st));
+  const hipStream_t st = fr.stream();
   // (no bitmap: S holds live rows only)
-  const CollapseArgs a{c->sc_vals.p, nullptr, c->cl_tab.p, m, bits, zero_mode == SVS_COLLAPSE_ZERO_SINGLE ? 1 : 0};
-  const bool timed = idx->timing.load() > 0;
-  const TimedSpan t_gather(timed), t_reduce(timed), t_mark(timed), t_clear(timed), t_select(timed);
+  CollapseFrame cf(idx, c, nq, k, {entry, m, m, "rows in scope", true, 0, c->sc_vals.p, nullptr, zero_mode});
+  if ((rc = c->scores.grow((size_t)qc * (size_t)sstride)) != SVS_OK || (rc = cf.prepare(st)) != SVS_OK) return rc;
+  const TimedSpan t_gather(idx->timing.load() > 0);
   for (int32_t q0 = 0; q0 < nq; q0 += qc) {
     const int32_t nc = std::min<int32_t>(qc, nq - q0);
-    const bool last_chunk = q0 + nc == nq;   // (svs_index_set_timing: spans around the last chunk's gather and the last query's stages)
+    const bool last_chunk = q0 + nc == nq;   // (svs_index_set_timing: a span around the last chunk's gather)
     if (last_chunk) t_gather.begin(st);
     if ((rc = launch_gather(idx, c, c->q_dev + (size_t)q0 * d, nc, c->list_dev, m, c->scores, sstride, st)) != SVS_OK) return rc;
     if (last_chunk) t_gather.end(st);
-    for (int32_t q = q0; q < q0 + nc; ++q) {
-      const bool last = q == nq - 1;
-      float* const sv = c->scores.p + (size_t)(q - q0) * (size_t)sstride;
-      c->cl_clean = false;
-      if (last) t_reduce.begin(st);
-      launch_record("collapse_reduce_kernel", m, 1);
-      hipLaunchKernelGGL(collapse_reduce_kernel, dim3(blocks), dim3(CL_THREADS), 0, st, a, (const float*)sv);
-      if (last) { t_reduce.end(st); t_mark.begin(st); }
-      launch_record("collapse_mark_kernel", m, 1);
-      hipLaunchKernelGGL(collapse_mark_kernel, dim3(blocks), dim3(CL_THREADS), 0, st, a, sv, c->cl_cnt.p + q);
-      if (last) { t_mark.end(st); t_clear.begin(st); }
-      HIP_TRY(hipMemsetAsync(c->cl_tab, 0, tab_words * sizeof(unsigned long long), st));
-      c->cl_clean = true;
-      if (last) t_clear.end(st);
-      if (ks == 0) continue;
-      if (last) t_select.begin(st);
-      if ((rc = run_select(idx, c, sv, m, sstride, 1, ks, ks, c->out_s_pin + (size_t)q * ks, c->lab_pos + (size_t)q * ks, st, 0)) != SVS_OK)
-        return rc;
-      if (last) t_select.end(st);
-      hipLaunchKernelGGL(collapse_values_kernel, dim3((unsigned)std::min((ks + 255) / 256, 64)), dim3(256), 0, st,
-                         (const int64_t*)(c->lab_pos + (size_t)q * ks), ks, (int64_t)0, m, (const uint32_t*)c->sc_vals.p,
-                         c->cl_val_pin + (size_t)q * ks);
-    }
+    for (int32_t q = q0; q < q0 + nc; ++q)
+      if ((rc = cf.query(q, c->scores.p + (size_t)(q - q0) * (size_t)sstride, sstride, nullptr, st)) != SVS_OK) return rc;
   }
-  const size_t nres = (size_t)nq * (size_t)ks;
-  if (nres)   // the positions -> global rows, on the device
-    hipLaunchKernelGGL(label_map_rows_kernel, dim3((unsigned)std::min<size_t>((nres + 255) / 256, 1024)), dim3(256), 0, st,
-                       (const int64_t*)c->lab_pos.p, (int64_t)nres, (const uint32_t*)c->list_dev.p, m, idx->row_offset, c->out_r_pin.p);
-  rc = read_back(fr, entry, {{c->cl_cnt_pin.p, c->cl_cnt.p, (size_t)nq * sizeof(unsigned long long)}});
-  if (rc != SVS_OK) return rc;
-  std::vector<int32_t> counts((size_t)nq);
-  for (int32_t q = 0; q < nq; ++q) {
-    const unsigned long long w = c->cl_cnt_pin[q];
-    if (w > (unsigned long long)m)
-      return fail(SVS_ERR_DEVICE, "%s: query %d came back with %llu groups of %lld rows in scope", entry, (int)q, w, (long long)m);
-    counts[(size_t)q] = (int32_t)std::min<unsigned long long>((unsigned long long)ks, w);
-  }
-  for (size_t i = 0; i < nres; ++i)
-    if (c->out_r_pin[i] < 0)
-      return fail(SVS_ERR_DEVICE, "%s: result %zu of query %zu is a position outside the %lld rows in scope", entry, i % (size_t)ks, i / (size_t)ks,
-                  (long long)m);
-  if (ks > 0) {
-    deliver_strided(o.scores, k, c->out_s_pin.p, ks, nq, counts.data());
-    deliver_strided(o.rows, k, c->out_r_pin.p, ks, nq, counts.data());
-    deliver_strided(o.values, k, c->cl_val_pin.p, ks, nq, counts.data());
-  }
-  for (int32_t q = 0; q < nq; ++q) {
-    o.counts[q] = counts[(size_t)q];
-    if (o.groups) o.groups[q] = (int64_t)c->cl_cnt_pin[q];
-  }
+  if ((rc = cf.finish(fr, o)) != SVS_OK) return rc;
   if (o.matched) *o.matched = m;
   const double write_ms = t_filter.ms();
   g_collapse_scope_ms[0] = filter_ms >= 0.0 && write_ms >= 0.0 ? filter_ms + write_ms : write_ms;
   g_collapse_scope_ms[1] = t_gather.ms();
-  g_collapse_scope_ms[2] = t_reduce.ms();
-  g_collapse_scope_ms[3] = t_mark.ms();
-  g_collapse_scope_ms[4] = t_clear.ms();
-  g_collapse_scope_ms[5] = ks > 0 ? t_select.ms() : -1.0;
+  g_collapse_scope_ms[2] = cf.t_reduce.ms();
+  g_collapse_scope_ms[3] = cf.t_mark.ms();
+  g_collapse_scope_ms[4] = cf.t_clear.ms();
+  g_collapse_scope_ms[5] = cf.select_ms();
   return SVS_OK;
 }
 
@@ -4407,9 +4377,9 @@ int32_t svs_index_search_collapsed_where(svs_index* idx, const float* queries, i
   RefGuard guard(idx);
   std::shared_lock<std::shared_mutex> geo(idx->rw);   // (set_column, mask_rows, compact take it exclusively: the count and the write see the same columns)
   // ---- everything is validated before anything is written, allocated or launched
-  const ScopedOut o{out_scores, out_rows, out_values, out_counts, out_groups, out_matched};
+  const CollapseOut o{out_scores, out_rows, out_values, out_counts, out_groups, out_matched};
   int rc = check_query_args(idx, queries, nq, d);
-  if (rc != SVS_OK || (rc = check_scoped_args(kEntry, nq, k, column, zero_mode, o)) != SVS_OK) return rc;
+  if (rc != SVS_OK || (rc = check_collapse_args(kEntry, nq, k, column, zero_mode, o)) != SVS_OK) return rc;
   WherePlan plan;
   if ((rc = plan.build(terms, nterms, kEntry)) != SVS_OK) return rc;
   if (nq == 0) return SVS_OK;
@@ -4433,7 +4403,7 @@ int32_t svs_index_search_collapsed_where(svs_index* idx, const float* queries, i
   if ((rc = fr.close(kEntry)) != SVS_OK) return rc;
   const int64_t m = (int64_t)c->lab_tot_pin[0];
   if (m < 0 || m > n) return fail(SVS_ERR_DEVICE, "%s: the filter counted %lld of %lld rows", kEntry, (long long)m, (long long)n);
-  if (m == 0) return scoped_empty(o, nq);
+  if (m == 0) return collapse_empty(o, nq);
   // 2. one write pass emits the list and the group column beside it
   if ((rc = c->list_dev.grow((size_t)m)) != SVS_OK || (rc = c->sc_vals.grow((size_t)score_stride(m))) != SVS_OK) return rc;
   st = fr.stream();
@@ -4457,15 +4427,15 @@ int32_t svs_index_search_collapsed_rows(svs_index* idx, const float* queries, in
   RefGuard guard(idx);
   std::shared_lock<std::shared_mutex> geo(idx->rw);   // (set_column, mask_rows, compact take it exclusively: the list and the column are one state's)
   // ---- everything is validated before anything is written, allocated or launched
-  const ScopedOut o{out_scores, out_rows, out_values, out_counts, out_groups, out_matched};
+  const CollapseOut o{out_scores, out_rows, out_values, out_counts, out_groups, out_matched};
   int rc = check_query_args(idx, queries, nq, d);
-  if (rc != SVS_OK || (rc = check_scoped_args(kEntry, nq, k, column, zero_mode, o)) != SVS_OK) return rc;
+  if (rc != SVS_OK || (rc = check_collapse_args(kEntry, nq, k, column, zero_mode, o)) != SVS_OK) return rc;
   const int64_t lo = idx->row_offset;
   bool ascending;
   if ((rc = check_row_list(rows, nrows, lo, idx->n, &ascending)) != SVS_OK) return rc;
   if (nq == 0) return SVS_OK;
   if ((rc = check_gather_rows(idx, kEntry)) != SVS_OK) return rc;
-  if (nrows == 0) return scoped_empty(o, nq);
+  if (nrows == 0) return collapse_empty(o, nq);
   HostCall fr(idx);
   if ((rc = fr.open()) != SVS_OK) return rc;
   Ctx* const c = fr.c;
@@ -4478,7 +4448,7 @@ int32_t svs_index_search_collapsed_rows(svs_index* idx, const float* queries, in
   } catch (const std::bad_alloc&) {
     return fail(SVS_ERR_NOMEM, "out of host memory for a %lld-row list", (long long)nrows);
   }
-  if (m == 0) return scoped_empty(o, nq);
+  if (m == 0) return collapse_empty(o, nq);
   if ((rc = c->list_dev.grow((size_t)m)) != SVS_OK || (rc = c->sc_vals.grow((size_t)score_stride(m))) != SVS_OK) return rc;
   const TimedSpan t_filter(idx->timing.load() > 0);
   const hipStream_t st = fr.stream();
@@ -4501,41 +4471,6 @@ int32_t svs_internal_collapsed_combined_kernel_ms(double* out) {
 
 int32_t svs_internal_score_pass_ms(double* out) { return report_ms(out, g_score_pass_ms); }
 
-int32_t svs_internal_multi_scores(svs_index* idx, const float* vectors, int32_t m, int32_t d, int32_t route, float* out, int64_t capacity) {
-  launch_reset();
-  g_score_pass_ms = -1.0;
-  if (!idx) return fail(SVS_ERR_INVALID, "svs_internal_multi_scores: null index");
-  RefGuard guard(idx);
-  std::shared_lock<std::shared_mutex> geo(idx->rw);
-  int rc = check_combined_args("svs_internal_multi_scores", idx, vectors, 1, m, d, nullptr, SVS_COMBINE_MAX);
-  if (rc != SVS_OK) return rc;
-  if (route < 0 || route > 2) return fail(SVS_ERR_INVALID, "svs_internal_multi_scores: route %d", (int)route);
-  const int64_t n = idx->n;
-  if (!out || capacity < (int64_t)m * n)
-    return fail(SVS_ERR_INVALID, "svs_internal_multi_scores: %d vectors over %lld rows, the output holds %lld floats", (int)m, (long long)n, (long long)capacity);
-  if (n == 0) return SVS_OK;
-  const CombineRoute r = combine_route(idx, idx->variant.load(), m, route);
-  if (route == 1 && !r.has_fused) return fail(SVS_ERR_UNSUPPORTED, "svs_internal_multi_scores: rows of %d elements have no fused kernel", idx->ld);
-  HostCall fr(idx);
-  if ((rc = fr.open()) != SVS_OK) return rc;
-  Ctx* const c = fr.c;
-  const hipStream_t st = fr.stream();
-  const int64_t sstride = score_stride(n);
-  const size_t vn = (size_t)m * d;
-  if ((rc = c->scores.grow((size_t)m * sstride)) != SVS_OK) return rc;
-  if ((rc = upload_combined(c, vectors, nullptr, vn, (size_t)m, st)) != SVS_OK) return rc;
-  const TimedSpan t_pass(idx->timing.load() > 0);
-  t_pass.begin(st);
-  if ((rc = enqueue_multi_scores(idx, c, r, c->q_dev, m, sstride, st)) != SVS_OK) return rc;
-  t_pass.end(st);
-  if ((rc = fr.launched("multi_scores")) != SVS_OK) return rc;
-  HIP_TRY(hipMemcpy2DAsync(out, (size_t)n * sizeof(float), c->scores, (size_t)sstride * sizeof(float), (size_t)n * sizeof(float), (size_t)m,
-                           hipMemcpyDeviceToHost, st));
-  if ((rc = fr.wait()) != SVS_OK) return rc;
-  g_score_pass_ms = t_pass.ms();
-  return SVS_OK;
-}
-
 int32_t svs_index_search_collapsed_combined(svs_index* idx, const float* vectors, int32_t nq, int32_t m, int32_t d, const float* weights, int32_t op,
                                             int32_t k, int32_t column, int32_t zero_mode, float* out_scores, int64_t* out_rows,
                                             uint32_t* out_values, int32_t* out_counts, int64_t* out_groups) {
@@ -4546,108 +4481,42 @@ int32_t svs_index_search_collapsed_combined(svs_index* idx, const float* vectors
   RefGuard guard(idx);
   std::shared_lock<std::shared_mutex> geo(idx->rw);   // (set_column, mask_rows, compact take it exclusively: every query sees one column)
   // ---- everything is validated before anything is written, allocated or launched
+  const CollapseOut o{out_scores, out_rows, out_values, out_counts, out_groups, nullptr};
   int rc = check_combined_args(kEntry, idx, vectors, nq, m, d, weights, op);
-  if (rc != SVS_OK || (rc = check_column(kEntry, column)) != SVS_OK) return rc;
-  if (zero_mode != SVS_COLLAPSE_ZERO_IS_GROUP && zero_mode != SVS_COLLAPSE_ZERO_SINGLE) return fail(SVS_ERR_INVALID, "%s: zero_mode %d", kEntry, (int)zero_mode);
-  if (!out_counts) return fail(SVS_ERR_INVALID, "%s: null out_counts", kEntry);
-  if (k > 0 && nq > 0 && (!out_scores || !out_rows || !out_values)) return fail(SVS_ERR_INVALID, "%s: null output", kEntry);
+  if (rc != SVS_OK || (rc = check_collapse_args(kEntry, nq, k, column, zero_mode, o)) != SVS_OK) return rc;
   if (nq == 0) return SVS_OK;
   const int64_t n = idx->n;
-  if (n == 0) {   // no row, no group
-    for (int32_t q = 0; q < nq; ++q) {
-      out_counts[q] = 0;
-      if (out_groups) out_groups[q] = 0;
-    }
-    return SVS_OK;
-  }
-  const int64_t live = n - (int64_t)idx->dead_list.size();
-  const int ks = (int)std::min<int64_t>(std::max(k, 0), live);   // entries a query can have: what the top-k stage is asked for
-  const int bits = collapse_table_bits(n);
-  const size_t slots = (size_t)1 << bits, tab_words = slots * CL_SLOT_WORDS, key_words = slots * (size_t)m;
-  const unsigned blocks = (unsigned)std::min<int64_t>((n + CL_STRIP - 1) / CL_STRIP, CL_GRID_MAX);
+  if (n == 0) return collapse_empty(o, nq);
   HostCall fr(idx);
   if ((rc = fr.open()) != SVS_OK) return rc;
   Ctx* const c = fr.c;
-  hipStream_t st = fr.stream();
-  const size_t vn = (size_t)nq * m * d, wn = (size_t)nq * m, on = std::max<size_t>((size_t)nq * (size_t)ks, 1);
+  const hipStream_t st = fr.stream();
+  const size_t vn = (size_t)nq * m * d, wn = (size_t)nq * m;
   const int64_t sstride = score_stride(n);
-  if ((rc = c->out_s_pin.grow(on)) != SVS_OK || (rc = c->out_r_pin.grow(on)) != SVS_OK || (rc = c->cl_val_pin.grow(on)) != SVS_OK) return rc;
-  if ((rc = c->cl_cnt.grow((size_t)nq)) != SVS_OK || (rc = c->cl_cnt_pin.grow((size_t)nq)) != SVS_OK) return rc;
-  if ((rc = c->scores.grow((size_t)m * sstride)) != SVS_OK) return rc;
-  if (ks > 0 && select_path(n, ks) == SelectPath::WINDOW && (rc = grow_select_scratch(c, 1, st)) != SVS_OK) return rc;
-  if (c->cl_tab.cap < tab_words || !c->cl_clean) {   // a fresh table, or one an earlier call left early: all of it goes to empty
-    if ((rc = c->cl_tab.grow(tab_words)) != SVS_OK) return rc;
-    HIP_TRY(hipMemsetAsync(c->cl_tab, 0, c->cl_tab.cap * sizeof(unsigned long long), st));
-    c->cl_clean = true;
-  }
-  if (c->cc_keys.cap < key_words || !c->cc_clean) {   // (the keys' layout depends on m: only an all-zero array fits every m)
-    if ((rc = c->cc_keys.grow(key_words)) != SVS_OK) return rc;
-    HIP_TRY(hipMemsetAsync(c->cc_keys, 0, c->cc_keys.cap * sizeof(uint32_t), st));
-    c->cc_clean = true;
-  }
-  HIP_TRY(hipMemsetAsync(c->cl_cnt, 0, (size_t)nq * sizeof(unsigned long long), st));
+  CollapseFrame cf(idx, c, nq, k, {"search_collapsed_combined", n, n - (int64_t)idx->dead_list.size(), "live rows", false, m, idx->cols[column], dead_bits_of(idx), zero_mode});
+  if ((rc = c->scores.grow((size_t)m * sstride)) != SVS_OK || (rc = cf.prepare(st)) != SVS_OK) return rc;
   const CombineRoute route = combine_route(idx, idx->variant.load(), m, (int)g_tune_combine_route.load());
   if ((rc = upload_combined(c, vectors, weights, vn, wn, st)) != SVS_OK) return rc;
-  const CollapseArgs a{idx->cols[column], dead_bits_of(idx), c->cl_tab.p, n, bits, zero_mode == SVS_COLLAPSE_ZERO_SINGLE ? 1 : 0};
-  const bool timed = idx->timing.load() > 0;
-  const TimedSpan t_scores(timed), t_reduce(timed), t_mark(timed), t_clear(timed), t_select(timed);
-  // every query back to back: score pass(es), reduce, mark, the fills, selection, values -- the context's score vectors,
-  // table, keys and selection scratch are reused in stream order; no host wait in between
+  const TimedSpan t_scores(idx->timing.load() > 0);
+  // every query back to back: score pass(es), then the frame's stages -- the context's score vectors, table, keys and
+  // selection scratch are reused in stream order; no host wait in between
   for (int32_t q = 0; q < nq; ++q) {
-    const bool last = q == nq - 1;   // (svs_index_set_timing: spans around the last query's stages)
+    const bool last = q == nq - 1;   // (svs_index_set_timing: a span around the last query's score pass)
     const GroupCombineArgs g{c->scores.p, sstride, c->q_dev + vn + (size_t)q * m, c->cc_keys.p, m, op};
     if (last) t_scores.begin(st);
-    if ((rc = enqueue_multi_scores(idx, c, route, c->q_dev + (size_t)q * m * d, m, sstride, st)) != SVS_OK) return rc;
+    if ((rc = enqueue_vector_scores(idx, c, route, c->q_dev + (size_t)q * m * d, m, sstride, kStoreScores, st)) != SVS_OK) return rc;
     if (last) t_scores.end(st);
-    c->cl_clean = false;
-    c->cc_clean = false;
-    if (last) t_reduce.begin(st);
-    launch_record("cc_reduce_kernel", n, m);
-    hipLaunchKernelGGL(cc_reduce_kernel, dim3(blocks), dim3(CL_THREADS), 0, st, a, g);
-    if (last) { t_reduce.end(st); t_mark.begin(st); }
-    launch_record("cc_mark_kernel", n, m);
-    hipLaunchKernelGGL(cc_mark_kernel, dim3(blocks), dim3(CL_THREADS), 0, st, a, g, c->cl_cnt.p + q);
-    if (last) { t_mark.end(st); t_clear.begin(st); }
-    HIP_TRY(hipMemsetAsync(c->cl_tab, 0, tab_words * sizeof(unsigned long long), st));
-    c->cl_clean = true;
-    HIP_TRY(hipMemsetAsync(c->cc_keys, 0, key_words * sizeof(uint32_t), st));
-    c->cc_clean = true;
-    if (last) t_clear.end(st);
-    if (ks == 0) continue;
-    if (last) t_select.begin(st);
-    if ((rc = run_select(idx, c, c->scores, n, sstride, 1, ks, ks, c->out_s_pin + (size_t)q * ks, c->out_r_pin + (size_t)q * ks, st,
-                         idx->row_offset)) != SVS_OK)
-      return rc;
-    if (last) t_select.end(st);
-    hipLaunchKernelGGL(collapse_values_kernel, dim3((unsigned)std::min((ks + 255) / 256, 64)), dim3(256), 0, st,
-                       (const int64_t*)(c->out_r_pin + (size_t)q * ks), ks, idx->row_offset, n, (const uint32_t*)idx->cols[column],
-                       c->cl_val_pin + (size_t)q * ks);
+    if ((rc = cf.query(q, c->scores.p, sstride, &g, st)) != SVS_OK) return rc;
   }
-  rc = read_back(fr, "search_collapsed_combined", {{c->cl_cnt_pin.p, c->cl_cnt.p, (size_t)nq * sizeof(unsigned long long)}});
-  if (rc != SVS_OK) return rc;
-  std::vector<int32_t> counts((size_t)nq);
-  for (int32_t q = 0; q < nq; ++q) {
-    const unsigned long long w = c->cl_cnt_pin[q];
-    if (w > (unsigned long long)live)
-      return fail(SVS_ERR_DEVICE, "search_collapsed_combined: query %d came back with %llu groups of %lld live rows", (int)q, w, (long long)live);
-    counts[(size_t)q] = (int32_t)std::min<unsigned long long>((unsigned long long)ks, w);
-  }
-  if (ks > 0) {
-    deliver_strided(out_scores, k, c->out_s_pin.p, ks, nq, counts.data());
-    deliver_strided(out_rows, k, c->out_r_pin.p, ks, nq, counts.data());
-    deliver_strided(out_values, k, c->cl_val_pin.p, ks, nq, counts.data());
-  }
-  for (int32_t q = 0; q < nq; ++q) {
-    out_counts[q] = counts[(size_t)q];
-    if (out_groups) out_groups[q] = (int64_t)c->cl_cnt_pin[q];
-  }
+  if ((rc = cf.finish(fr, o)) != SVS_OK) return rc;
   g_collapsed_combined_ms[0] = t_scores.ms();
-  g_collapsed_combined_ms[1] = t_reduce.ms();
-  g_collapsed_combined_ms[2] = t_mark.ms();
-  g_collapsed_combined_ms[3] = t_clear.ms();
-  g_collapsed_combined_ms[4] = ks > 0 ? t_select.ms() : -1.0;
+  g_collapsed_combined_ms[1] = cf.t_reduce.ms();
+  g_collapsed_combined_ms[2] = cf.t_mark.ms();
+  g_collapsed_combined_ms[3] = cf.t_clear.ms();
+  g_collapsed_combined_ms[4] = cf.select_ms();
   return SVS_OK;
 }
+
 
 static_assert(SVS_ASSIGN_MAX_VECTORS == AS_MAX_VECTORS, "the assign kernel's LDS count table holds SVS_ASSIGN_MAX_VECTORS slots");
 static_assert(SVS_ASSIGN_MAX_VECTORS == SVS_LABELS_MAX_SET, "every label an assignment writes can be named in one labelled call");

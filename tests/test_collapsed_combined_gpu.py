@@ -359,6 +359,61 @@ def test_three_queries_in_one_call_equal_three_calls(case):
             c.idx.search_batch_collapsed(c.v[:1], 10, 2, zero)                    # (the collapsed search shares the table)
 
 
+def test_all_four_entries_share_the_tables_of_one_context(gpu, data, case):
+    """One handle, one thread, so one context: group-combined with m = 8 and m = 2 (two key layouts), the collapsed
+    search (the same table, no keys), the collapsed search under a predicate and over a row list of 254 rows (a table of
+    the smallest size inside the large one), then group-combined with m = 3.  Every answer equals its model, and each
+    group-combined answer equals, byte for byte, the same call on a fresh handle over the same data: a table or a key
+    array that one entry left behind would add groups or raise maxima in the next."""
+    c = case
+    m, vec = data
+    v1 = _set(c, 1, np.arange(N) // 7 + 1)
+    v2 = _set(c, 2, np.arange(N) % 97)
+    where = [(2, "in", [5])]
+    in_scope = v2 == 5
+    rows = np.flatnonzero(in_scope)
+    assert len(rows) == 254
+    q = c.v[3:5]
+    ps, pr = c.idx.search_batch_within(q, len(rows), rows)          # the scope's truth: every row of it once, the gather kernel's bits
+    t = np.zeros((2, N), dtype=np.float32)
+    for qi in range(2):
+        assert sorted(pr[qi].tolist()) == rows.tolist()
+        t[qi, pr[qi]] = ps[qi]
+    K = 120
+
+    def combined(idx, mm, op):
+        out = idx.search_batch_collapsed_combined(c.v[None, :mm], K, 1, op, MIXED[None, :mm], SINGLE)
+        cnt = int(out[3][0])
+        _check((out[0][0, :cnt], out[1][0, :cnt], out[2][0, :cnt], int(out[4][0])),
+               collapsed_combined(c.s[:mm], MIXED[:mm], op, v1, None, True, K), (c.dtype, "shared tables", mm, op))
+        return [np.ascontiguousarray(a[0, :cnt]).tobytes() for a in out[:3]] + [out[3].tolist(), out[4].tolist()]
+
+    def scoped(out, what):
+        s, r, gv, counts, groups, matched = out
+        assert matched == 254
+        for qi in range(2):
+            es, er, ev, eg = collapse_model.collapsed(t[qi], v1, ~in_scope, True, K)
+            cnt = int(counts[qi])
+            _check((s[qi, :cnt], r[qi, :cnt], gv[qi, :cnt], int(groups[qi])), (es, er, ev, eg), (c.dtype, what, qi))
+
+    got = [combined(c.idx, 8, "sum"), combined(c.idx, 2, "min")]
+    s, r, gv, counts, groups = c.idx.search_batch_collapsed(q, K, 1, SINGLE)
+    for qi in range(2):
+        cnt = int(counts[qi])
+        _check((s[qi, :cnt], r[qi, :cnt], gv[qi, :cnt], int(groups[qi])), collapse_model.collapsed(c.s[3 + qi], v1, None, True, K),
+               (c.dtype, "collapsed", qi))
+    scoped(c.idx.search_batch_collapsed_where(q, K, where, 1, SINGLE), "where")
+    scoped(c.idx.search_batch_collapsed_within(q, K, rows, 1, SINGLE), "rows")
+    got.append(combined(c.idx, 3, "max"))
+    for (mm, op), answer in zip(((8, "sum"), (2, "min"), (3, "max")), got):
+        fresh = svs_amd.DeviceIndex(m, dtype=c.dtype)
+        try:
+            fresh.set_column(1, v1)
+            assert combined(fresh, mm, op) == answer, (c.dtype, "fresh handle", mm, op)
+        finally:
+            fresh.release()
+
+
 def test_nan_score_is_the_largest(gpu, data):
     m, vec = data
     mm = m[:9001].copy()
